@@ -1,9 +1,15 @@
 #!/usr/bin/env python
 """Headline benchmark of the hot path: mel-frames/s of Lip2Speech.inference on LRW-shaped clips.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]          (N > 1 without a launcher: bench.py starts the N ranks itself)
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]     (N > 1 without a launcher: bench.py starts the N ranks itself)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
            bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps and prints the headline line (`value`, `ms_per_step` = milliseconds per timed step).
+`--full` adds everything else below (the reference figures of the same K steps, the latency / bf16 / host-input / evaluate legs, the
+per-kernel roofline pass, the training leg and the CPU baseline).  `--dump-outputs DIR` writes what the caller of the timed path receives
+for the LAST timed step (that step's B=32 batch: DIR/mel_post.npy float32 (B, 80, S), DIR/lengths.npy float64 (B,)); the inputs are a
+pure function of the arguments, so two builds can be compared output for output.
 
 One "step" = one pass of the whole path (visual encoder -> decoder prologue -> 300 autoregressive steps ->
 post-net -> stop bookkeeping) over one synthetic batch of B=32 clips of 29 frames (BASELINE.json configs[1]).
@@ -21,7 +27,7 @@ steps as K sequential `l2s_inference` calls, `one_chain_at_a_time` the same with
 Each stream needs a hardware queue: GPU_MAX_HW_QUEUES is raised to 8 below, before the HIP runtime starts (the secondary figures
 use four chains).
 
-The JSON line also carries
+With --full the JSON line also carries
   roofline     for the kernel with the largest share of GPU time (HIP events per launch in a separate profiled pass, l2s_profile_*),
                `frac` = the FLOPs one launch executes / the duration of ONE launch alone on its stream (one event pair around a chain of
                launches, in the block form the timed region launches) / the ceiling of the pipe it runs on; `frac_overlapped` beside it =
@@ -31,12 +37,14 @@ The JSON line also carries
 """
 import argparse
 import json
+import math
 import os
 import sys
 import time
 
 os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")      # must precede the first HIP call (see the docstring)
 
+import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
@@ -112,6 +120,52 @@ def executed_flops(name, rows=B):
     return {"step_lstm_cell": 2 * rows * 2048 * (1024 + 1024) / 2}.get(name)      # both layers run K = 1024 (layer 0 on [content | prenet + a.V' | h0], option hoist_vproj = 2)
 
 
+def _u64(c):
+    """A uint64 constant as the int64 with the same bits (int64 adds and multiplies wrap like uint64 ones)."""
+    return c - (1 << 64) if c >= 1 << 63 else c
+
+
+def _srl(x, k):
+    """Logical right shift of int64 bits (torch's >> is arithmetic: clear the copied sign bits)."""
+    return (x >> k) & ((1 << (64 - k)) - 1)
+
+
+def _uniform01_on(key, n, seed, device):
+    """synth.uniform01 evaluated on `device`, bit for bit: the same splitmix64 counter hash in int64 arithmetic."""
+    base = (synth._fnv1a64(key) ^ (seed * 0x9E3779B97F4A7C15)) & 0xFFFFFFFFFFFFFFFF
+    x = torch.arange(n, dtype=torch.int64, device=device) * _u64(0xD1342543DE82EF95) + _u64(base) + _u64(0x9E3779B97F4A7C15)
+    x = (x ^ _srl(x, 30)) * _u64(0xBF58476D1CE4E5B9)
+    x = (x ^ _srl(x, 27)) * _u64(0x94D049BB133111EB)
+    x = x ^ _srl(x, 31)
+    return _srl(x, 40).to(torch.float32) * 2.0 ** -24        # 24-bit integers: exact in fp32, as numpy's float64 detour
+
+
+def synth_video_on(device, B, T, H=HW, W=HW, seed=1234, tag="video"):
+    """synth.synth_video(B, T, H, W, seed, tag), drawn on `device` and bit-identical to it: numpy takes seconds per 102.6 MB batch on the
+    host, and a run draws up to 24 distinct batches before its first step."""
+    key = f"{tag}:{B}x{T}x{H}x{W}"
+    n = B * 3 * T * H * W
+    acc = _uniform01_on(f"{key}#0", n, seed, device)
+    for j in range(1, 4):                                     # the Irwin-Hall sum of synth.pseudo_normal, same fp32 order
+        acc = acc + _uniform01_on(f"{key}#{j}", n, seed, device)
+    return ((acc - 2.0) * float(np.float32(math.sqrt(3.0)))).reshape(B, 3, T, H, W)
+
+
+def dump_outputs(path, out):
+    """--dump-outputs: what a caller of the timed path receives for one step (one B=32 batch), as .npy files (3.1 MB in all)."""
+    mel_post, lengths, _ = out
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "mel_post.npy"), mel_post.float().cpu().numpy())
+    np.save(os.path.join(path, "lengths.npy"), lengths.cpu().numpy().astype(np.float64))
+
+
+def host_threads():
+    """CPU threads this process may use: its affinity mask, capped by OMP_NUM_THREADS where the host sets it."""
+    n = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
+    cap = os.environ.get("OMP_NUM_THREADS", "")
+    return max(1, min(n, int(cap))) if cap.isdigit() and int(cap) > 0 else n
+
+
 def cpu_baseline(seconds_budget=12.0):
     """The CPU oracle on this host's cores, same B=32 / T=29 / S=300 workload, same synthetic checkpoint.
     torch's intra-op threading over-subscribes badly on the tiny per-step ops when given every hardware thread of a
@@ -121,7 +175,7 @@ def cpu_baseline(seconds_budget=12.0):
     video = synth.synth_video(B, T, tag="bench")
     emb = synth.synth_speaker_embedding(B, tag="bench")
     gum = synth.synth_gumbel(B * native.min_T(T), tag="bench")
-    hw = os.cpu_count() or 1
+    hw = host_threads()
     cands = sorted({c for c in (64, 32, 16, 8) if c <= hw} or {hw}, reverse=True)   # all 256 SMT threads: 100x slower, not probed
     probe = {}
     with torch.no_grad():
@@ -174,7 +228,7 @@ def cpu_baseline_train(Bt, St, seconds_budget=25.0):
     mels = synth.synth_mels(Bt, St, tag="train0")
     gate = torch.zeros(Bt, St)
     gate[:, -1] = 1.0
-    hw = os.cpu_count() or 1
+    hw = host_threads()
     cores = min(32, hw)
     torch.set_num_threads(cores)
     times = []
@@ -304,14 +358,16 @@ def train_main(args):
         elapsed = float(tt.item())
     loss = out["loss"].cpu()
     assert torch.isfinite(loss).all(), "non-finite loss"
-    # per-kernel HIP-event timing of ONE more step (events around every launch perturb the pipeline: separate pass); every rank takes the
-    # step (it contains the gradient all-reduce), rank 0 records it
-    if rank == 0:
-        native.profile_enable(True)
-        native.profile_reset()
-    step()
-    torch.cuda.synchronize()
-    if rank == 0:
+    # --full: per-kernel HIP-event timing of ONE more step (events around every launch perturb the pipeline: separate pass); every rank takes
+    # the step (it contains the gradient all-reduce), rank 0 records it
+    roof = cpu = None
+    if args.full:
+        if rank == 0:
+            native.profile_enable(True)
+            native.profile_reset()
+        step()
+        torch.cuda.synchronize()
+    if rank == 0 and args.full:
         prof = sorted(native.profile_read(), key=lambda r: -r[2])
         native.profile_enable(False)
         gpu_ms = sum(r[2] for r in prof)
@@ -328,6 +384,7 @@ def train_main(args):
                                  "launch (AI = 4 FLOP/B): per-launch HIP-event brackets add ~1.8 us to these us-scale kernels")
                 break
         cpu = cpu_baseline_train(Bt, St) if (world == 1 and not args.skip_cpu_baseline) else None
+    if rank == 0:
         print(json.dumps({
             "metric": "training clips/sec (forward + loss + backward + all-reduce + clip + AdamW-amsgrad + weight re-pack)",
             "value": world * Bt * args.steps / elapsed, "unit": "clips/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -366,10 +423,10 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=None, help="default: 192 inference passes (0.9 s) / 20 training steps")
     ap.add_argument("--warmup", type=int, default=None, help="default: 16 / 3")
-    ap.add_argument("--skip-cpu-baseline", action="store_true", help="for profiler runs")
+    ap.add_argument("--skip-cpu-baseline", action="store_true", help="--full: leave the CPU baseline out (profiler runs)")
     ap.add_argument("--opt", action="append", default=[], metavar="NAME=VALUE", help="run-time option of the library (include/l2s.h) set as the process "
                     "default before any model is created - A/B runs; the line records them under config.options")
-    ap.add_argument("--skip-train-leg", action="store_true", help="inference mode: leave the train_step_B8 leg out of the line (profiler runs)")
+    ap.add_argument("--skip-train-leg", action="store_true", help="--full, inference mode: leave the train_step_B8 leg out of the line (profiler runs)")
     ap.add_argument("--group", type=int, default=8, help="independent B=32 batches advanced per launch chain (l2s_inference_multi, 1..8); 1 = one batch per chain")
     ap.add_argument("--inflight", type=int, default=None, help="launch chains in flight per GPU (HIP streams + host threads); default: InflightPool.chains_for(steps, group) "
                     "- two, or three where K steps cut into fuller launches that way (20 steps: 7 + 7 + 6 instead of 4 x 5); 1 = strictly sequential chains "
@@ -378,11 +435,19 @@ def main():
                     "(option train_bf16; BASELINE.json configs[2] names bf16), fp32 accumulation / master weights / recurrent loop")
     ap.add_argument("--mode", choices=["inference", "train"], default="inference",
                     help="inference = the headline metric (default); train = one data-parallel training step per 'step' (SURVEY.md §8 config 3)")
+    ap.add_argument("--full", action="store_true", help="also every secondary figure (reference runs of the same steps, latency, bf16, host-input and "
+                    "evaluate legs, per-kernel roofline, training leg, CPU baseline); a plain run only times the K steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="inference mode: write what the last timed step returned "
+                    "(DIR/mel_post.npy float32, DIR/lengths.npy float64)")
     args = ap.parse_args()
     if args.steps is None:
         args.steps = 20 if args.mode == "train" else 192
     if args.warmup is None:
         args.warmup = 3 if args.mode == "train" else 16
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and args.mode == "train":
+        ap.error("--dump-outputs: inference mode only (the training step draws its dropout masks at random)")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return _self_launch(args)
     if args.mode == "train":
@@ -423,7 +488,7 @@ def main():
     batches = []
     for i in range(n_distinct):
         tag = f"bench{rank}.{i}" if (rank or i) else "bench"
-        batches.append((synth.synth_video(B, T, tag=tag).cuda(), synth.synth_speaker_embedding(B, tag=tag).cuda(),
+        batches.append((synth_video_on("cuda", B, T, tag=tag), synth.synth_speaker_embedding(B, tag=tag).cuda(),
                         synth.synth_gumbel(B * native.min_T(T), tag=tag).cuda()))
     video, emb, gum = batches[0]
     work = lambda n: [batches[i % n_distinct] for i in range(n)]      # noqa: E731
@@ -467,6 +532,28 @@ def main():
         extra += min(args.steps, 4 * n_distinct)
     elapsed, outs = timed(lambda: pool.map(work(args.steps), S=S))   # EXACTLY K steps
     assert all(torch.isfinite(o[0]).all() for o in outs), "non-finite mel output"
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, outs[-1])
+    value = world * B * S * args.steps / elapsed
+    line = {
+        "metric": "mel-frames/sec at LRW batch=32, 29-frame clips (Lip2Speech.inference, S=300)",
+        "value": value, "unit": "mel-frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "config": {"workload": "LRW single-word, batch=32 per step, 29x96x96 RGB mouth crops, S=300 decode steps, speaker embedding "
+                               "supplied (encoding=voice), random-init weights; every step is one full pass over one B=32 batch",
+                   "batch_per_step": B, "frames": T, "decode_steps": S, "options": list(args.opt), "library": os.path.basename(native.LIB_PATH), "parallelism": f"dp{world} (clip sharding, no collective)",
+                   "batches_per_launch_chain": G, "launch_chains_in_flight_per_gpu": NI, "distinct_batches_per_gpu": n_distinct,
+                   "collective_backend": backend, "ranks": world},
+        "warmup_extra_steps_until_steady": extra,
+    }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+        if dist:
+            dist.destroy_process_group()
+        return
+
     # reference figures, same K steps: strictly one batch at a time on one stream; and one chain of G batches at a time
     seq_elapsed, _ = timed(lambda: [nm.inference(*batches[i % n_distinct], S=S) for i in range(args.steps)])
     one_chain = InflightPool(model=nm, n_inflight=1, group=G)
@@ -649,18 +736,7 @@ def main():
         roof["path_tflops"] = per_gpu * 36.18e6 / 1e12
         roof["path_frac_fp32_peak"] = roof["path_tflops"] / FP32_MFMA_PEAK_TFLOPS      # mixed pipes (f32 trunk / first phase, split-bf16 elsewhere): a ratio to the data's dtype peak, not a pipe roofline
 
-        value = world * B * S * args.steps / elapsed
-        line = {
-            "metric": "mel-frames/sec at LRW batch=32, 29-frame clips (Lip2Speech.inference, S=300)",
-            "value": value, "unit": "mel-frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "config": {"workload": "LRW single-word, batch=32 per step, 29x96x96 RGB mouth crops, S=300 decode steps, speaker embedding "
-                                   "supplied (encoding=voice), random-init weights; every step is one full pass over one B=32 batch",
-                       "batch_per_step": B, "frames": T, "decode_steps": S, "options": list(args.opt), "library": os.path.basename(native.LIB_PATH), "parallelism": f"dp{world} (clip sharding, no collective)",
-                       "batches_per_launch_chain": G, "launch_chains_in_flight_per_gpu": NI, "distinct_batches_per_gpu": n_distinct,
-                       "collective_backend": backend, "ranks": world},
-            "warmup_extra_steps_until_steady": extra,
+        line.update({
             "latency": {"ms_one_group_alone": group_latency * 1e3, "batches_in_group": G,
                         "note": "wall time of ONE launch chain over G batches on an otherwise idle GPU: what a caller waits for its G results; "
                                 "ms_per_step above is elapsed / steps with all chains busy, a throughput figure, not a latency"},
@@ -682,7 +758,7 @@ def main():
                                            "note": "PCIe-inclusive with the data boundary on the device: every step's packed uint8 frames (25.7 MB per batch) are copied from "
                                                    "pinned host memory and normalised + padded by l2s_normalise_pad_frames one group ahead on the pool's copy stream; same grouping and chains as `value`"},
             "roofline": roof,
-        }
+        })
         if lat:
             for nb, (ms, ms_launch) in lat.items():
                 line[f"latency_B{nb}_S300"] = {"ms": ms, "value": nb * S / ms * 1e3, "unit": "mel-frames/s", "ms_launch_per_phase_loop": ms_launch,

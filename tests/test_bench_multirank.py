@@ -19,7 +19,7 @@ def _launch(extra, timeout=900):
         port = sock.getsockname()[1]
     env = dict(os.environ, L2S_BENCH_ONE_DEVICE="1", L2S_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"))
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1", "--master-port", str(port),
-           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--skip-cpu-baseline"] + extra
+           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--full", "--skip-cpu-baseline"] + extra
     r = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=timeout)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

@@ -2,14 +2,14 @@
 # Round-6 counter evidence for the block forms the timed region of bench.py really launches (three chains in flight, half-CU forms:
 # skinny_rc4h<4,2,{2,6},3>, skinny_flat<21,22,2>, step_attn<true>): rocprofv3 kernel trace + one --pmc pass per counter set over
 # tools/coresident_probe.py CHAINS=3 MODE=decode FORMS=half (three decode loops of 256 rows at once on three streams).
-# -> profiles/r06_kernel_stats.md (the default bench command), r06_overlap_stamps.txt, r06_kernel_stats_decode256_3chains.md, r06_kernel_stats_decode256_1chain.md, r06_concurrency_3chains.txt, r06_pmc_decode_half3.json, r06_pmc_step_sq_half3.txt
+# -> profiles/r06_kernel_stats.md (bench.py --full), r06_overlap_stamps.txt, r06_kernel_stats_decode256_3chains.md, r06_kernel_stats_decode256_1chain.md, r06_concurrency_3chains.txt, r06_pmc_decode_half3.json, r06_pmc_step_sq_half3.txt
 # (run on the GPU box from the repo root; everything lands under gpurun_out/prof_r6/)
 set -u
 R=$PWD; O=$R/gpurun_out/prof_r6; mkdir -p $O; cd /tmp; export TMPDIR=/tmp
 P="env CHAINS=3 MODE=decode FORMS=half REP=1 python $R/tools/coresident_probe.py 8"
 run() { timeout 400 "$@" < /dev/null > /tmp/prof.log 2>&1 || tail -3 /tmp/prof.log; }
-rm -rf /tmp/p_bench; run rocprofv3 --kernel-trace --stats -d /tmp/p_bench -o b -- python $R/bench.py --steps 64 --warmup 16 --skip-cpu-baseline --skip-train-leg
-python $R/tools/rocprof_summary.py $(find /tmp/p_bench -name "*.db" | head -1) "rocprofv3 --kernel-trace --stats -- python bench.py --steps 64 --warmup 16 --skip-cpu-baseline --skip-train-leg (round 6: 8 batches per launch chain, 3 chains in flight, B=32, T=29, S=300)" > $O/r06_kernel_stats.md
+rm -rf /tmp/p_bench; run rocprofv3 --kernel-trace --stats -d /tmp/p_bench -o b -- python $R/bench.py --full --steps 64 --warmup 16 --skip-cpu-baseline --skip-train-leg
+python $R/tools/rocprof_summary.py $(find /tmp/p_bench -name "*.db" | head -1) "rocprofv3 --kernel-trace --stats -- python bench.py --full --steps 64 --warmup 16 --skip-cpu-baseline --skip-train-leg (round 6: 8 batches per launch chain, 3 chains in flight, B=32, T=29, S=300)" > $O/r06_kernel_stats.md
 rm -rf /tmp/p3; run rocprofv3 --kernel-trace --stats -d /tmp/p3 -o t -- $P
 TR=$(find /tmp/p3 -name "*.db" | head -1)
 python $R/tools/rocprof_summary.py $TR "rocprofv3 --kernel-trace --stats -- CHAINS=3 MODE=decode FORMS=half REP=1 python tools/coresident_probe.py 8 (three decode loops at once, 256 rows each, the half-CU block forms of bench.py's timed region)" > $O/r06_kernel_stats_decode256_3chains.md
