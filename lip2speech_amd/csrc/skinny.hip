@@ -579,7 +579,7 @@ void attn_set_timeline(unsigned long long* ts) { g_attn_ts = ts; }
 
 #endif
 int launch_step_attn(const AttnP& at, const SkinnyP& pre2, int pre2_tiles, hipStream_t s, int lds_values, int skip0) {
-    L2S_REQUIRE(at.T <= ATT_MAXT && at.m <= 16, "attention sizes");
+    L2S_REQUIRE(at.T <= ATT_MAXT && at.m >= 1 && at.m <= ATT_MAXM, "attention sizes");
     L2S_REQUIRE(pre2.K <= 16 * SK_WAVES * ATT_PRE2_MAXC, "prenet layer 2 is a 256-wide layer");
     StepB sb;
     sb.at = at;

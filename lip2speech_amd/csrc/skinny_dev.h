@@ -867,6 +867,7 @@ __device__ __forceinline__ float wave_sum_f(float x) {
 }
 
 constexpr int ATT_MAXT = 320;
+constexpr int ATT_MAXM = 48;                          // content keys per clip: m = T / 7 <= 42 at T = 300 (content_block_long, attn_bwd_kernel, the alpha tape)
 constexpr int ATT_SM_FLOATS = 512 + ATT_MAXT + 16 + 16;
 constexpr int ATT_VLDS_FLOATS = 32 * 256;            // a clip's projected values V' (<= 32 frames x 256) staged through LDS (attention_block<.., VLDS>)
 
@@ -1089,9 +1090,50 @@ __device__ __forceinline__ void attention_block(const AttnP& p, int b, float* sm
     if constexpr (TIMED) { __builtin_amdgcn_s_waitcnt(0); L2S_ATT_STAMP(6); }
 }
 
+// Content.forward for clips of more than 16 content keys (T = 119..300, m = 17..42): the arithmetic of content_block below - the same fp64 dot
+// products, soft-max and t-ascending fmaf chain, so the same bits at any m - with the key rows and the values read in loops instead of held in registers
+template <bool TRAIN = false>
+__device__ __forceinline__ void content_block_long(const AttnP& p, int b, float* sm, const AttnTrain* tr) {
+    float* qs = sm;                  // 256
+    float* csc = sm + 512;           // m <= ATT_MAXM, inside the ATT_MAXT logits slot
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int m = p.m;
+    const int col = tid & 255;
+    const float qv = p.qc[(int64_t)b * p.ldqc + col];
+    const float tau_c = p.tau_c[0];
+    const float* keyb = p.ckey + (int64_t)b * m * 256 + lane * 4;
+    const float* valb = p.cval + (int64_t)b * m * 256 + col;
+    if (tid < 256) qs[tid] = qv * tau_c;
+    __syncthreads();
+    const float* q4 = qs + lane * 4;
+    for (int i = wave; i < m; i += 8) {
+        const float4 kk = *reinterpret_cast<const float4*>(keyb + (int64_t)i * 256);
+        double d = (double)q4[0] * kk.x + (double)q4[1] * kk.y + (double)q4[2] * kk.z + (double)q4[3] * kk.w;
+        d = wave_sum_d(d);
+        if (lane == 0) csc[i] = (float)d;
+    }
+    __syncthreads();
+    if (tid < 256) {
+        float cmx = -INFINITY;
+        for (int i = 0; i < m; ++i) cmx = fmaxf(cmx, csc[i]);
+        float csum = 0.f;
+        for (int i = 0; i < m; ++i) csum += expf(csc[i] - cmx);
+        float o = 0.f;
+        for (int i = 0; i < m; ++i) o = fmaf(expf(csc[i] - cmx) / csum, valb[(int64_t)i * 256], o);
+        p.cc_frag[frag16_index(b, tid, 256)] = o;
+        if constexpr (TRAIN) {
+            if (tr->cc_plain) tr->cc_plain[(int64_t)b * 256 + tid] = o;
+            if (tr->alpha && tid < m) tr->alpha[(int64_t)b * tr->ld_alpha + tid] = expf(csc[tid] - cmx) / csum;
+        }
+    }
+}
+
 // Content.forward (decoder.py:262-271) for one batch row: alpha = softmax_m(SiLU(..)*tau_c . key), cc = alpha @ value
+// (m <= 16: two key rows per wave and the values in registers; longer clips take content_block_long)
 template <bool TRAIN = false>
 __device__ __forceinline__ void content_block(const AttnP& p, int b, float* sm, const AttnTrain* tr = nullptr) {
+    if (p.m > 16) { content_block_long<TRAIN>(p, b, sm, tr); return; }
     float* qs = sm;                  // 256
     float* csc = sm + 512;           // 16
     const int tid = threadIdx.x, lane = tid & 63;

@@ -356,12 +356,12 @@ struct StepTape {
     float *h0, *h1, *c0, *c1;       // (S+1, B, 512): state before step s (s = S: final)
     float *z1, *z2, *zc, *cc, *u;   // (S, B, 256)
     float *zq, *av;                 // (S, B, 512)
-    float *alpha;                   // (S, B, 16)
+    float *alpha;                   // (S, B, ATT_MAXM)
     float *g0, *g1;                 // (S, B, 2048) gates i,f,g,o after their nonlinearities
     float *yprev;                   // (S, B, 96)  frame fed to the prenet at step s (cols 80.. zero)
 };
 static int64_t step_tape_floats(int B, int S) {
-    return (int64_t)(S + 1) * B * 512 * 4 + (int64_t)S * B * (256 * 5 + 512 * 2 + 16 + 2048 * 2 + 96) + 64 * 20;
+    return (int64_t)(S + 1) * B * 512 * 4 + (int64_t)S * B * (256 * 5 + 512 * 2 + ATT_MAXM + 2048 * 2 + 96) + 64 * 20;
 }
 static StepTape step_tape(float* base, int B, int S) {
     StepTape t;
@@ -370,7 +370,7 @@ static StepTape step_tape(float* base, int B, int S) {
     const int64_t SB = (int64_t)S * B, S1B = (int64_t)(S + 1) * B;
     t.h0 = take(S1B * 512); t.h1 = take(S1B * 512); t.c0 = take(S1B * 512); t.c1 = take(S1B * 512);
     t.z1 = take(SB * 256); t.z2 = take(SB * 256); t.zc = take(SB * 256); t.cc = take(SB * 256); t.u = take(SB * 256);
-    t.zq = take(SB * 512); t.av = take(SB * 512); t.alpha = take(SB * 16); t.g0 = take(SB * 2048); t.g1 = take(SB * 2048);
+    t.zq = take(SB * 512); t.av = take(SB * 512); t.alpha = take(SB * ATT_MAXM); t.g0 = take(SB * 2048); t.g1 = take(SB * 2048);
     t.yprev = take(SB * 96);
     return t;
 }
@@ -458,7 +458,7 @@ struct AttnBwdP {
     const float* lmask; int ld_lmask;          // dropout multiplier of the logits [b*ld + t] or null
     const float* k; const float* v;   // [B][T][512]
     const float* zq; const float* wq; const float* pos; const float* tau;
-    const float* alpha;               // [B][16]
+    const float* alpha;               // [B][ATT_MAXM]
     const float* ckey; const float* cval; const float* zc; const float* tau_c;
     float* dk; float* dv; float* dckey; float* dcval;         // accumulated over steps
     float* dzq_frag; float* dq_stack;                         // frag16 K=512; [B][512]
@@ -468,7 +468,7 @@ struct AttnBwdP {
 };
 
 __global__ __launch_bounds__(512) void attn_bwd_kernel(const AttnBwdP p) {
-    __shared__ float s_dav[512], s_a[ATT_MAXT], s_dl[ATT_MAXT], s_red[16], s_dcc[256], s_qc[256], s_dlc[16], s_al[16];
+    __shared__ float s_dav[512], s_a[ATT_MAXT], s_dl[ATT_MAXT], s_red[16], s_dcc[256], s_qc[256], s_dlc[ATT_MAXM], s_al[ATT_MAXM];
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int T = p.T, m = p.m;
     const float tau = p.tau[0], tau_c = p.tau_c[0];
@@ -564,11 +564,11 @@ __global__ __launch_bounds__(512) void attn_bwd_kernel(const AttnBwdP p) {
         const float zc = p.zc[(int64_t)b * 256 + tid];
         s_qc[tid] = zc / (1.f + expf(-zc));
     }
-    if (tid < 16) s_al[tid] = tid < m ? p.alpha[(int64_t)b * 16 + tid] : 0.f;
+    if (tid < ATT_MAXM) s_al[tid] = tid < m ? p.alpha[(int64_t)b * ATT_MAXM + tid] : 0.f;
     __syncthreads();
     const float* keyb = p.ckey + (int64_t)b * m * 256;
     const float* valb = p.cval + (int64_t)b * m * 256;
-    __shared__ float s_dal[16], s_dot[16];
+    __shared__ float s_dal[ATT_MAXM], s_dot[ATT_MAXM];
     for (int j = wave; j < m; j += 8) {                  // d alpha_j = dcc . value_j ; dot_j = qc . key_j
         float a0 = 0.f, a1 = 0.f;
 #pragma unroll
@@ -738,7 +738,7 @@ static int decode_train_fwd(l2s_model* m, float* state, int B, int T, int S, con
             at.qc = qc; at.ldqc = 256; at.ckey = state + sl.ckey; at.cval = state + sl.cval; at.tau_c = w.tau_c; at.cc_frag = cc;
             at.B = B; at.T = T; at.m = sl.m;
             if (drop.attn) { sb.att.logit_mask = drop.attn + (int64_t)i * B * T; sb.att.ld_lmask = T; }
-            sb.att.alpha = tp.alpha + (int64_t)i * B * 16; sb.att.ld_alpha = 16; sb.att.av_plain = tp.av + r512; sb.att.cc_plain = tp.cc + r256;
+            sb.att.alpha = tp.alpha + (int64_t)i * B * ATT_MAXM; sb.att.ld_alpha = ATT_MAXM; sb.att.av_plain = tp.av + r512; sb.att.cc_plain = tp.cc + r256;
             sb.pre2 = tsk(w.pre2, B);
             sb.pre2.seg[0] = {p1, 16}; sb.pre2.nseg = 1; sb.pre2.act = ACT_PSINE; sb.pre2.out = p2; sb.pre2.ldo = 256;
             if (fold) { sb.pre2.epi = SK_FRAG; sb.pre2.out = p2f; }
@@ -959,7 +959,7 @@ static int decode_train_bwd(l2s_model* m, float* state, int B, int T, int S, con
             a.dav = d0x + 1024; a.ld_dav = 1536; a.dcc = d0x; a.ld_dcc = 1536; a.logits = attn_logits + (int64_t)i * T; a.ld_logit_b = (int64_t)S * T;
             if (drop.attn) { a.lmask = drop.attn + (int64_t)i * B * T; a.ld_lmask = T; }
             a.k = state + sl.k; a.v = state + sl.v; a.zq = tp.zq + r512; a.wq = wq; a.pos = w.pos + (int64_t)i * 512; a.tau = w.tau;
-            a.alpha = tp.alpha + (int64_t)i * B * 16; a.ckey = state + sl.ckey; a.cval = state + sl.cval; a.zc = tp.zc + r256; a.tau_c = w.tau_c;
+            a.alpha = tp.alpha + (int64_t)i * B * ATT_MAXM; a.ckey = state + sl.ckey; a.cval = state + sl.cval; a.zc = tp.zc + r256; a.tau_c = w.tau_c;
             a.dk = dk; a.dv = dv; a.dckey = dckey; a.dcval = dcval; a.dzq_frag = f_dzq; a.dq_stack = st_dq + r512; a.dzc_frag = f_dzc;
             a.dqc_stack = st_dqc + r256; a.dtau_part = st_dtau + (int64_t)i * B; a.dtauc_part = st_dtauc + (int64_t)i * B;
             a.B = B; a.T = T; a.m = sl.m;
@@ -1562,6 +1562,12 @@ static int prologue_train_bwd(l2s_model* m, const float* vis, const float* emb, 
 // ================================================================================================ C ABI
 using namespace l2s;
 
+// the attention blocks of the training loop (train_step_attn_kernel, attn_bwd_kernel) hold T logits and m content weights in LDS
+static bool train_attn_sizes_ok(int T) {
+    int L[4];
+    return T >= 7 && T <= L2S_MAX_STEPS && T <= ATT_MAXT && content_lens(T, L) >= 1 && content_lens(T, L) <= ATT_MAXM;
+}
+
 extern "C" {
 
 int l2s_train_bind(l2s_model* m, const char* key, float* param_dev, float* grad_dev) {
@@ -1583,7 +1589,8 @@ int l2s_train_steps_fwd(l2s_model* m, float* state, int B, int T, int S, const f
                         const uint8_t* teacher_mask_dev, float* tape, float* mel, float* stop, float* attn_logits, const float* drop_prenet,
                         const float* drop_attn, const float* drop_rnn, void* ws, int64_t ws_bytes, void* stream) {
     L2S_REQUIRE(m && m->finalized && m->has_dec && state && tape && mel && stop && attn_logits && ws, "bad arguments");
-    L2S_REQUIRE(S >= 1 && S <= L2S_MAX_STEPS && B <= 96, "sizes");
+    L2S_REQUIRE(S >= 1 && S <= L2S_MAX_STEPS && B >= 1 && B <= 96, "sizes");
+    L2S_REQUIRE(train_attn_sizes_ok(T), "T must be in [7, 300] (m = T / 7 content keys <= ATT_MAXM)");
     L2S_REQUIRE(!teacher || (teacher_mask && teacher_mask_dev), "teacher frames need the step mask on host and device");
     return decode_train_fwd(m, state, B, T, S, teacher, teacher_mask, teacher_mask_dev, tape, mel, stop, attn_logits, StepDrop{drop_prenet, drop_attn, drop_rnn}, ws,
                             ws_bytes, (hipStream_t)stream);
@@ -1594,6 +1601,8 @@ int l2s_train_steps_bwd(l2s_model* m, float* state, int B, int T, int S, const u
                         float* de_c, const float* drop_prenet, const float* drop_attn, const float* drop_rnn, void* ws, int64_t ws_bytes, void* stream) {
     L2S_REQUIRE(m && m->finalized && m->has_dec && state && tape && attn_logits && dmel && dstop && wbuf && dk && dv && dckey && dcval && dh_init && de_c && ws,
                 "bad arguments");
+    L2S_REQUIRE(S >= 1 && S <= L2S_MAX_STEPS && B >= 1 && B <= 96, "sizes");
+    L2S_REQUIRE(train_attn_sizes_ok(T), "T must be in [7, 300] (m = T / 7 content keys <= ATT_MAXM)");
     return decode_train_bwd(m, state, B, T, S, teacher_mask, tape, attn_logits, dmel, dstop, wbuf, dk, dv, dckey, dcval, dh_init, de_c,
                             StepDrop{drop_prenet, drop_attn, drop_rnn}, ws, ws_bytes, (hipStream_t)stream);
 }

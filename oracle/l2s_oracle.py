@@ -261,13 +261,15 @@ def decoder_prologue(sd: SD, vis: torch.Tensor, emb: torch.Tensor, gumbel: torch
 
 
 def decode_loop(sd: SD, st: dict, S: int, p: str = "decoder.", teacher: Optional[torch.Tensor] = None,
-                teacher_mask: Optional[torch.Tensor] = None, return_logits: bool = False, drop: Optional[dict] = None):
+                teacher_mask: Optional[torch.Tensor] = None, return_logits: bool = False, drop: Optional[dict] = None,
+                alphas: Optional[list] = None):
     """decoder.py:412-429 (inference) / 353-375 (forward).  ``teacher`` (B,S,80) with boolean ``teacher_mask`` (S,)
     substitutes the previous frame at the marked steps (scheduled sampling made explicit).  ``drop`` holds the train-mode dropout
     multipliers (0 or 1/(1-p)) as explicit tensors: 'prenet' (S,B,256) nn.Dropout(0.2) :308, 'attn' (S,B,T) F.dropout(logits, 0.1) :363
     (the returned logits are the dropped ones, as the reference appends after the dropout), 'rnn' (S,B,512) nn.LSTM(dropout=0.1) :312
     between the two layers.  Returns
-    mel (B,S,80), stop logits (B,S), attention (B,S,T) (post-softmax, or tau*q.k logits if return_logits)."""
+    mel (B,S,80), stop logits (B,S), attention (B,S,T) (post-softmax, or tau*q.k logits if return_logits).  ``alphas``: a list that receives
+    the content-attention weights of every step, (B,m) each."""
     k, v, key, value = st["k"], st["v"], st["key"], st["value"]
     h0, h1 = st["hidden"][0], st["hidden"][1]
     B = h0.shape[0]
@@ -295,6 +297,8 @@ def decode_loop(sd: SD, st: dict, S: int, p: str = "decoder.", teacher: Optional
         u = pr + o
         qc = silu(linear(torch.cat([c0, c1], dim=1), sd, p + "content.Q.0"))
         al = torch.softmax(torch.bmm((qc * tau_c).unsqueeze(1), key).squeeze(1), dim=-1)
+        if alphas is not None:
+            alphas.append(al)
         cc = torch.bmm(al.unsqueeze(1), value).squeeze(1)
         h0, c0 = lstm_cell(torch.cat([cc, u], dim=1), h0, c0,
                            sd[p + "decoder_rnn.weight_ih_l0"], sd[p + "decoder_rnn.weight_hh_l0"],
