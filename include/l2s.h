@@ -133,6 +133,16 @@ int64_t l2s_speaker_workspace_bytes(int B, int n_samples);
 int l2s_speaker_encoder_fwd(l2s_model* m, const float* audio, int B, int n_samples, float* emb,
                             void* ws, int64_t ws_bytes, void* stream);
 
+/* face speaker tower: FaceRecognizer (reference vgg_face.py:28-60), facenet_pytorch's InceptionResnetV1 (casia-webface) in eval mode + projection.
+ * Needs a model holding the vgg_face.* keys (resnet.* without logits.*, projection_layer.*).  H = W = 160 only (the reference's loaders resize faces
+ * to 160); other sizes return an error (the workspace query returns -1).  Runs fp32-exact on the split-bf16 matrix path under every option
+ * ("infer_bf16" does not apply to the tower).  A face's outputs have the same bits whatever else is in the batch.
+ * faces dev: image b at faces + b*batch_stride floats, (3,H,W) contiguous (the strided face_frames[:, 0] view works as it is)
+ * -> proj dev (B,256) the pre-ReLU projection (forward's output; may be NULL), emb dev (B,256) = normalize(relu(proj)) (inference's output) */
+int64_t l2s_face_workspace_bytes(int B, int H, int W);
+int l2s_face_encoder_fwd(l2s_model* m, const float* faces, int64_t batch_stride, int B, int H, int W,
+                         float* proj, float* emb, void* ws, int64_t ws_bytes, void* stream);
+
 /* ---- vocoder + metric of evaluate.py -------------------------------------------------------------
  * The reference vocodes the predicted mels with torchaudio 0.9.0 (datasets/spectograms.py:76-95: exp -> InverseMelScale ->
  * GriffinLim, 256 iterations each) and scores them with pystoi 0.3.3 (evaluate.py:41-45: stoi(gt, pred, fs, extended=True)).

@@ -67,6 +67,15 @@ int l2s_op_conv1d_bwd(const float* dZ, const float* X, const float* Wp, float* d
 /* fused Conv3d(3->24,5x7x7,s(1,2,2),p(2,3,3)) + BN + PReLU + MaxPool(1,3,3)/s(1,2,2)/p(0,1,1) of the model:
  * video dev (B,3,T,H,W) -> out dev (B*T, H/4, W/4, 24) channel-last */
 int l2s_op_frontend(l2s_model* m, const float* video, int B, int T, int H, int W, float* out, void* stream);
+/* one Conv2d of the face tower's implicit-GEMM kernel (face_tower.hip, split-K by the same per-image rule as the tower):
+ * x dev NHWC (B,H,W,Cin) when x_bstride == 0, else the NCHW view image b at x + b*x_bstride, (Cin,H,W) contiguous; w dev [Cout][kh][kw][Cin];
+ * y dev NHWC (B,Ho,Wo,Cout) = act((conv * scale[n] + shift[n]) + res), res NHWC like y or NULL, act = ReLU if relu */
+int l2s_op_face_conv2d(const float* x, int64_t x_bstride, int B, int H, int W, int Cin, const float* w, const float* scale, const float* shift,
+                       const float* res, int relu, float* y, int Cout, int kh, int kw, int stride, int ph, int pw, void* stream);
+/* l2s_face_encoder_fwd plus stage taps: taps = 8 dev pointers (each may be NULL) receiving, channel-last, conv2d_4b and repeat_1 (B,17,17,256),
+ * mixed_6a and repeat_2 (B,8,8,896), mixed_7a and block8 (B,3,3,1792), the pooled features (B,1792) and last_bn's output (B,512) */
+int l2s_op_face_taps(l2s_model* m, const float* faces, int64_t batch_stride, int B, float* const* taps, float* proj, float* emb, void* ws,
+                     int64_t ws_bytes, void* stream);
 /* average duration (us) of the decoder LSTM-cell kernel over a chain of n_pairs x {layer 0, layer 1} launches bracketed by ONE pair
  * of HIP events on `stream` (bench.py's roofline figure; synchronises) */
 int l2s_op_lstm_cell_chain(l2s_model* m, int B, int n_pairs, void* ws, int64_t ws_bytes, void* stream, double* avg_us);

@@ -1,7 +1,7 @@
 """The model-facing halves of the reference's caller loops, without their I/O:
 
-  * ``demo_clips`` / ``demo_clip`` - demo.py:60-90: per clip, speaker embedding from the VOICE tower (``--encoding voice``) or a
-                         supplied one, ``net.inference(..., return_attention_map=True)``, truncate to ``output_lengths[0]``.
+  * ``demo_clips`` / ``demo_clip`` - demo.py:60-90: per clip, speaker embedding from the VOICE tower (``--encoding voice``), a
+                         supplied one or the model's FACE tower (``encoding="face"``, ``--encoding face``), ``net.inference(..., return_attention_map=True)``, truncate to ``output_lengths[0]``.
   * ``evaluate_mels`` / ``evaluate_net`` - evaluate.py:22-51: ``net(..., tf_ratio=1)[1]`` in eval mode over collated batches.
   * ``train_iterations`` - train.py:150-193.
 
@@ -21,15 +21,18 @@ import torch
 from . import native
 
 
-def demo_clip(net, batch, speaker_encoder=None, speaker_embedding: Optional[torch.Tensor] = None, device="cuda"):
+def demo_clip(net, batch, speaker_encoder=None, speaker_embedding: Optional[torch.Tensor] = None, device="cuda", encoding: str = "voice"):
     """``batch`` = one item of ``DataLoader(ds, batch_size=1, collate_fn=test_collate_fn_pad)`` (one iteration of demo.py:60-90): the direct
     ``net.inference`` call, which for one clip takes the library's latency form (the decode loop as one persistent launch, option "persist_decode") -
-    a single clip has no grouping to stay consistent with; ``demo_clips`` streams a whole loader through the grouped path instead."""
-    if speaker_embedding is None and speaker_encoder is None:
+    a single clip has no grouping to stay consistent with; ``demo_clips`` streams a whole loader through the grouped path instead.
+    ``encoding="face"`` (demo.py ``--encoding face``): no embedding is passed, the model takes it from its face tower (``net.vgg_face``)."""
+    _check_encoding(encoding)
+    if encoding == "voice" and speaker_embedding is None and speaker_encoder is None:
         raise ValueError("pass a SpeakerEncoder (voice route) or a speaker_embedding")
     (videos, _), (audios, _), _, face_crops, _ = batch
     with torch.no_grad():
-        emb = speaker_embedding if speaker_embedding is not None else speaker_encoder.inference(audios.to(device, non_blocking=True))
+        emb = _voice_embedding(encoding, speaker_encoder, speaker_embedding, audios, device)
+        face_crops = face_crops.to(device, non_blocking=True) if encoding == "face" else face_crops
         mel, lengths, attn = net.inference(videos.to(device, non_blocking=True), face_crops, speaker_embedding=emb, return_attention_map=True)
     n = int(lengths[0])                                  # synchronises: a timed-out persistent launch is reported here, not handed on as NaN
     native.check_persist_timeouts()
@@ -37,17 +40,19 @@ def demo_clip(net, batch, speaker_encoder=None, speaker_embedding: Optional[torc
 
 
 def demo_clips(net, batches: Iterable, speaker_encoder=None, speaker_embedding: Optional[torch.Tensor] = None, device="cuda",
-               group: int = 8, n_inflight: int = 3):
+               group: int = 8, n_inflight: int = 3, encoding: str = "voice"):
     """demo.py:60-90 over a whole loader: per clip the speaker embedding from the VOICE tower (``--encoding voice``) or a supplied one,
     ``net.inference(..., return_attention_map=True)``, truncation to ``output_lengths[0]``.  The clips are advanced ``group`` per launch
-    chain with ``n_inflight`` chains on the GPU (``Lip2Speech.inference_many``); yields ``(mel, lengths, attention)`` per clip, in order."""
-    if speaker_embedding is None and speaker_encoder is None:
+    chain with ``n_inflight`` chains on the GPU (``Lip2Speech.inference_many``); yields ``(mel, lengths, attention)`` per clip, in order.
+    ``encoding="face"``: the embedding comes from the model's face tower instead."""
+    _check_encoding(encoding)
+    if encoding == "voice" and speaker_embedding is None and speaker_encoder is None:
         raise ValueError("pass a SpeakerEncoder (voice route) or a speaker_embedding")
 
     def calls():
         for (videos, _), (audios, _), _, face_crops, _ in batches:
             with torch.no_grad():
-                emb = speaker_embedding if speaker_embedding is not None else speaker_encoder.inference(audios.to(device, non_blocking=True))
+                emb = _voice_embedding(encoding, speaker_encoder, speaker_embedding, audios, device)
             yield videos, face_crops, emb, True
 
     for mel, lengths, attn in net.inference_many(calls(), group=group, n_inflight=n_inflight):
@@ -55,7 +60,21 @@ def demo_clips(net, batches: Iterable, speaker_encoder=None, speaker_embedding: 
         yield mel[:1, :, :n], lengths, attn[:, :n]
 
 
-def _evaluate_outputs(net, batches: Iterable, speaker_encoder, device, group: int, n_inflight: int):
+def _check_encoding(encoding: str) -> None:
+    if encoding not in ("voice", "face"):
+        raise ValueError(f"encoding must be 'voice' or 'face' (demo.py --encoding), got {encoding!r}")
+
+
+def _voice_embedding(encoding, speaker_encoder, speaker_embedding, audios, device):
+    """The embedding a caller passes on: none on the face route (the model's face tower computes it), else the supplied one or the voice tower's."""
+    if encoding == "face":
+        return None
+    if speaker_embedding is not None:
+        return speaker_embedding
+    return speaker_encoder.inference(audios.to(device, non_blocking=True)) if speaker_encoder is not None else None
+
+
+def _evaluate_outputs(net, batches: Iterable, speaker_encoder, device, group: int, n_inflight: int, encoding: str = "voice"):
     """The eval-mode ``net(..., tf_ratio=1)`` of evaluate.py:32-38 for every collated batch (``train_collate_fn_pad`` layout), on the grouped
     path: yields ``(batch, outputs)`` in loader order."""
     kept = []
@@ -65,31 +84,34 @@ def _evaluate_outputs(net, batches: Iterable, speaker_encoder, device, group: in
             (videos, vlen), (audios, alen), (melspecs, mlen, _gate), face_crops = batch
             kept.append(batch)
             with torch.no_grad():
-                emb = speaker_encoder.inference(audios.to(device, non_blocking=True)) if speaker_encoder is not None else None
+                emb = _voice_embedding(encoding, speaker_encoder, None, audios, device)
             yield videos, face_crops, audios, melspecs, vlen, alen, mlen, 1, {"speaker_embedding": emb}
 
     for out in net.forward_many(calls(), group=group, n_inflight=n_inflight):
         yield kept.pop(0), out
 
 
-def evaluate_mels(net, batches: Iterable, speaker_encoder=None, device="cuda", group: int = 8, n_inflight: int = 3) -> List[torch.Tensor]:
+def evaluate_mels(net, batches: Iterable, speaker_encoder=None, device="cuda", group: int = 8, n_inflight: int = 3,
+                  encoding: str = "voice") -> List[torch.Tensor]:
     """Post-net mels of ``net(..., tf_ratio=1)[1]`` for every collated batch (``train_collate_fn_pad`` layout; evaluate.py:32-38), ``group``
     loader batches per launch chain (``l2s_forward_eval_multi``), ``n_inflight`` chains in flight."""
     was_training = net.training
     net.eval()
     try:
-        return [out[1] for _, out in _evaluate_outputs(net, batches, speaker_encoder, device, group, n_inflight)]
+        return [out[1] for _, out in _evaluate_outputs(net, batches, speaker_encoder, device, group, n_inflight, encoding)]
     finally:
         net.train(was_training)
 
 
 def evaluate_net(net, batches: Iterable, speaker_encoder=None, device="cuda", max_iters: int = 256, sampling_rate: int = None,
-                 group: int = 8, n_inflight: int = 3, timings: Optional[dict] = None, vocoder_backend: str = "auto", metric: str = "auto") -> float:
+                 group: int = 8, n_inflight: int = 3, timings: Optional[dict] = None, vocoder_backend: str = "auto", metric: str = "auto",
+                 encoding: str = "voice") -> float:
     """Mean ESTOI of the vocoded predictions against the ground-truth audio (reference: evaluate.py:22-51): `net(..., tf_ratio=1)[1]`
     -> `MelSpec2Audio` (InverseMelScale + Griffin-Lim, `max_iters` each) -> `stoi(gt, pred, fs, extended=True)` per clip.  Vocoder and
     metric are restatements of third-party algorithms (parity unpinned); the mels come from the HIP path, `group` loader batches per launch
     chain, and the next groups' chains run while this thread vocodes and scores.  `timings` (a dict) receives the wall seconds spent waiting
-    for the model, in the vocoder and in the metric."""
+    for the model, in the vocoder and in the metric.  `encoding="face"`: the speaker embedding comes from the model's face tower."""
+    _check_encoding(encoding)
     import time
     from .datasets.spectrograms import MelSpec2Audio
     from .hparams import create_hparams
@@ -143,7 +165,7 @@ def evaluate_net(net, batches: Iterable, speaker_encoder=None, device="cuda", ma
         with torch.no_grad():
             t0 = time.perf_counter()
             pending = []
-            for batch, out in _evaluate_outputs(net, batches, speaker_encoder, device, group, n_inflight):
+            for batch, out in _evaluate_outputs(net, batches, speaker_encoder, device, group, n_inflight, encoding):
                 mel = out[1]
                 if pending and (len(pending) == max(1, group) or pending[0][1].shape[1:] != mel.shape[1:]):
                     t["model_wait_s"] += time.perf_counter() - t0
@@ -174,12 +196,15 @@ def reconstruction_losses(outputs, targets) -> dict:
 
 
 def train_iterations(net, batches: List, n_iters: int, speaker_encoder=None, tf_ratio: float = 0.0, lr: float = 1e-4, weight_decay: float = 1e-6,
-                     grad_clip: float = 1.0, fused_optimizer: bool = True, device="cuda", bf16: bool = False) -> List[dict]:
+                     grad_clip: float = 1.0, fused_optimizer: bool = True, device="cuda", bf16: bool = False,
+                     encoding: str = "voice") -> List[dict]:
     """The model-facing half of `train.py`'s loop (train.py:102-104,150-193): `net.train()`; cycle through the collated batches
     (`tf_ratio += 0.1` every 10 epochs); forward -> 4-term loss -> `backward()` -> gradient all-reduce when a process group is up
     (one process per GPU) -> clip at `grad_clip` -> AdamW(amsgrad) on the decoder and encoder groups.  Returns the per-iteration loss
     log (python floats; the `.item()` calls are this loop's only host synchronisations, like the reference's `loss_log`).
-    `bf16=True`: the training entry points run their GEMMs with bf16 operands (option "train_bf16", include/l2s.h)."""
+    `bf16=True`: the training entry points run their GEMMs with bf16 operands (option "train_bf16", include/l2s.h).  `encoding="face"`: the
+    speaker embedding comes from the model's face tower (train.py's own call passes none); it is a constant of the step, as in the reference."""
+    _check_encoding(encoding)
     from .losses import Loss
     from .training import AdamWAmsgrad, GradAllReducer
     net.train()
@@ -206,7 +231,7 @@ def train_iterations(net, batches: List, n_iters: int, speaker_encoder=None, tf_
                 tf_ratio += 0.1
         (videos, vlen), (audios, alen), (melspecs, mlen, gates), face_crops = batches[pos]
         pos += 1
-        emb = speaker_encoder.inference(audios.to(device)) if speaker_encoder is not None else None
+        emb = _voice_embedding(encoding, speaker_encoder, None, audios, device)
         outputs = net(videos.to(device), face_crops.to(device) if face_crops is not None else None, audios.to(device), melspecs.to(device), vlen, alen,
                       mlen, tf_ratio, speaker_embedding=emb)
         losses = reconstruction_criterion(outputs, (melspecs.to(device), gates.to(device)), dict())

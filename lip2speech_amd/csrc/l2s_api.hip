@@ -197,7 +197,7 @@ static int lstm_perm_row(int np, int H) {      // packed row (unit-major: 4*unit
 }
 
 
-static int pack_host(l2s_model* m, Packer& P, bool& want_enc, bool& want_dec, bool& want_spk) {
+static int pack_host(l2s_model* m, Packer& P, bool& want_enc, bool& want_dec, bool& want_spk, bool& want_face) {
     m->w = Weights{};
     Weights& w = m->w;
     const std::string E = "encoder.", Dk = "decoder.";
@@ -208,8 +208,12 @@ static int pack_host(l2s_model* m, Packer& P, bool& want_enc, bool& want_dec, bo
         return false;
     };
     const std::string Sk = "speaker_encoder.";
-    want_enc = has_prefix(E); want_dec = has_prefix(Dk); want_spk = has_prefix(Sk);
-    if (!want_enc && !want_dec && !want_spk) { set_error("l2s_model_finalize: no encoder.* / decoder.* / speaker_encoder.* tensors were set"); return 1; }
+    const std::string Fk = "vgg_face.";
+    want_enc = has_prefix(E); want_dec = has_prefix(Dk); want_spk = has_prefix(Sk); want_face = has_prefix(Fk);
+    if (!want_enc && !want_dec && !want_spk && !want_face) {
+        set_error("l2s_model_finalize: no encoder.* / decoder.* / speaker_encoder.* / vgg_face.* tensors were set");
+        return 1;
+    }
     if (want_enc) {
 
     // ---- frontend: Conv3d (24,3,5,7,7) -> [slab = ci*5+kt][50][32]
@@ -577,6 +581,79 @@ static int pack_host(l2s_model* m, Packer& P, bool& want_enc, bool& want_dec, bo
         P.copy(Sk + "linear.weight", (int64_t)256 * 256, &w.spk_linear.W);
         P.copy(Sk + "linear.bias", 256, &w.spk_linear.shift);
     }   // want_spk
+    if (want_face) {
+        // face tower (vgg_face.py:28-60; face_tower.hip): every convolution of the layer table re-laid as [Cout][kh][kw][Cin] (fused heads: the
+        // parts' rows one after the other), BasicConv2d's BatchNorm (eps 1e-3) folded into scale / shift, the blocks' up-projections as
+        // scale = block scale, shift = bias * scale; resnet.logits is held by the caller and not packed
+        const auto& layers = face_layers();
+        if ((int)layers.size() != FACE_N_CONVS) { set_error("l2s_model_finalize: face layer table has " + std::to_string(layers.size()) + " entries"); return 1; }
+        for (int li = 0; li < FACE_N_CONVS; ++li) {
+            const FaceLayer& L = layers[li];
+            const int np = (int)L.parts.size(), N = L.cout * np, taps = L.kh * L.kw, K = taps * L.cin;
+            const int64_t wn = (int64_t)L.cout * K;
+            std::vector<const std::vector<float>*> wt(np), g(np), b(np), mu(np), var(np);
+            bool ok = true;
+            for (int j = 0; j < np; ++j) {
+                const std::string pre = Fk + L.parts[j];
+                if (L.res_scale == 0.f) {
+                    wt[j] = P.get(pre + ".conv.weight", wn);
+                    g[j] = P.get(pre + ".bn.weight", L.cout); b[j] = P.get(pre + ".bn.bias", L.cout);
+                    mu[j] = P.get(pre + ".bn.running_mean", L.cout); var[j] = P.get(pre + ".bn.running_var", L.cout);
+                    ok = ok && wt[j] && g[j] && b[j] && mu[j] && var[j];
+                } else {
+                    wt[j] = P.get(pre + ".weight", wn); b[j] = P.get(pre + ".bias", L.cout);
+                    ok = ok && wt[j] && b[j];
+                }
+            }
+            if (!ok) continue;
+            const int64_t wo = P.blob.alloc((int64_t)N * K), so = P.blob.alloc(N), ho = P.blob.alloc(N);
+            for (int j = 0; j < np; ++j) {
+                const std::vector<float>& v = *wt[j];
+                for (int n = 0; n < L.cout; ++n) {
+                    const int64_t row = wo + (int64_t)(j * L.cout + n) * K;
+                    for (int ci = 0; ci < L.cin; ++ci)
+                        for (int t = 0; t < taps; ++t) P.blob.data[row + (int64_t)t * L.cin + ci] = v[((int64_t)n * L.cin + ci) * taps + t];
+                    float sc, sh;
+                    if (L.res_scale == 0.f) {
+                        sc = (*g[j])[n] / std::sqrt((*var[j])[n] + FACE_BN_EPS);
+                        sh = (*b[j])[n] - (*mu[j])[n] * sc;
+                    } else {
+                        sc = L.res_scale;
+                        sh = (*b[j])[n] * L.res_scale;
+                    }
+                    P.blob.data[so + j * L.cout + n] = sc;
+                    P.blob.data[ho + j * L.cout + n] = sh;
+                }
+            }
+            P.bind(&w.face.convs[li].w, wo); P.bind(&w.face.convs[li].scale, so); P.bind(&w.face.convs[li].shift, ho);
+        }
+        auto transposed = [&](const std::string& key, int out, int in, const float** slot) {      // nn.Linear weight (out, in) -> [in][out]
+            auto v = P.get(key, (int64_t)out * in);
+            if (!v) return;
+            const int64_t o = P.blob.alloc((int64_t)out * in);
+            for (int r = 0; r < out; ++r)
+                for (int c = 0; c < in; ++c) P.blob.data[o + (int64_t)c * out + r] = (*v)[(int64_t)r * in + c];
+            P.bind(slot, o);
+        };
+        transposed(Fk + "resnet.last_linear.weight", 512, 1792, &w.face.tail.llT);
+        {
+            const std::string pre = Fk + "resnet.last_bn.";
+            auto g = P.get(pre + "weight", 512), b = P.get(pre + "bias", 512), mu = P.get(pre + "running_mean", 512), var = P.get(pre + "running_var", 512);
+            if (g && b && mu && var) {
+                const int64_t so = P.blob.alloc(512), ho = P.blob.alloc(512);
+                for (int i = 0; i < 512; ++i) {
+                    const float sc = (*g)[i] / std::sqrt((*var)[i] + FACE_BN_EPS);
+                    P.blob.data[so + i] = sc;
+                    P.blob.data[ho + i] = (*b)[i] - (*mu)[i] * sc;
+                }
+                P.bind(&w.face.tail.bn_s, so); P.bind(&w.face.tail.bn_h, ho);
+            }
+        }
+        transposed(Fk + "projection_layer.0.weight", 512, 512, &w.face.tail.p0T);
+        P.copy(Fk + "projection_layer.0.bias", 512, &w.face.tail.p0b);
+        transposed(Fk + "projection_layer.2.weight", 256, 512, &w.face.tail.p2T);
+        P.copy(Fk + "projection_layer.2.bias", 256, &w.face.tail.p2b);
+    }   // want_face
     if (!P.missing.empty()) { set_error("l2s_model_finalize: " + P.missing); return 1; }
     return 0;
 }
@@ -665,8 +742,8 @@ static int derive_unit_planes(l2s_model* m, hipStream_t s) {
 
 static int pack_model(l2s_model* m, hipStream_t stream) {
     Packer P{m};
-    bool want_enc = false, want_dec = false, want_spk = false;
-    if (pack_host(m, P, want_enc, want_dec, want_spk)) return 1;
+    bool want_enc = false, want_dec = false, want_spk = false, want_face = false;
+    if (pack_host(m, P, want_enc, want_dec, want_spk, want_face)) return 1;
     if (m->opt.refresh_map && build_refresh_map(m, P, stream)) return 1;
     m->folded_valid = true; m->planes_valid = true;
 
@@ -683,6 +760,7 @@ static int pack_model(l2s_model* m, hipStream_t stream) {
     m->has_enc = want_enc;
     m->has_dec = want_dec;
     m->has_spk = want_spk;
+    m->has_face = want_face;
     if (m->lstm_planes) { (void)hipFree(m->lstm_planes); m->lstm_planes = nullptr; }
     if (derive_lstm_planes(m, stream)) return 1;
     if (m->gemm_planes) { (void)hipFree(m->gemm_planes); m->gemm_planes = nullptr; }
@@ -713,8 +791,8 @@ static int build_refresh_map(l2s_model* m, const Packer& P, hipStream_t stream) 
     Weights saved = m->w;
     m->host.swap(shadow);
     Packer P2{m};
-    bool e = false, d = false, k = false;
-    const int rc = pack_host(m, P2, e, d, k);
+    bool e = false, d = false, k = false, f = false;
+    const int rc = pack_host(m, P2, e, d, k, f);
     m->host.swap(shadow);
     m->w = saved;
     if (rc) return 1;
@@ -1687,6 +1765,21 @@ int l2s_speaker_encoder_fwd(l2s_model* m, const float* audio, int B, int n_sampl
     return speaker_run(m, audio, B, n_samples, emb, ws, ws_bytes, (hipStream_t)stream);
 }
 
+int64_t l2s_face_workspace_bytes(int B, int H, int W) {
+    if (B <= 0 || H != 160 || W != 160) { set_error("l2s_face_workspace_bytes: faces are 160 x 160 (B > 0)"); return -1; }
+    const int64_t f = face_ws_floats(B);
+    return f < 0 ? -1 : f * (int64_t)sizeof(float) + (1 << 12);
+}
+
+int l2s_face_encoder_fwd(l2s_model* m, const float* faces, int64_t batch_stride, int B, int H, int W, float* proj, float* emb, void* ws, int64_t ws_bytes,
+                         void* stream) {
+    L2S_MODEL_READY(m);
+    L2S_REQUIRE(m->has_face, "model holds no vgg_face.* weights");
+    L2S_REQUIRE(H == 160 && W == 160, "the face tower takes 160 x 160 faces");
+    L2S_REQUIRE(faces && emb && ws && B > 0 && batch_stride >= (int64_t)3 * H * W, "bad arguments");
+    return face_run(m, faces, batch_stride, B, proj, emb, ws, ws_bytes, (hipStream_t)stream, nullptr);
+}
+
 int l2s_output_lengths(const float* stop, int B, int S, int64_t* lengths, void* stream) {
     L2S_REQUIRE(stop && lengths && B > 0 && S > 0, "bad arguments");
     return launch_output_lengths(stop, B, S, lengths, (hipStream_t)stream);
@@ -1923,6 +2016,34 @@ int l2s_op_frontend(l2s_model* m, const float* video, int B, int T, int H, int W
     fe.pair = m->opt.frontend_x3 >= 2; fe.pipe = m->opt.frontend_x3 == 3;
     if (!m->opt.infer_bf16 || !m->planes_valid) fe.w1 = nullptr;
     return launch_frontend(fe, frame_src(video, B), B, T, H, W, out, (hipStream_t)stream);
+}
+int l2s_op_face_conv2d(const float* x, int64_t x_bstride, int B, int H, int W, int Cin, const float* w, const float* scale, const float* shift,
+                       const float* res, int relu, float* y, int Cout, int kh, int kw, int stride, int ph, int pw, void* stream) {
+    L2S_REQUIRE(x && w && scale && shift && y && B > 0 && Cin > 0 && Cout > 0 && kh > 0 && kw > 0 && stride > 0, "bad arguments");
+    FaceConvP p{};
+    p.x = x; p.x_bstride = x_bstride; p.nchw = x_bstride > 0; p.H = H; p.W = W; p.Cin = Cin; p.ldx = Cin; p.xoff = 0;
+    L2S_REQUIRE(!p.nchw || x_bstride >= (int64_t)Cin * H * W, "bad batch stride");
+    p.w = w; p.scale = scale; p.shift = shift; p.res = res; p.ldr = Cout; p.relu = relu;
+    p.y = y; p.ldy = Cout; p.yoff = 0;
+    p.kh = kh; p.kw = kw; p.stride = stride; p.ph = ph; p.pw = pw;
+    p.Ho = (H + 2 * ph - kh) / stride + 1; p.Wo = (W + 2 * pw - kw) / stride + 1;
+    L2S_REQUIRE(p.Ho > 0 && p.Wo > 0, "empty output");
+    p.M = B * p.Ho * p.Wo; p.N = Cout; p.K = kh * kw * Cin;
+    int kc;
+    const int ns = face_conv_splits(p.Ho * p.Wo, p.K, &kc);
+    const int64_t part_floats = ns > 1 ? (int64_t)ns * p.M * p.N : 0;
+    float* part = nullptr;
+    if (part_floats) L2S_CHECK_HIP(hipMalloc(&part, part_floats * sizeof(float)));
+    const int rc = launch_face_conv(p, part, part_floats, (hipStream_t)stream);
+    if (part) { (void)hipStreamSynchronize((hipStream_t)stream); (void)hipFree(part); }
+    return rc;
+}
+int l2s_op_face_taps(l2s_model* m, const float* faces, int64_t batch_stride, int B, float* const* taps, float* proj, float* emb, void* ws, int64_t ws_bytes,
+                     void* stream) {
+    L2S_MODEL_READY(m);
+    L2S_REQUIRE(m->has_face, "model holds no vgg_face.* weights");
+    L2S_REQUIRE(faces && taps && emb && ws && B > 0 && batch_stride >= (int64_t)3 * 160 * 160, "bad arguments");
+    return face_run(m, faces, batch_stride, B, proj, emb, ws, ws_bytes, (hipStream_t)stream, taps);
 }
 
 #endif

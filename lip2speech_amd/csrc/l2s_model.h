@@ -41,6 +41,32 @@ struct UnitW {
     const float* b1_frag = nullptr; int kin = 0;                                      // stride-2 units: banch1 pw, and pw1, have K = kin = pad16(cin)
     const void* pw1_p3 = nullptr; const void* pw2_p3 = nullptr; const void* b1_p3 = nullptr;   // the same as bf16 operand planes (launch_su_planes; option "trunk_x3")
 };
+// face tower (face_tower.hip)
+struct FaceConvP {                      // one Conv2d as an implicit GEMM (face_conv_kernel)
+    const float* x; int64_t x_bstride;  // NHWC input (B,H,W,ldx), channels [xoff, xoff + Cin); nchw: image b at x + b*x_bstride, (Cin,H,W)
+    int nchw, H, W, Cin, ldx, xoff;
+    const float* w;                     // [N][kh][kw][Cin]
+    const float* scale; const float* shift;     // v = acc*scale + shift (+ res) (ReLU)
+    const float* res; int ldr, relu;
+    float* y; int ldy, yoff;            // y[row*ldy + yoff + n], row = (b, oh, ow)
+    int kh, kw, stride, ph, pw, Ho, Wo, M, N, K;
+    int kchunk; float* part;            // split-K (set by launch_face_conv): slice z covers k in [z*kchunk, (z+1)*kchunk), raw sums to part[z][M][N]
+};
+struct FaceConvW { const float* w = nullptr; const float* scale = nullptr; const float* shift = nullptr; };      // geometry: face_layers()
+struct FaceTailW {                      // transposed ([in][out]) Linear weights of the tail kernel
+    const float* llT = nullptr;         // last_linear [1792][512]
+    const float* bn_s = nullptr; const float* bn_h = nullptr;      // last_bn folded (eps 1e-3)
+    const float* p0T = nullptr; const float* p0b = nullptr;        // projection_layer.0 [512][512], bias
+    const float* p2T = nullptr; const float* p2b = nullptr;        // projection_layer.2 [512][256], bias
+};
+constexpr int FACE_N_CONVS = 104;      // entries of face_layers()
+struct FaceW { FaceConvW convs[FACE_N_CONVS]; FaceTailW tail; };      // fixed arrays: the packer's pointer slots live inside l2s_model::w
+// one entry of the tower's layer table: a BasicConv2d (res_scale == 0: conv without bias, BatchNorm eps 1e-3, ReLU) or the 1x1 up-projection of an
+// Inception-ResNet block (res_scale > 0: conv with bias, scaled); several parts = 1x1 heads fused into one GEMM (output columns in part order)
+struct FaceLayer { std::vector<std::string> parts; int cin, cout, kh, kw, stride, ph, pw; float res_scale; };
+const std::vector<FaceLayer>& face_layers();
+constexpr float FACE_BN_EPS = 1e-3f;
+
 struct SkW { const float* W = nullptr; const float* bias = nullptr; const float* actw = nullptr; int N = 0, K = 0, tiles = 0; const void* W3 = nullptr; };      // W3: bf16 planes (split-bf16 LSTM blocks)
 
 struct Weights {
@@ -70,6 +96,7 @@ struct Weights {
     ConvW spk_ih[3];                 // input weights [1024][in] with shift = b_ih + b_hh
     SkW spk_hh[3];                   // recurrent weights, frag16, rows permuted to (unit, gate)
     ConvW spk_linear;
+    FaceW face;                      // face tower (vgg_face.*): the layer table's convolutions in order, the tail
 };
 
 }  // namespace l2s
@@ -79,7 +106,7 @@ struct l2s_model {
     float* blob = nullptr;
     int64_t blob_floats = 0;
     bool finalized = false;
-    bool has_enc = false, has_dec = false, has_spk = false;
+    bool has_enc = false, has_dec = false, has_spk = false, has_face = false;
     l2s::Weights w;
     l2s::Options opt;            // this model's run-time options (l2s_model_set_option; defaults from l2s_set_option at creation)
     // captured decode loops (hipGraph), replayed on a private non-blocking stream fenced against the caller's stream
@@ -118,6 +145,13 @@ struct l2s_model {
 
 namespace l2s {
 constexpr int NM_ = L2S_N_MELS;
+int face_conv_splits(int HoWo, int K, int* kchunk);
+int launch_face_conv(FaceConvP p, float* part, int64_t part_floats, hipStream_t s);
+int64_t face_ws_floats(int B);
+// taps (or null): 8 device pointers (each may be null) receiving conv2d_4b, repeat_1 (B,17,17,256), mixed_6a, repeat_2 (B,8,8,896), mixed_7a, block8
+// (B,3,3,1792), the pooled (B,1792) and last_bn's (B,512) outputs
+int face_run(l2s_model* m, const float* faces, int64_t bstride, int B, float* proj, float* emb, void* ws, int64_t ws_bytes, hipStream_t s,
+             float* const* taps);
 struct Bump {
     char* base; int64_t cap; int64_t off = 0; bool overflow = false;
     Bump(void* p, int64_t c) : base((char*)p), cap(c) {}

@@ -31,6 +31,7 @@ ABI_SYMBOLS = (
     "l2s_min_T", "l2s_workspace_bytes", "l2s_state_floats", "l2s_state_offset",
     "l2s_encoder_fwd", "l2s_normalise_pad_frames", "l2s_build_visual", "l2s_decoder_prologue", "l2s_decode_steps", "l2s_postnet",
     "l2s_output_lengths", "l2s_inference", "l2s_inference_multi", "l2s_workspace_bytes_multi", "l2s_forward_eval", "l2s_forward_eval_multi", "l2s_model_set_option", "l2s_persist_available", "l2s_persist_timeouts", "l2s_set_thread_chains", "l2s_speaker_workspace_bytes", "l2s_speaker_encoder_fwd",
+    "l2s_face_workspace_bytes", "l2s_face_encoder_fwd",
     "l2s_inverse_mel_workspace_bytes", "l2s_inverse_mel", "l2s_griffin_lim_workspace_bytes", "l2s_griffin_lim", "l2s_estoi_workspace_bytes", "l2s_estoi",
     "l2s_set_option",
     "l2s_train_scratch_bytes", "l2s_loss", "l2s_grad_norm", "l2s_adamw_amsgrad_step",
@@ -44,6 +45,7 @@ ABI_SYMBOLS = (
 # what include/l2s_diag.h adds: exported by libl2s_diag.so only
 DIAG_SYMBOLS = (
     "l2s_op_gemm", "l2s_op_conv1d", "l2s_op_gemm_ex", "l2s_op_conv1d_ex", "l2s_op_conv1d_bwd", "l2s_op_frontend", "l2s_op_launch_chain", "l2s_op_launch_chain2", "l2s_op_skinny_timeline", "l2s_op_attn_timeline", "l2s_op_flat_timeline", "l2s_op_pdecode_timeline", "l2s_op_gemm_x3_timeline", "l2s_op_fused_unit_timeline", "l2s_op_lstm_cell_chain", "l2s_op_step_attn_chain", "l2s_op_stamp_log",
+    "l2s_op_face_conv2d", "l2s_op_face_taps",
 )
 
 # run-time options only the diagnostic build accepts (block-form A/B switches of the same arithmetic, include/l2s_diag.h)
@@ -115,6 +117,9 @@ def _bind(L: ctypes.CDLL) -> None:
     L.l2s_speaker_workspace_bytes.argtypes = [_i, _i]
     L.l2s_speaker_workspace_bytes.restype = _i64
     L.l2s_speaker_encoder_fwd.argtypes = [_vp, _fp, _i, _i, _fp, _vp, _i64, _vp]
+    L.l2s_face_workspace_bytes.argtypes = [_i, _i, _i]
+    L.l2s_face_workspace_bytes.restype = _i64
+    L.l2s_face_encoder_fwd.argtypes = [_vp, _fp, _i64, _i, _i, _i, _fp, _fp, _vp, _i64, _vp]
     L.l2s_inference.argtypes = [_vp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _fp, _vp, _fp, _vp, _i64, _vp]
     L.l2s_workspace_bytes_multi.argtypes = [_i] * 6
     L.l2s_workspace_bytes_multi.restype = _i64
@@ -189,6 +194,8 @@ def _bind_diag(L: ctypes.CDLL) -> None:
     L.l2s_op_step_attn_chain.argtypes = [_vp, _fp, _i, _i, _i, _vp, _i64, _vp]
     L.l2s_op_lstm_cell_chain.argtypes = [_vp, _i, _i, _vp, _i64, _vp, ctypes.POINTER(ctypes.c_double)]
     L.l2s_op_stamp_log.argtypes = [_vp, _i64]
+    L.l2s_op_face_conv2d.argtypes = [_fp, _i64, _i, _i, _i, _i, _fp, _fp, _fp, _fp, _i, _fp, _i, _i, _i, _i, _i, _i, _vp]
+    L.l2s_op_face_taps.argtypes = [_vp, _fp, _i64, _i, _vp, _fp, _fp, _vp, _i64, _vp]
 
 
 def check(rc: int, L: Optional[ctypes.CDLL] = None) -> None:
@@ -415,6 +422,37 @@ class NativeModel:
         ws = torch.empty(int(self._L.l2s_speaker_workspace_bytes(B, N)), dtype=torch.uint8, device=audio.device)
         self._check(self._L.l2s_speaker_encoder_fwd(self._h, _ptr(audio), B, N, _ptr(emb), _ptr(ws), ws.numel(), _stream()))
         return emb
+
+    def _faces(self, faces: torch.Tensor):
+        """(B,3,160,160) fp32 on the device, each image contiguous; the batch stride may be anything (face_frames[:, 0] is used as it is)."""
+        if not faces.is_cuda:
+            raise RuntimeError("the face tower runs on the GPU: move face_frames to cuda (no CPU fallback)")
+        if faces.dim() != 4 or faces.shape[1] != 3:
+            raise ValueError(f"faces must be (B, 3, H, W), got {tuple(faces.shape)}")
+        B, _, H, W = faces.shape
+        if faces.dtype != torch.float32 or faces.stride()[1:] != (H * W, W, 1) or faces.stride(0) < 3 * H * W:
+            faces = faces.detach().to(torch.float32).contiguous()
+        need = int(self._L.l2s_face_workspace_bytes(B, H, W))
+        if need < 0:
+            self._check(1)
+        return faces, B, H, W, need
+
+    def face_encoder_fwd(self, faces: torch.Tensor, want_proj: bool = False, taps: bool = False):
+        """FaceRecognizer (vgg_face.py:28-60): faces (B,3,160,160) -> emb (B,256) = normalize(relu(proj)), and proj (B,256) with want_proj.
+        taps=True (diagnostic library only): also the stage outputs of l2s_op_face_taps as a list of 8 tensors."""
+        faces, B, H, W, need = self._faces(faces)
+        dev = faces.device
+        emb = torch.empty(B, 256, dtype=torch.float32, device=dev)
+        proj = torch.empty(B, 256, dtype=torch.float32, device=dev) if want_proj else None
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        if taps:
+            shapes = [(B, 17, 17, 256)] * 2 + [(B, 8, 8, 896)] * 2 + [(B, 3, 3, 1792)] * 2 + [(B, 1792), (B, 512)]
+            outs = [torch.empty(s, dtype=torch.float32, device=dev) for s in shapes]
+            arr = (_vp * 8)(*[t.data_ptr() for t in outs])
+            _dcheck(diag().l2s_op_face_taps(self._h, faces.data_ptr(), faces.stride(0), B, arr, _ptr(proj), _ptr(emb), _ptr(ws), ws.numel(), _stream()))
+            return emb, proj, outs
+        self._check(self._L.l2s_face_encoder_fwd(self._h, faces.data_ptr(), faces.stride(0), B, H, W, _ptr(proj), _ptr(emb), _ptr(ws), ws.numel(), _stream()))
+        return (emb, proj) if want_proj else emb
 
     # ------------------------------------------------------------------ training (forward with tapes + backward, DESIGN.md section 9)
     def train_bind(self, params: Dict[str, torch.Tensor], grads: Dict[str, torch.Tensor]) -> None:
@@ -647,6 +685,30 @@ def op_conv1d(X, Wp, scale=None, shift=None, actw=None, taps=1, stride=1, pad=0,
     _dcheck(diag().l2s_op_conv1d_ex(_ptr(X), _ptr(Wp), _ptr(scale), _ptr(shift), _ptr(actw), _ptr(out), B, Tin, Cin, Cout,
                                  taps, stride, pad, act, (1 if x3 else 0) | (2 if bf16 else 0) | (4 if x3_narrow else 0) | (8 if x3_dma else 0), _stream()))
     return out
+
+
+def op_face_conv2d(x, w, scale, shift, stride=1, pad=(0, 0), res=None, relu=True, nchw=False) -> torch.Tensor:
+    """One Conv2d of the face tower's kernel: x NHWC (B,H,W,Cin), or with nchw=True a (B,Cin,H,W) view whose images are contiguous (any
+    batch stride); w (Cout,Cin,kh,kw) as torch stores it (re-laid here as [Cout][kh][kw][Cin]); -> NHWC (B,Ho,Wo,Cout)."""
+    if not x.is_cuda:
+        raise RuntimeError("device tensors only")
+    Cout, Cin, kh, kw = w.shape
+    if nchw:
+        B, _, H, W = x.shape
+        assert x.stride()[1:] == (H * W, W, 1)
+        bstride = x.stride(0)
+    else:
+        x = _f32(x)
+        B, H, W, _ = x.shape
+        bstride = 0
+    wp = _f32(w.permute(0, 2, 3, 1))
+    ph, pw = pad
+    Ho, Wo = (H + 2 * ph - kh) // stride + 1, (W + 2 * pw - kw) // stride + 1
+    y = torch.empty(B, Ho, Wo, Cout, dtype=torch.float32, device=x.device)
+    res = _f32(res) if res is not None else None
+    _dcheck(diag().l2s_op_face_conv2d(x.data_ptr(), bstride, B, H, W, Cin, _ptr(wp), _ptr(_f32(scale)), _ptr(_f32(shift)), _ptr(res), 1 if relu else 0,
+                                      _ptr(y), Cout, kh, kw, stride, ph, pw, _stream()))
+    return y
 
 
 def set_option(name: str, value: int) -> None:

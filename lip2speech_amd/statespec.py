@@ -43,7 +43,7 @@ CONTENT_KS = (1, 3, 5, 7)
 POSTNET_K = 5
 POSTNET_LAYERS = 5
 
-BUFFER_KINDS = {"bn_rm", "bn_rv", "bn_nbt", "pos_table"}
+BUFFER_KINDS = {"bn_rm", "bn_rv", "bn_nbt", "pos_table", "face_bn_rm", "face_bn_rv"}
 
 
 def _bn(prefix: str, c: int) -> Spec:
@@ -176,6 +176,64 @@ def speaker_encoder_spec(prefix: str = "") -> Spec:
         s.append((f"{prefix}lstm.bias_ih_l{layer}", (1024,), "lstm:256"))
         s.append((f"{prefix}lstm.bias_hh_l{layer}", (1024,), "lstm:256"))
     s += [(prefix + "linear.weight", (256, 256), "default"), (prefix + "linear.bias", (256,), "bias:256")]
+    return s
+
+
+def _face_bc(p: str, cin: int, cout: int, kh: int, kw: int) -> Spec:
+    """BasicConv2d of facenet_pytorch: Conv2d without bias, BatchNorm2d(eps=0.001), ReLU."""
+    s: Spec = [(p + ".conv.weight", (cout, cin, kh, kw), "conv_face")]
+    s += [(p + ".bn.weight", (cout,), "face_bn_w"), (p + ".bn.bias", (cout,), "face_bn_b"),
+          (p + ".bn.running_mean", (cout,), "face_bn_rm"), (p + ".bn.running_var", (cout,), "face_bn_rv"),
+          (p + ".bn.num_batches_tracked", (), "bn_nbt")]
+    return s
+
+
+def face_tower_spec(prefix: str = "") -> Spec:
+    """vgg_face.* keys (reference/model/modules/vgg_face.py:12-26): facenet_pytorch 2.5.2's InceptionResnetV1 (casia-webface: logits
+    has 10575 classes) as ``resnet.*``, then ``projection_layer.{0,2}``.  The architecture is restated from the published package
+    (not on this host): parity against the package is unpinned."""
+    r = prefix + "resnet."
+    s: Spec = []
+    s += _face_bc(r + "conv2d_1a", 3, 32, 3, 3)
+    s += _face_bc(r + "conv2d_2a", 32, 32, 3, 3)
+    s += _face_bc(r + "conv2d_2b", 32, 64, 3, 3)
+    s += _face_bc(r + "conv2d_3b", 64, 80, 1, 1)
+    s += _face_bc(r + "conv2d_4a", 80, 192, 3, 3)
+    s += _face_bc(r + "conv2d_4b", 192, 256, 3, 3)
+
+    def up(p, cin, cout):
+        return [(p + ".weight", (cout, cin, 1, 1), "conv_face"), (p + ".bias", (cout,), f"bias:{cin}")]
+
+    for i in range(5):                                   # Block35(scale=0.17)
+        p = f"{r}repeat_1.{i}."
+        s += _face_bc(p + "branch0", 256, 32, 1, 1)
+        s += _face_bc(p + "branch1.0", 256, 32, 1, 1) + _face_bc(p + "branch1.1", 32, 32, 3, 3)
+        s += _face_bc(p + "branch2.0", 256, 32, 1, 1) + _face_bc(p + "branch2.1", 32, 32, 3, 3) + _face_bc(p + "branch2.2", 32, 32, 3, 3)
+        s += up(p + "conv2d", 96, 256)
+    p = r + "mixed_6a."
+    s += _face_bc(p + "branch0", 256, 384, 3, 3)
+    s += _face_bc(p + "branch1.0", 256, 192, 1, 1) + _face_bc(p + "branch1.1", 192, 192, 3, 3) + _face_bc(p + "branch1.2", 192, 256, 3, 3)
+    for i in range(10):                                  # Block17(scale=0.10)
+        p = f"{r}repeat_2.{i}."
+        s += _face_bc(p + "branch0", 896, 128, 1, 1)
+        s += _face_bc(p + "branch1.0", 896, 128, 1, 1) + _face_bc(p + "branch1.1", 128, 128, 1, 7) + _face_bc(p + "branch1.2", 128, 128, 7, 1)
+        s += up(p + "conv2d", 256, 896)
+    p = r + "mixed_7a."
+    s += _face_bc(p + "branch0.0", 896, 256, 1, 1) + _face_bc(p + "branch0.1", 256, 384, 3, 3)
+    s += _face_bc(p + "branch1.0", 896, 256, 1, 1) + _face_bc(p + "branch1.1", 256, 256, 3, 3)
+    s += _face_bc(p + "branch2.0", 896, 256, 1, 1) + _face_bc(p + "branch2.1", 256, 256, 3, 3) + _face_bc(p + "branch2.2", 256, 256, 3, 3)
+    for name in [f"repeat_3.{i}" for i in range(5)] + ["block8"]:      # Block8(scale=0.20), block8: scale 1.0, no ReLU
+        p = f"{r}{name}."
+        s += _face_bc(p + "branch0", 1792, 192, 1, 1)
+        s += _face_bc(p + "branch1.0", 1792, 192, 1, 1) + _face_bc(p + "branch1.1", 192, 192, 1, 3) + _face_bc(p + "branch1.2", 192, 192, 3, 1)
+        s += up(p + "conv2d", 384, 1792)
+    s.append((r + "last_linear.weight", (512, 1792), "conv_face"))
+    s += [(r + "last_bn.weight", (512,), "face_bn_w"), (r + "last_bn.bias", (512,), "face_bn_b"),
+          (r + "last_bn.running_mean", (512,), "face_bn_rm"), (r + "last_bn.running_var", (512,), "face_bn_rv"),
+          (r + "last_bn.num_batches_tracked", (), "bn_nbt")]
+    s += [(r + "logits.weight", (10575, 512), "default"), (r + "logits.bias", (10575,), "bias:512")]
+    s += [(prefix + "projection_layer.0.weight", (512, 512), "default"), (prefix + "projection_layer.0.bias", (512,), "bias:512"),
+          (prefix + "projection_layer.2.weight", (256, 512), "default"), (prefix + "projection_layer.2.bias", (256,), "bias:512")]
     return s
 
 

@@ -94,6 +94,16 @@ def _draw(key: str, shape: Tuple[int, ...], kind: str, seed: int) -> torch.Tenso
         n = int(np.prod(shape[2:])) * shape[0]
         sigma = math.sqrt(2.0 / n)
         arr = sym_uniform(key, shape, sigma * math.sqrt(3.0), seed)
+    elif kind == "conv_face":
+        # He-scaled (fan-in) for the face tower's ~100 layers: with the near-identity BatchNorm statistics below the activations stay O(1)
+        fan_in = int(np.prod(shape[1:]))
+        arr = sym_uniform(key, shape, math.sqrt(2.0 / fan_in) * math.sqrt(3.0), seed)
+    elif kind == "face_bn_w":
+        arr = 0.8 + 0.4 * uniform01(key, shape[0], seed)
+    elif kind in ("face_bn_b", "face_bn_rm"):
+        arr = sym_uniform(key, shape, 0.1, seed)
+    elif kind == "face_bn_rv":
+        arr = 0.8 + 0.4 * uniform01(key, shape[0], seed)
     elif kind == "bn_w":
         arr = 0.5 + uniform01(key, shape[0], seed)
     elif kind == "bn_b":
@@ -135,6 +145,16 @@ def synth_state_dict(spec: Iterable = None, seed: int = 1234) -> Dict[str, torch
     """Synthetic checkpoint for the measured path (encoder.* + decoder.* keys)."""
     spec = statespec.model_spec() if spec is None else spec
     return {key: _draw(key, tuple(shape), kind, seed) for key, shape, kind in spec}
+
+
+def synth_face_state_dict(seed: int = 1234) -> Dict[str, torch.Tensor]:
+    """Synthetic vgg_face.* tensors (the face tower + projection, statespec.face_tower_spec("vgg_face."))."""
+    return synth_state_dict(statespec.face_tower_spec("vgg_face."), seed)
+
+
+def synth_faces(B: int, n_faces: int = 2, seed: int = 1234, tag: str = "faces") -> torch.Tensor:
+    """face_crops (B, n_faces, 3, 160, 160) in [-1, 1): what the loaders hand the model ((x - 127.5) / 128 of a 160 x 160 RGB crop)."""
+    return torch.from_numpy(sym_uniform(f"{tag}:{B}x{n_faces}", (B, n_faces, 3, 160, 160), 1.0, seed))
 
 
 def synth_video(B: int, T: int, H: int = 96, W: int = 96, seed: int = 1234, tag: str = "video") -> torch.Tensor:
