@@ -342,7 +342,24 @@ int l2s_train_encoder_bwd(l2s_model* m, const float* video, int B, int T, int H,
  *                            own (same bits), 1 = one frame per block, 0 = the f32 MFMA kernel
  *   "trunk_x3"          (1)  the fused ShuffleNet units' pointwise convs on the split-bf16 path; 0 = f32 MFMA
  *   "lstm_x3"           (3)  the decode step's two LSTM launches on the split-bf16 path (1 / 2 / 3: four-wave / eight-wave / half-CU block forms of the
- *                            same arithmetic, same bits - 3 picks by l2s_set_thread_chains); 0 = f32 MFMAs (other bits, rounding-level) */
+ *                            same arithmetic, same bits - 3 picks by l2s_set_thread_chains); 0 = f32 MFMAs (other bits, rounding-level)
+ *   "early_stop"        (0)  free-running inference (l2s_inference, l2s_inference_multi, l2s_decode_steps without teacher frames) ends the decode loop once
+ *                            every clip of the call has stopped, instead of always running S steps as the reference does (decoder.py:412-435).  With
+ *                            len_b = the clip's output_lengths entry, E_b = min(S, len_b + 10) and E = max E_b over the call's rows (all G x B of a group):
+ *                            the post-net is five Conv1d layers of kernel 5, so frame j < len_b of mel_post reads decoded frames up to len_b + 9 only, and
+ *                            decoding E_b steps gives every kept frame the inputs of the S-step pass.  On:
+ *                              - lengths are exactly the option-off lengths; shapes stay (B,80,S) / (B,S,T);
+ *                              - mel_post[b][:][j] and attn[b][j][:] for j < len_b are the S-step values (same bits on the launch-per-phase route);
+ *                              - for j >= len_b - what every caller drops - both are exactly 0: the reference's output masked by its own lengths;
+ *                              - l2s_decode_steps' staged mel / stop / attention: steps < E_b as with the option off, steps >= E exactly 0, steps in
+ *                                [E_b, E) computed on the launch-per-phase route (the batch runs until its last clip ends) and 0 on the persistent route
+ *                                (each clip leaves on its own); the buffers are zero-filled on the stream first, nothing stays unwritten;
+ *                              - a call with a clip that never stops (len_b = S) runs to S: the option-off call plus the masking.
+ *                            The decision is made on the device - the host enqueues all S steps without synchronising; the step kernels past the end
+ *                            return at their top (launch route), the persistent loop's workgroups leave their loop.  The post-net still runs over all
+ *                            S frames (of zeros past E).  Ignored by l2s_forward_eval(_multi), teacher-forced l2s_decode_steps and the training entry
+ *                            points (their S comes from the target).  With "use_graph" the call takes the plain launch route (a replayed graph carries
+ *                            no control block of the call); the diagnostic post-net overlap ("overlap_postnet") likewise takes the plain route */
 int l2s_set_option(const char* name, int value);
 int l2s_model_set_option(l2s_model* m, const char* name, int value);
 /* The persistent forms (option "persist_decode") spin on other workgroups and need all of them resident at once.  l2s_persist_available: 1 where that

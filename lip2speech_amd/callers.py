@@ -21,11 +21,14 @@ import torch
 from . import native
 
 
-def demo_clip(net, batch, speaker_encoder=None, speaker_embedding: Optional[torch.Tensor] = None, device="cuda", encoding: str = "voice"):
+def demo_clip(net, batch, speaker_encoder=None, speaker_embedding: Optional[torch.Tensor] = None, device="cuda", encoding: str = "voice",
+              early_stop: bool = False):
     """``batch`` = one item of ``DataLoader(ds, batch_size=1, collate_fn=test_collate_fn_pad)`` (one iteration of demo.py:60-90): the direct
     ``net.inference`` call, which for one clip takes the library's latency form (the decode loop as one persistent launch, option "persist_decode") -
     a single clip has no grouping to stay consistent with; ``demo_clips`` streams a whole loader through the grouped path instead.
-    ``encoding="face"`` (demo.py ``--encoding face``): no embedding is passed, the model takes it from its face tower (``net.vgg_face``)."""
+    ``encoding="face"`` (demo.py ``--encoding face``): no embedding is passed, the model takes it from its face tower (``net.vgg_face``).
+    ``early_stop``: the decode loop ends once the clip has stopped (model option "early_stop", set on ``net`` for this call and after); the
+    returned mel and attention are already truncated to ``output_lengths[0]`` and are the same either way."""
     _check_encoding(encoding)
     if encoding == "voice" and speaker_embedding is None and speaker_encoder is None:
         raise ValueError("pass a SpeakerEncoder (voice route) or a speaker_embedding")
@@ -33,18 +36,20 @@ def demo_clip(net, batch, speaker_encoder=None, speaker_embedding: Optional[torc
     with torch.no_grad():
         emb = _voice_embedding(encoding, speaker_encoder, speaker_embedding, audios, device)
         face_crops = face_crops.to(device, non_blocking=True) if encoding == "face" else face_crops
-        mel, lengths, attn = net.inference(videos.to(device, non_blocking=True), face_crops, speaker_embedding=emb, return_attention_map=True)
+        mel, lengths, attn = net.inference(videos.to(device, non_blocking=True), face_crops, speaker_embedding=emb, return_attention_map=True,
+                                           early_stop=bool(early_stop))
     n = int(lengths[0])                                  # synchronises: a timed-out persistent launch is reported here, not handed on as NaN
     native.check_persist_timeouts()
     return mel[:1, :, :n], lengths, attn[:, :n]
 
 
 def demo_clips(net, batches: Iterable, speaker_encoder=None, speaker_embedding: Optional[torch.Tensor] = None, device="cuda",
-               group: int = 8, n_inflight: int = 3, encoding: str = "voice"):
+               group: int = 8, n_inflight: int = 3, encoding: str = "voice", early_stop: bool = False):
     """demo.py:60-90 over a whole loader: per clip the speaker embedding from the VOICE tower (``--encoding voice``) or a supplied one,
     ``net.inference(..., return_attention_map=True)``, truncation to ``output_lengths[0]``.  The clips are advanced ``group`` per launch
     chain with ``n_inflight`` chains on the GPU (``Lip2Speech.inference_many``); yields ``(mel, lengths, attention)`` per clip, in order.
-    ``encoding="face"``: the embedding comes from the model's face tower instead."""
+    ``encoding="face"``: the embedding comes from the model's face tower instead.  ``early_stop``: every group's decode loop ends once all of
+    its clips have stopped (model option "early_stop", set once on ``net`` before the chains start); the yielded tensors are the same."""
     _check_encoding(encoding)
     if encoding == "voice" and speaker_embedding is None and speaker_encoder is None:
         raise ValueError("pass a SpeakerEncoder (voice route) or a speaker_embedding")
@@ -55,7 +60,7 @@ def demo_clips(net, batches: Iterable, speaker_encoder=None, speaker_embedding: 
                 emb = _voice_embedding(encoding, speaker_encoder, speaker_embedding, audios, device)
             yield videos, face_crops, emb, True
 
-    for mel, lengths, attn in net.inference_many(calls(), group=group, n_inflight=n_inflight):
+    for mel, lengths, attn in net.inference_many(calls(), group=group, n_inflight=n_inflight, early_stop=bool(early_stop)):
         n = int(lengths[0])
         yield mel[:1, :, :n], lengths, attn[:, :n]
 

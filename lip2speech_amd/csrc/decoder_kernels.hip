@@ -209,6 +209,26 @@ int launch_output_lengths(const float* stop, int B, int S, int64_t* lengths, hip
     return 0;
 }
 
+// option "early_stop": what a caller drops anyway comes back as exact zeros - mel_post[b][c][j] and attn[b][j][t] for j >= lengths[b].  Stores only:
+// whatever the truncated loop left there (zero fill, frames of the margin, post-net output over them) is never read.
+__global__ __launch_bounds__(256) void mask_by_lengths_kernel(const int64_t* __restrict__ lengths, int S, int T, float* __restrict__ mel_post, float* __restrict__ attn) {
+    const int b = blockIdx.x;
+    const int len = (int)lengths[b], tail = S - len;
+    if (tail <= 0) return;
+    float* const mp = mel_post + (int64_t)b * 80 * S;
+    for (int i = threadIdx.x; i < 80 * tail; i += 256) mp[(int64_t)(i / tail) * S + len + i % tail] = 0.f;
+    if (attn) {
+        float* const at = attn + ((int64_t)b * S + len) * T;
+        for (int i = threadIdx.x; i < tail * T; i += 256) at[i] = 0.f;
+    }
+}
+int launch_mask_by_lengths(const int64_t* lengths, int B, int S, int T, float* mel_post, float* attn, hipStream_t s) {
+    ProfScope ps("mask_by_lengths", s);
+    hipLaunchKernelGGL(mask_by_lengths_kernel, dim3(B), dim3(256), 0, s, lengths, S, T, mel_post, attn);
+    L2S_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
 // stop_const[b] = dot(ecell[b][0:512], w_tail[0:512]) + bias   (the encoder_cell half of stop_token_layer,
 // constant over the decode steps; decoder.py:429)
 __global__ __launch_bounds__(64) void stop_const_kernel(const float* __restrict__ ecell, const float* __restrict__ w_tail,

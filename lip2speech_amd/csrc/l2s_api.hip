@@ -33,7 +33,7 @@ int set_option_field(Options& o, const char* name, int value) {
     static const Row product[] = {
         {"persist_decode", &Options::persist}, {"use_graph", &Options::graph}, {"fold_step_weights", &Options::fold}, {"refresh_map", &Options::refresh_map},
         {"infer_bf16", &Options::infer_bf16}, {"train_bf16", &Options::train_bf16}, {"gemm_x3", &Options::gemm_x3}, {"frontend_x3", &Options::frontend_x3},
-        {"trunk_x3", &Options::trunk_x3}, {"lstm_x3", &Options::lstm_x3}};
+        {"trunk_x3", &Options::trunk_x3}, {"lstm_x3", &Options::lstm_x3}, {"early_stop", &Options::early_stop}};
     for (auto& t : product)
         if (!std::strcmp(name, t.name)) { o.*(t.field) = value; return 0; }
 #ifdef L2S_DIAG
@@ -1049,7 +1049,7 @@ static int64_t prologue_ws_floats(int B, int T) {
 }
 static int64_t decode_ws_floats(int B) {
     int64_t Bp = pad16(B);
-    return Bp * (512 * 4 + 512 * 2 + 512 + 256 * 4 + 96) + (int64_t)B * (512 + 256 + 256) + 64 * 24 + (B <= 8 ? pdecode_ws_bytes(B) / 4 + 64 : 0);
+    return Bp * (512 * 4 + 512 * 2 + 512 + 256 * 4 + 96) + (int64_t)B * (512 + 256 + 256) + 64 * 24 + (B + 2 + 64) /* EsCtl */ + (B <= 8 ? pdecode_ws_bytes(B) / 4 + 64 : 0);
 }
 constexpr int POST_TAPSPLIT_ROWS = 640;      // a batch with at most this many post-net rows (one or two clips of 300 frames) runs its Conv1d layers one K slice per tap
 static int64_t postnet_ws_floats(int B, int S) { return (int64_t)B * S * 512 * ((int64_t)B * S <= POST_TAPSPLIT_ROWS * MAX_GROUP ? 9 : 4) + 64 * 7; }
@@ -1368,7 +1368,7 @@ struct DecodeBufs {
 // on_frames(n): called (if set) right after the launch that completes mel frames [0, n) has been enqueued on `s`
 static int decode_launches(l2s_model* m, float* state, int B, int T, int S, const float* teacher, const uint8_t* teacher_mask,
                            float* mel, float* stop, float* attn, int attn_logits, void* ws, int64_t ws_bytes, hipStream_t s, bool fold,
-                           const std::function<int(int)>* on_frames = nullptr) {
+                           const std::function<int(int)>* on_frames = nullptr, bool early = false) {
     const Weights& w = m->w;
     StateLayout sl = state_layout(B, T);
     const int Bp = pad16(B);
@@ -1382,7 +1382,12 @@ static int decode_launches(l2s_model* m, float* state, int B, int T, int S, cons
     d.p1 = bp.f((int64_t)Bp * 256); d.cc = bp.f((int64_t)Bp * 256); d.uu = bp.f((int64_t)Bp * 256); d.p2f = bp.f((int64_t)Bp * 256);
     d.yf = bp.f((int64_t)Bp * 96);
     d.q = bp.f((int64_t)B * 512); d.qc = bp.f((int64_t)B * 256); d.p2 = bp.f((int64_t)B * 256);
+    // option "early_stop" (free-running loops only): this call's control block, armed on the stream - chains in flight on other streams have their own
+    EsCtl* const es = early ? reinterpret_cast<EsCtl*>(bp.f(B + 2)) : nullptr;
     L2S_REQUIRE(!bp.overflow, "decode workspace too small");
+    L2S_REQUIRE(!early || !teacher, "early stop is for free-running loops");
+    if (es) L2S_CHECK_HIP(hipMemsetAsync(es, 0, sizeof(int) * (B + 2), s));
+    const int* const es_end = es ? &es->end_rel : nullptr;
 
     // initial state: h from the prologue, c = 0, y = BOS; padded rows of every frag buffer zero
     L2S_CHECK_HIP(hipMemcpyAsync(d.h0[0], state + sl.h, sizeof(float) * Bp * 512, hipMemcpyDeviceToDevice, s));
@@ -1399,6 +1404,7 @@ static int decode_launches(l2s_model* m, float* state, int B, int T, int S, cons
         a.seg[0] = {h1buf, 32}; a.nseg = 1; a.epi = SK_MEL;
         a.mel = mel + (int64_t)step * NM; a.ld_mel_b = (int64_t)S * NM;
         a.stop = stop + step; a.ld_stop_b = S; a.stop_const = state + sl.stopc; a.yfrag = write_y ? d.yf : nullptr;
+        if (es) { a.es_ctl = reinterpret_cast<int*>(es); a.es_end = std::min(S, step + 1 + ES_MARGIN) - S; }
         return a;
     };
 
@@ -1423,6 +1429,8 @@ static int decode_launches(l2s_model* m, float* state, int B, int T, int S, cons
             sb.p[2] = c; sb.ntiles[2] = w.cq.tiles;
             sb.count = 3;
             if (fold && i > 0) { sb.p[3] = fc_group(i - 1, d.h1[cur], false); sb.ntiles[3] = w.fc.tiles; sb.count = 4; }
+            // the folded launch also finishes step i - 1 (its mel frame and stop logit): it is skipped as part of THAT step, i.e. one step later
+            sb.es_end = es_end; sb.es_step = (fold && i > 0 ? i - 1 : i) - S;
             if (launch_skinny(sb, s, fold ? "step_prenet1_q_cq_fc" : "step_prenet1_q_cq", m->opt)) return 1;
             if (fold && i > 0 && on_frames && (*on_frames)(i)) return 1;
         }
@@ -1433,6 +1441,7 @@ static int decode_launches(l2s_model* m, float* state, int B, int T, int S, cons
             at.attn_out = attn ? attn + (int64_t)i * T : nullptr; at.ld_attn_b = (int64_t)S * T; at.attn_logits = attn_logits;
             at.qc = d.qc; at.ldqc = 256; at.ckey = state + sl.ckey; at.cval = state + sl.cval; at.tau_c = w.tau_c; at.cc_frag = d.cc;
             at.B = B; at.T = T; at.m = sl.m;
+            at.es_end = es_end; at.es_step = i - S;
             SkinnyP pr = sk_base(w.pre2, B);
             pr.seg[0] = {d.p1, 16}; pr.nseg = 1; pr.act = ACT_PSINE;
             if (fold) { pr.epi = SK_FRAG; pr.out = d.p2f; pr.ldo = 256; }
@@ -1444,6 +1453,7 @@ static int decode_launches(l2s_model* m, float* state, int B, int T, int S, cons
             SkinnyP a = sk_base(w.aproj, B);
             a.seg[0] = {d.av, 32}; a.nseg = 1; a.epi = SK_FRAG; a.out = d.uu; a.ldo = 256; a.add = d.p2; a.ld_add = 256;
             sb.p[0] = a; sb.ntiles[0] = w.aproj.tiles; sb.count = 1;
+            sb.es_end = es_end; sb.es_step = i - S;
             if (launch_skinny(sb, s, "step_attention_proj", m->opt)) return 1;
         }
         {   // phase D: LSTM layer 0 on cat(content, u), h0  (folded: cat(content, prenet, a@v) against [W_ih | W_ih_u W_ap | W_hh])
@@ -1454,6 +1464,7 @@ static int decode_launches(l2s_model* m, float* state, int B, int T, int S, cons
             else { a.seg[0] = {d.cc, 16}; a.seg[1] = {d.uu, 16}; a.seg[2] = {d.h0[cur], 32}; a.nseg = 3; }
             a.epi = SK_LSTM; a.H = 512; a.c_in = d.c0; a.c_out = d.c0; a.h_out = d.h0[nxt]; a.h_out_K = 512; a.h_out_off = 0;
             sb.p[0] = a; sb.ntiles[0] = 128; sb.count = 1;
+            sb.es_end = es_end; sb.es_step = i - S;
             if (launch_skinny(sb, s, "step_lstm_cell", m->opt)) return 1;
         }
         {   // phase E: LSTM layer 1 on the new h0
@@ -1462,11 +1473,13 @@ static int decode_launches(l2s_model* m, float* state, int B, int T, int S, cons
             a.seg[0] = {d.h0[nxt], 32}; a.seg[1] = {d.h1[cur], 32}; a.nseg = 2;
             a.epi = SK_LSTM; a.H = 512; a.c_in = d.c1; a.c_out = d.c1; a.h_out = d.h1[nxt]; a.h_out_K = 512; a.h_out_off = 0;
             sb.p[0] = a; sb.ntiles[0] = w.lstm1.tiles; sb.count = 1;
+            sb.es_end = es_end; sb.es_step = i - S;
             if (launch_skinny(sb, s, "step_lstm_cell", m->opt)) return 1;
         }
         if (!fold || i == S - 1) {   // phase F: mel frame + stop logit (folded mode: only the last step needs its own launch)
             SkinnyBatch sb{};
             sb.p[0] = fc_group(i, d.h1[nxt], !fold); sb.ntiles[0] = w.fc.tiles; sb.count = 1;
+            sb.es_end = es_end; sb.es_step = i - S;
             if (launch_skinny(sb, s, "step_fc_out_stop", m->opt)) return 1;
             if (on_frames && (*on_frames)(i + 1)) return 1;
         }
@@ -1475,9 +1488,17 @@ static int decode_launches(l2s_model* m, float* state, int B, int T, int S, cons
 }
 
 static int decode_run(l2s_model* m, float* state, int B, int T, int S, const float* teacher, const uint8_t* teacher_mask,
-                      float* mel, float* stop, float* attn, int attn_logits, void* ws, int64_t ws_bytes, hipStream_t s) {
+                      float* mel, float* stop, float* attn, int attn_logits, void* ws, int64_t ws_bytes, hipStream_t s, bool may_stop_early) {
     L2S_REQUIRE(S >= 1 && S <= L2S_MAX_STEPS, "S must be in [1, 300] (positional table)");
     const bool fold = m->opt.fold != 0 && m->folded_valid;
+    // option "early_stop": free-running loops only (a teacher-forced loop's S comes from the target).  The steps the loop never reaches are exact zeros
+    // in the staged outputs: zero-filled on the stream first
+    const bool early = may_stop_early && m->opt.early_stop != 0 && !teacher;
+    if (early) {
+        L2S_CHECK_HIP(hipMemsetAsync(mel, 0, sizeof(float) * B * S * NM, s));
+        L2S_CHECK_HIP(hipMemsetAsync(stop, 0, sizeof(float) * B * S, s));
+        if (attn) L2S_CHECK_HIP(hipMemsetAsync(attn, 0, sizeof(float) * B * S * T, s));
+    }
     if (!teacher && fold && m->opt.persist > 0 && B <= m->opt.persist && !grouped_entry()) {      // the latency form: one launch for the whole loop
         const Weights& w = m->w;
         StateLayout sl = state_layout(B, T);
@@ -1497,11 +1518,12 @@ static int decode_run(l2s_model* m, float* state, int B, int T, int S, const flo
             p.h_init = state + sl.h; p.stop_const = state + sl.stopc;
             p.mel = mel; p.stop = stop; p.attn = attn; p.attn_logits = attn_logits;
             p.B = B; p.T = T; p.m = sl.m; p.S = S;
+            p.early = early ? ES_MARGIN : 0;
             return launch_pdecode(p, ws, ws_bytes, s);
         }
     }
-    const bool use_graph = m->opt.graph && !teacher && !g_prof_on;
-    if (!use_graph) return decode_launches(m, state, B, T, S, teacher, teacher_mask, mel, stop, attn, attn_logits, ws, ws_bytes, s, fold);
+    const bool use_graph = m->opt.graph && !teacher && !g_prof_on && !early;      // "early_stop" takes the plain route: a replayed graph knows no control block of this call
+    if (!use_graph) return decode_launches(m, state, B, T, S, teacher, teacher_mask, mel, stop, attn, attn_logits, ws, ws_bytes, s, fold, nullptr, early);
 
     std::lock_guard<std::mutex> side_lock(m->side_mu);      // graph cache, side stream and events are per model; chains of other threads wait here
     if (!m->side) {
@@ -1747,7 +1769,7 @@ int l2s_decode_steps(l2s_model* m, float* state, int B, int T, int S, const floa
                      float* stop, float* attn, int attn_logits, void* ws, int64_t ws_bytes, void* stream) {
     L2S_DEC_READY(m);
     L2S_REQUIRE(state && mel && stop && ws && B > 0, "bad arguments");
-    return decode_run(m, state, B, T, S, teacher, teacher_mask, mel, stop, attn, attn_logits, ws, ws_bytes, (hipStream_t)stream);
+    return decode_run(m, state, B, T, S, teacher, teacher_mask, mel, stop, attn, attn_logits, ws, ws_bytes, (hipStream_t)stream, true);
 }
 
 int l2s_postnet(l2s_model* m, const float* mel, int B, int S, float* mel_post, float* mel_cf, void* ws, int64_t ws_bytes, void* stream) {
@@ -1806,9 +1828,10 @@ static int path_run(l2s_model* m, const FrameSrc& video, const float* emb, const
     const int64_t rest_bytes = ws_bytes - bp.off;
     if (encoder_run(m, video, B, T, H, W, emb, vis, nullptr, rest, rest_bytes, s)) return 1;
     if (prologue_run(m, vis, emb, gumbel, B, T, state, o.content_dis, rest, rest_bytes, s)) return 1;
-    const bool plain = !m->opt.overlap_postnet || g_prof_on || m->opt.graph || teacher || o.mel_cf;
+    const bool early = m->opt.early_stop != 0 && !teacher && o.lengths;      // l2s_inference(_multi); l2s_forward_eval's S comes from the target
+    const bool plain = !m->opt.overlap_postnet || g_prof_on || m->opt.graph || teacher || o.mel_cf || early;      // "early_stop" takes the plain route
     if (plain) {
-        if (decode_run(m, state, B, T, S, teacher, teacher_mask, mel, stop, o.attn, o.attn_logits, rest, rest_bytes, s)) return 1;
+        if (decode_run(m, state, B, T, S, teacher, teacher_mask, mel, stop, o.attn, o.attn_logits, rest, rest_bytes, s, early)) return 1;
         if (postnet_run(m, mel, B, S, o.mel_post, o.mel_cf, rest, rest_bytes, s)) return 1;
     } else {
         // The decode loop is a chain of small latency-bound launches that leaves most CUs idle, and the post-net of frame t
@@ -1850,7 +1873,10 @@ static int path_run(l2s_model* m, const FrameSrc& video, const float* emb, const
         L2S_CHECK_HIP(hipEventRecord(m->ev_out, m->side));
         L2S_CHECK_HIP(hipStreamWaitEvent(s, m->ev_out, 0));
     }
-    return o.lengths ? launch_output_lengths(stop, B, S, o.lengths, s) : 0;
+    if (o.lengths && launch_output_lengths(stop, B, S, o.lengths, s)) return 1;
+    // option "early_stop": the frames every caller drops (j >= lengths[b]) come back as exact zeros - the reference's output masked by its own lengths
+    if (early && launch_mask_by_lengths(o.lengths, B, S, T, o.mel_post, o.attn, s)) return 1;
+    return 0;
 }
 
 static int inference_run(l2s_model* m, const FrameSrc& video, const float* emb, const float* gumbel, int B, int T, int H, int W, int S,

@@ -94,6 +94,8 @@ struct Options {
                                 //   weights through two L2s, activations through four, instead of one and eight): 22.3 -> 18.4 MB through the fabric per launch; same bits
     int attn_skip0 = 1;         // "attn_skip0" (diagnostic A/B): when chains overlap, the attention blocks fetch a frame's projected values only if its soft-max weight is
                                 //   not exactly zero (28.4 -> 23.5 MB per launch; same bits); 2 = also for a chain alone (one more round trip in the block: slower there), 0 = never
+    int early_stop = 0;         // "early_stop": free-running inference ends the decode loop once every clip of the call has crossed its stop token, plus the post-net's
+                                //   receptive margin (ES_MARGIN steps); frames at or past a clip's length come back as exact zeros (include/l2s.h)
     int infer_bf16 = 0;         // "infer_bf16": the bf16 leg of inference / evaluate: front-end conv, GEMMs and Conv1d stacks of encoder, prologue, post-net and
                                 //   voice tower with bf16 operands (fp32 accumulation); the recurrent loops, the fused ShuffleNet units and all statistics stay fp32
 };
@@ -368,9 +370,18 @@ struct SkinnyP {
     float* stop; int64_t ld_stop_b;    // stop[b*ld_stop_b]   (already offset to this step)
     const float* stop_const;           // [B]
     float* yfrag;                      // frag16, K = 80
+    int* es_ctl; int es_end;           // option "early_stop" (else null): the call's EsCtl block; the end step (minus S) to store once the last clip has crossed at this step
 };
+// Option "early_stop" on the launch-per-phase loop: a per-call control block in the call's own workspace.  The SK_MEL epilogue notes a clip's FIRST stop
+// crossing; the one that completes the count lowers the end step (ordinary vector atomics).  Every step kernel carries its step index and returns at its
+// top once that index is at or past the end - a uniform branch on a kernel argument that is null when the option is off.  Steps are kept RELATIVE to S
+// (end_rel = end - S <= 0, es_step = step - S < 0), so that one memset to zero arms the block: "run to S".
+struct EsCtl { int end_rel; int count; int crossed[1]; };      // crossed[B]
+constexpr int ES_POST_LAYERS = 5, ES_POST_TAPS = 5;
+constexpr int ES_MARGIN = ES_POST_LAYERS * (ES_POST_TAPS / 2);      // post-net frame j reads pre-post-net frames j - 10 .. j + 10 (five Conv1d layers, kernel 5, pad 2)
 constexpr int SKINNY_MAX_GROUP = 4;
-struct SkinnyBatch { SkinnyP p[SKINNY_MAX_GROUP]; int ntiles[SKINNY_MAX_GROUP]; int count; };
+struct SkinnyBatch { SkinnyP p[SKINNY_MAX_GROUP]; int ntiles[SKINNY_MAX_GROUP]; int count; const int* es_end; int es_step; };
+#define L2S_ES_RETURN(arg) do { if ((arg).es_end && (arg).es_step >= *(arg).es_end) return; } while (0)
 int launch_skinny(const SkinnyBatch& b, hipStream_t s, const char* name, const Options& o = Options());
 int launch_skx_planes(const float* Wf, int ntiles, int K, void* out, hipStream_t s);      // bf16 planes of a packed LSTM weight (SkinnyP::W3): ntiles * K * 16 * 6 bytes
 bool skinny_sum_supported(const Options& o);           // launches with SkinnyP::a_sum need the straight-line four-wave blocks: default operand batching, no stamped build
@@ -397,6 +408,7 @@ struct AttnP {
     const float* tau_c;
     float* cc_frag;                   // frag16, K = 256
     int B, T, m;
+    const int* es_end; int es_step;   // option "early_stop" (else null): the launch returns at once when es_step (step - S) >= *es_end (EsCtl::end_rel)
 };
 // attention role + second prenet layer in one grid (skinny.hip)
 int launch_step_attn(const AttnP& at, const SkinnyP& pre2, int pre2_tiles, hipStream_t s, int lds_values = 1, int skip0 = 0);
@@ -416,6 +428,8 @@ int launch_tile_rows(const float* src, int lds, float* dst, int ldd, int B, int 
 // (B,S,C) -> (B,C,S)
 int launch_transpose_bsc(const float* in, int B, int S, int C, float* out, hipStream_t s);
 int launch_output_lengths(const float* stop, int B, int S, int64_t* lengths, hipStream_t s);
+// option "early_stop": mel_post[b][:][j] = 0 and attn[b][j][:] = 0 (attn may be null) for j >= lengths[b]
+int launch_mask_by_lengths(const int64_t* lengths, int B, int S, int T, float* mel_post, float* attn, hipStream_t s);
 int launch_frame_window(const float* audio, int B, int N, int L, int n_fft, int hop, const float* window, float* frames, hipStream_t s);
 int launch_power(const float* spec, int lds, int64_t rows, int nf, float* power, int ldp, hipStream_t s);
 // stop_const[b] = dot(ecell[b], w[512:1024]) + bias

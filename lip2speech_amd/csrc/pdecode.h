@@ -24,6 +24,7 @@ struct PDecP {
     u64* xch;                             // exchange granules (zeroed before the launch)
     unsigned* status;                     // [0]: set to 1 by a workgroup whose poll timed out (every workgroup then leaves)
     int attn_logits, B, T, m, S;
+    int early;                            // option "early_stop": 0 = run S steps; else the margin (steps decoded past a clip's stop crossing, ES_MARGIN)
     int b0;                               // set by launch_pdecode: first clip of THIS launch (clips go two at a time)
     unsigned long long* ts; int ts_step;  // measurement (tools/pdecode_timeline.py): [256 workgroups][16] stamps of step ts_step, or null
 };

@@ -177,7 +177,15 @@ __device__ __forceinline__ float2 pd_w2(const float* W, int NC, int n, int k) {
 // (Measured and not kept: prenet2 computed once PER XCD - eight columns per workgroup, a plain store that stays in the XCD's L2, its 32 workgroups polling
 // it there, XCC ids and ranks taken at start - 9.24 against 9.33 us; the same loop on EIGHT waves, 512 threads with k = t - 9.41 against 9.48 at one clip,
 // 14.3 against 12.7 at two: a step is its four edges, 4 x ~1.75 us, plus ~2.4 us.)
-template <int NG, int V>
+// ES (option "early_stop"; the ES = false instantiation is the loop as it was): each clip leaves the step loop on its own.  The thread that owns the stop
+// column forms the stop logit of step s - 1 among phase 3's deferred sums of step s.  On the clip's FIRST crossing it stores the clip's end step
+// min(S, s + margin) to the clip's notice word (agent scope), then a release fence, and only then - in phase 4 of the same step, in program order -
+// publishes its h1' / c1' granules, which every workgroup of the clip polls in phase 1 of step s + 1.  The thread that polls exactly those granules (es_obs,
+// one per workgroup) reads the notice after its poll has succeeded and an acquire fence, and hands it to its workgroup through LDS across a barrier of the
+// same step: the order holds by construction (cdna_hip_programming.md section 6, guideline 16), not by the margin's slack.  All workgroups of the clip
+// therefore know the end by step s + 1 < end and leave at the top of step `end`, exactly where the full loop leaves at S: after the poll of the last
+// h1' / c1', which everybody has published - nobody waits for a workgroup that has left, and every wait is still a PdPoll.
+template <int NG, int V, bool ES = false>
 __global__ __launch_bounds__(PD_NT, 1) void pdecode_kernel(const PDecP p) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
     float* const qs = sm;                                   // [512]              q * tau
@@ -197,6 +205,12 @@ __global__ __launch_bounds__(PD_NT, 1) void pdecode_kernel(const PDecP p) {
     const int gc = p.b0 + g;                                // ... the clip's row in the caller's batch
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int T = p.T, M = p.m, S = p.S;
+    int Send = S;                                           // the clip's end step: S, or (ES) what the stop column's owner has announced
+    int* const es_note = reinterpret_cast<int*>(p.status) + 4 + g;      // ES: the clip's notice word (0 = none yet; zeroed with the exchange buffer every launch)
+    int* const es_lds = reinterpret_cast<int*>(vs + (T4 + M4) * 256);   // ES: the notice as the workgroup's observer read it (the launch's LDS is >= PD_LDS_MIN: room to spare)
+    constexpr int es_obs = V * (80 / V) + ((80 % V) >> 1);   // ES: the thread whose phase-1 poll covers the h1' granules the stop column's owner publishes (unit 2 cjv + cu of tid = 80 % V in workgroup 80 / V)
+    bool es_crossed = false;
+    int es_val = 0;
     u64* const X = p.xch;
     const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(X + (int64_t)(j % PD_MAXREP) * pd_rstride(NG), 0, pd_granules(NG) * 8, 0x00020000);      // this workgroup's replica
     const __amdgpu_buffer_rsrc_t rsall = __builtin_amdgcn_make_buffer_rsrc(X, 0, PD_MAXREP * pd_rstride(NG) * 8, 0x00020000);
@@ -313,13 +327,13 @@ __global__ __launch_bounds__(PD_NT, 1) void pdecode_kernel(const PDecP p) {
         __syncthreads();
     }
 
-    for (int s = 0; s <= S; ++s) {
+    for (int s = 0; s <= Send; ++s) {
         const unsigned tag_prev = (unsigned)s + 1u, tag_now = (unsigned)s + 2u;
         PD_STAMP(0);
         // ------------------------------------------------------------ phase 1
         float2 hy, cy;
         {
-            const float posv = (s < S && tid < 4 * V && fk < 2) ? p.pos[(int64_t)s * 512 + 2 * fjv + fk] : 0.f;      // requested before the poll, used after it
+            const float posv = (s < Send && tid < 4 * V && fk < 2) ? p.pos[(int64_t)s * 512 + 2 * fjv + fk] : 0.f;      // requested before the poll, used after it
             do {
                 const uint4 a = pd_load16(rs, gH1 + 2 * tid), c = pd_load16(rs, gC1 + 2 * tid);
                 const bool ok = a.y == tag_prev && a.w == tag_prev && c.y == tag_prev && c.w == tag_prev;
@@ -329,7 +343,13 @@ __global__ __launch_bounds__(PD_NT, 1) void pdecode_kernel(const PDecP p) {
             } while (true);
             if (poll.gave_up()) return;
             PD_STAMP(1);
-            if (s < S) {
+            if (s < Send) {
+                if constexpr (ES) {                         // the observer's poll has seen the owner's granules of step s - 1: what the owner stored before them is visible
+                    if (tid == es_obs) {
+                        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+                        es_val = __hip_atomic_load(es_note, PD_RLX);      // used after phase 2's logits: the load is in flight under the rest of this phase
+                    }
+                }
                 float v[4 * V];
 #pragma unroll
                 for (int b = 0; b < V; ++b) {
@@ -352,7 +372,7 @@ __global__ __launch_bounds__(PD_NT, 1) void pdecode_kernel(const PDecP p) {
                 rpar ^= 1;
             }
             PD_STAMP(3);
-            if (s < S && tid < 2 * V) {                     // W_hh0 h0 from phase 4 of the previous step, for phase 3 (redC is valid since this phase's barrier)
+            if (s < Send && tid < 2 * V) {                  // W_hh0 h0 from phase 4 of the previous step, for phase 3 (redC is valid since this phase's barrier)
 #pragma unroll
                 for (int q = 0; q < 4; ++q) l0hh[q] = PD_SUM4(redC, RD, 12 * cb + 4 * cu + q);
             }
@@ -368,11 +388,12 @@ __global__ __launch_bounds__(PD_NT, 1) void pdecode_kernel(const PDecP p) {
                 PD_WSUM(v, 12 * V, redB, RD);
             }
         }
-        if (s == S) {                                        // the last mel frame
+        if (s == Send) {                                     // the last mel frame
             __syncthreads();
+            const int last = ES ? s - 1 : S - 1;
             if (tid < V && mjv <= 80) {
                 const float x = PD_SUM4(redB, RD, 12 * tid + 8) + e_bfc;
-                if (mjv < 80) p.mel[((int64_t)gc * S + (S - 1)) * 80 + mjv] = x; else p.stop[(int64_t)gc * S + (S - 1)] = x + stopc;
+                if (mjv < 80) p.mel[((int64_t)gc * S + last) * 80 + mjv] = x; else p.stop[(int64_t)gc * S + last] = x + stopc;
             }
             break;
         }
@@ -432,7 +453,9 @@ __global__ __launch_bounds__(PD_NT, 1) void pdecode_kernel(const PDecP p) {
                 ca += pd_dpp<0xB1>(ca); ca += pd_dpp<0x4E>(ca); ca += pd_dpp<0x124>(ca); ca += pd_dpp<0x128>(ca);      // the 16 lanes of a content frame
                 if (cp == 0 && cf < M) sc[32 + cf] = ca;
             }
+            if constexpr (ES) { if (tid == es_obs) es_lds[0] = es_val; }
             __syncthreads();
+            if constexpr (ES) { const int e = es_lds[0]; if (e) Send = e; }      // e > s + 1 or e == S: no decision of this step changes (next written after three more barriers)
             PD_STAMP(6);
             if (o_role) ppre = pd_load16(rs, gP2 + xc);
             {   // every wave: softmax of its role's logits (lane = frame), then its threads' two columns of a @ V' / alpha @ value (decoder.py:414-419, 262-271)
@@ -499,6 +522,13 @@ __global__ __launch_bounds__(PD_NT, 1) void pdecode_kernel(const PDecP p) {
             if (s > 0 && tid < V && mjv <= 80) {
                 const float x = PD_SUM4(redB, RD, 12 * tid + 8) + e_bfc;
                 if (mjv < 80) p.mel[((int64_t)gc * S + (s - 1)) * 80 + mjv] = x; else p.stop[(int64_t)gc * S + (s - 1)] = x + stopc;
+                if constexpr (ES) {
+                    if (mjv == 80 && !es_crossed && x + stopc > 0.f) {      // the clip's first crossing (output_lengths_kernel's test), at step s - 1: end = min(S, (s - 1) + 1 + margin)
+                        es_crossed = true;
+                        __hip_atomic_store(es_note, min(S, s + p.early), PD_RLX);
+                        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");       // ... complete before this thread's phase-4 publish below
+                    }
+                }
             }
             if (tid < 2 * V) {
 #pragma unroll
@@ -712,7 +742,9 @@ static PdDevice* pd_device_locked() {
         if (fits) {
             (void)hipFuncSetAttribute(reinterpret_cast<const void*>(pdecode_kernel<1, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, PD_LDS_MAX);
             (void)hipFuncSetAttribute(reinterpret_cast<const void*>(pdecode_kernel<2, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, PD_LDS_MAX);
-            fits = pd_fits(pdecode_kernel<1, 2>, PD_LDS_MAX) && pd_fits(pdecode_kernel<2, 2>, PD_LDS_MAX) && pd_fits(pbilstm_kernel<1>, 0) && pd_fits(pbilstm_kernel<2>, 0);
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(pdecode_kernel<1, 2, true>), hipFuncAttributeMaxDynamicSharedMemorySize, PD_LDS_MAX);
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(pdecode_kernel<2, 2, true>), hipFuncAttributeMaxDynamicSharedMemorySize, PD_LDS_MAX);
+            fits = pd_fits(pdecode_kernel<1, 2>, PD_LDS_MAX) && pd_fits(pdecode_kernel<2, 2>, PD_LDS_MAX) && pd_fits(pdecode_kernel<1, 2, true>, PD_LDS_MAX) && pd_fits(pdecode_kernel<2, 2, true>, PD_LDS_MAX) && pd_fits(pbilstm_kernel<1>, 0) && pd_fits(pbilstm_kernel<2>, 0);
         }
         d.resident = fits;
         d.init = true;
@@ -782,7 +814,11 @@ int launch_pdecode(const PDecP& p, void* ws, int64_t ws_bytes, hipStream_t s) {
 #else
         constexpr int starve = 0;
 #endif
-        if (n == 1) hipLaunchKernelGGL((pdecode_kernel<1, 2>), dim3(PD_WG / 2 - starve), dim3(PD_NT), lds, s, q);
+        if (p.early) {      // option "early_stop": the instantiations whose clips leave the loop on their own
+            if (n == 1) hipLaunchKernelGGL((pdecode_kernel<1, 2, true>), dim3(PD_WG / 2 - starve), dim3(PD_NT), lds, s, q);
+            else hipLaunchKernelGGL((pdecode_kernel<2, 2, true>), dim3(PD_WG - starve), dim3(PD_NT), lds, s, q);
+        }
+        else if (n == 1) hipLaunchKernelGGL((pdecode_kernel<1, 2>), dim3(PD_WG / 2 - starve), dim3(PD_NT), lds, s, q);
         else hipLaunchKernelGGL((pdecode_kernel<2, 2>), dim3(PD_WG - starve), dim3(PD_NT), lds, s, q);
         hipLaunchKernelGGL(pdecode_guard_kernel, dim3(8), dim3(256), 0, s, q.status, q.mel, q.stop, q.attn, q.B * q.S * 80, q.B * q.S, q.attn ? q.B * q.S * q.T : 0, dv->timeouts);
         L2S_CHECK_HIP(hipGetLastError());

@@ -69,10 +69,21 @@ static int skinny_layout_of(const SkinnyP& p) {
     return 0;
 }
 
+// Every step kernel exists twice: ES = false is the kernel as it always was; ES = true (option "early_stop", launched when the batch carries a control
+// block) returns at its top once its step is at or past the call's end step.  Two symbols rather than one run-time null test: the test's kernel-argument
+// load would sit in front of every other argument load of every launch, option on or off.
+#define SK_UNPACK(...) __VA_ARGS__
+#define SK_ES_LAUNCH(es, NAME, TARGS, ...)                                                        \
+    do {                                                                                          \
+        if (es) hipLaunchKernelGGL((NAME<SK_UNPACK TARGS, true>), __VA_ARGS__);                   \
+        else hipLaunchKernelGGL((NAME<SK_UNPACK TARGS, false>), __VA_ARGS__);                     \
+    } while (0)
+
 // MAXC = chunks per wave the instance is unrolled for (K <= 128 * MAXC): the 24 operand registers per chunk pair are what sets the
 // kernel's VGPR count, so launches whose longest K is 512 / 1024 get their own, smaller instances
-template <int MAXC>
+template <int MAXC, bool ES = false>
 __global__ __launch_bounds__(512) void skinny_kernel(const SkinnyBatch batch) {
+    if constexpr (ES) L2S_ES_RETURN(batch);
     __shared__ float red[SK_RED_FLOATS];
     const int g = blockIdx.z;
     const SkinnyP& p = batch.p[g];
@@ -84,16 +95,18 @@ __global__ __launch_bounds__(512) void skinny_kernel(const SkinnyBatch batch) {
     else skinny_block<false, MAXC>(p, blockIdx.x, blockIdx.y, red, batch.ntiles[g]);
 }
 // instances with their operand loads in NB batches (options "skinny_split" = NB for K <= 1536, "skinny_split8" = NB for K <= 1024)
-template <int MAXC, int NB, int WPS>
+template <int MAXC, int NB, int WPS, bool ES = false>
 __global__ __launch_bounds__(512, WPS) void skinny_kernel_split(const SkinnyBatch batch) {
+    if constexpr (ES) L2S_ES_RETURN(batch);
     __shared__ float red[SK_RED_FLOATS];
     const int g = blockIdx.z;
     skinny_block<false, MAXC, false, SegRuntime, NB>(batch.p[g], blockIdx.x, blockIdx.y, red, batch.ntiles[g]);
 }
 
 // register-blocked instances for many batch rows (grouped decode, skinny_dev.h skinny_block_rc): RT x CT tiles of 16x16 per block
-template <int RT, int CT, int MAXC, int JB, int WPS, int DEPTH = 2>
+template <int RT, int CT, int MAXC, int JB, int WPS, int DEPTH = 2, bool ES = false>
 __global__ __launch_bounds__(512, WPS) void skinny_rc_kernel(const SkinnyBatch batch, int mts) {
+    if constexpr (ES) L2S_ES_RETURN(batch);
     __shared__ float red[SkRc<RT, CT>::RED_FLOATS];
     const int g = blockIdx.z;
     skinny_block_rc<RT, CT, MAXC, JB, DEPTH>(batch.p[g], blockIdx.x, blockIdx.y, red, batch.ntiles[g], mts);
@@ -105,22 +118,25 @@ template <> struct SkLay<2> { using T = SegLay<32, 32, 0, 0>; };
 template <> struct SkLay<3> { using T = SegLay<16, 16, 32, 32>; };
 template <> struct SkLay<5> { using T = SegLay<16, 16, 16, 32>; };
 template <> struct SkLay<6> { using T = SegLay<16, 16, 32, 0, true>; };
-template <int RT, int CT, int LAYID, int DEPTH, int WPS, bool IS_LSTM>
+template <int RT, int CT, int LAYID, int DEPTH, int WPS, bool IS_LSTM, bool ES = false>
 __global__ __launch_bounds__(512, WPS) void skinny_rcs_kernel(const SkinnyBatch batch, int mts) {
+    if constexpr (ES) L2S_ES_RETURN(batch);
     __shared__ float red[SkRc<RT, CT>::RED_FLOATS];
     const int g = blockIdx.z;
     skinny_block_rcs<RT, CT, typename SkLay<LAYID>::T, DEPTH, IS_LSTM>(batch.p[g], blockIdx.x, blockIdx.y, red, batch.ntiles[g], mts);
 }
 // four real waves per block (one per SIMD, each playing two K slices): skinny_block_rcs<..., NW = 4>
-template <int RT, int CT, int LAYID, int DEPTH, bool IS_LSTM>
+template <int RT, int CT, int LAYID, int DEPTH, bool IS_LSTM, bool ES = false>
 __global__ __launch_bounds__(256, 1) void skinny_rc4_kernel(const SkinnyBatch batch, int mts) {
+    if constexpr (ES) L2S_ES_RETURN(batch);
     __shared__ float red[SkRc<RT, CT>::RED_FLOATS];
     const int g = blockIdx.z;
     skinny_block_rcs<RT, CT, typename SkLay<LAYID>::T, DEPTH, IS_LSTM, false, 4>(batch.p[g], blockIdx.x, blockIdx.y, red, batch.ntiles[g], mts);
 }
 // the same LSTM blocks on the bf16 matrix cores (skinny_block_rcs<..., X3>): every group of the launch carries pre-split weight planes (SkinnyP::W3)
-template <int RT, int CT, int LAYID, int DEPTH>
+template <int RT, int CT, int LAYID, int DEPTH, bool ES = false>
 __global__ __launch_bounds__(256, 1) void skinny_rc4x_kernel(const SkinnyBatch batch, int mts) {
+    if constexpr (ES) L2S_ES_RETURN(batch);
     __shared__ float red[SkRc<RT, CT>::RED_FLOATS];
     const int g = blockIdx.z;
     skinny_block_rcs<RT, CT, typename SkLay<LAYID>::T, DEPTH, true, false, 4, true>(batch.p[g], blockIdx.x, blockIdx.y, red, batch.ntiles[g], mts);
@@ -129,16 +145,18 @@ __global__ __launch_bounds__(256, 1) void skinny_rc4x_kernel(const SkinnyBatch b
 // on ONE set of accumulators (skinny_block_rcs<.., SEQ>: same partial sums, same bits as the other forms) - so that two blocks share a CU: of one
 // launch (more than 256 blocks) or of two launch chains on different streams, whose kernels then OVERLAP instead of queueing (a block alone leaves
 // its CU's load path and matrix pipe idle two thirds of its lifetime: first-operand latency, reduction, store drain, launch boundary)
-template <int RT, int CT, int LAYID, int DEPTH>
+template <int RT, int CT, int LAYID, int DEPTH, bool ES = false>
 __global__ __launch_bounds__(256, 2) void skinny_rc4h_kernel(const SkinnyBatch batch, int mts) {
+    if constexpr (ES) L2S_ES_RETURN(batch);
     __shared__ float red[SkRc<RT, CT>::RED_FLOATS];
     const int g = blockIdx.z;
     L2S_BLOCK_STAMP_BEGIN();
     skinny_block_rcs<RT, CT, typename SkLay<LAYID>::T, DEPTH, true, false, 4, true, false, true>(batch.p[g], blockIdx.x, blockIdx.y, red, batch.ntiles[g], mts);
     L2S_BLOCK_STAMP_END(1u, batch.p[g].c_out);
 }
-template <int RT, int CT, int LAYID, int DEPTH>
+template <int RT, int CT, int LAYID, int DEPTH, bool ES = false>
 __global__ __launch_bounds__(512, 1) void skinny_rc8x_kernel(const SkinnyBatch batch, int mts) {      // the same on eight waves: the two waves of a SIMD alternate split VALU and MFMAs
+    if constexpr (ES) L2S_ES_RETURN(batch);
     __shared__ float red[SkRc<RT, CT>::RED_FLOATS];
     const int g = blockIdx.z;
     L2S_BLOCK_STAMP_BEGIN();
@@ -178,34 +196,34 @@ static bool launch_rc4(const SkinnyBatch& bl, int lay, int kind, int maxt, int m
     constexpr int HD = 3;       // operand slots in flight of the half-CU 4x2 form (four: its 256 registers spill)
     if constexpr (RT * CT >= 8) {       // the half-CU form exists for the 4x2 block; the smaller shapes already leave room beside them
         if (kind == 2 && x3 == 3 && (lay == 1 || lay == 2 || lay == 6)) {
-            if (lay == 1) hipLaunchKernelGGL((skinny_rc4h_kernel<RT, CT, 1, HD>), grid, blk, 0, s, bl, mts);
-            else if (lay == 2) hipLaunchKernelGGL((skinny_rc4h_kernel<RT, CT, 2, HD>), grid, blk, 0, s, bl, mts);
-            else hipLaunchKernelGGL((skinny_rc4h_kernel<RT, CT, 6, HD>), grid, blk, 0, s, bl, mts);
+            if (lay == 1) SK_ES_LAUNCH(bl.es_end, skinny_rc4h_kernel, (RT, CT, 1, HD), grid, blk, 0, s, bl, mts);
+            else if (lay == 2) SK_ES_LAUNCH(bl.es_end, skinny_rc4h_kernel, (RT, CT, 2, HD), grid, blk, 0, s, bl, mts);
+            else SK_ES_LAUNCH(bl.es_end, skinny_rc4h_kernel, (RT, CT, 6, HD), grid, blk, 0, s, bl, mts);
             return true;
         }
     }
     if (kind == 2 && x3 >= 2 && (lay == 1 || lay == 2 || lay == 6)) {
-        if (lay == 1) hipLaunchKernelGGL((skinny_rc8x_kernel<RT, CT, 1, DEPTH>), grid, dim3(512), 0, s, bl, mts);      // the BiLSTM recurrence (K = 512)
-        else if (lay == 2) hipLaunchKernelGGL((skinny_rc8x_kernel<RT, CT, 2, DEPTH>), grid, dim3(512), 0, s, bl, mts);
-        else hipLaunchKernelGGL((skinny_rc8x_kernel<RT, CT, 6, DEPTH>), grid, dim3(512), 0, s, bl, mts);
+        if (lay == 1) SK_ES_LAUNCH(bl.es_end, skinny_rc8x_kernel, (RT, CT, 1, DEPTH), grid, dim3(512), 0, s, bl, mts);      // the BiLSTM recurrence (K = 512)
+        else if (lay == 2) SK_ES_LAUNCH(bl.es_end, skinny_rc8x_kernel, (RT, CT, 2, DEPTH), grid, dim3(512), 0, s, bl, mts);
+        else SK_ES_LAUNCH(bl.es_end, skinny_rc8x_kernel, (RT, CT, 6, DEPTH), grid, dim3(512), 0, s, bl, mts);
         return true;
     }
     if (kind == 2 && x3 && (lay == 1 || lay == 2 || lay == 6)) {
-        if (lay == 1) hipLaunchKernelGGL((skinny_rc4x_kernel<RT, CT, 1, DEPTH>), grid, blk, 0, s, bl, mts);
-        else if (lay == 2) hipLaunchKernelGGL((skinny_rc4x_kernel<RT, CT, 2, DEPTH>), grid, blk, 0, s, bl, mts);
-        else hipLaunchKernelGGL((skinny_rc4x_kernel<RT, CT, 6, DEPTH>), grid, blk, 0, s, bl, mts);
+        if (lay == 1) SK_ES_LAUNCH(bl.es_end, skinny_rc4x_kernel, (RT, CT, 1, DEPTH), grid, blk, 0, s, bl, mts);
+        else if (lay == 2) SK_ES_LAUNCH(bl.es_end, skinny_rc4x_kernel, (RT, CT, 2, DEPTH), grid, blk, 0, s, bl, mts);
+        else SK_ES_LAUNCH(bl.es_end, skinny_rc4x_kernel, (RT, CT, 6, DEPTH), grid, blk, 0, s, bl, mts);
         return true;
     }
     if (kind == 2) {
-        if (lay == 1) hipLaunchKernelGGL((skinny_rc4_kernel<RT, CT, 1, DEPTH, true>), grid, blk, 0, s, bl, mts);
-        else if (lay == 2) hipLaunchKernelGGL((skinny_rc4_kernel<RT, CT, 2, DEPTH, true>), grid, blk, 0, s, bl, mts);
-        else if (lay == 3) hipLaunchKernelGGL((skinny_rc4_kernel<RT, CT, 3, DEPTH, true>), grid, blk, 0, s, bl, mts);
-        else if (lay == 5) hipLaunchKernelGGL((skinny_rc4_kernel<RT, CT, 5, DEPTH, true>), grid, blk, 0, s, bl, mts);
-        else if (lay == 6) hipLaunchKernelGGL((skinny_rc4_kernel<RT, CT, 6, DEPTH, true>), grid, blk, 0, s, bl, mts);
+        if (lay == 1) SK_ES_LAUNCH(bl.es_end, skinny_rc4_kernel, (RT, CT, 1, DEPTH, true), grid, blk, 0, s, bl, mts);
+        else if (lay == 2) SK_ES_LAUNCH(bl.es_end, skinny_rc4_kernel, (RT, CT, 2, DEPTH, true), grid, blk, 0, s, bl, mts);
+        else if (lay == 3) SK_ES_LAUNCH(bl.es_end, skinny_rc4_kernel, (RT, CT, 3, DEPTH, true), grid, blk, 0, s, bl, mts);
+        else if (lay == 5) SK_ES_LAUNCH(bl.es_end, skinny_rc4_kernel, (RT, CT, 5, DEPTH, true), grid, blk, 0, s, bl, mts);
+        else if (lay == 6) SK_ES_LAUNCH(bl.es_end, skinny_rc4_kernel, (RT, CT, 6, DEPTH, true), grid, blk, 0, s, bl, mts);
         else return false;
     } else if (kind == 1) {
-        if (lay == 1) hipLaunchKernelGGL((skinny_rc4_kernel<RT, CT, 1, DEPTH, false>), grid, blk, 0, s, bl, mts);
-        else if (lay == 2) hipLaunchKernelGGL((skinny_rc4_kernel<RT, CT, 2, DEPTH, false>), grid, blk, 0, s, bl, mts);
+        if (lay == 1) SK_ES_LAUNCH(bl.es_end, skinny_rc4_kernel, (RT, CT, 1, DEPTH, false), grid, blk, 0, s, bl, mts);
+        else if (lay == 2) SK_ES_LAUNCH(bl.es_end, skinny_rc4_kernel, (RT, CT, 2, DEPTH, false), grid, blk, 0, s, bl, mts);
         else return false;
     } else return false;
     return true;
@@ -224,14 +242,14 @@ template <int RT, int CT, int DEPTH>
 static bool launch_rcs(const SkinnyBatch& bl, int lay, int kind, int maxt, int mts, hipStream_t s) {
     const dim3 grid((maxt + CT - 1) / CT, (mts + RT - 1) / RT, bl.count), blk(512);
     if (kind == 2) {
-        if (lay == 1) hipLaunchKernelGGL((skinny_rcs_kernel<RT, CT, 1, DEPTH, 2, true>), grid, blk, 0, s, bl, mts);
-        else if (lay == 2) hipLaunchKernelGGL((skinny_rcs_kernel<RT, CT, 2, DEPTH, 2, true>), grid, blk, 0, s, bl, mts);
-        else if (lay == 3) hipLaunchKernelGGL((skinny_rcs_kernel<RT, CT, 3, DEPTH, 2, true>), grid, blk, 0, s, bl, mts);
-        else if (lay == 5) hipLaunchKernelGGL((skinny_rcs_kernel<RT, CT, 5, DEPTH, 2, true>), grid, blk, 0, s, bl, mts);
+        if (lay == 1) SK_ES_LAUNCH(bl.es_end, skinny_rcs_kernel, (RT, CT, 1, DEPTH, 2, true), grid, blk, 0, s, bl, mts);
+        else if (lay == 2) SK_ES_LAUNCH(bl.es_end, skinny_rcs_kernel, (RT, CT, 2, DEPTH, 2, true), grid, blk, 0, s, bl, mts);
+        else if (lay == 3) SK_ES_LAUNCH(bl.es_end, skinny_rcs_kernel, (RT, CT, 3, DEPTH, 2, true), grid, blk, 0, s, bl, mts);
+        else if (lay == 5) SK_ES_LAUNCH(bl.es_end, skinny_rcs_kernel, (RT, CT, 5, DEPTH, 2, true), grid, blk, 0, s, bl, mts);
         else return false;
     } else if (kind == 1) {
-        if (lay == 1) hipLaunchKernelGGL((skinny_rcs_kernel<RT, CT, 1, DEPTH, 2, false>), grid, blk, 0, s, bl, mts);
-        else if (lay == 2) hipLaunchKernelGGL((skinny_rcs_kernel<RT, CT, 2, DEPTH, 2, false>), grid, blk, 0, s, bl, mts);
+        if (lay == 1) SK_ES_LAUNCH(bl.es_end, skinny_rcs_kernel, (RT, CT, 1, DEPTH, 2, false), grid, blk, 0, s, bl, mts);
+        else if (lay == 2) SK_ES_LAUNCH(bl.es_end, skinny_rcs_kernel, (RT, CT, 2, DEPTH, 2, false), grid, blk, 0, s, bl, mts);
         else return false;
     } else return false;
     return true;
@@ -255,26 +273,26 @@ static void launch_rc(const SkinnyBatch& bl, int cls, int maxt, int mts, hipStre
         // (15): 19.9; 2 / 4: the two-chunk batches, two in flight, of round 2.  (Two 2x2 blocks SHARING a CU - one-chunk batches, three in flight,
         // 118 VGPRs - are slower, 21.2 us: the same CU then pulls 786 KB instead of 590 KB; what bounds these launches is bytes per CU.)
         if (rc_jb == 2 || rc_jb == 4) {
-            if (cls == 4) hipLaunchKernelGGL((skinny_rc_kernel<RT, CT, 4, 2, 2>), grid, blk, 0, s, bl, mts);
-            else if (cls == 8) hipLaunchKernelGGL((skinny_rc_kernel<RT, CT, 8, 2, 2>), grid, blk, 0, s, bl, mts);
-            else hipLaunchKernelGGL((skinny_rc_kernel<RT, CT, 12, 2, 2>), grid, blk, 0, s, bl, mts);
+            if (cls == 4) SK_ES_LAUNCH(bl.es_end, skinny_rc_kernel, (RT, CT, 4, 2, 2, 2), grid, blk, 0, s, bl, mts);
+            else if (cls == 8) SK_ES_LAUNCH(bl.es_end, skinny_rc_kernel, (RT, CT, 8, 2, 2, 2), grid, blk, 0, s, bl, mts);
+            else SK_ES_LAUNCH(bl.es_end, skinny_rc_kernel, (RT, CT, 12, 2, 2, 2), grid, blk, 0, s, bl, mts);
         } else if (rc_jb == 15) {
-            if (cls == 4) hipLaunchKernelGGL((skinny_rc_kernel<RT, CT, 4, 1, 2, 4>), grid, blk, 0, s, bl, mts);
-            else if (cls == 8) hipLaunchKernelGGL((skinny_rc_kernel<RT, CT, 8, 1, 2, 5>), grid, blk, 0, s, bl, mts);
-            else hipLaunchKernelGGL((skinny_rc_kernel<RT, CT, 12, 1, 2, 5>), grid, blk, 0, s, bl, mts);
+            if (cls == 4) SK_ES_LAUNCH(bl.es_end, skinny_rc_kernel, (RT, CT, 4, 1, 2, 4), grid, blk, 0, s, bl, mts);
+            else if (cls == 8) SK_ES_LAUNCH(bl.es_end, skinny_rc_kernel, (RT, CT, 8, 1, 2, 5), grid, blk, 0, s, bl, mts);
+            else SK_ES_LAUNCH(bl.es_end, skinny_rc_kernel, (RT, CT, 12, 1, 2, 5), grid, blk, 0, s, bl, mts);
         } else {
-            if (cls == 4) hipLaunchKernelGGL((skinny_rc_kernel<RT, CT, 4, 1, 2, 4>), grid, blk, 0, s, bl, mts);
-            else if (cls == 8) hipLaunchKernelGGL((skinny_rc_kernel<RT, CT, 8, 1, 2, 4>), grid, blk, 0, s, bl, mts);
-            else hipLaunchKernelGGL((skinny_rc_kernel<RT, CT, 12, 1, 2, 4>), grid, blk, 0, s, bl, mts);
+            if (cls == 4) SK_ES_LAUNCH(bl.es_end, skinny_rc_kernel, (RT, CT, 4, 1, 2, 4), grid, blk, 0, s, bl, mts);
+            else if (cls == 8) SK_ES_LAUNCH(bl.es_end, skinny_rc_kernel, (RT, CT, 8, 1, 2, 4), grid, blk, 0, s, bl, mts);
+            else SK_ES_LAUNCH(bl.es_end, skinny_rc_kernel, (RT, CT, 12, 1, 2, 4), grid, blk, 0, s, bl, mts);
         }
     } else if (rc_jb == 4) {
-        if (cls == 4) hipLaunchKernelGGL((skinny_rc_kernel<RT, CT, 4, 4, 2>), grid, blk, 0, s, bl, mts);
-        else if (cls == 8) hipLaunchKernelGGL((skinny_rc_kernel<RT, CT, 8, 4, 2>), grid, blk, 0, s, bl, mts);
-        else hipLaunchKernelGGL((skinny_rc_kernel<RT, CT, 12, 4, 2>), grid, blk, 0, s, bl, mts);
+        if (cls == 4) SK_ES_LAUNCH(bl.es_end, skinny_rc_kernel, (RT, CT, 4, 4, 2, 2), grid, blk, 0, s, bl, mts);
+        else if (cls == 8) SK_ES_LAUNCH(bl.es_end, skinny_rc_kernel, (RT, CT, 8, 4, 2, 2), grid, blk, 0, s, bl, mts);
+        else SK_ES_LAUNCH(bl.es_end, skinny_rc_kernel, (RT, CT, 12, 4, 2, 2), grid, blk, 0, s, bl, mts);
     } else {
-        if (cls == 4) hipLaunchKernelGGL((skinny_rc_kernel<RT, CT, 4, 2, 2>), grid, blk, 0, s, bl, mts);
-        else if (cls == 8) hipLaunchKernelGGL((skinny_rc_kernel<RT, CT, 8, 2, 2>), grid, blk, 0, s, bl, mts);
-        else hipLaunchKernelGGL((skinny_rc_kernel<RT, CT, 12, 2, 2>), grid, blk, 0, s, bl, mts);
+        if (cls == 4) SK_ES_LAUNCH(bl.es_end, skinny_rc_kernel, (RT, CT, 4, 2, 2, 2), grid, blk, 0, s, bl, mts);
+        else if (cls == 8) SK_ES_LAUNCH(bl.es_end, skinny_rc_kernel, (RT, CT, 8, 2, 2, 2), grid, blk, 0, s, bl, mts);
+        else SK_ES_LAUNCH(bl.es_end, skinny_rc_kernel, (RT, CT, 12, 2, 2, 2), grid, blk, 0, s, bl, mts);
     }
 }
 
@@ -305,8 +323,9 @@ __device__ __forceinline__ void flat_xcd_map(int b, int local, int nc, int nr, i
 }
 // One instance per pair of shapes (S8 for the K <= 1024 groups, S4 for the K <= 512 groups; RT * 10 + CT): an instance that carries every
 // shape is 60 KB of code and pays ~2.5 us of instruction fetch per launch.
-template <int S8, int S4, int STATIC = 0, bool TIMED = false>
+template <int S8, int S4, int STATIC = 0, bool TIMED = false, bool ES = false>
 __global__ __launch_bounds__(STATIC == 2 ? 256 : 512, STATIC == 2 ? 1 : 2) void skinny_flat_kernel(const SkinnyBatch batch, const SkinnyFlat fl, int mts, unsigned long long* ts = nullptr) {
+    if constexpr (ES) L2S_ES_RETURN(batch);
     constexpr int R8 = S8 / 10, C8 = S8 % 10, R4 = S4 / 10, C4 = S4 % 10;
     constexpr int RED = SkRc<R8, C8>::RED_FLOATS > SkRc<R4, C4>::RED_FLOATS ? SkRc<R8, C8>::RED_FLOATS : SkRc<R4, C4>::RED_FLOATS;
     __shared__ float red[RED];
@@ -385,9 +404,9 @@ static void launch_flat(const SkinnyBatch& bl, const SkinnyFlat& fl, int mts, hi
         if constexpr (S8 == 22 && S4 == 42) { hipLaunchKernelGGL((skinny_flat_kernel<S8, S4, 1, true>), dim3(fl.first[SKINNY_MAX_GROUP]), dim3(512), 0, s, bl, fl, mts, g_flat_ts); return; }
     }
 #endif
-    if (stat == 2) hipLaunchKernelGGL((skinny_flat_kernel<S8, S4, 2>), dim3(fl.first[SKINNY_MAX_GROUP]), dim3(256), 0, s, bl, fl, mts, (unsigned long long*)nullptr);
-    else if (stat == 1) hipLaunchKernelGGL((skinny_flat_kernel<S8, S4, 1>), dim3(fl.first[SKINNY_MAX_GROUP]), dim3(512), 0, s, bl, fl, mts, (unsigned long long*)nullptr);
-    else hipLaunchKernelGGL((skinny_flat_kernel<S8, S4, 0>), dim3(fl.first[SKINNY_MAX_GROUP]), dim3(512), 0, s, bl, fl, mts, (unsigned long long*)nullptr);
+    if (stat == 2) SK_ES_LAUNCH(bl.es_end, skinny_flat_kernel, (S8, S4, 2, false), dim3(fl.first[SKINNY_MAX_GROUP]), dim3(256), 0, s, bl, fl, mts, (unsigned long long*)nullptr);
+    else if (stat == 1) SK_ES_LAUNCH(bl.es_end, skinny_flat_kernel, (S8, S4, 1, false), dim3(fl.first[SKINNY_MAX_GROUP]), dim3(512), 0, s, bl, fl, mts, (unsigned long long*)nullptr);
+    else SK_ES_LAUNCH(bl.es_end, skinny_flat_kernel, (S8, S4, 0, false), dim3(fl.first[SKINNY_MAX_GROUP]), dim3(512), 0, s, bl, fl, mts, (unsigned long long*)nullptr);
 }
 
 #ifdef L2S_DIAG
@@ -515,12 +534,12 @@ int launch_skinny(const SkinnyBatch& b, hipStream_t s, const char* name, const O
     else if (shape == 22) launch_rc<2, 2>(bl, cls, maxt, mts, s, o.rc_jb, rc_lay, rc_kind, x3);
     else if (shape == 21) launch_rc<2, 1>(bl, cls, maxt, mts, s, o.rc_jb, rc_lay, rc_kind, x3);
     else if (any_sum) L2S_REQUIRE(false, "skinny: no block form of this launch sums u = prenet + o in its loader (SkinnyP::a_sum would be ignored)");
-    else if (cls == 4) hipLaunchKernelGGL(skinny_kernel<4>, dim3(maxt, mts, b.count), dim3(512), 0, s, bl);
-    else if (cls == 8 && o.skinny_split8 == 2) hipLaunchKernelGGL((skinny_kernel_split<8, 2, 8>), dim3(maxt, mts, b.count), dim3(512), 0, s, bl);
-    else if (cls == 8) hipLaunchKernelGGL(skinny_kernel<8>, dim3(maxt, mts, b.count), dim3(512), 0, s, bl);
-    else if (cls == 12 && o.skinny_split == 2) hipLaunchKernelGGL((skinny_kernel_split<12, 2, 6>), dim3(maxt, mts, b.count), dim3(512), 0, s, bl);
-    else if (cls == 12 && o.skinny_split == 3) hipLaunchKernelGGL((skinny_kernel_split<12, 3, 8>), dim3(maxt, mts, b.count), dim3(512), 0, s, bl);
-    else hipLaunchKernelGGL(skinny_kernel<12>, dim3(maxt, mts, b.count), dim3(512), 0, s, bl);
+    else if (cls == 4) SK_ES_LAUNCH(bl.es_end, skinny_kernel, (4), dim3(maxt, mts, b.count), dim3(512), 0, s, bl);
+    else if (cls == 8 && o.skinny_split8 == 2) SK_ES_LAUNCH(bl.es_end, skinny_kernel_split, (8, 2, 8), dim3(maxt, mts, b.count), dim3(512), 0, s, bl);
+    else if (cls == 8) SK_ES_LAUNCH(bl.es_end, skinny_kernel, (8), dim3(maxt, mts, b.count), dim3(512), 0, s, bl);
+    else if (cls == 12 && o.skinny_split == 2) SK_ES_LAUNCH(bl.es_end, skinny_kernel_split, (12, 2, 6), dim3(maxt, mts, b.count), dim3(512), 0, s, bl);
+    else if (cls == 12 && o.skinny_split == 3) SK_ES_LAUNCH(bl.es_end, skinny_kernel_split, (12, 3, 8), dim3(maxt, mts, b.count), dim3(512), 0, s, bl);
+    else SK_ES_LAUNCH(bl.es_end, skinny_kernel, (12), dim3(maxt, mts, b.count), dim3(512), 0, s, bl);
     L2S_CHECK_HIP(hipGetLastError());
     return 0;
 }
@@ -539,10 +558,11 @@ struct StepB {
 };
 
 constexpr int ATT_PRE2_MAXC = 2;      // prenet layer 2: K = 256 = 16 * 8 waves * 2 chunks
-template <bool VL, bool SKIP0 = false>
+template <bool VL, bool SKIP0 = false, bool ES = false>
 __global__ __launch_bounds__(512) void step_attn_kernel(const StepB sb) {
     constexpr int SMF = ATT_SM_FLOATS + (VL && !SKIP0 ? ATT_VLDS_FLOATS : 0);
     __shared__ __attribute__((aligned(16))) float sm[SMF > SK_RED_FLOATS ? SMF : SK_RED_FLOATS];
+    if constexpr (ES) L2S_ES_RETURN(sb.at);
     const int nb = sb.at.B, ptiles = sb.pre2_tiles;
     L2S_PIN_S("s"(nb), "s"(ptiles));
     const int bid = blockIdx.x;
@@ -595,9 +615,9 @@ int launch_step_attn(const AttnP& at, const SkinnyP& pre2, int pre2_tiles, hipSt
     if (g_attn_ts && vl) hipLaunchKernelGGL(step_attn_timed_kernel, dim3(2 * at.B + pre2_tiles * sb.mts), dim3(512), 0, s, sb, g_attn_ts);
     else
 #endif
-    if (vl && skip0 && (skip0 >= 2 || chains_hint() >= 2)) hipLaunchKernelGGL((step_attn_kernel<true, true>), dim3(2 * at.B + pre2_tiles * sb.mts), dim3(512), 0, s, sb);
-    else if (vl) hipLaunchKernelGGL(step_attn_kernel<true>, dim3(2 * at.B + pre2_tiles * sb.mts), dim3(512), 0, s, sb);
-    else hipLaunchKernelGGL(step_attn_kernel<false>, dim3(2 * at.B + pre2_tiles * sb.mts), dim3(512), 0, s, sb);
+    if (vl && skip0 && (skip0 >= 2 || chains_hint() >= 2)) SK_ES_LAUNCH(sb.at.es_end, step_attn_kernel, (true, true), dim3(2 * at.B + pre2_tiles * sb.mts), dim3(512), 0, s, sb);
+    else if (vl) SK_ES_LAUNCH(sb.at.es_end, step_attn_kernel, (true, false), dim3(2 * at.B + pre2_tiles * sb.mts), dim3(512), 0, s, sb);
+    else SK_ES_LAUNCH(sb.at.es_end, step_attn_kernel, (false, false), dim3(2 * at.B + pre2_tiles * sb.mts), dim3(512), 0, s, sb);
     L2S_CHECK_HIP(hipGetLastError());
     return 0;
 }

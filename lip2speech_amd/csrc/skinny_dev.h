@@ -52,6 +52,15 @@ __device__ __forceinline__ float act_apply(float v, int act, const float* actw, 
     return v;
 }
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
+// option "early_stop" (SkinnyP::es_ctl, else null): the SK_MEL epilogue notes clip b's FIRST stop crossing (the test of output_lengths_kernel: logit > 0);
+// the thread that completes the count stores the end step.  The end it stores lies past the step of every launch that can be in progress, so a block
+// that reads the old or the new value at its top takes the same branch.
+__device__ __forceinline__ void sk_note_stop(const SkinnyP& p, int b, float logit) {
+    if (p.es_ctl && logit > 0.f) {
+        EsCtl* const c = reinterpret_cast<EsCtl*>(p.es_ctl);
+        if (atomicExch(&c->crossed[b], 1) == 0 && atomicAdd(&c->count, 1) + 1 == p.B) atomicMin(&c->end_rel, p.es_end);
+    }
+}
 
 // One block (8 waves): output tile `tile` (16 columns) x batch tile `mt` (16 rows).  Wave w owns the K chunks
 // c = w, w+8, w+16, ...; ALL of its operand loads (<= 12 A + 12 W float4 per lane) are issued before the first MFMA so
@@ -279,6 +288,7 @@ __device__ __forceinline__ void skinny_block(const SkinnyP& p, int tile, int mt,
             if (p.yfrag) p.yfrag[frag16_index(b, np, 80)] = v;
         } else if (np == 80) {
             p.stop[(int64_t)b * p.ld_stop_b] = v + p.stop_const[b];
+            sk_note_stop(p, b, v + p.stop_const[b]);
         }
         return;
     }
@@ -478,6 +488,7 @@ __device__ __forceinline__ void skinny_block_rc(const SkinnyP& p, int tp, int mg
                 if (p.yfrag) p.yfrag[frag16_index(b, np, 80)] = v;
             } else if (np == 80) {
                 p.stop[(int64_t)b * p.ld_stop_b] = v + p.stop_const[b];
+                sk_note_stop(p, b, v + p.stop_const[b]);
             }
             continue;
         }
@@ -801,6 +812,7 @@ __device__ __forceinline__ void skinny_block_rcs(const SkinnyP& p, int tp, int m
                     if (p.yfrag) p.yfrag[frag16_index(b, np, 80)] = v;
                 } else if (np == 80) {
                     p.stop[(int64_t)b * p.ld_stop_b] = v + p.stop_const[b];
+                    sk_note_stop(p, b, v + p.stop_const[b]);
                 }
                 continue;
             }

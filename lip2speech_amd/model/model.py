@@ -8,6 +8,8 @@ prologue, 300-step loop and post-net enqueued back to back on the current stream
 """
 from __future__ import annotations
 
+from typing import Optional
+
 import torch
 import torch.nn.functional as F
 from torch import nn
@@ -234,13 +236,23 @@ class Lip2Speech(NativeBacked):
             return item[:-1], item[-1]
         return item, {}
 
-    def inference_many(self, calls, group: int = 8, n_inflight: int = 3):
+    def set_early_stop(self, early_stop: Optional[bool]) -> None:
+        """Option "early_stop" of this model's native handle (include/l2s.h): `None` leaves it alone.  The option is per MODEL, not per call: a
+        model shared by several threads (`inference_many`'s chains, a serving pool) should set it once, before the threads start."""
+        if early_stop is not None:
+            self.native_model().set_option("early_stop", 1 if early_stop else 0)
+
+    def inference_many(self, calls, group: int = 8, n_inflight: int = 3, early_stop: Optional[bool] = None):
         """`inference` over a stream of batches - the loop of demo.py:60-90 - with `group` batches advanced per launch chain
         (`l2s_inference_multi`) and `n_inflight` chains on the GPU at once.  `calls` is any iterable (e.g. a generator over a DataLoader) of
         argument tuples `(video_frames, face_frames[, speaker_embedding[, return_attention_map[, gumbel_noise]]])`, optionally ending in a
         dict of keyword arguments; inputs may live on the host (they are copied on the pool's copy stream, one group ahead).  Yields, in
-        order, exactly what `inference(*call)` returns for each - bit-identical when the Gumbel noise is supplied."""
+        order, exactly what `inference(*call)` returns for each - bit-identical when the Gumbel noise is supplied.
+        `early_stop`: `None` leaves the model's option alone, `True` / `False` sets it ONCE for the model before the first chain starts (every
+        chain of the pool drives this one model): the decode loop of a group then ends once all its clips have stopped, and frames at or
+        past a clip's length are exact zeros (`inference`)."""
         self.native_model()
+        self.set_early_stop(early_stop)
         prep = lambda item: (lambda a, k: self._inference_job(*a, **k))(*self._call(item))      # noqa: E731
         return self.pool(group, n_inflight).imap(calls, prep)
 
@@ -286,7 +298,13 @@ class Lip2Speech(NativeBacked):
                                                              gumbel_noise.detach().to(torch.float32).contiguous(), melspecs, mask if any(mask) else None, drop)
         return [mel, mel_post, stop, emb, attn, dis, video_lengths]
 
-    def inference(self, video_frames, face_frames, speaker_embedding=None, return_attention_map=False, gumbel_noise=None):
+    def inference(self, video_frames, face_frames, speaker_embedding=None, return_attention_map=False, gumbel_noise=None, early_stop=None):
+        """The reference's `Lip2Speech.inference` (model.py:43-59).  `early_stop` (not in the reference; default `None` = leave the model's option
+        "early_stop" as it is, off unless set): `True` / `False` sets the option for this MODEL before the call.  On: the decode loop ends once
+        every clip of the batch has crossed its stop token (plus the post-net's 10-frame margin) instead of running all `max_decoder_steps`;
+        `output_lengths` and every frame below a clip's length are what the full loop gives, the frames at or past it - which every caller
+        drops - come back as exact zeros.  A model shared by threads should set it once (`set_early_stop`), not per call."""
+        self.set_early_stop(early_stop)
         with torch.no_grad():
             emb = self._speaker(face_frames, speaker_embedding)
             B, _, T, _, _ = video_frames.shape

@@ -75,9 +75,12 @@ class InflightPool:
     `tensors` / `keys`: the checkpoint tensors as for `NativeModel.load`.  `map(batches)` takes a list of (video, emb, gumbel) and returns
     the (mel_post, lengths, attn) tuples in order."""
 
-    def __init__(self, tensors: Dict[str, torch.Tensor] = None, keys=None, n_inflight: int = 2, device=None, group: int = 1, model=None):
+    def __init__(self, tensors: Dict[str, torch.Tensor] = None, keys=None, n_inflight: int = 2, device=None, group: int = 1, model=None,
+                 early_stop: bool = None):
         """`model`: an already packed `NativeModel` to share (then `tensors` is not needed) - e.g. a second pool with another shape of
-        concurrency over the same weight blob."""
+        concurrency over the same weight blob.  `early_stop`: `None` leaves the model's option "early_stop" alone, else it is set here, once,
+        before any chain starts; under `run_sharded` every rank sets it on its own model - the stop decision is made on each rank's device
+        and needs no collective."""
         from . import native
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         if n_inflight > 4:
@@ -92,6 +95,8 @@ class InflightPool:
             model = native.NativeModel()              # ONE packed blob for every chain
             model.load(tensors, list(tensors.keys()) if keys is None else list(keys))
         self.model = model
+        if early_stop is not None:
+            model.set_option("early_stop", 1 if early_stop else 0)
         self.streams = [torch.cuda.Stream(device=self.device) for _ in range(max(1, n_inflight))]
         self.copy_stream = None                       # created on first use of map(prepare=...): ONE stream for every chain's input staging
         self._stats_lock = threading.Lock()
