@@ -24,7 +24,8 @@
  *   - every function returns 0 on success, non-zero on error; l2s_last_error() gives
  *     the message for the calling thread.
  *   - lengths are ignored exactly as in the reference (no key masking, zero-padded
- *     frames are encoded and attended like real ones; decoder.py:320-379).
+ *     frames are encoded and attended like real ones; decoder.py:320-379) - except by
+ *     the *_masked entry points ("per-clip video lengths" below), which are opt-in.
  */
 #ifndef L2S_H
 #define L2S_H
@@ -181,6 +182,42 @@ int l2s_inference(l2s_model* m, const float* video, const float* emb, const floa
                   int B, int T, int H, int W, int S,
                   float* mel_post, int64_t* lengths, float* attn,
                   void* ws, int64_t ws_bytes, void* stream);
+
+/* ---- per-clip video lengths: padded clips decode as they would alone -----------------------------------------------------------------------------
+ * The entry points above ignore lengths as the reference does: a clip's speech then depends on what it was padded to.  The *_masked forms take one
+ * more argument, `video_lengths`: a HOST array of B int32 (the collate holds the lengths on the host; the library plans its launches from them and
+ * carries what the kernels need to the device in kernel arguments on `stream` - the array may be freed when the call returns).
+ *
+ * Contract.  The batch is B clips ZERO-padded to T: frames t >= len_b of clip b must be EXACTLY 0.0f, as l2s_normalise_pad_frames and the reference's
+ * train_collate_fn_pad produce (the front-end's temporal padding is zeros too, which is what makes a padded clip's real frames see what a solo clip
+ * sees; non-zero pad frames leak into the last two real frames of a clip).  len_b in [7, T]; anything else is an error (l2s_last_error names the row).
+ * Row b of every output is then what the same entry point returns for clip b ALONE at T = len_b - mel_post, the pre-post-net mel, stop logits,
+ * output lengths, attention at t < len_b - with the same order of the same fp32 sums wherever the kernel choice does not depend on the row count
+ * (DESIGN.md section 8), rounding-level otherwise.  Attention columns t >= len_b are exactly 0; attention LOGITS (l2s_forward_eval_masked,
+ * attn_logits != 0) are -INFINITY there, so that the caller's softmax over T (train.py:244) gives those columns exactly 0 as well.
+ * Content slots: m_b = l2s_min_T(len_b) <= m = l2s_min_T(T).  Clip b uses the FIRST m_b of its m Gumbel rows (rows b*m .. b*m + m_b - 1 of `gumbel`)
+ * and of its m content_dis rows; its other content_dis rows are zeros.
+ * State buffer of the staged pair: rows t >= len_b of L2S_ST_ENC are zeros, of L2S_ST_K / _V / _VP unspecified (finite, never read by a masked loop);
+ * content keys / values of slots >= m_b unspecified / zero.  A state written by l2s_decoder_prologue_masked goes to l2s_decode_steps_masked with the
+ * same lengths.
+ * Options: masked calls always take the launch-per-phase route - "persist_decode" and "use_graph" do not apply to them; "early_stop",
+ * "fold_step_weights" and "infer_bf16" compose.  There is no masked form of the grouped (*_multi) or training (l2s_train_*) entry points.
+ * Workspace: l2s_workspace_bytes_masked (the unmasked size plus the device length table), for all four calls.
+ * l2s_masked_bilstm_plan: the launch plan of the BiLSTM recurrence, a pure host function.  The recurrence stays T uniform launches (step s reads frame
+ * s forward and frame T-1-s backward); capture_steps = the steps AFTER which a row kernel hands over the forward finals of the clips that ended there
+ * (s = len_b - 1), reset_steps = the steps BEFORE which a row kernel restarts, from the site embedding, the backward rows of the shorter clips whose
+ * last frame is read there (s = T - len_b, len_b < T).  Both ascending without repeats, at most B entries each. */
+int64_t l2s_workspace_bytes_masked(int B, int T, int H, int W, int S);
+int l2s_masked_bilstm_plan(const int32_t* video_lengths, int B, int T, int32_t* capture_steps, int32_t* reset_steps, int* n_capture, int* n_reset);
+int l2s_inference_masked(l2s_model* m, const float* video, const float* emb, const float* gumbel, int B, int T, int H, int W, int S,
+                         float* mel_post, int64_t* lengths, float* attn, void* ws, int64_t ws_bytes, void* stream, const int32_t* video_lengths);
+int l2s_forward_eval_masked(l2s_model* m, const float* video, const float* emb, const float* gumbel, int B, int T, int H, int W, int S,
+                            const float* teacher, const uint8_t* teacher_mask, float* mel_cf, float* mel_post, float* stop, float* attn_logits,
+                            float* content_dis, void* ws, int64_t ws_bytes, void* stream, const int32_t* video_lengths);
+int l2s_decoder_prologue_masked(l2s_model* m, const float* vis, const float* emb, const float* gumbel, int B, int T, float* state,
+                                float* content_dis, void* ws, int64_t ws_bytes, void* stream, const int32_t* video_lengths);
+int l2s_decode_steps_masked(l2s_model* m, float* state, int B, int T, int S, const float* teacher, const uint8_t* teacher_mask, float* mel,
+                            float* stop, float* attn, int attn_logits, void* ws, int64_t ws_bytes, void* stream, const int32_t* video_lengths);
 
 /* Grouped inference ("advance G independent batches per launch"): G batches of B clips each - separate tensors, wherever the caller's
  * loader put them - run as rows g*B .. g*B+B-1 of ONE launch chain on ONE weight blob: the 300 x 4 step launches, the BiLSTM recurrence and

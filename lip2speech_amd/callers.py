@@ -11,6 +11,10 @@ The inference-side loops run on the GROUPED path by default: the loader's batche
 
 The reference then vocodes the mels (InverseMelScale + Griffin-Lim, torchaudio) and scores ESTOI (pystoi); both are
 third-party, stochastic and out of scope here - these functions return the mels.
+
+``honour_lengths=True`` (off by default, as the reference ignores lengths): the loader's ``video_lengths`` are passed on to the length-masked entry
+points (``l2s_inference_masked`` / ``l2s_forward_eval_masked``), so a clip's output no longer depends on what it was padded to.  Those have no
+grouped form: the batches then run one call each, in loader order.
 """
 from __future__ import annotations
 
@@ -22,37 +26,43 @@ from . import native
 
 
 def demo_clip(net, batch, speaker_encoder=None, speaker_embedding: Optional[torch.Tensor] = None, device="cuda", encoding: str = "voice",
-              early_stop: bool = False):
+              early_stop: bool = False, honour_lengths: bool = False):
     """``batch`` = one item of ``DataLoader(ds, batch_size=1, collate_fn=test_collate_fn_pad)`` (one iteration of demo.py:60-90): the direct
     ``net.inference`` call, which for one clip takes the library's latency form (the decode loop as one persistent launch, option "persist_decode") -
     a single clip has no grouping to stay consistent with; ``demo_clips`` streams a whole loader through the grouped path instead.
     ``encoding="face"`` (demo.py ``--encoding face``): no embedding is passed, the model takes it from its face tower (``net.vgg_face``).
     ``early_stop``: the decode loop ends once the clip has stopped (model option "early_stop", set on ``net`` for this call and after); the
-    returned mel and attention are already truncated to ``output_lengths[0]`` and are the same either way."""
+    returned mel and attention are already truncated to ``output_lengths[0]`` and are the same either way.
+    ``honour_lengths``: the batch's ``video_lengths`` go to ``net.inference(video_lengths=...)`` (a batch of several padded clips)."""
     _check_encoding(encoding)
     if encoding == "voice" and speaker_embedding is None and speaker_encoder is None:
         raise ValueError("pass a SpeakerEncoder (voice route) or a speaker_embedding")
-    (videos, _), (audios, _), _, face_crops, _ = batch
+    (videos, vlen), (audios, _), _, face_crops, _ = batch
     with torch.no_grad():
         emb = _voice_embedding(encoding, speaker_encoder, speaker_embedding, audios, device)
         face_crops = face_crops.to(device, non_blocking=True) if encoding == "face" else face_crops
         mel, lengths, attn = net.inference(videos.to(device, non_blocking=True), face_crops, speaker_embedding=emb, return_attention_map=True,
-                                           early_stop=bool(early_stop))
+                                           early_stop=bool(early_stop), video_lengths=vlen if honour_lengths else None)
     n = int(lengths[0])                                  # synchronises: a timed-out persistent launch is reported here, not handed on as NaN
     native.check_persist_timeouts()
     return mel[:1, :, :n], lengths, attn[:, :n]
 
 
 def demo_clips(net, batches: Iterable, speaker_encoder=None, speaker_embedding: Optional[torch.Tensor] = None, device="cuda",
-               group: int = 8, n_inflight: int = 3, encoding: str = "voice", early_stop: bool = False):
+               group: int = 8, n_inflight: int = 3, encoding: str = "voice", early_stop: bool = False, honour_lengths: bool = False):
     """demo.py:60-90 over a whole loader: per clip the speaker embedding from the VOICE tower (``--encoding voice``) or a supplied one,
     ``net.inference(..., return_attention_map=True)``, truncation to ``output_lengths[0]``.  The clips are advanced ``group`` per launch
     chain with ``n_inflight`` chains on the GPU (``Lip2Speech.inference_many``); yields ``(mel, lengths, attention)`` per clip, in order.
     ``encoding="face"``: the embedding comes from the model's face tower instead.  ``early_stop``: every group's decode loop ends once all of
-    its clips have stopped (model option "early_stop", set once on ``net`` before the chains start); the yielded tensors are the same."""
+    its clips have stopped (model option "early_stop", set once on ``net`` before the chains start); the yielded tensors are the same.
+    ``honour_lengths``: every batch goes through ``demo_clip`` with its ``video_lengths`` (the masked entry point has no grouped form)."""
     _check_encoding(encoding)
     if encoding == "voice" and speaker_embedding is None and speaker_encoder is None:
         raise ValueError("pass a SpeakerEncoder (voice route) or a speaker_embedding")
+    if honour_lengths:
+        for batch in batches:
+            yield demo_clip(net, batch, speaker_encoder, speaker_embedding, device, encoding, early_stop, honour_lengths=True)
+        return
 
     def calls():
         for (videos, _), (audios, _), _, face_crops, _ in batches:
@@ -79,9 +89,23 @@ def _voice_embedding(encoding, speaker_encoder, speaker_embedding, audios, devic
     return speaker_encoder.inference(audios.to(device, non_blocking=True)) if speaker_encoder is not None else None
 
 
-def _evaluate_outputs(net, batches: Iterable, speaker_encoder, device, group: int, n_inflight: int, encoding: str = "voice"):
+def _evaluate_outputs(net, batches: Iterable, speaker_encoder, device, group: int, n_inflight: int, encoding: str = "voice",
+                      honour_lengths: bool = False):
     """The eval-mode ``net(..., tf_ratio=1)`` of evaluate.py:32-38 for every collated batch (``train_collate_fn_pad`` layout), on the grouped
-    path: yields ``(batch, outputs)`` in loader order."""
+    path: yields ``(batch, outputs)`` in loader order.  ``honour_lengths``: one ``net(...)`` call per batch with the model's
+    ``honour_video_lengths`` switched on for the loop (``l2s_forward_eval_masked``; no grouped form)."""
+    if honour_lengths:
+        was = net.honour_video_lengths
+        net.honour_video_lengths = True
+        try:
+            for batch in batches:
+                (videos, vlen), (audios, alen), (melspecs, mlen, _gate), face_crops = batch
+                with torch.no_grad():
+                    emb = _voice_embedding(encoding, speaker_encoder, None, audios, device)
+                    yield batch, net(videos, face_crops, audios, melspecs, vlen, alen, mlen, 1, speaker_embedding=emb)
+        finally:
+            net.honour_video_lengths = was
+        return
     kept = []
 
     def calls():
@@ -97,20 +121,20 @@ def _evaluate_outputs(net, batches: Iterable, speaker_encoder, device, group: in
 
 
 def evaluate_mels(net, batches: Iterable, speaker_encoder=None, device="cuda", group: int = 8, n_inflight: int = 3,
-                  encoding: str = "voice") -> List[torch.Tensor]:
+                  encoding: str = "voice", honour_lengths: bool = False) -> List[torch.Tensor]:
     """Post-net mels of ``net(..., tf_ratio=1)[1]`` for every collated batch (``train_collate_fn_pad`` layout; evaluate.py:32-38), ``group``
     loader batches per launch chain (``l2s_forward_eval_multi``), ``n_inflight`` chains in flight."""
     was_training = net.training
     net.eval()
     try:
-        return [out[1] for _, out in _evaluate_outputs(net, batches, speaker_encoder, device, group, n_inflight, encoding)]
+        return [out[1] for _, out in _evaluate_outputs(net, batches, speaker_encoder, device, group, n_inflight, encoding, honour_lengths)]
     finally:
         net.train(was_training)
 
 
 def evaluate_net(net, batches: Iterable, speaker_encoder=None, device="cuda", max_iters: int = 256, sampling_rate: int = None,
                  group: int = 8, n_inflight: int = 3, timings: Optional[dict] = None, vocoder_backend: str = "auto", metric: str = "auto",
-                 encoding: str = "voice") -> float:
+                 encoding: str = "voice", honour_lengths: bool = False) -> float:
     """Mean ESTOI of the vocoded predictions against the ground-truth audio (reference: evaluate.py:22-51): `net(..., tf_ratio=1)[1]`
     -> `MelSpec2Audio` (InverseMelScale + Griffin-Lim, `max_iters` each) -> `stoi(gt, pred, fs, extended=True)` per clip.  Vocoder and
     metric are restatements of third-party algorithms (parity unpinned); the mels come from the HIP path, `group` loader batches per launch
@@ -170,7 +194,7 @@ def evaluate_net(net, batches: Iterable, speaker_encoder=None, device="cuda", ma
         with torch.no_grad():
             t0 = time.perf_counter()
             pending = []
-            for batch, out in _evaluate_outputs(net, batches, speaker_encoder, device, group, n_inflight, encoding):
+            for batch, out in _evaluate_outputs(net, batches, speaker_encoder, device, group, n_inflight, encoding, honour_lengths):
                 mel = out[1]
                 if pending and (len(pending) == max(1, group) or pending[0][1].shape[1:] != mel.shape[1:]):
                     t["model_wait_s"] += time.perf_counter() - t0

@@ -9,6 +9,7 @@
 #include "l2s_model.h"
 #include "pdecode.h"
 
+#include <algorithm>
 #include <cmath>
 #include <functional>
 #include <cstring>
@@ -1173,8 +1174,34 @@ static SkinnyP sk_base(const SkW& sw, int B) {
     return p;
 }
 
+// ---- per-clip video lengths (the *_masked entry points, include/l2s.h)
+static int check_lengths(const int32_t* video_lengths, int B, int T) {
+    L2S_REQUIRE(video_lengths, "video_lengths is null");
+    for (int b = 0; b < B; ++b)
+        if (video_lengths[b] < 7 || video_lengths[b] > T) {
+            set_error("l2s: video_lengths[" + std::to_string(b) + "] = " + std::to_string(video_lengths[b]) + " is outside [7, T = " + std::to_string(T) + "]");
+            return 1;
+        }
+    return 0;
+}
+// Where the uniform BiLSTM recurrence needs its two row kernels (step = launch index 0 .. T-1; the forward direction reads frame `step`, the backward
+// direction frame T-1-step): capture AFTER the steps at which some clip's last frame was read forward (step = len_b - 1), reset BEFORE the steps at which
+// a shorter clip's last frame is read backward (step = T - len_b, len_b < T).  Both ascending, without repeats.
+static void masked_bilstm_plan(const int32_t* video_lengths, int B, int T, std::vector<int>& capture, std::vector<int>& reset) {
+    capture.clear(); reset.clear();
+    for (int b = 0; b < B; ++b) {
+        capture.push_back(video_lengths[b] - 1);
+        if (video_lengths[b] < T) reset.push_back(T - video_lengths[b]);
+    }
+    for (std::vector<int>* v : {&capture, &reset}) { std::sort(v->begin(), v->end()); v->erase(std::unique(v->begin(), v->end()), v->end()); }
+}
+static int64_t len_table_bytes(int B) { return align_up((int64_t)2 * B * (int64_t)sizeof(int), 256); }
+
+// lens / lens_host (both or neither): the device length table and the host lengths it was written from - row b then computes what clip b alone at
+// T = len_b computes (always on the launch-per-step recurrence)
 static int prologue_run(l2s_model* m, const float* vis, const float* emb, const float* gumbel, int B, int T,
-                        float* state, float* content_dis, void* ws, int64_t ws_bytes, hipStream_t s) {
+                        float* state, float* content_dis, void* ws, int64_t ws_bytes, hipStream_t s, const int* lens = nullptr,
+                        const int32_t* lens_host = nullptr) {
     X3Scope x3scope(m->opt.infer_bf16 ? 0 : m->opt.gemm_x3);
     Bf16Scope bf16scope(m->opt.infer_bf16);      // the bf16 leg: bf16-operand GEMM / Conv1d kernels instead of the f32 / split-bf16 ones
     const Weights& w = m->w;
@@ -1209,7 +1236,7 @@ static int prologue_run(l2s_model* m, const float* vis, const float* emb, const 
     float* bott_part = bp.f((int64_t)8 * BT * 512);
     // one or two clips of a single-batch call: the BiLSTM recurrence as ONE persistent launch (pdecode.hip pbilstm_kernel; option "persist_decode")
     // (the envelope of the latency path; a persistent launch that timed out since the last call fails THIS call once: pdecode_gate)
-    const int pgate = (m->opt.persist > 0 && B <= m->opt.persist && !grouped_entry() && pbilstm_supported(B, T) && pdecode_supported(B, T, mT)) ? pdecode_gate() : 0;
+    const int pgate = (!lens && m->opt.persist > 0 && B <= m->opt.persist && !grouped_entry() && pbilstm_supported(B, T) && pdecode_supported(B, T, mT)) ? pdecode_gate() : 0;
     if (pgate < 0) return 1;
     const bool pbi = pgate > 0;
     float* pbx = pbi ? bp.f(pbilstm_ws_bytes() / 4 + 64) : nullptr;
@@ -1246,9 +1273,19 @@ static int prologue_run(l2s_model* m, const float* vis, const float* emb, const 
         if (launch_to_frag(s_e, 512, B, 512, cf[d], 512, 0, 0, s)) return 1;
         if (launch_fill(hf[d][1], (int64_t)Bp * 512, 0.f, s)) return 1;
     }
+    std::vector<int> cap_steps, rst_steps;
+    size_t cap_i = 0, rst_i = 0;
+    if (lens) {
+        masked_bilstm_plan(lens_host, B, T, cap_steps, rst_steps);
+        if (launch_fill(state + sl.h, (int64_t)Bp * 512, 0.f, s)) return 1;      // forward finals arrive row by row; the padded rows stay zero
+    }
     for (int step = 0; step < T; ++step) {
         SkinnyBatch sb{};
         const int cur = step & 1, nxt = cur ^ 1;
+        if (rst_i < rst_steps.size() && rst_steps[rst_i] == step) {      // backward rows whose clip ends at frame T-1-step start here, from s_e
+            ++rst_i;
+            if (launch_bilstm_reset(hf[1][cur], cf[1], lens, B, T - 1 - step, s_e, s)) return 1;
+        }
         for (int d = 0; d < 2; ++d) {
             const int t = d == 0 ? step : T - 1 - step;
             SkinnyP p = sk_base(w.whh[d], B);
@@ -1262,13 +1299,17 @@ static int prologue_run(l2s_model* m, const float* vis, const float* emb, const 
         }
         sb.count = 2;
         if (launch_skinny(sb, s, "bilstm_step", m->opt)) return 1;
+        if (cap_i < cap_steps.size() && cap_steps[cap_i] == step) {      // forward rows whose clip ended at frame `step`: their finals, now
+            ++cap_i;
+            if (launch_bilstm_capture(hf[0][nxt], cf[0], lens, B, step, state + sl.h, cellcat, 1024, s)) return 1;
+        }
     }
     const int fin = T & 1;     // buffer holding the final hidden states
     // decoder initial hidden = BiLSTM finals (fwd -> layer 0, bwd -> layer 1); kept in the state buffer as frag16
-    L2S_CHECK_HIP(hipMemcpyAsync(state + sl.h, hf[0][fin], sizeof(float) * Bp * 512, hipMemcpyDeviceToDevice, s));
+    if (!lens) L2S_CHECK_HIP(hipMemcpyAsync(state + sl.h, hf[0][fin], sizeof(float) * Bp * 512, hipMemcpyDeviceToDevice, s));
     L2S_CHECK_HIP(hipMemcpyAsync(state + sl.h + (int64_t)Bp * 512, hf[1][fin], sizeof(float) * Bp * 512, hipMemcpyDeviceToDevice, s));
     // encoder_cell = E_C(cat(c_fwd, c_bwd))
-    if (launch_from_frag(cf[0], 512, B, 512, cellcat, 1024, 0, s)) return 1;
+    if (!lens && launch_from_frag(cf[0], 512, B, 512, cellcat, 1024, 0, s)) return 1;
     if (launch_from_frag(cf[1], 512, B, 512, cellcat, 1024, 512, s)) return 1;
     }
     {
@@ -1284,7 +1325,9 @@ static int prologue_run(l2s_model* m, const float* vis, const float* emb, const 
         p.R1 = resid; p.ldr1 = 512; p.r1_mod = 0;
         p.R2 = s_a; p.ldr2 = 512; p.r2_div = T;     // attention_site embedding, broadcast over the T frames of a clip
         if (launch_gemm_splitk(p, 4, bott_part, s, "prologue_gemm")) return 1;
-        if (launch_copy_cols(cat, 4608, 0, state + sl.enc, 512, 0, 1, BT, 512, s)) return 1;
+        // with lengths: rows t >= len_b become zeros on the way (the K / V convolutions below then read past a clip's end what a solo call reads as padding)
+        if (lens ? launch_mask_copy_rows(cat, 4608, state + sl.enc, 512, lens, B, T, 512, s)
+                 : launch_copy_cols(cat, 4608, 0, state + sl.enc, 512, 0, 1, BT, 512, s)) return 1;
     }
     // MultiHopConv branches of K and V (8 convs, one grouped launch), then the two bottlenecks (+PSine +pos)
     {
@@ -1328,7 +1371,12 @@ static int prologue_run(l2s_model* m, const float* vis, const float* emb, const 
         pc.x[0] = cat; pc.L[0] = T; pc.ld[0] = 4608;
         for (int j = 0; j < 4; ++j) { pc.x[j + 1] = cmap[j]; pc.L[j + 1] = L[j]; pc.ld[j + 1] = 512; }
         pc.nmaps = 5; pc.B = B; pc.m = mT; pc.C = 512; pc.out = pooled;
-        if (launch_pool_cat(pc, s)) return 1;
+        if (lens) {
+            PoolDiv pd{};
+            pd.div[0] = 1;
+            for (int j = 0; j < 4; ++j) pd.div[j + 1] = CT_KS[j];
+            if (launch_pool_cat_masked(pc, pd, lens, s)) return 1;
+        } else if (launch_pool_cat(pc, s)) return 1;
         const int R = B * mT;
         GemmP p = gemm_plain(pooled, 2560, w.ct_bott.W, wv, 256, R, 256, 2560);
         p.shift = w.ct_bott.shift;
@@ -1347,6 +1395,7 @@ static int prologue_run(l2s_model* m, const float* vis, const float* emb, const 
         p3.shift = w.ct_fc4.shift; p3.act = ACT_SILU;
         if (launch_gemm1(p3, s, "content_gemm")) return 1;
         if (launch_gumbel_softmax(logits, gumbel, R, VOC, 0.1f, z, VOCP, content_dis, s)) return 1;
+        if (lens && launch_zero_slot_rows(z, VOCP, content_dis, VOC, B, mT, lens, s)) return 1;      // slots i >= m_b: zero z (so zero values) and zero content_dis
         GemmP p4 = gemm_plain(z, VOCP, w.ct_emb.W, state + sl.cval, 256, R, 256, VOCP);
         if (launch_gemm1(p4, s, "content_gemm")) return 1;
     }
@@ -1368,7 +1417,7 @@ struct DecodeBufs {
 // on_frames(n): called (if set) right after the launch that completes mel frames [0, n) has been enqueued on `s`
 static int decode_launches(l2s_model* m, float* state, int B, int T, int S, const float* teacher, const uint8_t* teacher_mask,
                            float* mel, float* stop, float* attn, int attn_logits, void* ws, int64_t ws_bytes, hipStream_t s, bool fold,
-                           const std::function<int(int)>* on_frames = nullptr, bool early = false) {
+                           const std::function<int(int)>* on_frames = nullptr, bool early = false, const int* lens = nullptr) {
     const Weights& w = m->w;
     StateLayout sl = state_layout(B, T);
     const int Bp = pad16(B);
@@ -1446,7 +1495,8 @@ static int decode_launches(l2s_model* m, float* state, int B, int T, int S, cons
             pr.seg[0] = {d.p1, 16}; pr.nseg = 1; pr.act = ACT_PSINE;
             if (fold) { pr.epi = SK_FRAG; pr.out = d.p2f; pr.ldo = 256; }
             else { pr.epi = SK_PLAIN; pr.out = d.p2; pr.ldo = 256; }
-            if (launch_step_attn(at, pr, w.pre2.tiles, s, m->opt.attn_lds, m->opt.attn_skip0)) return 1;
+            if (lens ? launch_step_attn_masked(at, pr, w.pre2.tiles, lens, s, m->opt.attn_lds, m->opt.attn_skip0)
+                     : launch_step_attn(at, pr, w.pre2.tiles, s, m->opt.attn_lds, m->opt.attn_skip0)) return 1;
         }
         if (!fold) {   // phase C: u = prenet + attention_proj(a @ v)
             SkinnyBatch sb{};
@@ -1488,7 +1538,8 @@ static int decode_launches(l2s_model* m, float* state, int B, int T, int S, cons
 }
 
 static int decode_run(l2s_model* m, float* state, int B, int T, int S, const float* teacher, const uint8_t* teacher_mask,
-                      float* mel, float* stop, float* attn, int attn_logits, void* ws, int64_t ws_bytes, hipStream_t s, bool may_stop_early) {
+                      float* mel, float* stop, float* attn, int attn_logits, void* ws, int64_t ws_bytes, hipStream_t s, bool may_stop_early,
+                      const int* lens = nullptr) {
     L2S_REQUIRE(S >= 1 && S <= L2S_MAX_STEPS, "S must be in [1, 300] (positional table)");
     const bool fold = m->opt.fold != 0 && m->folded_valid;
     // option "early_stop": free-running loops only (a teacher-forced loop's S comes from the target).  The steps the loop never reaches are exact zeros
@@ -1499,7 +1550,7 @@ static int decode_run(l2s_model* m, float* state, int B, int T, int S, const flo
         L2S_CHECK_HIP(hipMemsetAsync(stop, 0, sizeof(float) * B * S, s));
         if (attn) L2S_CHECK_HIP(hipMemsetAsync(attn, 0, sizeof(float) * B * S * T, s));
     }
-    if (!teacher && fold && m->opt.persist > 0 && B <= m->opt.persist && !grouped_entry()) {      // the latency form: one launch for the whole loop
+    if (!lens && !teacher && fold && m->opt.persist > 0 && B <= m->opt.persist && !grouped_entry()) {      // the latency form: one launch for the whole loop (never with lengths)
         const Weights& w = m->w;
         StateLayout sl = state_layout(B, T);
         const int pgate = (pdecode_supported(B, T, sl.m) && w.vproj.W && w.pre1f.W && w.lstm0.W && w.lstm1.W) ? pdecode_gate() : 0;
@@ -1522,8 +1573,8 @@ static int decode_run(l2s_model* m, float* state, int B, int T, int S, const flo
             return launch_pdecode(p, ws, ws_bytes, s);
         }
     }
-    const bool use_graph = m->opt.graph && !teacher && !g_prof_on && !early;      // "early_stop" takes the plain route: a replayed graph knows no control block of this call
-    if (!use_graph) return decode_launches(m, state, B, T, S, teacher, teacher_mask, mel, stop, attn, attn_logits, ws, ws_bytes, s, fold, nullptr, early);
+    const bool use_graph = m->opt.graph && !teacher && !g_prof_on && !early && !lens;      // "early_stop" and per-clip lengths take the plain route: a replayed graph knows no control block / length table of this call
+    if (!use_graph) return decode_launches(m, state, B, T, S, teacher, teacher_mask, mel, stop, attn, attn_logits, ws, ws_bytes, s, fold, nullptr, early, lens);
 
     std::lock_guard<std::mutex> side_lock(m->side_mu);      // graph cache, side stream and events are per model; chains of other threads wait here
     if (!m->side) {
@@ -1815,10 +1866,12 @@ struct PathOut {
 };
 
 static int path_run(l2s_model* m, const FrameSrc& video, const float* emb, const float* gumbel, int B, int T, int H, int W, int S,
-                    const float* teacher, const uint8_t* teacher_mask, const PathOut& o, void* ws, int64_t ws_bytes, hipStream_t s) {
+                    const float* teacher, const uint8_t* teacher_mask, const PathOut& o, void* ws, int64_t ws_bytes, hipStream_t s,
+                    const int32_t* video_lengths = nullptr) {
     X3Scope x3scope(m->opt.infer_bf16 ? 0 : m->opt.gemm_x3);
     Bf16Scope bf16scope(m->opt.infer_bf16);      // the bf16 leg: bf16-operand GEMM / Conv1d kernels instead of the f32 / split-bf16 ones
     Bump bp(ws, ws_bytes);
+    int* lens = video_lengths ? reinterpret_cast<int*>(bp.f(len_table_bytes(B) / 4)) : nullptr;      // the *_masked entry points (l2s_workspace_bytes_masked)
     float* vis = bp.f((int64_t)B * T * 1024);
     float* state = bp.f(l2s_state_floats(B, T));
     float* mel = bp.f((int64_t)B * S * NM);
@@ -1826,12 +1879,13 @@ static int path_run(l2s_model* m, const FrameSrc& video, const float* emb, const
     L2S_REQUIRE(!bp.overflow, "workspace too small (l2s_workspace_bytes)");
     void* rest = (char*)ws + bp.off;
     const int64_t rest_bytes = ws_bytes - bp.off;
+    if (lens && launch_len_table(video_lengths, B, lens, s)) return 1;
     if (encoder_run(m, video, B, T, H, W, emb, vis, nullptr, rest, rest_bytes, s)) return 1;
-    if (prologue_run(m, vis, emb, gumbel, B, T, state, o.content_dis, rest, rest_bytes, s)) return 1;
+    if (prologue_run(m, vis, emb, gumbel, B, T, state, o.content_dis, rest, rest_bytes, s, lens, video_lengths)) return 1;
     const bool early = m->opt.early_stop != 0 && !teacher && o.lengths;      // l2s_inference(_multi); l2s_forward_eval's S comes from the target
-    const bool plain = !m->opt.overlap_postnet || g_prof_on || m->opt.graph || teacher || o.mel_cf || early;      // "early_stop" takes the plain route
+    const bool plain = !m->opt.overlap_postnet || g_prof_on || m->opt.graph || teacher || o.mel_cf || early || lens;      // "early_stop" and lengths take the plain route
     if (plain) {
-        if (decode_run(m, state, B, T, S, teacher, teacher_mask, mel, stop, o.attn, o.attn_logits, rest, rest_bytes, s, early)) return 1;
+        if (decode_run(m, state, B, T, S, teacher, teacher_mask, mel, stop, o.attn, o.attn_logits, rest, rest_bytes, s, early, lens)) return 1;
         if (postnet_run(m, mel, B, S, o.mel_post, o.mel_cf, rest, rest_bytes, s)) return 1;
     } else {
         // The decode loop is a chain of small latency-bound launches that leaves most CUs idle, and the post-net of frame t
@@ -1892,6 +1946,70 @@ int l2s_inference(l2s_model* m, const float* video, const float* emb, const floa
     L2S_DEC_READY(m);
     L2S_REQUIRE(video && emb && gumbel && mel_post && lengths && ws && B > 0, "bad arguments");
     return inference_run(m, frame_src(video, B), emb, gumbel, B, T, H, W, S, mel_post, lengths, attn, ws, ws_bytes, (hipStream_t)stream);
+}
+
+// ---- per-clip video lengths: row b of a zero-padded batch computes what clip b computes alone at T = len_b (include/l2s.h).  New entry points only;
+// the launch-per-phase route, whatever "persist_decode" / "use_graph" say.
+int64_t l2s_workspace_bytes_masked(int B, int T, int H, int W, int S) { return l2s_workspace_bytes(B, T, H, W, S) + len_table_bytes(B) + 256; }
+
+int l2s_masked_bilstm_plan(const int32_t* video_lengths, int B, int T, int32_t* capture_steps, int32_t* reset_steps, int* n_capture, int* n_reset) {
+    L2S_REQUIRE(B > 0 && capture_steps && reset_steps && n_capture && n_reset, "bad arguments");
+    if (check_lengths(video_lengths, B, T)) return 1;
+    std::vector<int> cap, rst;
+    masked_bilstm_plan(video_lengths, B, T, cap, rst);
+    std::copy(cap.begin(), cap.end(), capture_steps);
+    std::copy(rst.begin(), rst.end(), reset_steps);
+    *n_capture = (int)cap.size(); *n_reset = (int)rst.size();
+    return 0;
+}
+
+int l2s_inference_masked(l2s_model* m, const float* video, const float* emb, const float* gumbel, int B, int T, int H, int W, int S,
+                         float* mel_post, int64_t* lengths, float* attn, void* ws, int64_t ws_bytes, void* stream, const int32_t* video_lengths) {
+    L2S_ENC_READY(m);
+    L2S_DEC_READY(m);
+    L2S_REQUIRE(video && emb && gumbel && mel_post && lengths && ws && B > 0, "bad arguments");
+    if (check_lengths(video_lengths, B, T)) return 1;
+    PathOut o;
+    o.mel_post = mel_post; o.lengths = lengths; o.attn = attn;
+    return path_run(m, frame_src(video, B), emb, gumbel, B, T, H, W, S, nullptr, nullptr, o, ws, ws_bytes, (hipStream_t)stream, video_lengths);
+}
+
+int l2s_forward_eval_masked(l2s_model* m, const float* video, const float* emb, const float* gumbel, int B, int T, int H, int W, int S,
+                            const float* teacher, const uint8_t* teacher_mask, float* mel_cf, float* mel_post, float* stop, float* attn_logits,
+                            float* content_dis, void* ws, int64_t ws_bytes, void* stream, const int32_t* video_lengths) {
+    L2S_ENC_READY(m);
+    L2S_DEC_READY(m);
+    L2S_REQUIRE(video && emb && gumbel && mel_post && stop && ws && B > 0, "bad arguments");
+    L2S_REQUIRE((teacher != nullptr) == (teacher_mask != nullptr), "teacher frames and teacher_mask come together");
+    if (check_lengths(video_lengths, B, T)) return 1;
+    PathOut o;
+    o.mel_post = mel_post; o.mel_cf = mel_cf; o.stop = stop; o.attn = attn_logits; o.attn_logits = 1; o.content_dis = content_dis;
+    return path_run(m, frame_src(video, B), emb, gumbel, B, T, H, W, S, teacher, teacher_mask, o, ws, ws_bytes, (hipStream_t)stream, video_lengths);
+}
+
+// the staged pair: each call writes its own length table at the front of its workspace
+int l2s_decoder_prologue_masked(l2s_model* m, const float* vis, const float* emb, const float* gumbel, int B, int T, float* state,
+                                float* content_dis, void* ws, int64_t ws_bytes, void* stream, const int32_t* video_lengths) {
+    L2S_DEC_READY(m);
+    L2S_REQUIRE(vis && emb && gumbel && state && ws && B > 0, "bad arguments");
+    if (check_lengths(video_lengths, B, T)) return 1;
+    L2S_REQUIRE(ws_bytes > len_table_bytes(B), "workspace too small (l2s_workspace_bytes_masked)");
+    int* lens = reinterpret_cast<int*>(ws);
+    if (launch_len_table(video_lengths, B, lens, (hipStream_t)stream)) return 1;
+    return prologue_run(m, vis, emb, gumbel, B, T, state, content_dis, (char*)ws + len_table_bytes(B), ws_bytes - len_table_bytes(B), (hipStream_t)stream, lens,
+                        video_lengths);
+}
+
+int l2s_decode_steps_masked(l2s_model* m, float* state, int B, int T, int S, const float* teacher, const uint8_t* teacher_mask, float* mel,
+                            float* stop, float* attn, int attn_logits, void* ws, int64_t ws_bytes, void* stream, const int32_t* video_lengths) {
+    L2S_DEC_READY(m);
+    L2S_REQUIRE(state && mel && stop && ws && B > 0, "bad arguments");
+    if (check_lengths(video_lengths, B, T)) return 1;
+    L2S_REQUIRE(ws_bytes > len_table_bytes(B), "workspace too small (l2s_workspace_bytes_masked)");
+    int* lens = reinterpret_cast<int*>(ws);
+    if (launch_len_table(video_lengths, B, lens, (hipStream_t)stream)) return 1;
+    return decode_run(m, state, B, T, S, teacher, teacher_mask, mel, stop, attn, attn_logits, (char*)ws + len_table_bytes(B), ws_bytes - len_table_bytes(B),
+                      (hipStream_t)stream, true, lens);
 }
 
 // Grouped inference: the G batches are rows g*B .. g*B+B-1 of ONE launch chain on ONE weight blob.  Every kernel of the path is row-independent

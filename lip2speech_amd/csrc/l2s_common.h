@@ -430,6 +430,21 @@ int launch_transpose_bsc(const float* in, int B, int S, int C, float* out, hipSt
 int launch_output_lengths(const float* stop, int B, int S, int64_t* lengths, hipStream_t s);
 // option "early_stop": mel_post[b][:][j] = 0 and attn[b][j][:] = 0 (attn may be null) for j >= lengths[b]
 int launch_mask_by_lengths(const int64_t* lengths, int B, int S, int T, float* mel_post, float* attn, hipStream_t s);
+// ---- per-clip video lengths (masked_kernels.hip; the *_masked entry points).  The device length table is 2*B int32: len_b, then m_b = l2s_min_T(len_b)
+constexpr int LEN_CHUNK = 64;                                  // lengths per table-writing launch (they travel in the kernel arguments)
+struct LenChunk { int len[LEN_CHUNK]; int n; };
+int launch_len_table(const int32_t* lens_host, int B, int* table, hipStream_t s);
+// forward BiLSTM rows with len_b - 1 == t: h (frag16) -> h_dst_frag (same row), c (frag16) -> c_dst[b*ld_c + unit]
+int launch_bilstm_capture(const float* h_frag, const float* c_frag, const int* lens, int B, int t, float* h_dst_frag, float* c_dst, int ld_c, hipStream_t s);
+// backward BiLSTM rows with len_b - 1 == t: h = c = s_e[b] (frag16 buffers)
+int launch_bilstm_reset(float* h_frag, float* c_frag, const int* lens, int B, int t, const float* s_e, hipStream_t s);
+// x rows (b, t >= len_b) := 0 in place; out := x (the masked copy)
+int launch_mask_copy_rows(float* x, int ldx, float* out, int ldo, const int* lens, int B, int T, int cols, hipStream_t s);
+struct PoolDiv { int div[5]; };                                // map j of a clip of len frames has len / div[j] valid positions
+int launch_pool_cat_masked(const PoolCatP& p, const PoolDiv& d, const int* lens, hipStream_t s);
+int launch_zero_slot_rows(float* z, int ldz, float* dis, int n, int B, int m, const int* lens, hipStream_t s);
+// launch_step_attn with per-row lengths: row b's soft-max and a @ V' over t < len_b (attention columns past it: 0, or -inf for logits), content over m_b slots
+int launch_step_attn_masked(const AttnP& at, const SkinnyP& pre2, int pre2_tiles, const int* lens, hipStream_t s, int lds_values = 1, int skip0 = 0);
 int launch_frame_window(const float* audio, int B, int N, int L, int n_fft, int hop, const float* window, float* frames, hipStream_t s);
 int launch_power(const float* spec, int lds, int64_t rows, int nf, float* power, int ldp, hipStream_t s);
 // stop_const[b] = dot(ecell[b], w[512:1024]) + bias

@@ -579,6 +579,50 @@ __global__ __launch_bounds__(512) void step_attn_kernel(const StepB sb) {
     L2S_BLOCK_STAMP_END(3u, sb.at.q);
 }
 
+// The same grid with per-row lengths (the *_masked entry points): lens[b] = len_b frames, lens[B + b] = m_b content slots of clip b inside rows laid
+// out for the padded T / m.  The length is block-uniform (one scalar load per block); the prenet blocks are the unmasked ones.
+template <bool VL, bool SKIP0 = false, bool ES = false>
+__global__ __launch_bounds__(512) void step_attn_masked_kernel(const StepB sb, const int* __restrict__ lens) {
+    constexpr int SMF = ATT_SM_FLOATS + (VL && !SKIP0 ? ATT_VLDS_FLOATS : 0);
+    __shared__ __attribute__((aligned(16))) float sm[SMF > SK_RED_FLOATS ? SMF : SK_RED_FLOATS];
+    if constexpr (ES) L2S_ES_RETURN(sb.at);
+    const int nb = sb.at.B, ptiles = sb.pre2_tiles;
+    L2S_PIN_S("s"(nb), "s"(ptiles));
+    const int bid = blockIdx.x;
+    if (bid < nb) {
+        const int len = min(max(lens[bid], 1), sb.at.T);           // validated on the host (7 .. T); clamped so that no table content can index past a row
+        L2S_PIN_S("s"(len));
+        attention_block<false, false, VL, SKIP0, true>(sb.at, bid, sm, nullptr, nullptr, len);
+    } else if (bid < 2 * nb) {
+        const int mb = min(max(lens[bid], 1), sb.at.m);             // lens[B + b] with b = bid - B
+        L2S_PIN_S("s"(mb));
+        content_block<false, true>(sb.at, bid - nb, sm, nullptr, mb);
+    } else {
+        const int j = bid - 2 * nb;
+        const int tile = j % ptiles, mt = j / ptiles;
+        skinny_block<false, ATT_PRE2_MAXC>(sb.pre2, tile, mt, sm);
+    }
+}
+
+int launch_step_attn_masked(const AttnP& at, const SkinnyP& pre2, int pre2_tiles, const int* lens, hipStream_t s, int lds_values, int skip0) {
+    L2S_REQUIRE(at.T <= ATT_MAXT && at.m >= 1 && at.m <= ATT_MAXM && lens, "attention sizes");
+    L2S_REQUIRE(pre2.K <= 16 * SK_WAVES * ATT_PRE2_MAXC, "prenet layer 2 is a 256-wide layer");
+    StepB sb;
+    sb.at = at;
+    sb.pre2 = pre2;
+    sb.pre2_tiles = pre2_tiles;
+    sb.mts = (at.B + 15) / 16;
+    ProfScope ps("step_attention_prenet2_masked", s);
+    // the block forms are chosen on the PADDED length (the LDS staging and the lane-per-frame soft-max need T <= 32), as launch_step_attn does
+    const bool vl = lds_values && (lds_values >= 2 || at.B <= 128 || chains_hint() >= 2) && at.vp != nullptr && at.T <= 32;
+    const dim3 grid(2 * at.B + pre2_tiles * sb.mts);
+    if (vl && skip0 && (skip0 >= 2 || chains_hint() >= 2)) SK_ES_LAUNCH(sb.at.es_end, step_attn_masked_kernel, (true, true), grid, dim3(512), 0, s, sb, lens);
+    else if (vl) SK_ES_LAUNCH(sb.at.es_end, step_attn_masked_kernel, (true, false), grid, dim3(512), 0, s, sb, lens);
+    else SK_ES_LAUNCH(sb.at.es_end, step_attn_masked_kernel, (false, false), grid, dim3(512), 0, s, sb, lens);
+    L2S_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
 #ifdef L2S_DIAG
 // measurement build (tools/attn_timeline.py): thread 0 of every attention block stamps the 100 MHz wall clock at seven points
 __global__ __launch_bounds__(512) void step_attn_timed_kernel(const StepB sb, unsigned long long* ts) {

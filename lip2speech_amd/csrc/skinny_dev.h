@@ -914,16 +914,20 @@ __device__ __forceinline__ float block_sum8(float x, float* scratch) {
 // The block then fetches the projected values of the non-zero frames only, AFTER the soft-max (one more round trip in the block's life, a quarter
 // fewer bytes through the fabric per launch: 7.6 of 29.7 MB at 256 rows) - for launches that run beside other chains' kernels, where the launch is
 // bound by the fabric, not by its own latency chain.
-template <bool TRAIN = false, bool TIMED = false, bool VLDS = false, bool SKIP0 = false>
-__device__ __forceinline__ void attention_block(const AttnP& p, int b, float* sm, const AttnTrain* tr = nullptr, unsigned long long* ats = nullptr) {
+// ML (the *_masked entry points): the clip has `len` <= T real frames inside rows laid out for the padded T - every loop, descriptor and soft-max lane
+// runs over len, as a solo call at T = len does (same order of the same sums); attention columns len .. T-1 are written as 0 (-inf for logits)
+template <bool TRAIN = false, bool TIMED = false, bool VLDS = false, bool SKIP0 = false, bool ML = false>
+__device__ __forceinline__ void attention_block(const AttnP& p, int b, float* sm, const AttnTrain* tr = nullptr, unsigned long long* ats = nullptr, int len = 0) {
     static_assert(!SKIP0 || VLDS, "the zero-weight skip rides on the buffer-load form of the inference step");
+    static_assert(!ML || (!TRAIN && !TIMED), "per-row lengths: the inference step only");
     L2S_ATT_STAMP(0);
     float* qs = sm;                  // 512
     float* sc = sm + 512;            // ATT_MAXT
     float* scratch = sc + ATT_MAXT;  // 16
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int T = p.T;
+    const int T = p.T;                              // row stride of k / v / attention
+    const int Te = ML ? len : T;                    // frames the clip has
     // values: v (512 columns) or, when the caller hoisted attention_proj into the prologue, V' = V W_ap^T + b_ap (256 columns: waves 4-7 have none)
     const int vcols = p.vp ? 256 : 512;
     const float* const pq = p.q; const float* const pk = p.k; const float* const pv = p.vp ? p.vp : p.v; const float* const ptau = p.tau;
@@ -941,7 +945,7 @@ __device__ __forceinline__ void attention_block(const AttnP& p, int b, float* sm
         // buffer loads: one scalar descriptor per clip, the frame as a scalar byte offset, one per-lane offset for all eight requests - no 64-bit address
         // per request (the flat form kept ~20 registers of addresses alive and the block at 102: two blocks per CU, the launch's 768 blocks in 1.5 rounds);
         // frames past T read zero through the descriptor's byte count
-        const __amdgpu_buffer_rsrc_t rk = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(pk + (int64_t)b * T * 512), 0, T * 2048, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rk = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(pk + (int64_t)b * T * 512), 0, Te * 2048, 0x00020000);
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int so = __builtin_amdgcn_readfirstlane((wave + 8 * r) * 2048);
@@ -952,7 +956,7 @@ __device__ __forceinline__ void attention_block(const AttnP& p, int b, float* sm
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int t = wave + 8 * r;
-            if (t < T) {
+            if (t < Te) {
                 k0[r] = *reinterpret_cast<const float4*>(kb + (int64_t)t * 512);
                 k1[r] = *reinterpret_cast<const float4*>(kb + (int64_t)t * 512 + 4);
             }
@@ -965,12 +969,12 @@ __device__ __forceinline__ void attention_block(const AttnP& p, int b, float* sm
     if constexpr (SKIP0) {
         // nothing up front: the values of the frames that count are requested after the soft-max
     } else if constexpr (vlds) {
-        const __amdgpu_buffer_rsrc_t rv = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(pv + (int64_t)b * T * 256), 0, T * 1024, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rv = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(pv + (int64_t)b * T * 256), 0, Te * 1024, 0x00020000);
 #pragma unroll
         for (int i = 0; i < 4; ++i) vq[i] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rv, tid * 16, 8192 * i, 0));
     } else {
 #pragma unroll
-        for (int e = 0; e < 32; ++e) vv[e] = (vlane && e < T) ? vb[(int64_t)e * vcols] : 0.f;
+        for (int e = 0; e < 32; ++e) vv[e] = (vlane && e < Te) ? vb[(int64_t)e * vcols] : 0.f;
     }
     L2S_ATT_STAMP(1);               // every request issued
     // ---- logits
@@ -983,14 +987,14 @@ __device__ __forceinline__ void attention_block(const AttnP& p, int b, float* sm
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
         const int t = wave + 8 * r;
-        if (t < T) {
+        if (t < Te) {
             double d = (double)qq[0] * k0[r].x + (double)qq[1] * k0[r].y + (double)qq[2] * k0[r].z + (double)qq[3] * k0[r].w +
                        (double)qq[4] * k1[r].x + (double)qq[5] * k1[r].y + (double)qq[6] * k1[r].z + (double)qq[7] * k1[r].w;
             d = wave_sum_d(d);
             if (lane == 0) sc[t] = (float)d;
         }
     }
-    for (int t = wave + 32; t < T; t += 8) {             // clips longer than 32 frames: remaining rows, one at a time
+    for (int t = wave + 32; t < Te; t += 8) {             // clips longer than 32 frames: remaining rows, one at a time
         const float4 a0 = *reinterpret_cast<const float4*>(kb + (int64_t)t * 512);
         const float4 a1 = *reinterpret_cast<const float4*>(kb + (int64_t)t * 512 + 4);
         double d = (double)qq[0] * a0.x + (double)qq[1] * a0.y + (double)qq[2] * a0.z + (double)qq[3] * a0.w +
@@ -1000,7 +1004,7 @@ __device__ __forceinline__ void attention_block(const AttnP& p, int b, float* sm
     }
     if constexpr (vlds) {
 #pragma unroll
-        for (int i = 0; i < 4; ++i) { const int idx = tid + 512 * i; if (idx < T * 64) reinterpret_cast<float4*>(vs)[idx] = vq[i]; }
+        for (int i = 0; i < 4; ++i) { const int idx = tid + 512 * i; if (idx < Te * 64) reinterpret_cast<float4*>(vs)[idx] = vq[i]; }
     }
     L2S_ATT_STAMP(3);               // this wave's logits (its k rows have landed)
     __syncthreads();
@@ -1011,17 +1015,17 @@ __device__ __forceinline__ void attention_block(const AttnP& p, int b, float* sm
     if constexpr (VLDS) {
         // T <= 32: each wave runs the 29-lane softmax itself (same shuffles, same bits in every wave) and keeps the weights in a register - no LDS
         // round trip and no third block barrier; a@V' below broadcasts weight e with v_readlane
-        const bool on = lane < T;
+        const bool on = lane < Te;
         const float x = on ? sc[lane] : -INFINITY;
         const float mx = wave_max_f(x);
         const float ex = on ? expf(x - mx) : 0.f;
         const float tot = wave_sum_f(ex);
         awr = on ? ex / tot : 0.f;
         if (wave == 0 && on && pattn) pattn[(int64_t)b * ld_attn + lane] = logits ? x : awr;
-    } else if (T <= 64) {
+    } else if (Te <= 64) {
         // one wave, shuffles only (LRW: T = 29): one block barrier instead of five
         if (wave == 0) {
-            const bool on = lane < T;
+            const bool on = lane < Te;
             float x = on ? sc[lane] : -INFINITY;
             if constexpr (TRAIN) { if (on && tr->logit_mask) x *= tr->logit_mask[(int64_t)b * tr->ld_lmask + lane]; }
             const float mx = wave_max_f(x);
@@ -1036,7 +1040,7 @@ __device__ __forceinline__ void attention_block(const AttnP& p, int b, float* sm
         __syncthreads();
     } else {
         // T <= 320 < 512: one element per thread
-        const bool on = tid < T;
+        const bool on = tid < Te;
         float x = on ? sc[tid] : -INFINITY;
         if constexpr (TRAIN) { if (on && tr->logit_mask) x *= tr->logit_mask[(int64_t)b * tr->ld_lmask + tid]; }
         const float mx = block_max8(x, scratch);
@@ -1055,7 +1059,7 @@ __device__ __forceinline__ void attention_block(const AttnP& p, int b, float* sm
     if constexpr (SKIP0) {
         const unsigned long long nz = __ballot(awr != 0.f);          // the same in every wave (each ran the same soft-max)
         if (wave < 4) {                                               // 256 value columns: waves 0-3, one column per thread
-            const __amdgpu_buffer_rsrc_t rv = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(pv + (int64_t)b * T * 256), 0, T * 1024, 0x00020000);
+            const __amdgpu_buffer_rsrc_t rv = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(pv + (int64_t)b * T * 256), 0, Te * 1024, 0x00020000);
             unsigned long long m = nz;
             while (m) {                                               // four frames per round: their loads are in flight together; t ascending as in the full form
                 int tt[4]; float ww[4], vl[4];
@@ -1079,38 +1083,43 @@ __device__ __forceinline__ void attention_block(const AttnP& p, int b, float* sm
         for (int h = 0; h < 2; ++h) {                                         // sixteen unconditional reads in flight at a time (a guarded read per frame serialises them)
             float vl[16];
 #pragma unroll
-            for (int e = 0; e < 16; ++e) vl[e] = vc[(16 * h + e < T ? 16 * h + e : 0) * 256];
+            for (int e = 0; e < 16; ++e) vl[e] = vc[(16 * h + e < Te ? 16 * h + e : 0) * 256];
 #pragma unroll
             for (int e = 0; e < 16; ++e)
-                if (16 * h + e < T) acc = fmaf(__builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, awr), 16 * h + e)), vl[e], acc);
+                if (16 * h + e < Te) acc = fmaf(__builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, awr), 16 * h + e)), vl[e], acc);
         }
     } else {
 #pragma unroll
         for (int e = 0; e < 32; ++e)
-            if (e < T) acc = fmaf(sc[e], vv[e], acc);
+            if (e < Te) acc = fmaf(sc[e], vv[e], acc);
     }
-    for (int t0 = 32; t0 < T; t0 += 16) {
+    for (int t0 = 32; t0 < Te; t0 += 16) {
         float v2[16];
 #pragma unroll
-        for (int e = 0; e < 16; ++e) v2[e] = (vlane && t0 + e < T) ? vb[(int64_t)(t0 + e) * vcols] : 0.f;
+        for (int e = 0; e < 16; ++e) v2[e] = (vlane && t0 + e < Te) ? vb[(int64_t)(t0 + e) * vcols] : 0.f;
 #pragma unroll
         for (int e = 0; e < 16; ++e)
-            if (t0 + e < T) acc = fmaf(sc[t0 + e], v2[e], acc);
+            if (t0 + e < Te) acc = fmaf(sc[t0 + e], v2[e], acc);
     }
     if (vlane) pav[frag16_index(b, tid, vcols)] = acc;
+    if constexpr (ML) {                              // the padded attention columns: what a masked soft-max gives them
+        if (pattn)
+            for (int t = Te + tid; t < T; t += 512) pattn[(int64_t)b * ld_attn + t] = logits ? -INFINITY : 0.f;
+    }
     if constexpr (TRAIN) { if (tr->av_plain) tr->av_plain[(int64_t)b * 512 + tid] = acc; }
     if constexpr (TIMED) { __builtin_amdgcn_s_waitcnt(0); L2S_ATT_STAMP(6); }
 }
 
 // Content.forward for clips of more than 16 content keys (T = 119..300, m = 17..42): the arithmetic of content_block below - the same fp64 dot
 // products, soft-max and t-ascending fmaf chain, so the same bits at any m - with the key rows and the values read in loops instead of held in registers
-template <bool TRAIN = false>
-__device__ __forceinline__ void content_block_long(const AttnP& p, int b, float* sm, const AttnTrain* tr) {
+template <bool TRAIN = false, bool ML = false>
+__device__ __forceinline__ void content_block_long(const AttnP& p, int b, float* sm, const AttnTrain* tr, int mb = 0) {
     float* qs = sm;                  // 256
     float* csc = sm + 512;           // m <= ATT_MAXM, inside the ATT_MAXT logits slot
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int m = p.m;
+    const int m = p.m;                              // slot stride of key / value
+    const int me = ML ? mb : m;                     // slots the clip uses
     const int col = tid & 255;
     const float qv = p.qc[(int64_t)b * p.ldqc + col];
     const float tau_c = p.tau_c[0];
@@ -1119,7 +1128,7 @@ __device__ __forceinline__ void content_block_long(const AttnP& p, int b, float*
     if (tid < 256) qs[tid] = qv * tau_c;
     __syncthreads();
     const float* q4 = qs + lane * 4;
-    for (int i = wave; i < m; i += 8) {
+    for (int i = wave; i < me; i += 8) {
         const float4 kk = *reinterpret_cast<const float4*>(keyb + (int64_t)i * 256);
         double d = (double)q4[0] * kk.x + (double)q4[1] * kk.y + (double)q4[2] * kk.z + (double)q4[3] * kk.w;
         d = wave_sum_d(d);
@@ -1128,11 +1137,11 @@ __device__ __forceinline__ void content_block_long(const AttnP& p, int b, float*
     __syncthreads();
     if (tid < 256) {
         float cmx = -INFINITY;
-        for (int i = 0; i < m; ++i) cmx = fmaxf(cmx, csc[i]);
+        for (int i = 0; i < me; ++i) cmx = fmaxf(cmx, csc[i]);
         float csum = 0.f;
-        for (int i = 0; i < m; ++i) csum += expf(csc[i] - cmx);
+        for (int i = 0; i < me; ++i) csum += expf(csc[i] - cmx);
         float o = 0.f;
-        for (int i = 0; i < m; ++i) o = fmaf(expf(csc[i] - cmx) / csum, valb[(int64_t)i * 256], o);
+        for (int i = 0; i < me; ++i) o = fmaf(expf(csc[i] - cmx) / csum, valb[(int64_t)i * 256], o);
         p.cc_frag[frag16_index(b, tid, 256)] = o;
         if constexpr (TRAIN) {
             if (tr->cc_plain) tr->cc_plain[(int64_t)b * 256 + tid] = o;
@@ -1143,14 +1152,16 @@ __device__ __forceinline__ void content_block_long(const AttnP& p, int b, float*
 
 // Content.forward (decoder.py:262-271) for one batch row: alpha = softmax_m(SiLU(..)*tau_c . key), cc = alpha @ value
 // (m <= 16: two key rows per wave and the values in registers; longer clips take content_block_long)
-template <bool TRAIN = false>
-__device__ __forceinline__ void content_block(const AttnP& p, int b, float* sm, const AttnTrain* tr = nullptr) {
-    if (p.m > 16) { content_block_long<TRAIN>(p, b, sm, tr); return; }
+// ML: the clip uses the first `mb` <= m of its m slots (rows laid out for m): soft-max and alpha @ value over those, as a solo call with m = mb
+template <bool TRAIN = false, bool ML = false>
+__device__ __forceinline__ void content_block(const AttnP& p, int b, float* sm, const AttnTrain* tr = nullptr, int mb = 0) {
+    if (p.m > 16) { content_block_long<TRAIN, ML>(p, b, sm, tr, mb); return; }
     float* qs = sm;                  // 256
     float* csc = sm + 512;           // 16
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int m = p.m;
+    const int m = p.m;                              // slot stride of key / value
+    const int me = ML ? mb : m;                     // slots the clip uses
     const int col = tid & 255;
     const float* const pqc = p.qc; const float* const pkey = p.ckey; const float* const pval = p.cval; const float* const ptc = p.tau_c;
     float* const pcc = p.cc_frag; const int ldqc = p.ldqc;
@@ -1163,18 +1174,18 @@ __device__ __forceinline__ void content_block(const AttnP& p, int b, float* sm, 
 #pragma unroll
     for (int r = 0; r < 2; ++r) {
         const int i = wave + 8 * r;
-        if (i < m) kk[r] = *reinterpret_cast<const float4*>(keyb + (int64_t)i * 256);
+        if (i < me) kk[r] = *reinterpret_cast<const float4*>(keyb + (int64_t)i * 256);
     }
     float vals[16];
 #pragma unroll
-    for (int i = 0; i < 16; ++i) vals[i] = i < m ? valb[(int64_t)i * 256] : 0.f;
+    for (int i = 0; i < 16; ++i) vals[i] = i < me ? valb[(int64_t)i * 256] : 0.f;
     if (tid < 256) qs[tid] = qv * tau_c;
     __syncthreads();
     const float* q4 = qs + lane * 4;
 #pragma unroll
     for (int r = 0; r < 2; ++r) {
         const int i = wave + 8 * r;
-        if (i < m) {
+        if (i < me) {
             double d = (double)q4[0] * kk[r].x + (double)q4[1] * kk[r].y + (double)q4[2] * kk[r].z + (double)q4[3] * kk[r].w;
             d = wave_sum_d(d);
             if (lane == 0) csc[i] = (float)d;
@@ -1183,13 +1194,13 @@ __device__ __forceinline__ void content_block(const AttnP& p, int b, float* sm, 
     __syncthreads();
     if (tid < 256) {
         float cmx = -INFINITY;
-        for (int i = 0; i < m; ++i) cmx = fmaxf(cmx, csc[i]);
+        for (int i = 0; i < me; ++i) cmx = fmaxf(cmx, csc[i]);
         float csum = 0.f;
-        for (int i = 0; i < m; ++i) csum += expf(csc[i] - cmx);
+        for (int i = 0; i < me; ++i) csum += expf(csc[i] - cmx);
         float o = 0.f;
 #pragma unroll
         for (int i = 0; i < 16; ++i)
-            if (i < m) o = fmaf(expf(csc[i] - cmx) / csum, vals[i], o);
+            if (i < me) o = fmaf(expf(csc[i] - cmx) / csum, vals[i], o);
         pcc[frag16_index(b, tid, 256)] = o;
         if constexpr (TRAIN) {
             if (tr->cc_plain) tr->cc_plain[(int64_t)b * 256 + tid] = o;

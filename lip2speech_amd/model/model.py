@@ -98,6 +98,10 @@ class Lip2Speech(NativeBacked):
         self.vgg_face = FaceRecognizer()
         self.encoder = VideoExtractor()
         self.decoder = Decoder()
+        # Off (the default): `video_lengths` is ignored as in the reference, whatever hparams.mask_padding says (nothing reads that).  On: eval-mode
+        # `forward` hands the `video_lengths` it receives to `l2s_forward_eval_masked` - every clip of a ZERO-padded batch then comes out as it would
+        # alone (include/l2s.h "per-clip video lengths").  train() mode has no masked form: `forward` raises NotImplementedError.
+        self.honour_video_lengths = False
         # one packed weight blob for the whole path; the sub-modules borrow it while they live inside this model
         self.encoder.__dict__["_native_parent"] = self
         self.decoder.__dict__["_native_parent"] = self
@@ -166,6 +170,10 @@ class Lip2Speech(NativeBacked):
 
     def forward(self, video_frames, face_frames, audio_frames, melspecs, video_lengths, audio_lengths, melspec_lengths,
                 tf_ratio, speaker_embedding=None, gumbel_noise=None, dropout_masks=None):
+        masked = bool(self.honour_video_lengths) and video_lengths is not None
+        if masked and (self.training or (torch.is_grad_enabled() and any(p.requires_grad for p in self.decoder.parameters()))):
+            raise NotImplementedError("honour_video_lengths: the training entry points have no length-masked form (include/l2s.h); "
+                                      "use it in eval() mode under torch.no_grad()")
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.decoder.parameters()):
             return self._forward_train(video_frames, face_frames, melspecs, video_lengths, tf_ratio, speaker_embedding, gumbel_noise, dropout_masks)
         if self.training:
@@ -177,7 +185,8 @@ class Lip2Speech(NativeBacked):
             outputs = self.decoder(vis, face, melspecs, video_lengths, melspec_lengths, tf_ratio, gumbel_noise=gumbel_noise)
             return outputs + [video_lengths]
         job = self._forward_job(video_frames, face_frames, melspecs, video_lengths, tf_ratio, speaker_embedding, gumbel_noise)
-        out = self.native_model().forward_eval(job["video"], job["emb"], job["gumbel"], job["S"], teacher=job.get("teacher"), teacher_mask=job.get("mask"))
+        out = self.native_model().forward_eval(job["video"], job["emb"], job["gumbel"], job["S"], teacher=job.get("teacher"), teacher_mask=job.get("mask"),
+                                               video_lengths=video_lengths if masked else None)
         return job["finish"](out)
 
     def _forward_job(self, video_frames, face_frames, melspecs, video_lengths, tf_ratio, speaker_embedding=None, gumbel_noise=None):
@@ -264,6 +273,8 @@ class Lip2Speech(NativeBacked):
         Batches group when they share shape, S and scheduled-sampling mask (always at tf_ratio = 1: no step is teacher-forced)."""
         if self.training:
             raise RuntimeError("forward_many is the evaluate path: call .eval() first (train() mode trains through forward / backward)")
+        if self.honour_video_lengths:
+            raise NotImplementedError("honour_video_lengths: the grouped entry points have no length-masked form (include/l2s.h); call forward per batch")
         self.native_model()
 
         def prep(item):
@@ -298,12 +309,17 @@ class Lip2Speech(NativeBacked):
                                                              gumbel_noise.detach().to(torch.float32).contiguous(), melspecs, mask if any(mask) else None, drop)
         return [mel, mel_post, stop, emb, attn, dis, video_lengths]
 
-    def inference(self, video_frames, face_frames, speaker_embedding=None, return_attention_map=False, gumbel_noise=None, early_stop=None):
+    def inference(self, video_frames, face_frames, speaker_embedding=None, return_attention_map=False, gumbel_noise=None, early_stop=None,
+                  video_lengths=None, **kwargs):
         """The reference's `Lip2Speech.inference` (model.py:43-59).  `early_stop` (not in the reference; default `None` = leave the model's option
         "early_stop" as it is, off unless set): `True` / `False` sets the option for this MODEL before the call.  On: the decode loop ends once
         every clip of the batch has crossed its stop token (plus the post-net's 10-frame margin) instead of running all `max_decoder_steps`;
         `output_lengths` and every frame below a clip's length are what the full loop gives, the frames at or past it - which every caller
-        drops - come back as exact zeros.  A model shared by threads should set it once (`set_early_stop`), not per call."""
+        drops - come back as exact zeros.  A model shared by threads should set it once (`set_early_stop`), not per call.
+        `video_lengths` (not read by the reference, whose signature takes it through `**kwargs`; default `None` = lengths ignored as there): the
+        frame count of every clip of a batch ZERO-padded to T, B integers in [7, T] - the call then runs `l2s_inference_masked`, and every clip
+        comes out as it would alone (its attention columns past its length are zeros).  Other keyword arguments are accepted and ignored,
+        as by the reference."""
         self.set_early_stop(early_stop)
         with torch.no_grad():
             emb = self._speaker(face_frames, speaker_embedding)
@@ -311,7 +327,7 @@ class Lip2Speech(NativeBacked):
             if gumbel_noise is None:
                 gumbel_noise = Decoder.draw_gumbel(B * native.min_T(T), video_frames.device)
             mel, lengths, attn = self.native_model().inference(
-                video_frames, emb, gumbel_noise, S=self.decoder.hparams.max_decoder_steps, want_attn=return_attention_map)
+                video_frames, emb, gumbel_noise, S=self.decoder.hparams.max_decoder_steps, want_attn=return_attention_map, video_lengths=video_lengths)
         if return_attention_map:
             return mel, lengths, attn
         return mel, lengths

@@ -30,6 +30,7 @@ ABI_SYMBOLS = (
     "l2s_model_create", "l2s_model_set_tensor", "l2s_model_finalize", "l2s_model_destroy",
     "l2s_min_T", "l2s_workspace_bytes", "l2s_state_floats", "l2s_state_offset",
     "l2s_encoder_fwd", "l2s_normalise_pad_frames", "l2s_build_visual", "l2s_decoder_prologue", "l2s_decode_steps", "l2s_postnet",
+    "l2s_workspace_bytes_masked", "l2s_masked_bilstm_plan", "l2s_inference_masked", "l2s_forward_eval_masked", "l2s_decoder_prologue_masked", "l2s_decode_steps_masked",
     "l2s_output_lengths", "l2s_inference", "l2s_inference_multi", "l2s_workspace_bytes_multi", "l2s_forward_eval", "l2s_forward_eval_multi", "l2s_model_set_option", "l2s_persist_available", "l2s_persist_timeouts", "l2s_set_thread_chains", "l2s_speaker_workspace_bytes", "l2s_speaker_encoder_fwd",
     "l2s_face_workspace_bytes", "l2s_face_encoder_fwd",
     "l2s_inverse_mel_workspace_bytes", "l2s_inverse_mel", "l2s_griffin_lim_workspace_bytes", "l2s_griffin_lim", "l2s_estoi_workspace_bytes", "l2s_estoi",
@@ -174,6 +175,17 @@ def _bind(L: ctypes.CDLL) -> None:
     L.l2s_estoi.argtypes = [_fp, _fp, _i, _i, _fp, _i, _i, _i, _i, _i, ctypes.POINTER(ctypes.c_int), _fp, _vp, _i64, _vp]
     L.l2s_profile_enable.argtypes = [_i]
     L.l2s_profile_get.argtypes = [_i, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(_i64), ctypes.POINTER(ctypes.c_double)]
+    # per-clip video lengths: the unmasked signature plus the host length array.  A library of the same ABI version built before these entry points
+    # existed still binds (tools/masked_lengths/time_masked_lengths.py times one next to this build); lib() itself is checked against ABI_SYMBOLS by build()
+    if hasattr(L, "l2s_inference_masked"):
+        _lens = ctypes.POINTER(ctypes.c_int32)
+        L.l2s_workspace_bytes_masked.argtypes = [_i] * 5
+        L.l2s_workspace_bytes_masked.restype = _i64
+        L.l2s_masked_bilstm_plan.argtypes = [_lens, _i, _i, _lens, _lens, ctypes.POINTER(_i), ctypes.POINTER(_i)]
+        L.l2s_inference_masked.argtypes = L.l2s_inference.argtypes + [_lens]
+        L.l2s_forward_eval_masked.argtypes = L.l2s_forward_eval.argtypes + [_lens]
+        L.l2s_decoder_prologue_masked.argtypes = L.l2s_decoder_prologue.argtypes + [_lens]
+        L.l2s_decode_steps_masked.argtypes = L.l2s_decode_steps.argtypes + [_lens]
 
 
 def _bind_diag(L: ctypes.CDLL) -> None:
@@ -228,6 +240,36 @@ def min_T(T: int) -> int:
     return int(lib().l2s_min_T(T))
 
 
+def video_lengths_array(video_lengths, B: int, T: int):
+    """The `video_lengths` argument of the `*_masked` entry points (include/l2s.h "per-clip video lengths"), checked BEFORE the native call: a
+    1-D sequence / integer tensor of B lengths in [7, T] -> a host `int32[B]` ctypes array.  A device tensor is copied to the host (the library
+    plans its launches from the lengths).  Raises `TypeError` for a non-integer dtype, `ValueError` for a wrong shape or a length out of range."""
+    if isinstance(video_lengths, torch.Tensor):
+        if video_lengths.is_floating_point() or video_lengths.is_complex() or video_lengths.dtype == torch.bool:
+            raise TypeError(f"video_lengths must hold integers, got {video_lengths.dtype}")
+        arr = video_lengths.detach().cpu().numpy()
+    else:
+        arr = np.asarray(video_lengths)
+        if arr.dtype.kind not in "iu":
+            raise TypeError(f"video_lengths must hold integers, got {arr.dtype}")
+    if arr.shape != (B,):
+        raise ValueError(f"video_lengths must have shape ({B},) - one length per clip - got {tuple(arr.shape)}")
+    bad = [(b, int(v)) for b, v in enumerate(arr) if v < 7 or v > T]
+    if bad:
+        raise ValueError(f"video_lengths outside [7, T = {T}]: " + ", ".join(f"clip {b}: {v}" for b, v in bad))
+    return (ctypes.c_int32 * B)(*[int(v) for v in arr])
+
+
+def masked_bilstm_plan(video_lengths, T: int):
+    """`l2s_masked_bilstm_plan`: (capture_steps, reset_steps) of the BiLSTM recurrence for these lengths - a pure host function of the library."""
+    B = len(video_lengths)
+    lens = (ctypes.c_int32 * B)(*[int(v) for v in video_lengths])
+    cap, rst = (ctypes.c_int32 * B)(), (ctypes.c_int32 * B)()
+    nc, nr = _i(), _i()
+    check(lib().l2s_masked_bilstm_plan(lens, B, int(T), cap, rst, ctypes.byref(nc), ctypes.byref(nr)))
+    return list(cap[:nc.value]), list(rst[:nr.value])
+
+
 class NativeModel:
     """Owns an ``l2s_model`` (the packed device weight blob)."""
 
@@ -264,8 +306,10 @@ class NativeModel:
         self._check(L.l2s_model_finalize(self._h, _stream()))
 
     # ------------------------------------------------------------------ workspace (caller-owned, cached)
-    def workspace(self, B: int, T: int, H: int, W: int, S: int, device, G: int = 0) -> torch.Tensor:
+    def workspace(self, B: int, T: int, H: int, W: int, S: int, device, G: int = 0, masked: bool = False) -> torch.Tensor:
         need = int(self._L.l2s_workspace_bytes_multi(G, B, T, H, W, S)) if G else int(self._L.l2s_workspace_bytes(B, T, H, W, S))
+        if masked:
+            need = int(self._L.l2s_workspace_bytes_masked(B, T, H, W, S))
         ws = getattr(self._tls, "ws", None)
         if ws is None or ws.numel() < need or ws.device != device:
             ws = self._tls.ws = torch.empty(need, dtype=torch.uint8, device=device)
@@ -281,22 +325,29 @@ class NativeModel:
         self._check(self._L.l2s_encoder_fwd(self._h, _ptr(video), B, T, H, W, _ptr(feat), _ptr(ws), ws.numel(), _stream()))
         return feat
 
-    def decoder_prologue(self, vis: torch.Tensor, emb: torch.Tensor, gumbel: torch.Tensor, want_dis: bool = True):
+    def decoder_prologue(self, vis: torch.Tensor, emb: torch.Tensor, gumbel: torch.Tensor, want_dis: bool = True, video_lengths=None):
+        """`video_lengths` (B integers in [7, T]): `l2s_decoder_prologue_masked` - hand the same lengths to `decode_steps`."""
         vis, emb, gumbel = _f32(vis), _f32(emb), _f32(gumbel)
         B, T, C = vis.shape
+        lens = video_lengths_array(video_lengths, B, T) if video_lengths is not None else None
         assert C == 1024 and emb.shape == (B, 256)
         m = min_T(T)
         assert m == 0 or gumbel.shape == (B * m, 501), f"gumbel noise must be {(B * m, 501)}"
         state = torch.zeros(int(self._L.l2s_state_floats(B, T)), dtype=torch.float32, device=vis.device)
         dis = torch.empty(B * m, 501, dtype=torch.float32, device=vis.device) if want_dis else None
-        ws = self.workspace(B, T, 96, 96, 1, vis.device)
+        ws = self.workspace(B, T, 96, 96, 1, vis.device, masked=lens is not None)
+        if lens is not None:
+            self._check(self._L.l2s_decoder_prologue_masked(self._h, _ptr(vis), _ptr(emb), _ptr(gumbel), B, T, _ptr(state), _ptr(dis),
+                                                            _ptr(ws), ws.numel(), _stream(), lens))
+            return state, dis
         self._check(self._L.l2s_decoder_prologue(self._h, _ptr(vis), _ptr(emb), _ptr(gumbel), B, T, _ptr(state), _ptr(dis),
                                          _ptr(ws), ws.numel(), _stream()))
         return state, dis
 
     def decode_steps(self, state: torch.Tensor, B: int, T: int, S: int, teacher: Optional[torch.Tensor] = None,
-                     teacher_mask=None, want_attn: bool = True, attn_logits: bool = False):
+                     teacher_mask=None, want_attn: bool = True, attn_logits: bool = False, video_lengths=None):
         dev = state.device
+        lens = video_lengths_array(video_lengths, B, T) if video_lengths is not None else None
         mel = torch.empty(B, S, 80, dtype=torch.float32, device=dev)
         stop = torch.empty(B, S, dtype=torch.float32, device=dev)
         attn = torch.empty(B, S, T, dtype=torch.float32, device=dev) if want_attn else None
@@ -309,7 +360,11 @@ class NativeModel:
             mask_buf = mask_np.ctypes.data_as(_vp)
         else:
             teacher = None
-        ws = self.workspace(B, T, 96, 96, S, dev)
+        ws = self.workspace(B, T, 96, 96, S, dev, masked=lens is not None)
+        if lens is not None:
+            self._check(self._L.l2s_decode_steps_masked(self._h, _ptr(state), B, T, S, _ptr(teacher), mask_buf, _ptr(mel), _ptr(stop),
+                                                        _ptr(attn), 1 if attn_logits else 0, _ptr(ws), ws.numel(), _stream(), lens))
+            return mel, stop, attn
         self._check(self._L.l2s_decode_steps(self._h, _ptr(state), B, T, S, _ptr(teacher), mask_buf, _ptr(mel), _ptr(stop),
                                      _ptr(attn), 1 if attn_logits else 0, _ptr(ws), ws.numel(), _stream()))
         return mel, stop, attn
@@ -325,11 +380,40 @@ class NativeModel:
         return out, cf
 
     def forward_eval(self, video: torch.Tensor, emb: torch.Tensor, gumbel: torch.Tensor, S: int, teacher: Optional[torch.Tensor] = None,
-                     teacher_mask=None):
+                     teacher_mask=None, video_lengths=None):
         """`Lip2Speech.forward(..., tf_ratio)` in eval mode as ONE native call (`l2s_forward_eval`; what evaluate.py runs, evaluate.py:38):
         S = mels.shape[2] steps, free-running unless `teacher` (B,S,80) = cat(BOS, mels)[:, :S] and the per-step `teacher_mask` are given.
-        Returns (mel (B,80,S), mel_post (B,80,S), stop (B,S), attention LOGITS (B,S,T), content_dis)."""
-        return self.forward_eval_multi([(video, emb, gumbel, teacher)], S, teacher_mask=teacher_mask)[0]
+        Returns (mel (B,80,S), mel_post (B,80,S), stop (B,S), attention LOGITS (B,S,T), content_dis).
+        `video_lengths` (B integers in [7, T]; the clips ZERO-padded to T): `l2s_forward_eval_masked` - row b is what clip b alone at T = len_b
+        gives; logits of the columns t >= len_b are -inf, content_dis rows past a clip's min_T(len_b) slots are zeros."""
+        if video_lengths is None:
+            return self.forward_eval_multi([(video, emb, gumbel, teacher)], S, teacher_mask=teacher_mask)[0]
+        video, emb, gumbel = _f32(video), _f32(emb), _f32(gumbel)
+        B, _, T, H, W = video.shape
+        m = min_T(T)
+        if emb.shape != (B, 256) or gumbel.shape != (B * m, 501):
+            raise ValueError(f"emb must be {(B, 256)} and the gumbel noise {(B * m, 501)}, got {tuple(emb.shape)} and {tuple(gumbel.shape)}")
+        lens = video_lengths_array(video_lengths, B, T)
+        mask_buf = mask_np = None
+        if teacher_mask is not None and any(teacher_mask):
+            mask_np = np.ascontiguousarray(np.asarray(teacher_mask, dtype=np.uint8))
+            assert mask_np.shape == (S,)
+            mask_buf = mask_np.ctypes.data_as(_vp)
+            teacher = _f32(teacher)
+            assert teacher.shape == (B, S, 80), "teacher frames are (B,S,80) = cat(BOS, mels)[:, :S]"
+        else:
+            teacher = None
+        dev = video.device
+        mel_cf = torch.empty(B, 80, S, dtype=torch.float32, device=dev)
+        mel_post = torch.empty(B, 80, S, dtype=torch.float32, device=dev)
+        stop = torch.empty(B, S, dtype=torch.float32, device=dev)
+        attn = torch.empty(B, S, T, dtype=torch.float32, device=dev)
+        dis = torch.empty(B * m, 501, dtype=torch.float32, device=dev)
+        self.calls["l2s_forward_eval_masked"] += 1
+        ws = self.workspace(B, T, H, W, S, dev, masked=True)
+        self._check(self._L.l2s_forward_eval_masked(self._h, _ptr(video), _ptr(emb), _ptr(gumbel), B, T, H, W, S, _ptr(teacher), mask_buf, _ptr(mel_cf),
+                                                    _ptr(mel_post), _ptr(stop), _ptr(attn), _ptr(dis), _ptr(ws), ws.numel(), _stream(), lens))
+        return mel_cf, mel_post, stop, attn, dis
 
     def forward_eval_multi(self, batches, S: int, teacher_mask=None):
         """Grouped `forward_eval` (`l2s_forward_eval_multi`): up to 8 (video, emb, gumbel[, teacher]) tuples of one shape through ONE launch
@@ -381,22 +465,37 @@ class NativeModel:
         mel_post, mel_cf = self.postnet(mel, want_cf=True)
         return mel_cf, mel_post, stop, attn, dis
 
-    def inference(self, video: torch.Tensor, emb: torch.Tensor, gumbel: torch.Tensor, S: int = 300, want_attn: bool = False):
+    def inference(self, video: torch.Tensor, emb: torch.Tensor, gumbel: torch.Tensor, S: int = 300, want_attn: bool = False, video_lengths=None):
+        """`video_lengths` (B integers in [7, T]; the clips ZERO-padded to T): `l2s_inference_masked` - row b is what clip b alone at T = len_b
+        gives, attention columns t >= len_b are zeros; clip b uses the first min_T(len_b) of its min_T(T) Gumbel rows."""
         video, emb, gumbel = _f32(video), _f32(emb), _f32(gumbel)
         B, _, T, H, W = video.shape
+        lens = None
+        if video_lengths is not None:
+            if emb.shape != (B, 256) or gumbel.shape != (B * min_T(T), 501):
+                raise ValueError(f"emb must be {(B, 256)} and the gumbel noise {(B * min_T(T), 501)}, got {tuple(emb.shape)} and {tuple(gumbel.shape)}")
+            lens = video_lengths_array(video_lengths, B, T)
         mel_post = torch.empty(B, 80, S, dtype=torch.float32, device=video.device)
         lengths = torch.empty(B, dtype=torch.int64, device=video.device)
         attn = torch.empty(B, S, T, dtype=torch.float32, device=video.device) if want_attn else None
+        if lens is not None:
+            self.calls["l2s_inference_masked"] += 1
+            ws = self.workspace(B, T, H, W, S, video.device, masked=True)
+            self._check(self._L.l2s_inference_masked(self._h, _ptr(video), _ptr(emb), _ptr(gumbel), B, T, H, W, S, _ptr(mel_post),
+                                                     _ptr(lengths), _ptr(attn), _ptr(ws), ws.numel(), _stream(), lens))
+            return mel_post, lengths, attn
         self.calls["l2s_inference"] += 1
         ws = self.workspace(B, T, H, W, S, video.device)
         self._check(self._L.l2s_inference(self._h, _ptr(video), _ptr(emb), _ptr(gumbel), B, T, H, W, S, _ptr(mel_post),
                                   _ptr(lengths), _ptr(attn), _ptr(ws), ws.numel(), _stream()))
         return mel_post, lengths, attn
 
-    def inference_multi(self, batches, S: int = 300, want_attn: bool = False):
+    def inference_multi(self, batches, S: int = 300, want_attn: bool = False, video_lengths=None):
         """Grouped inference (`l2s_inference_multi`): `batches` = up to 8 (video, emb, gumbel) tuples of the same shape, advanced through ONE
         launch chain.  Returns [(mel_post (B,80,S), lengths (B,), attn (B,S,T) or None)] - views of one allocation, each bit-identical to
         `inference` on that batch."""
+        if video_lengths is not None:
+            raise NotImplementedError("the grouped entry points have no length-masked form (include/l2s.h): call inference(..., video_lengths=) per batch")
         G = len(batches)
         assert 1 <= G <= 8, "1..8 batches per group"
         vids = [_f32(b[0]) for b in batches]

@@ -5,9 +5,12 @@ The inference path has no exchange step: clips are independent, so N ranks (one 
 same kernels.  The only communication is the host-side gather of per-clip results (metrics, lengths), done with
 ``all_gather_object`` over whatever backend the job uses ("nccl" = RCCL on the GPU box, "gloo" in the CPU tests).
 
-Padding note: the model ignores lengths, so zero-padded frames change results.  ``shard_batches``
-therefore never re-pads: it cuts a list of already collated batches, so every batch keeps the composition the
-single-process run would have used and results are identical to it.
+Padding note: by default the model ignores lengths as the reference does, so zero-padded frames
+change results.  ``shard_batches`` therefore never re-pads: it cuts a list of already collated batches, so every
+batch keeps the composition the single-process run would have used and results are identical to it.  With the
+length-masked entry points (``NativeModel.inference(..., video_lengths=)``, ``Lip2Speech.honour_video_lengths``;
+include/l2s.h "per-clip video lengths") a clip's output no longer depends on what shares its batch - but the pools
+below drive the grouped entry points, which have no masked form: masked calls go one batch per call.
 """
 from __future__ import annotations
 
