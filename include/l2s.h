@@ -361,6 +361,16 @@ int l2s_train_encoder_bwd(l2s_model* m, const float* video, int B, int T, int H,
  *                            overwrites mel / stop / attention with NaN and counts in l2s_persist_timeouts(); the NEXT persistent-eligible call on that
  *                            device fails once with that error, later ones take the launch path until the option is set to a positive value again
  *                            (which re-arms the device).  0 = always four launches per step; l2s_*_multi never uses it
+ *   "persist_frames"    (32) the longest clip, in frames, whose calls take the persistent forms above.  At the default only clips of <= 32 frames do,
+ *                            exactly as before the option existed.  Above 32 (the built maximum is 80: GRID's 75-frame clips, AVSpeech's 26-50) clips
+ *                            of 33 .. min(value, 80) frames take the long-clip forms of the same loop: two key frames per thread in registers, the keys
+ *                            of frames 64 .. 79 in LDS, a soft-max lane carrying two frames (256 VGPRs + 216 AGPRs, no scratch; LDS <= 134 KB), and
+ *                            for one or two clips the persistent BiLSTM of the prologue as well.  Clips of <= 32 frames launch the same kernels
+ *                            whatever the value; masked, teacher-forced, grouped and "use_graph" calls and clips of more than 80 frames keep the launch
+ *                            path; "early_stop" composes.  Same bounds as the short forms (5e-4 of the launch path, 1e-3 of the reference); where
+ *                            a long form does not fit one workgroup per compute unit the long envelope alone is off on that device.  Measured
+ *                            against the launch path, same call, S = 300 (profiles/persist_long_times.txt): one clip of 75 frames 9.6 -> 3.8 ms,
+ *                            two 9.5 -> 4.0, four (two launches in sequence) 10.2 -> 7.5; 50 frames: 8.5 -> 3.5, 8.3 -> 3.7, 8.7 -> 6.8
  *   "use_graph"         (0)  replay the decode loop from a captured hipGraph (BASELINE config 4's streaming decoder; slower than plain launches
  *                            on this runtime at every size measured, so off by default)
  *   "fold_step_weights" (1)  4-launch step with pre-multiplied prenet1*fc_out and attention_proj hoisted onto the values; 0 = the literal 6-phase

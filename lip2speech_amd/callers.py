@@ -26,15 +26,18 @@ from . import native
 
 
 def demo_clip(net, batch, speaker_encoder=None, speaker_embedding: Optional[torch.Tensor] = None, device="cuda", encoding: str = "voice",
-              early_stop: bool = False, honour_lengths: bool = False):
+              early_stop: bool = False, honour_lengths: bool = False, persist_frames: int = 0):
     """``batch`` = one item of ``DataLoader(ds, batch_size=1, collate_fn=test_collate_fn_pad)`` (one iteration of demo.py:60-90): the direct
     ``net.inference`` call, which for one clip takes the library's latency form (the decode loop as one persistent launch, option "persist_decode") -
     a single clip has no grouping to stay consistent with; ``demo_clips`` streams a whole loader through the grouped path instead.
     ``encoding="face"`` (demo.py ``--encoding face``): no embedding is passed, the model takes it from its face tower (``net.vgg_face``).
     ``early_stop``: the decode loop ends once the clip has stopped (model option "early_stop", set on ``net`` for this call and after); the
     returned mel and attention are already truncated to ``output_lengths[0]`` and are the same either way.
-    ``honour_lengths``: the batch's ``video_lengths`` go to ``net.inference(video_lengths=...)`` (a batch of several padded clips)."""
+    ``honour_lengths``: the batch's ``video_lengths`` go to ``net.inference(video_lengths=...)`` (a batch of several padded clips).
+    ``persist_frames``: 0 leaves the model's option "persist_frames" alone (32 unless set); a positive value sets it on ``net`` for this call and
+    after - above 32, clips of up to that many frames (80 at the most: a 75-frame GRID clip) take the latency form too (include/l2s.h)."""
     _check_encoding(encoding)
+    _set_persist_frames(net, persist_frames)
     if encoding == "voice" and speaker_embedding is None and speaker_encoder is None:
         raise ValueError("pass a SpeakerEncoder (voice route) or a speaker_embedding")
     (videos, vlen), (audios, _), _, face_crops, _ = batch
@@ -49,14 +52,18 @@ def demo_clip(net, batch, speaker_encoder=None, speaker_embedding: Optional[torc
 
 
 def demo_clips(net, batches: Iterable, speaker_encoder=None, speaker_embedding: Optional[torch.Tensor] = None, device="cuda",
-               group: int = 8, n_inflight: int = 3, encoding: str = "voice", early_stop: bool = False, honour_lengths: bool = False):
+               group: int = 8, n_inflight: int = 3, encoding: str = "voice", early_stop: bool = False, honour_lengths: bool = False,
+               persist_frames: int = 0):
     """demo.py:60-90 over a whole loader: per clip the speaker embedding from the VOICE tower (``--encoding voice``) or a supplied one,
     ``net.inference(..., return_attention_map=True)``, truncation to ``output_lengths[0]``.  The clips are advanced ``group`` per launch
     chain with ``n_inflight`` chains on the GPU (``Lip2Speech.inference_many``); yields ``(mel, lengths, attention)`` per clip, in order.
     ``encoding="face"``: the embedding comes from the model's face tower instead.  ``early_stop``: every group's decode loop ends once all of
     its clips have stopped (model option "early_stop", set once on ``net`` before the chains start); the yielded tensors are the same.
-    ``honour_lengths``: every batch goes through ``demo_clip`` with its ``video_lengths`` (the masked entry point has no grouped form)."""
+    ``honour_lengths``: every batch goes through ``demo_clip`` with its ``video_lengths`` (the masked entry point has no grouped form).
+    ``persist_frames``: as in ``demo_clip``, set once on ``net`` before the first clip (grouped and masked calls themselves never take the
+    persistent forms; the option is the model's and holds for its later single-clip calls)."""
     _check_encoding(encoding)
+    _set_persist_frames(net, persist_frames)
     if encoding == "voice" and speaker_embedding is None and speaker_encoder is None:
         raise ValueError("pass a SpeakerEncoder (voice route) or a speaker_embedding")
     if honour_lengths:
@@ -73,6 +80,12 @@ def demo_clips(net, batches: Iterable, speaker_encoder=None, speaker_embedding: 
     for mel, lengths, attn in net.inference_many(calls(), group=group, n_inflight=n_inflight, early_stop=bool(early_stop)):
         n = int(lengths[0])
         yield mel[:1, :, :n], lengths, attn[:, :n]
+
+
+def _set_persist_frames(net, persist_frames: int) -> None:
+    """Model option "persist_frames" (include/l2s.h): 0 leaves the model's value alone."""
+    if persist_frames:
+        net.native_model().set_option("persist_frames", int(persist_frames))
 
 
 def _check_encoding(encoding: str) -> None:

@@ -34,7 +34,8 @@ int set_option_field(Options& o, const char* name, int value) {
     static const Row product[] = {
         {"persist_decode", &Options::persist}, {"use_graph", &Options::graph}, {"fold_step_weights", &Options::fold}, {"refresh_map", &Options::refresh_map},
         {"infer_bf16", &Options::infer_bf16}, {"train_bf16", &Options::train_bf16}, {"gemm_x3", &Options::gemm_x3}, {"frontend_x3", &Options::frontend_x3},
-        {"trunk_x3", &Options::trunk_x3}, {"lstm_x3", &Options::lstm_x3}, {"early_stop", &Options::early_stop}};
+        {"trunk_x3", &Options::trunk_x3}, {"lstm_x3", &Options::lstm_x3}, {"early_stop", &Options::early_stop},
+        {"persist_frames", &Options::persist_frames}};
     for (auto& t : product)
         if (!std::strcmp(name, t.name)) { o.*(t.field) = value; return 0; }
 #ifdef L2S_DIAG
@@ -1236,7 +1237,7 @@ static int prologue_run(l2s_model* m, const float* vis, const float* emb, const 
     float* bott_part = bp.f((int64_t)8 * BT * 512);
     // one or two clips of a single-batch call: the BiLSTM recurrence as ONE persistent launch (pdecode.hip pbilstm_kernel; option "persist_decode")
     // (the envelope of the latency path; a persistent launch that timed out since the last call fails THIS call once: pdecode_gate)
-    const int pgate = (!lens && m->opt.persist > 0 && B <= m->opt.persist && !grouped_entry() && pbilstm_supported(B, T) && pdecode_supported(B, T, mT)) ? pdecode_gate() : 0;
+    const int pgate = (!lens && m->opt.persist > 0 && B <= m->opt.persist && !grouped_entry() && pbilstm_supported(B, T) && pdecode_supported(B, T, mT, m->opt.persist_frames)) ? pdecode_gate(T) : 0;
     if (pgate < 0) return 1;
     const bool pbi = pgate > 0;
     float* pbx = pbi ? bp.f(pbilstm_ws_bytes() / 4 + 64) : nullptr;
@@ -1553,7 +1554,7 @@ static int decode_run(l2s_model* m, float* state, int B, int T, int S, const flo
     if (!lens && !teacher && fold && m->opt.persist > 0 && B <= m->opt.persist && !grouped_entry()) {      // the latency form: one launch for the whole loop (never with lengths)
         const Weights& w = m->w;
         StateLayout sl = state_layout(B, T);
-        const int pgate = (pdecode_supported(B, T, sl.m) && w.vproj.W && w.pre1f.W && w.lstm0.W && w.lstm1.W) ? pdecode_gate() : 0;
+        const int pgate = (pdecode_supported(B, T, sl.m, m->opt.persist_frames) && w.vproj.W && w.pre1f.W && w.lstm0.W && w.lstm1.W) ? pdecode_gate(T) : 0;
         if (pgate < 0) return 1;      // an earlier persistent launch on this device gave up (its outputs are NaN): reported here, once
         if (pgate > 0) {
             PDecP p{};

@@ -83,8 +83,11 @@ struct Options {
                                 //   1.907 -> 1.832 at 128, 3.61 -> 3.59 at 256 - at 256 clips the kernel sits at the chip's clock under MFMA load)
     int train_bf16 = 0;         // "train_bf16": the training step's GEMMs / Conv1d stacks (forward and backward) with bf16 operands on the bf16 matrix cores
     int persist = 4;            // "persist_decode": the free-running decode loop of a single-batch call with at most this many clips (pdecode.hip: up to 4 clips
-                                //   of <= 32 frames, two per launch) as persistent weight-stationary launches instead of four launches per step; 0 = never.  A
+                                //   of <= 32 frames - "persist_frames" below: up to 80 -, two per launch) as persistent weight-stationary launches instead of four launches per step; 0 = never.  A
                                 //   latency form: one call owns the chip, such launches are chained one after the other; grouped calls (l2s_*_multi) never take it
+    int persist_frames = 32;    // "persist_frames": the longest clip (frames) whose calls take the persistent forms; above 32 the long-clip forms of the decode loop
+                                //   (pdecode.hip: two key frames per thread in registers, the keys of up to 16 more frames in LDS) serve clips of up to 80 frames.
+                                //   Values below 32 act as 32 (the short forms are "persist_decode"'s), values above 80 as 80; the default changes nothing
     int frontend_solo = 0;      // "frontend_solo" (diagnostic A/B): when chains overlap, the front-end conv takes ONE block per CU (an LDS pad) so that step kernels of other
                                 //   chains (half-CU blocks) run beside it instead of waiting for its 530-us blocks to retire
     int trunk_chain = 1;        // "trunk_chain" (diagnostic A/B): the consecutive stride-1 units of a ShuffleNet stage as ONE launch (the map stays on chip between the

@@ -9,7 +9,8 @@
 // store each and polled by the threads that consume them - the data is the flag (cdna_hip_programming.md section 6 Guideline 16 R2); a thread reads
 // exactly the granules of its own K slice, straight into registers.  Every phase consumes a full vector from all of the clip's producers, so a phase is
 // also a barrier among them and single-buffered granules are safe.  Keys (registers), projected values and content values (LDS) of the clip sit in every
-// one of its workgroups, so attention is computed whole and locally (T <= 32 frames).  Two clips share nothing: each has its half of the chip.
+// one of its workgroups, so attention is computed whole and locally (T <= 32 frames; option "persist_frames": the long-clip forms, T <= 80, keep two key
+// frames per thread in registers and the keys past frame 64 in LDS).  Two clips share nothing: each has its half of the chip.
 //
 // Measured on MI355X (profiles/r04_persist_edge_probe.txt, r04_pdecode_timeline.txt, r04_latency_path.txt): one all-to-all edge costs ~1.2 us among 128
 // workgroups and ~1.8 among 256 with the exchange buffer replicated per XCD (2.1-2.6 with all 256 polling one copy), growing linearly beyond 2 048 floats
@@ -29,12 +30,20 @@ namespace l2s {
 constexpr int PD_WG = 256;                // workgroups of a full launch = compute units (128 per clip)
 constexpr int PD_NT = 256;                // threads per workgroup
 constexpr int PD_MAXT = 32, PD_MAXM = 16, PD_MAXB = 4;
+// the long-clip forms (option "persist_frames"; clips of PD_MAXT < T <= PD_MAXT_LONG frames): PD_KF_LONG key frames per thread in registers - a third does
+// not fit (26 VGPRs spill) - and the keys of up to PD_TAIL frames past those in LDS
+constexpr int PD_KF_LONG = 2, PD_TAIL = 16;
+__host__ __device__ constexpr int pd_form_maxt(int KF) { return 32 * KF + (KF > 1 ? PD_TAIL : 0); }
+constexpr int PD_MAXT_LONG = pd_form_maxt(PD_KF_LONG);
 constexpr int PD_LDS_MIN = 84 * 1024;     // at least 84 KB of LDS per workgroup: more than half of a CU's, so the workgroups sit one per CU
 constexpr int PD_LDS_MAX = 159 * 1024;    // most dynamic LDS a launch may ask for (a few static bytes ride along)
 // LDS of a workgroup, in floats: the fixed part, then its clip's projected values V' [T4][256] and content values [m4][256] (T4, m4 = T, m rounded up to 4;
-// the rows past T / m are zero)
-__host__ __device__ constexpr int pd_lds_fixed(int V) { return 512 + 256 + 48 + 2 * 4 * 8 * V + 2 * 4 * 12 * V + 4 * 32; }
-__host__ __device__ inline int pd_lds_floats(int V, int T, int m) { return pd_lds_fixed(V) + (((T + 3) & ~3) + ((m + 3) & ~3)) * 256; }
+// the rows past T / m are zero).  MT = the form's maximum T: logits and soft-max weights are sized by it, and a long form (MT > 32) keeps the four floats of
+// the early-stop notice in its fixed part (the short forms keep it behind the values, inside PD_LDS_MIN) and, behind the values, the keys of its frames
+// past 32 PD_KF_LONG: [16 chunks][TT8 frames][8 threads] float4, TT8 = the tail frames rounded up to 8 (a wave's read is 1 KB in a row)
+__host__ __device__ constexpr int pd_lds_fixed(int V, int MT = 32) { return 512 + 256 + (MT + 16) + 2 * 4 * 8 * V + 2 * 4 * 12 * V + 4 * MT + (MT > 32 ? 4 : 0); }
+__host__ __device__ constexpr int pd_tail8(int T, int MT) { return MT > 32 && T > 32 * PD_KF_LONG ? (T - 32 * PD_KF_LONG + 7) & ~7 : 0; }
+__host__ __device__ inline int pd_lds_floats(int V, int T, int m, int MT = 32) { return pd_lds_fixed(V, MT) + (((T + 3) & ~3) + ((m + 3) & ~3)) * 256 + pd_tail8(T, MT) * 512; }
 // granule arrays of one replica, in u64 units, for NB clips: [h0 | h1 | c0 | c1 | q: NB x 512 each][qc, p1, p2: NB x 256 each]
 __host__ __device__ constexpr int pd_off_h0(int NB) { return 0; }
 __host__ __device__ constexpr int pd_off_h1(int NB) { return NB * 512; }
@@ -185,18 +194,24 @@ __device__ __forceinline__ float2 pd_w2(const float* W, int NC, int n, int k) {
 // same step: the order holds by construction (cdna_hip_programming.md section 6, guideline 16), not by the margin's slack.  All workgroups of the clip
 // therefore know the end by step s + 1 < end and leave at the top of step `end`, exactly where the full loop leaves at S: after the poll of the last
 // h1' / c1', which everybody has published - nobody waits for a workgroup that has left, and every wait is still a PdPoll.
-template <int NG, int V, bool ES = false>
+// KF (option "persist_frames"; the KF = 1 instantiations are the loop as it was): key frames per thread.  A thread holds the 64 k-values of frames
+// kf, kf + 32, .. kf + 32 (KF - 1) in registers (64 KF of them); a form with KF > 1 also serves up to PD_TAIL frames past 32 KF, whose keys sit in LDS
+// (threads kf < T - 32 KF, i.e. waves 0 and 1, form their logits after those of their register frames), so it takes clips of up to MT = 32 KF + PD_TAIL
+// frames.  The logits of a thread's register frames share one read of q from LDS, a soft-max lane carries ceil(MT / 64) frames (lane, lane + 64)
+// through the same wave max / sum, and the logits and weights in LDS are MT long.  Everything outside phase 2 and its set-up is the same code.
+template <int NG, int V, bool ES = false, int KF = 1>
 __global__ __launch_bounds__(PD_NT, 1) void pdecode_kernel(const PDecP p) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
+    constexpr int MT = pd_form_maxt(KF), NL = (MT + 63) / 64;      // most frames of the form; frames per soft-max lane
     float* const qs = sm;                                   // [512]              q * tau
     float* const qcs = qs + 512;                            // [256]              qc * tau_c
-    float* const sc = qcs + 256;                            // [48]               attention logits [0, 32), content logits [32, 48)
+    float* const sc = qcs + 256;                            // [MT + 16]          attention logits [0, MT), content logits [MT, MT + 16)
     constexpr int RS = 8 * V, RD = 12 * V;                // floats per wave: a phase's critical sums, its deferred sums
-    float* const red = sc + 48;                             // [2][4 waves][RS]   critical sums, ping-pong by phase
+    float* const red = sc + MT + 16;                        // [2][4 waves][RS]   critical sums, ping-pong by phase
     float* const redB = red + 2 * 4 * RS;                   // [4 waves][RD]      phase 1's deferred sums: W_hh1 h1', fc
     float* const redC = redB + 4 * RD;                      // [4 waves][RD]      phase 4's deferred sums: W_hh0 h0', the h0 / c0 parts of q0, q1, qc
-    float* const aws = redC + 4 * RD;                       // [4 waves][32]      each wave's softmax weights, for broadcast reads
-    float* const vs = aws + 4 * 32;                         // [T4 + m4][256]     projected values V' and content values of the clip, rows past T / m zero
+    float* const aws = redC + 4 * RD;                       // [4 waves][MT]      each wave's softmax weights, for broadcast reads
+    float* const vs = aws + 4 * MT + (MT > 32 ? 4 : 0);     // [T4 + m4][256]     projected values V' and content values of the clip, rows past T / m zero
     const int T4 = (p.T + 3) & ~3, M4 = (p.m + 3) & ~3;
 
     constexpr int WPG = PD_WG / V;                          // workgroups per clip (the launch has NG * WPG of them)
@@ -207,7 +222,7 @@ __global__ __launch_bounds__(PD_NT, 1) void pdecode_kernel(const PDecP p) {
     const int T = p.T, M = p.m, S = p.S;
     int Send = S;                                           // the clip's end step: S, or (ES) what the stop column's owner has announced
     int* const es_note = reinterpret_cast<int*>(p.status) + 4 + g;      // ES: the clip's notice word (0 = none yet; zeroed with the exchange buffer every launch)
-    int* const es_lds = reinterpret_cast<int*>(vs + (T4 + M4) * 256);   // ES: the notice as the workgroup's observer read it (the launch's LDS is >= PD_LDS_MIN: room to spare)
+    int* const es_lds = reinterpret_cast<int*>(MT > 32 ? aws + 4 * MT : vs + (T4 + M4) * 256);   // ES: the notice as the workgroup's observer read it (the launch's LDS is >= PD_LDS_MIN: room to spare; a long form: its own four floats)
     constexpr int es_obs = V * (80 / V) + ((80 % V) >> 1);   // ES: the thread whose phase-1 poll covers the h1' granules the stop column's owner publishes (unit 2 cjv + cu of tid = 80 % V in workgroup 80 / V)
     bool es_crossed = false;
     int es_val = 0;
@@ -262,16 +277,26 @@ __global__ __launch_bounds__(PD_NT, 1) void pdecode_kernel(const PDecP p) {
     const int cf = tid >> 4, cp = tid & 15;                 // content logits: 16 threads per content frame, 16 k each
     const bool o_role = wave >= 2;                          // waves 2, 3 form u[2 (tid - 128) ..] = prenet2 + o; waves 0, 1 form cc[2 tid ..] (wave-uniform: a scalar)
     const int xc = o_role ? 2 * (tid - 128) : 2 * tid;      // this thread's pair of columns of o / cc
-    float4 kreg[16], ckreg[4];
+    float4 kreg[KF][16], ckreg[4];
     const float* const vrow = vs + (o_role ? 0 : T4 * 256) + xc;      // this thread's pair of columns in LDS, row pitch 256
 #pragma unroll
-    for (int i = 0; i < 16; ++i)
-        kreg[i] = kf < T ? *reinterpret_cast<const float4*>(p.k + ((int64_t)gc * T + kf) * 512 + 4 * kp + 32 * i) : make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int r = 0; r < KF; ++r)
+#pragma unroll
+        for (int i = 0; i < 16; ++i)
+            kreg[r][i] = kf + 32 * r < T ? *reinterpret_cast<const float4*>(p.k + ((int64_t)gc * T + kf + 32 * r) * 512 + 4 * kp + 32 * i) : make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
     for (int i = 0; i < 4; ++i)
         ckreg[i] = cf < M ? *reinterpret_cast<const float4*>(p.ckey + ((int64_t)gc * M + cf) * 256 + 4 * (cp + 16 * i)) : make_float4(0.f, 0.f, 0.f, 0.f);
     for (int i = tid; i < T4 * 64; i += PD_NT)
         *reinterpret_cast<float4*>(vs + 4 * i) = i < T * 64 ? *reinterpret_cast<const float4*>(p.vp + (int64_t)gc * T * 256 + 4 * i) : make_float4(0.f, 0.f, 0.f, 0.f);
+    const int TT = T - 32 * KF, TT8 = pd_tail8(T, MT);      // KF > 1: frames whose keys sit in LDS
+    float4* const kt = reinterpret_cast<float4*>(vs + (T4 + M4) * 256);      // [16][TT8][8]: chunk i of frame 32 KF + f for thread kp
+    if constexpr (KF > 1) {
+        for (int i = tid; i < TT8 * 128; i += PD_NT) {
+            const int kp_ = i & 7, f = (i >> 3) % TT8, c = (i >> 3) / TT8;
+            kt[i] = f < TT ? *reinterpret_cast<const float4*>(p.k + ((int64_t)gc * T + 32 * KF + f) * 512 + 4 * kp_ + 32 * c) : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+    }
     for (int i = tid; i < M4 * 64; i += PD_NT)
         *reinterpret_cast<float4*>(vs + T4 * 256 + 4 * i) = i < M * 64 ? *reinterpret_cast<const float4*>(p.cval + (int64_t)gc * M * 256 + 4 * i) : make_float4(0.f, 0.f, 0.f, 0.f);
     // prenet1 of the BOS frame (step 0 has no previous h1; decoder.py:407,413): the finisher's column (fk = 3 uses it)
@@ -432,17 +457,53 @@ __global__ __launch_bounds__(PD_NT, 1) void pdecode_kernel(const PDecP p) {
             __syncthreads();                                 // qs / qcs visible to the block (and phase 1's deferred sums in redB)
             PD_STAMP(5);
             {   // logits: 8 threads per frame (keys in registers, q from LDS: the 8 frames of a wave read the same addresses), 16 threads per content frame
-                pd_f2 a01 = {0.f, 0.f}, a23 = {0.f, 0.f};     // two packed accumulators: v_pk_fma_f32, two products per instruction
                 const float* qr = qs + 4 * kp;
+                if constexpr (KF == 1) {                     // the short forms: the loop as it was (same machine code)
+                    pd_f2 a01 = {0.f, 0.f}, a23 = {0.f, 0.f};     // two packed accumulators: v_pk_fma_f32, two products per instruction
 #pragma unroll
-                for (int i = 0; i < 16; ++i) {
-                    const float4 qq = *reinterpret_cast<const float4*>(qr + 32 * i);
-                    a01 = __builtin_elementwise_fma(pd_f2{qq.x, qq.y}, pd_f2{kreg[i].x, kreg[i].y}, a01);
-                    a23 = __builtin_elementwise_fma(pd_f2{qq.z, qq.w}, pd_f2{kreg[i].z, kreg[i].w}, a23);
+                    for (int i = 0; i < 16; ++i) {
+                        const float4 qq = *reinterpret_cast<const float4*>(qr + 32 * i);
+                        a01 = __builtin_elementwise_fma(pd_f2{qq.x, qq.y}, pd_f2{kreg[0][i].x, kreg[0][i].y}, a01);
+                        a23 = __builtin_elementwise_fma(pd_f2{qq.z, qq.w}, pd_f2{kreg[0][i].z, kreg[0][i].w}, a23);
+                    }
+                    float a = (a01.x + a01.y) + (a23.x + a23.y);
+                    a += pd_dpp<0xB1>(a); a += pd_dpp<0x4E>(a); a += pd_dpp<0x141>(a);      // the 8 lanes of a frame (row_half_mirror)
+                    if (kp == 0 && kf < T) sc[kf] = a;
+                } else {
+                    pd_f2 a01[KF], a23[KF];                       // two packed accumulators per frame: v_pk_fma_f32, two products per instruction
+#pragma unroll
+                    for (int r = 0; r < KF; ++r) a01[r] = pd_f2{0.f, 0.f};
+#pragma unroll
+                    for (int r = 0; r < KF; ++r) a23[r] = pd_f2{0.f, 0.f};
+#pragma unroll
+                    for (int i = 0; i < 16; ++i) {
+                        const float4 qq = *reinterpret_cast<const float4*>(qr + 32 * i);
+#pragma unroll
+                        for (int r = 0; r < KF; ++r) {
+                            a01[r] = __builtin_elementwise_fma(pd_f2{qq.x, qq.y}, pd_f2{kreg[r][i].x, kreg[r][i].y}, a01[r]);
+                            a23[r] = __builtin_elementwise_fma(pd_f2{qq.z, qq.w}, pd_f2{kreg[r][i].z, kreg[r][i].w}, a23[r]);
+                        }
+                    }
+#pragma unroll
+                    for (int r = 0; r < KF; ++r) {
+                        float a = (a01[r].x + a01[r].y) + (a23[r].x + a23[r].y);
+                        a += pd_dpp<0xB1>(a); a += pd_dpp<0x4E>(a); a += pd_dpp<0x141>(a);      // the 8 lanes of a frame (row_half_mirror)
+                        if (kp == 0 && kf + 32 * r < T) sc[kf + 32 * r] = a;
+                    }
+                    if (kf < TT) {                            // the frames past the registers: keys from LDS (the 8 threads of a frame branch together)
+                        pd_f2 t01 = {0.f, 0.f}, t23 = {0.f, 0.f};
+                        const float4* kr = kt + kf * 8 + kp;
+#pragma unroll
+                        for (int i = 0; i < 16; ++i) {
+                            const float4 qq = *reinterpret_cast<const float4*>(qr + 32 * i), kk = kr[i * TT8 * 8];
+                            t01 = __builtin_elementwise_fma(pd_f2{qq.x, qq.y}, pd_f2{kk.x, kk.y}, t01);
+                            t23 = __builtin_elementwise_fma(pd_f2{qq.z, qq.w}, pd_f2{kk.z, kk.w}, t23);
+                        }
+                        float a = (t01.x + t01.y) + (t23.x + t23.y);
+                        a += pd_dpp<0xB1>(a); a += pd_dpp<0x4E>(a); a += pd_dpp<0x141>(a);
+                        if (kp == 0) sc[32 * KF + kf] = a;
+                    }
                 }
-                float a = (a01.x + a01.y) + (a23.x + a23.y);
-                a += pd_dpp<0xB1>(a); a += pd_dpp<0x4E>(a); a += pd_dpp<0x141>(a);      // the 8 lanes of a frame (row_half_mirror)
-                if (kp == 0 && kf < T) sc[kf] = a;
                 float c0a = 0.f, c1a = 0.f, c2a = 0.f, c3a = 0.f;
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
@@ -451,29 +512,52 @@ __global__ __launch_bounds__(PD_NT, 1) void pdecode_kernel(const PDecP p) {
                 }
                 float ca = (c0a + c1a) + (c2a + c3a);
                 ca += pd_dpp<0xB1>(ca); ca += pd_dpp<0x4E>(ca); ca += pd_dpp<0x124>(ca); ca += pd_dpp<0x128>(ca);      // the 16 lanes of a content frame
-                if (cp == 0 && cf < M) sc[32 + cf] = ca;
+                if (cp == 0 && cf < M) sc[MT + cf] = ca;
             }
             if constexpr (ES) { if (tid == es_obs) es_lds[0] = es_val; }
             __syncthreads();
             if constexpr (ES) { const int e = es_lds[0]; if (e) Send = e; }      // e > s + 1 or e == S: no decision of this step changes (next written after three more barriers)
             PD_STAMP(6);
             if (o_role) ppre = pd_load16(rs, gP2 + xc);
-            {   // every wave: softmax of its role's logits (lane = frame), then its threads' two columns of a @ V' / alpha @ value (decoder.py:414-419, 262-271)
+            {   // every wave: softmax of its role's logits (lane = frames lane, lane + 64), then its threads' two columns of a @ V' / alpha @ value (decoder.py:414-419, 262-271)
                 const int n = o_role ? T : M;
-                const bool on = lane < n;
-                const float x = on ? sc[(o_role ? 0 : 32) + lane] : -INFINITY;
-                const float mx = pd_wave_max(x);
-                const float ex = on ? expf(x - mx) : 0.f;
-                const float aw = ex * __frcp_rn(pd_wave_sum(ex));
-                if (wave == 2 && jl == 0 && on && p.attn) p.attn[((int64_t)gc * S + s) * T + lane] = p.attn_logits ? x : aw;
-                // the wave's weights through LDS (lanes past n hold 0, value rows past T / m are 0): four frames per trip, no per-frame predicate
-                if (lane < 32) aws[wave * 32 + lane] = aw;
+                if constexpr (KF == 1) {                     // the short forms: one frame per lane, as it was (same machine code)
+                    const bool on = lane < n;
+                    const float x = on ? sc[(o_role ? 0 : MT) + lane] : -INFINITY;
+                    const float mx = pd_wave_max(x);
+                    const float ex = on ? expf(x - mx) : 0.f;
+                    const float aw = ex * __frcp_rn(pd_wave_sum(ex));
+                    if (wave == 2 && jl == 0 && on && p.attn) p.attn[((int64_t)gc * S + s) * T + lane] = p.attn_logits ? x : aw;
+                    // the wave's weights through LDS (lanes past n hold 0, value rows past T / m are 0): four frames per trip, no per-frame predicate
+                    if (lane < 32) aws[wave * MT + lane] = aw;
+                } else {
+                    bool on[NL]; float x[NL], ex[NL];
+#pragma unroll
+                    for (int i = 0; i < NL; ++i) {
+                        on[i] = lane + 64 * i < n;
+                        x[i] = on[i] ? sc[(o_role ? 0 : MT) + lane + 64 * i] : -INFINITY;
+                    }
+                    float xm = x[0];
+#pragma unroll
+                    for (int i = 1; i < NL; ++i) xm = fmaxf(xm, x[i]);
+                    const float mx = pd_wave_max(xm);
+                    float es = 0.f;
+#pragma unroll
+                    for (int i = 0; i < NL; ++i) { ex[i] = on[i] ? expf(x[i] - mx) : 0.f; es = i ? es + ex[i] : ex[i]; }
+                    const float rsum = __frcp_rn(pd_wave_sum(es));
+#pragma unroll
+                    for (int i = 0; i < NL; ++i) {
+                        const float aw = ex[i] * rsum;
+                        if (wave == 2 && jl == 0 && on[i] && p.attn) p.attn[((int64_t)gc * S + s) * T + lane + 64 * i] = p.attn_logits ? x[i] : aw;
+                        if (lane + 64 * i < MT) aws[wave * MT + lane + 64 * i] = aw;
+                    }
+                }
                 __builtin_amdgcn_wave_barrier();
                 const int n4 = (n + 3) & ~3;
                 float ox = 0.f, oy = 0.f, ox2 = 0.f, oy2 = 0.f;
 #pragma unroll 2
                 for (int f = 0; f < n4; f += 4) {
-                    const float4 w4 = *reinterpret_cast<const float4*>(aws + wave * 32 + f);
+                    const float4 w4 = *reinterpret_cast<const float4*>(aws + wave * MT + f);
                     const float2 v0 = *reinterpret_cast<const float2*>(vrow + f * 256), v1 = *reinterpret_cast<const float2*>(vrow + (f + 1) * 256);
                     const float2 v2 = *reinterpret_cast<const float2*>(vrow + (f + 2) * 256), v3 = *reinterpret_cast<const float2*>(vrow + (f + 3) * 256);
                     ox = fmaf(w4.x, v0.x, ox); oy = fmaf(w4.x, v0.y, oy); ox2 = fmaf(w4.y, v1.x, ox2); oy2 = fmaf(w4.y, v1.y, oy2);
@@ -683,8 +767,11 @@ __global__ void pdecode_guard_kernel(const unsigned* status, float* a, float* b,
 }
 
 int64_t pdecode_ws_bytes(int) { return (int64_t)pd_rstride(2) * 8 * PD_MAXREP + 256; }      // laid out for two clips per launch
-bool pdecode_supported(int B, int T, int m) {
-    return B >= 1 && B <= PD_MAXB && T >= 1 && T <= PD_MAXT && m >= 1 && m <= PD_MAXM && pd_lds_floats(2, T, m) * 4 <= PD_LDS_MAX;
+// the form of a T-frame clip: one key frame per thread up to PD_MAXT, PD_KF_LONG beyond (whatever "persist_frames" says, a short clip takes the short form)
+static int pd_form_mt(int T) { return T <= PD_MAXT ? PD_MAXT : PD_MAXT_LONG; }
+bool pdecode_supported(int B, int T, int m, int max_frames) {
+    return B >= 1 && B <= PD_MAXB && T >= 1 && T <= std::min(std::max(max_frames, PD_MAXT), PD_MAXT_LONG) && m >= 1 && m <= PD_MAXM &&
+           pd_lds_floats(2, T, m, pd_form_mt(T)) * 4 <= PD_LDS_MAX;
 }
 
 // every persistent launch needs all its workgroups resident at once: two of them in flight on different streams could each hold half of the chip and
@@ -693,6 +780,7 @@ struct PdDevice {
     bool init = false;
     int cus = 0;
     bool resident = false;        // every persistent kernel fits one workgroup per compute unit AND nothing in the environment takes compute units away
+    bool resident_long = false;   // ... and so does every long-clip form of the decode loop (else clips of more than PD_MAXT frames keep the launch path)
     hipEvent_t ev = nullptr;
     unsigned* timeouts = nullptr; // pinned, device-visible word of THIS device: its launches whose workgroups gave up (pdecode_guard_kernel)
     unsigned seen = 0;            // ... of which the gate has already reported (pdecode_gate)
@@ -747,6 +835,14 @@ static PdDevice* pd_device_locked() {
             fits = pd_fits(pdecode_kernel<1, 2>, PD_LDS_MAX) && pd_fits(pdecode_kernel<2, 2>, PD_LDS_MAX) && pd_fits(pdecode_kernel<1, 2, true>, PD_LDS_MAX) && pd_fits(pdecode_kernel<2, 2, true>, PD_LDS_MAX) && pd_fits(pbilstm_kernel<1>, 0) && pd_fits(pbilstm_kernel<2>, 0);
         }
         d.resident = fits;
+        if (fits) {      // the long-clip forms ("persist_frames"): more registers; where one does not fit, the long envelope alone is off on this device
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(pdecode_kernel<1, 2, false, PD_KF_LONG>), hipFuncAttributeMaxDynamicSharedMemorySize, PD_LDS_MAX);
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(pdecode_kernel<2, 2, false, PD_KF_LONG>), hipFuncAttributeMaxDynamicSharedMemorySize, PD_LDS_MAX);
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(pdecode_kernel<1, 2, true, PD_KF_LONG>), hipFuncAttributeMaxDynamicSharedMemorySize, PD_LDS_MAX);
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(pdecode_kernel<2, 2, true, PD_KF_LONG>), hipFuncAttributeMaxDynamicSharedMemorySize, PD_LDS_MAX);
+            d.resident_long = pd_fits(pdecode_kernel<1, 2, false, PD_KF_LONG>, PD_LDS_MAX) && pd_fits(pdecode_kernel<2, 2, false, PD_KF_LONG>, PD_LDS_MAX) &&
+                              pd_fits(pdecode_kernel<1, 2, true, PD_KF_LONG>, PD_LDS_MAX) && pd_fits(pdecode_kernel<2, 2, true, PD_KF_LONG>, PD_LDS_MAX);
+        }
         d.init = true;
     }
     return &d;
@@ -764,10 +860,10 @@ bool pdecode_device_ok() {
 // persistent launch on this device gave up since the last call through the gate - its outputs are NaN - and THIS call fails once with that error
 // (l2s_last_error); the calls after it take the launch path until the device is re-armed.  The count sits in pinned host memory and is written by
 // the guard kernel at the end of the timed-out launch, so a caller that has synchronized with that launch is certain to see it here.
-int pdecode_gate() {
+int pdecode_gate(int T) {
     std::lock_guard<std::mutex> lock(g_pd_mu);
     PdDevice* const d = pd_device_locked();
-    if (!d || !d->resident) return 0;
+    if (!d || !d->resident || (T > PD_MAXT && !d->resident_long)) return 0;
     const unsigned n = __atomic_load_n(d->timeouts, __ATOMIC_RELAXED);
     if (n != d->seen) {
         d->seen = n;
@@ -787,12 +883,14 @@ void pdecode_rearm() {
 }
 
 int launch_pdecode(const PDecP& p, void* ws, int64_t ws_bytes, hipStream_t s) {
-    L2S_REQUIRE(pdecode_supported(p.B, p.T, p.m), "persistent decode: <= 4 clips of <= 32 frames whose values fit the LDS");
+    L2S_REQUIRE(pdecode_supported(p.B, p.T, p.m, PD_MAXT_LONG), "persistent decode: <= 4 clips of <= 80 frames whose values fit the LDS");
     L2S_REQUIRE(ws && ws_bytes >= pdecode_ws_bytes(2), "persistent decode: exchange buffer too small");
     std::lock_guard<std::mutex> lock(g_pd_mu);
     PdDevice* const dv = pd_device_locked();
     L2S_REQUIRE(pd_armed(dv), "persistent decode needs 256 compute units, one resident workgroup each (none masked), and no timed-out launch since the device was armed");
-    const int lds = std::max(pd_lds_floats(2, p.T, p.m) * 4, PD_LDS_MIN);
+    const bool longf = p.T > PD_MAXT;      // the long-clip forms (callers ask pdecode_gate(T) first)
+    L2S_REQUIRE(!longf || dv->resident_long, "persistent decode: the long-clip forms do not fit one workgroup per compute unit on this device");
+    const int lds = std::max(pd_lds_floats(2, p.T, p.m, pd_form_mt(p.T)) * 4, PD_LDS_MIN);
     L2S_CHECK_HIP(hipStreamWaitEvent(s, dv->ev, 0));      // a never-recorded event is complete
     ProfScope ps("decode_persistent", s);
     // clips two at a time (three or four clips: two launches one after the other - still shorter than 300 x four launches)
@@ -814,7 +912,15 @@ int launch_pdecode(const PDecP& p, void* ws, int64_t ws_bytes, hipStream_t s) {
 #else
         constexpr int starve = 0;
 #endif
-        if (p.early) {      // option "early_stop": the instantiations whose clips leave the loop on their own
+        if (longf) {        // option "persist_frames": PD_KF_LONG key frames per thread, the same loop otherwise
+            if (p.early) {
+                if (n == 1) hipLaunchKernelGGL((pdecode_kernel<1, 2, true, PD_KF_LONG>), dim3(PD_WG / 2 - starve), dim3(PD_NT), lds, s, q);
+                else hipLaunchKernelGGL((pdecode_kernel<2, 2, true, PD_KF_LONG>), dim3(PD_WG - starve), dim3(PD_NT), lds, s, q);
+            }
+            else if (n == 1) hipLaunchKernelGGL((pdecode_kernel<1, 2, false, PD_KF_LONG>), dim3(PD_WG / 2 - starve), dim3(PD_NT), lds, s, q);
+            else hipLaunchKernelGGL((pdecode_kernel<2, 2, false, PD_KF_LONG>), dim3(PD_WG - starve), dim3(PD_NT), lds, s, q);
+        }
+        else if (p.early) {      // option "early_stop": the instantiations whose clips leave the loop on their own
             if (n == 1) hipLaunchKernelGGL((pdecode_kernel<1, 2, true>), dim3(PD_WG / 2 - starve), dim3(PD_NT), lds, s, q);
             else hipLaunchKernelGGL((pdecode_kernel<2, 2, true>), dim3(PD_WG - starve), dim3(PD_NT), lds, s, q);
         }
