@@ -200,8 +200,9 @@ int l2s_inference(l2s_model* m, const float* video, const float* emb, const floa
  * State buffer of the staged pair: rows t >= len_b of L2S_ST_ENC are zeros, of L2S_ST_K / _V / _VP unspecified (finite, never read by a masked loop);
  * content keys / values of slots >= m_b unspecified / zero.  A state written by l2s_decoder_prologue_masked goes to l2s_decode_steps_masked with the
  * same lengths.
- * Options: masked calls always take the launch-per-phase route - "persist_decode" and "use_graph" do not apply to them; "early_stop",
- * "fold_step_weights" and "infer_bf16" compose.  There is no masked form of the grouped (*_multi) or training (l2s_train_*) entry points.
+ * Options: masked calls take the launch-per-phase route - "persist_decode" and "use_graph" do not apply to them - unless "persist_masked" is set
+ * (below: free-running masked calls inside the persistent envelope then take the persistent forms); "early_stop", "fold_step_weights" and
+ * "infer_bf16" compose.  There is no masked form of the grouped (*_multi) or training (l2s_train_*) entry points.
  * Workspace: l2s_workspace_bytes_masked (the unmasked size plus the device length table), for all four calls.
  * l2s_masked_bilstm_plan: the launch plan of the BiLSTM recurrence, a pure host function.  The recurrence stays T uniform launches (step s reads frame
  * s forward and frame T-1-s backward); capture_steps = the steps AFTER which a row kernel hands over the forward finals of the clips that ended there
@@ -371,6 +372,21 @@ int l2s_train_encoder_bwd(l2s_model* m, const float* video, int B, int T, int H,
  *                            a long form does not fit one workgroup per compute unit the long envelope alone is off on that device.  Measured
  *                            against the launch path, same call, S = 300 (profiles/persist_long_times.txt): one clip of 75 frames 9.6 -> 3.8 ms,
  *                            two 9.5 -> 4.0, four (two launches in sequence) 10.2 -> 7.5; 50 frames: 8.5 -> 3.5, 8.3 -> 3.7, 8.7 -> 6.8
+ *   "persist_masked"    (0)  > 0: the *_masked entry points take the persistent forms above as well, where the call is otherwise inside their envelope:
+ *                            free-running (l2s_inference_masked, l2s_decode_steps_masked without teacher frames, l2s_decoder_prologue_masked), not
+ *                            "use_graph", B <= min("persist_decode", 4), PADDED T <= max(32, min("persist_frames", 80)), l2s_persist_available().  A
+ *                            clip's workgroups read its length from the device length table and run the loop of a len_b-frame clip (the padded T is
+ *                            only the row pitch of keys, values and attention); every launch of one or two clips takes the form and the LDS of ITS
+ *                            longest clip, so two short clips under long padding take the short form.  The prologue's BiLSTM runs len_b steps per
+ *                            (direction, clip) at B <= 2; at B = 3, 4 the prologue keeps the launch route, as for unmasked calls.  Attention columns
+ *                            t >= len_b are exactly 0 (-INFINITY as logits), as on the launch route.  Row b is within 5e-4 of the masked launch route
+ *                            and 1e-3 of clip b alone on the reference; all lengths = T gives the bits of the unmasked persistent call, and a clip's
+ *                            row has the same bits beside another partner or under another padding when the clip count and the form are the same
+ *                            (DESIGN.md section 8).  "early_stop" composes.  Teacher-forced calls (l2s_forward_eval_masked, teacher frames) and
+ *                            calls outside the envelope keep the launch route, bit for bit.  0 = masked calls never take the persistent forms,
+ *                            exactly as before the option existed.  Not yet timed on an MI355X (tools/persist_masked/time_persist_masked.py writes
+ *                            profiles/persist_masked_times.txt, B = 3, 4 - two launches in sequence - included); the expectation is the unmasked
+ *                            figures under "persist_frames" above: the same loop over fewer frames
  *   "use_graph"         (0)  replay the decode loop from a captured hipGraph (BASELINE config 4's streaming decoder; slower than plain launches
  *                            on this runtime at every size measured, so off by default)
  *   "fold_step_weights" (1)  4-launch step with pre-multiplied prenet1*fc_out and attention_proj hoisted onto the values; 0 = the literal 6-phase

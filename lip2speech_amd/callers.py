@@ -26,7 +26,7 @@ from . import native
 
 
 def demo_clip(net, batch, speaker_encoder=None, speaker_embedding: Optional[torch.Tensor] = None, device="cuda", encoding: str = "voice",
-              early_stop: bool = False, honour_lengths: bool = False, persist_frames: int = 0):
+              early_stop: bool = False, honour_lengths: bool = False, persist_frames: int = 0, persist_masked: int = 0):
     """``batch`` = one item of ``DataLoader(ds, batch_size=1, collate_fn=test_collate_fn_pad)`` (one iteration of demo.py:60-90): the direct
     ``net.inference`` call, which for one clip takes the library's latency form (the decode loop as one persistent launch, option "persist_decode") -
     a single clip has no grouping to stay consistent with; ``demo_clips`` streams a whole loader through the grouped path instead.
@@ -35,9 +35,13 @@ def demo_clip(net, batch, speaker_encoder=None, speaker_embedding: Optional[torc
     returned mel and attention are already truncated to ``output_lengths[0]`` and are the same either way.
     ``honour_lengths``: the batch's ``video_lengths`` go to ``net.inference(video_lengths=...)`` (a batch of several padded clips).
     ``persist_frames``: 0 leaves the model's option "persist_frames" alone (32 unless set); a positive value sets it on ``net`` for this call and
-    after - above 32, clips of up to that many frames (80 at the most: a 75-frame GRID clip) take the latency form too (include/l2s.h)."""
+    after - above 32, clips of up to that many frames (80 at the most: a 75-frame GRID clip) take the latency form too (include/l2s.h).
+    ``persist_masked``: 0 leaves the model's option "persist_masked" alone (0 unless set: a ``honour_lengths`` call takes the launch-per-phase
+    route); a positive value sets it on ``net`` for this call and after - a ``honour_lengths`` batch of up to four clips inside the envelope
+    of "persist_decode" / "persist_frames" then takes the latency form too, each clip at its own length."""
     _check_encoding(encoding)
     _set_persist_frames(net, persist_frames)
+    _set_persist_masked(net, persist_masked)
     if encoding == "voice" and speaker_embedding is None and speaker_encoder is None:
         raise ValueError("pass a SpeakerEncoder (voice route) or a speaker_embedding")
     (videos, vlen), (audios, _), _, face_crops, _ = batch
@@ -53,17 +57,20 @@ def demo_clip(net, batch, speaker_encoder=None, speaker_embedding: Optional[torc
 
 def demo_clips(net, batches: Iterable, speaker_encoder=None, speaker_embedding: Optional[torch.Tensor] = None, device="cuda",
                group: int = 8, n_inflight: int = 3, encoding: str = "voice", early_stop: bool = False, honour_lengths: bool = False,
-               persist_frames: int = 0):
+               persist_frames: int = 0, persist_masked: int = 0):
     """demo.py:60-90 over a whole loader: per clip the speaker embedding from the VOICE tower (``--encoding voice``) or a supplied one,
     ``net.inference(..., return_attention_map=True)``, truncation to ``output_lengths[0]``.  The clips are advanced ``group`` per launch
     chain with ``n_inflight`` chains on the GPU (``Lip2Speech.inference_many``); yields ``(mel, lengths, attention)`` per clip, in order.
     ``encoding="face"``: the embedding comes from the model's face tower instead.  ``early_stop``: every group's decode loop ends once all of
     its clips have stopped (model option "early_stop", set once on ``net`` before the chains start); the yielded tensors are the same.
     ``honour_lengths``: every batch goes through ``demo_clip`` with its ``video_lengths`` (the masked entry point has no grouped form).
-    ``persist_frames``: as in ``demo_clip``, set once on ``net`` before the first clip (grouped and masked calls themselves never take the
-    persistent forms; the option is the model's and holds for its later single-clip calls)."""
+    ``persist_frames``: as in ``demo_clip``, set once on ``net`` before the first clip (grouped calls themselves never take the persistent
+    forms; the option is the model's and holds for its later single-batch calls).
+    ``persist_masked``: as in ``demo_clip``, set once on ``net`` before the first clip: with ``honour_lengths`` every batch still goes through
+    ``demo_clip``, and its masked call takes the persistent forms where it is inside their envelope (masked calls never do without it)."""
     _check_encoding(encoding)
     _set_persist_frames(net, persist_frames)
+    _set_persist_masked(net, persist_masked)
     if encoding == "voice" and speaker_embedding is None and speaker_encoder is None:
         raise ValueError("pass a SpeakerEncoder (voice route) or a speaker_embedding")
     if honour_lengths:
@@ -86,6 +93,12 @@ def _set_persist_frames(net, persist_frames: int) -> None:
     """Model option "persist_frames" (include/l2s.h): 0 leaves the model's value alone."""
     if persist_frames:
         net.native_model().set_option("persist_frames", int(persist_frames))
+
+
+def _set_persist_masked(net, persist_masked: int) -> None:
+    """Model option "persist_masked" (include/l2s.h): 0 leaves the model's value alone."""
+    if persist_masked:
+        net.native_model().set_option("persist_masked", int(persist_masked))
 
 
 def _check_encoding(encoding: str) -> None:

@@ -35,7 +35,7 @@ int set_option_field(Options& o, const char* name, int value) {
         {"persist_decode", &Options::persist}, {"use_graph", &Options::graph}, {"fold_step_weights", &Options::fold}, {"refresh_map", &Options::refresh_map},
         {"infer_bf16", &Options::infer_bf16}, {"train_bf16", &Options::train_bf16}, {"gemm_x3", &Options::gemm_x3}, {"frontend_x3", &Options::frontend_x3},
         {"trunk_x3", &Options::trunk_x3}, {"lstm_x3", &Options::lstm_x3}, {"early_stop", &Options::early_stop},
-        {"persist_frames", &Options::persist_frames}};
+        {"persist_frames", &Options::persist_frames}, {"persist_masked", &Options::persist_masked}};
     for (auto& t : product)
         if (!std::strcmp(name, t.name)) { o.*(t.field) = value; return 0; }
 #ifdef L2S_DIAG
@@ -1199,10 +1199,10 @@ static void masked_bilstm_plan(const int32_t* video_lengths, int B, int T, std::
 static int64_t len_table_bytes(int B) { return align_up((int64_t)2 * B * (int64_t)sizeof(int), 256); }
 
 // lens / lens_host (both or neither): the device length table and the host lengths it was written from - row b then computes what clip b alone at
-// T = len_b computes (always on the launch-per-step recurrence)
+// T = len_b computes (on the launch-per-step recurrence; with option "persist_masked", inside the persistent envelope, on pbilstm_kernel's masked form)
 static int prologue_run(l2s_model* m, const float* vis, const float* emb, const float* gumbel, int B, int T,
                         float* state, float* content_dis, void* ws, int64_t ws_bytes, hipStream_t s, const int* lens = nullptr,
-                        const int32_t* lens_host = nullptr) {
+                        const int32_t* lens_host = nullptr, bool free_running = true) {      // free_running = false: the prologue of a teacher-forced masked call (launch route, whatever "persist_masked" says)
     X3Scope x3scope(m->opt.infer_bf16 ? 0 : m->opt.gemm_x3);
     Bf16Scope bf16scope(m->opt.infer_bf16);      // the bf16 leg: bf16-operand GEMM / Conv1d kernels instead of the f32 / split-bf16 ones
     const Weights& w = m->w;
@@ -1237,7 +1237,7 @@ static int prologue_run(l2s_model* m, const float* vis, const float* emb, const 
     float* bott_part = bp.f((int64_t)8 * BT * 512);
     // one or two clips of a single-batch call: the BiLSTM recurrence as ONE persistent launch (pdecode.hip pbilstm_kernel; option "persist_decode")
     // (the envelope of the latency path; a persistent launch that timed out since the last call fails THIS call once: pdecode_gate)
-    const int pgate = (!lens && m->opt.persist > 0 && B <= m->opt.persist && !grouped_entry() && pbilstm_supported(B, T) && pdecode_supported(B, T, mT, m->opt.persist_frames)) ? pdecode_gate(T) : 0;
+    const int pgate = ((!lens || (m->opt.persist_masked > 0 && free_running)) && m->opt.persist > 0 && B <= m->opt.persist && !grouped_entry() && pbilstm_supported(B, T) && pdecode_supported(B, T, mT, m->opt.persist_frames)) ? pdecode_gate(T) : 0;
     if (pgate < 0) return 1;
     const bool pbi = pgate > 0;
     float* pbx = pbi ? bp.f(pbilstm_ws_bytes() / 4 + 64) : nullptr;
@@ -1266,6 +1266,7 @@ static int prologue_run(l2s_model* m, const float* vis, const float* emb, const 
     if (pbi) {
         PBiP q{};
         q.Whh0 = w.whh[0].W; q.Whh1 = w.whh[1].W; q.gin = gin; q.s_e = s_e; q.rnn = rnn; q.h_state = state + sl.h; q.cellcat = cellcat; q.B = B; q.T = T;
+        q.lens = lens;      // masked: pair (direction, clip) runs its clip's own length; the masked steps below are those of the launch route
         if (launch_pbilstm(q, pbx, pbilstm_ws_bytes(), s)) return 1;
     } else {
     // recurrence: h0 = c0 = s_e for both directions (decoder.py:386-389)
@@ -1540,7 +1541,7 @@ static int decode_launches(l2s_model* m, float* state, int B, int T, int S, cons
 
 static int decode_run(l2s_model* m, float* state, int B, int T, int S, const float* teacher, const uint8_t* teacher_mask,
                       float* mel, float* stop, float* attn, int attn_logits, void* ws, int64_t ws_bytes, hipStream_t s, bool may_stop_early,
-                      const int* lens = nullptr) {
+                      const int* lens = nullptr, const int32_t* lens_host = nullptr) {
     L2S_REQUIRE(S >= 1 && S <= L2S_MAX_STEPS, "S must be in [1, 300] (positional table)");
     const bool fold = m->opt.fold != 0 && m->folded_valid;
     // option "early_stop": free-running loops only (a teacher-forced loop's S comes from the target).  The steps the loop never reaches are exact zeros
@@ -1551,7 +1552,7 @@ static int decode_run(l2s_model* m, float* state, int B, int T, int S, const flo
         L2S_CHECK_HIP(hipMemsetAsync(stop, 0, sizeof(float) * B * S, s));
         if (attn) L2S_CHECK_HIP(hipMemsetAsync(attn, 0, sizeof(float) * B * S * T, s));
     }
-    if (!lens && !teacher && fold && m->opt.persist > 0 && B <= m->opt.persist && !grouped_entry()) {      // the latency form: one launch for the whole loop (never with lengths)
+    if ((!lens || (m->opt.persist_masked > 0 && lens_host)) && !teacher && fold && m->opt.persist > 0 && B <= m->opt.persist && !grouped_entry()) {      // the latency form: one launch for the whole loop (with lengths: option "persist_masked")
         const Weights& w = m->w;
         StateLayout sl = state_layout(B, T);
         const int pgate = (pdecode_supported(B, T, sl.m, m->opt.persist_frames) && w.vproj.W && w.pre1f.W && w.lstm0.W && w.lstm1.W) ? pdecode_gate(T) : 0;
@@ -1571,7 +1572,8 @@ static int decode_run(l2s_model* m, float* state, int B, int T, int S, const flo
             p.mel = mel; p.stop = stop; p.attn = attn; p.attn_logits = attn_logits;
             p.B = B; p.T = T; p.m = sl.m; p.S = S;
             p.early = early ? ES_MARGIN : 0;
-            return launch_pdecode(p, ws, ws_bytes, s);
+            p.lens = lens;
+            return launch_pdecode(p, ws, ws_bytes, s, lens_host);
         }
     }
     const bool use_graph = m->opt.graph && !teacher && !g_prof_on && !early && !lens;      // "early_stop" and per-clip lengths take the plain route: a replayed graph knows no control block / length table of this call
@@ -1882,11 +1884,11 @@ static int path_run(l2s_model* m, const FrameSrc& video, const float* emb, const
     const int64_t rest_bytes = ws_bytes - bp.off;
     if (lens && launch_len_table(video_lengths, B, lens, s)) return 1;
     if (encoder_run(m, video, B, T, H, W, emb, vis, nullptr, rest, rest_bytes, s)) return 1;
-    if (prologue_run(m, vis, emb, gumbel, B, T, state, o.content_dis, rest, rest_bytes, s, lens, video_lengths)) return 1;
+    if (prologue_run(m, vis, emb, gumbel, B, T, state, o.content_dis, rest, rest_bytes, s, lens, video_lengths, !teacher)) return 1;
     const bool early = m->opt.early_stop != 0 && !teacher && o.lengths;      // l2s_inference(_multi); l2s_forward_eval's S comes from the target
     const bool plain = !m->opt.overlap_postnet || g_prof_on || m->opt.graph || teacher || o.mel_cf || early || lens;      // "early_stop" and lengths take the plain route
     if (plain) {
-        if (decode_run(m, state, B, T, S, teacher, teacher_mask, mel, stop, o.attn, o.attn_logits, rest, rest_bytes, s, early, lens)) return 1;
+        if (decode_run(m, state, B, T, S, teacher, teacher_mask, mel, stop, o.attn, o.attn_logits, rest, rest_bytes, s, early, lens, video_lengths)) return 1;
         if (postnet_run(m, mel, B, S, o.mel_post, o.mel_cf, rest, rest_bytes, s)) return 1;
     } else {
         // The decode loop is a chain of small latency-bound launches that leaves most CUs idle, and the post-net of frame t
@@ -2010,7 +2012,7 @@ int l2s_decode_steps_masked(l2s_model* m, float* state, int B, int T, int S, con
     int* lens = reinterpret_cast<int*>(ws);
     if (launch_len_table(video_lengths, B, lens, (hipStream_t)stream)) return 1;
     return decode_run(m, state, B, T, S, teacher, teacher_mask, mel, stop, attn, attn_logits, (char*)ws + len_table_bytes(B), ws_bytes - len_table_bytes(B),
-                      (hipStream_t)stream, true, lens);
+                      (hipStream_t)stream, true, lens, video_lengths);
 }
 
 // Grouped inference: the G batches are rows g*B .. g*B+B-1 of ONE launch chain on ONE weight blob.  Every kernel of the path is row-independent

@@ -88,6 +88,9 @@ struct Options {
     int persist_frames = 32;    // "persist_frames": the longest clip (frames) whose calls take the persistent forms; above 32 the long-clip forms of the decode loop
                                 //   (pdecode.hip: two key frames per thread in registers, the keys of up to 16 more frames in LDS) serve clips of up to 80 frames.
                                 //   Values below 32 act as 32 (the short forms are "persist_decode"'s), values above 80 as 80; the default changes nothing
+    int persist_masked = 0;     // "persist_masked": > 0 = free-running masked calls (per-clip video lengths) inside the envelope of the two options above take the
+                                //   persistent forms too (pdecode.hip: the length-masked instantiations - a clip's workgroups run the loop of its own length; the
+                                //   prologue's BiLSTM at <= 2 clips); 0 (default) = masked calls always take the launch-per-phase route
     int frontend_solo = 0;      // "frontend_solo" (diagnostic A/B): when chains overlap, the front-end conv takes ONE block per CU (an LDS pad) so that step kernels of other
                                 //   chains (half-CU blocks) run beside it instead of waiting for its 530-us blocks to retire
     int trunk_chain = 1;        // "trunk_chain" (diagnostic A/B): the consecutive stride-1 units of a ShuffleNet stage as ONE launch (the map stays on chip between the

@@ -27,6 +27,7 @@ struct PDecP {
     int early;                            // option "early_stop": 0 = run S steps; else the margin (steps decoded past a clip's stop crossing, ES_MARGIN)
     int b0;                               // set by launch_pdecode: first clip of THIS launch (clips go two at a time)
     unsigned long long* ts; int ts_step;  // measurement (tools/pdecode_timeline.py): [256 workgroups][16] stamps of step ts_step, or null
+    const int* lens;                      // option "persist_masked": the device length table of a masked call ([B] frames, then [B] content slots), or null; T and m above are then row pitches
 };
 
 // the prologue's BiLSTM recurrence in the same form (pbilstm_kernel)
@@ -39,6 +40,7 @@ struct PBiP {
     float *cellcat;                       // [B][1024] out: final c (forward | backward)
     u64* xch; unsigned* status;           // set by launch_pbilstm
     int B, T;
+    const int* lens;                      // option "persist_masked": the device length table of a masked call (pair (d, b) runs lens[b] steps), or null
 };
 int64_t pbilstm_ws_bytes();
 bool pbilstm_supported(int B, int T);                   // one or two clips
@@ -50,6 +52,6 @@ int pdecode_timeouts();                                 // persistent launches o
 int64_t pdecode_ws_bytes(int B);                       // exchange granules + status word
 bool pdecode_supported(int B, int T, int m, int max_frames = 32);      // <= 4 clips of <= max(32, min(max_frames, 80)) frames (option "persist_frames")
 void pdecode_set_timeline(unsigned long long* ts, int step);      // non-null: thread 0 of every workgroup stamps the phases of that step
-int launch_pdecode(const PDecP& p, void* ws, int64_t ws_bytes, hipStream_t s);      // xch / status are carved from ws
+int launch_pdecode(const PDecP& p, void* ws, int64_t ws_bytes, hipStream_t s, const int32_t* lens_host = nullptr);      // xch / status are carved from ws; lens_host: the lengths p.lens was written from
 
 }  // namespace l2s

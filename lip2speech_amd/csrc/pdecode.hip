@@ -199,7 +199,12 @@ __device__ __forceinline__ float2 pd_w2(const float* W, int NC, int n, int k) {
 // (threads kf < T - 32 KF, i.e. waves 0 and 1, form their logits after those of their register frames), so it takes clips of up to MT = 32 KF + PD_TAIL
 // frames.  The logits of a thread's register frames share one read of q from LDS, a soft-max lane carries ceil(MT / 64) frames (lane, lane + 64)
 // through the same wave max / sum, and the logits and weights in LDS are MT long.  Everything outside phase 2 and its set-up is the same code.
-template <int NG, int V, bool ES = false, int KF = 1>
+// ML (option "persist_masked"; the ML = false instantiations are the loop as it was): per-clip lengths.  A workgroup reads its clip's frame count len_g
+// and slot count m_g = l2s_min_T(len_g) from the device length table (one uniform load each, kept in scalars) and runs the loop of a len_g-frame clip:
+// key registers, LDS key tail, value rows, logits, soft-max and value loop all end at len_g / m_g, and the LDS is laid out for them.  The padded T / m of
+// the call are the row pitches of p.k, p.vp, p.attn / p.ckey, p.cval and nothing else.  Attention columns len_g .. T - 1 of every step are written as 0
+// (-inf with attn_logits), as the masked launch route returns them.  The launch picks KF and its LDS size from the longest clip of the launch.
+template <int NG, int V, bool ES = false, int KF = 1, bool ML = false>
 __global__ __launch_bounds__(PD_NT, 1) void pdecode_kernel(const PDecP p) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
     constexpr int MT = pd_form_maxt(KF), NL = (MT + 63) / 64;      // most frames of the form; frames per soft-max lane
@@ -212,14 +217,20 @@ __global__ __launch_bounds__(PD_NT, 1) void pdecode_kernel(const PDecP p) {
     float* const redC = redB + 4 * RD;                      // [4 waves][RD]      phase 4's deferred sums: W_hh0 h0', the h0 / c0 parts of q0, q1, qc
     float* const aws = redC + 4 * RD;                       // [4 waves][MT]      each wave's softmax weights, for broadcast reads
     float* const vs = aws + 4 * MT + (MT > 32 ? 4 : 0);     // [T4 + m4][256]     projected values V' and content values of the clip, rows past T / m zero
-    const int T4 = (p.T + 3) & ~3, M4 = (p.m + 3) & ~3;
+    int T4 = (p.T + 3) & ~3, M4 = (p.m + 3) & ~3;
 
     constexpr int WPG = PD_WG / V;                          // workgroups per clip (the launch has NG * WPG of them)
     const int j = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
     const int g = j / WPG, jl = j - g * WPG;                // this workgroup's clip (of the launch's NG), its index among the clip's workgroups
     const int gc = p.b0 + g;                                // ... the clip's row in the caller's batch
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int T = p.T, M = p.m, S = p.S;
+    int T = p.T, M = p.m;                                   // the clip's frames and content slots ...
+    const int TP = p.T, MP = p.m, S = p.S;                  // ... and the row pitches of the call's state and attention (ML: the padded lengths)
+    if constexpr (ML) {                                     // clamped so that no table content can index past a row or past the form's registers / LDS
+        T = __builtin_amdgcn_readfirstlane(min(max(p.lens[gc], 1), min(TP, MT)));
+        M = __builtin_amdgcn_readfirstlane(min(max(p.lens[p.B + gc], 1), min(MP, PD_MAXM)));
+        T4 = (T + 3) & ~3; M4 = (M + 3) & ~3;
+    }
     int Send = S;                                           // the clip's end step: S, or (ES) what the stop column's owner has announced
     int* const es_note = reinterpret_cast<int*>(p.status) + 4 + g;      // ES: the clip's notice word (0 = none yet; zeroed with the exchange buffer every launch)
     int* const es_lds = reinterpret_cast<int*>(MT > 32 ? aws + 4 * MT : vs + (T4 + M4) * 256);   // ES: the notice as the workgroup's observer read it (the launch's LDS is >= PD_LDS_MIN: room to spare; a long form: its own four floats)
@@ -283,22 +294,22 @@ __global__ __launch_bounds__(PD_NT, 1) void pdecode_kernel(const PDecP p) {
     for (int r = 0; r < KF; ++r)
 #pragma unroll
         for (int i = 0; i < 16; ++i)
-            kreg[r][i] = kf + 32 * r < T ? *reinterpret_cast<const float4*>(p.k + ((int64_t)gc * T + kf + 32 * r) * 512 + 4 * kp + 32 * i) : make_float4(0.f, 0.f, 0.f, 0.f);
+            kreg[r][i] = kf + 32 * r < T ? *reinterpret_cast<const float4*>(p.k + ((int64_t)gc * TP + kf + 32 * r) * 512 + 4 * kp + 32 * i) : make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
     for (int i = 0; i < 4; ++i)
-        ckreg[i] = cf < M ? *reinterpret_cast<const float4*>(p.ckey + ((int64_t)gc * M + cf) * 256 + 4 * (cp + 16 * i)) : make_float4(0.f, 0.f, 0.f, 0.f);
+        ckreg[i] = cf < M ? *reinterpret_cast<const float4*>(p.ckey + ((int64_t)gc * MP + cf) * 256 + 4 * (cp + 16 * i)) : make_float4(0.f, 0.f, 0.f, 0.f);
     for (int i = tid; i < T4 * 64; i += PD_NT)
-        *reinterpret_cast<float4*>(vs + 4 * i) = i < T * 64 ? *reinterpret_cast<const float4*>(p.vp + (int64_t)gc * T * 256 + 4 * i) : make_float4(0.f, 0.f, 0.f, 0.f);
+        *reinterpret_cast<float4*>(vs + 4 * i) = i < T * 64 ? *reinterpret_cast<const float4*>(p.vp + (int64_t)gc * TP * 256 + 4 * i) : make_float4(0.f, 0.f, 0.f, 0.f);
     const int TT = T - 32 * KF, TT8 = pd_tail8(T, MT);      // KF > 1: frames whose keys sit in LDS
     float4* const kt = reinterpret_cast<float4*>(vs + (T4 + M4) * 256);      // [16][TT8][8]: chunk i of frame 32 KF + f for thread kp
     if constexpr (KF > 1) {
         for (int i = tid; i < TT8 * 128; i += PD_NT) {
             const int kp_ = i & 7, f = (i >> 3) % TT8, c = (i >> 3) / TT8;
-            kt[i] = f < TT ? *reinterpret_cast<const float4*>(p.k + ((int64_t)gc * T + 32 * KF + f) * 512 + 4 * kp_ + 32 * c) : make_float4(0.f, 0.f, 0.f, 0.f);
+            kt[i] = f < TT ? *reinterpret_cast<const float4*>(p.k + ((int64_t)gc * TP + 32 * KF + f) * 512 + 4 * kp_ + 32 * c) : make_float4(0.f, 0.f, 0.f, 0.f);
         }
     }
     for (int i = tid; i < M4 * 64; i += PD_NT)
-        *reinterpret_cast<float4*>(vs + T4 * 256 + 4 * i) = i < M * 64 ? *reinterpret_cast<const float4*>(p.cval + (int64_t)gc * M * 256 + 4 * i) : make_float4(0.f, 0.f, 0.f, 0.f);
+        *reinterpret_cast<float4*>(vs + T4 * 256 + 4 * i) = i < M * 64 ? *reinterpret_cast<const float4*>(p.cval + (int64_t)gc * MP * 256 + 4 * i) : make_float4(0.f, 0.f, 0.f, 0.f);
     // prenet1 of the BOS frame (step 0 has no previous h1; decoder.py:407,413): the finisher's column (fk = 3 uses it)
     float p1_bos;
     {
@@ -527,7 +538,7 @@ __global__ __launch_bounds__(PD_NT, 1) void pdecode_kernel(const PDecP p) {
                     const float mx = pd_wave_max(x);
                     const float ex = on ? expf(x - mx) : 0.f;
                     const float aw = ex * __frcp_rn(pd_wave_sum(ex));
-                    if (wave == 2 && jl == 0 && on && p.attn) p.attn[((int64_t)gc * S + s) * T + lane] = p.attn_logits ? x : aw;
+                    if (wave == 2 && jl == 0 && on && p.attn) p.attn[((int64_t)gc * S + s) * TP + lane] = p.attn_logits ? x : aw;
                     // the wave's weights through LDS (lanes past n hold 0, value rows past T / m are 0): four frames per trip, no per-frame predicate
                     if (lane < 32) aws[wave * MT + lane] = aw;
                 } else {
@@ -548,8 +559,14 @@ __global__ __launch_bounds__(PD_NT, 1) void pdecode_kernel(const PDecP p) {
 #pragma unroll
                     for (int i = 0; i < NL; ++i) {
                         const float aw = ex[i] * rsum;
-                        if (wave == 2 && jl == 0 && on[i] && p.attn) p.attn[((int64_t)gc * S + s) * T + lane + 64 * i] = p.attn_logits ? x[i] : aw;
+                        if (wave == 2 && jl == 0 && on[i] && p.attn) p.attn[((int64_t)gc * S + s) * TP + lane + 64 * i] = p.attn_logits ? x[i] : aw;
                         if (lane + 64 * i < MT) aws[wave * MT + lane + 64 * i] = aw;
+                    }
+                }
+                if constexpr (ML) {                          // the columns past the clip's length: what the masked launch route returns there
+                    if (wave == 2 && jl == 0 && p.attn) {
+                        const float padv = p.attn_logits ? -INFINITY : 0.f;
+                        for (int c = T + lane; c < TP; c += 64) p.attn[((int64_t)gc * S + s) * TP + c] = padv;
                     }
                 }
                 __builtin_amdgcn_wave_barrier();
@@ -677,10 +694,13 @@ __global__ __launch_bounds__(PD_NT, 1) void pdecode_kernel(const PDecP p) {
 // group as tagged granules (ping-pong by step parity: a step reads and rewrites it), the input gates W_ih x + b come from the prologue's GEMM, the cell
 // state stays in the cell threads.  Outputs as the launch path leaves them: rnn_out (B, T, 1024), the final h of both directions as the decoder's initial
 // hidden state (frag16), the final c side by side for E_C.
+// ML (option "persist_masked"; the ML = false instantiations are the kernel as it was): pair (d, b) runs len_b steps - forward over frames 0 .. len_b - 1,
+// backward over len_b - 1 .. 0, the padded T as row pitch -, takes its finals after them and writes its columns of the rnn rows len_b .. T - 1 as zeros.  No
+// pair waits for another pair, so the pairs' different trip counts add no wait.
 // ------------------------------------------------------------------------------------------------------------------------------------------------------
 __host__ __device__ constexpr int pb_granules(int NB) { return 2 * NB * 2 * 512; }      // [pair][parity][512]
 __host__ __device__ constexpr int pb_rstride(int NB) { return pb_granules(NB) + 520; }
-template <int NB>
+template <int NB, bool ML = false>
 __global__ __launch_bounds__(PD_NT, 1) void pbilstm_kernel(const PBiP p) {
     constexpr int NP = 2 * NB, WPG = PD_WG / NP, U = 512 / WPG, C = 4 * U;      // pairs, workgroups per pair, hidden units and gate columns per workgroup
     __shared__ float red[2][4][C];
@@ -689,6 +709,8 @@ __global__ __launch_bounds__(PD_NT, 1) void pbilstm_kernel(const PBiP p) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int pr = j / WPG, jl = j - pr * WPG, d = pr & 1, b = pr >> 1;      // this workgroup's (direction, clip), its index in the group
     const int T = p.T;
+    int L = T;                                               // this pair's steps (ML: its clip's length, clamped so that no table content can index past a row)
+    if constexpr (ML) L = __builtin_amdgcn_readfirstlane(min(max(p.lens[b], 1), T));
     if (tid == 0) pad[0] = 0.f;
     u64* const X = p.xch;
     const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(X + (int64_t)(j % PD_MAXREP) * pb_rstride(NB), 0, pb_granules(NB) * 8, 0x00020000);
@@ -709,8 +731,8 @@ __global__ __launch_bounds__(PD_NT, 1) void pbilstm_kernel(const PBiP p) {
     if (tid < U) publish(0, 1u, cst);
     int rpar = 0;
     float hlast = cst;
-    for (int s = 0; s < T; ++s) {
-        const int t = d == 0 ? s : T - 1 - s;
+    for (int s = 0; s < L; ++s) {
+        const int t = d == 0 ? s : L - 1 - s;
         // this step's input gates (bias folded in by the GEMM), requested before the poll
         float pre[4];
         if (tid < U) {
@@ -746,6 +768,9 @@ __global__ __launch_bounds__(PD_NT, 1) void pbilstm_kernel(const PBiP p) {
         }
         rpar ^= 1;
     }
+    if constexpr (ML) {
+        if (tid < U) for (int t = L; t < T; ++t) p.rnn[((int64_t)b * T + t) * 1024 + d * 512 + unit] = 0.f;
+    }
     if (tid < U) {      // finals: forward -> decoder layer 0, backward -> layer 1 (decoder.py:398-399); cells side by side for E_C
         p.h_state[(int64_t)d * ((p.B + 15) & ~15) * 512 + frag16_index(b, unit, 512)] = hlast;
         p.cellcat[(int64_t)b * 1024 + d * 512 + unit] = cst;
@@ -769,6 +794,13 @@ __global__ void pdecode_guard_kernel(const unsigned* status, float* a, float* b,
 int64_t pdecode_ws_bytes(int) { return (int64_t)pd_rstride(2) * 8 * PD_MAXREP + 256; }      // laid out for two clips per launch
 // the form of a T-frame clip: one key frame per thread up to PD_MAXT, PD_KF_LONG beyond (whatever "persist_frames" says, a short clip takes the short form)
 static int pd_form_mt(int T) { return T <= PD_MAXT ? PD_MAXT : PD_MAXT_LONG; }
+// the longest clip among clips b0 .. b0 + n - 1 of a call: its padded T, or (masked calls) the longest of their lengths
+static int pd_longest(const int32_t* lens_host, int T, int b0, int n) {
+    if (!lens_host) return T;
+    int t = 1;
+    for (int b = b0; b < b0 + n; ++b) t = std::max(t, std::min((int)lens_host[b], T));
+    return t;
+}
 bool pdecode_supported(int B, int T, int m, int max_frames) {
     return B >= 1 && B <= PD_MAXB && T >= 1 && T <= std::min(std::max(max_frames, PD_MAXT), PD_MAXT_LONG) && m >= 1 && m <= PD_MAXM &&
            pd_lds_floats(2, T, m, pd_form_mt(T)) * 4 <= PD_LDS_MAX;
@@ -809,6 +841,18 @@ static bool pd_fits(K kernel, int lds) {
     return hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kernel, PD_NT, (size_t)lds) == hipSuccess && nb >= 1;
 }
 
+// the four length-masked instantiations of the decode loop with KF key frames per thread (and, with the short forms, the masked BiLSTM): LDS limit raised, one workgroup per CU
+template <int KF>
+static bool pd_resident_masked() {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(pdecode_kernel<1, 2, false, KF, true>), hipFuncAttributeMaxDynamicSharedMemorySize, PD_LDS_MAX);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(pdecode_kernel<2, 2, false, KF, true>), hipFuncAttributeMaxDynamicSharedMemorySize, PD_LDS_MAX);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(pdecode_kernel<1, 2, true, KF, true>), hipFuncAttributeMaxDynamicSharedMemorySize, PD_LDS_MAX);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(pdecode_kernel<2, 2, true, KF, true>), hipFuncAttributeMaxDynamicSharedMemorySize, PD_LDS_MAX);
+    return pd_fits(pdecode_kernel<1, 2, false, KF, true>, PD_LDS_MAX) && pd_fits(pdecode_kernel<2, 2, false, KF, true>, PD_LDS_MAX) &&
+           pd_fits(pdecode_kernel<1, 2, true, KF, true>, PD_LDS_MAX) && pd_fits(pdecode_kernel<2, 2, true, KF, true>, PD_LDS_MAX) &&
+           (KF > 1 || (pd_fits(pbilstm_kernel<1, true>, 0) && pd_fits(pbilstm_kernel<2, true>, 0)));
+}
+
 // the current device's entry (g_pd_mu held); nullptr when the device cannot be queried
 static PdDevice* pd_device_locked() {
     int dev = 0;
@@ -834,6 +878,7 @@ static PdDevice* pd_device_locked() {
             (void)hipFuncSetAttribute(reinterpret_cast<const void*>(pdecode_kernel<2, 2, true>), hipFuncAttributeMaxDynamicSharedMemorySize, PD_LDS_MAX);
             fits = pd_fits(pdecode_kernel<1, 2>, PD_LDS_MAX) && pd_fits(pdecode_kernel<2, 2>, PD_LDS_MAX) && pd_fits(pdecode_kernel<1, 2, true>, PD_LDS_MAX) && pd_fits(pdecode_kernel<2, 2, true>, PD_LDS_MAX) && pd_fits(pbilstm_kernel<1>, 0) && pd_fits(pbilstm_kernel<2>, 0);
         }
+        if (fits) fits = pd_resident_masked<1>();      // the length-masked instantiations ("persist_masked") of the same forms
         d.resident = fits;
         if (fits) {      // the long-clip forms ("persist_frames"): more registers; where one does not fit, the long envelope alone is off on this device
             (void)hipFuncSetAttribute(reinterpret_cast<const void*>(pdecode_kernel<1, 2, false, PD_KF_LONG>), hipFuncAttributeMaxDynamicSharedMemorySize, PD_LDS_MAX);
@@ -841,7 +886,8 @@ static PdDevice* pd_device_locked() {
             (void)hipFuncSetAttribute(reinterpret_cast<const void*>(pdecode_kernel<1, 2, true, PD_KF_LONG>), hipFuncAttributeMaxDynamicSharedMemorySize, PD_LDS_MAX);
             (void)hipFuncSetAttribute(reinterpret_cast<const void*>(pdecode_kernel<2, 2, true, PD_KF_LONG>), hipFuncAttributeMaxDynamicSharedMemorySize, PD_LDS_MAX);
             d.resident_long = pd_fits(pdecode_kernel<1, 2, false, PD_KF_LONG>, PD_LDS_MAX) && pd_fits(pdecode_kernel<2, 2, false, PD_KF_LONG>, PD_LDS_MAX) &&
-                              pd_fits(pdecode_kernel<1, 2, true, PD_KF_LONG>, PD_LDS_MAX) && pd_fits(pdecode_kernel<2, 2, true, PD_KF_LONG>, PD_LDS_MAX);
+                              pd_fits(pdecode_kernel<1, 2, true, PD_KF_LONG>, PD_LDS_MAX) && pd_fits(pdecode_kernel<2, 2, true, PD_KF_LONG>, PD_LDS_MAX) &&
+                              pd_resident_masked<PD_KF_LONG>();
         }
         d.init = true;
     }
@@ -882,20 +928,31 @@ void pdecode_rearm() {
     if (d && d->timeouts) d->armed_at = __atomic_load_n(d->timeouts, __ATOMIC_RELAXED);      // `seen` stays: a time-out nobody has been told about is still reported by the gate
 }
 
-int launch_pdecode(const PDecP& p, void* ws, int64_t ws_bytes, hipStream_t s) {
+// the masked instantiations of one (ES, KF) form for the launch's one or two clips
+template <bool ES, int KF>
+static void pd_launch_masked(int n, int starve, int lds, hipStream_t s, const PDecP& q) {
+    if (n == 1) hipLaunchKernelGGL((pdecode_kernel<1, 2, ES, KF, true>), dim3(PD_WG / 2 - starve), dim3(PD_NT), lds, s, q);
+    else hipLaunchKernelGGL((pdecode_kernel<2, 2, ES, KF, true>), dim3(PD_WG - starve), dim3(PD_NT), lds, s, q);
+}
+
+// lens_host (with p.lens, the device length table written from it): a masked call - every launch takes the form and the LDS of the longest of ITS clips
+int launch_pdecode(const PDecP& p, void* ws, int64_t ws_bytes, hipStream_t s, const int32_t* lens_host) {
     L2S_REQUIRE(pdecode_supported(p.B, p.T, p.m, PD_MAXT_LONG), "persistent decode: <= 4 clips of <= 80 frames whose values fit the LDS");
     L2S_REQUIRE(ws && ws_bytes >= pdecode_ws_bytes(2), "persistent decode: exchange buffer too small");
     std::lock_guard<std::mutex> lock(g_pd_mu);
     PdDevice* const dv = pd_device_locked();
     L2S_REQUIRE(pd_armed(dv), "persistent decode needs 256 compute units, one resident workgroup each (none masked), and no timed-out launch since the device was armed");
-    const bool longf = p.T > PD_MAXT;      // the long-clip forms (callers ask pdecode_gate(T) first)
-    L2S_REQUIRE(!longf || dv->resident_long, "persistent decode: the long-clip forms do not fit one workgroup per compute unit on this device");
-    const int lds = std::max(pd_lds_floats(2, p.T, p.m, pd_form_mt(p.T)) * 4, PD_LDS_MIN);
+    L2S_REQUIRE(!lens_host == !p.lens, "persistent decode: host lengths and the device length table come together");
+    L2S_REQUIRE(pd_longest(lens_host, p.T, 0, p.B) <= PD_MAXT || dv->resident_long, "persistent decode: the long-clip forms do not fit one workgroup per compute unit on this device");      // (callers ask pdecode_gate(T) first)
     L2S_CHECK_HIP(hipStreamWaitEvent(s, dv->ev, 0));      // a never-recorded event is complete
     ProfScope ps("decode_persistent", s);
     // clips two at a time (three or four clips: two launches one after the other - still shorter than 300 x four launches)
     for (int b0 = 0; b0 < p.B; b0 += 2) {
         const int n = p.B - b0 >= 2 ? 2 : 1;
+        int Lc[4];
+        const int Tl = pd_longest(lens_host, p.T, b0, n), ml = lens_host ? std::max(content_lens(Tl, Lc), 1) : p.m;      // the launch's longest clip, its content slots
+        const bool longf = Tl > PD_MAXT;      // the long-clip forms
+        const int lds = std::max(pd_lds_floats(2, Tl, ml, pd_form_mt(Tl)) * 4, PD_LDS_MIN);
         PDecP q = p;
         q.b0 = b0;
         q.xch = reinterpret_cast<u64*>(ws);
@@ -912,7 +969,12 @@ int launch_pdecode(const PDecP& p, void* ws, int64_t ws_bytes, hipStream_t s) {
 #else
         constexpr int starve = 0;
 #endif
-        if (longf) {        // option "persist_frames": PD_KF_LONG key frames per thread, the same loop otherwise
+        if (lens_host) {    // option "persist_masked": the length-masked instantiations of the same four forms
+            if (longf) { if (p.early) pd_launch_masked<true, PD_KF_LONG>(n, starve, lds, s, q); else pd_launch_masked<false, PD_KF_LONG>(n, starve, lds, s, q); }
+            else if (p.early) pd_launch_masked<true, 1>(n, starve, lds, s, q);
+            else pd_launch_masked<false, 1>(n, starve, lds, s, q);
+        }
+        else if (longf) {   // option "persist_frames": PD_KF_LONG key frames per thread, the same loop otherwise
             if (p.early) {
                 if (n == 1) hipLaunchKernelGGL((pdecode_kernel<1, 2, true, PD_KF_LONG>), dim3(PD_WG / 2 - starve), dim3(PD_NT), lds, s, q);
                 else hipLaunchKernelGGL((pdecode_kernel<2, 2, true, PD_KF_LONG>), dim3(PD_WG - starve), dim3(PD_NT), lds, s, q);
@@ -947,7 +1009,11 @@ int launch_pbilstm(const PBiP& p, void* ws, int64_t ws_bytes, hipStream_t s) {
     L2S_CHECK_HIP(hipMemsetAsync(q.h_state, 0, sizeof(float) * 2 * ((p.B + 15) & ~15) * 512, s));
     L2S_CHECK_HIP(hipStreamWaitEvent(s, dv->ev, 0));
     ProfScope ps("bilstm_persistent", s);
-    if (p.B == 1) hipLaunchKernelGGL(pbilstm_kernel<1>, dim3(PD_WG), dim3(PD_NT), 0, s, q);
+    if (p.lens) {      // option "persist_masked": every (direction, clip) pair runs its clip's own length
+        if (p.B == 1) hipLaunchKernelGGL((pbilstm_kernel<1, true>), dim3(PD_WG), dim3(PD_NT), 0, s, q);
+        else hipLaunchKernelGGL((pbilstm_kernel<2, true>), dim3(PD_WG), dim3(PD_NT), 0, s, q);
+    }
+    else if (p.B == 1) hipLaunchKernelGGL(pbilstm_kernel<1>, dim3(PD_WG), dim3(PD_NT), 0, s, q);
     else hipLaunchKernelGGL(pbilstm_kernel<2>, dim3(PD_WG), dim3(PD_NT), 0, s, q);
     hipLaunchKernelGGL(pdecode_guard_kernel, dim3(8), dim3(256), 0, s, q.status, q.rnn, q.cellcat, q.h_state, p.B * p.T * 1024, p.B * 1024, 2 * ((p.B + 15) & ~15) * 512, dv->timeouts);
     L2S_CHECK_HIP(hipGetLastError());
