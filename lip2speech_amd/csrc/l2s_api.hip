@@ -1198,11 +1198,16 @@ static void masked_bilstm_plan(const int32_t* video_lengths, int B, int T, std::
 }
 static int64_t len_table_bytes(int B) { return align_up((int64_t)2 * B * (int64_t)sizeof(int), 256); }
 
-// lens / lens_host (both or neither): the device length table and the host lengths it was written from - row b then computes what clip b alone at
-// T = len_b computes (on the launch-per-step recurrence; with option "persist_masked", inside the persistent envelope, on pbilstm_kernel's masked form)
+// The envelope of the persistent latency forms (pdecode.hip), the part that the prologue and the decode loop share: the options allow them for this
+// call, it is no grouped call, and its clips fit the decode loop's forms.  Each stage adds its own terms and then asks pdecode_gate(T), once.
+static bool persist_envelope(const l2s_model* m, bool masked, int B, int T, int mT) {
+    return (!masked || m->opt.persist_masked > 0) && m->opt.persist > 0 && B <= m->opt.persist && !grouped_entry() && pdecode_supported(B, T, mT, m->opt.persist_frames);
+}
+
+// lens (a masked call): row b computes what clip b alone at T = len_b computes (the launch-per-step recurrence, or pbilstm_kernel's masked form: "persist_masked")
 static int prologue_run(l2s_model* m, const float* vis, const float* emb, const float* gumbel, int B, int T,
-                        float* state, float* content_dis, void* ws, int64_t ws_bytes, hipStream_t s, const int* lens = nullptr,
-                        const int32_t* lens_host = nullptr, bool free_running = true) {      // free_running = false: the prologue of a teacher-forced masked call (launch route, whatever "persist_masked" says)
+                        float* state, float* content_dis, void* ws, int64_t ws_bytes, hipStream_t s, ClipLens lens = {},
+                        bool free_running = true) {      // free_running = false: the prologue of a teacher-forced masked call (launch route, whatever "persist_masked" says)
     X3Scope x3scope(m->opt.infer_bf16 ? 0 : m->opt.gemm_x3);
     Bf16Scope bf16scope(m->opt.infer_bf16);      // the bf16 leg: bf16-operand GEMM / Conv1d kernels instead of the f32 / split-bf16 ones
     const Weights& w = m->w;
@@ -1237,7 +1242,7 @@ static int prologue_run(l2s_model* m, const float* vis, const float* emb, const 
     float* bott_part = bp.f((int64_t)8 * BT * 512);
     // one or two clips of a single-batch call: the BiLSTM recurrence as ONE persistent launch (pdecode.hip pbilstm_kernel; option "persist_decode")
     // (the envelope of the latency path; a persistent launch that timed out since the last call fails THIS call once: pdecode_gate)
-    const int pgate = ((!lens || (m->opt.persist_masked > 0 && free_running)) && m->opt.persist > 0 && B <= m->opt.persist && !grouped_entry() && pbilstm_supported(B, T) && pdecode_supported(B, T, mT, m->opt.persist_frames)) ? pdecode_gate(T) : 0;
+    const int pgate = (persist_envelope(m, (bool)lens, B, T, mT) && pbilstm_supported(B, T) && (!lens || free_running)) ? pdecode_gate(T) : 0;
     if (pgate < 0) return 1;
     const bool pbi = pgate > 0;
     float* pbx = pbi ? bp.f(pbilstm_ws_bytes() / 4 + 64) : nullptr;
@@ -1266,7 +1271,7 @@ static int prologue_run(l2s_model* m, const float* vis, const float* emb, const 
     if (pbi) {
         PBiP q{};
         q.Whh0 = w.whh[0].W; q.Whh1 = w.whh[1].W; q.gin = gin; q.s_e = s_e; q.rnn = rnn; q.h_state = state + sl.h; q.cellcat = cellcat; q.B = B; q.T = T;
-        q.lens = lens;      // masked: pair (direction, clip) runs its clip's own length; the masked steps below are those of the launch route
+        q.lens = lens.dev;      // masked: pair (direction, clip) runs its clip's own length; the masked steps below are those of the launch route
         if (launch_pbilstm(q, pbx, pbilstm_ws_bytes(), s)) return 1;
     } else {
     // recurrence: h0 = c0 = s_e for both directions (decoder.py:386-389)
@@ -1278,7 +1283,7 @@ static int prologue_run(l2s_model* m, const float* vis, const float* emb, const 
     std::vector<int> cap_steps, rst_steps;
     size_t cap_i = 0, rst_i = 0;
     if (lens) {
-        masked_bilstm_plan(lens_host, B, T, cap_steps, rst_steps);
+        masked_bilstm_plan(lens.host, B, T, cap_steps, rst_steps);
         if (launch_fill(state + sl.h, (int64_t)Bp * 512, 0.f, s)) return 1;      // forward finals arrive row by row; the padded rows stay zero
     }
     for (int step = 0; step < T; ++step) {
@@ -1286,7 +1291,7 @@ static int prologue_run(l2s_model* m, const float* vis, const float* emb, const 
         const int cur = step & 1, nxt = cur ^ 1;
         if (rst_i < rst_steps.size() && rst_steps[rst_i] == step) {      // backward rows whose clip ends at frame T-1-step start here, from s_e
             ++rst_i;
-            if (launch_bilstm_reset(hf[1][cur], cf[1], lens, B, T - 1 - step, s_e, s)) return 1;
+            if (launch_bilstm_reset(hf[1][cur], cf[1], lens.dev, B, T - 1 - step, s_e, s)) return 1;
         }
         for (int d = 0; d < 2; ++d) {
             const int t = d == 0 ? step : T - 1 - step;
@@ -1303,7 +1308,7 @@ static int prologue_run(l2s_model* m, const float* vis, const float* emb, const 
         if (launch_skinny(sb, s, "bilstm_step", m->opt)) return 1;
         if (cap_i < cap_steps.size() && cap_steps[cap_i] == step) {      // forward rows whose clip ended at frame `step`: their finals, now
             ++cap_i;
-            if (launch_bilstm_capture(hf[0][nxt], cf[0], lens, B, step, state + sl.h, cellcat, 1024, s)) return 1;
+            if (launch_bilstm_capture(hf[0][nxt], cf[0], lens.dev, B, step, state + sl.h, cellcat, 1024, s)) return 1;
         }
     }
     const int fin = T & 1;     // buffer holding the final hidden states
@@ -1328,7 +1333,7 @@ static int prologue_run(l2s_model* m, const float* vis, const float* emb, const 
         p.R2 = s_a; p.ldr2 = 512; p.r2_div = T;     // attention_site embedding, broadcast over the T frames of a clip
         if (launch_gemm_splitk(p, 4, bott_part, s, "prologue_gemm")) return 1;
         // with lengths: rows t >= len_b become zeros on the way (the K / V convolutions below then read past a clip's end what a solo call reads as padding)
-        if (lens ? launch_mask_copy_rows(cat, 4608, state + sl.enc, 512, lens, B, T, 512, s)
+        if (lens ? launch_mask_copy_rows(cat, 4608, state + sl.enc, 512, lens.dev, B, T, 512, s)
                  : launch_copy_cols(cat, 4608, 0, state + sl.enc, 512, 0, 1, BT, 512, s)) return 1;
     }
     // MultiHopConv branches of K and V (8 convs, one grouped launch), then the two bottlenecks (+PSine +pos)
@@ -1377,7 +1382,7 @@ static int prologue_run(l2s_model* m, const float* vis, const float* emb, const 
             PoolDiv pd{};
             pd.div[0] = 1;
             for (int j = 0; j < 4; ++j) pd.div[j + 1] = CT_KS[j];
-            if (launch_pool_cat_masked(pc, pd, lens, s)) return 1;
+            if (launch_pool_cat_masked(pc, pd, lens.dev, s)) return 1;
         } else if (launch_pool_cat(pc, s)) return 1;
         const int R = B * mT;
         GemmP p = gemm_plain(pooled, 2560, w.ct_bott.W, wv, 256, R, 256, 2560);
@@ -1397,7 +1402,7 @@ static int prologue_run(l2s_model* m, const float* vis, const float* emb, const 
         p3.shift = w.ct_fc4.shift; p3.act = ACT_SILU;
         if (launch_gemm1(p3, s, "content_gemm")) return 1;
         if (launch_gumbel_softmax(logits, gumbel, R, VOC, 0.1f, z, VOCP, content_dis, s)) return 1;
-        if (lens && launch_zero_slot_rows(z, VOCP, content_dis, VOC, B, mT, lens, s)) return 1;      // slots i >= m_b: zero z (so zero values) and zero content_dis
+        if (lens && launch_zero_slot_rows(z, VOCP, content_dis, VOC, B, mT, lens.dev, s)) return 1;      // slots i >= m_b: zero z (so zero values) and zero content_dis
         GemmP p4 = gemm_plain(z, VOCP, w.ct_emb.W, state + sl.cval, 256, R, 256, VOCP);
         if (launch_gemm1(p4, s, "content_gemm")) return 1;
     }
@@ -1419,7 +1424,7 @@ struct DecodeBufs {
 // on_frames(n): called (if set) right after the launch that completes mel frames [0, n) has been enqueued on `s`
 static int decode_launches(l2s_model* m, float* state, int B, int T, int S, const float* teacher, const uint8_t* teacher_mask,
                            float* mel, float* stop, float* attn, int attn_logits, void* ws, int64_t ws_bytes, hipStream_t s, bool fold,
-                           const std::function<int(int)>* on_frames = nullptr, bool early = false, const int* lens = nullptr) {
+                           const std::function<int(int)>* on_frames = nullptr, bool early = false, ClipLens lens = {}) {
     const Weights& w = m->w;
     StateLayout sl = state_layout(B, T);
     const int Bp = pad16(B);
@@ -1497,7 +1502,7 @@ static int decode_launches(l2s_model* m, float* state, int B, int T, int S, cons
             pr.seg[0] = {d.p1, 16}; pr.nseg = 1; pr.act = ACT_PSINE;
             if (fold) { pr.epi = SK_FRAG; pr.out = d.p2f; pr.ldo = 256; }
             else { pr.epi = SK_PLAIN; pr.out = d.p2; pr.ldo = 256; }
-            if (lens ? launch_step_attn_masked(at, pr, w.pre2.tiles, lens, s, m->opt.attn_lds, m->opt.attn_skip0)
+            if (lens ? launch_step_attn_masked(at, pr, w.pre2.tiles, lens.dev, s, m->opt.attn_lds, m->opt.attn_skip0)
                      : launch_step_attn(at, pr, w.pre2.tiles, s, m->opt.attn_lds, m->opt.attn_skip0)) return 1;
         }
         if (!fold) {   // phase C: u = prenet + attention_proj(a @ v)
@@ -1539,9 +1544,16 @@ static int decode_launches(l2s_model* m, float* state, int B, int T, int S, cons
     return 0;
 }
 
+static int side_stream_ready(l2s_model* m) {      // the model's side stream and its two events, made on first use (m->side_mu held)
+    if (m->side) return 0;
+    L2S_CHECK_HIP(hipStreamCreateWithFlags(&m->side, hipStreamNonBlocking));
+    L2S_CHECK_HIP(hipEventCreateWithFlags(&m->ev_in, hipEventDisableTiming));
+    L2S_CHECK_HIP(hipEventCreateWithFlags(&m->ev_out, hipEventDisableTiming));
+    return 0;
+}
+
 static int decode_run(l2s_model* m, float* state, int B, int T, int S, const float* teacher, const uint8_t* teacher_mask,
-                      float* mel, float* stop, float* attn, int attn_logits, void* ws, int64_t ws_bytes, hipStream_t s, bool may_stop_early,
-                      const int* lens = nullptr, const int32_t* lens_host = nullptr) {
+                      float* mel, float* stop, float* attn, int attn_logits, void* ws, int64_t ws_bytes, hipStream_t s, bool may_stop_early, ClipLens lens = {}) {
     L2S_REQUIRE(S >= 1 && S <= L2S_MAX_STEPS, "S must be in [1, 300] (positional table)");
     const bool fold = m->opt.fold != 0 && m->folded_valid;
     // option "early_stop": free-running loops only (a teacher-forced loop's S comes from the target).  The steps the loop never reaches are exact zeros
@@ -1552,39 +1564,33 @@ static int decode_run(l2s_model* m, float* state, int B, int T, int S, const flo
         L2S_CHECK_HIP(hipMemsetAsync(stop, 0, sizeof(float) * B * S, s));
         if (attn) L2S_CHECK_HIP(hipMemsetAsync(attn, 0, sizeof(float) * B * S * T, s));
     }
-    if ((!lens || (m->opt.persist_masked > 0 && lens_host)) && !teacher && fold && m->opt.persist > 0 && B <= m->opt.persist && !grouped_entry()) {      // the latency form: one launch for the whole loop (with lengths: option "persist_masked")
-        const Weights& w = m->w;
-        StateLayout sl = state_layout(B, T);
-        const int pgate = (pdecode_supported(B, T, sl.m, m->opt.persist_frames) && w.vproj.W && w.pre1f.W && w.lstm0.W && w.lstm1.W) ? pdecode_gate(T) : 0;
-        if (pgate < 0) return 1;      // an earlier persistent launch on this device gave up (its outputs are NaN): reported here, once
-        if (pgate > 0) {
-            PDecP p{};
-            p.Wq = w.q.W; p.bq = w.q.bias; p.aq = w.q.actw;
-            p.Wcq = w.cq.W; p.bcq = w.cq.bias;
-            p.Wp1f = w.pre1f.W; p.bp1f = w.pre1f.bias; p.ap1 = w.pre1f.actw;
-            p.Wp1 = w.pre1.W; p.bp1 = w.pre1.bias;
-            p.Wp2 = w.pre2.W; p.bp2 = w.pre2.bias; p.ap2 = w.pre2.actw;
-            p.Wl0 = w.lstm0.W; p.bl0 = w.lstm0.bias; p.Wl1 = w.lstm1.W; p.bl1 = w.lstm1.bias;
-            p.Wfc = w.fc.W; p.bfc = w.fc.bias;
-            p.pos = w.pos; p.tau = w.tau; p.tau_c = w.tau_c; p.bos = w.bos;
-            p.k = state + sl.k; p.vp = state + sl.vp; p.ckey = state + sl.ckey; p.cval = state + sl.cval;
-            p.h_init = state + sl.h; p.stop_const = state + sl.stopc;
-            p.mel = mel; p.stop = stop; p.attn = attn; p.attn_logits = attn_logits;
-            p.B = B; p.T = T; p.m = sl.m; p.S = S;
-            p.early = early ? ES_MARGIN : 0;
-            p.lens = lens;
-            return launch_pdecode(p, ws, ws_bytes, s, lens_host);
-        }
+    // the latency form: one launch for the whole loop (with lengths: option "persist_masked") - free-running, on the folded weights
+    const Weights& w = m->w;
+    StateLayout sl = state_layout(B, T);
+    const int pgate = (persist_envelope(m, (bool)lens, B, T, sl.m) && !teacher && fold && w.vproj.W && w.pre1f.W && w.lstm0.W && w.lstm1.W) ? pdecode_gate(T) : 0;
+    if (pgate < 0) return 1;      // an earlier persistent launch on this device gave up (its outputs are NaN): reported here, once
+    if (pgate > 0) {
+        PDecP p{};
+        p.Wq = w.q.W; p.bq = w.q.bias; p.aq = w.q.actw;
+        p.Wcq = w.cq.W; p.bcq = w.cq.bias;
+        p.Wp1f = w.pre1f.W; p.bp1f = w.pre1f.bias; p.ap1 = w.pre1f.actw;
+        p.Wp1 = w.pre1.W; p.bp1 = w.pre1.bias;
+        p.Wp2 = w.pre2.W; p.bp2 = w.pre2.bias; p.ap2 = w.pre2.actw;
+        p.Wl0 = w.lstm0.W; p.bl0 = w.lstm0.bias; p.Wl1 = w.lstm1.W; p.bl1 = w.lstm1.bias;
+        p.Wfc = w.fc.W; p.bfc = w.fc.bias;
+        p.pos = w.pos; p.tau = w.tau; p.tau_c = w.tau_c; p.bos = w.bos;
+        p.k = state + sl.k; p.vp = state + sl.vp; p.ckey = state + sl.ckey; p.cval = state + sl.cval;
+        p.h_init = state + sl.h; p.stop_const = state + sl.stopc;
+        p.mel = mel; p.stop = stop; p.attn = attn; p.attn_logits = attn_logits;
+        p.B = B; p.T = T; p.m = sl.m; p.S = S;
+        p.early = early ? ES_MARGIN : 0;
+        return launch_pdecode(p, ws, ws_bytes, s, lens);
     }
     const bool use_graph = m->opt.graph && !teacher && !g_prof_on && !early && !lens;      // "early_stop" and per-clip lengths take the plain route: a replayed graph knows no control block / length table of this call
     if (!use_graph) return decode_launches(m, state, B, T, S, teacher, teacher_mask, mel, stop, attn, attn_logits, ws, ws_bytes, s, fold, nullptr, early, lens);
 
     std::lock_guard<std::mutex> side_lock(m->side_mu);      // graph cache, side stream and events are per model; chains of other threads wait here
-    if (!m->side) {
-        L2S_CHECK_HIP(hipStreamCreateWithFlags(&m->side, hipStreamNonBlocking));
-        L2S_CHECK_HIP(hipEventCreateWithFlags(&m->ev_in, hipEventDisableTiming));
-        L2S_CHECK_HIP(hipEventCreateWithFlags(&m->ev_out, hipEventDisableTiming));
-    }
+    if (side_stream_ready(m)) return 1;
     l2s_model::GraphEntry* hit = nullptr;
     for (auto& g : m->graphs)
         if (g.B == B && g.T == T && g.S == S && g.attn_logits == attn_logits && g.fold == (int)fold && g.state == state && g.mel == mel &&
@@ -1812,18 +1818,39 @@ int l2s_build_visual(const float* feat, const float* emb, int B, int T, float* v
     return launch_tile_rows(emb, L2S_D_EMB, vis + L2S_D_FEAT, L2S_D_VIS, B, T, L2S_D_EMB, s);
 }
 
-int l2s_decoder_prologue(l2s_model* m, const float* vis, const float* emb, const float* gumbel, int B, int T, float* state,
-                         float* content_dis, void* ws, int64_t ws_bytes, void* stream) {
+// The staged pair.  Each entry point and its *_masked twin (further down) share one body; masked = the *_masked name: its video_lengths are checked, and
+// the call writes its own length table at the front of its workspace (l2s_workspace_bytes_masked)
+static int staged_lens(const int32_t* video_lengths, int B, int T, void*& ws, int64_t& ws_bytes, hipStream_t s, ClipLens& lens) {
+    if (check_lengths(video_lengths, B, T)) return 1;
+    L2S_REQUIRE(ws_bytes > len_table_bytes(B), "workspace too small (l2s_workspace_bytes_masked)");
+    lens = {reinterpret_cast<int*>(ws), video_lengths};
+    if (launch_len_table(video_lengths, B, lens.dev, s)) return 1;
+    ws = (char*)ws + len_table_bytes(B); ws_bytes -= len_table_bytes(B);
+    return 0;
+}
+static int prologue_entry(l2s_model* m, const float* vis, const float* emb, const float* gumbel, int B, int T, float* state, float* content_dis,
+                          void* ws, int64_t ws_bytes, void* stream, bool masked, const int32_t* video_lengths) {
     L2S_DEC_READY(m);
     L2S_REQUIRE(vis && emb && gumbel && state && ws && B > 0, "bad arguments");
-    return prologue_run(m, vis, emb, gumbel, B, T, state, content_dis, ws, ws_bytes, (hipStream_t)stream);
+    ClipLens lens;
+    if (masked && staged_lens(video_lengths, B, T, ws, ws_bytes, (hipStream_t)stream, lens)) return 1;
+    return prologue_run(m, vis, emb, gumbel, B, T, state, content_dis, ws, ws_bytes, (hipStream_t)stream, lens);
 }
-
-int l2s_decode_steps(l2s_model* m, float* state, int B, int T, int S, const float* teacher, const uint8_t* teacher_mask, float* mel,
-                     float* stop, float* attn, int attn_logits, void* ws, int64_t ws_bytes, void* stream) {
+int l2s_decoder_prologue(l2s_model* m, const float* vis, const float* emb, const float* gumbel, int B, int T, float* state,
+                         float* content_dis, void* ws, int64_t ws_bytes, void* stream) {
+    return prologue_entry(m, vis, emb, gumbel, B, T, state, content_dis, ws, ws_bytes, stream, false, nullptr);
+}
+static int decode_steps_entry(l2s_model* m, float* state, int B, int T, int S, const float* teacher, const uint8_t* teacher_mask, float* mel, float* stop,
+                              float* attn, int attn_logits, void* ws, int64_t ws_bytes, void* stream, bool masked, const int32_t* video_lengths) {
     L2S_DEC_READY(m);
     L2S_REQUIRE(state && mel && stop && ws && B > 0, "bad arguments");
-    return decode_run(m, state, B, T, S, teacher, teacher_mask, mel, stop, attn, attn_logits, ws, ws_bytes, (hipStream_t)stream, true);
+    ClipLens lens;
+    if (masked && staged_lens(video_lengths, B, T, ws, ws_bytes, (hipStream_t)stream, lens)) return 1;
+    return decode_run(m, state, B, T, S, teacher, teacher_mask, mel, stop, attn, attn_logits, ws, ws_bytes, (hipStream_t)stream, true, lens);
+}
+int l2s_decode_steps(l2s_model* m, float* state, int B, int T, int S, const float* teacher, const uint8_t* teacher_mask, float* mel,
+                     float* stop, float* attn, int attn_logits, void* ws, int64_t ws_bytes, void* stream) {
+    return decode_steps_entry(m, state, B, T, S, teacher, teacher_mask, mel, stop, attn, attn_logits, ws, ws_bytes, stream, false, nullptr);
 }
 
 int l2s_postnet(l2s_model* m, const float* mel, int B, int S, float* mel_post, float* mel_cf, void* ws, int64_t ws_bytes, void* stream) {
@@ -1874,7 +1901,7 @@ static int path_run(l2s_model* m, const FrameSrc& video, const float* emb, const
     X3Scope x3scope(m->opt.infer_bf16 ? 0 : m->opt.gemm_x3);
     Bf16Scope bf16scope(m->opt.infer_bf16);      // the bf16 leg: bf16-operand GEMM / Conv1d kernels instead of the f32 / split-bf16 ones
     Bump bp(ws, ws_bytes);
-    int* lens = video_lengths ? reinterpret_cast<int*>(bp.f(len_table_bytes(B) / 4)) : nullptr;      // the *_masked entry points (l2s_workspace_bytes_masked)
+    const ClipLens lens{video_lengths ? reinterpret_cast<int*>(bp.f(len_table_bytes(B) / 4)) : nullptr, video_lengths};      // the *_masked entry points (l2s_workspace_bytes_masked)
     float* vis = bp.f((int64_t)B * T * 1024);
     float* state = bp.f(l2s_state_floats(B, T));
     float* mel = bp.f((int64_t)B * S * NM);
@@ -1882,23 +1909,19 @@ static int path_run(l2s_model* m, const FrameSrc& video, const float* emb, const
     L2S_REQUIRE(!bp.overflow, "workspace too small (l2s_workspace_bytes)");
     void* rest = (char*)ws + bp.off;
     const int64_t rest_bytes = ws_bytes - bp.off;
-    if (lens && launch_len_table(video_lengths, B, lens, s)) return 1;
+    if (lens && launch_len_table(video_lengths, B, lens.dev, s)) return 1;
     if (encoder_run(m, video, B, T, H, W, emb, vis, nullptr, rest, rest_bytes, s)) return 1;
-    if (prologue_run(m, vis, emb, gumbel, B, T, state, o.content_dis, rest, rest_bytes, s, lens, video_lengths, !teacher)) return 1;
+    if (prologue_run(m, vis, emb, gumbel, B, T, state, o.content_dis, rest, rest_bytes, s, lens, !teacher)) return 1;
     const bool early = m->opt.early_stop != 0 && !teacher && o.lengths;      // l2s_inference(_multi); l2s_forward_eval's S comes from the target
     const bool plain = !m->opt.overlap_postnet || g_prof_on || m->opt.graph || teacher || o.mel_cf || early || lens;      // "early_stop" and lengths take the plain route
     if (plain) {
-        if (decode_run(m, state, B, T, S, teacher, teacher_mask, mel, stop, o.attn, o.attn_logits, rest, rest_bytes, s, early, lens, video_lengths)) return 1;
+        if (decode_run(m, state, B, T, S, teacher, teacher_mask, mel, stop, o.attn, o.attn_logits, rest, rest_bytes, s, early, lens)) return 1;
         if (postnet_run(m, mel, B, S, o.mel_post, o.mel_cf, rest, rest_bytes, s)) return 1;
     } else {
         // The decode loop is a chain of small latency-bound launches that leaves most CUs idle, and the post-net of frame t
         // only needs mel frames t-10..t+10: run the post-net in time windows on a second stream while later steps decode.
         std::lock_guard<std::mutex> side_lock(m->side_mu);      // the side stream and its events are per model: one chain at a time enqueues on them
-        if (!m->side) {
-            L2S_CHECK_HIP(hipStreamCreateWithFlags(&m->side, hipStreamNonBlocking));
-            L2S_CHECK_HIP(hipEventCreateWithFlags(&m->ev_in, hipEventDisableTiming));
-            L2S_CHECK_HIP(hipEventCreateWithFlags(&m->ev_out, hipEventDisableTiming));
-        }
+        if (side_stream_ready(m)) return 1;
         Bump pbump((char*)rest + align_up(decode_ws_floats(B) * (int64_t)sizeof(float), 256), rest_bytes - align_up(decode_ws_floats(B) * (int64_t)sizeof(float), 256));
         PostBufs pb;
         L2S_REQUIRE(postnet_alloc(pbump, B, S, pb) == 0, "workspace too small (l2s_workspace_bytes)");
@@ -1936,23 +1959,43 @@ static int path_run(l2s_model* m, const FrameSrc& video, const float* emb, const
     return 0;
 }
 
-static int inference_run(l2s_model* m, const FrameSrc& video, const float* emb, const float* gumbel, int B, int T, int H, int W, int S,
-                         float* mel_post, int64_t* lengths, float* attn, void* ws, int64_t ws_bytes, hipStream_t s) {
-    PathOut o;
-    o.mel_post = mel_post; o.lengths = lengths; o.attn = attn;
-    return path_run(m, video, emb, gumbel, B, T, H, W, S, nullptr, nullptr, o, ws, ws_bytes, s);
-}
-
-int l2s_inference(l2s_model* m, const float* video, const float* emb, const float* gumbel, int B, int T, int H, int W, int S,
-                  float* mel_post, int64_t* lengths, float* attn, void* ws, int64_t ws_bytes, void* stream) {
+static int inference_entry(l2s_model* m, const float* video, const float* emb, const float* gumbel, int B, int T, int H, int W, int S, float* mel_post,
+                           int64_t* lengths, float* attn, void* ws, int64_t ws_bytes, void* stream, bool masked, const int32_t* video_lengths) {
     L2S_ENC_READY(m);
     L2S_DEC_READY(m);
     L2S_REQUIRE(video && emb && gumbel && mel_post && lengths && ws && B > 0, "bad arguments");
-    return inference_run(m, frame_src(video, B), emb, gumbel, B, T, H, W, S, mel_post, lengths, attn, ws, ws_bytes, (hipStream_t)stream);
+    if (masked && check_lengths(video_lengths, B, T)) return 1;
+    PathOut o;
+    o.mel_post = mel_post; o.lengths = lengths; o.attn = attn;
+    return path_run(m, frame_src(video, B), emb, gumbel, B, T, H, W, S, nullptr, nullptr, o, ws, ws_bytes, (hipStream_t)stream, video_lengths);
+}
+int l2s_inference(l2s_model* m, const float* video, const float* emb, const float* gumbel, int B, int T, int H, int W, int S,
+                  float* mel_post, int64_t* lengths, float* attn, void* ws, int64_t ws_bytes, void* stream) {
+    return inference_entry(m, video, emb, gumbel, B, T, H, W, S, mel_post, lengths, attn, ws, ws_bytes, stream, false, nullptr);
+}
+// Lip2Speech.forward(..., tf_ratio) in eval() mode / under no_grad (model.py:23-40 + decoder.py:320-379; what evaluate.py:38 runs at
+// tf_ratio = 1): S = mels.shape[2] steps, attention LOGITS out, optional teacher frames for the steps the caller's scheduled-sampling
+// draws selected.  One launch chain, like l2s_inference.
+static int forward_eval_entry(l2s_model* m, const float* video, const float* emb, const float* gumbel, int B, int T, int H, int W, int S, const float* teacher,
+                              const uint8_t* teacher_mask, float* mel_cf, float* mel_post, float* stop, float* attn_logits, float* content_dis, void* ws,
+                              int64_t ws_bytes, void* stream, bool masked, const int32_t* video_lengths) {
+    L2S_ENC_READY(m);
+    L2S_DEC_READY(m);
+    L2S_REQUIRE(video && emb && gumbel && mel_post && stop && ws && B > 0, "bad arguments");
+    L2S_REQUIRE((teacher != nullptr) == (teacher_mask != nullptr), "teacher frames and teacher_mask come together");
+    if (masked && check_lengths(video_lengths, B, T)) return 1;
+    PathOut o;
+    o.mel_post = mel_post; o.mel_cf = mel_cf; o.stop = stop; o.attn = attn_logits; o.attn_logits = 1; o.content_dis = content_dis;
+    return path_run(m, frame_src(video, B), emb, gumbel, B, T, H, W, S, teacher, teacher_mask, o, ws, ws_bytes, (hipStream_t)stream, video_lengths);
+}
+int l2s_forward_eval(l2s_model* m, const float* video, const float* emb, const float* gumbel, int B, int T, int H, int W, int S,
+                     const float* teacher, const uint8_t* teacher_mask, float* mel_cf, float* mel_post, float* stop, float* attn_logits,
+                     float* content_dis, void* ws, int64_t ws_bytes, void* stream) {
+    return forward_eval_entry(m, video, emb, gumbel, B, T, H, W, S, teacher, teacher_mask, mel_cf, mel_post, stop, attn_logits, content_dis, ws, ws_bytes, stream, false, nullptr);
 }
 
-// ---- per-clip video lengths: row b of a zero-padded batch computes what clip b computes alone at T = len_b (include/l2s.h).  New entry points only;
-// the launch-per-phase route, whatever "persist_decode" / "use_graph" say.
+// ---- per-clip video lengths: row b of a zero-padded batch computes what clip b computes alone at T = len_b (include/l2s.h).  New entry points only: the
+// launch-per-phase route whatever "use_graph" says, or (options "persist_decode" and "persist_masked", free-running, persist_envelope) the persistent forms.
 int64_t l2s_workspace_bytes_masked(int B, int T, int H, int W, int S) { return l2s_workspace_bytes(B, T, H, W, S) + len_table_bytes(B) + 256; }
 
 int l2s_masked_bilstm_plan(const int32_t* video_lengths, int B, int T, int32_t* capture_steps, int32_t* reset_steps, int* n_capture, int* n_reset) {
@@ -1968,51 +2011,20 @@ int l2s_masked_bilstm_plan(const int32_t* video_lengths, int B, int T, int32_t* 
 
 int l2s_inference_masked(l2s_model* m, const float* video, const float* emb, const float* gumbel, int B, int T, int H, int W, int S,
                          float* mel_post, int64_t* lengths, float* attn, void* ws, int64_t ws_bytes, void* stream, const int32_t* video_lengths) {
-    L2S_ENC_READY(m);
-    L2S_DEC_READY(m);
-    L2S_REQUIRE(video && emb && gumbel && mel_post && lengths && ws && B > 0, "bad arguments");
-    if (check_lengths(video_lengths, B, T)) return 1;
-    PathOut o;
-    o.mel_post = mel_post; o.lengths = lengths; o.attn = attn;
-    return path_run(m, frame_src(video, B), emb, gumbel, B, T, H, W, S, nullptr, nullptr, o, ws, ws_bytes, (hipStream_t)stream, video_lengths);
+    return inference_entry(m, video, emb, gumbel, B, T, H, W, S, mel_post, lengths, attn, ws, ws_bytes, stream, true, video_lengths);
 }
-
 int l2s_forward_eval_masked(l2s_model* m, const float* video, const float* emb, const float* gumbel, int B, int T, int H, int W, int S,
                             const float* teacher, const uint8_t* teacher_mask, float* mel_cf, float* mel_post, float* stop, float* attn_logits,
                             float* content_dis, void* ws, int64_t ws_bytes, void* stream, const int32_t* video_lengths) {
-    L2S_ENC_READY(m);
-    L2S_DEC_READY(m);
-    L2S_REQUIRE(video && emb && gumbel && mel_post && stop && ws && B > 0, "bad arguments");
-    L2S_REQUIRE((teacher != nullptr) == (teacher_mask != nullptr), "teacher frames and teacher_mask come together");
-    if (check_lengths(video_lengths, B, T)) return 1;
-    PathOut o;
-    o.mel_post = mel_post; o.mel_cf = mel_cf; o.stop = stop; o.attn = attn_logits; o.attn_logits = 1; o.content_dis = content_dis;
-    return path_run(m, frame_src(video, B), emb, gumbel, B, T, H, W, S, teacher, teacher_mask, o, ws, ws_bytes, (hipStream_t)stream, video_lengths);
+    return forward_eval_entry(m, video, emb, gumbel, B, T, H, W, S, teacher, teacher_mask, mel_cf, mel_post, stop, attn_logits, content_dis, ws, ws_bytes, stream, true, video_lengths);
 }
-
-// the staged pair: each call writes its own length table at the front of its workspace
 int l2s_decoder_prologue_masked(l2s_model* m, const float* vis, const float* emb, const float* gumbel, int B, int T, float* state,
                                 float* content_dis, void* ws, int64_t ws_bytes, void* stream, const int32_t* video_lengths) {
-    L2S_DEC_READY(m);
-    L2S_REQUIRE(vis && emb && gumbel && state && ws && B > 0, "bad arguments");
-    if (check_lengths(video_lengths, B, T)) return 1;
-    L2S_REQUIRE(ws_bytes > len_table_bytes(B), "workspace too small (l2s_workspace_bytes_masked)");
-    int* lens = reinterpret_cast<int*>(ws);
-    if (launch_len_table(video_lengths, B, lens, (hipStream_t)stream)) return 1;
-    return prologue_run(m, vis, emb, gumbel, B, T, state, content_dis, (char*)ws + len_table_bytes(B), ws_bytes - len_table_bytes(B), (hipStream_t)stream, lens,
-                        video_lengths);
+    return prologue_entry(m, vis, emb, gumbel, B, T, state, content_dis, ws, ws_bytes, stream, true, video_lengths);
 }
-
 int l2s_decode_steps_masked(l2s_model* m, float* state, int B, int T, int S, const float* teacher, const uint8_t* teacher_mask, float* mel,
                             float* stop, float* attn, int attn_logits, void* ws, int64_t ws_bytes, void* stream, const int32_t* video_lengths) {
-    L2S_DEC_READY(m);
-    L2S_REQUIRE(state && mel && stop && ws && B > 0, "bad arguments");
-    if (check_lengths(video_lengths, B, T)) return 1;
-    L2S_REQUIRE(ws_bytes > len_table_bytes(B), "workspace too small (l2s_workspace_bytes_masked)");
-    int* lens = reinterpret_cast<int*>(ws);
-    if (launch_len_table(video_lengths, B, lens, (hipStream_t)stream)) return 1;
-    return decode_run(m, state, B, T, S, teacher, teacher_mask, mel, stop, attn, attn_logits, (char*)ws + len_table_bytes(B), ws_bytes - len_table_bytes(B),
-                      (hipStream_t)stream, true, lens, video_lengths);
+    return decode_steps_entry(m, state, B, T, S, teacher, teacher_mask, mel, stop, attn, attn_logits, ws, ws_bytes, stream, true, video_lengths);
 }
 
 // Grouped inference: the G batches are rows g*B .. g*B+B-1 of ONE launch chain on ONE weight blob.  Every kernel of the path is row-independent
@@ -2045,22 +2057,9 @@ int l2s_inference_multi(l2s_model* m, int G, const float* const* video, const fl
         L2S_CHECK_HIP(hipMemcpyAsync(gum_all + (int64_t)g * B * mT * VOC, gumbel[g], sizeof(float) * B * mT * VOC, hipMemcpyDeviceToDevice, s));
     }
     X3Group x3group(G);
-    return inference_run(m, src, emb_all, gum_all, G * B, T, H, W, S, mel_post, lengths, attn, (char*)ws + bp.off, ws_bytes - bp.off, s);
-}
-
-// Lip2Speech.forward(..., tf_ratio) in eval() mode / under no_grad (model.py:23-40 + decoder.py:320-379; what evaluate.py:38 runs at
-// tf_ratio = 1): S = mels.shape[2] steps, attention LOGITS out, optional teacher frames for the steps the caller's scheduled-sampling
-// draws selected.  One launch chain, like l2s_inference.
-int l2s_forward_eval(l2s_model* m, const float* video, const float* emb, const float* gumbel, int B, int T, int H, int W, int S,
-                     const float* teacher, const uint8_t* teacher_mask, float* mel_cf, float* mel_post, float* stop, float* attn_logits,
-                     float* content_dis, void* ws, int64_t ws_bytes, void* stream) {
-    L2S_ENC_READY(m);
-    L2S_DEC_READY(m);
-    L2S_REQUIRE(video && emb && gumbel && mel_post && stop && ws && B > 0, "bad arguments");
-    L2S_REQUIRE((teacher != nullptr) == (teacher_mask != nullptr), "teacher frames and teacher_mask come together");
     PathOut o;
-    o.mel_post = mel_post; o.mel_cf = mel_cf; o.stop = stop; o.attn = attn_logits; o.attn_logits = 1; o.content_dis = content_dis;
-    return path_run(m, frame_src(video, B), emb, gumbel, B, T, H, W, S, teacher, teacher_mask, o, ws, ws_bytes, (hipStream_t)stream);
+    o.mel_post = mel_post; o.lengths = lengths; o.attn = attn;
+    return path_run(m, src, emb_all, gum_all, G * B, T, H, W, S, nullptr, nullptr, o, (char*)ws + bp.off, ws_bytes - bp.off, s);
 }
 
 // The grouped form: G batches of the evaluate loop as rows of ONE launch chain (see l2s_inference_multi).  The batches of a group share S

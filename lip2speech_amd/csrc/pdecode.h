@@ -27,7 +27,7 @@ struct PDecP {
     int early;                            // option "early_stop": 0 = run S steps; else the margin (steps decoded past a clip's stop crossing, ES_MARGIN)
     int b0;                               // set by launch_pdecode: first clip of THIS launch (clips go two at a time)
     unsigned long long* ts; int ts_step;  // measurement (tools/pdecode_timeline.py): [256 workgroups][16] stamps of step ts_step, or null
-    const int* lens;                      // option "persist_masked": the device length table of a masked call ([B] frames, then [B] content slots), or null; T and m above are then row pitches
+    const int* lens;                      // set by launch_pdecode, option "persist_masked": the device length table of a masked call ([B] frames, then [B] content slots), or null; T and m above are then row pitches
 };
 
 // the prologue's BiLSTM recurrence in the same form (pbilstm_kernel)
@@ -52,6 +52,13 @@ int pdecode_timeouts();                                 // persistent launches o
 int64_t pdecode_ws_bytes(int B);                       // exchange granules + status word
 bool pdecode_supported(int B, int T, int m, int max_frames = 32);      // <= 4 clips of <= max(32, min(max_frames, 80)) frames (option "persist_frames")
 void pdecode_set_timeline(unsigned long long* ts, int step);      // non-null: thread 0 of every workgroup stamps the phases of that step
-int launch_pdecode(const PDecP& p, void* ws, int64_t ws_bytes, hipStream_t s, const int32_t* lens_host = nullptr);      // xch / status are carved from ws; lens_host: the lengths p.lens was written from
+// the clips' own lengths of a masked call, one value: the device length table ([B] frames, then [B] content slots) and the host lengths it was written
+// from; both null: an unmasked call
+struct ClipLens {
+    int* dev = nullptr;
+    const int32_t* host = nullptr;
+    explicit operator bool() const { return dev != nullptr; }
+};
+int launch_pdecode(const PDecP& p, void* ws, int64_t ws_bytes, hipStream_t s, ClipLens lens = {});      // xch / status are carved from ws; p.lens is set from lens
 
 }  // namespace l2s

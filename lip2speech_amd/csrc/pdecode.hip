@@ -835,22 +835,44 @@ int pdecode_timeouts() {      // process-wide: the sum over the devices this pro
     return (int)n;
 }
 
-template <typename K>
-static bool pd_fits(K kernel, int lds) {
+// The kernel forms, named HERE and nowhere else: the residency check walks these two tables and the launchers look their form up in them, so that no
+// form is launched whose LDS limit was not raised and whose co-residency was not checked
+struct PdForm { const void* fn; int grid; };
+template <int NG, bool ES, int KF, bool ML>
+static PdForm pd_row() { return {reinterpret_cast<const void*>(pdecode_kernel<NG, 2, ES, KF, ML>), PD_WG * NG / 2}; }      // 128 workgroups per clip (launch_pdecode)
+template <int NB, bool ML>
+static PdForm pb_row() { return {reinterpret_cast<const void*>(pbilstm_kernel<NB, ML>), PD_WG}; }
+// the decode loop for the n (1 or 2) clips of a launch: es = option "early_stop" (clips leave the loop on their own), longf = option "persist_frames"
+// (PD_KF_LONG key frames per thread), ml = option "persist_masked" (the length-masked instantiations)
+static PdForm pd_form(int n, bool es, bool longf, bool ml) {
+    static const PdForm forms[2][2][2][2] = {      // [ml][longf][es][n - 1]
+        {{{pd_row<1, false, 1, false>(), pd_row<2, false, 1, false>()}, {pd_row<1, true, 1, false>(), pd_row<2, true, 1, false>()}},
+         {{pd_row<1, false, PD_KF_LONG, false>(), pd_row<2, false, PD_KF_LONG, false>()}, {pd_row<1, true, PD_KF_LONG, false>(), pd_row<2, true, PD_KF_LONG, false>()}}},
+        {{{pd_row<1, false, 1, true>(), pd_row<2, false, 1, true>()}, {pd_row<1, true, 1, true>(), pd_row<2, true, 1, true>()}},
+         {{pd_row<1, false, PD_KF_LONG, true>(), pd_row<2, false, PD_KF_LONG, true>()}, {pd_row<1, true, PD_KF_LONG, true>(), pd_row<2, true, PD_KF_LONG, true>()}}}};
+    return forms[ml][longf][es][n - 1];
+}
+// the BiLSTM recurrence of a call of n (1 or 2) clips; ml: every (direction, clip) pair runs its clip's own length
+static PdForm pb_form(int n, bool ml) {
+    static const PdForm forms[2][2] = {{pb_row<1, false>(), pb_row<2, false>()}, {pb_row<1, true>(), pb_row<2, true>()}};      // [ml][n - 1]
+    return forms[ml][n - 1];
+}
+
+static bool pd_fits(const void* kernel, int lds) {
     int nb = 0;
     return hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kernel, PD_NT, (size_t)lds) == hipSuccess && nb >= 1;
 }
-
-// the four length-masked instantiations of the decode loop with KF key frames per thread (and, with the short forms, the masked BiLSTM): LDS limit raised, one workgroup per CU
-template <int KF>
-static bool pd_resident_masked() {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(pdecode_kernel<1, 2, false, KF, true>), hipFuncAttributeMaxDynamicSharedMemorySize, PD_LDS_MAX);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(pdecode_kernel<2, 2, false, KF, true>), hipFuncAttributeMaxDynamicSharedMemorySize, PD_LDS_MAX);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(pdecode_kernel<1, 2, true, KF, true>), hipFuncAttributeMaxDynamicSharedMemorySize, PD_LDS_MAX);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(pdecode_kernel<2, 2, true, KF, true>), hipFuncAttributeMaxDynamicSharedMemorySize, PD_LDS_MAX);
-    return pd_fits(pdecode_kernel<1, 2, false, KF, true>, PD_LDS_MAX) && pd_fits(pdecode_kernel<2, 2, false, KF, true>, PD_LDS_MAX) &&
-           pd_fits(pdecode_kernel<1, 2, true, KF, true>, PD_LDS_MAX) && pd_fits(pdecode_kernel<2, 2, true, KF, true>, PD_LDS_MAX) &&
-           (KF > 1 || (pd_fits(pbilstm_kernel<1, true>, 0) && pd_fits(pbilstm_kernel<2, true>, 0)));
+// every form of one envelope fits one workgroup per compute unit: the eight short forms of the decode loop (LDS limit raised, asked at the largest
+// request) and the four BiLSTM forms, or (longf) the eight long-clip forms
+static bool pd_resident(bool longf) {
+    for (int i = 0; i < 8; ++i) {
+        const PdForm f = pd_form(1 + (i & 1), (i & 2) != 0, longf, (i & 4) != 0);
+        (void)hipFuncSetAttribute(f.fn, hipFuncAttributeMaxDynamicSharedMemorySize, PD_LDS_MAX);
+        if (!pd_fits(f.fn, PD_LDS_MAX)) return false;
+    }
+    for (int i = 0; i < 4 && !longf; ++i)
+        if (!pd_fits(pb_form(1 + (i & 1), (i & 2) != 0).fn, 0)) return false;
+    return true;
 }
 
 // the current device's entry (g_pd_mu held); nullptr when the device cannot be queried
@@ -870,25 +892,8 @@ static PdDevice* pd_device_locked() {
         // compute-unit mask in the environment (the device then still reports 256 but hands out fewer).  What cannot be seen from here - another
         // process on the device - is bounded by the kernels' own 2 s give-up and reported through the guard kernel.
         const bool masked = std::getenv("HSA_CU_MASK") || std::getenv("ROC_GLOBAL_CU_MASK");
-        bool fits = d.cus >= PD_WG && !masked && d.timeouts;
-        if (fits) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(pdecode_kernel<1, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, PD_LDS_MAX);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(pdecode_kernel<2, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, PD_LDS_MAX);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(pdecode_kernel<1, 2, true>), hipFuncAttributeMaxDynamicSharedMemorySize, PD_LDS_MAX);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(pdecode_kernel<2, 2, true>), hipFuncAttributeMaxDynamicSharedMemorySize, PD_LDS_MAX);
-            fits = pd_fits(pdecode_kernel<1, 2>, PD_LDS_MAX) && pd_fits(pdecode_kernel<2, 2>, PD_LDS_MAX) && pd_fits(pdecode_kernel<1, 2, true>, PD_LDS_MAX) && pd_fits(pdecode_kernel<2, 2, true>, PD_LDS_MAX) && pd_fits(pbilstm_kernel<1>, 0) && pd_fits(pbilstm_kernel<2>, 0);
-        }
-        if (fits) fits = pd_resident_masked<1>();      // the length-masked instantiations ("persist_masked") of the same forms
-        d.resident = fits;
-        if (fits) {      // the long-clip forms ("persist_frames"): more registers; where one does not fit, the long envelope alone is off on this device
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(pdecode_kernel<1, 2, false, PD_KF_LONG>), hipFuncAttributeMaxDynamicSharedMemorySize, PD_LDS_MAX);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(pdecode_kernel<2, 2, false, PD_KF_LONG>), hipFuncAttributeMaxDynamicSharedMemorySize, PD_LDS_MAX);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(pdecode_kernel<1, 2, true, PD_KF_LONG>), hipFuncAttributeMaxDynamicSharedMemorySize, PD_LDS_MAX);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(pdecode_kernel<2, 2, true, PD_KF_LONG>), hipFuncAttributeMaxDynamicSharedMemorySize, PD_LDS_MAX);
-            d.resident_long = pd_fits(pdecode_kernel<1, 2, false, PD_KF_LONG>, PD_LDS_MAX) && pd_fits(pdecode_kernel<2, 2, false, PD_KF_LONG>, PD_LDS_MAX) &&
-                              pd_fits(pdecode_kernel<1, 2, true, PD_KF_LONG>, PD_LDS_MAX) && pd_fits(pdecode_kernel<2, 2, true, PD_KF_LONG>, PD_LDS_MAX) &&
-                              pd_resident_masked<PD_KF_LONG>();
-        }
+        d.resident = d.cus >= PD_WG && !masked && d.timeouts && pd_resident(false);
+        d.resident_long = d.resident && pd_resident(true);      // more registers; where a long-clip form does not fit, the long envelope alone is off on this device
         d.init = true;
     }
     return &d;
@@ -928,32 +933,25 @@ void pdecode_rearm() {
     if (d && d->timeouts) d->armed_at = __atomic_load_n(d->timeouts, __ATOMIC_RELAXED);      // `seen` stays: a time-out nobody has been told about is still reported by the gate
 }
 
-// the masked instantiations of one (ES, KF) form for the launch's one or two clips
-template <bool ES, int KF>
-static void pd_launch_masked(int n, int starve, int lds, hipStream_t s, const PDecP& q) {
-    if (n == 1) hipLaunchKernelGGL((pdecode_kernel<1, 2, ES, KF, true>), dim3(PD_WG / 2 - starve), dim3(PD_NT), lds, s, q);
-    else hipLaunchKernelGGL((pdecode_kernel<2, 2, ES, KF, true>), dim3(PD_WG - starve), dim3(PD_NT), lds, s, q);
-}
-
-// lens_host (with p.lens, the device length table written from it): a masked call - every launch takes the form and the LDS of the longest of ITS clips
-int launch_pdecode(const PDecP& p, void* ws, int64_t ws_bytes, hipStream_t s, const int32_t* lens_host) {
+// lens: a masked call (p.lens is set from it here) - every launch takes the form and the LDS of the longest of ITS clips
+int launch_pdecode(const PDecP& p, void* ws, int64_t ws_bytes, hipStream_t s, ClipLens lens) {
     L2S_REQUIRE(pdecode_supported(p.B, p.T, p.m, PD_MAXT_LONG), "persistent decode: <= 4 clips of <= 80 frames whose values fit the LDS");
     L2S_REQUIRE(ws && ws_bytes >= pdecode_ws_bytes(2), "persistent decode: exchange buffer too small");
     std::lock_guard<std::mutex> lock(g_pd_mu);
     PdDevice* const dv = pd_device_locked();
     L2S_REQUIRE(pd_armed(dv), "persistent decode needs 256 compute units, one resident workgroup each (none masked), and no timed-out launch since the device was armed");
-    L2S_REQUIRE(!lens_host == !p.lens, "persistent decode: host lengths and the device length table come together");
-    L2S_REQUIRE(pd_longest(lens_host, p.T, 0, p.B) <= PD_MAXT || dv->resident_long, "persistent decode: the long-clip forms do not fit one workgroup per compute unit on this device");      // (callers ask pdecode_gate(T) first)
+    L2S_REQUIRE(pd_longest(lens.host, p.T, 0, p.B) <= PD_MAXT || dv->resident_long, "persistent decode: the long-clip forms do not fit one workgroup per compute unit on this device");      // (callers ask pdecode_gate(T) first)
     L2S_CHECK_HIP(hipStreamWaitEvent(s, dv->ev, 0));      // a never-recorded event is complete
     ProfScope ps("decode_persistent", s);
     // clips two at a time (three or four clips: two launches one after the other - still shorter than 300 x four launches)
     for (int b0 = 0; b0 < p.B; b0 += 2) {
         const int n = p.B - b0 >= 2 ? 2 : 1;
         int Lc[4];
-        const int Tl = pd_longest(lens_host, p.T, b0, n), ml = lens_host ? std::max(content_lens(Tl, Lc), 1) : p.m;      // the launch's longest clip, its content slots
+        const int Tl = pd_longest(lens.host, p.T, b0, n), ml = lens.host ? std::max(content_lens(Tl, Lc), 1) : p.m;      // the launch's longest clip, its content slots
         const bool longf = Tl > PD_MAXT;      // the long-clip forms
         const int lds = std::max(pd_lds_floats(2, Tl, ml, pd_form_mt(Tl)) * 4, PD_LDS_MIN);
         PDecP q = p;
+        q.lens = lens.dev;
         q.b0 = b0;
         q.xch = reinterpret_cast<u64*>(ws);
         q.status = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(ws) + (int64_t)pd_rstride(2) * 8 * PD_MAXREP);
@@ -969,25 +967,9 @@ int launch_pdecode(const PDecP& p, void* ws, int64_t ws_bytes, hipStream_t s, co
 #else
         constexpr int starve = 0;
 #endif
-        if (lens_host) {    // option "persist_masked": the length-masked instantiations of the same four forms
-            if (longf) { if (p.early) pd_launch_masked<true, PD_KF_LONG>(n, starve, lds, s, q); else pd_launch_masked<false, PD_KF_LONG>(n, starve, lds, s, q); }
-            else if (p.early) pd_launch_masked<true, 1>(n, starve, lds, s, q);
-            else pd_launch_masked<false, 1>(n, starve, lds, s, q);
-        }
-        else if (longf) {   // option "persist_frames": PD_KF_LONG key frames per thread, the same loop otherwise
-            if (p.early) {
-                if (n == 1) hipLaunchKernelGGL((pdecode_kernel<1, 2, true, PD_KF_LONG>), dim3(PD_WG / 2 - starve), dim3(PD_NT), lds, s, q);
-                else hipLaunchKernelGGL((pdecode_kernel<2, 2, true, PD_KF_LONG>), dim3(PD_WG - starve), dim3(PD_NT), lds, s, q);
-            }
-            else if (n == 1) hipLaunchKernelGGL((pdecode_kernel<1, 2, false, PD_KF_LONG>), dim3(PD_WG / 2 - starve), dim3(PD_NT), lds, s, q);
-            else hipLaunchKernelGGL((pdecode_kernel<2, 2, false, PD_KF_LONG>), dim3(PD_WG - starve), dim3(PD_NT), lds, s, q);
-        }
-        else if (p.early) {      // option "early_stop": the instantiations whose clips leave the loop on their own
-            if (n == 1) hipLaunchKernelGGL((pdecode_kernel<1, 2, true>), dim3(PD_WG / 2 - starve), dim3(PD_NT), lds, s, q);
-            else hipLaunchKernelGGL((pdecode_kernel<2, 2, true>), dim3(PD_WG - starve), dim3(PD_NT), lds, s, q);
-        }
-        else if (n == 1) hipLaunchKernelGGL((pdecode_kernel<1, 2>), dim3(PD_WG / 2 - starve), dim3(PD_NT), lds, s, q);
-        else hipLaunchKernelGGL((pdecode_kernel<2, 2>), dim3(PD_WG - starve), dim3(PD_NT), lds, s, q);
+        const PdForm f = pd_form(n, p.early != 0, longf, lens.host != nullptr);
+        void* args[] = {&q};
+        (void)hipLaunchKernel(f.fn, dim3(f.grid - starve), dim3(PD_NT), args, lds, s);      // a failed launch is reported by hipGetLastError below
         hipLaunchKernelGGL(pdecode_guard_kernel, dim3(8), dim3(256), 0, s, q.status, q.mel, q.stop, q.attn, q.B * q.S * 80, q.B * q.S, q.attn ? q.B * q.S * q.T : 0, dv->timeouts);
         L2S_CHECK_HIP(hipGetLastError());
     }
@@ -1009,12 +991,9 @@ int launch_pbilstm(const PBiP& p, void* ws, int64_t ws_bytes, hipStream_t s) {
     L2S_CHECK_HIP(hipMemsetAsync(q.h_state, 0, sizeof(float) * 2 * ((p.B + 15) & ~15) * 512, s));
     L2S_CHECK_HIP(hipStreamWaitEvent(s, dv->ev, 0));
     ProfScope ps("bilstm_persistent", s);
-    if (p.lens) {      // option "persist_masked": every (direction, clip) pair runs its clip's own length
-        if (p.B == 1) hipLaunchKernelGGL((pbilstm_kernel<1, true>), dim3(PD_WG), dim3(PD_NT), 0, s, q);
-        else hipLaunchKernelGGL((pbilstm_kernel<2, true>), dim3(PD_WG), dim3(PD_NT), 0, s, q);
-    }
-    else if (p.B == 1) hipLaunchKernelGGL(pbilstm_kernel<1>, dim3(PD_WG), dim3(PD_NT), 0, s, q);
-    else hipLaunchKernelGGL(pbilstm_kernel<2>, dim3(PD_WG), dim3(PD_NT), 0, s, q);
+    const PdForm f = pb_form(p.B, p.lens != nullptr);
+    void* args[] = {&q};
+    (void)hipLaunchKernel(f.fn, dim3(f.grid), dim3(PD_NT), args, 0, s);
     hipLaunchKernelGGL(pdecode_guard_kernel, dim3(8), dim3(256), 0, s, q.status, q.rnn, q.cellcat, q.h_state, p.B * p.T * 1024, p.B * 1024, 2 * ((p.B + 15) & ~15) * 512, dv->timeouts);
     L2S_CHECK_HIP(hipGetLastError());
     L2S_CHECK_HIP(hipEventRecord(dv->ev, s));
