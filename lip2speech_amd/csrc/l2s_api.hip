@@ -1,6 +1,6 @@
-// C-ABI of libl2s_hip.so (include/l2s.h): weight packing, workspace planning and the launch sequences of
-// the visual encoder, decoder prologue, decode loop and post-net.  Host code only orchestrates; all
-// arithmetic is in the kernels of gemm_nt.hip / encoder_kernels.hip / skinny.hip / decoder_kernels.hip.
+// C-ABI of libl2s_hip.so (include/l2s.h): workspace planning and the launch sequences of the visual encoder,
+// decoder prologue, decode loop and post-net (the weight blob is built and refreshed in l2s_pack.hip).  Host code
+// only orchestrates; all arithmetic is in the kernels of gemm_nt.hip / encoder_kernels.hip / skinny.hip / decoder_kernels.hip.
 #include "../../include/l2s.h"
 #ifdef L2S_DIAG
 #include "../../include/l2s_diag.h"
@@ -105,897 +105,6 @@ static void prof_drain() {
 
 namespace l2s {
 
-// host-side blob builder: every sub-array 64-float (256 B) aligned
-struct Blob {
-    std::vector<float> data;
-    int64_t alloc(int64_t n) {
-        int64_t off = align_up((int64_t)data.size(), 64);
-        data.resize(off + n, 0.f);
-        return off;
-    }
-};
-
-struct Packer {
-    l2s_model* m;
-    Blob blob;
-    std::vector<std::pair<const float**, int64_t>> fixups;   // pointer slots to patch once the device address is known
-    std::string missing;
-
-    const std::vector<float>* get(const std::string& key, int64_t numel) {
-        auto it = m->host.find(key);
-        if (it == m->host.end()) { if (missing.empty()) missing = "missing tensor " + key; return nullptr; }
-        if ((int64_t)it->second.size() != numel) {
-            if (missing.empty()) missing = "tensor " + key + " has " + std::to_string(it->second.size()) + " elements, expected " + std::to_string(numel);
-            return nullptr;
-        }
-        return &it->second;
-    }
-    void bind(const float** slot, int64_t off) { fixups.emplace_back(slot, off); }
-
-    // BatchNorm (eval) as scale/shift, optionally absorbing a conv bias: v = (acc + b - mu) * s + beta
-    std::vector<l2s_model::RefreshBn> bn_rec;
-    std::vector<l2s_model::RefreshSum> sum_rec;
-    void bn(const std::string& p, int c, const std::vector<float>* bias, const float** scale, const float** shift, const std::string& bias_key = std::string()) {
-        auto g = get(p + ".weight", c), b = get(p + ".bias", c), mu = get(p + ".running_mean", c), var = get(p + ".running_var", c);
-        if (!g || !b || !mu || !var) return;
-        int64_t so = blob.alloc(c), ho = blob.alloc(c);
-        for (int i = 0; i < c; ++i) {
-            float s = (*g)[i] / std::sqrt((*var)[i] + BN_EPS);
-            float cb = bias ? (*bias)[i] : 0.f;
-            blob.data[so + i] = s;
-            blob.data[ho + i] = (cb - (*mu)[i]) * s + (*b)[i];
-        }
-        bind(scale, so);
-        bind(shift, ho);
-        bn_rec.push_back({p, bias_key, c, so, ho});
-    }
-    void copy(const std::string& key, int64_t n, const float** slot) {
-        auto v = get(key, n);
-        if (!v) return;
-        int64_t o = blob.alloc(n);
-        std::memcpy(&blob.data[o], v->data(), n * sizeof(float));
-        bind(slot, o);
-    }
-    // Conv1d weight (co, ci, k) -> [co][k*ci] (tap-major K)
-    void conv1d_w(const std::string& key, int co, int ci, int k, const float** slot) {
-        auto v = get(key, (int64_t)co * ci * k);
-        if (!v) return;
-        int64_t o = blob.alloc((int64_t)co * ci * k);
-        for (int n = 0; n < co; ++n)
-            for (int c = 0; c < ci; ++c)
-                for (int t = 0; t < k; ++t) blob.data[o + ((int64_t)n * k + t) * ci + c] = (*v)[((int64_t)n * ci + c) * k + t];
-        bind(slot, o);
-    }
-    // depthwise (c,1,3,3) -> [9][c]
-    void dw_w(const std::string& key, int c, const float** slot) {
-        auto v = get(key, (int64_t)c * 9);
-        if (!v) return;
-        int64_t o = blob.alloc((int64_t)c * 9);
-        for (int ch = 0; ch < c; ++ch)
-            for (int t = 0; t < 9; ++t) blob.data[o + (int64_t)t * c + ch] = (*v)[(int64_t)ch * 9 + t];
-        bind(slot, o);
-    }
-    // frag16 packing of rows[n] (each K long) of a virtual [Npad][K] matrix; row_of(n) returns nullptr for zero rows
-    template <typename RowFn>
-    void frag16(int Npad, int K, RowFn row_of, const float** slot) {
-        int64_t o = blob.alloc((int64_t)Npad * K);
-        const int NC = K / 16;
-        std::vector<float> row(K);
-        for (int n = 0; n < Npad; ++n) {
-            bool nz = row_of(n, row.data());
-            if (!nz) continue;
-            for (int k = 0; k < K; ++k) {
-                int tile = n >> 4, i = n & 15, c = k >> 4, g = (k >> 2) & 3, e = k & 3;
-                blob.data[o + ((int64_t)(tile * NC + c) * 64 + g * 16 + i) * 4 + e] = row[k];
-            }
-        }
-        bind(slot, o);
-    }
-};
-
-static int lstm_perm_row(int np, int H) {      // packed row (unit-major: 4*unit + gate) -> PyTorch row gate*H + unit
-    int unit = np >> 2, gate = np & 3;
-    return gate * H + unit;
-}
-
-
-static int pack_host(l2s_model* m, Packer& P, bool& want_enc, bool& want_dec, bool& want_spk, bool& want_face) {
-    m->w = Weights{};
-    Weights& w = m->w;
-    const std::string E = "encoder.", Dk = "decoder.";
-    // The two halves of the path are packed independently so that a VideoExtractor or a Decoder used on its
-    // own (as the reference allows: net.encoder / net.decoder) needs only its own keys.
-    auto has_prefix = [&](const std::string& pre) {
-        for (auto& kv : m->host) if (kv.first.compare(0, pre.size(), pre) == 0) return true;
-        return false;
-    };
-    const std::string Sk = "speaker_encoder.";
-    const std::string Fk = "vgg_face.";
-    want_enc = has_prefix(E); want_dec = has_prefix(Dk); want_spk = has_prefix(Sk); want_face = has_prefix(Fk);
-    if (!want_enc && !want_dec && !want_spk && !want_face) {
-        set_error("l2s_model_finalize: no encoder.* / decoder.* / speaker_encoder.* / vgg_face.* tensors were set");
-        return 1;
-    }
-    if (want_enc) {
-
-    // ---- frontend: Conv3d (24,3,5,7,7) -> [slab = ci*5+kt][50][32]
-    {
-        auto v = P.get(E + "frontend3D.0.weight", 24 * 3 * 5 * 49);
-        if (v) {
-            int64_t o = P.blob.alloc(15 * 50 * 32);
-            for (int co = 0; co < 24; ++co)
-                for (int ci = 0; ci < 3; ++ci)
-                    for (int kt = 0; kt < 5; ++kt)
-                        for (int tap = 0; tap < 49; ++tap)
-                            P.blob.data[o + ((int64_t)(ci * 5 + kt) * 50 + tap) * 32 + co] = (*v)[(((int64_t)co * 3 + ci) * 5 + kt) * 49 + tap];
-            P.bind(&w.fe.w, o);
-            // the same weights as split-bf16 operand planes (frontend3d_x3_kernel): per slab, step s = kernel rows 2s, 2s+1 (row 7: zeros),
-            // 8 taps per row = one zero tap + the 7 real ones; every value split exactly into hi + mid + lo by truncation
-            const int64_t o3 = P.blob.alloc(15 * 18432 / 4);
-            unsigned char* base3 = reinterpret_cast<unsigned char*>(&P.blob.data[o3]);
-            for (int slab = 0; slab < 15; ++slab)
-                for (int st = 0; st < 4; ++st)
-                    for (int n = 0; n < 32; ++n)
-                        for (int k = 0; k < 16; ++k) {
-                            const int kh = 2 * st + (k >> 3), kw = (k & 7) - 1, ci = slab / 5, kt = slab % 5;
-                            float x = 0.f;
-                            if (n < 24 && kh < 7 && kw >= 0) x = (*v)[(((int64_t)n * 3 + ci) * 5 + kt) * 49 + kh * 7 + kw];
-                            uint32_t xb, hb, mb, lb; float r1, r2, tmp;
-                            std::memcpy(&xb, &x, 4); hb = xb & 0xFFFF0000u; std::memcpy(&tmp, &hb, 4); r1 = x - tmp;
-                            std::memcpy(&mb, &r1, 4); mb &= 0xFFFF0000u; std::memcpy(&tmp, &mb, 4); r2 = r1 - tmp;
-                            std::memcpy(&lb, &r2, 4);
-                            const uint16_t planes[3] = {(uint16_t)(hb >> 16), (uint16_t)(mb >> 16), (uint16_t)(lb >> 16)};
-                            for (int pl = 0; pl < 3; ++pl)
-                                std::memcpy(base3 + (int64_t)slab * 18432 + ((st * 3 + pl) * 32 + n) * 48 + k * 2, &planes[pl], 2);
-                        }
-            P.bind(&w.fe.w3, o3);
-            // and as ONE bf16 plane rounded to nearest even, for the bf16 leg (option "infer_bf16")
-            const int64_t o1 = P.blob.alloc(15 * 6144 / 4);
-            unsigned char* base1 = reinterpret_cast<unsigned char*>(&P.blob.data[o1]);
-            for (int slab = 0; slab < 15; ++slab)
-                for (int st = 0; st < 4; ++st)
-                    for (int n = 0; n < 32; ++n)
-                        for (int k = 0; k < 16; ++k) {
-                            const int kh = 2 * st + (k >> 3), kw = (k & 7) - 1, ci = slab / 5, kt = slab % 5;
-                            float x = 0.f;
-                            if (n < 24 && kh < 7 && kw >= 0) x = (*v)[(((int64_t)n * 3 + ci) * 5 + kt) * 49 + kh * 7 + kw];
-                            uint32_t xb; std::memcpy(&xb, &x, 4);
-                            const uint16_t r = (uint16_t)((xb + 0x7FFFu + ((xb >> 16) & 1u)) >> 16);
-                            std::memcpy(base1 + (int64_t)slab * 6144 + (st * 32 + n) * 48 + k * 2, &r, 2);
-                        }
-            P.bind(&w.fe.w1, o1);
-        }
-        P.bn(E + "frontend3D.1", 24, nullptr, &w.fe.scale, &w.fe.shift);
-        P.copy(E + "frontend3D.2.weight", 24, &w.fe.slope);
-    }
-    // ---- ShuffleNet units
-    {
-        int u = 0, cin = STAGE_CH[0];
-        for (int st = 0; st < 3; ++st) {
-            int cout = STAGE_CH[st + 1], half = cout / 2;
-            for (int r = 0; r < STAGE_REP[st]; ++r, ++u) {
-                UnitW& U = w.unit[u];
-                std::string p = E + "trunk.0." + std::to_string(u) + ".";
-                U.stride2 = (r == 0);
-                U.cin = cin;
-                U.half = half;
-                int pw1_in = U.stride2 ? cin : half;
-                if (U.stride2) {
-                    P.dw_w(p + "banch1.0.weight", cin, &U.b1_dw.w9);
-                    P.bn(p + "banch1.1", cin, nullptr, &U.b1_dw.scale, &U.b1_dw.shift);
-                    P.copy(p + "banch1.2.weight", (int64_t)half * cin, &U.b1_pw.W);
-                    P.bn(p + "banch1.3", half, nullptr, &U.b1_pw.scale, &U.b1_pw.shift);
-                }
-                P.copy(p + "banch2.0.weight", (int64_t)half * pw1_in, &U.pw1.W);
-                P.bn(p + "banch2.1", half, nullptr, &U.pw1.scale, &U.pw1.shift);
-                P.dw_w(p + "banch2.3.weight", half, &U.dw.w9);
-                P.bn(p + "banch2.4", half, nullptr, &U.dw.scale, &U.dw.shift);
-                P.copy(p + "banch2.5.weight", (int64_t)half * half, &U.pw2.W);
-                P.bn(p + "banch2.6", half, nullptr, &U.pw2.scale, &U.pw2.shift);
-                {   // fused-unit operands: the pointwise weights in frag16 layout, K zero-padded to a multiple of 16
-                    U.kpad = pad16(half);
-                    U.kin = pad16(pw1_in);
-                    struct { const char* key; int K, Kp; const float** slot; } fr[3] = {
-                        {"banch2.0.weight", pw1_in, U.stride2 ? U.kin : U.kpad, &U.pw1_frag},
-                        {"banch2.5.weight", half, U.kpad, &U.pw2_frag},
-                        {"banch1.2.weight", cin, U.kin, &U.b1_frag}};
-                    for (int which = 0; which < (U.stride2 ? 3 : 2); ++which) {
-                        const int K = fr[which].K, Kp = fr[which].Kp;
-                        auto wv = P.get(p + fr[which].key, (int64_t)half * K);
-                        if (!wv) continue;
-                        P.frag16(pad16(half), Kp, [&](int n, float* row) {
-                            if (n >= half) return false;
-                            std::memset(row, 0, sizeof(float) * Kp);
-                            std::memcpy(row, wv->data() + (int64_t)n * K, sizeof(float) * K);
-                            return true;
-                        }, fr[which].slot);
-                    }
-                }
-                cin = cout;
-            }
-        }
-        P.copy(E + "trunk.1.0.weight", (int64_t)LAST_CH * STAGE_CH[3], &w.conv_last.W);
-        P.bn(E + "trunk.1.1", LAST_CH, nullptr, &w.conv_last.scale, &w.conv_last.shift);
-    }
-    }   // want_enc
-    if (want_dec) {
-    // ---- decoder prologue
-    auto linear = [&](const std::string& p, int co, int ci, ConvW& c) {
-        P.copy(p + ".weight", (int64_t)co * ci, &c.W);
-        P.copy(p + ".bias", co, &c.shift);
-    };
-    P.conv1d_w(Dk + "residual_bottleneck.weight", D, 1024, 1, &w.resid.W);
-    P.copy(Dk + "residual_bottleneck.bias", D, &w.resid.shift);
-    linear(Dk + "encoder_site.0.linear_layer", D, 256, w.enc_site);
-    P.copy(Dk + "encoder_site.1.w", D, &w.enc_site.actw);
-    linear(Dk + "attention_site.0.linear_layer", D, 256, w.attn_site);
-    P.copy(Dk + "attention_site.1.w", D, &w.attn_site.actw);
-    linear(Dk + "E_C.linear_layer", D, 1024, w.e_c);
-    linear(Dk + "encoder_proj.linear_layer", D, 1024, w.enc_proj);
-    {   // BiLSTM: input weights of both directions stacked [4096][1024]; b_ih + b_hh folded into the GEMM shift
-        const char* suf[2] = {"l0", "l0_reverse"};
-        int64_t wo = P.blob.alloc((int64_t)4096 * 1024), bo = P.blob.alloc(4096);
-        for (int d = 0; d < 2; ++d) {
-            auto wi = P.get(Dk + "encoder_rnn.weight_ih_" + suf[d], (int64_t)2048 * 1024);
-            auto bi = P.get(Dk + "encoder_rnn.bias_ih_" + suf[d], 2048), bh = P.get(Dk + "encoder_rnn.bias_hh_" + suf[d], 2048);
-            auto wh = P.get(Dk + "encoder_rnn.weight_hh_" + suf[d], (int64_t)2048 * 512);
-            if (!wi || !bi || !bh || !wh) continue;
-            std::memcpy(&P.blob.data[wo + (int64_t)d * 2048 * 1024], wi->data(), sizeof(float) * 2048 * 1024);
-            for (int i = 0; i < 2048; ++i) P.blob.data[bo + d * 2048 + i] = (*bi)[i] + (*bh)[i];
-            P.sum_rec.push_back({Dk + "encoder_rnn.bias_ih_" + suf[d], Dk + "encoder_rnn.bias_hh_" + suf[d], 2048, 0, bo + d * 2048});
-            P.frag16(2048, 512, [&](int np, float* row) {
-                std::memcpy(row, wh->data() + (int64_t)lstm_perm_row(np, 512) * 512, sizeof(float) * 512);
-                return true;
-            }, &w.whh[d].W);
-            w.whh[d].N = 2048; w.whh[d].K = 512; w.whh[d].tiles = 128;
-        }
-        P.bind(&w.wih_cat, wo);
-        P.bind(&w.bih_cat, bo);
-    }
-    for (int kv = 0; kv < 2; ++kv) {
-        std::string p = Dk + (kv == 0 ? "K" : "V");
-        for (int j = 0; j < 4; ++j) {
-            std::string c = p + ".0.conv." + std::to_string(j);
-            P.conv1d_w(c + ".0.weight", D, D, MH_KS[j], &w.mh_branch[kv][j].W);
-            P.bn(c + ".1", D, P.get(c + ".0.bias", D), &w.mh_branch[kv][j].scale, &w.mh_branch[kv][j].shift, c + ".0.bias");
-        }
-        P.conv1d_w(p + ".0.bottleneck.weight", D, 5 * D, 1, &w.mh_bott[kv].W);
-        P.copy(p + ".0.bottleneck.bias", D, &w.mh_bott[kv].shift);
-        P.copy(p + ".1.w", D, &w.mh_bott[kv].actw);
-    }
-    P.copy(Dk + "positional_encodings.pos_table", (int64_t)L2S_MAX_STEPS * D, &w.pos);
-    for (int j = 0; j < 4; ++j) {
-        std::string c = Dk + "content.agg." + std::to_string(j);
-        P.conv1d_w(c + ".0.weight", D, D, CT_KS[j], &w.ct_branch[j].W);
-        P.bn(c + ".1", D, P.get(c + ".0.bias", D), &w.ct_branch[j].scale, &w.ct_branch[j].shift, c + ".0.bias");
-    }
-    P.conv1d_w(Dk + "content.bottleneck.weight", 256, 5 * D, 1, &w.ct_bott.W);
-    P.copy(Dk + "content.bottleneck.bias", 256, &w.ct_bott.shift);
-    linear(Dk + "content.K.0", 256, 256, w.ct_k0);
-    linear(Dk + "content.K.2", 256, 256, w.ct_k2);
-    linear(Dk + "content.location_fc.0", 256, 256, w.ct_fc0);
-    linear(Dk + "content.location_fc.2", 256, 256, w.ct_fc2);
-    linear(Dk + "content.location_fc.4", VOC, 256, w.ct_fc4);
-    {   // word_embeddings (501,256) -> transposed, K padded: [256][504]
-        auto v = P.get(Dk + "content.word_embeddings", (int64_t)VOC * 256);
-        if (v) {
-            int64_t o = P.blob.alloc((int64_t)256 * VOCP);
-            for (int n = 0; n < 256; ++n)
-                for (int k = 0; k < VOC; ++k) P.blob.data[o + (int64_t)n * VOCP + k] = (*v)[(int64_t)k * 256 + n];
-            P.bind(&w.ct_emb.W, o);
-        }
-    }
-    // ---- decode-step weights in frag16 layout
-    auto sk_linear = [&](const std::string& wkey, const std::string& bkey, int N, int K, SkW& s) {
-        auto wv = P.get(wkey, (int64_t)N * K);
-        int Np = pad16(N);
-        if (wv)
-            P.frag16(Np, K, [&](int n, float* row) {
-                if (n >= N) return false;
-                std::memcpy(row, wv->data() + (int64_t)n * K, sizeof(float) * K);
-                return true;
-            }, &s.W);
-        auto bv = P.get(bkey, N);
-        if (bv) {
-            int64_t o = P.blob.alloc(Np);
-            std::memcpy(&P.blob.data[o], bv->data(), sizeof(float) * N);
-            P.bind(&s.bias, o);
-        }
-        s.N = N; s.K = K; s.tiles = Np / 16;
-    };
-    sk_linear(Dk + "prenet.0.linear_layer.weight", Dk + "prenet.0.linear_layer.bias", 256, NM, w.pre1);
-    P.copy(Dk + "prenet.1.w", 256, &w.pre1.actw);
-    sk_linear(Dk + "prenet.3.linear_layer.weight", Dk + "prenet.3.linear_layer.bias", 256, 256, w.pre2);
-    P.copy(Dk + "prenet.4.w", 256, &w.pre2.actw);
-    sk_linear(Dk + "Q.0.linear_layer.weight", Dk + "Q.0.linear_layer.bias", D, 1024, w.q);
-    P.copy(Dk + "Q.1.w", D, &w.q.actw);
-    sk_linear(Dk + "content.Q.0.weight", Dk + "content.Q.0.bias", 256, 1024, w.cq);
-    sk_linear(Dk + "attention_proj.linear_layer.weight", Dk + "attention_proj.linear_layer.bias", 256, D, w.aproj);
-    for (int l = 0; l < 2; ++l) {
-        SkW& s = l == 0 ? w.lstm0 : w.lstm1;
-        std::string sl = "l" + std::to_string(l);
-        auto wi = P.get(Dk + "decoder_rnn.weight_ih_" + sl, (int64_t)2048 * 512), wh = P.get(Dk + "decoder_rnn.weight_hh_" + sl, (int64_t)2048 * 512);
-        auto bi = P.get(Dk + "decoder_rnn.bias_ih_" + sl, 2048), bh = P.get(Dk + "decoder_rnn.bias_hh_" + sl, 2048);
-        if (!wi || !wh || !bi || !bh) continue;
-        P.frag16(2048, 1024, [&](int np, float* row) {
-            int r = lstm_perm_row(np, 512);
-            std::memcpy(row, wi->data() + (int64_t)r * 512, sizeof(float) * 512);
-            std::memcpy(row + 512, wh->data() + (int64_t)r * 512, sizeof(float) * 512);
-            return true;
-        }, &s.W);
-        int64_t o = P.blob.alloc(2048);
-        for (int np = 0; np < 2048; ++np) { int r = lstm_perm_row(np, 512); P.blob.data[o + np] = (*bi)[r] + (*bh)[r]; }
-        P.bind(&s.bias, o);
-        P.sum_rec.push_back({Dk + "decoder_rnn.bias_ih_" + sl, Dk + "decoder_rnn.bias_hh_" + sl, 2048, 512, o});
-        s.N = 2048; s.K = 1024; s.tiles = 128;
-    }
-    {   // fc_out (80 rows) + stop-token row over h1 (row 80) in one weight: [96][512]
-        auto wf = P.get(Dk + "fc_out.linear_layer.weight", (int64_t)NM * D), bf = P.get(Dk + "fc_out.linear_layer.bias", NM);
-        auto ws = P.get(Dk + "stop_token_layer.linear_layer.weight", 1024);
-        if (wf && bf && ws) {
-            P.frag16(96, D, [&](int n, float* row) {
-                if (n < NM) std::memcpy(row, wf->data() + (int64_t)n * D, sizeof(float) * D);
-                else if (n == NM) std::memcpy(row, ws->data(), sizeof(float) * D);
-                else return false;
-                return true;
-            }, &w.fc.W);
-            int64_t o = P.blob.alloc(96);
-            std::memcpy(&P.blob.data[o], bf->data(), sizeof(float) * NM);
-            P.bind(&w.fc.bias, o);
-            int64_t t = P.blob.alloc(D);
-            std::memcpy(&P.blob.data[t], ws->data() + D, sizeof(float) * D);
-            P.bind(&w.stop_tail, t);
-        }
-        w.fc.N = NM + 1; w.fc.K = D; w.fc.tiles = 6;
-        P.copy(Dk + "stop_token_layer.linear_layer.bias", 1, &w.stop_bias);
-    }
-    {   // Phase merging: two linear maps that are applied back to back with nothing in between are
-        // pre-multiplied once, in fp64, and rounded to fp32:
-        //   prenet1(fc_out(h1)) = PSine(W_p1 (W_out h1 + b_out) + b_p1) = PSine((W_p1 W_out) h1 + (W_p1 b_out + b_p1))
-        //   LSTM0 gates on u = p2 + W_ap av + b_ap:  W_ih[:,256:] u = W_ih[:,256:] p2 + (W_ih[:,256:] W_ap) av + W_ih[:,256:] b_ap
-        auto wp1 = P.get(Dk + "prenet.0.linear_layer.weight", (int64_t)256 * NM), bp1 = P.get(Dk + "prenet.0.linear_layer.bias", 256);
-        auto wo = P.get(Dk + "fc_out.linear_layer.weight", (int64_t)NM * D), bo = P.get(Dk + "fc_out.linear_layer.bias", NM);
-        if (wp1 && bp1 && wo && bo) {
-            std::vector<float> wf((size_t)256 * D);
-            int64_t bo_off = P.blob.alloc(256);
-            std::vector<double> row(D);
-            for (int n = 0; n < 256; ++n) {
-                std::fill(row.begin(), row.end(), 0.0);
-                double bacc = (*bp1)[n];
-                for (int k = 0; k < NM; ++k) {
-                    const double a = (*wp1)[(int64_t)n * NM + k];
-                    const float* wr = wo->data() + (int64_t)k * D;
-                    for (int j = 0; j < D; ++j) row[j] += a * wr[j];
-                    bacc += a * (*bo)[k];
-                }
-                for (int j = 0; j < D; ++j) wf[(size_t)n * D + j] = (float)row[j];
-                P.blob.data[bo_off + n] = (float)bacc;
-            }
-            P.frag16(256, D, [&](int n, float* r) { std::memcpy(r, wf.data() + (size_t)n * D, sizeof(float) * D); return true; }, &w.pre1f.W);
-            P.bind(&w.pre1f.bias, bo_off);
-            P.copy(Dk + "prenet.1.w", 256, &w.pre1f.actw);
-            w.pre1f.N = 256; w.pre1f.K = D; w.pre1f.tiles = 16;
-        }
-        auto wi = P.get(Dk + "decoder_rnn.weight_ih_l0", (int64_t)2048 * 512), wh = P.get(Dk + "decoder_rnn.weight_hh_l0", (int64_t)2048 * 512);
-        auto bi = P.get(Dk + "decoder_rnn.bias_ih_l0", 2048), bh = P.get(Dk + "decoder_rnn.bias_hh_l0", 2048);
-        auto wap = P.get(Dk + "attention_proj.linear_layer.weight", (int64_t)256 * D), bap = P.get(Dk + "attention_proj.linear_layer.bias", 256);
-        if (wi && wh && bi && bh && wap && bap) {
-            std::vector<float> prod((size_t)2048 * D);      // (W_ih[:,256:512] @ W_ap) in PyTorch row order
-            std::vector<float> badd(2048);
-            std::vector<double> row(D);
-            for (int r = 0; r < 2048; ++r) {
-                std::fill(row.begin(), row.end(), 0.0);
-                double bacc = 0.0;
-                for (int k = 0; k < 256; ++k) {
-                    const double a = (*wi)[(int64_t)r * 512 + 256 + k];
-                    const float* wr = wap->data() + (int64_t)k * D;
-                    for (int j = 0; j < D; ++j) row[j] += a * wr[j];
-                    bacc += a * (*bap)[k];
-                }
-                for (int j = 0; j < D; ++j) prod[(size_t)r * D + j] = (float)row[j];
-                badd[r] = (float)((double)(*bi)[r] + (double)(*bh)[r] + bacc);
-            }
-            P.frag16(2048, 1536, [&](int np, float* rowp) {
-                int r = lstm_perm_row(np, 512);
-                std::memcpy(rowp, wi->data() + (int64_t)r * 512, sizeof(float) * 512);          // [cc | p2] columns of W_ih
-                std::memcpy(rowp + 512, prod.data() + (size_t)r * D, sizeof(float) * D);         // av columns
-                std::memcpy(rowp + 1024, wh->data() + (int64_t)r * 512, sizeof(float) * 512);   // h0 columns
-                return true;
-            }, &w.lstm0f.W);
-            int64_t o = P.blob.alloc(2048);
-            for (int np = 0; np < 2048; ++np) P.blob.data[o + np] = badd[lstm_perm_row(np, 512)];
-            P.bind(&w.lstm0f.bias, o);
-            w.lstm0f.N = 2048; w.lstm0f.K = 1536; w.lstm0f.tiles = 128;
-            // the same step with attention_proj applied to the VALUES once, in the prologue (V' = V W_ap^T + b_ap; the attention weights sum
-            // to one, so a @ V' = W_ap (a @ v) + b_ap): LSTM0 then reads o = a @ V' (256 wide) through a second copy of W_ih's u columns -
-            // K = 1280 instead of 1536, verbatim copies of the parameters only (the device-side refresh keeps them current by itself)
-            P.frag16(2048, 1280, [&](int np, float* rowp) {
-                int r = lstm_perm_row(np, 512);
-                std::memcpy(rowp, wi->data() + (int64_t)r * 512, sizeof(float) * 512);                 // [cc | p2] columns of W_ih
-                std::memcpy(rowp + 512, wi->data() + (int64_t)r * 512 + 256, sizeof(float) * 256);     // o: the u columns again
-                std::memcpy(rowp + 768, wh->data() + (int64_t)r * 512, sizeof(float) * 512);           // h0 columns
-                return true;
-            }, &w.lstm0v.W);
-            for (size_t fi = 0; fi < P.fixups.size(); ++fi)      // the plain LSTM0 bias (b_ih + b_hh, kept current by the refresh's bias-sum records)
-                if (P.fixups[fi].first == &w.lstm0.bias) { P.bind(&w.lstm0v.bias, P.fixups[fi].second); break; }
-            w.lstm0v.N = 2048; w.lstm0v.K = 1280; w.lstm0v.tiles = 128;
-            P.copy(Dk + "attention_proj.linear_layer.weight", (int64_t)256 * D, &w.vproj.W);
-            P.copy(Dk + "attention_proj.linear_layer.bias", 256, &w.vproj.shift);
-        }
-    }
-    P.copy(Dk + "BOS", NM, &w.bos);
-    P.copy(Dk + "temperature", 1, &w.tau);
-    P.copy(Dk + "content.temperature", 1, &w.tau_c);
-    // ---- postnet
-    for (int i = 0; i < 5; ++i) {
-        int ci = i == 0 ? NM : D, co = i == 4 ? NM : D;
-        std::string c = Dk + "postnet.convolutions." + std::to_string(i);
-        P.conv1d_w(c + ".0.conv.weight", co, ci, 5, &w.post[i].W);
-        P.bn(c + ".1", co, P.get(c + ".0.conv.bias", co), &w.post[i].scale, &w.post[i].shift, c + ".0.conv.bias");
-        if (i < 4) P.copy(Dk + "postnet.sin_activation." + std::to_string(i) + ".w", D, &w.post[i].actw);
-    }
-    }   // want_dec
-    if (want_spk) {
-        constexpr int NFFT = 400, NF = 201, NMEL = 40, NFP = 204;
-        {   // hann window (periodic), real-DFT matrix [cos | sin] and HTK mel filterbank, all computed in fp64
-            const double PI = 3.14159265358979323846;
-            int64_t wo = P.blob.alloc(NFFT), dof = P.blob.alloc((int64_t)2 * NF * NFFT), fo = P.blob.alloc((int64_t)NMEL * NFP);
-            for (int j = 0; j < NFFT; ++j) P.blob.data[wo + j] = (float)(0.5 - 0.5 * std::cos(2.0 * PI * j / NFFT));
-            for (int k = 0; k < NF; ++k)
-                for (int j = 0; j < NFFT; ++j) {
-                    const double ang = 2.0 * PI * (double)((int64_t)k * j % NFFT) / NFFT;
-                    P.blob.data[dof + (int64_t)k * NFFT + j] = (float)std::cos(ang);
-                    P.blob.data[dof + (int64_t)(NF + k) * NFFT + j] = (float)std::sin(ang);
-                }
-            // torchaudio.functional.create_fb_matrix(n_freqs=201, f_min=0, f_max=8000, n_mels=40, sample_rate=16000, norm=None), HTK scale
-            std::vector<double> fpts(NMEL + 2);
-            const double m_min = 0.0, m_max = 2595.0 * std::log10(1.0 + 8000.0 / 700.0);
-            for (int i = 0; i < NMEL + 2; ++i) {
-                const double mpt = m_min + (m_max - m_min) * i / (NMEL + 1);
-                fpts[i] = 700.0 * (std::pow(10.0, mpt / 2595.0) - 1.0);
-            }
-            for (int k = 0; k < NF; ++k) {
-                const double f = 8000.0 * k / (NF - 1);
-                for (int mm = 0; mm < NMEL; ++mm) {
-                    const double down = (f - fpts[mm]) / (fpts[mm + 1] - fpts[mm]);
-                    const double up = (fpts[mm + 2] - f) / (fpts[mm + 2] - fpts[mm + 1]);
-                    P.blob.data[fo + (int64_t)mm * NFP + k] = (float)std::max(0.0, std::min(down, up));
-                }
-            }
-            P.bind(&w.spk_window, wo); P.bind(&w.spk_dft, dof); P.bind(&w.spk_fbT, fo);
-        }
-        for (int l = 0; l < 3; ++l) {
-            const int in = l == 0 ? 40 : 256;
-            const std::string sl = "l" + std::to_string(l);
-            auto wi = P.get(Sk + "lstm.weight_ih_" + sl, (int64_t)1024 * in), wh = P.get(Sk + "lstm.weight_hh_" + sl, (int64_t)1024 * 256);
-            auto bi = P.get(Sk + "lstm.bias_ih_" + sl, 1024), bh = P.get(Sk + "lstm.bias_hh_" + sl, 1024);
-            if (!wi || !wh || !bi || !bh) continue;
-            P.copy(Sk + "lstm.weight_ih_" + sl, (int64_t)1024 * in, &w.spk_ih[l].W);
-            int64_t bo = P.blob.alloc(1024);
-            for (int i = 0; i < 1024; ++i) P.blob.data[bo + i] = (*bi)[i] + (*bh)[i];
-            P.bind(&w.spk_ih[l].shift, bo);
-            P.frag16(1024, 256, [&](int np, float* row) {
-                std::memcpy(row, wh->data() + (int64_t)lstm_perm_row(np, 256) * 256, sizeof(float) * 256);
-                return true;
-            }, &w.spk_hh[l].W);
-            w.spk_hh[l].N = 1024; w.spk_hh[l].K = 256; w.spk_hh[l].tiles = 64;
-        }
-        P.copy(Sk + "linear.weight", (int64_t)256 * 256, &w.spk_linear.W);
-        P.copy(Sk + "linear.bias", 256, &w.spk_linear.shift);
-    }   // want_spk
-    if (want_face) {
-        // face tower (vgg_face.py:28-60; face_tower.hip): every convolution of the layer table re-laid as [Cout][kh][kw][Cin] (fused heads: the
-        // parts' rows one after the other), BasicConv2d's BatchNorm (eps 1e-3) folded into scale / shift, the blocks' up-projections as
-        // scale = block scale, shift = bias * scale; resnet.logits is held by the caller and not packed
-        const auto& layers = face_layers();
-        if ((int)layers.size() != FACE_N_CONVS) { set_error("l2s_model_finalize: face layer table has " + std::to_string(layers.size()) + " entries"); return 1; }
-        for (int li = 0; li < FACE_N_CONVS; ++li) {
-            const FaceLayer& L = layers[li];
-            const int np = (int)L.parts.size(), N = L.cout * np, taps = L.kh * L.kw, K = taps * L.cin;
-            const int64_t wn = (int64_t)L.cout * K;
-            std::vector<const std::vector<float>*> wt(np), g(np), b(np), mu(np), var(np);
-            bool ok = true;
-            for (int j = 0; j < np; ++j) {
-                const std::string pre = Fk + L.parts[j];
-                if (L.res_scale == 0.f) {
-                    wt[j] = P.get(pre + ".conv.weight", wn);
-                    g[j] = P.get(pre + ".bn.weight", L.cout); b[j] = P.get(pre + ".bn.bias", L.cout);
-                    mu[j] = P.get(pre + ".bn.running_mean", L.cout); var[j] = P.get(pre + ".bn.running_var", L.cout);
-                    ok = ok && wt[j] && g[j] && b[j] && mu[j] && var[j];
-                } else {
-                    wt[j] = P.get(pre + ".weight", wn); b[j] = P.get(pre + ".bias", L.cout);
-                    ok = ok && wt[j] && b[j];
-                }
-            }
-            if (!ok) continue;
-            const int64_t wo = P.blob.alloc((int64_t)N * K), so = P.blob.alloc(N), ho = P.blob.alloc(N);
-            for (int j = 0; j < np; ++j) {
-                const std::vector<float>& v = *wt[j];
-                for (int n = 0; n < L.cout; ++n) {
-                    const int64_t row = wo + (int64_t)(j * L.cout + n) * K;
-                    for (int ci = 0; ci < L.cin; ++ci)
-                        for (int t = 0; t < taps; ++t) P.blob.data[row + (int64_t)t * L.cin + ci] = v[((int64_t)n * L.cin + ci) * taps + t];
-                    float sc, sh;
-                    if (L.res_scale == 0.f) {
-                        sc = (*g[j])[n] / std::sqrt((*var[j])[n] + FACE_BN_EPS);
-                        sh = (*b[j])[n] - (*mu[j])[n] * sc;
-                    } else {
-                        sc = L.res_scale;
-                        sh = (*b[j])[n] * L.res_scale;
-                    }
-                    P.blob.data[so + j * L.cout + n] = sc;
-                    P.blob.data[ho + j * L.cout + n] = sh;
-                }
-            }
-            P.bind(&w.face.convs[li].w, wo); P.bind(&w.face.convs[li].scale, so); P.bind(&w.face.convs[li].shift, ho);
-        }
-        auto transposed = [&](const std::string& key, int out, int in, const float** slot) {      // nn.Linear weight (out, in) -> [in][out]
-            auto v = P.get(key, (int64_t)out * in);
-            if (!v) return;
-            const int64_t o = P.blob.alloc((int64_t)out * in);
-            for (int r = 0; r < out; ++r)
-                for (int c = 0; c < in; ++c) P.blob.data[o + (int64_t)c * out + r] = (*v)[(int64_t)r * in + c];
-            P.bind(slot, o);
-        };
-        transposed(Fk + "resnet.last_linear.weight", 512, 1792, &w.face.tail.llT);
-        {
-            const std::string pre = Fk + "resnet.last_bn.";
-            auto g = P.get(pre + "weight", 512), b = P.get(pre + "bias", 512), mu = P.get(pre + "running_mean", 512), var = P.get(pre + "running_var", 512);
-            if (g && b && mu && var) {
-                const int64_t so = P.blob.alloc(512), ho = P.blob.alloc(512);
-                for (int i = 0; i < 512; ++i) {
-                    const float sc = (*g)[i] / std::sqrt((*var)[i] + FACE_BN_EPS);
-                    P.blob.data[so + i] = sc;
-                    P.blob.data[ho + i] = (*b)[i] - (*mu)[i] * sc;
-                }
-                P.bind(&w.face.tail.bn_s, so); P.bind(&w.face.tail.bn_h, ho);
-            }
-        }
-        transposed(Fk + "projection_layer.0.weight", 512, 512, &w.face.tail.p0T);
-        P.copy(Fk + "projection_layer.0.bias", 512, &w.face.tail.p0b);
-        transposed(Fk + "projection_layer.2.weight", 256, 512, &w.face.tail.p2T);
-        P.copy(Fk + "projection_layer.2.bias", 256, &w.face.tail.p2b);
-    }   // want_face
-    if (!P.missing.empty()) { set_error("l2s_model_finalize: " + P.missing); return 1; }
-    return 0;
-}
-
-static int build_refresh_map(l2s_model* m, const Packer& P, hipStream_t stream);
-
-// bf16 planes of the two decoder LSTM weights (layer 0 in its unmerged [content | u | h0] form, layer 1) for the split-bf16 LSTM blocks: derived on the
-// device from the packed fp32 fragments, after every pack and every device-side refresh
-static int derive_lstm_planes(l2s_model* m, hipStream_t s) {
-    Weights& w = m->w;
-    SkW* const sk[4] = {&w.lstm0, &w.lstm1, &w.whh[0], &w.whh[1]};          // decoder layers 0 (unmerged [content | u | h0]) and 1, the BiLSTM's two directions
-    for (SkW* k : sk) k->W3 = nullptr;
-    if (!m->has_dec) return 0;
-    int64_t bytes[4], total = 0;
-    for (int i = 0; i < 4; ++i) {
-        if (!sk[i]->W || sk[i]->K % 256) return 0;
-        bytes[i] = (int64_t)sk[i]->tiles * sk[i]->K * 96;                    // 16 columns x K x 6 bytes per tile
-        total += bytes[i];
-    }
-    if (!m->lstm_planes) L2S_CHECK_HIP(hipMalloc(&m->lstm_planes, total));
-    char* base = reinterpret_cast<char*>(m->lstm_planes);
-    for (int i = 0; i < 4; ++i) {
-        if (launch_skx_planes(sk[i]->W, sk[i]->tiles, sk[i]->K, base, s)) return 1;
-        sk[i]->W3 = base;
-        base += bytes[i];
-    }
-    return 0;
-}
-
-// bf16 planes of the constant weights that meet the split-bf16 GEMM's wide tile (post-net layers 0-3, the BiLSTM input matrix, conv_last) for its LDS-DMA
-// weight operand: derived on the device
-// from the packed fp32 [N][K] matrices, after every pack and every device-side refresh
-static int derive_gemm_planes(l2s_model* m, hipStream_t s) {
-    Weights& w = m->w;
-    for (int i = 0; i < 5; ++i) w.post[i].W3 = nullptr;
-    w.wih_cat3 = nullptr; w.conv_last.W3 = nullptr;
-    for (int kv = 0; kv < 2; ++kv) for (int j = 0; j < 4; ++j) w.mh_branch[kv][j].W3 = nullptr;
-    struct Item { const float* W; int N, K; const void** slot; };
-    std::vector<Item> items;
-    if (m->has_dec) {
-        const int Ks[4] = {5 * NM, 5 * 512, 5 * 512, 5 * 512};
-        for (int i = 0; i < 4; ++i) items.push_back({w.post[i].W, 512, Ks[i], &w.post[i].W3});
-        items.push_back({w.wih_cat, 4096, 1024, &w.wih_cat3});
-        for (int kv = 0; kv < 2; ++kv)
-            for (int j = 0; j < 4; ++j) items.push_back({w.mh_branch[kv][j].W, 512, 512 * MH_KS[j], &w.mh_branch[kv][j].W3});      // the eight MultiHop convs (k = 1, 3, 7, 11; K and V)
-    }
-    if (m->has_enc) items.push_back({w.conv_last.W, LAST_CH, STAGE_CH[3], &w.conv_last.W3});
-    int64_t total = 0;
-    for (const Item& it : items) { if (!it.W) return 0; total += (int64_t)it.N * it.K * 6; }
-    if (!total) return 0;
-    if (!m->gemm_planes) L2S_CHECK_HIP(hipMalloc(&m->gemm_planes, total));
-    char* base = reinterpret_cast<char*>(m->gemm_planes);
-    for (const Item& it : items) {
-        if (launch_gemm_planes(it.W, it.N, it.K, base, s)) return 1;
-        *it.slot = base;
-        base += (int64_t)it.N * it.K * 6;
-    }
-    return 0;
-}
-
-// bf16 operand planes of the fused ShuffleNet units' pointwise convs (option "trunk_x3"): derived on the device from the packed [N][K] matrices,
-// after every pack and every device-side refresh
-static int derive_unit_planes(l2s_model* m, hipStream_t s) {
-    Weights& w = m->w;
-    for (UnitW& U : w.unit) { U.pw1_p3 = nullptr; U.pw2_p3 = nullptr; U.b1_p3 = nullptr; }
-    if (!m->has_enc) return 0;
-    struct Item { const float* W; int N, K; const void** slot; };
-    std::vector<Item> items;
-    for (UnitW& U : w.unit) {
-        const int pw1_in = U.stride2 ? U.cin : U.half;
-        items.push_back({U.pw1.W, U.half, pw1_in, &U.pw1_p3});
-        items.push_back({U.pw2.W, U.half, U.half, &U.pw2_p3});
-        if (U.stride2) items.push_back({U.b1_pw.W, U.half, U.cin, &U.b1_p3});
-    }
-    int64_t total = 0;
-    for (const Item& it : items) { if (!it.W) return 0; total += su_planes_bytes(it.N, it.K); }
-    if (!m->unit_planes) L2S_CHECK_HIP(hipMalloc(&m->unit_planes, total));
-    char* base = reinterpret_cast<char*>(m->unit_planes);
-    for (const Item& it : items) {
-        if (launch_su_planes(it.W, it.N, it.K, base, s)) return 1;
-        *it.slot = base;
-        base += su_planes_bytes(it.N, it.K);
-    }
-    return 0;
-}
-
-static int pack_model(l2s_model* m, hipStream_t stream) {
-    Packer P{m};
-    bool want_enc = false, want_dec = false, want_spk = false, want_face = false;
-    if (pack_host(m, P, want_enc, want_dec, want_spk, want_face)) return 1;
-    if (m->opt.refresh_map && build_refresh_map(m, P, stream)) return 1;
-    m->folded_valid = true; m->planes_valid = true;
-
-    // upload and patch pointers
-    for (auto& g : m->graphs) { (void)hipGraphExecDestroy(g.exec); (void)hipGraphDestroy(g.graph); }
-    m->graphs.clear();
-    if (m->blob) { (void)hipFree(m->blob); m->blob = nullptr; }
-    m->blob_floats = (int64_t)P.blob.data.size();
-    L2S_CHECK_HIP(hipMalloc(&m->blob, m->blob_floats * sizeof(float)));
-    L2S_CHECK_HIP(hipMemcpyAsync(m->blob, P.blob.data.data(), m->blob_floats * sizeof(float), hipMemcpyHostToDevice, stream));
-    L2S_CHECK_HIP(hipStreamSynchronize(stream));     // the host staging vector dies with this scope
-    for (auto& f : P.fixups) *f.first = m->blob + f.second;
-    m->finalized = true;
-    m->has_enc = want_enc;
-    m->has_dec = want_dec;
-    m->has_spk = want_spk;
-    m->has_face = want_face;
-    if (m->lstm_planes) { (void)hipFree(m->lstm_planes); m->lstm_planes = nullptr; }
-    if (derive_lstm_planes(m, stream)) return 1;
-    if (m->gemm_planes) { (void)hipFree(m->gemm_planes); m->gemm_planes = nullptr; }
-    if (derive_gemm_planes(m, stream)) return 1;
-    if (m->unit_planes) { (void)hipFree(m->unit_planes); m->unit_planes = nullptr; }
-    if (derive_unit_planes(m, stream)) return 1;
-    return 0;
-}
-
-// ------------------------------------------------------------------------------------------------ device-side refresh (training)
-// Which checkpoint element does each blob float copy?  Pack a shadow checkpoint whose elements carry their own global id as raw bits
-// (ids < 2^31 - 2^23 are finite positive floats, so plain copies preserve them; arithmetic on them produces other patterns), then keep an
-// entry only if the real blob holds exactly the value of the element the id names.  Computed entries (BatchNorm folds, bias sums) are
-// refreshed from the records the packer left; the phase-merged step weights are fp64 products and are invalidated instead.
-static int build_refresh_map(l2s_model* m, const Packer& P, hipStream_t stream) {
-    std::vector<std::string> keys;
-    for (auto& kv : m->host) keys.push_back(kv.first);
-    std::sort(keys.begin(), keys.end());
-    std::vector<int64_t> base(keys.size() + 1, 0);
-    for (size_t i = 0; i < keys.size(); ++i) base[i + 1] = base[i] + (int64_t)m->host[keys[i]].size();
-    L2S_REQUIRE(base.back() < 0x7F000000LL, "too many checkpoint elements for the refresh map");
-    std::unordered_map<std::string, std::vector<float>> shadow;
-    for (size_t i = 0; i < keys.size(); ++i) {
-        std::vector<float> v(m->host[keys[i]].size());
-        for (size_t j = 0; j < v.size(); ++j) { const uint32_t id = (uint32_t)(base[i] + (int64_t)j + 1); std::memcpy(&v[j], &id, 4); }
-        shadow.emplace(keys[i], std::move(v));
-    }
-    Weights saved = m->w;
-    m->host.swap(shadow);
-    Packer P2{m};
-    bool e = false, d = false, k = false, f = false;
-    const int rc = pack_host(m, P2, e, d, k, f);
-    m->host.swap(shadow);
-    m->w = saved;
-    if (rc) return 1;
-    L2S_REQUIRE(P2.blob.data.size() == P.blob.data.size(), "refresh map: shadow pack differs in size");
-    const int64_t n = (int64_t)P.blob.data.size();
-    std::vector<int32_t> rk(n, -1), ri(n, 0);
-    size_t cur = 0;
-    int64_t copies = 0;
-    for (int64_t i = 0; i < n; ++i) {
-        uint32_t id; std::memcpy(&id, &P2.blob.data[i], 4);
-        if (id == 0 || (int64_t)id > base.back()) continue;
-        const int64_t g = (int64_t)id - 1;
-        if (!(g >= base[cur] && g < base[cur + 1])) cur = (size_t)(std::upper_bound(base.begin(), base.end(), g) - base.begin()) - 1;
-        const std::vector<float>& src = m->host[keys[cur]];
-        const int64_t j = g - base[cur];
-        uint32_t a, b; std::memcpy(&a, &P.blob.data[i], 4); std::memcpy(&b, &src[j], 4);
-        if (a != b) continue;
-        rk[i] = (int32_t)cur; ri[i] = (int32_t)j; ++copies;
-    }
-    if (m->r_key) { (void)hipFree(m->r_key); m->r_key = nullptr; }
-    if (m->r_idx) { (void)hipFree(m->r_idx); m->r_idx = nullptr; }
-    L2S_CHECK_HIP(hipMalloc(&m->r_key, n * sizeof(int32_t)));
-    L2S_CHECK_HIP(hipMalloc(&m->r_idx, n * sizeof(int32_t)));
-    L2S_CHECK_HIP(hipMemcpyAsync(m->r_key, rk.data(), n * sizeof(int32_t), hipMemcpyHostToDevice, stream));
-    L2S_CHECK_HIP(hipMemcpyAsync(m->r_idx, ri.data(), n * sizeof(int32_t), hipMemcpyHostToDevice, stream));
-    L2S_CHECK_HIP(hipStreamSynchronize(stream));
-    m->r_keys = keys;
-    m->r_bn = P.bn_rec;
-    m->r_sum = P.sum_rec;
-    (void)copies;
-    return 0;
-}
-
-struct RBn { const float *g, *b, *mu, *var, *bias; float *scale, *shift; int c; };
-struct RSum { const float *a, *b; float* dst; int n, perm_H; };
-
-__global__ __launch_bounds__(256) void refresh_gather_kernel(float* __restrict__ blob, const int32_t* __restrict__ rk, const int32_t* __restrict__ ri,
-                                                             const float* const* __restrict__ ptrs, int64_t n) {
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-        const int k = rk[i];
-        if (k < 0) continue;
-        const float* src = ptrs[k];
-        if (src) blob[i] = src[ri[i]];
-    }
-}
-__global__ __launch_bounds__(256) void refresh_bn_kernel(const RBn* __restrict__ recs) {
-    const RBn r = recs[blockIdx.y];
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= r.c) return;
-    const float s = __fdiv_rn(r.g[i], __fsqrt_rn(r.var[i] + BN_EPS));   // correctly rounded, like the host packer's expression
-    const float cb = r.bias ? r.bias[i] : 0.f;
-    r.scale[i] = s;
-    r.shift[i] = __fadd_rn(__fmul_rn(__fsub_rn(cb, r.mu[i]), s), r.b[i]);      // no fused multiply-add: the host packer's x86 code has none either
-}
-__global__ __launch_bounds__(256) void refresh_sum_kernel(const RSum* __restrict__ recs) {
-    const RSum r = recs[blockIdx.y];
-    const int np = blockIdx.x * 256 + threadIdx.x;
-    if (np >= r.n) return;
-    const int src = r.perm_H ? (np & 3) * r.perm_H + (np >> 2) : np;
-    r.dst[np] = r.a[src] + r.b[src];
-}
-
-// ---- the front-end conv's bf16 operand planes (FrontendW::w3 / w1), re-derived from the bound Conv3d weight exactly as pack_host derives
-// them: per slab (ci, kt), step st = kernel rows 2st, 2st+1 (row 7: zeros), 8 taps per row = one zero tap + the 7 real ones; w3 = the
-// truncation split hi + mid + lo (exact), w1 = one plane rounded to nearest even
-__global__ __launch_bounds__(256) void refresh_frontend_planes_kernel(const float* __restrict__ w, uint16_t* __restrict__ w3, uint16_t* __restrict__ w1) {
-    const int idx = blockIdx.x * 256 + threadIdx.x;
-    if (idx >= 15 * 4 * 32 * 16) return;
-    const int k = idx & 15, n = (idx >> 4) & 31, st = (idx >> 9) & 3, slab = idx >> 11;
-    const int kh = 2 * st + (k >> 3), kw = (k & 7) - 1, ci = slab / 5, kt = slab % 5;
-    float x = 0.f;
-    if (n < 24 && kh < 7 && kw >= 0) x = w[(((int64_t)n * 3 + ci) * 5 + kt) * 49 + kh * 7 + kw];
-    const uint32_t xb = __float_as_uint(x), hb = xb & 0xFFFF0000u;
-    const float r1 = __fsub_rn(x, __uint_as_float(hb));
-    const uint32_t mb = __float_as_uint(r1) & 0xFFFF0000u;
-    const float r2 = __fsub_rn(r1, __uint_as_float(mb));
-    const uint32_t lb = __float_as_uint(r2);
-    const uint16_t planes[3] = {(uint16_t)(hb >> 16), (uint16_t)(mb >> 16), (uint16_t)(lb >> 16)};
-#pragma unroll
-    for (int pl = 0; pl < 3; ++pl) w3[(int64_t)slab * 9216 + ((st * 3 + pl) * 32 + n) * 24 + k] = planes[pl];      // byte offsets / 2 (18432-byte slabs, 48-byte rows)
-    w1[(int64_t)slab * 3072 + (st * 32 + n) * 24 + k] = (uint16_t)((xb + 0x7FFFu + ((xb >> 16) & 1u)) >> 16);
-}
-
-// ---- device-side re-merge of the two pre-multiplied step matrices (the host packer's fp64 products, here as fp32 MFMA products of the bound
-// parameters): prenet1 o fc_out -> w.pre1f, LSTM0 with attention_proj folded in -> w.lstm0f, both in the frag16 weight layout of the blob
-struct MergeSeg { const float* src; int ld, col0, k_lo, k_hi; };
-__global__ __launch_bounds__(256) void merge_pack_kernel(float* __restrict__ dst, int N, int K, MergeSeg s0, MergeSeg s1, MergeSeg s2, int perm_H) {
-    const int64_t total = (int64_t)N * K;
-    for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * 256) {
-        const int k = idx % K, np = idx / K;
-        const int r = perm_H ? (np & 3) * perm_H + (np >> 2) : np;
-        const MergeSeg* segs[3] = {&s0, &s1, &s2};
-        float v = 0.f;
-#pragma unroll
-        for (int q = 0; q < 3; ++q) {
-            const MergeSeg& g = *segs[q];
-            if (g.src && k >= g.k_lo && k < g.k_hi) v = g.src[(int64_t)r * g.ld + g.col0 + (k - g.k_lo)];
-        }
-        dst[frag16_index(np, k, K)] = v;
-    }
-}
-// out[np] = a[r] (+ b[r]) + sum_k W[r*ld + col0 + k] * x[k],  r = perm(np)
-__global__ __launch_bounds__(256) void merge_bias_kernel(float* __restrict__ out, int N, const float* __restrict__ a, const float* __restrict__ b,
-                                                         const float* __restrict__ W, int ld, int col0, int K, const float* __restrict__ x, int perm_H) {
-    const int np = blockIdx.x * 256 + threadIdx.x;
-    if (np >= N) return;
-    const int r = perm_H ? (np & 3) * perm_H + (np >> 2) : np;
-    double acc = (double)a[r] + (b ? (double)b[r] : 0.0);
-    for (int k = 0; k < K; ++k) acc += (double)W[(int64_t)r * ld + col0 + k] * (double)x[k];
-    out[np] = (float)acc;
-}
-static int remerge_step_weights(l2s_model* m, hipStream_t s) {
-    const std::string D = "decoder.";
-    auto P = [&](const char* k) { return m->canon(D + k); };
-    const float *wp1 = P("prenet.0.linear_layer.weight"), *bp1 = P("prenet.0.linear_layer.bias"), *wfc = P("fc_out.linear_layer.weight"), *bfc = P("fc_out.linear_layer.bias");
-    const float *wih = P("decoder_rnn.weight_ih_l0"), *whh = P("decoder_rnn.weight_hh_l0"), *bih = P("decoder_rnn.bias_ih_l0"), *bhh = P("decoder_rnn.bias_hh_l0");
-    const float *wap = P("attention_proj.linear_layer.weight"), *bap = P("attention_proj.linear_layer.bias");
-    if (!(wp1 && bp1 && wfc && bfc && wih && whh && bih && bhh && wap && bap) || !m->w.pre1f.W || !m->w.lstm0f.W) return 0;      // decoder not bound: stays invalid
-    if (!m->merge_scratch) L2S_CHECK_HIP(hipMalloc(&m->merge_scratch, sizeof(float) * ((int64_t)2048 * 512 + (int64_t)256 * 512)));
-    float* prod_ap = m->merge_scratch; float* prod_p1 = prod_ap + (int64_t)2048 * 512;
-    // (W_ih[:,256:512] @ W_ap) (2048 x 512) and (W_p1 @ W_out) (256 x 512): C = A . B with B row-major is the input-gradient form of the backward GEMM
-    if (launch_gemm_bwd(bwd_dx(wih + 256, 512, wap, prod_ap, 512, 1, 2048, 2048, 256, 512, 1, 0, false), s, "train_merge_step_weights")) return 1;
-    if (launch_gemm_bwd(bwd_dx(wp1, NM, wfc, prod_p1, 512, 1, 256, 256, NM, 512, 1, 0, false), s, "train_merge_step_weights")) return 1;
-    ProfScope ps("train_merge_step_weights", s);
-    const MergeSeg none{nullptr, 0, 0, 0, 0};
-    hipLaunchKernelGGL(merge_pack_kernel, dim3(4096), dim3(256), 0, s, const_cast<float*>(m->w.lstm0f.W), 2048, 1536, MergeSeg{wih, 512, 0, 0, 512},
-                       MergeSeg{prod_ap, 512, 0, 512, 1024}, MergeSeg{whh, 512, 0, 1024, 1536}, 512);
-    hipLaunchKernelGGL(merge_pack_kernel, dim3(512), dim3(256), 0, s, const_cast<float*>(m->w.pre1f.W), 256, 512, MergeSeg{prod_p1, 512, 0, 0, 512}, none, none, 0);
-    hipLaunchKernelGGL(merge_bias_kernel, dim3(8), dim3(256), 0, s, const_cast<float*>(m->w.lstm0f.bias), 2048, bih, bhh, wih, 512, 256, 256, bap, 512);
-    hipLaunchKernelGGL(merge_bias_kernel, dim3(1), dim3(256), 0, s, const_cast<float*>(m->w.pre1f.bias), 256, bp1, (const float*)nullptr, wp1, NM, 0, NM, bfc, 0);
-    L2S_CHECK_HIP(hipGetLastError());
-    m->folded_valid = true;
-    return 0;
-}
-
-static int refresh_weights(l2s_model* m, hipStream_t s) {
-    L2S_REQUIRE(m->finalized && m->r_key && m->r_idx, "no refresh map: set option refresh_map=1 before l2s_model_finalize");
-    const size_t nk = m->r_keys.size(), nb = m->r_bn.size(), ns = m->r_sum.size();
-    const size_t off_bn = align_up((int64_t)(nk * sizeof(float*)), 64), off_sum = off_bn + align_up((int64_t)(nb * sizeof(RBn)), 64);
-    const size_t total = off_sum + ns * sizeof(RSum) + 64;
-    m->r_tables_host.assign(total, 0);
-    const float** ptrs = reinterpret_cast<const float**>(m->r_tables_host.data());
-    for (size_t i = 0; i < nk; ++i) ptrs[i] = m->canon(m->r_keys[i]);
-    RBn* bn = reinterpret_cast<RBn*>(m->r_tables_host.data() + off_bn);
-    size_t nb_live = 0;
-    int maxc = 1;
-    for (const auto& r : m->r_bn) {
-        RBn d{m->canon(r.p + ".weight"), m->canon(r.p + ".bias"), m->canon(r.p + ".running_mean"), m->canon(r.p + ".running_var"),
-              r.bias_key.empty() ? nullptr : m->canon(r.bias_key), m->blob + r.so, m->blob + r.ho, r.c};
-        if (!d.g && !d.b && !d.mu && !d.var) continue;                   // a module that is not bound at all (e.g. frozen) keeps its packed values
-        L2S_REQUIRE(d.g && d.b && d.mu && d.var && (r.bias_key.empty() || d.bias), "refresh: BatchNorm tensors of a layer are only partly bound");
-        bn[nb_live++] = d; maxc = std::max(maxc, r.c);
-    }
-    RSum* sm = reinterpret_cast<RSum*>(m->r_tables_host.data() + off_sum);
-    size_t ns_live = 0;
-    int maxn = 1;
-    for (const auto& r : m->r_sum) {
-        RSum d{m->canon(r.a), m->canon(r.b), m->blob + r.dst, r.n, r.perm_H};
-        if (!d.a && !d.b) continue;
-        L2S_REQUIRE(d.a && d.b, "refresh: bias pair only partly bound");
-        sm[ns_live++] = d; maxn = std::max(maxn, r.n);
-    }
-    if ((int64_t)total > m->r_tables_bytes) {
-        if (m->r_tables) (void)hipFree(m->r_tables);
-        L2S_CHECK_HIP(hipMalloc(&m->r_tables, total));
-        m->r_tables_bytes = (int64_t)total;
-        m->r_tables_uploaded.clear();
-    }
-    // the tables only change when tensors are (re)bound: upload them then, not on every optimizer step (the upload comes from a pageable vector,
-    // so it ends in a stream synchronise - once per step that drained the pipeline between steps)
-    if (m->r_tables_host != m->r_tables_uploaded) {
-        L2S_CHECK_HIP(hipMemcpyAsync(m->r_tables, m->r_tables_host.data(), total, hipMemcpyHostToDevice, s));
-        L2S_CHECK_HIP(hipStreamSynchronize(s));                         // pageable staging buffer: the copy must have left the host vector
-        m->r_tables_uploaded = m->r_tables_host;
-    }
-    char* T = (char*)m->r_tables;
-    {
-        ProfScope ps("train_refresh_gather", s);
-        hipLaunchKernelGGL(refresh_gather_kernel, dim3(4096), dim3(256), 0, s, m->blob, m->r_key, m->r_idx, reinterpret_cast<const float* const*>(T), m->blob_floats);
-    }
-    if (nb_live) hipLaunchKernelGGL(refresh_bn_kernel, dim3((maxc + 255) / 256, (unsigned)nb_live), dim3(256), 0, s, reinterpret_cast<const RBn*>(T + off_bn));
-    if (ns_live) hipLaunchKernelGGL(refresh_sum_kernel, dim3((maxn + 255) / 256, (unsigned)ns_live), dim3(256), 0, s, reinterpret_cast<const RSum*>(T + off_sum));
-    L2S_CHECK_HIP(hipGetLastError());
-    // the front-end's bf16 operand planes are splits of the old weights: re-split them from the bound Conv3d weight (an encoder that is not
-    // bound keeps its packed planes, like every other unbound module)
-    if (const float* w3d = m->canon("encoder.frontend3D.0.weight"); w3d && m->w.fe.w3 && m->w.fe.w1) {
-        ProfScope ps("train_refresh_frontend_planes", s);
-        hipLaunchKernelGGL(refresh_frontend_planes_kernel, dim3(15 * 4 * 32 * 16 / 256), dim3(256), 0, s, w3d,
-                           reinterpret_cast<uint16_t*>(const_cast<float*>(m->w.fe.w3)), reinterpret_cast<uint16_t*>(const_cast<float*>(m->w.fe.w1)));
-        L2S_CHECK_HIP(hipGetLastError());
-    }
-    if (m->lstm_planes && derive_lstm_planes(m, s)) return 1;      // the LSTM weights' bf16 planes are splits of the old weights too
-    if (m->gemm_planes && derive_gemm_planes(m, s)) return 1;
-    if (m->unit_planes && derive_unit_planes(m, s)) return 1;
-    m->folded_valid = false;        // W_p1 W_out and W_ih W_ap are products of the old parameters ...
-    if (remerge_step_weights(m, s)) return 1;      // ... rebuilt here when the decoder's tensors are bound (then the 4-launch step stays valid)
-    for (auto& g : m->graphs) { (void)hipGraphExecDestroy(g.exec); (void)hipGraphDestroy(g.graph); }
-    m->graphs.clear();
-    return 0;
-}
-
 // ------------------------------------------------------------------------------------------------ workspace
 struct EncPlan {
     int NF, Hp;
@@ -1078,10 +187,10 @@ static int encoder_run(l2s_model* m, const FrameSrc& video, int B, int T, int H,
     float* a = bp.f(pl.act_a); float* b = bp.f(pl.act_b); float* t1 = bp.f(pl.t1); float* t2 = bp.f(pl.t2); float* last = bp.f(pl.last);
     L2S_REQUIRE(!bp.overflow, "encoder workspace too small");
     FrontendW fe = w.fe;
-    if (!m->opt.frontend_x3 || !m->planes_valid) fe.w3 = nullptr;        // after a device-side refresh the split planes are stale
+    if (!m->opt.frontend_x3) fe.w3 = nullptr;
     fe.pair = m->opt.frontend_x3 >= 2; fe.pipe = m->opt.frontend_x3 == 3;
     fe.solo = m->opt.frontend_solo && (m->opt.frontend_solo >= 2 || chains_hint() >= 2);
-    if (!m->opt.infer_bf16 || !m->planes_valid) fe.w1 = nullptr;
+    if (!m->opt.infer_bf16) fe.w1 = nullptr;
     if (launch_frontend(fe, video, B, T, H, W, a, s)) return 1;
     float* x = a; float* y = b;
     int h = pl.Hp;
@@ -1753,17 +862,10 @@ int l2s_model_finalize(l2s_model* m, void* stream) {
 }
 int l2s_model_destroy(l2s_model* m) {
     if (!m) return 0;
-    for (auto& g : m->graphs) { (void)hipGraphExecDestroy(g.exec); (void)hipGraphDestroy(g.graph); }
+    drop_graphs(m);
     if (m->side) { (void)hipStreamDestroy(m->side); (void)hipEventDestroy(m->ev_in); (void)hipEventDestroy(m->ev_out); }
     for (auto e : m->ev_pool) (void)hipEventDestroy(e);
-    if (m->blob) (void)hipFree(m->blob);
-    if (m->r_key) (void)hipFree(m->r_key);
-    if (m->r_idx) (void)hipFree(m->r_idx);
-    if (m->r_tables) (void)hipFree(m->r_tables);
-    if (m->merge_scratch) (void)hipFree(m->merge_scratch);
-    if (m->lstm_planes) (void)hipFree(m->lstm_planes);
-    if (m->gemm_planes) (void)hipFree(m->gemm_planes);
-    if (m->unit_planes) (void)hipFree(m->unit_planes);
+    free_model_device(m);
     delete m;
     return 0;
 }
@@ -2158,9 +1260,9 @@ int l2s_op_conv1d_bwd(const float* dZ, const float* X, const float* Wp, float* d
 int l2s_op_frontend(l2s_model* m, const float* video, int B, int T, int H, int W, float* out, void* stream) {
     L2S_ENC_READY(m);
     FrontendW fe = m->w.fe;
-    if (!m->opt.frontend_x3 || !m->planes_valid) fe.w3 = nullptr;
+    if (!m->opt.frontend_x3) fe.w3 = nullptr;
     fe.pair = m->opt.frontend_x3 >= 2; fe.pipe = m->opt.frontend_x3 == 3;
-    if (!m->opt.infer_bf16 || !m->planes_valid) fe.w1 = nullptr;
+    if (!m->opt.infer_bf16) fe.w1 = nullptr;
     return launch_frontend(fe, frame_src(video, B), B, T, H, W, out, (hipStream_t)stream);
 }
 int l2s_op_face_conv2d(const float* x, int64_t x_bstride, int B, int H, int W, int Cin, const float* w, const float* scale, const float* shift,

@@ -1,4 +1,4 @@
-// Model-side declarations shared by the HIP translation units that orchestrate launches (l2s_api.hip, train_decoder.hip).
+// Model-side declarations shared by the HIP translation units that build the model (l2s_pack.hip) and orchestrate launches (l2s_api.hip, train_decoder.hip).
 #pragma once
 #include "../../include/l2s.h"
 #include "l2s_common.h"
@@ -30,7 +30,7 @@ static inline int pad16(int b) { return (b + 15) & ~15; }
 
 // ------------------------------------------------------------------------------------------------ model
 struct ConvW { const float* W = nullptr; const float* scale = nullptr; const float* shift = nullptr; const float* actw = nullptr;
-               const void* W3 = nullptr; };      // W3: W as pre-split bf16 planes (GemmP::W3), derived on the device (derive_gemm_planes)
+               const void* W3 = nullptr; };      // W3: W as pre-split bf16 planes (GemmP::W3), derived on the device (derive_all_planes)
 struct DwW { const float* w9 = nullptr; const float* scale = nullptr; const float* shift = nullptr; };
 struct UnitW {
     bool stride2 = false;
@@ -130,7 +130,6 @@ struct l2s_model {
     void* r_tables = nullptr; int64_t r_tables_bytes = 0;     // device scratch for the pointer / descriptor tables
     std::vector<char> r_tables_host, r_tables_uploaded;       // what the next refresh needs / what the device table holds
     bool folded_valid = true;                                 // the phase-merged step weights match the current parameters
-    bool planes_valid = true;                                 // the front-end's bf16 operand planes (w3 / w1) match the current parameters
     float* merge_scratch = nullptr;                           // device: the two products of the device-side re-merge (l2s_train_refresh_weights)
     void* gemm_planes = nullptr;                              // device: bf16 planes of the post-net's Conv1d weights, the BiLSTM input matrix and conv_last (option "gemm_x3_dma"); rebuilt like lstm_planes
     void* unit_planes = nullptr;                              // device: bf16 operand planes of the fused ShuffleNet units' pointwise convs (option "trunk_x3"); rebuilt like lstm_planes
@@ -145,6 +144,11 @@ struct l2s_model {
 
 namespace l2s {
 constexpr int NM_ = L2S_N_MELS;
+// building the weight blob and keeping it current (l2s_pack.hip)
+int pack_model(l2s_model* m, hipStream_t stream);           // host pack of m->host, upload, derived planes; with option "refresh_map" the refresh map too
+int refresh_weights(l2s_model* m, hipStream_t s);           // device-side refresh of the blob from the bound tensors (training)
+void drop_graphs(l2s_model* m);                             // destroys the captured decode loops (their kernel arguments point into the blob and the derived pools)
+void free_model_device(l2s_model* m);                       // frees the blob, the refresh map and tables and every derived pool
 int face_conv_splits(int HoWo, int K, int* kchunk);
 int launch_face_conv(FaceConvP p, float* part, int64_t part_floats, hipStream_t s);
 int64_t face_ws_floats(int B);
