@@ -202,7 +202,8 @@ int l2s_inference(l2s_model* m, const float* video, const float* emb, const floa
  * same lengths.
  * Options: masked calls take the launch-per-phase route - "persist_decode" and "use_graph" do not apply to them - unless "persist_masked" is set
  * (below: free-running masked calls inside the persistent envelope then take the persistent forms); "early_stop", "fold_step_weights" and
- * "infer_bf16" compose.  There is no masked form of the grouped (*_multi) or training (l2s_train_*) entry points.
+ * "infer_bf16" compose.  The grouped (*_multi) entry points have no masked form: batches of unequal length share a launch chain through
+ * l2s_inference_ragged ("ragged groups" below); the training (l2s_train_*) entry points have none either.
  * Workspace: l2s_workspace_bytes_masked (the unmasked size plus the device length table), for all four calls.
  * l2s_masked_bilstm_plan: the launch plan of the BiLSTM recurrence, a pure host function.  The recurrence stays T uniform launches (step s reads frame
  * s forward and frame T-1-s backward); capture_steps = the steps AFTER which a row kernel hands over the forward finals of the clips that ended there
@@ -234,6 +235,35 @@ int l2s_inference_multi(l2s_model* m, int G, const float* const* video, const fl
                         int B, int T, int H, int W, int S,
                         float* mel_post, int64_t* lengths, float* attn,
                         void* ws, int64_t ws_bytes, void* stream);
+
+/* ---- ragged groups: batches of unequal length share one launch chain -------------------------------------------------------------------------------------
+ * G padded batches, each with its OWN B_g and T_g (a loader that pads every batch to its longest clip), run as rows of ONE launch chain, every clip
+ * decoded as it would be alone, the visual encoder on the real frames only.  Clip c = the c-th clip in batch order (N = sum B_g clips, Tmax = max T_g).
+ *   video[g] dev (B_g,3,T_g,H,W), 16-byte aligned, read in place; emb[g] dev (B_g,256); gumbel[g] dev (B_g * l2s_min_T(T_g), 501) - exactly what
+ *   l2s_inference_masked takes for that batch alone; batch_B / batch_T host (G); video_lengths host (N), may be freed when the call returns;
+ *   mel_post dev (N,80,S), lengths dev (N) int64, attn dev (N,S,Tmax) or NULL.
+ * Limits: 1 <= G <= L2S_MAX_GROUP, N <= L2S_MAX_RAGGED_CLIPS, 7 <= len_c <= T_g <= 300 (T_g may exceed its batch's longest clip).  A violation is an
+ * error that names the batch and the row (l2s_last_error), raised before anything is launched: the outputs of a failed call are untouched.
+ * Contract.  Row c of every output is what l2s_inference_masked gives for that clip - so what l2s_inference gives for the clip alone at T = len_c;
+ * attention columns t >= len_c are exactly 0.  The same bits wherever the kernel choice is the same, rounding-level inside the 1e-3
+ * gate elsewhere.  The choices that depend on the row count (the split-bf16 GEMM's tile threshold, the post-net's one-slice-per-tap form) are made on the
+ * rows of the WHOLE call, as for one masked call of N clips padded to Tmax: "rows of one batch", which the *_multi calls decide on, has no meaning in a
+ * ragged group.  Frames t >= len_c of a clip are NEVER READ - the front-end looks its clip up in a table and bounds its temporal taps by len_c - so the
+ * zero-padding contract of the *_masked entry points is not needed here: the pad frames may hold anything.
+ * Route and options: the launch-per-phase route, like every masked call and every grouped call - never a persistent form, whatever "persist_decode" /
+ * "persist_masked" say; "early_stop" and "fold_step_weights" compose; "use_graph" does not apply.  "infer_bf16" set, or "frontend_x3" other than 3, is an
+ * error that names the option: the ragged front-end exists in the default form only, and there is no padded copy of the frames to fall back on.
+ * l2s_ragged_plan (pure host): frame0[c] / pair0[c] = prefix sums of len_c and of ceil(len_c / 2) over the clips, N + 1 entries each - clip c owns the
+ * compact encoder frames frame0[c] .. frame0[c+1] - 1 and the front-end's pair blocks pair0[c] .. pair0[c+1] - 1 (two output frames per block).
+ * l2s_workspace_bytes_ragged: the worst case, every frame real; -1 (and l2s_last_error) for shapes outside the limits. */
+#define L2S_MAX_RAGGED_CLIPS 256          /* = L2S_MAX_GROUP x 32, the largest row count the grouped route is benchmarked at */
+int l2s_ragged_plan(int G, const int32_t* batch_B, const int32_t* batch_T, const int32_t* video_lengths,
+                    int32_t* frame0, int32_t* pair0, int* N, int* Tmax);
+int64_t l2s_workspace_bytes_ragged(int G, const int32_t* batch_B, const int32_t* batch_T, int H, int W, int S);
+int l2s_inference_ragged(l2s_model* m, int G, const float* const* video, const float* const* emb, const float* const* gumbel,
+                         const int32_t* batch_B, const int32_t* batch_T, const int32_t* video_lengths,
+                         int H, int W, int S, float* mel_post, int64_t* lengths,
+                         float* attn, void* ws, int64_t ws_bytes, void* stream);
 
 /* Lip2Speech.forward(..., tf_ratio) in eval() mode (model/model.py:23-40 + model/modules/decoder.py:320-379) - what evaluate.py:32-38 runs on
  * every batch at tf_ratio = 1 - as ONE launch chain: encoder, prologue, S = mels.shape[2] steps, post-net.

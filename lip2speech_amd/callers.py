@@ -14,7 +14,8 @@ third-party, stochastic and out of scope here - these f
 
 ``honour_lengths=True`` (off by default, as the reference ignores lengths): the loader's ``video_lengths`` are passed on to the length-masked entry
 points (``l2s_inference_masked`` / ``l2s_forward_eval_masked``), so a clip's output no longer depends on what it was padded to.  Those have no
-grouped form: the batches then run one call each, in loader order.
+grouped form: the batches then run one call each, in loader order - unless ``demo_clips`` is also given ``group_lengths=True``: batches of unequal
+length then share launch chains as ragged groups (``l2s_inference_ragged``, ``Lip2Speech.inference_many_lengths``).
 """
 from __future__ import annotations
 
@@ -57,13 +58,15 @@ def demo_clip(net, batch, speaker_encoder=None, speaker_embedding: Optional[torc
 
 def demo_clips(net, batches: Iterable, speaker_encoder=None, speaker_embedding: Optional[torch.Tensor] = None, device="cuda",
                group: int = 8, n_inflight: int = 3, encoding: str = "voice", early_stop: bool = False, honour_lengths: bool = False,
-               persist_frames: int = 0, persist_masked: int = 0):
+               persist_frames: int = 0, persist_masked: int = 0, group_lengths: bool = False):
     """demo.py:60-90 over a whole loader: per clip the speaker embedding from the VOICE tower (``--encoding voice``) or a supplied one,
     ``net.inference(..., return_attention_map=True)``, truncation to ``output_lengths[0]``.  The clips are advanced ``group`` per launch
     chain with ``n_inflight`` chains on the GPU (``Lip2Speech.inference_many``); yields ``(mel, lengths, attention)`` per clip, in order.
     ``encoding="face"``: the embedding comes from the model's face tower instead.  ``early_stop``: every group's decode loop ends once all of
     its clips have stopped (model option "early_stop", set once on ``net`` before the chains start); the yielded tensors are the same.
     ``honour_lengths``: every batch goes through ``demo_clip`` with its ``video_lengths`` (the masked entry point has no grouped form).
+    ``group_lengths`` (with ``honour_lengths``; off by default): the batches - whatever their B and T - run ``group`` per launch chain as ragged
+    groups instead (``Lip2Speech.inference_many_lengths``, ``l2s_inference_ragged``): the same clips out, each as it would come out alone.
     ``persist_frames``: as in ``demo_clip``, set once on ``net`` before the first clip (grouped calls themselves never take the persistent
     forms; the option is the model's and holds for its later single-batch calls).
     ``persist_masked``: as in ``demo_clip``, set once on ``net`` before the first clip: with ``honour_lengths`` every batch still goes through
@@ -73,9 +76,22 @@ def demo_clips(net, batches: Iterable, speaker_encoder=None, speaker_embedding: 
     _set_persist_masked(net, persist_masked)
     if encoding == "voice" and speaker_embedding is None and speaker_encoder is None:
         raise ValueError("pass a SpeakerEncoder (voice route) or a speaker_embedding")
-    if honour_lengths:
+    if group_lengths and not honour_lengths:
+        raise ValueError("group_lengths groups the length-honouring calls: pass honour_lengths=True as well")
+    if honour_lengths and not group_lengths:
         for batch in batches:
             yield demo_clip(net, batch, speaker_encoder, speaker_embedding, device, encoding, early_stop, honour_lengths=True)
+        return
+    if honour_lengths:
+        def ragged_calls():
+            for (videos, vlen), (audios, _), _, face_crops, _ in batches:
+                with torch.no_grad():
+                    emb = _voice_embedding(encoding, speaker_encoder, speaker_embedding, audios, device)
+                yield videos, face_crops, emb, True, {"video_lengths": vlen}
+
+        for mel, lengths, attn in net.inference_many_lengths(ragged_calls(), group=group, n_inflight=n_inflight, early_stop=bool(early_stop)):
+            n = int(lengths[0])
+            yield mel[:1, :, :n], lengths, attn[:, :n]
         return
 
     def calls():

@@ -87,6 +87,17 @@ void prof_end(hipStream_t s) {
     g_prof[g_prof_cur].launches++;
     g_prof_cur = -1;
 }
+void prof_count(const char* name, int64_t n) {      // a counter among the entries (e.g. the pair blocks of the ragged front-end's grid): no events, no time
+    if (!g_prof_on) return;
+    std::lock_guard<std::mutex> lk(g_prof_mu);
+    auto it = g_prof_idx.find(name);
+    if (it == g_prof_idx.end()) {
+        g_prof_idx[name] = (int)g_prof.size();
+        g_prof.push_back(ProfEntry{name});
+        it = g_prof_idx.find(name);
+    }
+    g_prof[it->second].launches += n;
+}
 static void prof_drain() {
     std::lock_guard<std::mutex> lk(g_prof_mu);
     for (auto& e : g_prof) {
@@ -110,9 +121,9 @@ struct EncPlan {
     int NF, Hp;
     int64_t act_a, act_b, t1, t2, last;
 };
-static EncPlan enc_plan(int B, int T, int H) {
+static EncPlan enc_plan(int NF, int H) {      // NF frames: B * T of a padded call, sum len of a ragged one
     EncPlan p{};
-    p.NF = B * T;
+    p.NF = NF;
     p.Hp = H / 4;
     int64_t hw = (int64_t)p.Hp * p.Hp;
     int64_t amax = (int64_t)p.NF * hw * STAGE_CH[0], t1 = 0, t2 = 0;
@@ -132,8 +143,8 @@ static EncPlan enc_plan(int B, int T, int H) {
     p.last = (int64_t)p.NF * h * h * LAST_CH;
     return p;
 }
-static int64_t enc_ws_floats(int B, int T, int H) {
-    EncPlan p = enc_plan(B, T, H);
+static int64_t enc_ws_floats(int NF, int H) {
+    EncPlan p = enc_plan(NF, H);
     return p.act_a + p.act_b + p.t1 + p.t2 + p.last + 64 * 8;
 }
 
@@ -177,12 +188,14 @@ static GemmP pw_gemm(const float* A, int lda, int a_off, const ConvW& c, float* 
 
 static FrameSrc frame_src(const float* video, int B) { FrameSrc f{}; f.p[0] = video; f.per = B; return f; }
 
+// rg (a ragged group, l2s_inference_ragged): the front-end and the trunk run on the rg->NF real frames of the group's clips, compact; vis comes out as
+// (rg->N, rg->Tmax, 1024) with zero rows past each clip's length.  B, T are then rg->N, rg->Tmax.
 static int encoder_run(l2s_model* m, const FrameSrc& video, int B, int T, int H, int W, const float* emb, float* vis,
-                       float* feat, void* ws, int64_t ws_bytes, hipStream_t s) {
+                       float* feat, void* ws, int64_t ws_bytes, hipStream_t s, const RaggedTab* rg = nullptr) {
     X3Scope x3scope(m->opt.infer_bf16 ? 0 : m->opt.gemm_x3);
     Bf16Scope bf16scope(m->opt.infer_bf16);      // the bf16 leg: bf16-operand GEMM / Conv1d kernels instead of the f32 / split-bf16 ones
     const Weights& w = m->w;
-    EncPlan pl = enc_plan(B, T, H);
+    EncPlan pl = enc_plan(rg ? rg->NF : B * T, H);
     Bump bp(ws, ws_bytes);
     float* a = bp.f(pl.act_a); float* b = bp.f(pl.act_b); float* t1 = bp.f(pl.t1); float* t2 = bp.f(pl.t2); float* last = bp.f(pl.last);
     L2S_REQUIRE(!bp.overflow, "encoder workspace too small");
@@ -191,7 +204,7 @@ static int encoder_run(l2s_model* m, const FrameSrc& video, int B, int T, int H,
     fe.pair = m->opt.frontend_x3 >= 2; fe.pipe = m->opt.frontend_x3 == 3;
     fe.solo = m->opt.frontend_solo && (m->opt.frontend_solo >= 2 || chains_hint() >= 2);
     if (!m->opt.infer_bf16) fe.w1 = nullptr;
-    if (launch_frontend(fe, video, B, T, H, W, a, s)) return 1;
+    if (rg ? launch_frontend_ragged(fe, video, *rg, H, W, a, s) : launch_frontend(fe, video, B, T, H, W, a, s)) return 1;
     float* x = a; float* y = b;
     int h = pl.Hp;
     const int NF = pl.NF;
@@ -261,6 +274,7 @@ static int encoder_run(l2s_model* m, const FrameSrc& video, int B, int T, int H,
         if (!m->opt.gemm_x3_dma) pc.W3 = nullptr;
         if (launch_gemm1(pc, s, "conv_last_gemm")) return 1;
     }
+    if (rg) return launch_pool_norm_cat_ragged(last, *rg, h * h, LAST_CH, emb, L2S_D_EMB, vis, L2S_D_VIS, s);
     if (launch_pool_norm_cat(last, NF, h * h, LAST_CH, emb, L2S_D_EMB, T, vis, L2S_D_VIS, feat, s)) return 1;
     return 0;
 }
@@ -872,12 +886,16 @@ int l2s_model_destroy(l2s_model* m) {
 
 int l2s_min_T(int T) { int L[4]; return content_lens(T, L); }
 
-int64_t l2s_workspace_bytes(int B, int T, int H, int W, int S) {
-    (void)W;
-    int64_t enc = enc_ws_floats(B, T, H), pro = prologue_ws_floats(B, T), dec = decode_ws_floats(B), post = postnet_ws_floats(B, S);
+// one pass over B rows padded to T whose encoder works on enc_frames frames (B * T, or the frames of a ragged group)
+static int64_t path_ws_bytes(int enc_frames, int B, int T, int H, int S) {
+    int64_t enc = enc_ws_floats(enc_frames, H), pro = prologue_ws_floats(B, T), dec = decode_ws_floats(B), post = postnet_ws_floats(B, S);
     int64_t io = (int64_t)B * T * 1024 + l2s_state_floats(B, T) + (int64_t)B * S * (NM + 1) + 64 * 8;   // l2s_inference intermediates
     int64_t mx = std::max(std::max(enc, pro), dec + post + 64);      // decode and post-net buffers are live together (overlap)
     return (mx + io) * (int64_t)sizeof(float) + (1 << 16);
+}
+int64_t l2s_workspace_bytes(int B, int T, int H, int W, int S) {
+    (void)W;
+    return path_ws_bytes(B * T, B, T, H, S);
 }
 int64_t l2s_state_floats(int B, int T) { return state_layout(B, T).total; }
 int64_t l2s_state_offset(int B, int T, int field) {
@@ -999,7 +1017,7 @@ struct PathOut {
 
 static int path_run(l2s_model* m, const FrameSrc& video, const float* emb, const float* gumbel, int B, int T, int H, int W, int S,
                     const float* teacher, const uint8_t* teacher_mask, const PathOut& o, void* ws, int64_t ws_bytes, hipStream_t s,
-                    const int32_t* video_lengths = nullptr) {
+                    const int32_t* video_lengths = nullptr, const RaggedTab* rg = nullptr) {      // rg: the encoder stage of a ragged group (encoder_run)
     X3Scope x3scope(m->opt.infer_bf16 ? 0 : m->opt.gemm_x3);
     Bf16Scope bf16scope(m->opt.infer_bf16);      // the bf16 leg: bf16-operand GEMM / Conv1d kernels instead of the f32 / split-bf16 ones
     Bump bp(ws, ws_bytes);
@@ -1012,7 +1030,7 @@ static int path_run(l2s_model* m, const FrameSrc& video, const float* emb, const
     void* rest = (char*)ws + bp.off;
     const int64_t rest_bytes = ws_bytes - bp.off;
     if (lens && launch_len_table(video_lengths, B, lens.dev, s)) return 1;
-    if (encoder_run(m, video, B, T, H, W, emb, vis, nullptr, rest, rest_bytes, s)) return 1;
+    if (encoder_run(m, video, B, T, H, W, emb, vis, nullptr, rest, rest_bytes, s, rg)) return 1;
     if (prologue_run(m, vis, emb, gumbel, B, T, state, o.content_dis, rest, rest_bytes, s, lens, !teacher)) return 1;
     const bool early = m->opt.early_stop != 0 && !teacher && o.lengths;      // l2s_inference(_multi); l2s_forward_eval's S comes from the target
     const bool plain = !m->opt.overlap_postnet || g_prof_on || m->opt.graph || teacher || o.mel_cf || early || lens;      // "early_stop" and lengths take the plain route
@@ -1196,6 +1214,113 @@ int l2s_forward_eval_multi(l2s_model* m, int G, const float* const* video, const
     PathOut o;
     o.mel_post = mel_post; o.mel_cf = mel_cf; o.stop = stop; o.attn = attn_logits; o.attn_logits = 1; o.content_dis = content_dis;
     return path_run(m, src, emb_all, gum_all, G * B, T, H, W, S, teach_all, teacher_mask, o, (char*)ws + bp.off, ws_bytes - bp.off, s);
+}
+
+// ---- ragged groups: G padded batches, each with its own B_g and T_g, as rows of ONE launch chain; every clip decoded as it would be alone, the encoder
+// on the real frames only (include/l2s.h).  The decoder stages are those of ONE masked call of N = sum B_g clips padded to Tmax = max T_g.
+static int ragged_plan(int G, const int32_t* batch_B, const int32_t* batch_T, const int32_t* video_lengths, std::vector<RaggedClip>& clips, RaggedTab& rg) {
+    L2S_REQUIRE(batch_B && batch_T, "l2s ragged: batch_B / batch_T is null");
+    if (G < 1 || G > L2S_MAX_GROUP) { set_error("l2s ragged: G = " + std::to_string(G) + " is outside [1, L2S_MAX_GROUP = " + std::to_string(L2S_MAX_GROUP) + "]"); return 1; }
+    int64_t N = 0;
+    int Tmax = 0;
+    for (int g = 0; g < G; ++g) {
+        if (batch_B[g] < 1) { set_error("l2s ragged: batch " + std::to_string(g) + " has B = " + std::to_string(batch_B[g]) + " clips"); return 1; }
+        if (batch_T[g] < 7 || batch_T[g] > L2S_MAX_STEPS) {
+            set_error("l2s ragged: batch " + std::to_string(g) + " has T = " + std::to_string(batch_T[g]) + ", outside [7, " + std::to_string(L2S_MAX_STEPS) + "]");
+            return 1;
+        }
+        N += batch_B[g];
+        Tmax = std::max(Tmax, (int)batch_T[g]);
+    }
+    if (N > L2S_MAX_RAGGED_CLIPS) { set_error("l2s ragged: N = " + std::to_string(N) + " clips exceed L2S_MAX_RAGGED_CLIPS = " + std::to_string(L2S_MAX_RAGGED_CLIPS)); return 1; }
+    clips.clear();
+    rg = RaggedTab{};
+    rg.N = (int)N; rg.Tmax = Tmax;
+    if (!video_lengths) return 0;      // the workspace query: shapes only
+    for (int g = 0; g < G; ++g)
+        for (int r = 0; r < batch_B[g]; ++r) {
+            const int c = (int)clips.size(), len = video_lengths[c];
+            if (len < 7 || len > batch_T[g]) {
+                set_error("l2s ragged: video_lengths[" + std::to_string(c) + "] = " + std::to_string(len) + " (batch " + std::to_string(g) + ", row " + std::to_string(r) +
+                          ") is outside [7, T = " + std::to_string(batch_T[g]) + "]");
+                return 1;
+            }
+            clips.push_back(RaggedClip{g, r, batch_T[g], len, rg.NF, rg.NP});
+            rg.NF += len; rg.NP += (len + 1) / 2;
+        }
+    return 0;
+}
+
+int l2s_ragged_plan(int G, const int32_t* batch_B, const int32_t* batch_T, const int32_t* video_lengths, int32_t* frame0, int32_t* pair0, int* N, int* Tmax) {
+    L2S_REQUIRE(video_lengths && frame0 && pair0 && N && Tmax, "bad arguments");
+    std::vector<RaggedClip> clips;
+    RaggedTab rg;
+    if (ragged_plan(G, batch_B, batch_T, video_lengths, clips, rg)) return 1;
+    for (int c = 0; c < rg.N; ++c) { frame0[c] = clips[c].frame0; pair0[c] = clips[c].pair0; }
+    frame0[rg.N] = rg.NF; pair0[rg.N] = rg.NP;
+    *N = rg.N; *Tmax = rg.Tmax;
+    return 0;
+}
+
+int64_t l2s_workspace_bytes_ragged(int G, const int32_t* batch_B, const int32_t* batch_T, int H, int W, int S) {
+    (void)W;
+    std::vector<RaggedClip> clips;
+    RaggedTab rg;
+    if (ragged_plan(G, batch_B, batch_T, nullptr, clips, rg)) return -1;
+    int64_t frames = 0, pairs = 0;      // the worst case: every frame real
+    for (int g = 0; g < G; ++g) { frames += (int64_t)batch_B[g] * batch_T[g]; pairs += (int64_t)batch_B[g] * ((batch_T[g] + 1) / 2); }
+    int L[4];
+    return path_ws_bytes((int)frames, rg.N, rg.Tmax, H, S) + len_table_bytes(rg.N) + 256 + align_up((int64_t)rg.N * L2S_D_EMB * 4, 256) +
+           align_up((int64_t)rg.N * content_lens(rg.Tmax, L) * VOC * 4, 256) + align_up((int64_t)rg.N * (int64_t)sizeof(RaggedClip), 256) + align_up(pairs * 4, 256);
+}
+
+int l2s_inference_ragged(l2s_model* m, int G, const float* const* video, const float* const* emb, const float* const* gumbel, const int32_t* batch_B,
+                         const int32_t* batch_T, const int32_t* video_lengths, int H, int W, int S, float* mel_post, int64_t* lengths, float* attn, void* ws,
+                         int64_t ws_bytes, void* stream) {
+    L2S_ENC_READY(m);
+    L2S_DEC_READY(m);
+    L2S_REQUIRE(video && emb && gumbel && video_lengths && mel_post && lengths && ws, "bad arguments");
+    // everything that can be refused is refused here, before the first launch: the outputs of a failed call are untouched
+    std::vector<RaggedClip> clips;
+    RaggedTab rg;
+    if (ragged_plan(G, batch_B, batch_T, video_lengths, clips, rg)) return 1;
+    L2S_REQUIRE(!m->opt.infer_bf16, "l2s_inference_ragged: option \"infer_bf16\" is set - the ragged front-end exists in the default form only");
+    L2S_REQUIRE(m->opt.frontend_x3 == 3, "l2s_inference_ragged: option \"frontend_x3\" is not 3 - the ragged front-end exists in the default form only");
+    L2S_REQUIRE(!m->opt.frontend_solo, "l2s_inference_ragged: option \"frontend_solo\" is set - the ragged front-end exists in the default form only");
+    L2S_REQUIRE(H == W && (H == 96 || H == 88), "frontend supports 96x96 and 88x88 mouth crops");
+    L2S_REQUIRE(S >= 1 && S <= L2S_MAX_STEPS, "S must be in [1, 300] (positional table)");
+    FrameSrc src{};
+    for (int g = 0; g < G; ++g) {
+        if (!video[g] || !emb[g] || !gumbel[g] || (reinterpret_cast<uintptr_t>(video[g]) & 15u)) {
+            set_error("l2s_inference_ragged: batch " + std::to_string(g) + ": null pointer, or video not 16-byte aligned");
+            return 1;
+        }
+        src.p[g] = video[g];
+    }
+    hipStream_t s = (hipStream_t)stream;
+    int L[4];
+    const int mT = content_lens(rg.Tmax, L), N = rg.N;
+    Bump bp(ws, ws_bytes);
+    float* emb_all = bp.f((int64_t)N * L2S_D_EMB);
+    float* gum_all = bp.f((int64_t)N * mT * VOC);
+    RaggedClip* clips_dev = reinterpret_cast<RaggedClip*>(bp.f((int64_t)N * (int64_t)(sizeof(RaggedClip) / sizeof(float))));
+    int* pair_clip = reinterpret_cast<int*>(bp.f(rg.NP));
+    L2S_REQUIRE(!bp.overflow, "workspace too small (l2s_workspace_bytes_ragged)");
+    // the small per-batch operands are gathered, the frames are read in place.  Clip c owns mT Gumbel rows of the group's buffer and uses the first
+    // min_T(len) of them (a masked call's rule); its batch supplied min_T(T_g) <= mT rows per clip: one strided copy per batch, the rest zeros
+    L2S_CHECK_HIP(hipMemsetAsync(gum_all, 0, sizeof(float) * (size_t)N * mT * VOC, s));
+    for (int g = 0, c0 = 0; g < G; c0 += batch_B[g], ++g) {
+        const size_t rowb = sizeof(float) * (size_t)content_lens(batch_T[g], L) * VOC;
+        L2S_CHECK_HIP(hipMemcpyAsync(emb_all + (int64_t)c0 * L2S_D_EMB, emb[g], sizeof(float) * batch_B[g] * L2S_D_EMB, hipMemcpyDeviceToDevice, s));
+        L2S_CHECK_HIP(hipMemcpy2DAsync(gum_all + (int64_t)c0 * mT * VOC, sizeof(float) * (size_t)mT * VOC, gumbel[g], rowb, rowb, batch_B[g], hipMemcpyDeviceToDevice, s));
+    }
+    if (launch_ragged_table(clips.data(), N, clips_dev, pair_clip, s)) return 1;
+    rg.clips = clips_dev; rg.pair_clip = pair_clip;
+    // the row-count-dependent kernel choices are made on the whole call's rows, as for one masked call of N clips: "rows of one batch" has no meaning here
+    X3Group x3group(1);
+    PathOut o;
+    o.mel_post = mel_post; o.lengths = lengths; o.attn = attn;
+    return path_run(m, src, emb_all, gum_all, N, rg.Tmax, H, W, S, nullptr, nullptr, o, (char*)ws + bp.off, ws_bytes - bp.off, s, video_lengths, &rg);
 }
 
 // ---- operator-level entry points

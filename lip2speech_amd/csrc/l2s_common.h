@@ -32,6 +32,7 @@ void set_error(const std::string& msg);
 // ---------------------------------------------------------------- optional per-kernel event timing
 void prof_begin(const char* name, hipStream_t s);
 void prof_end(hipStream_t s);
+void prof_count(const char* name, int64_t n);      // a counter among the profile entries: adds n to its `launches` (no time); nothing when profiling is off
 struct ProfScope {
     hipStream_t s;
     ProfScope(const char* name, hipStream_t st) : s(st) { prof_begin(name, st); }
@@ -276,6 +277,17 @@ inline int launch_frontend(const FrontendW& w, const float* video, int B, int T,
     FrameSrc f{}; f.p[0] = video; f.per = B;
     return launch_frontend(w, f, B, T, H, W, out, s, zout);
 }
+// ---- ragged groups (l2s_inference_ragged): the clips of up to MAX_GROUP padded batches, each with its own B_g and T_g, as rows of ONE launch chain; the
+// encoder works on the real frames only.  Clip c (batch order) owns the compact frames frame0 .. frame0 + len - 1 and the front-end pair blocks
+// pair0 .. pair0 + ceil(len / 2) - 1.  The device table is written from kernel arguments (launch_ragged_table), like the length table of the masked calls.
+struct RaggedClip { int g, row, T, len, frame0, pair0; };      // source tensor, row in it, ITS frame pitch T_g, frames of the clip, first compact frame, first pair block
+constexpr int RAGGED_CHUNK = 32;                               // clips per table-writing launch
+struct RaggedChunk { RaggedClip c[RAGGED_CHUNK]; int n; };
+struct RaggedTab { const RaggedClip* clips; const int* pair_clip; int N, Tmax, NF, NP; };      // device table and pair map; clips, row pitch of the decoder, sum len, sum ceil(len / 2)
+int launch_ragged_table(const RaggedClip* clips_host, int N, RaggedClip* clips_dev, int* pair_clip_dev, hipStream_t s);      // masked_kernels.hip
+// the ragged form of the default front-end (frontend3d_x3q_kernel): blockIdx.y = pair block; clip c's block j is block (0, 2j) of the clip alone at T = len
+// (same slabs, same order: same bits), read in place at pitch T_g, written to compact frames frame0 + 2j (+1).  Frames t >= len are never read.
+int launch_frontend_ragged(const FrontendW& w, const FrameSrc& video, const RaggedTab& rg, int H, int W, float* out, hipStream_t s);
 // batch-statistics pass of the front-end conv (training): partials[(block*2 + k)*24 + ch], *nblocks blocks
 int launch_frontend_stats(const FrontendW& w, const float* video, int B, int T, int H, int W, float* partials /*[blocks][2][24]*/, int* nblocks, hipStream_t s, float* raw_out = nullptr);
 // raw_out (NF,H/2,W/2,24): the statistics pass also parks the raw conv map; launch_bn_apply on it + launch_frontend_pool then replace the second conv pass
@@ -323,6 +335,8 @@ int launch_copy_cols(const float* in, int ldi, int off_i, float* out, int ldo, i
 // x (NF, P, C) -> mean over P -> L2 normalise over C -> vis[f*ldv + c]; emb (B,E) tiled into vis[f*ldv + C + e]
 int launch_pool_norm_cat(const float* x, int NF, int P, int C, const float* emb, int E, int T,
                          float* vis, int ldv, float* feat /*optional (NF,C)*/, hipStream_t s);
+// the ragged form: one block per (clip c, t) of the N x Tmax grid; t < len: compact frame frame0 + t (same sums, same order) + emb[c] -> vis row c*Tmax + t, else a zero row
+int launch_pool_norm_cat_ragged(const float* x, const RaggedTab& rg, int P, int C, const float* emb, int E, float* vis, int ldv, hipStream_t s);
 
 // ---------------------------------------------------------------- skinny (batch-row) MFMA kernels (skinny.hip)
 // "frag16" layout of a row-major X[R][K] (R padded to 16, K multiple of 16):

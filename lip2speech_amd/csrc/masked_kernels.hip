@@ -26,6 +26,30 @@ int launch_len_table(const int32_t* lens_host, int B, int* table, hipStream_t s)
     return 0;
 }
 
+// ---- the clip table of a ragged group (l2s_inference_ragged), carried the same way, and the pair map of its front-end: pair_clip[pair0[c] + j] = c
+__global__ __launch_bounds__(64) void ragged_table_kernel(const RaggedChunk c, RaggedClip* __restrict__ clips, int base) {
+    const int i = threadIdx.x;
+    if (i < c.n) clips[base + i] = c.c[i];
+}
+
+__global__ __launch_bounds__(64) void ragged_pair_map_kernel(const RaggedClip* __restrict__ clips, int* __restrict__ pair_clip) {
+    const int c = blockIdx.x;
+    const RaggedClip k = clips[c];
+    for (int j = threadIdx.x; j < (k.len + 1) / 2; j += 64) pair_clip[k.pair0 + j] = c;
+}
+
+int launch_ragged_table(const RaggedClip* clips_host, int N, RaggedClip* clips_dev, int* pair_clip_dev, hipStream_t s) {
+    for (int base = 0; base < N; base += RAGGED_CHUNK) {
+        RaggedChunk c{};
+        c.n = std::min(RAGGED_CHUNK, N - base);
+        for (int i = 0; i < c.n; ++i) c.c[i] = clips_host[base + i];
+        hipLaunchKernelGGL(ragged_table_kernel, dim3(1), dim3(64), 0, s, c, clips_dev, base);
+    }
+    hipLaunchKernelGGL(ragged_pair_map_kernel, dim3(N), dim3(64), 0, s, clips_dev, pair_clip_dev);
+    L2S_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
 // ---- BiLSTM, forward direction: the rows whose clip ends at frame t (len_b - 1 == t) hand over their finals - h (frag16) into the decoder's
 // initial hidden state, c (plain) into the E_C input - right after the step that computed them.  One block per batch row.
 __global__ __launch_bounds__(256) void bilstm_capture_kernel(const float* __restrict__ h_frag, const float* __restrict__ c_frag, const int* __restrict__ lens,

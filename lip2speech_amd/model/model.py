@@ -209,7 +209,11 @@ class Lip2Speech(NativeBacked):
         job["finish"] = lambda o: [o[0], o[1], o[2].unsqueeze(2), emb, o[3], o[4], video_lengths]
         return job
 
-    def _inference_job(self, video_frames, face_frames, speaker_embedding=None, return_attention_map=False, gumbel_noise=None):
+    def _inference_job(self, video_frames, face_frames, speaker_embedding=None, return_attention_map=False, gumbel_noise=None, video_lengths=None):
+        """`video_lengths` given: a job of the ragged route (`l2s_inference_ragged`), validated here - before the batch is staged on the device."""
+        lens = None
+        if video_lengths is not None:
+            lens = list(native.video_lengths_array(video_lengths, video_frames.shape[0], video_frames.shape[2]))
         dev = self.decoder.BOS.device
         with torch.no_grad():
             video = video_frames.to(dev, non_blocking=True)
@@ -218,9 +222,12 @@ class Lip2Speech(NativeBacked):
             B, _, T, _, _ = video.shape
             if gumbel_noise is None:
                 gumbel_noise = Decoder.draw_gumbel(B * native.min_T(T), dev)
-        return {"entry": "inference", "video": video, "emb": emb, "gumbel": gumbel_noise.to(dev, non_blocking=True),
-                "S": self.decoder.hparams.max_decoder_steps, "want_attn": bool(return_attention_map),
-                "finish": (lambda o: (o[0], o[1], o[2])) if return_attention_map else (lambda o: (o[0], o[1]))}
+        job = {"entry": "inference", "video": video, "emb": emb, "gumbel": gumbel_noise.to(dev, non_blocking=True),
+               "S": self.decoder.hparams.max_decoder_steps, "want_attn": bool(return_attention_map),
+               "finish": (lambda o: (o[0], o[1], o[2])) if return_attention_map else (lambda o: (o[0], o[1]))}
+        if lens is not None:
+            job["entry"], job["video_lengths"] = "inference_ragged", lens
+        return job
 
     # ------------------------------------------------------------------ loader-driven callers: G batches per launch chain, chains in flight
     def pool(self, group: int = 8, n_inflight: int = 3):
@@ -263,6 +270,23 @@ class Lip2Speech(NativeBacked):
         self.native_model()
         self.set_early_stop(early_stop)
         prep = lambda item: (lambda a, k: self._inference_job(*a, **k))(*self._call(item))      # noqa: E731
+        return self.pool(group, n_inflight).imap(calls, prep)
+
+    def inference_many_lengths(self, calls, group: int = 8, n_inflight: int = 3, early_stop: Optional[bool] = None):
+        """`inference(..., video_lengths=)` over a stream of batches whose B and T differ - a loader that pads every batch to its own longest clip
+        (GRID, AVSpeech, in-the-wild clips) - with `group` batches, at most 256 clips, advanced per launch chain as a ragged group
+        (`l2s_inference_ragged`) and `n_inflight` chains on the GPU at once.  `calls`: as for `inference_many`, every item with `video_lengths=` in its
+        trailing dict (required: without lengths the batches could not share a chain).  Yields, in order, what `inference(*call)` returns for each:
+        every clip as it would come out alone, the encoder run on the real frames only.  `early_stop`: as in `inference_many`."""
+        self.native_model()
+        self.set_early_stop(early_stop)
+
+        def prep(item):
+            a, k = self._call(item)
+            if k.get("video_lengths") is None:
+                raise ValueError("inference_many_lengths: every call needs video_lengths= (use inference_many for batches whose lengths are ignored)")
+            k = {key: v for key, v in k.items() if key != "early_stop"}
+            return self._inference_job(*a, **k)
         return self.pool(group, n_inflight).imap(calls, prep)
 
     def forward_many(self, calls, group: int = 8, n_inflight: int = 3):

@@ -31,6 +31,7 @@ ABI_SYMBOLS = (
     "l2s_min_T", "l2s_workspace_bytes", "l2s_state_floats", "l2s_state_offset",
     "l2s_encoder_fwd", "l2s_normalise_pad_frames", "l2s_build_visual", "l2s_decoder_prologue", "l2s_decode_steps", "l2s_postnet",
     "l2s_workspace_bytes_masked", "l2s_masked_bilstm_plan", "l2s_inference_masked", "l2s_forward_eval_masked", "l2s_decoder_prologue_masked", "l2s_decode_steps_masked",
+    "l2s_ragged_plan", "l2s_workspace_bytes_ragged", "l2s_inference_ragged",
     "l2s_output_lengths", "l2s_inference", "l2s_inference_multi", "l2s_workspace_bytes_multi", "l2s_forward_eval", "l2s_forward_eval_multi", "l2s_model_set_option", "l2s_persist_available", "l2s_persist_timeouts", "l2s_set_thread_chains", "l2s_speaker_workspace_bytes", "l2s_speaker_encoder_fwd",
     "l2s_face_workspace_bytes", "l2s_face_encoder_fwd",
     "l2s_inverse_mel_workspace_bytes", "l2s_inverse_mel", "l2s_griffin_lim_workspace_bytes", "l2s_griffin_lim", "l2s_estoi_workspace_bytes", "l2s_estoi",
@@ -186,6 +187,14 @@ def _bind(L: ctypes.CDLL) -> None:
         L.l2s_forward_eval_masked.argtypes = L.l2s_forward_eval.argtypes + [_lens]
         L.l2s_decoder_prologue_masked.argtypes = L.l2s_decoder_prologue.argtypes + [_lens]
         L.l2s_decode_steps_masked.argtypes = L.l2s_decode_steps.argtypes + [_lens]
+    # ragged groups (include/l2s.h): likewise absent from a library built before them (tools/ragged/time_ragged.py times one next to this build)
+    if hasattr(L, "l2s_inference_ragged"):
+        _lens = ctypes.POINTER(ctypes.c_int32)
+        L.l2s_ragged_plan.argtypes = [_i, _lens, _lens, _lens, _lens, _lens, ctypes.POINTER(_i), ctypes.POINTER(_i)]
+        L.l2s_workspace_bytes_ragged.argtypes = [_i, _lens, _lens, _i, _i, _i]
+        L.l2s_workspace_bytes_ragged.restype = _i64
+        L.l2s_inference_ragged.argtypes = [_vp, _i, ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp), _lens, _lens, _lens, _i, _i, _i, _fp, _vp, _fp,
+                                           _vp, _i64, _vp]
 
 
 def _bind_diag(L: ctypes.CDLL) -> None:
@@ -270,6 +279,36 @@ def masked_bilstm_plan(video_lengths, T: int):
     return list(cap[:nc.value]), list(rst[:nr.value])
 
 
+def workspace_bytes_ragged(batch_B, batch_T, H: int = 96, W: int = 96, S: int = 300) -> int:
+    """`l2s_workspace_bytes_ragged`: the workspace of a ragged group of these batch shapes, every frame real."""
+    G, i32 = len(batch_B), ctypes.c_int32
+    need = int(lib().l2s_workspace_bytes_ragged(G, (i32 * G)(*[int(b) for b in batch_B]), (i32 * G)(*[int(t) for t in batch_T]), H, W, S))
+    if need < 0:
+        check(1)
+    return need
+
+
+MAX_GROUP = 8             # L2S_MAX_GROUP
+MAX_RAGGED_CLIPS = 256    # L2S_MAX_RAGGED_CLIPS
+
+
+def ragged_plan(batch_B, batch_T, video_lengths):
+    """`l2s_ragged_plan`: the compact layout of a ragged group, a pure host function of the library.  `batch_B` / `batch_T`: clips and padded length of
+    every batch; `video_lengths`: one list per batch, or the flat list of all N lengths in batch order.  Returns `(frame0, pair0, N, Tmax)`: the prefix
+    sums (N + 1 entries each) of the lengths and of ceil(len / 2).  Raises `RuntimeError` with the library's message for shapes outside the limits."""
+    G = len(batch_B)
+    flat = [int(v) for v in video_lengths] if not (len(video_lengths) and hasattr(video_lengths[0], "__len__")) else [int(v) for b in video_lengths for v in b]
+    n = sum(int(b) for b in batch_B)
+    if len(flat) != n:
+        raise ValueError(f"video_lengths must hold {n} lengths (sum of batch_B), got {len(flat)}")
+    i32 = ctypes.c_int32
+    f0, p0 = (i32 * (n + 1))(), (i32 * (n + 1))()
+    N, Tmax = _i(), _i()
+    check(lib().l2s_ragged_plan(G, (i32 * G)(*[int(b) for b in batch_B]), (i32 * G)(*[int(t) for t in batch_T]), (i32 * max(n, 1))(*flat), f0, p0,
+                                ctypes.byref(N), ctypes.byref(Tmax)))
+    return list(f0[:N.value + 1]), list(p0[:N.value + 1]), N.value, Tmax.value
+
+
 class NativeModel:
     """Owns an ``l2s_model`` (the packed device weight blob)."""
 
@@ -310,6 +349,9 @@ class NativeModel:
         need = int(self._L.l2s_workspace_bytes_multi(G, B, T, H, W, S)) if G else int(self._L.l2s_workspace_bytes(B, T, H, W, S))
         if masked:
             need = int(self._L.l2s_workspace_bytes_masked(B, T, H, W, S))
+        return self._workspace(need, device)
+
+    def _workspace(self, need: int, device) -> torch.Tensor:
         ws = getattr(self._tls, "ws", None)
         if ws is None or ws.numel() < need or ws.device != device:
             ws = self._tls.ws = torch.empty(need, dtype=torch.uint8, device=device)
@@ -513,6 +555,54 @@ class NativeModel:
         self._check(self._L.l2s_inference_multi(self._h, G, arr(vids), arr(embs), arr(gums), B, T, H, W, S, _ptr(mel_post), _ptr(lengths), _ptr(attn),
                                         _ptr(ws), ws.numel(), _stream()))
         return [(mel_post[g * B:(g + 1) * B], lengths[g * B:(g + 1) * B], attn[g * B:(g + 1) * B] if want_attn else None) for g in range(G)]
+
+    def inference_ragged(self, batches, video_lengths, S: int = 300, want_attn: bool = False):
+        """A ragged group (`l2s_inference_ragged`): `batches` = up to 8 (video, emb, gumbel) tuples, each batch with its own B and T (padded to its own
+        longest clip, or further), at most 256 clips in all; `video_lengths` = one sequence of B_g lengths in [7, T_g] per batch.  All clips run as rows
+        of ONE launch chain, each decoded as it would be alone, the encoder on the real frames only (frames past a clip's length are never read).
+        Returns, per batch, `(mel_post (B_g,80,S), lengths (B_g,), attn (B_g,S,T_g) or None)` - slices of the group's tensors; row b is what
+        `inference(batch, video_lengths=)` gives for it."""
+        G = len(batches)
+        if not 1 <= G <= MAX_GROUP:
+            raise ValueError(f"a ragged group holds 1..{MAX_GROUP} batches (L2S_MAX_GROUP), got {G}")
+        if len(video_lengths) != G:
+            raise ValueError(f"video_lengths must hold one sequence of lengths per batch ({G}), got {len(video_lengths)}")
+        shapes = [tuple(b[0].shape) for b in batches]
+        if any(len(sh) != 5 or sh[1] != 3 for sh in shapes) or any(sh[3:] != shapes[0][3:] for sh in shapes):
+            raise ValueError(f"the batches of a ragged group are (B,3,T,H,W) videos of one H x W, got {shapes}")
+        lens = [video_lengths_array(vl, sh[0], sh[2]) for vl, sh in zip(video_lengths, shapes)]      # ValueError / TypeError before anything reaches the device
+        N = sum(sh[0] for sh in shapes)
+        if N > MAX_RAGGED_CLIPS:
+            raise ValueError(f"a ragged group holds at most {MAX_RAGGED_CLIPS} clips (L2S_MAX_RAGGED_CLIPS), got {N}")
+        for b, sh in zip(batches, shapes):
+            m = sh[2] // 7      # l2s_min_T(T_g) for T_g >= 7 (the stride-7 branch of Content.agg)
+            if tuple(b[1].shape) != (sh[0], 256) or tuple(b[2].shape) != (sh[0] * m, 501):
+                raise ValueError(f"emb must be {(sh[0], 256)} and the gumbel noise {(sh[0] * m, 501)}, got {tuple(b[1].shape)} and {tuple(b[2].shape)}")
+        vids = [_f32(b[0]) for b in batches]
+        embs = [_f32(b[1]) for b in batches]
+        gums = [_f32(b[2]) for b in batches]
+        H, W = shapes[0][3:]
+        Tmax = max(sh[2] for sh in shapes)
+        i32 = ctypes.c_int32
+        bB, bT = (i32 * G)(*[sh[0] for sh in shapes]), (i32 * G)(*[sh[2] for sh in shapes])
+        flat = (i32 * N)(*[v for l in lens for v in l])
+        dev = vids[0].device
+        need = int(self._L.l2s_workspace_bytes_ragged(G, bB, bT, H, W, S))
+        if need < 0:
+            self._check(1)
+        ws = self._workspace(need, dev)
+        mel_post = torch.empty(N, 80, S, dtype=torch.float32, device=dev)
+        lengths = torch.empty(N, dtype=torch.int64, device=dev)
+        attn = torch.empty(N, S, Tmax, dtype=torch.float32, device=dev) if want_attn else None
+        self.calls["l2s_inference_ragged"] += 1
+        arr = lambda ts: (_vp * G)(*[t.data_ptr() for t in ts])      # noqa: E731
+        self._check(self._L.l2s_inference_ragged(self._h, G, arr(vids), arr(embs), arr(gums), bB, bT, flat, H, W, S, _ptr(mel_post), _ptr(lengths), _ptr(attn),
+                                                 _ptr(ws), ws.numel(), _stream()))
+        out, c = [], 0
+        for sh in shapes:
+            out.append((mel_post[c:c + sh[0]], lengths[c:c + sh[0]], attn[c:c + sh[0], :, :sh[2]] if want_attn else None))
+            c += sh[0]
+        return out
 
     def speaker_encoder_fwd(self, audio: torch.Tensor) -> torch.Tensor:
         audio = _f32(audio)

@@ -9,8 +9,9 @@ Padding note: by default the model ignores lengths as the refere
 change results.  ``shard_batches`` therefore never re-pads: it cuts a list of already collated batches, so every
 batch keeps the composition the single-process run would have used and results are identical to it.  With the
 length-masked entry points (``NativeModel.inference(..., video_lengths=)``, ``Lip2Speech.honour_video_lengths``;
-include/l2s.h "per-clip video lengths") a clip's output no longer depends on what shares its batch - but the pools
-below drive the grouped entry points, which have no masked form: masked calls go one batch per call.
+include/l2s.h "per-clip video lengths") a clip's output no longer depends on what shares its batch, and masked
+calls no longer have to go one batch per call: the pool's job entry "inference_ragged" (``Lip2Speech.inference_many_lengths``)
+runs batches of unequal B and T as rows of one launch chain (``l2s_inference_ragged``, include/l2s.h "ragged groups").
 """
 from __future__ import annotations
 
@@ -255,9 +256,35 @@ class InflightPool:
     # ------------------------------------------------------------------------------------------------ streaming form
     @staticmethod
     def _job_key(job: dict):
+        if job["entry"] == "inference_ragged":      # a ragged group takes batches of any B and T: the key ignores both
+            return (job["entry"], int(job["video"].shape[3]), int(job["video"].shape[4]), int(job["S"]), bool(job.get("want_attn", False)))
         mask = job.get("mask")
         return (job["entry"], tuple(job["video"].shape), int(job["S"]), bool(job.get("want_attn", False)),
                 bytes(bytearray(mask)) if mask is not None else None)
+
+    @staticmethod
+    def group_accepts(group_jobs: List[dict], job: dict, group: int) -> bool:
+        """The grouping rule of `imap`, a pure function: may `job` join the running group `group_jobs`?  A group closes at `group` jobs and when the
+        key changes (`_job_key`: entry, shape, S, mask - for "inference_ragged" entry, H, W, S, want_attn only); a ragged group also when the next
+        batch would take its clips past 256 (L2S_MAX_RAGGED_CLIPS)."""
+        if not group_jobs:
+            return True
+        if len(group_jobs) >= group or InflightPool._job_key(job) != InflightPool._job_key(group_jobs[0]):
+            return False
+        if job["entry"] == "inference_ragged":
+            return sum(int(j["video"].shape[0]) for j in group_jobs) + int(job["video"].shape[0]) <= 256
+        return True
+
+    @staticmethod
+    def job_groups(jobs: Sequence[dict], group: int) -> List[List[int]]:
+        """`group_accepts` applied to a whole sequence of jobs: the index runs that `imap` would put into one launch chain each."""
+        out: List[List[int]] = []
+        for i, job in enumerate(jobs):
+            if out and InflightPool.group_accepts([jobs[k] for k in out[-1]], job, group):
+                out[-1].append(i)
+            else:
+                out.append([i])
+        return out
 
     def _run_group(self, jobs: List[dict]) -> List[tuple]:
         j0 = jobs[0]
@@ -269,12 +296,16 @@ class InflightPool:
             return self.model.inference_multi([(j["video"], j["emb"], j["gumbel"]) for j in jobs], S=j0["S"], want_attn=j0.get("want_attn", False))
         if j0["entry"] == "forward":
             return self.model.forward_eval_multi([(j["video"], j["emb"], j["gumbel"], j.get("teacher")) for j in jobs], j0["S"], teacher_mask=j0.get("mask"))
+        if j0["entry"] == "inference_ragged":
+            return self.model.inference_ragged([(j["video"], j["emb"], j["gumbel"]) for j in jobs], [j["video_lengths"] for j in jobs], S=j0["S"],
+                                               want_attn=j0.get("want_attn", False))
         raise ValueError(f"unknown entry {j0['entry']!r}")
 
     def imap(self, items: Iterable, prepare: Callable, depth: int = 2) -> Iterator:
         """Streaming `map` for loader-driven callers (the reference's demo.py:60-90 / evaluate.py:22-51 loops take one batch per iteration):
         `items` is any iterable (a DataLoader), `prepare(item)` turns an item into a job - a dict with `entry` ("inference" =
-        `Lip2Speech.inference`, "forward" = eval-mode `Lip2Speech.forward`), device tensors `video`, `emb`, `gumbel`, the step count `S`, and
+        `Lip2Speech.inference`, "forward" = eval-mode `Lip2Speech.forward`, "inference_ragged" = `Lip2Speech.inference(video_lengths=)`: the job also
+        carries `video_lengths`, and jobs of ANY B and T share a chain - `l2s_inference_ragged`, at most 256 clips), device tensors `video`, `emb`, `gumbel`, the step count `S`, and
         optionally `want_attn` (inference), `teacher` + `mask` (forward: scheduled sampling) and `finish(result) -> value`.  Yields one value per
         item, IN ORDER, each bit-identical to the single-batch call.
 
@@ -316,8 +347,8 @@ class InflightPool:
                             job = prepare(item)
                             idx = st["next"]
                             st["next"] += 1
-                        if group and self._job_key(job) != self._job_key(group[0][1]):
-                            st["pending"] = (idx, job)          # another shape / S / mask closes the running group
+                        if not self.group_accepts([j for _, j in group], job, self.group):
+                            st["pending"] = (idx, job)          # another shape / S / mask (a ragged group: too many clips) closes the running group
                             break
                         group.append((idx, job))
                     ev = torch.cuda.Event()
