@@ -93,6 +93,32 @@ int64_t l2s_state_offset(int B, int T, int field);
 int l2s_normalise_pad_frames(const uint8_t* packed_u8, const int64_t* offsets, const int32_t* frames, int B, int T, int H, int W,
                              float* video, void* stream);
 
+/* The audio half of the same boundary (datasets/spectograms.py:41-59: torchaudio MelSpectrogram - hann window, centre / reflect padding, power 2 -
+ * then log(clamp(x, 1e-5)); datasets/__init__.py:7-46: the audio / mel / gate padding of the collates): B waveforms packed back to back in ONE device
+ * buffer become the padded log-mel targets, the gates, the mel lengths and the zero-padded audio, in one launch chain (mel_targets.hip).  torchaudio is
+ * absent from the build image: the transform is the algorithm as restated in lip2speech_amd/datasets/spectrograms.py - PARITY UNPINNED against the package,
+ * like the vocoder below; the kernel is tested against that restatement in fp64.
+ * l2s_mel_frames: the frames torch.stft(center=True) makes of n samples at hop 256, n / 256 + 1; 0 and an error for n < 513 (reflect padding of 512
+ *   needs n > 512) or n > 2^30.
+ * l2s_mel_targets:
+ *   audio_packed dev fp32; clip b starts at float offset offsets[b] and has n_samples[b] samples (both HOST arrays of B entries, like the frame tables
+ *                above; they may be freed when the call returns).  Any offset works; clips that start on 8-byte boundaries are read with 8-byte loads
+ *   fb           dev fp32 (513, n_mels) dense filterbank, fb_nnz its non-zero count (exact, host-side; at most 2048) - the caller's definition of the mel
+ *                scale, as l2s_inverse_mel takes it
+ *   mels         dev (B, n_mels, M_pad): frame t < l2s_mel_frames(n_b) = log(max(mel_power, 1e-5)) if log_output else mel_power, mel_power = sum over the
+ *                band's bins, ascending, of |STFT|^2 fb (fp32; the log is the fp64 one rounded to nearest); frames past it = mel_pad
+ *   gate         dev (B, M_pad) or NULL: 0 before frame M_b - 1, 1 from it on
+ *   audio_pad    dev (B, A_pad) or NULL: the samples, then zeros
+ *   mel_lengths  dev (B) int64 or NULL: M_b
+ * Every element of every given output is written.  One 64-lane wave per frame: a frame's values are the same bits whatever else is in the call.
+ * Built for n_fft = win_length = 1024 and hop = 256 (what l2s_griffin_lim supports), 1 <= n_mels <= 128, 513 <= n_b <= 2^30, M_pad >= max M_b,
+ * A_pad >= max n_b where audio_pad is given; anything else is an error that names the argument, raised before anything is launched. */
+int     l2s_mel_frames(int64_t n_samples);
+int64_t l2s_mel_targets_workspace_bytes(int B, int n_mels);
+int l2s_mel_targets(const float* audio_packed, const int64_t* offsets, const int64_t* n_samples, int B, const float* fb, int fb_nnz, int n_mels,
+                    int n_fft, int hop, int log_output, float mel_pad, int M_pad, int64_t A_pad, float* mels, float* gate, float* audio_pad,
+                    int64_t* mel_lengths, void* ws, int64_t ws_bytes, void* stream);
+
 /* VideoExtractor.forward (video.py:76-87): video dev (B,3,T,H,W) -> feat dev (B,T,768), L2-normalised.
  * H = W in {88, 96}. */
 int l2s_encoder_fwd(l2s_model* m, const float* video, int B, int T, int H, int W,

@@ -467,6 +467,13 @@ int launch_zero_slot_rows(float* z, int ldz, float* dis, int n, int B, int m, co
 int launch_step_attn_masked(const AttnP& at, const SkinnyP& pre2, int pre2_tiles, const int* lens, hipStream_t s, int lds_values = 1, int skip0 = 0);
 int launch_frame_window(const float* audio, int B, int N, int L, int n_fft, int hop, const float* window, float* frames, hipStream_t s);
 int launch_power(const float* spec, int lds, int64_t rows, int nf, float* power, int ldp, hipStream_t s);
+// ---------------------------------------------------------------- mel filterbank band tables (vocoder.hip; read by l2s_inverse_mel and l2s_mel_targets)
+constexpr int IM_MAXF = 576;      // 9 bins per lane
+constexpr int IM_MAXM = 128;      // 2 mel bands per lane
+constexpr int IM_NNZ = 2048;      // capacity of each compact table (the 513 x 80 HTK filterbank has ~1 100 non-zeros)
+// fb dev (n_freqs, n_mels) -> tab: [n_mels][3] first bin / last+1 / offset into fwd; [n_freqs][3] first band / last+1 / offset into bwd; then the two totals
+// (3 (n_mels + n_freqs) + 2 ints); fwd / bwd (IM_NNZ floats each): fb's values over those ranges, band-major / bin-major.  One block, on `s`
+int launch_mel_bands(const float* fb, int n_freqs, int n_mels, int* tab, float* fwd, float* bwd, hipStream_t s);
 // stop_const[b] = dot(ecell[b], w[512:1024]) + bias
 int launch_stop_const(const float* ecell, const float* w_tail, const float* bias, int B, float* out, hipStream_t s);
 

@@ -21,10 +21,7 @@ namespace l2s {
 // evaluates the reference's rules per call (new_loss < 1e-5, |loss - new_loss| < 1e-8; the update of the stopping iteration is still
 // applied) and a second pass re-runs only the calls that stop early, with their iteration count.
 // =====================================================================================================================================
-constexpr int IM_MAXF = 576;      // 9 bins per lane
-constexpr int IM_MAXM = 128;      // 2 mel bands per lane
-constexpr int IM_ROWS = 8;        // rows (waves) per block: they share the compact filterbank tables in LDS
-constexpr int IM_NNZ = 2048;      // capacity of each compact table (the 513 x 80 HTK filterbank has ~1 100 non-zeros)
+constexpr int IM_ROWS = 8;        // rows (waves) per block: they share the compact filterbank tables in LDS (IM_MAXF / IM_MAXM / IM_NNZ: l2s_common.h)
 
 struct InvMelP {
     const float* mel;        // (N, n_mels, L) power mel, or log-mel when log_input
@@ -71,6 +68,12 @@ __global__ __launch_bounds__(256) void inverse_mel_bands_kernel(const float* fb,
         if (i < n_mels) { for (int f = lo; f < hi; ++f) if (o + f - lo < IM_NNZ) fwd[o + f - lo] = fb[(int64_t)f * n_mels + i]; }
         else { const int f = i - n_mels; for (int m = lo; m < hi; ++m) if (o + m - lo < IM_NNZ) bwd[o + m - lo] = fb[(int64_t)f * n_mels + m]; }
     }
+}
+
+int launch_mel_bands(const float* fb, int n_freqs, int n_mels, int* tab, float* fwd, float* bwd, hipStream_t s) {
+    L2S_REQUIRE(n_mels > 0 && n_mels <= IM_MAXM && n_freqs > 0 && n_freqs <= IM_MAXF, "mel bands: at most 128 mel bands and 576 frequency bins");
+    hipLaunchKernelGGL(inverse_mel_bands_kernel, dim3(1), dim3(256), 0, s, fb, n_freqs, n_mels, tab, fwd, bwd);
+    return 0;
 }
 
 __global__ __launch_bounds__(IM_ROWS * 64) void inverse_mel_kernel(const InvMelP p) {
@@ -513,7 +516,7 @@ int l2s_inverse_mel(const float* mel, int log_input, const float* fb, int fb_nnz
     float* loss_rows = (float*)w; w += im_align(rows * (iters > 0 ? iters : 1) * 4);
     int* iters_call = iters_run ? iters_run : (int*)w;
     ProfScope ps("vocoder_inverse_mel", s);
-    hipLaunchKernelGGL(inverse_mel_bands_kernel, dim3(1), dim3(256), 0, s, fb, n_freqs, n_mels, tab, fwd, bwd);
+    if (launch_mel_bands(fb, n_freqs, n_mels, tab, fwd, bwd, s)) return 1;
     InvMelP p{mel, init, tab, fwd, bwd, spec, iters > 0 ? loss_rows : nullptr, nullptr, N, L, n_mels, n_freqs, rows_per_call, iters, log_input, 0};
     const unsigned blocks = (unsigned)((rows + IM_ROWS - 1) / IM_ROWS);
     hipLaunchKernelGGL(inverse_mel_kernel, dim3(blocks), dim3(IM_ROWS * 64), 0, s, p);

@@ -49,12 +49,14 @@ def face_recog_resize(frame_u8: torch.Tensor) -> torch.Tensor:
 
 
 class LRW(Dataset):
-    def __init__(self, rootpth, face_size=(96, 96), mode="train", demo=False, duration=1, face_augmentation=None, *args, raw_frames=False, **kwargs):
+    def __init__(self, rootpth, face_size=(96, 96), mode="train", demo=False, duration=1, face_augmentation=None, *args, raw_frames=False, raw_audio=False, **kwargs):
         """`raw_frames=True` (an extension): items carry the decoded uint8 clip `(T,H,W,3)` instead of the normalised fp32 one - the
-        normalisation then runs on the device (`datasets.device.device_collate_fn_pad` + `PackedFrames.to_device`).  Extra positional /
-        keyword arguments are accepted and ignored (the reference forwards them to `Dataset.__init__`, which takes none)."""
+        normalisation then runs on the device (`datasets.device.device_collate_fn_pad` + `PackedFrames.to_device`).  `raw_audio=True` (likewise):
+        the CPU mel transform is skipped and the items' melspec slot is `None` - the targets then come from the device
+        (`datasets.device.device_collate_fn_pad_raw` + `PackedAudio.to_device`).  Extra positional / keyword arguments are accepted and ignored
+        (the reference forwards them to `Dataset.__init__`, which takes none)."""
         super().__init__()
-        self.raw_frames = raw_frames
+        self.raw_frames, self.raw_audio = raw_frames, raw_audio
         assert mode in ("train", "test", "val")
         self.rootpth, self.mode, self.demo = rootpth, mode, demo
         self.face_size, self.duration = face_size, duration
@@ -79,7 +81,7 @@ class LRW(Dataset):
         frames = load_frames(mouth_path)
         mouth = torch.from_numpy(np.ascontiguousarray(frames)) if self.raw_frames else normalise_mouth(frames)
         speech = torch.from_numpy(np.load(audio_path)["data"][np.newaxis])
-        melspec = self.melspec_g(speech).squeeze(0)
+        melspec = None if self.raw_audio else self.melspec_g(speech).squeeze(0)
         # two random face frames resized to 160x160 feed the third-party face tower (dataset.py:139-141).  The tower is outside this path,
         # but the draw is part of an epoch's RNG consumption: `torch.rand(2)` is taken exactly where the reference takes it, face file or not
         draw = torch.rand(2)

@@ -30,8 +30,14 @@ def mel_filterbank(n_freqs: int, f_min: float, f_max: float, n_mels: int, sample
 
 class MelSpectrogram(torch.nn.Module):
     def __init__(self, hparams=None, n_fft=None, hop_length=None, win_length=None, n_mels=None, f_min=None, f_max=None,
-                 sample_rate=None, log=True):
+                 sample_rate=None, log=True, backend: str = "auto"):
+        """`backend`: "hip" = the device kernel behind `l2s_mel_targets` (mel_targets.hip: one wave per frame, wave-level 1024-point FFT, banded
+        filterbank sums); "torch" = the restatement on `torch.stft` below (what the kernel is tested against); "auto" = "hip" for fp32 device
+        tensors of a supported shape (n_fft = win = 1024, hop 256, at most 128 mel bands, at least 513 samples), else "torch".  CPU tensors always
+        take the torch path."""
         super().__init__()
+        assert backend in ("auto", "hip", "torch"), backend
+        self.backend = backend
         hp = hparams or create_hparams()
         self.n_fft = n_fft or hp.filter_length
         self.hop = hop_length or hp.hop_length
@@ -43,11 +49,27 @@ class MelSpectrogram(torch.nn.Module):
         f_max = hp.mel_fmax if f_max is None else f_max
         self.register_buffer("window", torch.hann_window(self.win, periodic=True))
         self.register_buffer("fb", mel_filterbank(self.n_fft // 2 + 1, f_min, f_max, n_mels, self.sr))
+        self.fb_nnz = int((self.fb != 0).sum())
+
+    def _use_hip(self, x: torch.Tensor) -> bool:
+        ok = (x.is_cuda and x.dtype == torch.float32 and self.fb.dtype == torch.float32 and self.fb.device == x.device and self.n_fft == 1024 and
+              self.win == 1024 and self.hop == 256 and self.fb.shape[1] <= 128 and 0 < self.fb_nnz <= 2048 and x.shape[0] > 0 and x.shape[-1] >= 513 and
+              not (x.requires_grad and torch.is_grad_enabled()))              # the kernel has no backward: a waveform that wants a gradient keeps torch's
+        if self.backend == "hip" and not ok:
+            raise RuntimeError("MelSpectrogram(backend='hip'): needs fp32 device tensors (module on the same device), n_fft = win = 1024, hop 256, "
+                               "at most 128 mel bands and at least 513 samples per waveform")
+        return ok and self.backend in ("auto", "hip")
 
     def forward(self, waveform: torch.Tensor) -> torch.Tensor:
         """(..., N) -> (..., n_mels, N // hop + 1)"""
         shape = waveform.shape
         x = waveform.reshape(-1, shape[-1])
+        if self._use_hip(x):
+            from .. import native
+            R, N = x.shape
+            x = x.detach().contiguous()                                            # the rows of a contiguous (R, N) tensor ARE waveforms packed back to back
+            mel = native.mel_targets(x.reshape(-1), [r * N for r in range(R)], [N] * R, self.fb, self.fb_nnz, log=self.log, want_audio=False)[0]
+            return mel.reshape(*shape[:-1], mel.shape[-2], mel.shape[-1])
         spec = torch.stft(x, self.n_fft, hop_length=self.hop, win_length=self.win, window=self.window, center=True,
                           pad_mode="reflect", normalized=False, onesided=True, return_complex=True)
         power = spec.real ** 2 + spec.imag ** 2                                   # (B, n_freqs, L)

@@ -29,6 +29,7 @@ ABI_SYMBOLS = (
     "l2s_abi_version", "l2s_last_error",
     "l2s_model_create", "l2s_model_set_tensor", "l2s_model_finalize", "l2s_model_destroy",
     "l2s_min_T", "l2s_workspace_bytes", "l2s_state_floats", "l2s_state_offset",
+    "l2s_mel_frames", "l2s_mel_targets_workspace_bytes", "l2s_mel_targets",
     "l2s_encoder_fwd", "l2s_normalise_pad_frames", "l2s_build_visual", "l2s_decoder_prologue", "l2s_decode_steps", "l2s_postnet",
     "l2s_workspace_bytes_masked", "l2s_masked_bilstm_plan", "l2s_inference_masked", "l2s_forward_eval_masked", "l2s_decoder_prologue_masked", "l2s_decode_steps_masked",
     "l2s_ragged_plan", "l2s_workspace_bytes_ragged", "l2s_inference_ragged",
@@ -195,6 +196,14 @@ def _bind(L: ctypes.CDLL) -> None:
         L.l2s_workspace_bytes_ragged.restype = _i64
         L.l2s_inference_ragged.argtypes = [_vp, _i, ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp), _lens, _lens, _lens, _i, _i, _i, _fp, _vp, _fp,
                                            _vp, _i64, _vp]
+    # device-side mel targets (include/l2s.h): likewise absent from a library built before them
+    if hasattr(L, "l2s_mel_targets"):
+        L.l2s_mel_frames.argtypes = [_i64]
+        L.l2s_mel_frames.restype = _i
+        L.l2s_mel_targets_workspace_bytes.argtypes = [_i, _i]
+        L.l2s_mel_targets_workspace_bytes.restype = _i64
+        L.l2s_mel_targets.argtypes = [_fp, ctypes.POINTER(_i64), ctypes.POINTER(_i64), _i, _fp, _i, _i, _i, _i, _i, ctypes.c_float, _i, _i64, _fp, _fp, _fp, _vp,
+                                      _vp, _i64, _vp]
 
 
 def _bind_diag(L: ctypes.CDLL) -> None:
@@ -829,6 +838,48 @@ def normalise_pad_frames(packed_u8: torch.Tensor, offsets, frames, H: int = 96, 
     fr = (ctypes.c_int32 * B)(*[int(f) for f in frames])
     check(lib().l2s_normalise_pad_frames(packed_u8.data_ptr(), off, fr, B, T, H, W, _ptr(video), _stream()))
     return video
+
+
+MEL_PAD = -11.5129      # ln(1e-5) as the collates write it (datasets.MEL_PAD)
+_mel_tls = threading.local()
+
+
+def mel_frames(n: int) -> int:
+    """`l2s_mel_frames`: the frames `torch.stft(center=True)` makes of n samples at hop 256 (n // 256 + 1); raises below 513 samples."""
+    m = int(lib().l2s_mel_frames(int(n)))
+    if m == 0:
+        check(1)
+    return m
+
+
+def mel_targets(audio_packed: torch.Tensor, offsets, n_samples, fb: torch.Tensor, fb_nnz: int, *, log: bool = True, mel_pad: float = MEL_PAD,
+                M: Optional[int] = None, A: Optional[int] = None, want_audio: bool = True):
+    """`l2s_mel_targets`: B waveforms packed back to back on the device (clip b = `n_samples[b]` floats at float offset `offsets[b]` of
+    `audio_packed`) -> (mels (B, n_mels, M) log-mel (power-mel when not `log`) padded with `mel_pad`, gate (B, M), audio (B, A) zero-padded or
+    None, mel_lengths (B,) int64 on the device).  M / A default to the longest clip's frames / samples; fb (513, n_mels) with `fb_nnz` non-zeros."""
+    assert audio_packed.is_cuda and audio_packed.dtype == torch.float32 and audio_packed.is_contiguous() and audio_packed.dim() == 1
+    fb = _f32(fb)
+    B, n_mels = len(n_samples), int(fb.shape[1])
+    assert len(offsets) == B and fb.shape[0] == 513, (len(offsets), B, fb.shape)
+    ns = [int(n) for n in n_samples]
+    off = [int(o) for o in offsets]
+    assert all(0 <= o and o + n <= audio_packed.numel() for o, n in zip(off, ns)), "a clip lies outside the packed buffer"
+    L = lib()
+    dev = audio_packed.device
+    M = (max(ns) // 256 + 1 if ns else 0) if M is None else int(M)
+    A = (max(ns) if ns else 0) if A is None else int(A)
+    need = int(L.l2s_mel_targets_workspace_bytes(B, n_mels))
+    cache = _mel_tls.__dict__.setdefault("ws", {})             # one workspace per device (and host thread): the band tables are rebuilt by every call
+    ws = cache.get(dev)
+    if ws is None or ws.numel() < need:
+        ws = cache[dev] = torch.empty(need, dtype=torch.uint8, device=dev)
+    mels = torch.empty(B, n_mels, M, dtype=torch.float32, device=dev)
+    gate = torch.empty(B, M, dtype=torch.float32, device=dev)
+    audio = torch.empty(B, A, dtype=torch.float32, device=dev) if want_audio else None
+    lengths = torch.empty(B, dtype=torch.int64, device=dev)
+    check(L.l2s_mel_targets(audio_packed.data_ptr(), (_i64 * B)(*off), (_i64 * B)(*ns), B, fb.data_ptr(), int(fb_nnz), n_mels, 1024, 256, int(bool(log)),
+                            float(mel_pad), M, A, mels.data_ptr(), gate.data_ptr(), _ptr(audio), lengths.data_ptr(), ws.data_ptr(), ws.numel(), _stream()))
+    return mels, gate, audio, lengths
 
 
 def build_visual(feat: torch.Tensor, emb: torch.Tensor) -> torch.Tensor:
