@@ -184,11 +184,19 @@ int l2s_face_encoder_fwd(l2s_model* m, const float* faces, int64_t batch_stride,
  *   rules - loss < 1e-5, |loss - previous loss| < 1e-8, the update of the stopping iteration still applied - are per call).
  *   spec dev (N, n_freqs, L) >= 0.  loss_per_iter dev (calls, iters) or NULL; iters_run dev int (calls) or NULL.
  * l2s_griffin_lim: torchaudio.functional.griffinlim (power 2, rand_init replaced by init_angles dev (N, n_freqs, L, 2) used as
- *   given, momentum 0.99): power_spec dev (N, 513, L) -> wave dev (N, hop*(L-1)).  n_fft = win_length = 1024, hop = 256, L <= 121.
+ *   given, momentum 0.99): power_spec dev (N, 513, L) -> wave dev (N, hop*(L-1)).  n_fft = win_length = 1024, hop = 256, L >= 5.
+ *   Up to 121 frames (1.9 s) the clip's waveform stays in one block's LDS for the whole loop: one launch.  From 122 frames on, one launch
+ *   per iteration over (clip, tile of 24 frames): a block recomputes the samples its frames read (a halo of three frames each side) and
+ *   the rebuilt spectra rotate through three workspace slots - l2s_griffin_lim_workspace_bytes grows from two to three slots there, about
+ *   14.6 KB per frame (140 MB at N = 32, L = 300); any L the workspace allows.  Either way a clip's waveform depends on neither N nor its
+ *   neighbours.
  * l2s_estoi: pystoi.stoi(clean, pred, fs, extended=True) per clip: clean / pred dev (N, n_samples); fir dev = the polyphase
  *   resampling filter of scipy.signal.resample_poly(x, up, down) INCLUDING its leading zero pad (n_fir taps, already scaled by up),
  *   n_pre_remove / n_resampled as resample_poly computes them, or fir = NULL when fs is already 10 kHz; band_lo_hi_host = HOST
- *   array of 2 x 15 ints, first / last+1 bin of each one-third octave band; score dev (N). */
+ *   array of 2 x 15 ints, first / last+1 bin of each one-third octave band; score dev (N).  Up to 16 512 resampled samples (1.65 s)
+ *   both signals stay in one block's LDS; above that, up to 48 256 (4.8 s), they live in the workspace and the resampler is a kernel of
+ *   its own - the same algorithm and order of sums.  l2s_estoi_workspace_bytes_long sizes the workspace of the form a call takes
+ *   (= l2s_estoi_workspace_bytes(N) up to 16 512 samples); l2s_estoi checks ws_bytes against it. */
 int64_t l2s_inverse_mel_workspace_bytes(int N, int L, int n_mels, int n_freqs, int rows_per_call, int iters);
 int l2s_inverse_mel(const float* mel, int log_input, const float* fb, int fb_nnz, const float* init, int N, int L, int n_mels, int n_freqs,
                     int rows_per_call, int iters, float* spec, float* loss_per_iter, int* iters_run, void* ws, int64_t ws_bytes, void* stream);
@@ -196,6 +204,7 @@ int64_t l2s_griffin_lim_workspace_bytes(int N, int L);
 int l2s_griffin_lim(const float* power_spec, const float* init_angles, int N, int L, int n_fft, int hop, int iters, float momentum,
                     float* wave, void* ws, int64_t ws_bytes, void* stream);
 int64_t l2s_estoi_workspace_bytes(int N);
+int64_t l2s_estoi_workspace_bytes_long(int N, int n_resampled);
 int l2s_estoi(const float* clean, const float* pred, int N, int n_samples, const float* fir, int n_fir, int up, int down, int n_pre_remove,
               int n_resampled, const int* band_lo_hi_host, float* score, void* ws, int64_t ws_bytes, void* stream);
 

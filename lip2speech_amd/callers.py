@@ -197,7 +197,7 @@ def evaluate_net(net, batches: Iterable, speaker_encoder=None, device="cuda", ma
     t = {"model_wait_s": 0.0, "vocoder_s": 0.0, "estoi_s": 0.0, "clips": 0}
     def vocode_and_score(pending):
         """One vocoder pass over the mels of up to `group` loader batches, then ESTOI per clip.  On the device path (`metric="hip"`, default
-        where the shapes allow: vocoder.hip) the vocoder is three launches per pass and the metric one block per clip - the predictions never
+        where the shapes allow: vocoder.hip) the vocoder is three launches per pass (plus one per Griffin-Lim iteration past 121 mel frames) and the metric one block per clip - the predictions never
         leave the GPU, one (N,) score vector comes back per group; `metric="host"` scores with the numpy restatement like the reference."""
         t1 = time.perf_counter()
         same = all(m.shape[0] == pending[0][1].shape[0] for _, m in pending)
@@ -207,9 +207,9 @@ def evaluate_net(net, batches: Iterable, speaker_encoder=None, device="cuda", ma
             pred_dev = torch.cat([vocoder(m) for _, m in pending], dim=0)
         n = min(min(a.shape[1] for a, _ in pending), pred_dev.shape[1])      # the device branch only (all audio lengths equal there)
         on_device = metric != "host" and pred_dev.is_cuda and all(a.shape[1] == pending[0][0].shape[1] for a, _ in pending) and \
-            -(-n * 10000 // fs) <= 16512
+            -(-n * 10000 // fs) <= native.ESTOI_MAX_SAMPLES
         if metric == "hip" and not on_device:
-            raise RuntimeError("evaluate_net(metric='hip'): needs device predictions and clips of at most 1.65 s")
+            raise RuntimeError(f"evaluate_net(metric='hip'): needs device predictions and clips of at most {native.ESTOI_MAX_SAMPLES} samples at 10 kHz (4.8 s)")
         if on_device:
             torch.cuda.synchronize()
             t2 = time.perf_counter()
@@ -238,7 +238,10 @@ def evaluate_net(net, batches: Iterable, speaker_encoder=None, device="cuda", ma
             pending = []
             for batch, out in _evaluate_outputs(net, batches, speaker_encoder, device, group, n_inflight, encoding, honour_lengths):
                 mel = out[1]
-                if pending and (len(pending) == max(1, group) or pending[0][1].shape[1:] != mel.shape[1:]):
+                # a pass holds batches of one mel shape AND one audio width: batches padded to different audio lengths are then scored per
+                # equal-width run (on the device where the metric runs there) - a batch's score does not depend on which batches share its group
+                if pending and (len(pending) == max(1, group) or pending[0][1].shape[1:] != mel.shape[1:] or
+                                pending[0][0].shape[1] != batch[1][0].shape[1]):
                     t["model_wait_s"] += time.perf_counter() - t0
                     vocode_and_score(pending)
                     pending = []

@@ -323,6 +323,148 @@ __global__ __launch_bounds__(NW * 64) void griffin_lim_kernel(const GriffinP p) 
 }
 
 // =====================================================================================================================================
+// Griffin-Lim, long form (L >= 122: the waveform no longer fits one block's LDS).  ONE LAUNCH PER ITERATION, one block per (clip, tile of
+// F consecutive STFT frames), no barrier or wait between blocks inside a launch.  A block recomputes the waveform samples its own forward
+// transforms read - [t0 hop - 512, (t1 - 1) hop + 512) plus the indices torch.stft's reflect padding mirrors into at the clip's two ends -
+// from the inverse transforms of every frame that covers them (a halo of three frames each side), with the short kernel's arithmetic: the
+// same spec_at, the same FFTs, the overlap-add in four barrier-separated phases ordered by the ABSOLUTE t mod 4 (so a sample's sum does not
+// depend on the tiling) and the same envelope division.  It then writes the forward transforms of its own frames, or on the last iteration
+// its own partition [t0 hop, t1 hop) of the waveform: every spectrum value and every sample has exactly one writer.
+// Other blocks of the launch still read rebuilt[it - 1] and rebuilt[it - 2] while this one writes rebuilt[it]: THREE rotating slots
+// (rebuilt[k] in slot k % 3; the start angles in slot 2, which it = 0 reads as "rebuilt[-1]").
+// =====================================================================================================================================
+// built tile: 24 own + 6 halo frames = at most 8 inverse transforms per overlap-add phase, one per wave.  174 VGPRs: one block per compute unit, so a launch
+// of up to 256 blocks (32 clips of 188 frames) is one round of blocks; smaller tiles are 10 % faster below that and 70 % slower at it (profiles/vocoder_long_times.txt)
+constexpr int GLT_F = 24, GLT_NW = 8;
+
+struct GriffinTileP {
+    const float* mag;        // ws: (N, L, 520) sqrt(power), frame-major
+    float2* reb;             // ws: (N, 3, L, 520) rotating rebuilt spectra
+    float* wave;             // (N, hop (L-1)) out
+    int N, L, it, iters;
+    float momentum;          // 0.99 / 1.99
+};
+
+// frame-major copies of sqrt(power) and of the start angles (what the short kernel's prologue writes), the angles into slot 2
+__global__ __launch_bounds__(256) void griffin_lim_tile_prologue_kernel(const float* power, const float* init, float* mag_all, float2* reb_all, int L) {
+    const int clip = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= GL_NBIN * L) return;
+    const int k = i / L, t = i - k * L;
+    const float* pw = power + (int64_t)clip * GL_NBIN * L;
+    const float2* in = reinterpret_cast<const float2*>(init) + (int64_t)clip * GL_NBIN * L;
+    mag_all[((int64_t)clip * L + t) * GL_LDK + k] = sqrtf(fmaxf(pw[i], 0.f));
+    reb_all[(((int64_t)clip * 3 + 2) * L + t) * GL_LDK + k] = in[i];
+}
+
+template <int NW, int F>
+__global__ __launch_bounds__(NW * 64) void griffin_lim_tile_kernel(const GriffinTileP p) {
+    constexpr int YCAP = (F + 3) * GL_HOP;                           // (F - 1) hop + n_fft samples; the clip-end extensions stay below it (F >= 2)
+    static_assert(F >= 2, "a tile's sample range is sized for at least two frames");
+    __shared__ __attribute__((aligned(16))) float y[YCAP];
+    __shared__ __attribute__((aligned(16))) float2 scratch[NW][GL_LDK];
+    __shared__ float w2[GL_NFFT];
+    const int clip = blockIdx.y, tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int L = p.L, ylen = GL_HOP * (L - 1), it = p.it;
+    const int t0 = blockIdx.x * F, t1 = t0 + F < L ? t0 + F : L;
+    float2* sc = scratch[wave];
+    const float* mag = p.mag + (int64_t)clip * L * GL_LDK;
+    float2* reb = p.reb + (int64_t)clip * 3 * L * GL_LDK;
+    const float2* cur = reb + (int64_t)((it + 2) % 3) * L * GL_LDK;  // rebuilt[it - 1] (it = 0: the start angles)
+    const float2* prv = reb + (int64_t)((it + 1) % 3) * L * GL_LDK;  // rebuilt[it - 2]; not read for it < 2
+    // ---- the samples [lo, hi) this block holds: what its forward transforms read, the reflect padding's mirrored indices included
+    const int smin = t0 * GL_HOP - GL_NFFT / 2, smax = (t1 - 1) * GL_HOP + GL_NFFT / 2 - 1;
+    int lo = smin < 0 ? 0 : smin, hi = smax > ylen - 1 ? ylen - 1 : smax;
+    if (smin < 0 && -smin > hi) hi = -smin;
+    if (smax > ylen - 1 && 2 * (ylen - 1) - smax < lo) lo = 2 * (ylen - 1) - smax;
+    lo &= ~1; hi = (hi + 2) & ~1;                                    // both even (ylen is): a frame's sample pair is in or out together; hi exclusive
+    int ta = (lo + GL_NFFT / 2) / GL_HOP - 3; ta = ta < 0 ? 0 : ta;  // frames [ta, tb) cover a sample of [lo, hi): frame t spans [t hop - 512, t hop + 512)
+    int tb = (hi + GL_NFFT / 2 + GL_HOP - 1) / GL_HOP; tb = tb > L ? L : tb;
+    for (int i = tid; i < GL_NFFT; i += NW * 64) { const float w = 0.5f - 0.5f * cospif((float)i / 512.0f); w2[i] = w * w; }
+    for (int i = tid; i < hi - lo; i += NW * 64) y[i] = 0.f;
+    Fft512Tw tw;
+    tw.init(lane);
+    float wn[8][2];
+#pragma unroll
+    for (int r = 0; r < 8; ++r) {
+        const int m = 2 * (lane + 64 * r);
+        wn[r][0] = 0.5f - 0.5f * cospif((float)m / 512.0f);
+        wn[r][1] = 0.5f - 0.5f * cospif((float)(m + 1) / 512.0f);
+    }
+    __syncthreads();
+    // ---------------- phase A: y[lo, hi) = istft(mag * ang)
+    for (int ph = 0; ph < 4; ++ph) {
+        for (int t = ta + ((ph - ta) & 3) + 4 * wave; t < tb; t += 4 * NW) {
+            const float* mg = mag + (int64_t)t * GL_LDK;
+            const float2* c = cur + (int64_t)t * GL_LDK;
+            const float2* q = prv + (int64_t)t * GL_LDK;
+            float2 v[8];
+            auto spec_at = [&](int k) -> float2 {
+                float2 a = c[k];
+                if (it >= 1) {
+                    if (it >= 2) { const float2 b = q[k]; a.x -= p.momentum * b.x; a.y -= p.momentum * b.y; }
+                    const float inv = 1.0f / (sqrtf(a.x * a.x + a.y * a.y) + 1e-16f);
+                    a.x *= inv; a.y *= inv;
+                }
+                const float g = mg[k];
+                return make_float2(g * a.x, g * a.y);
+            };
+#pragma unroll
+            for (int r = 0; r < 8; ++r) v[r] = spec_at(lane + 64 * r);
+            float2 s512 = make_float2(0.f, 0.f);
+            if (lane == 0) s512 = spec_at(512);
+            irfft1024_pre(v, s512, sc, lane, tw);
+            fft512<+1>(v, sc, lane, tw);
+            const int base = t * GL_HOP - GL_NFFT / 2;
+#pragma unroll
+            for (int r = 0; r < 8; ++r) {
+                const int idx = base + 2 * (lane + 64 * r);
+                if (idx >= lo && idx < hi) {
+                    float2 o = *reinterpret_cast<float2*>(y + idx - lo);
+                    o.x += v[r].x * (1.0f / 1024.0f) * wn[r][0];
+                    o.y += v[r].y * (1.0f / 1024.0f) * wn[r][1];
+                    *reinterpret_cast<float2*>(y + idx - lo) = o;
+                }
+            }
+        }
+        __syncthreads();
+    }
+    for (int j = tid; j < hi - lo; j += NW * 64) {
+        const int pp = lo + j + GL_NFFT / 2;
+        int e0 = (pp - (GL_NFFT - 1) + GL_HOP - 1) / GL_HOP; e0 = e0 < 0 ? 0 : e0;
+        int e1 = pp / GL_HOP; e1 = e1 > L - 1 ? L - 1 : e1;
+        float env = 0.f;
+        for (int t = e0; t <= e1; ++t) env += w2[pp - t * GL_HOP];
+        y[j] = y[j] / env;
+    }
+    __syncthreads();
+    if (it == p.iters) {                                             // the waveform: this tile's own partition
+        float* out = p.wave + (int64_t)clip * ylen;
+        const int o1 = t1 * GL_HOP < ylen ? t1 * GL_HOP : ylen;
+        for (int i = t0 * GL_HOP + tid; i < o1; i += NW * 64) out[i] = y[i - lo];
+        return;
+    }
+    // ---------------- phase B: rebuilt[it] = stft(y) (centre, reflect) for the tile's own frames
+    float2* dst = reb + (int64_t)(it % 3) * L * GL_LDK;
+    for (int t = t0 + wave; t < t1; t += NW) {
+        float2 v[8];
+#pragma unroll
+        for (int r = 0; r < 8; ++r) {
+            int s0 = t * GL_HOP + 2 * (lane + 64 * r) - GL_NFFT / 2, s1 = s0 + 1;
+            s0 = s0 < 0 ? -s0 : s0; s0 = s0 >= ylen ? 2 * (ylen - 1) - s0 : s0;
+            s1 = s1 < 0 ? -s1 : s1; s1 = s1 >= ylen ? 2 * (ylen - 1) - s1 : s1;
+            v[r] = make_float2(y[s0 - lo] * wn[r][0], y[s1 - lo] * wn[r][1]);
+        }
+        fft512<-1>(v, sc, lane, tw);
+        const float nyq = rfft1024_post(v, sc, lane, tw);
+        float2* d = dst + (int64_t)t * GL_LDK;
+#pragma unroll
+        for (int r = 0; r < 8; ++r) d[lane + 64 * r] = v[r];
+        if (lane == 0) d[512] = make_float2(nyq, 0.f);
+    }
+}
+
+// =====================================================================================================================================
 // ESTOI (pystoi 0.3.3 stoi(x, y, fs, extended=True) as restated in lip2speech_amd/metrics.py), one block per clip:
 //   resample_poly(., 10000 / g, fs / g) with the caller's polyphase FIR (pystoi's resample_oct window) -> drop the frames of the clean signal more than 40 dB below its
 //   loudest frame (256-sample hann frames, hop 128) from both signals and overlap-add the rest -> 512-point spectra of 256-sample frames ->
@@ -484,6 +626,172 @@ __global__ __launch_bounds__(1024) void estoi_kernel(const EstoiP p) {
     if (tid == 0) p.score[clip] = red[0] / (float)nseg;
 }
 
+// =====================================================================================================================================
+// ESTOI, long form (more than 16 512 samples at 10 kHz: the two signals no longer fit one block's LDS).  The same algorithm and the same
+// order of every per-clip sum as estoi_kernel; what changes is where things live.  The resampler is a grid-wide kernel of its own over
+// (chunk, signal, clip) into the workspace; then one block per clip: the overlap-added signals go to the workspace too (one clip's stay in
+// L2) and are staged into LDS 64 frames at a time for the spectra, the row statistics take the staging buffer's place once the spectra are
+// done, and a thread adds up the contributions of its (segment, frame) items as it computes them - in the order estoi_kernel sums them.
+// =====================================================================================================================================
+constexpr int ESL_MAXFRAMES = 376, ESL_MAXLEN = ES_HOP * (ESL_MAXFRAMES + 1), ESL_CHUNK = 64;      // 48 256 samples at 10 kHz
+
+struct EstoiLongP {
+    const float* clean; const float* pred;    // (N, n_samples)
+    const float* fir;
+    const int* band_lo; const int* band_hi;
+    float* rs;                                 // ws: (N, 2, ESL_MAXLEN) resampled signals
+    float* oa;                                 // ws: (N, 2, ESL_MAXLEN) the silent-frame-free signals
+    float* pw;                                 // ws: (N, 2, ESL_MAXFRAMES, ES_NBIN) power spectra of the frames
+    float* score;                              // (N)
+    int N, n_samples, n_fir, up, down, n_pre_remove, n_res;
+};
+
+__global__ __launch_bounds__(256) void estoi_resample_kernel(const EstoiLongP p) {
+    const int n = blockIdx.x * 256 + threadIdx.x, s = blockIdx.y, clip = blockIdx.z;
+    if (n >= p.n_res) return;
+    const float* x = (s ? p.pred : p.clean) + (int64_t)clip * p.n_samples;
+    float acc;
+    if (p.fir) {                               // upfirdn, zero-padded ends: out[n] = sum_i x[i] h[(n + n_pre_remove) down - i up]
+        const int64_t c = (int64_t)(n + p.n_pre_remove) * p.down;
+        int64_t ihi = c / p.up; if (ihi > p.n_samples - 1) ihi = p.n_samples - 1;
+        int64_t ilo = c - (p.n_fir - 1) <= 0 ? 0 : (c - (p.n_fir - 1) + p.up - 1) / p.up;
+        double a = 0.0;
+        for (int64_t i = ilo; i <= ihi; ++i) a += (double)x[i] * (double)p.fir[c - i * p.up];
+        acc = (float)a;
+    } else {
+        acc = x[n];
+    }
+    p.rs[((int64_t)clip * 2 + s) * ESL_MAXLEN + n] = acc;
+}
+
+__global__ __launch_bounds__(1024) void estoi_long_kernel(const EstoiLongP p) {
+    __shared__ float buf[2 * ESL_MAXFRAMES * ES_BANDS * 2];           // ESL_CHUNK frames of one signal for the spectra; later the row statistics
+    __shared__ float tob[2][ES_BANDS][ESL_MAXFRAMES];
+    __shared__ float2 twd[ES_NFFT];
+    __shared__ float win[ES_FRAME];
+    __shared__ float energy[ESL_MAXFRAMES];
+    __shared__ int keep_pos[ESL_MAXFRAMES];
+    __shared__ float red[1024];
+    __shared__ int n_keep_s;
+    static_assert(ES_HOP * (ESL_CHUNK + 1) <= 2 * ESL_MAXFRAMES * ES_BANDS * 2, "the staged frames fit the buffer the row statistics use later");
+    const int clip = blockIdx.x, tid = threadIdx.x;
+    const float* rs = p.rs + (int64_t)clip * 2 * ESL_MAXLEN;
+    float* oa = p.oa + (int64_t)clip * 2 * ESL_MAXLEN;
+    float* pw = p.pw + (int64_t)clip * 2 * ESL_MAXFRAMES * ES_NBIN;
+    const int nr = p.n_res;
+    constexpr float EPS = 2.220446049250313e-16f;
+    for (int i = tid; i < ES_NFFT; i += 1024) { float s, c; sincospif((float)i / 256.0f, &s, &c); twd[i] = make_float2(c, -s); }
+    for (int i = tid; i < ES_FRAME; i += 1024) win[i] = 0.5f - 0.5f * cospif(2.0f * (float)(i + 1) / (float)(ES_FRAME + 1));
+    __syncthreads();
+    // ---- silent-frame removal: energies of the clean signal's windowed frames (pystoi 0.3.3's frame rule: estoi_kernel)
+    const int nf = nr > ES_FRAME ? (nr - ES_FRAME + ES_HOP - 1) / ES_HOP : 0;
+    {
+        const int wv = tid >> 6, ln = tid & 63;
+        for (int f = wv; f < nf; f += 16) {
+            float e = 0.f;
+            for (int i = ln; i < ES_FRAME; i += 64) { const float v = rs[f * ES_HOP + i] * win[i]; e = fmaf(v, v, e); }
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) e += __shfl_xor(e, o);
+            if (ln == 0) energy[f] = 20.0f * log10f(sqrtf(e) + EPS);
+        }
+    }
+    __syncthreads();
+    if (tid == 0) {
+        float mx = -INFINITY;
+        for (int f = 0; f < nf; ++f) mx = fmaxf(mx, energy[f]);
+        int k = 0;
+        for (int f = 0; f < nf; ++f) if (mx - 40.0f - energy[f] < 0.f) keep_pos[k++] = f;
+        n_keep_s = k;
+    }
+    __syncthreads();
+    const int nk = n_keep_s;
+    const int len2 = nk > 0 ? (nk - 1) * ES_HOP + ES_FRAME : 0;
+    const int nf2 = len2 > ES_FRAME ? (len2 - ES_FRAME + ES_HOP - 1) / ES_HOP : 0;
+    if (nf2 < ES_SEG) { if (tid == 0) p.score[clip] = 1e-5f; return; }
+    for (int s = 0; s < 2; ++s)
+        for (int i = tid; i < len2; i += 1024) {
+            const int j1 = i / ES_HOP, j0 = j1 - 1;
+            float acc = 0.f;
+            if (j0 >= 0 && j0 < nk) { const int o = i - j0 * ES_HOP; acc += rs[s * ESL_MAXLEN + keep_pos[j0] * ES_HOP + o] * win[o]; }
+            if (j1 < nk) { const int o = i - j1 * ES_HOP; acc += rs[s * ESL_MAXLEN + keep_pos[j1] * ES_HOP + o] * win[o]; }
+            oa[s * ESL_MAXLEN + i] = acc;
+        }
+    __threadfence_block();                                             // this block's own global stores, re-read by other waves
+    __syncthreads();
+    // ---- power spectra of the bins the bands use, ESL_CHUNK frames of one signal staged in LDS at a time
+    const int k_lo = p.band_lo[0], k_hi = p.band_hi[ES_BANDS - 1], nkb = k_hi - k_lo;
+    for (int s = 0; s < 2; ++s)
+        for (int f0 = 0; f0 < nf2; f0 += ESL_CHUNK) {
+            const int nfc = nf2 - f0 < ESL_CHUNK ? nf2 - f0 : ESL_CHUNK;
+            for (int i = tid; i < nfc * ES_HOP + ES_HOP; i += 1024) buf[i] = oa[s * ESL_MAXLEN + f0 * ES_HOP + i];      // < len2: (nf2 + 1) hop = len2
+            __syncthreads();
+            for (int item = tid; item < nfc * nkb; item += 1024) {
+                const int f = item / nkb, k = k_lo + item - f * nkb;
+                const float* fr = buf + f * ES_HOP;
+                float re = 0.f, im = 0.f;
+                for (int i = 0; i < ES_FRAME; ++i) {
+                    const float v = fr[i] * win[i];
+                    const float2 w = twd[(k * i) & (ES_NFFT - 1)];
+                    re = fmaf(v, w.x, re); im = fmaf(v, w.y, im);
+                }
+                pw[(s * ESL_MAXFRAMES + f0 + f) * ES_NBIN + k] = re * re + im * im;
+            }
+            __syncthreads();
+        }
+    __threadfence_block();
+    __syncthreads();
+    for (int item = tid; item < 2 * nf2 * ES_BANDS; item += 1024) {
+        const int s = item / (nf2 * ES_BANDS), rem = item - s * nf2 * ES_BANDS, f = rem / ES_BANDS, b = rem - f * ES_BANDS;
+        float a = 0.f;
+        for (int k = p.band_lo[b]; k < p.band_hi[b]; ++k) a += pw[(s * ESL_MAXFRAMES + f) * ES_NBIN + k];
+        tob[s][b][f] = sqrtf(a);
+    }
+    __syncthreads();
+    // ---- segments of 30 frames: row statistics, then column normalisation and the frame's share of the correlation (estoi_kernel)
+    const int nseg = nf2 - ES_SEG + 1;
+    float* rstat = buf;                                                // [2][nseg][15][2]
+    for (int item = tid; item < 2 * nseg * ES_BANDS; item += 1024) {
+        const int s = item / (nseg * ES_BANDS), rem = item - s * nseg * ES_BANDS, seg = rem / ES_BANDS, b = rem - seg * ES_BANDS;
+        float mean = 0.f;
+        for (int i = 0; i < ES_SEG; ++i) mean += tob[s][b][seg + i];
+        mean /= (float)ES_SEG;
+        float nrm = 0.f;
+        for (int i = 0; i < ES_SEG; ++i) { const float v = tob[s][b][seg + i] - mean; nrm = fmaf(v, v, nrm); }
+        rstat[item * 2] = mean; rstat[item * 2 + 1] = 1.0f / (sqrtf(nrm) + EPS);
+    }
+    __syncthreads();
+    float part = 0.f;
+    for (int item = tid; item < nseg * ES_SEG; item += 1024) {
+        const int seg = item / ES_SEG, i = item - seg * ES_SEG;
+        float v[2][ES_BANDS];
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+            float mean = 0.f;
+#pragma unroll
+            for (int b = 0; b < ES_BANDS; ++b) {
+                const float* st = rstat + ((s * nseg + seg) * ES_BANDS + b) * 2;
+                v[s][b] = (tob[s][b][seg + i] - st[0]) * st[1];
+                mean += v[s][b];
+            }
+            mean /= (float)ES_BANDS;
+            float nrm = 0.f;
+#pragma unroll
+            for (int b = 0; b < ES_BANDS; ++b) { v[s][b] -= mean; nrm = fmaf(v[s][b], v[s][b], nrm); }
+            const float inv = 1.0f / (sqrtf(nrm) + EPS);
+#pragma unroll
+            for (int b = 0; b < ES_BANDS; ++b) v[s][b] *= inv;
+        }
+        float c = 0.f;
+#pragma unroll
+        for (int b = 0; b < ES_BANDS; ++b) c = fmaf(v[0][b], v[1][b], c);
+        part += c / (float)ES_SEG;
+    }
+    red[tid] = part;
+    __syncthreads();
+    for (int o = 512; o > 0; o >>= 1) { if (tid < o) red[tid] += red[tid + o]; __syncthreads(); }
+    if (tid == 0) p.score[clip] = red[0] / (float)nseg;
+}
+
 }  // namespace l2s
 
 using namespace l2s;
@@ -530,7 +838,8 @@ int l2s_inverse_mel(const float* mel, int log_input, const float* fb, int fb_nnz
 }
 
 int64_t l2s_griffin_lim_workspace_bytes(int N, int L) {
-    return (int64_t)N * L * GL_LDK * 4 + (int64_t)N * 2 * L * GL_LDK * 8 + 512;
+    const int slots = GL_HOP * (L - 1) <= 30720 ? 2 : 3;      // the long form rotates three rebuilt spectra
+    return (int64_t)N * L * GL_LDK * 4 + (int64_t)N * slots * L * GL_LDK * 8 + 512;
 }
 
 int l2s_griffin_lim(const float* power_spec, const float* init_angles, int N, int L, int n_fft, int hop, int iters, float momentum,
@@ -538,27 +847,40 @@ int l2s_griffin_lim(const float* power_spec, const float* init_angles, int N, in
     L2S_REQUIRE(power_spec && init_angles && wave && ws, "griffin_lim: null argument");
     L2S_REQUIRE(n_fft == GL_NFFT && hop == GL_HOP, "griffin_lim: built for n_fft = win_length = 1024, hop 256 (hparams.py)");
     L2S_REQUIRE(N > 0 && L >= 5 && iters >= 0, "griffin_lim: sizes");
-    L2S_REQUIRE(GL_HOP * (L - 1) <= 30720, "griffin_lim: at most 121 frames per clip (the waveform stays in LDS)");
+    L2S_REQUIRE(N <= 65535 && L <= (1 << 20), "griffin_lim: at most 65 535 clips and 2^20 frames per call");
     L2S_REQUIRE(ws_bytes >= l2s_griffin_lim_workspace_bytes(N, L), "griffin_lim: workspace too small");
     hipStream_t s = (hipStream_t)stream;
     char* w = (char*)(((uintptr_t)ws + 255) / 256 * 256);
-    GriffinP p{power_spec, init_angles, (float*)w, (float2*)(w + (int64_t)N * L * GL_LDK * 4), wave, N, L, iters, momentum / (1.0f + momentum)};
+    float* mag = (float*)w;
+    float2* reb = (float2*)(w + (int64_t)N * L * GL_LDK * 4);
     ProfScope ps("vocoder_griffin_lim", s);
-    if (GL_HOP * (L - 1) <= 19456) hipLaunchKernelGGL((griffin_lim_kernel<12, 19456>), dim3(N), dim3(768), 0, s, p);
-    else hipLaunchKernelGGL((griffin_lim_kernel<8, 30720>), dim3(N), dim3(512), 0, s, p);
+    if (GL_HOP * (L - 1) <= 30720) {
+        GriffinP p{power_spec, init_angles, mag, reb, wave, N, L, iters, momentum / (1.0f + momentum)};
+        if (GL_HOP * (L - 1) <= 19456) hipLaunchKernelGGL((griffin_lim_kernel<12, 19456>), dim3(N), dim3(768), 0, s, p);
+        else hipLaunchKernelGGL((griffin_lim_kernel<8, 30720>), dim3(N), dim3(512), 0, s, p);
+    } else {                                       // 122 frames and more: one launch per iteration over (tile, clip)
+        hipLaunchKernelGGL(griffin_lim_tile_prologue_kernel, dim3((GL_NBIN * L + 255) / 256, N), dim3(256), 0, s, power_spec, init_angles, mag, reb, L);
+        GriffinTileP p{mag, reb, wave, N, L, 0, iters, momentum / (1.0f + momentum)};
+        for (p.it = 0; p.it <= iters; ++p.it)
+            hipLaunchKernelGGL((griffin_lim_tile_kernel<GLT_NW, GLT_F>), dim3((L + GLT_F - 1) / GLT_F, N), dim3(GLT_NW * 64), 0, s, p);
+    }
     L2S_CHECK_HIP(hipGetLastError());
     return 0;
 }
 
 int64_t l2s_estoi_workspace_bytes(int N) { return 512 + 256 + (int64_t)N * 2 * ES_MAXLEN * 4 + (int64_t)N * 2 * ES_MAXFRAMES * ES_NBIN * 4; }
+int64_t l2s_estoi_workspace_bytes_long(int N, int n_resampled) {
+    if (n_resampled <= ES_MAXLEN) return l2s_estoi_workspace_bytes(N);
+    return 512 + 256 + (int64_t)N * 4 * ESL_MAXLEN * 4 + (int64_t)N * 2 * ESL_MAXFRAMES * ES_NBIN * 4;
+}
 
 int l2s_estoi(const float* clean, const float* pred, int N, int n_samples, const float* fir, int n_fir, int up, int down, int n_pre_remove, int n_resampled,
               const int* band_lo_hi_host, float* score, void* ws, int64_t ws_bytes, void* stream) {
     L2S_REQUIRE(clean && pred && score && ws && band_lo_hi_host, "estoi: null argument");
     L2S_REQUIRE(N > 0 && n_samples > 0, "estoi: sizes");
-    L2S_REQUIRE(n_resampled > 0 && n_resampled <= ES_MAXLEN, "estoi: at most 16 512 samples at 10 kHz per clip (the signals stay in LDS)");
+    L2S_REQUIRE(n_resampled > 0 && n_resampled <= ESL_MAXLEN, "estoi: at most 48 256 samples at 10 kHz per clip (4.8 s)");
     L2S_REQUIRE(fir ? (n_fir > 0 && up > 0 && down > 0 && n_pre_remove >= 0) : n_resampled == n_samples, "estoi: resampler arguments");
-    L2S_REQUIRE(ws_bytes >= l2s_estoi_workspace_bytes(N), "estoi: workspace too small");
+    L2S_REQUIRE(ws_bytes >= l2s_estoi_workspace_bytes_long(N, n_resampled), "estoi: workspace too small");
     for (int b = 0; b < ES_BANDS; ++b)
         L2S_REQUIRE(band_lo_hi_host[b] >= 0 && band_lo_hi_host[b] <= band_lo_hi_host[ES_BANDS + b] && band_lo_hi_host[ES_BANDS + b] <= ES_NBIN &&
                     (b == 0 || band_lo_hi_host[b] >= band_lo_hi_host[b - 1]), "estoi: band edges");
@@ -566,11 +888,20 @@ int l2s_estoi(const float* clean, const float* pred, int N, int n_samples, const
     char* w = (char*)(((uintptr_t)ws + 255) / 256 * 256);
     int* bands = (int*)w;
     float* rs = (float*)(w + 256);
-    float* pw = rs + (int64_t)N * 2 * ES_MAXLEN;
     L2S_CHECK_HIP(hipMemcpyAsync(bands, band_lo_hi_host, 2 * ES_BANDS * sizeof(int), hipMemcpyHostToDevice, s));
-    EstoiP p{clean, pred, fir, bands, bands + ES_BANDS, rs, pw, score, N, n_samples, n_fir, up, down, n_pre_remove, n_resampled};
     ProfScope ps("metric_estoi", s);
-    hipLaunchKernelGGL(estoi_kernel, dim3(N), dim3(1024), 0, s, p);
+    if (n_resampled <= ES_MAXLEN) {
+        float* pw = rs + (int64_t)N * 2 * ES_MAXLEN;
+        EstoiP p{clean, pred, fir, bands, bands + ES_BANDS, rs, pw, score, N, n_samples, n_fir, up, down, n_pre_remove, n_resampled};
+        hipLaunchKernelGGL(estoi_kernel, dim3(N), dim3(1024), 0, s, p);
+    } else {                                       // the long form: the signals in the workspace, the resampler a kernel of its own
+        L2S_REQUIRE(N <= 65535, "estoi: at most 65 535 clips per call");
+        float* oa = rs + (int64_t)N * 2 * ESL_MAXLEN;
+        float* pw = oa + (int64_t)N * 2 * ESL_MAXLEN;
+        EstoiLongP p{clean, pred, fir, bands, bands + ES_BANDS, rs, oa, pw, score, N, n_samples, n_fir, up, down, n_pre_remove, n_resampled};
+        hipLaunchKernelGGL(estoi_resample_kernel, dim3((n_resampled + 255) / 256, 2, N), dim3(256), 0, s, p);
+        hipLaunchKernelGGL(estoi_long_kernel, dim3(N), dim3(1024), 0, s, p);
+    }
     L2S_CHECK_HIP(hipGetLastError());
     return 0;
 }

@@ -93,9 +93,10 @@ class MelSpec2Audio(torch.nn.Module):
 
     def __init__(self, hparams=None, max_iters: int = 256, backend: str = "auto"):
         """`backend`: "hip" = the fused device kernels behind `l2s_inverse_mel` / `l2s_griffin_lim` (vocoder.hip: one wave per mel frame for
-        the SGD, one block per clip with the waveform in LDS and wave-level FFTs for Griffin-Lim); "torch" = the same algorithms as ~5 000
-        torch launches per call (the restatement the kernels are tested against); "auto" = "hip" for device tensors of a supported shape
-        (n_fft = win = 1024, hop 256, at most 121 frames per clip), else "torch".  Both draw the same random start iterates in the same order."""
+        the SGD; wave-level FFTs for Griffin-Lim: one block per clip with the waveform in LDS up to 121 frames, one launch per iteration over
+        tiles of frames above); "torch" = the same algorithms as ~5 000 torch launches per call (the restatement the kernels are tested
+        against); "auto" = "hip" for device tensors of a supported shape (n_fft = win = 1024, hop 256, at least 5 frames per clip), else
+        "torch".  Both draw the same random start iterates in the same order."""
         super().__init__()
         hp = hparams or create_hparams()
         self.n_fft, self.hop, self.win, self.sr = hp.filter_length, hp.hop_length, hp.win_length, hp.sampling_rate
@@ -106,9 +107,9 @@ class MelSpec2Audio(torch.nn.Module):
         self.fb_nnz = int((self.fb != 0).sum())
 
     def _use_hip(self, t: torch.Tensor, L: int) -> bool:
-        ok = t.is_cuda and self.n_fft == 1024 and self.win == 1024 and self.hop == 256 and 5 <= L <= 121 and self.fb_nnz <= 2048
+        ok = t.is_cuda and self.n_fft == 1024 and self.win == 1024 and self.hop == 256 and L >= 5 and self.fb_nnz <= 2048
         if self.backend == "hip" and not ok:
-            raise RuntimeError("MelSpec2Audio(backend='hip'): needs device tensors, n_fft = win = 1024, hop 256 and 5..121 frames per clip")
+            raise RuntimeError("MelSpec2Audio(backend='hip'): needs device tensors, n_fft = win = 1024, hop 256 and at least 5 frames per clip")
         return ok and self.backend in ("auto", "hip")
 
     # -- torchaudio.transforms.InverseMelScale.forward (0.9.0)

@@ -35,7 +35,7 @@ ABI_SYMBOLS = (
     "l2s_ragged_plan", "l2s_workspace_bytes_ragged", "l2s_inference_ragged",
     "l2s_output_lengths", "l2s_inference", "l2s_inference_multi", "l2s_workspace_bytes_multi", "l2s_forward_eval", "l2s_forward_eval_multi", "l2s_model_set_option", "l2s_persist_available", "l2s_persist_timeouts", "l2s_set_thread_chains", "l2s_speaker_workspace_bytes", "l2s_speaker_encoder_fwd",
     "l2s_face_workspace_bytes", "l2s_face_encoder_fwd",
-    "l2s_inverse_mel_workspace_bytes", "l2s_inverse_mel", "l2s_griffin_lim_workspace_bytes", "l2s_griffin_lim", "l2s_estoi_workspace_bytes", "l2s_estoi",
+    "l2s_inverse_mel_workspace_bytes", "l2s_inverse_mel", "l2s_griffin_lim_workspace_bytes", "l2s_griffin_lim", "l2s_estoi_workspace_bytes", "l2s_estoi_workspace_bytes_long", "l2s_estoi",
     "l2s_set_option",
     "l2s_train_scratch_bytes", "l2s_loss", "l2s_grad_norm", "l2s_adamw_amsgrad_step",
     "l2s_train_steps_tape_floats", "l2s_train_steps_weights_floats", "l2s_train_steps_ws_bytes", "l2s_train_steps_pack_weights",
@@ -175,6 +175,10 @@ def _bind(L: ctypes.CDLL) -> None:
     L.l2s_estoi_workspace_bytes.argtypes = [_i]
     L.l2s_estoi_workspace_bytes.restype = _i64
     L.l2s_estoi.argtypes = [_fp, _fp, _i, _i, _fp, _i, _i, _i, _i, _i, ctypes.POINTER(ctypes.c_int), _fp, _vp, _i64, _vp]
+    # the long forms of the vocoder and the metric (include/l2s.h): the workspace query is absent from a library built before them
+    if hasattr(L, "l2s_estoi_workspace_bytes_long"):
+        L.l2s_estoi_workspace_bytes_long.argtypes = [_i, _i]
+        L.l2s_estoi_workspace_bytes_long.restype = _i64
     L.l2s_profile_enable.argtypes = [_i]
     L.l2s_profile_get.argtypes = [_i, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(_i64), ctypes.POINTER(ctypes.c_double)]
     # per-clip video lengths: the unmasked signature plus the host length array.  A library of the same ABI version built before these entry points
@@ -1045,6 +1049,12 @@ def inverse_mel(mel: torch.Tensor, fb: torch.Tensor, fb_nnz: int, init: torch.Te
     return (spec, loss, ran) if want_loss else spec
 
 
+GRIFFIN_LIM_SHORT_FRAMES = 121     # l2s_griffin_lim: up to here one launch with the waveform in LDS; above, one launch per iteration over tiles of
+GRIFFIN_LIM_TILE_FRAMES = 24       # this many frames (GLT_F in csrc/vocoder.hip)
+ESTOI_SHORT_SAMPLES = 16512        # l2s_estoi at 10 kHz: up to here both signals in LDS; above, up to
+ESTOI_MAX_SAMPLES = 48256          # this many, in the workspace (ESL_MAXLEN in csrc/vocoder.hip)
+
+
 def griffin_lim(power_spec: torch.Tensor, init_angles: torch.Tensor, iters: int, n_fft: int = 1024, hop: int = 256, momentum: float = 0.99) -> torch.Tensor:
     """`l2s_griffin_lim`: power_spec (N, n_fft/2+1, L), init_angles complex (N, n_fft/2+1, L) or float (..., 2) -> wave (N, hop*(L-1))."""
     power_spec = _f32(power_spec)
@@ -1067,7 +1077,8 @@ def estoi(clean: torch.Tensor, pred: torch.Tensor, fir: Optional[torch.Tensor], 
     assert pred.shape == clean.shape
     L = lib()
     bands = (ctypes.c_int * 30)(*[int(v) for v in band_lo_hi])
-    ws = torch.empty(int(L.l2s_estoi_workspace_bytes(N)), dtype=torch.uint8, device=clean.device)
+    ws_bytes = L.l2s_estoi_workspace_bytes_long(N, n_resampled) if hasattr(L, "l2s_estoi_workspace_bytes_long") else L.l2s_estoi_workspace_bytes(N)
+    ws = torch.empty(int(ws_bytes), dtype=torch.uint8, device=clean.device)
     score = torch.empty(N, dtype=torch.float32, device=clean.device)
     check(L.l2s_estoi(clean.data_ptr(), pred.data_ptr(), N, n, _ptr(fir), 0 if fir is None else fir.numel(), up, down, n_pre_remove, n_resampled,
                       bands, score.data_ptr(), ws.data_ptr(), ws.numel(), _stream()))
