@@ -4,27 +4,64 @@
 // dense kernels of this path top out at 157 TFLOP/s (gemm_nt.hip reaches 119).  Every fp32 value is EXACTLY the sum of three bf16 values,
 //      x = hi + mid + lo,   hi = x with the low 16 significand bits cleared,  mid = (x - hi) likewise,  lo = x - hi - mid
 // (each difference is exact in fp32, and the last remainder has <= 8 significant bits), and a product of two bf16 values is exact in the
-// fp32 accumulator of v_mfma_f32_32x32x16_bf16.  Of the nine partial products of x*y the six with weight >= 2^-16 are kept,
+// fp32 accumulator of v_mfma_f32_16x16x32_bf16.  Of the nine partial products of x*y the six with weight >= 2^-16 are kept,
 //      x*y ~= hi*hi + hi*mid + mid*hi + mid*mid + hi*lo + lo*hi          (dropped: mid*lo + lo*mid + lo*lo <= 2^-22 |x*y|),
-// six bf16 MFMAs for one K step of 16 where the f32 form needs eight MFMAs of K = 2 at 16x the cost each: 6/16 of the f32 matrix time.
+// six bf16 MFMAs for 32 k of a 16x16 tile where the f32 form needs eight MFMAs of K = 4 at 16x the cost per FLOP: 6/16 of the f32 matrix time.
 // Accumulation is fp32 inside the MFMA as before; results differ from the f32-MFMA kernel by rounding-level amounts (tests/: measured
 // against an fp64 product next to the f32 kernel's own error).
 //
-// Block = 512 threads = 4 MFMA waves (2x2, each 64x64 = 2x2 tiles of 32x32, 64 accumulator registers) + 4 staging waves, block tile
-// 128(M) x 128(N) x 32(K).  Operands are fetched as fp32 float4 by range-checked buffer loads (the implicit-Conv1d addressing of
-// gemm_nt.hip), split while they are staged into LDS - three bf16 planes per operand, rows of 80 bytes (64 + 16 pad: conflict-free
-// ds_read_b128 for the 32x32x16 operand layout: lane l reads the 8 consecutive k of row l&31 at k offset 8*(l>>5)) - so a value is split once
-// per block that uses it and every ds_read_b128 is one MFMA operand.  Two LDS stages (120 KB, one block per CU).
+// MFMA shape: both tiles run on v_mfma_f32_16x16x32_bf16 (a wave's 64x64 output = 4x4 tiles of 16x16, 64 accumulator registers, 96 MFMAs of
+// 16 clk per 32 k - the matrix cycles, the LDS bytes and the accumulators of the 32x32x16 form they ran on before; the hardware notes measured a
+// higher sustained clock on this shape).  Operand layout: lane l carries row / column l & 15 and the 8 consecutive k from 8 * (l >> 4); D layout:
+// column l & 15, row 4 * (l >> 4) + r.  One accumulation is therefore 32 k wide, aligned to 32 from k = 0, in every form of the kernel - which is
+// what keeps the tiles' results bit-identical to each other; a half step past K is exact zeros.
+//
+// Block = 512 threads = 4 MFMA waves (2x2, each 64x64) + 4 staging waves, block tile 128(M) x 128(N) x 32(K).  Operands are fetched as fp32
+// float4 by range-checked buffer loads (the implicit-Conv1d addressing of gemm_nt.hip), split while they are staged into LDS - three bf16
+// planes per operand, rows of 64 bytes without padding; the 16-byte chunk c of row r sits at chunk c ^ (r & 8 ? 3 : 0), which makes the
+// ds_read_b128 lane groups of the 16x16x32 operand layout (16 rows x 4 chunks per read) conflict-free and leaves a staged row contiguous - so a
+// value is split once per block that uses it and every ds_read_b128 is one MFMA operand.  Two LDS stages (96 KB, one block per CU).
 #include "l2s_common.h"
 #include "gemm_dev.h"
 
 namespace l2s {
 
 constexpr int XM = 128, XN = 128, XK = 32;
-constexpr int XLDB = 80;                         // bytes per LDS row (32 bf16 + pad)
+constexpr int XLDB = 64;                         // bytes per LDS row (32 bf16, chunks swizzled)
 constexpr int XPLANE = XM * XLDB;                // bytes per plane (128 rows)
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+
+// The MFMA waves' K step, shared by both tiles: a wave holds the step's four A row tiles (x 3 planes, 48 registers) and streams the four B
+// column tiles through two buffers (2 x 12 registers) - with the 64 accumulators 136 registers.  Needs in scope: F3 fa[4], fb0, fb1; f32x4
+// acc[4][4]; read_a(F3&, stage byte offset, row tile), read_b(F3&, stage byte offset, column tile).  Per output element: K steps ascending, the
+// six terms smallest first (l*h, h*l, m*m, m*h, h*m, h*h).  MFMAs on one accumulator never follow each other directly (two or four row tiles
+// alternate).  Every LDS read is issued behind the first MFMAs of a block (right behind the barrier the matrix pipe is empty) and has at least
+// 12 MFMAs (192 clk) to land: column tile j + 1 is read under tile j's MFMAs; the barrier sits in front of the last column tile, under which the
+// next stage's first column tile and its row tiles are read - pair (0, 1) as soon as this step is done with it, pair (2, 3) at the end, which is
+// why a step's first block runs pair by pair as well.
+struct F3 { bf16x8 h, m, l; };
+#define L2S_X3_MFMA(A_, B_, C_) C_ = __builtin_amdgcn_mfma_f32_16x16x32_bf16(A_, B_, C_, 0, 0, 0);
+#define L2S_X3_TERM2(PA_, PB_, FB_, J_, T_) L2S_X3_MFMA(fa[T_].PA_, FB_.PB_, acc[T_][J_]) L2S_X3_MFMA(fa[(T_) + 1].PA_, FB_.PB_, acc[(T_) + 1][J_])
+#define L2S_X3_TAIL2(FB_, J_, T_) L2S_X3_TERM2(h, l, FB_, J_, T_) L2S_X3_TERM2(m, m, FB_, J_, T_) L2S_X3_TERM2(m, h, FB_, J_, T_) L2S_X3_TERM2(h, m, FB_, J_, T_) L2S_X3_TERM2(h, h, FB_, J_, T_)
+#define L2S_X3_ALL2(FB_, J_, T_) L2S_X3_TERM2(l, h, FB_, J_, T_) L2S_X3_TAIL2(FB_, J_, T_)
+#define L2S_X3_TERM4(PA_, PB_, FB_, J_) L2S_X3_TERM2(PA_, PB_, FB_, J_, 0) L2S_X3_TERM2(PA_, PB_, FB_, J_, 2)
+#define L2S_X3_TAIL4(FB_, J_) L2S_X3_TERM4(h, l, FB_, J_) L2S_X3_TERM4(m, m, FB_, J_) L2S_X3_TERM4(m, h, FB_, J_) L2S_X3_TERM4(h, m, FB_, J_) L2S_X3_TERM4(h, h, FB_, J_)
+#define L2S_X3_FENCE __builtin_amdgcn_sched_barrier(0);
+// SO_: byte offset of the stage this step multiplies, SN_: of the other one (past the last step its reads are unused)
+#define L2S_X3_STEP(KS_, SO_, SN_)                                                                                                 \
+        X3_STAMP(KS_, 0);                                                                                                          \
+        L2S_X3_TERM2(l, h, fb0, 0, 0) L2S_X3_FENCE read_b(fb1, SO_, 1); L2S_X3_FENCE L2S_X3_TAIL2(fb0, 0, 0) L2S_X3_FENCE L2S_X3_ALL2(fb0, 0, 2) L2S_X3_FENCE \
+        L2S_X3_TERM4(l, h, fb1, 1) L2S_X3_FENCE read_b(fb0, SO_, 2); L2S_X3_FENCE L2S_X3_TAIL4(fb1, 1) L2S_X3_FENCE               \
+        L2S_X3_TERM4(l, h, fb0, 2) L2S_X3_FENCE read_b(fb1, SO_, 3); L2S_X3_FENCE L2S_X3_TAIL4(fb0, 2) L2S_X3_FENCE               \
+        X3_STAMP(KS_, 1);                                                                                                          \
+        __syncthreads();              /* this stage is read (fb1 has landed: the barrier waits for it); the other one is written */ \
+        X3_STAMP(KS_, 2);                                                                                                          \
+        L2S_X3_TERM2(l, h, fb1, 3, 0) L2S_X3_FENCE read_b(fb0, SN_, 0); L2S_X3_FENCE L2S_X3_TAIL2(fb1, 3, 0) L2S_X3_FENCE          \
+        read_a(fa[0], SN_, 0); read_a(fa[1], SN_, 1); L2S_X3_FENCE                                                                 \
+        L2S_X3_ALL2(fb1, 3, 2) L2S_X3_FENCE                                                                                        \
+        read_a(fa[2], SN_, 2); read_a(fa[3], SN_, 3); L2S_X3_FENCE                                                                 \
+        X3_STAMP(KS_, 3);
 
 struct X3Split { uint2 hi, mid, lo; };           // 4 consecutive k as bf16 pairs
 
@@ -81,23 +118,20 @@ __global__ __launch_bounds__(512, 2) void gemm_x3_kernel(const GemmBatch batch, 
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
     const int nkt = (p.K + XK - 1) / XK;
     const int wm = (wave >> 1) & 1, wn = wave & 1;
-    const int li = lane & 31, lg = lane >> 5;
+    const int li = lane & 15, lg = lane >> 4;
 
-    f32x16 acc[2][2];
+    f32x4 acc[4][4];                                          // [row tile][column tile] of the wave's 64x64
 #pragma unroll
-    for (int i = 0; i < 2; ++i)
+    for (int i = 0; i < 4; ++i)
 #pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+        for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
     if (wave >= 4) {
         // ------------------------------------------------------------------------------------------------ producers
         const int pt = tid - 256;
-        // staging role: 8 lanes per row (32 k); the two rows of a 16-lane ds_write group are 4 apart - with 80-byte rows their 16-dword
-        // spans then fall on disjoint halves of the 32 banks a ds_write_b64 sees (consecutive rows overlap in 4 banks)
-        const int oct = pt >> 3;
-        const int lr = (oct & ~7) + ((oct & 1) << 2) + ((oct & 7) >> 1), kq = (pt & 7) * 4;
+        // staging role: 8 lanes per row (32 k); the two rows of a 16-lane ds_write group are consecutive: 128 contiguous bytes, all 32 banks a
+        // ds_write_b64 sees (the chunk swizzle permutes inside a row)
+        const int lr = pt >> 3, kq = (pt & 7) * 4;
         bool avalid[4], wvalid[4];
         int atbase[4];
         unsigned arow_off[4];                                // float offset of the row's sequence inside A
@@ -147,7 +181,8 @@ __global__ __launch_bounds__(512, 2) void gemm_x3_kernel(const GemmBatch batch, 
 #pragma unroll
             for (int j = 0; j < 4; ++j) woff[j] += wvalid[j] ? XK * 4u : 0u;
         };
-        const int st_off = lr * XLDB + kq * 2;                              // byte offset of this thread's first staged row inside a plane
+        // byte offset of this thread's first staged row inside a plane; rows lr + 32 j share the swizzle bit
+        const int st_off = lr * XLDB + (((kq >> 3) ^ ((lr & 8) ? 3 : 0)) * 16) + (kq & 4) * 2;
         auto stage = [&](const float4* ra, const float4* rb, int st, int kt_stamp) {
             unsigned char* base = smem + st * STAGE + st_off;
             if constexpr (TIMED) {                           // measurement build: all splits, stamp, all stores, stamp
@@ -211,54 +246,34 @@ __global__ __launch_bounds__(512, 2) void gemm_x3_kernel(const GemmBatch batch, 
         }
     } else {
         // ------------------------------------------------------------------------------------------------ consumers
-        // Operand fragments are double-buffered in registers: the ds_read_b128s of the next K step (or of the next tile's first step, right
-        // after the barrier) are in flight while the 24 MFMAs of the current one issue, so the matrix pipe never waits for LDS.
-        const unsigned char* a_rd = smem + (wm * 64 + li) * XLDB + lg * 16;               // this lane's operand rows: + i*32 rows, + s*32 bytes, + plane
-        const unsigned char* b_rd = smem + 3 * XPLANE + (wn * 64 + li) * XLDB + lg * 16;
-        struct Frags { bf16x8 ah[2], am[2], al[2], bh[2], bm[2], bl[2]; };
-        auto read_frags = [&](Frags& f, int so, int st) {
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                const unsigned char* ap = a_rd + so + i * 32 * XLDB + st * 32;
-                const unsigned char* bp = b_rd + so + i * 32 * XLDB + st * 32;
-                f.ah[i] = *reinterpret_cast<const bf16x8*>(ap); f.am[i] = *reinterpret_cast<const bf16x8*>(ap + XPLANE); f.al[i] = *reinterpret_cast<const bf16x8*>(ap + 2 * XPLANE);
-                f.bh[i] = *reinterpret_cast<const bf16x8*>(bp); f.bm[i] = *reinterpret_cast<const bf16x8*>(bp + XPLANE); f.bl[i] = *reinterpret_cast<const bf16x8*>(bp + 2 * XPLANE);
-            }
+        // this lane's operand rows (see L2S_X3_STEP): + t * 16 rows, + plane
+        const int swz = ((lg ^ ((li & 8) ? 3 : 0)) * 16);
+        const unsigned char* a_rd = smem + (wm * 64 + li) * XLDB + swz;
+        const unsigned char* b_rd = smem + 3 * XPLANE + (wn * 64 + li) * XLDB + swz;
+        auto read_a = [&](F3& f, int so, int t) {
+            const unsigned char* ap = a_rd + so + t * 16 * XLDB;
+            f.h = *reinterpret_cast<const bf16x8*>(ap); f.m = *reinterpret_cast<const bf16x8*>(ap + XPLANE); f.l = *reinterpret_cast<const bf16x8*>(ap + 2 * XPLANE);
         };
-        // smallest partial products first; the four accumulators interleave so that no MFMA waits on its predecessor
-#define L2S_X3_TERM(A_, B_)                                                                           \
-        acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A_[0], B_[0], acc[0][0], 0, 0, 0);     \
-        acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A_[0], B_[1], acc[0][1], 0, 0, 0);     \
-        acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A_[1], B_[0], acc[1][0], 0, 0, 0);     \
-        acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A_[1], B_[1], acc[1][1], 0, 0, 0);
-#define L2S_X3_MMA(F_) { L2S_X3_TERM(F_.al, F_.bh) L2S_X3_TERM(F_.ah, F_.bl) L2S_X3_TERM(F_.am, F_.bm) L2S_X3_TERM(F_.am, F_.bh) L2S_X3_TERM(F_.ah, F_.bm) L2S_X3_TERM(F_.ah, F_.bh) }
-        Frags f0, f1;
+        auto read_b = [&](F3& f, int so, int j) {
+            const unsigned char* bp = b_rd + so + j * 16 * XLDB;
+            f.h = *reinterpret_cast<const bf16x8*>(bp); f.m = *reinterpret_cast<const bf16x8*>(bp + XPLANE); f.l = *reinterpret_cast<const bf16x8*>(bp + 2 * XPLANE);
+        };
+        F3 fa[4], fb0, fb1;
         __syncthreads();                                     // stage 0 ready
-        read_frags(f0, 0, 0);
-        for (int kt = 0; kt < nkt; ++kt) {
-            const int so = (kt & 1) * STAGE;
-            X3_STAMP(kt, 0);
-            read_frags(f1, so, 1);
-            __builtin_amdgcn_sched_barrier(0);
-            L2S_X3_MMA(f0)
-            __builtin_amdgcn_sched_barrier(0);
-            X3_STAMP(kt, 1);                                 // the 24 MFMAs of step 0 are issued (not necessarily retired)
-            __syncthreads();                                 // this stage is read (f1 has landed: the barrier waits for it); the other one is written
-            X3_STAMP(kt, 2);
-            if (kt + 1 < nkt) read_frags(f0, STAGE - so, 0);
-            __builtin_amdgcn_sched_barrier(0);
-            L2S_X3_MMA(f1)
-            __builtin_amdgcn_sched_barrier(0);
-            X3_STAMP(kt, 3);
+        // in the order the loop's back edge leaves them in (the wait in front of a step's first MFMA is the stricter of the two edges')
+        read_b(fb0, 0, 0); L2S_X3_FENCE read_a(fa[0], 0, 0); read_a(fa[1], 0, 1); L2S_X3_FENCE read_a(fa[2], 0, 2); read_a(fa[3], 0, 3); L2S_X3_FENCE
+        int kt = 0;
+        for (; kt + 1 < nkt; kt += 2) {                      // pairs of tiles: no exit from the middle of the body (the accumulators would be copied at it)
+            L2S_X3_STEP(kt, 0, STAGE)
+            L2S_X3_STEP(kt + 1, STAGE, 0)
         }
-#undef L2S_X3_MMA
-#undef L2S_X3_TERM
+        if (kt < nkt) { L2S_X3_STEP(kt, 0, STAGE) }
     }
 
     // epilogue.  The accumulators leave through LDS, half a tile (the 32-row sub-tiles i of both wave rows = 64 rows x 128 columns, 32 KB)
     // at a time: every accumulator element is addressed with compile-time indices (a rolled loop over them would put all 64 in scratch
     // memory), the rolled store loop that follows - all eight waves - reads LDS, runs the fused epilogue once per element and writes rows
-    // of 128 consecutive columns.  C/D layout of a 32x32 tile: col = lane&31, row = (r&3) + 8*(r>>2) + 4*(lane>>5).
+    // of 128 consecutive columns.  C/D layout of a 16x16 tile: col = lane&15, row = 4*(lane>>4) + r.
     constexpr int CTLD = XN + 1;                               // odd pitch: rows and columns of the tile are both conflict-free to walk
     float* const ct = reinterpret_cast<float*>(smem);          // [64][129]; the operand stages are dead (barrier at the loop end)
     const GemmP pl = p;                                        // epilogue parameters in SGPRs: through the kernarg reference the rolled loop
@@ -268,10 +283,12 @@ __global__ __launch_bounds__(512, 2) void gemm_x3_kernel(const GemmBatch batch, 
         if (i) __syncthreads();
         if (wave < 4) {
 #pragma unroll
-            for (int j = 0; j < 2; ++j)
+            for (int t = 0; t < 2; ++t)
 #pragma unroll
-                for (int r = 0; r < 16; ++r)
-                    ct[(wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * lg) * CTLD + wn * 64 + j * 32 + li] = acc[i][j][r];
+                for (int j = 0; j < 4; ++j)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r)
+                        ct[(wm * 32 + t * 16 + 4 * lg + r) * CTLD + wn * 64 + j * 16 + li] = acc[2 * i + t][j][r];
         }
         __syncthreads();
         if (pl.c_tr_T > 0) {
@@ -299,26 +316,27 @@ __global__ __launch_bounds__(512, 2) void gemm_x3_kernel(const GemmBatch batch, 
     }
 }
 
-// ------------------------------------------------------------------------------------------------ wide tile: 128(M) x 256(N) x 16(K)
+// ------------------------------------------------------------------------------------------------ wide tile: 128(M) x 256(N) x 32(K)
 // What the stamped build of the kernel above showed (tools/gemm_x3_timeline.py, profiles/r03_gemm_x3_timeline.txt): per K tile of 32 the four MFMA
 // waves are busy ~1 950 clk (1 536 of matrix time) and the four staging waves ~2 430 - 540 to issue the next fetch, 240 of split VALU and **1 510 clk
 // for their 24 ds_write_b64**: the LDS STORE path (VGPR -> LDS, 2 clk per source dword per instruction, MI355X_MICROARCH.md section LDS) moves the
 // tile's 48 KB of planes at 32 B/clk and that, not the operand fetch, sets the pace.  A 128x128 tile needs 32 B of LDS fill per clk of MFMA time;
 // this one needs 24.  Block = 768 threads: EIGHT MFMA waves (2 x 4, two per SIMD, each 64x64 exactly as above: the pipe of a SIMD stays fed while
-// one of its two waves waits) + the same four staging waves; a stage is ONE K step (rows of 48 bytes = 16 bf16 + pad: conflict-free for the
-// ds_read_b128 lane groups), 2 x 54 KB of LDS.  A step runs as two column halves so that every LDS read has MFMAs to hide behind: B half 1 is read
-// while half 0's 12 MFMAs issue, the barrier sits between the halves, and the next step's A (into its second register set) and B half 0 are read
-// while half 1's MFMAs issue - 136 registers of accumulators and fragments, three waves per SIMD.  Per output element the accumulation order is the
-// narrow kernel's (K steps ascending, the six terms in the same order): bit-identical results.
-constexpr int WM = 128, WN = 256, WK = 16;
-constexpr int WLDB = 48;                         // bytes per LDS row (16 bf16 + pad)
-constexpr int WPA = WM * WLDB, WPB = WN * WLDB;  // bytes per plane
-constexpr int WSTAGE = 3 * WPA + 3 * WPB;        // 55 296
+// one of its two waves waits) + the same four staging waves.
+// Staging stays at 16-k granularity - a HALF step is one tap and one side of the A split for every thread, whatever Cin and a_split are modulo 32
+// (post-net layer 0: Cin = 80) - and a K step of 32 is a PAIR of resident half stages: [half][A planes, B planes][row][16 k], rows of 32 bytes
+// without padding (conflict-free as they are for the ds_read_b128 lane groups of the 16x16x32 operand layout: lanes 0-31 read chunks 0 / 1 of the
+// first half stage, lanes 32-63 of the second).  Two pairs = four half stages of 36 864 bytes, 144 KB of LDS, one block per CU; a pair is
+// published by ONE barrier.  With K an odd multiple of 16 the last pair's second half is staged as zeros (the buffer loads' range check; the
+// weight planes are zero-filled to a multiple of 32 k).  The MFMA waves run L2S_X3_STEP, the narrow kernel's: bit-identical results.
+constexpr int WM = 128, WN = 256, WK = 16;       // WK: the staging (half) step
+constexpr int WLDB = 32;                         // bytes per LDS row (16 bf16)
+constexpr int WPA = WM * WLDB, WPB = WN * WLDB;  // bytes per plane: 4 096, 8 192
+constexpr int WHSTG = 3 * WPA + 3 * WPB;         // a half stage: 36 864
+constexpr int WSTAGE = 2 * WHSTG;                // a stage (32 k): 73 728
 constexpr int WTHREADS = 768;
-// with the weight operand by LDS-DMA from pre-split planes (GemmP::W3): B rows of 32 bytes, no pad - the DMA's per-lane source address swaps the two
-// 16-byte halves of rows 8-15 (mod 16), which makes the consumers' ds_read_b128 lane groups conflict-free without it
-constexpr int WLDBD = 32, WPBD = WN * WLDBD;     // 8 192 bytes per plane
-constexpr int WSTAGED = 3 * WPA + 3 * WPBD;      // 43 008
+
+int64_t gemm_planes_bytes(int N, int K) { return (int64_t)N * ((K + 31) / 32 * 32) * 6; }
 
 template <bool TIMED, bool DMAW>
 __global__ __launch_bounds__(WTHREADS) void gemm_x3w_kernel(const GemmBatch batch, unsigned long long* __restrict__ ts, int stamp_block) {
@@ -336,13 +354,13 @@ __global__ __launch_bounds__(WTHREADS) void gemm_x3w_kernel(const GemmBatch batc
     const int m0 = by * WM, n0 = bx * WN;
     if (m0 >= p.M || n0 >= p.N) return;
 
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];      // 2 stages x {A planes, B planes}
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];      // 4 half stages x {A planes, B planes}
     const int tid = threadIdx.x;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
-    const int nks = (p.K + WK - 1) / WK;
+    const int nhs = p.K / WK;                        // half steps (K is a multiple of 16: launch check)
+    const int nks = (nhs + 1) / 2;                   // K steps of 32
     const int wm = (wave >> 2) & 1, wn = wave & 3;
-    const int li = lane & 31, lg = lane >> 5;
-    constexpr int STG = DMAW ? WSTAGED : WSTAGE;     // bytes per stage
+    const int li = lane & 15, lg = lane >> 4;
 
     // the accumulators leave through LDS, one 32-row sub-tile of both wave rows (64 rows x 256 columns, 64 KB) at a time; all twelve waves run
     // the fused epilogue over it (rows of 256 consecutive columns).  The accumulators are declared in the consumer branch only: live across the
@@ -365,9 +383,8 @@ __global__ __launch_bounds__(WTHREADS) void gemm_x3w_kernel(const GemmBatch batc
     if (wave >= 8) {
         // ------------------------------------------------------------------------------------------------ producers
         const int pt = tid - 512;
-        // 4 lanes per row (16 k); the four rows of a 16-lane ds_write group are 2 apart: with 48-byte rows their 8-dword spans tile the 32 banks
-        const int slot = pt >> 2;
-        const int lr = (slot & ~7) + ((slot & 3) << 1) + ((slot >> 2) & 1), kq = (pt & 3) * 4;
+        // 4 lanes per row (16 k); the four rows of a 16-lane ds_write group are consecutive: 128 contiguous bytes, all 32 banks
+        const int lr = pt >> 2, kq = (pt & 3) * 4;
         bool avalid[2];
         int atbase[2];
         unsigned arow_off[2];
@@ -375,7 +392,7 @@ __global__ __launch_bounds__(WTHREADS) void gemm_x3w_kernel(const GemmBatch batc
         asm volatile("" ::"s"(lp.K), "s"(lp.Cin), "s"(lp.taps), "s"(lp.Tin), "s"(lp.lda), "s"(lp.a_split), "s"(lp.a_gap));
         const int ldw = p.ldw ? p.ldw : lp.K;
         constexpr unsigned OOB = 0x80000000u;
-        // Addressing with the K position kept UNIFORM (scalar registers): a step's 16 k are one tap and one side of the A split for every thread
+        // Addressing with the K position kept UNIFORM (scalar registers): a half step's 16 k are one tap and one side of the A split for every thread
         // (launch checks: Cin and a_split multiples of 16), so the per-step advance is scalar arithmetic, the column offset travels in the buffer
         // instruction's scalar offset, and the per-thread part - row base + kq - only changes when the tap does (a uniform branch).  The first form
         // (per-thread ci / tap, offsets rebuilt per load) cost the staging waves 580 clk of address VALU per step beside two MFMA waves per SIMD.
@@ -396,21 +413,27 @@ __global__ __launch_bounds__(WTHREADS) void gemm_x3w_kernel(const GemmBatch batc
                 wfix[j] = n < p.N ? (unsigned)((int64_t)n * ldw + kq) * 4u : OOB;
             }
         }
-        int kb = 0, tap = 0, cib = 0;                        // uniform: first k of the step being requested, its tap, its first channel
+        int hs_req = 0, kb = 0, tap = 0, cib = 0;            // uniform: the half step being requested, its first k, its tap, its first channel
         const int nseq = (p.M + p.Tout - 1) / p.Tout;
-        const __amdgpu_buffer_rsrc_t ra_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.A), 0, (int)((int64_t)nseq * lp.Tin * lp.lda * 4), 0x00020000);
-        const __amdgpu_buffer_rsrc_t rw_rs = DMAW ? __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.W3), 0, (int)((int64_t)p.N * lp.K * 6), 0x00020000)
-                                                  : __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.W), 0, (int)((int64_t)p.N * ldw * 4), 0x00020000);
-        // LDS-DMA of the weight planes of K step `ks` into stage `st`: 3 planes x 256 rows x 32 bytes = 24 contiguous 1-KB pieces (a piece = 32 rows of
-        // one plane), six per staging wave; lane l fills 16-byte chunk l of its piece = (row l >> 1, half l & 1), reading the half the swizzle puts there
-        const unsigned dma_lane = (unsigned)((lane >> 1) * 32 + (((lane & 1) ^ ((lane >> 4) & 1)) * 16));
-        auto dma_b = [&](int ks, int st) {
-            if (ks < nks) {                                                                  // uniform
+        const int a_bytes = (int)((int64_t)nseq * lp.Tin * lp.lda * 4), w_bytes = (int)((int64_t)p.N * ldw * 4);
+        // two descriptors per fp32 operand, both loop-invariant: the matrix, and NO records - what a request past the last half step goes through (the
+        // range check returns zeros); the uniform flag of fetch() selects one
+        const __amdgpu_buffer_rsrc_t ra_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.A), 0, a_bytes, 0x00020000);
+        const __amdgpu_buffer_rsrc_t ra_zero = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.A), 0, 0, 0x00020000);
+        // the weight operand: the fp32 matrix likewise, or (DMAW) its planes, which reach to 2 * nks half steps (zeros past K)
+        const __amdgpu_buffer_rsrc_t rw_rs = DMAW ? __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.W3), 0, (int)((int64_t)p.N * (2 * nks * WK) * 6), 0x00020000)
+                                                  : __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.W), 0, w_bytes, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rw_zero = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.W), 0, 0, 0x00020000);
+        // LDS-DMA of the weight planes of half step `hs` into its half stage: 3 planes x 256 rows x 32 bytes = 24 contiguous 1-KB pieces (a piece = 32
+        // rows of one plane), six per staging wave; lane l fills 16-byte chunk l of its piece
+        const unsigned dma_lane = (unsigned)(lane * 16);
+        auto dma_b = [&](int hs) {
+            if (hs < 2 * nks) {                                                              // uniform
 #pragma unroll
                 for (int e = 0; e < 6; ++e) {
                     const int q = (wave - 8) * 6 + e, pl = q >> 3, sub = q & 7;
-                    const int soff = __builtin_amdgcn_readfirstlane((int)((((int64_t)ks * 3 + pl) * p.N + n0 + sub * 32) * 32));
-                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rw_rs, (__attribute__((address_space(3))) void*)(smem + st * STG + 3 * WPA + pl * WPBD + sub * 1024), 16,
+                    const int soff = __builtin_amdgcn_readfirstlane((int)((((int64_t)hs * 3 + pl) * p.N + n0 + sub * 32) * 32));
+                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rw_rs, (__attribute__((address_space(3))) void*)(smem + (hs & 3) * WHSTG + 3 * WPA + pl * WPB + sub * 1024), 16,
                                                              (int)dma_lane, soff, 0, 0);
                 }
             }
@@ -424,30 +447,32 @@ __global__ __launch_bounds__(WTHREADS) void gemm_x3w_kernel(const GemmBatch batc
             }
         };
         set_tap();
-        // K is a multiple of 16 here (launch check), so no quad of a step is past K and the per-thread offsets are loop-invariant registers: no
-        // VALU at all between the loads of one step and the next.  The requests past the last step (the loop runs two sets ahead) re-read the
-        // last step instead of running off the matrix: the uniform position simply stops advancing.
+        // K is a multiple of 16 here (launch check), so no quad of a half step is past K and the per-thread offsets are loop-invariant registers: no
+        // VALU at all between the loads of one half step and the next.  A request past the last half step - the loop runs two steps ahead, and the
+        // last step's second half where K is an odd multiple of 16 - goes through a descriptor of NO records: the range check returns zeros.
         auto fetch = [&](float4* ra, float4* rb) {
+            const bool in = hs_req < nhs;                                                    // uniform
             const int acol = __builtin_amdgcn_readfirstlane((cib + (cib >= lp.a_split ? lp.a_gap : 0)) * 4);
             const int wcol = __builtin_amdgcn_readfirstlane(kb * 4);
 #pragma unroll
             for (int j = 0; j < 2; ++j)
-                ra[j] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(ra_rs, (int)afix[j], acol, 0));
+                ra[j] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(in ? ra_rs : ra_zero, (int)afix[j], acol, 0));
             if constexpr (!DMAW) {
 #pragma unroll
                 for (int j = 0; j < 4; ++j)
-                    rb[j] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rw_rs, (int)wfix[j], wcol, 0));
+                    rb[j] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(in ? rw_rs : rw_zero, (int)wfix[j], wcol, 0));
             }
         };
         auto advance = [&]() {
-            if (kb + WK < lp.K) {                                                            // uniform
+            ++hs_req;
+            if (hs_req < nhs) {                                                              // uniform
                 kb += WK; cib += WK;
                 if (lp.taps > 1 && cib >= lp.Cin) { cib -= lp.Cin; ++tap; set_tap(); }
             }
         };
         const int st_off = lr * WLDB + kq * 2;
-        auto stage = [&](const float4* ra, const float4* rb, int st) {
-            unsigned char* base = smem + st * STG + st_off;
+        auto stage = [&](const float4* ra, const float4* rb, int hs) {
+            unsigned char* base = smem + (hs & 3) * WHSTG + st_off;
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
                 const X3Split sa = x3_split(ra[j]);
@@ -463,40 +488,38 @@ __global__ __launch_bounds__(WTHREADS) void gemm_x3w_kernel(const GemmBatch batc
                 }
             }
         };
-        // branch-free body, requests before the older sets are waited for (see the narrow kernel).  THREE register sets: the data staged in
-        // iteration ks (step ks+1) were requested in iteration ks-2 - two K steps (~3 500 clk) to land; with two sets (one step) the staging
-        // waves still waited ~400 clk per step for rows of A that come from HBM
-        float4 ra0[2], rb0[DMAW ? 1 : 4], ra1[2], rb1[DMAW ? 1 : 4], ra2[2], rb2[DMAW ? 1 : 4];
-        if constexpr (DMAW) dma_b(0, 0);
+        // branch-free body, requests before the older sets are waited for (see the narrow kernel).  FOUR register sets of a half step each = two K
+        // steps: the data staged in iteration ks (step ks+1) were requested in iteration ks-1 - a whole K step (~3 500 clk) to land
+        constexpr int NB = DMAW ? 1 : 4;
+        float4 ra0[2], rb0[NB], ra1[2], rb1[NB], ra2[2], rb2[NB], ra3[2], rb3[NB];
+        if constexpr (DMAW) { dma_b(0); dma_b(1); }
         fetch(ra0, rb0);
         advance(); fetch(ra1, rb1);
         advance(); fetch(ra2, rb2);
-        stage(ra0, rb0, 0);
-        if constexpr (DMAW) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // stage 0's weight planes have landed before the barrier publishes it
-        __syncthreads();                                     // stage 0 = step 0
-        // every request of the prologue has landed before the loop is entered: with loads pending on the entry edge the wait-count pass merges
-        // them with the back edge's at the loop header and drains ALL outstanding loads (vmcnt(0)) once per trip
+        advance(); fetch(ra3, rb3);
+        stage(ra0, rb0, 0); stage(ra1, rb1, 1);
+        // stage 0's weight planes have landed before the barrier publishes it, and so has every other request of the prologue: with loads pending
+        // on the entry edge the wait-count pass merges them with the back edge's at the loop header and drains ALL outstanding loads once per trip
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#define L2S_X3W_PRODUCE(KS_, RA_NEW, RB_NEW, RA_OLD, RB_OLD)                                                   \
+        __syncthreads();                                     // stage 0 = step 0
+#define L2S_X3W_PRODUCE(KS_, RA_N0, RB_N0, RA_N1, RB_N1, RA_O0, RB_O0, RA_O1, RB_O1)                           \
         X3_STAMP(KS_, 0);                                                                                      \
-        if constexpr (DMAW) dma_b((KS_) + 1, ((KS_) + 1) & 1);   /* that stage was last read in step KS_ - 1 */  \
-        advance(); fetch(RA_NEW, RB_NEW);                                                                      \
+        if constexpr (DMAW) { dma_b(2 * (KS_) + 2); dma_b(2 * (KS_) + 3); }   /* that stage was last read in step KS_ - 1 */ \
+        advance(); fetch(RA_N0, RB_N0); advance(); fetch(RA_N1, RB_N1);                                        \
         __builtin_amdgcn_sched_barrier(0);                                                                     \
         X3_STAMP(KS_, 4);                                                                                      \
         if constexpr (TIMED) { if constexpr (DMAW) asm volatile("s_waitcnt vmcnt(16)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(12)" ::: "memory"); X3_STAMP(KS_, 1); } \
-        stage(RA_OLD, RB_OLD, ((KS_) + 1) & 1);                                                                \
+        stage(RA_O0, RB_O0, 2 * (KS_) + 2); stage(RA_O1, RB_O1, 2 * (KS_) + 3);                                \
         if constexpr (TIMED) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }                            \
         X3_STAMP(KS_, 2);                                                                                      \
-        /* all but the two newest requests (this step's activation rows) are back: the DMA pieces of step KS_ + 1 have landed */ \
-        if constexpr (DMAW) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");                                   \
+        /* all but the four newest requests (this step's activation rows) are back: the DMA pieces of step KS_ + 1 have landed */ \
+        if constexpr (DMAW) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");                                   \
         __syncthreads();                                                                                       \
         X3_STAMP(KS_, 3);
-        for (int ks = 0; ks < nks; ks += 3) {
-            L2S_X3W_PRODUCE(ks, ra0, rb0, ra1, rb1)
+        for (int ks = 0; ks < nks; ks += 2) {
+            L2S_X3W_PRODUCE(ks, ra0, rb0, ra1, rb1, ra2, rb2, ra3, rb3)
             if (ks + 1 >= nks) break;
-            L2S_X3W_PRODUCE(ks + 1, ra1, rb1, ra2, rb2)
-            if (ks + 2 >= nks) break;
-            L2S_X3W_PRODUCE(ks + 2, ra2, rb2, ra0, rb0)
+            L2S_X3W_PRODUCE(ks + 1, ra2, rb2, ra3, rb3, ra0, rb0, ra1, rb1)
         }
 #undef L2S_X3W_PRODUCE
 #pragma unroll
@@ -507,78 +530,45 @@ __global__ __launch_bounds__(WTHREADS) void gemm_x3w_kernel(const GemmBatch batc
         }
     } else {
         // ------------------------------------------------------------------------------------------------ consumers
-        f32x16 acc[2][2];
+        f32x4 acc[4][4];                                     // [row tile][column tile] of the wave's 64x64
 #pragma unroll
-        for (int i = 0; i < 2; ++i)
+        for (int i = 0; i < 4; ++i)
 #pragma unroll
-            for (int j = 0; j < 2; ++j)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-        const unsigned char* a_rd = smem + (wm * 64 + li) * WLDB + lg * 16;
-        const unsigned char* b_rd = DMAW ? smem + 3 * WPA + (wn * 64 + li) * WLDBD + ((lg ^ ((li >> 3) & 1)) * 16)
-                                         : smem + 3 * WPA + (wn * 64 + li) * WLDB + lg * 16;
-        constexpr int BROW = DMAW ? WLDBD : WLDB, BPL = DMAW ? WPBD : WPB;
-        struct FA { bf16x8 h[2], m[2], l[2]; };
-        struct FB { bf16x8 h, m, l; };
-        auto read_a = [&](FA& f, int so) {
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                const unsigned char* ap = a_rd + so + i * 32 * WLDB;
-                f.h[i] = *reinterpret_cast<const bf16x8*>(ap); f.m[i] = *reinterpret_cast<const bf16x8*>(ap + WPA); f.l[i] = *reinterpret_cast<const bf16x8*>(ap + 2 * WPA);
-            }
+            for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+        // this lane's operand rows: k group lg = 16-byte chunk lg & 1 of half stage lg >> 1; + t * 16 rows, + plane
+        // (the second stage is past the reach of a ds_read's 16-bit offset: one opaque base per operand and stage, or the compiler keeps a register
+        // per read address - 22 of them - and spills)
+        const int a_off = (lg >> 1) * WHSTG + (wm * 64 + li) * WLDB + (lg & 1) * 16, b_off = (lg >> 1) * WHSTG + 3 * WPA + (wn * 64 + li) * WLDB + (lg & 1) * 16;
+        int a_off1 = a_off + WSTAGE, b_off1 = b_off + WSTAGE;
+        asm volatile("" : "+v"(a_off1), "+v"(b_off1));
+        auto read_a = [&](F3& f, int so, int t) {
+            const unsigned char* ap = smem + (so ? a_off1 : a_off) + t * 16 * WLDB;
+            f.h = *reinterpret_cast<const bf16x8*>(ap); f.m = *reinterpret_cast<const bf16x8*>(ap + WPA); f.l = *reinterpret_cast<const bf16x8*>(ap + 2 * WPA);
         };
-        auto read_b = [&](FB& f, int so, int j) {
-            const unsigned char* bp = b_rd + so + j * 32 * BROW;
-            f.h = *reinterpret_cast<const bf16x8*>(bp); f.m = *reinterpret_cast<const bf16x8*>(bp + BPL); f.l = *reinterpret_cast<const bf16x8*>(bp + 2 * BPL);
+        auto read_b = [&](F3& f, int so, int j) {
+            const unsigned char* bp = smem + (so ? b_off1 : b_off) + j * 16 * WLDB;
+            f.h = *reinterpret_cast<const bf16x8*>(bp); f.m = *reinterpret_cast<const bf16x8*>(bp + WPB); f.l = *reinterpret_cast<const bf16x8*>(bp + 2 * WPB);
         };
-        // smallest partial products first; the two accumulators of a half alternate so that no MFMA waits on its predecessor
-#define L2S_X3W_TERM(A_, B_, J_)                                                                              \
-        acc[0][J_] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A_[0], B_, acc[0][J_], 0, 0, 0);                \
-        acc[1][J_] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A_[1], B_, acc[1][J_], 0, 0, 0);
-#define L2S_X3W_MMA_HEAD(FA_, FB_, J_) { L2S_X3W_TERM(FA_.l, FB_.h, J_) }
-#define L2S_X3W_MMA_TAIL(FA_, FB_, J_) { L2S_X3W_TERM(FA_.h, FB_.l, J_) L2S_X3W_TERM(FA_.m, FB_.m, J_) L2S_X3W_TERM(FA_.m, FB_.h, J_) L2S_X3W_TERM(FA_.h, FB_.m, J_) L2S_X3W_TERM(FA_.h, FB_.h, J_) }
-        // the LDS reads of a half are issued AFTER its first two MFMAs: right behind the barrier every MFMA wave of the block starts from an empty
-        // pipe, and nine ds_read_b128 in front of the first MFMA were ~150 clk of that bubble per step
-#define L2S_X3W_STEP(KS_, FA_CUR, FA_NXT, SO_)                                                                 \
-        X3_STAMP(KS_, 0);                                                                                      \
-        L2S_X3W_MMA_HEAD(FA_CUR, fb0, 0)                                                                       \
-        __builtin_amdgcn_sched_barrier(0);                                                                     \
-        read_b(fb1, SO_, 1);                                                                                   \
-        __builtin_amdgcn_sched_barrier(0);                                                                     \
-        L2S_X3W_MMA_TAIL(FA_CUR, fb0, 0)                                                                       \
-        __builtin_amdgcn_sched_barrier(0);                                                                     \
-        X3_STAMP(KS_, 1);                                                                                      \
-        __syncthreads();              /* this stage is read (fb1 has landed); the other one is written */      \
-        X3_STAMP(KS_, 2);                                                                                      \
-        L2S_X3W_MMA_HEAD(FA_CUR, fb1, 1)                                                                       \
-        __builtin_amdgcn_sched_barrier(0);                                                                     \
-        read_a(FA_NXT, STG - (SO_)); read_b(fb0, STG - (SO_), 0);         /* past the last step: unused */     \
-        __builtin_amdgcn_sched_barrier(0);                                                                     \
-        L2S_X3W_MMA_TAIL(FA_CUR, fb1, 1)                                                                       \
-        __builtin_amdgcn_sched_barrier(0);                                                                     \
-        X3_STAMP(KS_, 3);
-        FA fa0, fa1;
-        FB fb0, fb1;
+        F3 fa[4], fb0, fb1;
         __syncthreads();                                     // stage 0 ready
-        read_a(fa0, 0); read_b(fb0, 0, 0);
+        // in the order the loop's back edge leaves them in (the wait in front of a step's first MFMA is the stricter of the two edges')
+        read_b(fb0, 0, 0); L2S_X3_FENCE read_a(fa[0], 0, 0); read_a(fa[1], 0, 1); L2S_X3_FENCE read_a(fa[2], 0, 2); read_a(fa[3], 0, 3); L2S_X3_FENCE
         int ks = 0;
         for (; ks + 1 < nks; ks += 2) {                      // pairs of steps: no exit from the middle of the body (the accumulators would be copied at it)
-            L2S_X3W_STEP(ks, fa0, fa1, 0)
-            L2S_X3W_STEP(ks + 1, fa1, fa0, STG)
+            L2S_X3_STEP(ks, 0, WSTAGE)
+            L2S_X3_STEP(ks + 1, WSTAGE, 0)
         }
-        if (ks < nks) { L2S_X3W_STEP(ks, fa0, fa1, 0) }
-#undef L2S_X3W_STEP
-#undef L2S_X3W_MMA_HEAD
-#undef L2S_X3W_MMA_TAIL
-#undef L2S_X3W_TERM
+        if (ks < nks) { L2S_X3_STEP(ks, 0, WSTAGE) }
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
             if (i) __syncthreads();
 #pragma unroll
-            for (int j = 0; j < 2; ++j)
+            for (int t = 0; t < 2; ++t)
 #pragma unroll
-                for (int r = 0; r < 16; ++r)
-                    ct[(wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * lg) * WN + wn * 64 + j * 32 + li] = acc[i][j][r];
+                for (int j = 0; j < 4; ++j)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r)
+                        ct[(wm * 32 + t * 16 + 4 * lg + r) * WN + wn * 64 + j * 16 + li] = acc[2 * i + t][j][r];
             __syncthreads();
             store_rows(i);
         }
@@ -623,9 +613,10 @@ static int g_x3_stamp_block = 0;
 void gemm_x3_set_timeline(unsigned long long* ts, int block) { g_x3_ts = ts; g_x3_stamp_block = block; }
 #endif
 
-// Which tile: both give the same bits, so the choice is free per launch.  The wide tile needs N, K, Cin and the A split to fit its uniform K steps, and
-// it pays when the launch runs in fewer "rounds" of 256 blocks x tile time: a wide tile takes ~1.7x a narrow one for twice the work (2 250 against
-// 2 x 1 320 clk per 16 k), so 9600 x 512 (150 wide tiles, one round, against 300 narrow = two) wins and 7424 x 512 (116 against 232: one round each) loses;
+// Which tile: both give the same bits, so the choice is free per launch.  The wide tile needs N, K, Cin and the A split to fit its uniform half steps of
+// 16 k, and it pays when the launch runs in fewer "rounds" of 256 blocks x tile time: a wide tile takes ~1.7x a narrow one for twice the work (the ratio
+// of the stamped builds on the 32x32x16 shape, 2 250 against 2 x 1 320 clk per 16 k; both tiles moved to 16x16x32 together, the MFMA waves' step is the
+// same code in both and the ratios were not re-fitted: 7424 x 512 on 16x16x32 times at 1.32-1.46x, tools/gemm_x3_shape), so 9600 x 512 (150 wide tiles, one round, against 300 narrow = two) wins and 7424 x 512 (116 against 232: one round each) loses;
 // grouped launches whose members differ in K (the MultiHop convs) have a longer tail with the longer tile and need a clearer margin.
 static bool x3_wide(const GemmBatch& b) {
     if (b.p[0].x3 & 4) return false;                          // mode bit 4 (option "gemm_x3" = 5, operator flag 4): the 128x128x32 tile everywhere
@@ -639,19 +630,20 @@ static bool x3_wide(const GemmBatch& b) {
     if (b.p[0].x3 & 2) return true;                           // forced (operator tests): the wide tile wherever it fits
     bool dma = true;
     for (int i = 0; i < b.count; ++i) dma = dma && b.p[i].W3 && b.p[i].ldw == 0;
-    // grouped launches whose members all bring weight planes (the MultiHop convs): the DMA form's K step is 2 013 clk against 2 x 1 320
+    // grouped launches whose members all bring weight planes (the MultiHop convs): the DMA form's ratio (2 013 clk against 2 x 1 320 per 16 k, same measurement)
     const double cost_w = (double)((wide + 255) / 256) * (b.count > 1 ? (dma ? 1.6 : 2.0) : 1.7), cost_n = (double)((narrow + 255) / 256);
     return cost_w < cost_n;
 }
 
-// W [N][K] (K contiguous) -> its split-bf16 planes [K / 16][3 planes][N][16 k], the layout gemm_x3w_kernel<., true> fetches by LDS-DMA (a K step of one
-// plane = N rows of 32 bytes); the same truncation split the staging waves apply, so both forms of the kernel multiply the same operand bits
+// W [N][K] (K contiguous) -> its split-bf16 planes [ceil32(K) / 16][3 planes][N][16 k], zero-filled past K: the layout gemm_x3w_kernel<., true>
+// fetches by LDS-DMA (a half step of one plane = N rows of 32 bytes, a K step of 32 = two of them, gemm_planes_bytes()); the same truncation split
+// the staging waves apply, so both forms of the kernel multiply the same operand bits
 __global__ __launch_bounds__(256) void gemm_planes_kernel(const float* __restrict__ W, int N, int K, unsigned char* __restrict__ planes) {
     const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const int kq4 = K / 4;
+    const int kq4 = (K + 31) / 32 * 8;
     if (idx >= (int64_t)N * kq4) return;
     const int n = (int)(idx / kq4), k = 4 * (int)(idx - (int64_t)n * kq4);
-    const X3Split sp = x3_split(*reinterpret_cast<const float4*>(W + (int64_t)n * K + k));
+    const X3Split sp = x3_split(k < K ? *reinterpret_cast<const float4*>(W + (int64_t)n * K + k) : make_float4(0.f, 0.f, 0.f, 0.f));
     const int64_t step = (int64_t)(k >> 4) * 3 * N;
     unsigned char* d = planes + ((step + n) * 16 + (k & 15)) * 2;
     *reinterpret_cast<uint2*>(d) = sp.hi;
@@ -660,7 +652,7 @@ __global__ __launch_bounds__(256) void gemm_planes_kernel(const float* __restric
 }
 int launch_gemm_planes(const float* W, int N, int K, void* planes, hipStream_t s) {
     L2S_REQUIRE(W && planes && N % WN == 0 && K % WK == 0, "gemm planes: N a multiple of 256, K of 16");
-    const int64_t n = (int64_t)N * (K / 4);
+    const int64_t n = (int64_t)N * ((K + 31) / 32 * 8);
     hipLaunchKernelGGL(gemm_planes_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, W, N, K, reinterpret_cast<unsigned char*>(planes));
     L2S_CHECK_HIP(hipGetLastError());
     return 0;
@@ -677,26 +669,25 @@ int launch_gemm_x3(const GemmBatch& b, hipStream_t s, const char* name) {
     ProfScope ps(name, s);
     if (x3_wide(b)) {
         dim3 grid((maxN + WN - 1) / WN, (maxM + WM - 1) / WM, b.count);
-        constexpr int LDS_BYTES = 2 * WSTAGE;                 // 110 592
-        constexpr int LDS_BYTES_D = 2 * WSTAGED;              // 86 016 (the epilogue's 64-row sub-tile needs 65 536)
+        constexpr int LDS_BYTES = 2 * WSTAGE;                 // 147 456: both forms (the epilogue's 64-row sub-tile needs 65 536)
         bool dma = true;
         for (int i = 0; i < b.count; ++i) dma = dma && b.p[i].W3 && b.p[i].ldw == 0;      // every member brings pre-split weight planes
         static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_x3w_kernel<false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
         L2S_CHECK_HIP(attr);
-        static const hipError_t attr_d = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_x3w_kernel<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES_D);
+        static const hipError_t attr_d = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_x3w_kernel<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
         L2S_CHECK_HIP(attr_d);
 #ifdef L2S_DIAG
         if (g_x3_ts) {
             static const hipError_t attr_t = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_x3w_kernel<true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
             L2S_CHECK_HIP(attr_t);
-            static const hipError_t attr_td = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_x3w_kernel<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES_D);
+            static const hipError_t attr_td = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_x3w_kernel<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
             L2S_CHECK_HIP(attr_td);
-            if (dma) hipLaunchKernelGGL((gemm_x3w_kernel<true, true>), grid, dim3(WTHREADS), LDS_BYTES_D, s, b, g_x3_ts, g_x3_stamp_block);
+            if (dma) hipLaunchKernelGGL((gemm_x3w_kernel<true, true>), grid, dim3(WTHREADS), LDS_BYTES, s, b, g_x3_ts, g_x3_stamp_block);
             else hipLaunchKernelGGL((gemm_x3w_kernel<true, false>), grid, dim3(WTHREADS), LDS_BYTES, s, b, g_x3_ts, g_x3_stamp_block);
         } else
 #endif
         if (dma) {
-            hipLaunchKernelGGL((gemm_x3w_kernel<false, true>), grid, dim3(WTHREADS), LDS_BYTES_D, s, b, (unsigned long long*)nullptr, 0);
+            hipLaunchKernelGGL((gemm_x3w_kernel<false, true>), grid, dim3(WTHREADS), LDS_BYTES, s, b, (unsigned long long*)nullptr, 0);
         } else {
             hipLaunchKernelGGL((gemm_x3w_kernel<false, false>), grid, dim3(WTHREADS), LDS_BYTES, s, b, (unsigned long long*)nullptr, 0);
         }
@@ -704,7 +695,7 @@ int launch_gemm_x3(const GemmBatch& b, hipStream_t s, const char* name) {
         return 0;
     }
     dim3 grid((maxN + XN - 1) / XN, (maxM + XM - 1) / XM, b.count);
-    constexpr int LDS_BYTES = 2 * 6 * XPLANE;              // 122 880: two operand stages (one block per CU)
+    constexpr int LDS_BYTES = 2 * 6 * XPLANE;              // 98 304: two operand stages (one block per CU)
     static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_x3_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
     L2S_CHECK_HIP(attr);
 #ifdef L2S_DIAG

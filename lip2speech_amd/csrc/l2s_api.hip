@@ -1345,7 +1345,7 @@ static std::mutex g_op_planes_mu;
 static const void* op_planes(const float* W, int N, int K, hipStream_t s) {
     if (N % 256 || K % 16) return nullptr;
     std::lock_guard<std::mutex> lk(g_op_planes_mu);
-    const int64_t need = (int64_t)N * K * 6;
+    const int64_t need = gemm_planes_bytes(N, K);
     if (need > g_op_planes_bytes) {
         if (g_op_planes) { (void)hipDeviceSynchronize(); (void)hipFree(g_op_planes); g_op_planes = nullptr; g_op_planes_bytes = 0; }
         if (hipMalloc(&g_op_planes, need) != hipSuccess) { g_op_planes = nullptr; return nullptr; }

@@ -137,8 +137,8 @@ struct GemmP {
     const float* mask;    // training: dropout multiplier mask[m*ldmask + n], applied after activation and addends
     int ldmask, mask_pre; //   (mask_pre: after the activation, before the addends)
     int ldw;              // row stride of W in floats (0: K) - a K slice of a wider matrix (split-K)
-    const void* W3;       // W as pre-split bf16 planes [K / 16][3 planes][N][16 k] (launch_gemm_planes; N % 256 == 0, K % 16 == 0, ldw == 0) or null: the
-                          //   128x256x16 split-bf16 tile then brings its weight operand in by LDS-DMA instead of load + split + ds_write
+    const void* W3;       // W as pre-split bf16 planes [ceil32(K) / 16][3 planes][N][16 k], zeros past K (launch_gemm_planes; N % 256 == 0, K % 16 == 0, ldw == 0) or null: the
+                          //   128x256x32 split-bf16 tile then brings its weight operand in by LDS-DMA instead of load + split + ds_write
     int x3;               // bit 1: run on the split-bf16 kernel (gemm_x3.hip) when the whole launch group is eligible; bit 2: whatever its size
                           //   (operator tests); bit 4: the 128x128x32 tile only; set from gemm_x3_mode()
     int x3_group;         // batches sharing this launch (grouped inference): the size thresholds of the kernel choice look at M / x3_group,
@@ -175,7 +175,8 @@ int& gemm_bf16_mode();
 struct Bf16Scope { int prev; explicit Bf16Scope(int on) : prev(gemm_bf16_mode()) { gemm_bf16_mode() = on; } ~Bf16Scope() { gemm_bf16_mode() = prev; } };
 bool gemm_x3_eligible(const GemmBatch& b);
 bool gemm_x3_member_ok(const GemmP& p);               // one member's operands and shape (no launch-size threshold)
-int launch_gemm_planes(const float* W, int N, int K, void* planes, hipStream_t s);      // planes: N * K * 6 bytes
+int64_t gemm_planes_bytes(int N, int K);                                                // N * ceil32(K) * 6
+int launch_gemm_planes(const float* W, int N, int K, void* planes, hipStream_t s);      // planes: gemm_planes_bytes(N, K)
 int launch_gemm_x3(const GemmBatch& b, hipStream_t s, const char* name);
 void gemm_x3_set_timeline(unsigned long long* ts, int block);      // non-null: launch the stamped measurement build (tools/gemm_x3_timeline.py)
 // split-K for plain GEMMs whose 64x64 tiles are too few to fill the chip (M <= 128 rows in the content path, the B-row Linears):

@@ -637,7 +637,7 @@ static int derive_gemm_planes(l2s_model* m, hipStream_t s) {
             for (int j = 0; j < 4; ++j) items.push_back({w.mh_branch[kv][j].W, 512, 512 * MH_KS[j], &w.mh_branch[kv][j].W3});      // k = 1, 3, 7, 11; K and V
     }
     if (m->has_enc) items.push_back({w.conv_last.W, LAST_CH, STAGE_CH[3], &w.conv_last.W3});
-    return derive_planes(items, [](int N, int K) { return (int64_t)N * K * 6; }, launch_gemm_planes, &m->gemm_planes, s);      // no part that has any: nothing to do
+    return derive_planes(items, gemm_planes_bytes, launch_gemm_planes, &m->gemm_planes, s);      // no part that has any: nothing to do
 }
 
 // the fused ShuffleNet units' pointwise convs, from the packed [N][K] matrices (option "trunk_x3")

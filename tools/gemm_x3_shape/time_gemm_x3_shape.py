@@ -1,0 +1,126 @@
+"""The split-bf16 GEMM family (gemm_x3.hip) on the 16x16x32 MFMA shape against the parent commit's build (32x32x16), kernel level: the headline path's
+launches of that family, each through the operator entries of the diagnostic build with the split-bf16 kernel forced and, where the model brings
+weight planes, the LDS-DMA weight form (flags 1 | 8; the per-call derivation of the planes is inside the bracket for both builds alike) -
+  Conv1d 256 x 300 rows 512 -> 512, 80 -> 512 and 512 -> 80 with k = 5 (post-net layers 1-3, 0 and 4), the eight MultiHop branch convs at 256 x 29
+  rows (k = 1, 3, 7, 11, twice each; the operator entries launch one conv at a time, so the group is timed as its members back to back), the BiLSTM
+  input GEMM 7 424 x 4 096 x 1 024 and conv_last 7 424 x 768 x 464 (K an odd multiple of 16).
+`PARENT_DIAG_LIB=<path to a libl2s_diag.so built from the parent commit>`: loaded into the same process and timed interleaved with this build's;
+without it only this build is timed.  Per shape one untimed round on each build, then ROUNDS interleaved rounds of REPS warm calls each (7 x 10), HIP events around the REPS calls; per shape and
+build every round's figure, the median of the rounds and the spread (max - min), then the sum over the shapes.  Last, outside the sum and on this
+build alone, 7 424 x 512 on the wide tile against the narrow one (116 tiles against 232, one round of blocks each): the case the tile choice
+(x3_wide in gemm_x3.hip) decides by its cost ratio.
+-> profiles/gemm_x3_shape_times.txt (stdout)
+
+Lives in a sub-directory of tools/ (like masked_lengths/ and early_stop/): the flat tools/ inventory is pinned by tests/test_tools_smoke.py."""
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, ROOT)
+import torch
+
+from lip2speech_amd import native
+
+REPS = int(os.environ.get("REPS", 10))
+ROUNDS = int(os.environ.get("ROUNDS", 7))
+CLIPS = int(os.environ.get("CLIPS", 256))
+
+
+def conv_case(name, B, T, Ci, Co, k, flags):
+    X = torch.randn(B, T, Ci, device="cuda")
+    Wp = (torch.randn(Co, k * Ci, device="cuda") / (k * Ci) ** 0.5)
+    out = torch.empty(B, T, Co, device="cuda")
+
+    def run(L):
+        native.check(L.l2s_op_conv1d_ex(X.data_ptr(), Wp.data_ptr(), None, None, None, out.data_ptr(), B, T, Ci, Co, k, 1, k // 2, 0, flags, native._stream()), L)
+        return out
+    return name, [run]
+
+
+def gemm_case(name, M, N, K, flags):
+    A = torch.randn(M, K, device="cuda")
+    W = (torch.randn(N, K, device="cuda") / K ** 0.5)
+    C = torch.empty(M, N, device="cuda")
+
+    def run(L):
+        native.check(L.l2s_op_gemm_ex(A.data_ptr(), W.data_ptr(), None, None, None, C.data_ptr(), M, N, K, 0, flags, native._stream()), L)
+        return C
+    return name, [run]
+
+
+def timed(fns, L):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(REPS):
+        for fn in fns:
+            fn(L)
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) * 1e3 / REPS
+
+
+def main():
+    torch.manual_seed(0)
+    rows = CLIPS * 29
+    multihop = ("MultiHop branches, 8 convs 512 -> 512 (k = 1, 3, 7, 11 twice), %d x 29 rows" % CLIPS,
+                [conv_case("", CLIPS, 29, 512, 512, k, 9)[1][0] for k in (11, 11, 7, 7, 3, 3, 1, 1)])
+    cases = [conv_case(f"Conv1d {CLIPS} x 300 rows 512 -> 512 k = 5 (dma)", CLIPS, 300, 512, 512, 5, 9),
+             conv_case(f"Conv1d {CLIPS} x 300 rows  80 -> 512 k = 5 (dma)", CLIPS, 300, 80, 512, 5, 9),
+             conv_case(f"Conv1d {CLIPS} x 300 rows 512 ->  80 k = 5 (narrow tile)", CLIPS, 300, 512, 80, 5, 1),
+             multihop,
+             gemm_case(f"BiLSTM input GEMM {rows} x 4096 x 1024 (dma)", rows, 4096, 1024, 9),
+             gemm_case(f"conv_last {rows} x 768 x 464 (dma)", rows, 768, 464, 9)]
+    builds = [("this build", native.diag())]
+    parent_path = os.environ.get("PARENT_DIAG_LIB")
+    if parent_path:
+        builds.insert(0, ("parent build", native._load(parent_path)))
+    print(f"{ROUNDS} interleaved rounds x {REPS} warm calls, HIP events; us per call: median of the rounds (spread = max - min)")
+    t = {(c, b): [] for c in range(len(cases)) for b in range(len(builds))}
+    for c, (name, fns) in enumerate(cases):
+        for _, L in builds:                     # warm-up of every shape on every build: one untimed round (a single call leaves the first timed
+            timed(fns, L)                       # round of a shape 7-17 % slow on either build, the clock still settling)
+        for r in range(ROUNDS):
+            for b in (range(len(builds)) if r % 2 == 0 else reversed(range(len(builds)))):
+                t[(c, b)].append(timed(fns, builds[b][1]))
+    total = [[0.0] * ROUNDS for _ in builds]
+    for c, (name, _) in enumerate(cases):
+        line = f"{name:<78}"
+        for b, (bname, _) in enumerate(builds):
+            x = t[(c, b)]
+            total[b] = [a + v for a, v in zip(total[b], x)]
+            line += f"  {bname} {statistics.median(x):8.1f} ({max(x) - min(x):5.1f})"
+        if len(builds) == 2:
+            mp, mt = statistics.median(t[(c, 0)]), statistics.median(t[(c, 1)])
+            spread = max(max(t[(c, b)]) - min(t[(c, b)]) for b in range(2))
+            line += f"  this / parent {mt / mp:5.3f}  {'LOWER by more than the larger spread' if mp - mt > spread else 'not lower by more than the larger spread'}"
+        print(line)
+        for b, (bname, _) in enumerate(builds):
+            print(f"    {bname:<12} rounds: " + " ".join(f"{v:8.1f}" for v in t[(c, b)]))
+    line = f"{'sum over the six shapes (round by round)':<78}"
+    for b, (bname, _) in enumerate(builds):
+        line += f"  {bname} {statistics.median(total[b]):8.1f} ({max(total[b]) - min(total[b]):5.1f})"
+    if len(builds) == 2:
+        mp, mt = statistics.median(total[0]), statistics.median(total[1])
+        spread = max(max(x) - min(x) for x in total)
+        line += f"  this / parent {mt / mp:5.3f}  {'LOWER by more than the larger spread' if mp - mt > spread else 'not lower by more than the larger spread'}"
+    print(line)
+    for b, (bname, _) in enumerate(builds):
+        print(f"    {bname:<12} rounds: " + " ".join(f"{v:8.1f}" for v in total[b]))
+    # the tile choice's margin case on this build: flags 1 = the wide tile wherever it fits, 1 | 4 = the narrow tile everywhere (in-kernel weight split in both)
+    L = builds[-1][1]
+    for K in (512, 2560):
+        forms = [gemm_case("", rows, 512, K, f)[1] for f in (1, 5)]
+        for fns in forms:
+            fns[0](L)
+        torch.cuda.synchronize()
+        x = [[], []]
+        for r in range(ROUNDS):
+            for f in ((0, 1) if r % 2 == 0 else (1, 0)):
+                x[f].append(timed(forms[f], L))
+        print(f"tile choice, this build, {rows} x 512 x {K}: wide tile {statistics.median(x[0]):7.1f} ({max(x[0]) - min(x[0]):4.1f})  narrow tile {statistics.median(x[1]):7.1f} "
+              f"({max(x[1]) - min(x[1]):4.1f})  wide / narrow {statistics.median(x[0]) / statistics.median(x[1]):5.3f}")
+
+
+if __name__ == "__main__":
+    main()
