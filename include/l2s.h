@@ -155,7 +155,8 @@ int l2s_postnet(l2s_model* m, const float* mel, int B, int S, float* mel_post, f
 
 /* SpeakerEncoder.inference (model/modules/audio.py:131-150; called at demo.py:84): audio dev (B, n_samples) 16 kHz ->
  * 40-band mel power spectrogram (n_fft 400, hop 160, hann, centre/reflect, HTK, no log) -> 3 x LSTM(256) ->
- * Linear(last hidden) -> ReLU -> L2 normalise -> emb dev (B,256).  Needs the speaker_encoder.* keys in the model. */
+ * Linear(last hidden) -> ReLU -> L2 normalise -> emb dev (B,256).  Needs the speaker_encoder.* keys in the model.
+ * n_samples > 200 (the reflect padding) and ws_bytes >= l2s_speaker_workspace_bytes(B, n_samples), else the call fails before it launches anything. */
 int64_t l2s_speaker_workspace_bytes(int B, int n_samples);
 int l2s_speaker_encoder_fwd(l2s_model* m, const float* audio, int B, int n_samples, float* emb,
                             void* ws, int64_t ws_bytes, void* stream);

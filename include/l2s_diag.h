@@ -76,6 +76,11 @@ int l2s_op_face_conv2d(const float* x, int64_t x_bstride, int B, int H, int W, i
  * mixed_6a and repeat_2 (B,8,8,896), mixed_7a and block8 (B,3,3,1792), the pooled features (B,1792) and last_bn's output (B,512) */
 int l2s_op_face_taps(l2s_model* m, const float* faces, int64_t batch_stride, int B, float* const* taps, float* proj, float* emb, void* ws,
                      int64_t ws_bytes, void* stream);
+/* l2s_speaker_encoder_fwd plus stage taps: taps = 7 dev pointers (each may be NULL) receiving, with R = B * L rows (L = n_samples / 160 + 1 frames per
+ * clip), the DFT product spec (R,402) = [re | im], the power spectrum (R,204; columns 201-203 zero), the mel (R,40), the hidden sequences of the three
+ * LSTM layers (B,L,256) each, and the Linear + ReLU output (B,256) before normalisation.  Same kernels, same launches: each tap is a device-to-device
+ * copy put on the stream after its stage (layer 0's sequence shares its workspace buffer with layer 2's) */
+int l2s_op_speaker_taps(l2s_model* m, const float* audio, int B, int n_samples, float* const* taps, float* emb, void* ws, int64_t ws_bytes, void* stream);
 /* average duration (us) of the decoder LSTM-cell kernel over a chain of n_pairs x {layer 0, layer 1} launches bracketed by ONE pair
  * of HIP events on `stream` (bench.py's roofline figure; synchronises) */
 int l2s_op_lstm_cell_chain(l2s_model* m, int B, int n_pairs, void* ws, int64_t ws_bytes, void* stream, double* avg_us);

@@ -795,9 +795,21 @@ static int64_t spk_ws_floats(int B, int N) {
     const int64_t L = N / 160 + 1, R = (int64_t)B * L;
     return R * (400 + 402 + 204 + 40 + 1024 + 256 * 2) + (int64_t)pad16(B) * 256 * 3 + (int64_t)B * 256 + 64 * 16;
 }
+static int64_t spk_ws_bytes(int B, int N) { return spk_ws_floats(B, N) * (int64_t)sizeof(float) + (1 << 12); }
 
 // SpeakerEncoder.inference (audio.py:131-150): mel40 -> 3 x LSTM(256), zero initial state -> Linear(h_last) -> ReLU -> L2 norm
-static int speaker_run(l2s_model* m, const float* audio, int B, int N, float* emb, void* ws, int64_t ws_bytes, hipStream_t s) {
+#ifdef L2S_DIAG      // stage taps (l2s_op_speaker_taps): a host-side copy after the stage, device to device on the call's stream - layer 0's sequence shares its buffer with layer 2's
+static int spk_tap(float* const* taps, int i, const float* src, int64_t n, hipStream_t s) {
+    if (taps && taps[i]) L2S_CHECK_HIP(hipMemcpyAsync(taps[i], src, (size_t)n * sizeof(float), hipMemcpyDeviceToDevice, s));
+    return 0;
+}
+#define L2S_SPK_TAP(i, src, n) do { if (spk_tap(taps, i, src, n, s)) return 1; } while (0)
+#define L2S_SPK_TAPS_ARG , float* const* taps = nullptr
+#else
+#define L2S_SPK_TAP(i, src, n) do {} while (0)
+#define L2S_SPK_TAPS_ARG
+#endif
+static int speaker_run(l2s_model* m, const float* audio, int B, int N, float* emb, void* ws, int64_t ws_bytes, hipStream_t s L2S_SPK_TAPS_ARG) {
     X3Scope x3scope(m->opt.infer_bf16 ? 0 : m->opt.gemm_x3);
     Bf16Scope bf16scope(m->opt.infer_bf16);      // the bf16 leg: bf16-operand GEMM / Conv1d kernels instead of the f32 / split-bf16 ones
     const Weights& w = m->w;
@@ -809,11 +821,15 @@ static int speaker_run(l2s_model* m, const float* audio, int B, int N, float* em
     float* pre = bp.f(R * 1024); float* hseq[2] = {bp.f(R * 256), bp.f(R * 256)};
     float* hf[2] = {bp.f((int64_t)Bp * 256), bp.f((int64_t)Bp * 256)}; float* cf = bp.f((int64_t)Bp * 256);
     float* lin = bp.f((int64_t)B * 256);
-    L2S_REQUIRE(!bp.overflow, "speaker-encoder workspace too small");
+    // the published size, not what the carve above happens to need: its alignment slack would let a short workspace through
+    L2S_REQUIRE(!bp.overflow && ws_bytes >= spk_ws_bytes(B, N), "speaker-encoder workspace too small");
     if (launch_frame_window(audio, B, N, L, 400, 160, w.spk_window, frames, s)) return 1;
     if (launch_gemm1(gemm_plain(frames, 400, w.spk_dft, spec, 402, (int)R, 402, 400), s, "spk_dft_gemm")) return 1;
+    L2S_SPK_TAP(0, spec, R * 402);
     if (launch_power(spec, 402, R, 201, power, 204, s)) return 1;
+    L2S_SPK_TAP(1, power, R * 204);
     if (launch_gemm1(gemm_plain(power, 204, w.spk_fbT, mel, 40, (int)R, 40, 204), s, "spk_mel_gemm")) return 1;
+    L2S_SPK_TAP(2, mel, R * 40);
     const float* x = mel;
     int xin = 40;
     for (int l = 0; l < 3; ++l) {
@@ -836,6 +852,7 @@ static int speaker_run(l2s_model* m, const float* audio, int B, int N, float* em
             sb.p[0] = p; sb.ntiles[0] = 64; sb.count = 1;
             if (launch_skinny(sb, s, "spk_lstm_step", m->opt)) return 1;
         }
+        L2S_SPK_TAP(3 + l, out, R * 256);
         x = out;
         xin = 256;
     }
@@ -843,6 +860,7 @@ static int speaker_run(l2s_model* m, const float* audio, int B, int N, float* em
     GemmP g = gemm_plain(x + (int64_t)(L - 1) * 256, L * 256, w.spk_linear.W, lin, 256, B, 256, 256);
     g.shift = w.spk_linear.shift; g.act = ACT_RELU;
     if (launch_gemm1(g, s, "spk_linear_gemm")) return 1;
+    L2S_SPK_TAP(6, lin, (int64_t)B * 256);
     return launch_pool_norm_cat(lin, B, 1, 256, nullptr, 0, 1, nullptr, 0, emb, s);
 }
 
@@ -979,7 +997,7 @@ int l2s_postnet(l2s_model* m, const float* mel, int B, int S, float* mel_post, f
     return postnet_run(m, mel, B, S, mel_post, mel_cf, ws, ws_bytes, (hipStream_t)stream);
 }
 
-int64_t l2s_speaker_workspace_bytes(int B, int n_samples) { return spk_ws_floats(B, n_samples) * (int64_t)sizeof(float) + (1 << 12); }
+int64_t l2s_speaker_workspace_bytes(int B, int n_samples) { return spk_ws_bytes(B, n_samples); }
 
 int l2s_speaker_encoder_fwd(l2s_model* m, const float* audio, int B, int n_samples, float* emb, void* ws, int64_t ws_bytes, void* stream) {
     L2S_MODEL_READY(m);
@@ -1417,6 +1435,12 @@ int l2s_op_face_taps(l2s_model* m, const float* faces, int64_t batch_stride, int
     L2S_REQUIRE(m->has_face, "model holds no vgg_face.* weights");
     L2S_REQUIRE(faces && taps && emb && ws && B > 0 && batch_stride >= (int64_t)3 * 160 * 160, "bad arguments");
     return face_run(m, faces, batch_stride, B, proj, emb, ws, ws_bytes, (hipStream_t)stream, taps);
+}
+int l2s_op_speaker_taps(l2s_model* m, const float* audio, int B, int n_samples, float* const* taps, float* emb, void* ws, int64_t ws_bytes, void* stream) {
+    L2S_MODEL_READY(m);
+    L2S_REQUIRE(m->has_spk, "model holds no speaker_encoder.* weights");
+    L2S_REQUIRE(audio && taps && emb && ws && B > 0, "bad arguments");
+    return speaker_run(m, audio, B, n_samples, emb, ws, ws_bytes, (hipStream_t)stream, taps);
 }
 
 #endif

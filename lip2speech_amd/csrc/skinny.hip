@@ -52,10 +52,10 @@ int set_stamp_log(unsigned long long* log, long long cap) {
 #endif
 
 // segment layouts with their own instance (chunks of 16 columns per segment): the decode step's and the BiLSTM's operand shapes
-//   1: [32]            K = 512   fc_out+stop, prenet1∘fc_out, BiLSTM / speaker LSTM recurrences
+//   1: [32]            K = 512   fc_out+stop, prenet1∘fc_out, BiLSTM recurrences
 //   2: [32 | 32]       K = 1024  LSTM1 on [h0' | h1], Q on [h0 | h1], content Q on [c0 | c1]
 //   3: [16|16|32|32]   K = 1536  LSTM0 on [content | prenet | a.v | h0] (attention_proj folded in)
-//   4: [16]            K = 256   prenet layers
+//   4: [16]            K = 256   prenet layers, speaker LSTM recurrences (launch_skinny runs this layout on the general blocks: the LSTM epilogue there)
 //   5: [16|16|16|32]   K = 1280  LSTM0 on [content | prenet | a.V' | h0] (attention_proj hoisted into the prologue)
 //   6: [16|16+16|32]   K = 1024  LSTM0 on [content | prenet + a.V' | h0]: segment 1 summed from two sources by the loader (SkinnyP::a_sum)
 static int skinny_layout_of(const SkinnyP& p) {

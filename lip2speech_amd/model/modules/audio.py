@@ -2,8 +2,10 @@
 
 Holds the ``speaker_encoder.*`` checkpoint tensors (3-layer LSTM(256) + Linear) so demo-style loaders
 (``demo.py:33-43``: ``SpeakerEncoder(state_dict=...)`` then ``.inference(audios)``) keep working, and runs
-``inference`` on the device through ``l2s_speaker_encoder_fwd``: 40-band mel front-end (DFT and filterbank as fp32
-MFMA GEMMs), three LSTM layers on the batch-row LSTM kernel, Linear + ReLU + L2 normalisation.
+``inference`` on the device through ``l2s_speaker_encoder_fwd``: 40-band mel front-end (DFT and filterbank as GEMMs: the
+fp32 MFMA kernel, except that the DFT product moves to the split-bf16 kernel - fp32 operands as three bf16 planes, fp32-grade
+sums - from 3 969 frames per call at the default ``gemm_x3`` = 1, and that a model with ``infer_bf16`` rounds the operands of both
+to bf16), three LSTM layers on the batch-row LSTM kernel, Linear + ReLU + L2 normalisation.
 The mel front-end restates torchaudio 0.9's published algorithm (third-party, absent here): parity UNPINNED for
 that piece; the LSTM/Linear tail is checked against ``torch.nn.LSTM`` in the tests.
 """

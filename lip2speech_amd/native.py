@@ -48,7 +48,7 @@ ABI_SYMBOLS = (
 # what include/l2s_diag.h adds: exported by libl2s_diag.so only
 DIAG_SYMBOLS = (
     "l2s_op_gemm", "l2s_op_conv1d", "l2s_op_gemm_ex", "l2s_op_conv1d_ex", "l2s_op_conv1d_bwd", "l2s_op_frontend", "l2s_op_launch_chain", "l2s_op_launch_chain2", "l2s_op_skinny_timeline", "l2s_op_attn_timeline", "l2s_op_flat_timeline", "l2s_op_pdecode_timeline", "l2s_op_gemm_x3_timeline", "l2s_op_fused_unit_timeline", "l2s_op_lstm_cell_chain", "l2s_op_step_attn_chain", "l2s_op_stamp_log",
-    "l2s_op_face_conv2d", "l2s_op_face_taps",
+    "l2s_op_face_conv2d", "l2s_op_face_taps", "l2s_op_speaker_taps",
 )
 
 # run-time options only the diagnostic build accepts (block-form A/B switches of the same arithmetic, include/l2s_diag.h)
@@ -230,6 +230,7 @@ def _bind_diag(L: ctypes.CDLL) -> None:
     L.l2s_op_stamp_log.argtypes = [_vp, _i64]
     L.l2s_op_face_conv2d.argtypes = [_fp, _i64, _i, _i, _i, _i, _fp, _fp, _fp, _fp, _i, _fp, _i, _i, _i, _i, _i, _i, _vp]
     L.l2s_op_face_taps.argtypes = [_vp, _fp, _i64, _i, _vp, _fp, _fp, _vp, _i64, _vp]
+    L.l2s_op_speaker_taps.argtypes = [_vp, _fp, _i, _i, _vp, _fp, _vp, _i64, _vp]
 
 
 def check(rc: int, L: Optional[ctypes.CDLL] = None) -> None:
@@ -617,11 +618,20 @@ class NativeModel:
             c += sh[0]
         return out
 
-    def speaker_encoder_fwd(self, audio: torch.Tensor) -> torch.Tensor:
+    def speaker_encoder_fwd(self, audio: torch.Tensor, taps: bool = False):
+        """SpeakerEncoder.inference (audio.py:131-150): audio (B,N) -> emb (B,256).  taps=True (diagnostic library only): also the stage outputs of
+        l2s_op_speaker_taps as a list of 7 tensors - spec (B*L,402), power (B*L,204), mel (B*L,40), the three hidden sequences (B,L,256), linear (B,256)."""
         audio = _f32(audio)
         B, N = audio.shape
         emb = torch.empty(B, 256, dtype=torch.float32, device=audio.device)
         ws = torch.empty(int(self._L.l2s_speaker_workspace_bytes(B, N)), dtype=torch.uint8, device=audio.device)
+        if taps:
+            L = N // 160 + 1
+            shapes = [(B * L, 402), (B * L, 204), (B * L, 40)] + [(B, L, 256)] * 3 + [(B, 256)]
+            outs = [torch.empty(s, dtype=torch.float32, device=audio.device) for s in shapes]
+            arr = (_vp * 7)(*[t.data_ptr() for t in outs])
+            _dcheck(diag().l2s_op_speaker_taps(self._h, _ptr(audio), B, N, arr, _ptr(emb), _ptr(ws), ws.numel(), _stream()))
+            return emb, outs
         self._check(self._L.l2s_speaker_encoder_fwd(self._h, _ptr(audio), B, N, _ptr(emb), _ptr(ws), ws.numel(), _stream()))
         return emb
 
