@@ -161,6 +161,26 @@ int64_t l2s_speaker_workspace_bytes(int B, int n_samples);
 int l2s_speaker_encoder_fwd(l2s_model* m, const float* audio, int B, int n_samples, float* emb,
                             void* ws, int64_t ws_bytes, void* stream);
 
+/* The same tower over B clips of UNEQUAL length: emb dev (B,256), row b (call order) = what l2s_speaker_encoder_fwd returns for clip b alone at
+ * B = 1, n_samples = n_samples[b].  audio_packed dev fp32: clip b is the n_samples[b] floats at float offset offsets[b] (any offset; no alignment
+ * asked); nothing outside [offsets[b], offsets[b] + n_samples[b]) is read, so a zero-padded (B, N) tensor is the special case offsets[b] = b * N
+ * and what pads it never matters.  offsets / n_samples are HOST int64 arrays that may be freed on return (as in l2s_mel_targets).
+ * Limits: n_samples[b] in [201, 2^30]; 1 <= B <= L2S_SPK_MAX_CLIPS and R = sum L_b <= L2S_SPK_MAX_ROWS, L_b = n_samples[b] / 160 + 1 - the row
+ * counts l2s_speaker_encoder_fwd itself can launch (it states no limit: its recurrence puts ceil(B / 16) row tiles and its GEMMs ceil(B L / 64) in
+ * the grid's y dimension, 65 535 at the most).  A violation is an error naming the row, raised before anything is launched; emb is then untouched.
+ * Rows: the time-major compact layout (torch's PackedSequence) - clips ranked by L_b descending, ties in call order; frame l of the clip of rank r
+ * is row step_row0[l] + r of R.  l2s_speaker_packed_plan is that layout as a pure host function: order[B] (rank -> clip), step_rows[L_max]
+ * (clips with L_b > t), step_row0[L_max + 1] (its prefix sum), L_max, R; size the three arrays for max n_samples / 160 + 2 entries.
+ * Bits: every kernel is row-wise; where R and the step row counts pick the kernel forms of the solo call (R < 3 969 and B <= 96 under the
+ * defaults) the embedding has the solo call's bits, elsewhere it agrees to rounding.
+ * l2s_speaker_workspace_bytes_packed is sized from the R compact rows; -1 (with l2s_last_error) outside the limits. */
+#define L2S_SPK_MAX_CLIPS 1048560
+#define L2S_SPK_MAX_ROWS 4194240
+int l2s_speaker_packed_plan(const int64_t* n_samples, int B, int32_t* order, int32_t* step_rows, int32_t* step_row0, int* L_max, int64_t* R);
+int64_t l2s_speaker_workspace_bytes_packed(const int64_t* n_samples, int B);
+int l2s_speaker_encoder_packed(l2s_model* m, const float* audio_packed, const int64_t* offsets, const int64_t* n_samples, int B, float* emb,
+                               void* ws, int64_t ws_bytes, void* stream);
+
 /* face speaker tower: FaceRecognizer (reference vgg_face.py:28-60), facenet_pytorch's InceptionResnetV1 (casia-webface) in eval mode + projection.
  * Needs a model holding the vgg_face.* keys (resnet.* without logits.*, projection_layer.*).  H = W = 160 only (the reference's loaders resize faces
  * to 160); other sizes return an error (the workspace query returns -1).  Runs fp32-exact on the split-bf16 matrix path under every option

@@ -81,6 +81,11 @@ int l2s_op_face_taps(l2s_model* m, const float* faces, int64_t batch_stride, int
  * LSTM layers (B,L,256) each, and the Linear + ReLU output (B,256) before normalisation.  Same kernels, same launches: each tap is a device-to-device
  * copy put on the stream after its stage (layer 0's sequence shares its workspace buffer with layer 2's) */
 int l2s_op_speaker_taps(l2s_model* m, const float* audio, int B, int n_samples, float* const* taps, float* emb, void* ws, int64_t ws_bytes, void* stream);
+/* l2s_speaker_encoder_packed plus the same seven taps in ITS row layout (l2s_speaker_packed_plan: frame l of the clip of rank r is row
+ * step_row0[l] + r of R): spec (R,402), power (R,204), mel (R,40), the three hidden sequences (R,256) each, and the Linear + ReLU output (B,256)
+ * in call order.  One body with the product entry point, as above */
+int l2s_op_speaker_taps_packed(l2s_model* m, const float* audio_packed, const int64_t* offsets, const int64_t* n_samples, int B, float* const* taps, float* emb,
+                               void* ws, int64_t ws_bytes, void* stream);
 /* average duration (us) of the decoder LSTM-cell kernel over a chain of n_pairs x {layer 0, layer 1} launches bracketed by ONE pair
  * of HIP events on `stream` (bench.py's roofline figure; synchronises) */
 int l2s_op_lstm_cell_chain(l2s_model* m, int B, int n_pairs, void* ws, int64_t ws_bytes, void* stream, double* avg_us);

@@ -13,7 +13,9 @@ The reference then vocodes the mels (InverseMelScale + Griffin-Lim, torchaudio) 
 third-party, stochastic and out of scope here - these functions return the mels.
 
 ``honour_lengths=True`` (off by default, as the reference ignores lengths): the loader's ``video_lengths`` are passed on to the length-masked entry
-points (``l2s_inference_masked`` / ``l2s_forward_eval_masked``), so a clip's output no longer depends on what it was padded to.  Those have no
+points (``l2s_inference_masked`` / ``l2s_forward_eval_masked``), and on the voice route the batch's audio lengths go to the speaker tower
+(``SpeakerEncoder.inference(audios, audio_lengths=...)``, ``l2s_speaker_encoder_packed``), so a clip's output no longer depends on what it was
+padded to or batched with - neither through the video nor through the embedding that conditions every decoder stage.  The masked entry points have no
 grouped form: the batches then run one call each, in loader order - unless ``demo_clips`` is also given ``group_lengths=True``: batches of unequal
 length then share launch chains as ragged groups (``l2s_inference_ragged``, ``Lip2Speech.inference_many_lengths``).
 """
@@ -45,9 +47,9 @@ def demo_clip(net, batch, speaker_encoder=None, speaker_embedding: Optional[torc
     _set_persist_masked(net, persist_masked)
     if encoding == "voice" and speaker_embedding is None and speaker_encoder is None:
         raise ValueError("pass a SpeakerEncoder (voice route) or a speaker_embedding")
-    (videos, vlen), (audios, _), _, face_crops, _ = batch
+    (videos, vlen), (audios, alen), _, face_crops, _ = batch
     with torch.no_grad():
-        emb = _voice_embedding(encoding, speaker_encoder, speaker_embedding, audios, device)
+        emb = _voice_embedding(encoding, speaker_encoder, speaker_embedding, audios, device, alen if honour_lengths else None)
         face_crops = face_crops.to(device, non_blocking=True) if encoding == "face" else face_crops
         mel, lengths, attn = net.inference(videos.to(device, non_blocking=True), face_crops, speaker_embedding=emb, return_attention_map=True,
                                            early_stop=bool(early_stop), video_lengths=vlen if honour_lengths else None)
@@ -84,9 +86,9 @@ def demo_clips(net, batches: Iterable, speaker_encoder=None, speaker_embedding: 
         return
     if honour_lengths:
         def ragged_calls():
-            for (videos, vlen), (audios, _), _, face_crops, _ in batches:
+            for (videos, vlen), (audios, alen), _, face_crops, _ in batches:
                 with torch.no_grad():
-                    emb = _voice_embedding(encoding, speaker_encoder, speaker_embedding, audios, device)
+                    emb = _voice_embedding(encoding, speaker_encoder, speaker_embedding, audios, device, alen)
                 yield videos, face_crops, emb, True, {"video_lengths": vlen}
 
         for mel, lengths, attn in net.inference_many_lengths(ragged_calls(), group=group, n_inflight=n_inflight, early_stop=bool(early_stop)):
@@ -122,13 +124,19 @@ def _check_encoding(encoding: str) -> None:
         raise ValueError(f"encoding must be 'voice' or 'face' (demo.py --encoding), got {encoding!r}")
 
 
-def _voice_embedding(encoding, speaker_encoder, speaker_embedding, audios, device):
-    """The embedding a caller passes on: none on the face route (the model's face tower computes it), else the supplied one or the voice tower's."""
+def _voice_embedding(encoding, speaker_encoder, speaker_embedding, audios, device, audio_lengths=None):
+    """The embedding a caller passes on: none on the face route (the model's face tower computes it), else the supplied one or the voice tower's.
+    ``audio_lengths`` (the ``honour_lengths`` callers pass the batch's): the tower runs each clip over its own samples only
+    (``SpeakerEncoder.inference(audios, audio_lengths=...)``), so the embedding of a padded clip is the one it has alone."""
     if encoding == "face":
         return None
     if speaker_embedding is not None:
         return speaker_embedding
-    return speaker_encoder.inference(audios.to(device, non_blocking=True)) if speaker_encoder is not None else None
+    if speaker_encoder is None:
+        return None
+    if audio_lengths is not None:
+        return speaker_encoder.inference(audios.to(device, non_blocking=True), audio_lengths=audio_lengths)
+    return speaker_encoder.inference(audios.to(device, non_blocking=True))
 
 
 def _evaluate_outputs(net, batches: Iterable, speaker_encoder, device, group: int, n_inflight: int, encoding: str = "voice",
@@ -143,7 +151,7 @@ def _evaluate_outputs(net, batches: Iterable, speaker_encoder, device, group: in
             for batch in batches:
                 (videos, vlen), (audios, alen), (melspecs, mlen, _gate), face_crops = batch
                 with torch.no_grad():
-                    emb = _voice_embedding(encoding, speaker_encoder, None, audios, device)
+                    emb = _voice_embedding(encoding, speaker_encoder, None, audios, device, alen)
                     yield batch, net(videos, face_crops, audios, melspecs, vlen, alen, mlen, 1, speaker_embedding=emb)
         finally:
             net.honour_video_lengths = was

@@ -274,6 +274,72 @@ int launch_frame_window(const float* audio, int B, int N, int L, int n_fft, int 
     return 0;
 }
 
+// ---- the same front-end over clips of unequal length packed into one buffer (l2s_speaker_encoder_packed), rows in the time-major compact layout:
+// frames[(step_row0[l] + r)*400 + j] = reflect_r(l*160 + j - 200) * hann[j] for the clip of rank r, reflected at ITS OWN 0 and n_r - 1 and read
+// from audio + off_r - nothing outside [off_r, off_r + n_r) is touched.
+// The table, carried to the device in kernel arguments like the length table of the masked entry points (no host buffer outlives the call)
+__global__ __launch_bounds__(64) void spk_table_kernel(const SpkChunk c, int32_t* __restrict__ table) {
+    for (int i = threadIdx.x; i < c.n; i += 64) table[i] = c.v[i];
+}
+int launch_spk_table(const int32_t* words_host, int64_t n_words, int32_t* table, hipStream_t s) {
+    for (int64_t base = 0; base < n_words; base += SPK_CHUNK) {
+        SpkChunk c{};
+        c.n = (int)std::min<int64_t>(SPK_CHUNK, n_words - base);
+        for (int i = 0; i < c.n; ++i) c.v[i] = words_host[base + i];
+        hipLaunchKernelGGL(spk_table_kernel, dim3(1), dim3(64), 0, s, c, table + base);
+    }
+    L2S_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+// One block per (rank, frame) of the B x L_max grid, lanes along j: a block's reads are one contiguous run of the clip (but for the reflected ends) and
+// its writes one contiguous row.  Which table: a block is handed (r, l) by its index, so ranks[r] (16 bytes) and step_row0[l] are two INDEPENDENT
+// loads and the audio address hangs off one of them - one dependent level.  A table per step alone (row base and count) would have to be searched for
+// the row's step, a chain of dependent loads per row; a table per row gives the same single level but is R x 16 bytes to carry in kernel arguments
+// (38 table launches for 16 clips of 3 s) against B x 16 + (L_max + 1) x 4 (one).  Blocks with l >= L_r (B L_max - R of them) leave after the rank load.
+__global__ __launch_bounds__(256) void frame_window_packed_kernel(const float* __restrict__ audio, const SpkRank* __restrict__ ranks,
+                                                                  const int* __restrict__ step_row0, int64_t cells, int L_max, int n_fft, int hop,
+                                                                  const float* __restrict__ window, float* __restrict__ frames) {
+    const int half = n_fft / 2;
+    for (int64_t cell = blockIdx.x; cell < cells; cell += gridDim.x) {
+        const int r = (int)(cell / L_max), l = (int)(cell - (int64_t)r * L_max);
+        const SpkRank k = ranks[r];
+        if (l >= k.n / hop + 1) continue;
+        const float* x = audio + k.off;
+        float* dst = frames + ((int64_t)step_row0[l] + r) * n_fft;
+        for (int j = threadIdx.x; j < n_fft; j += 256) {
+            int i = l * hop + j - half;
+            if (i < 0) i = -i;
+            if (i >= k.n) i = 2 * (k.n - 1) - i;
+            dst[j] = x[i] * window[j];
+        }
+    }
+}
+int launch_frame_window_packed(const float* audio_packed, const SpkRank* ranks, const int* step_row0, int B, int L_max, int n_fft, int hop, const float* window,
+                               float* frames, hipStream_t s) {
+    const int64_t cells = (int64_t)B * L_max;
+    ProfScope ps("spk_frame_window_packed", s);
+    hipLaunchKernelGGL(frame_window_packed_kernel, dim3((unsigned)std::min<int64_t>(cells, 1 << 20)), dim3(256), 0, s, audio_packed, ranks, step_row0, cells, L_max,
+                       n_fft, hop, window, frames);
+    L2S_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+// the top layer's hidden state at each clip's own last frame, into call order: h_last[b] = hseq[step_row0[L_b - 1] + rank(b)]
+__global__ __launch_bounds__(256) void spk_last_hidden_kernel(const float* __restrict__ hseq, const SpkRank* __restrict__ ranks, const int* __restrict__ step_row0,
+                                                              int hop, float* __restrict__ h_last) {
+    const int r = blockIdx.x;
+    const SpkRank k = ranks[r];
+    const int64_t row = (int64_t)step_row0[k.n / hop] + r;
+    h_last[(int64_t)k.b * 256 + threadIdx.x] = hseq[row * 256 + threadIdx.x];
+}
+int launch_spk_last_hidden(const float* hseq, const SpkRank* ranks, const int* step_row0, int B, float* h_last, hipStream_t s) {
+    ProfScope ps("spk_last_hidden", s);
+    hipLaunchKernelGGL(spk_last_hidden_kernel, dim3(B), dim3(256), 0, s, hseq, ranks, step_row0, 160, h_last);
+    L2S_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
 // power[r][k] = re[r][k]^2 + im[r][k]^2 from the DFT GEMM output spec[r] = [re(0..nf-1) | im(0..nf-1)] (ld = lds); columns nf..ldp-1 zero
 __global__ __launch_bounds__(256) void power_kernel(const float* __restrict__ spec, int lds, int64_t rows, int nf, float* __restrict__ power, int ldp) {
     const int64_t total = rows * ldp;

@@ -864,6 +864,131 @@ static int speaker_run(l2s_model* m, const float* audio, int B, int N, float* em
     return launch_pool_norm_cat(lin, B, 1, 256, nullptr, 0, 1, nullptr, 0, emb, s);
 }
 
+// ---- the tower over B clips of unequal length (l2s_speaker_encoder_packed): every clip as speaker_run computes it alone at B = 1, N = n_b.
+// Rows in the time-major compact layout (torch's PackedSequence): clips by frame count L_b = n_b / 160 + 1 descending, ties in call order; frame l of
+// the clip of rank r is row step_row0[l] + r of R = sum L_b, step_row0 the prefix sum of step_rows[t] = #{b : L_b > t}.  Step t of the recurrence is
+// then the contiguous block of step_rows[t] rows at step_row0[t], and the rows that have ended are the LAST ones of the state buffers: the count only
+// falls, so they are never read again and the cell kernel needs no mask.
+struct SpkPlan { std::vector<int32_t> order, step_rows, step_row0; int L_max = 0; int64_t R = 0; };
+static int spk_packed_plan(const int64_t* n_samples, int B, SpkPlan& pl) {
+    L2S_REQUIRE(n_samples, "l2s speaker packed: n_samples is null");
+    if (B < 1 || B > L2S_SPK_MAX_CLIPS) {
+        set_error("l2s speaker packed: B = " + std::to_string(B) + " is outside [1, L2S_SPK_MAX_CLIPS = " + std::to_string(L2S_SPK_MAX_CLIPS) + "]");
+        return 1;
+    }
+    pl = SpkPlan{};
+    for (int b = 0; b < B; ++b) {
+        if (n_samples[b] <= 200 || n_samples[b] > (1ll << 30)) {
+            set_error("l2s speaker packed: n_samples[" + std::to_string(b) + "] = " + std::to_string(n_samples[b]) +
+                      " is outside [201, 2^30] (the reflect padding of 200 needs more than 200 samples)");
+            return 1;
+        }
+        const int L = (int)(n_samples[b] / 160) + 1;
+        pl.R += L;
+        pl.L_max = std::max(pl.L_max, L);
+    }
+    if (pl.R > L2S_SPK_MAX_ROWS) {
+        set_error("l2s speaker packed: R = " + std::to_string(pl.R) + " frames exceed L2S_SPK_MAX_ROWS = " + std::to_string(L2S_SPK_MAX_ROWS));
+        return 1;
+    }
+    pl.order.resize(B);
+    for (int b = 0; b < B; ++b) pl.order[b] = b;
+    std::stable_sort(pl.order.begin(), pl.order.end(), [&](int a, int b) { return n_samples[a] / 160 > n_samples[b] / 160; });
+    pl.step_rows.assign(pl.L_max, 0);
+    pl.step_row0.assign(pl.L_max + 1, 0);
+    for (int b = 0; b < B; ++b) pl.step_rows[n_samples[b] / 160] += 1;      // clips ENDING at step t ...
+    for (int t = pl.L_max - 2; t >= 0; --t) pl.step_rows[t] += pl.step_rows[t + 1];      // ... summed from the back: clips with L_b > t
+    for (int t = 0; t < pl.L_max; ++t) pl.step_row0[t + 1] = pl.step_row0[t] + pl.step_rows[t];
+    return 0;
+}
+static int64_t spk_table_words(int B, int L_max) { return (int64_t)B * (int64_t)(sizeof(SpkRank) / 4) + L_max + 1; }
+static int64_t spk_ws_bytes_packed(const SpkPlan& pl, int B) {
+    const int64_t f = pl.R * (400 + 402 + 204 + 40 + 1024 + 256 * 2) + (int64_t)pad16(B) * 256 * 3 + (int64_t)B * 256 * 2 + 64 * 16;
+    return f * (int64_t)sizeof(float) + align_up(spk_table_words(B, pl.L_max) * 4, 256) + (1 << 12);
+}
+
+static int speaker_packed_run(l2s_model* m, const float* audio, const int64_t* offsets, const int64_t* n_samples, const SpkPlan& pl, int B, float* emb, void* ws,
+                              int64_t ws_bytes, hipStream_t s L2S_SPK_TAPS_ARG) {
+    X3Scope x3scope(m->opt.infer_bf16 ? 0 : m->opt.gemm_x3);
+    Bf16Scope bf16scope(m->opt.infer_bf16);      // the bf16 leg: bf16-operand GEMM / Conv1d kernels instead of the f32 / split-bf16 ones
+    const Weights& w = m->w;
+    const int Bp = pad16(B), L = pl.L_max;
+    const int64_t R = pl.R;
+    Bump bp(ws, ws_bytes);
+    float* frames = bp.f(R * 400); float* spec = bp.f(R * 402); float* power = bp.f(R * 204); float* mel = bp.f(R * 40);
+    float* pre = bp.f(R * 1024); float* hseq[2] = {bp.f(R * 256), bp.f(R * 256)};
+    float* hf[2] = {bp.f((int64_t)Bp * 256), bp.f((int64_t)Bp * 256)}; float* cf = bp.f((int64_t)Bp * 256);
+    float* hlast = bp.f((int64_t)B * 256); float* lin = bp.f((int64_t)B * 256);
+    const int64_t words = spk_table_words(B, L);
+    int32_t* table = reinterpret_cast<int32_t*>(bp.f(words));
+    L2S_REQUIRE(!bp.overflow && ws_bytes >= spk_ws_bytes_packed(pl, B), "speaker-encoder workspace too small (l2s_speaker_workspace_bytes_packed)");
+    // the device table: B x SpkRank in rank order, then step_row0
+    std::vector<int32_t> host((size_t)words);
+    SpkRank* hr = reinterpret_cast<SpkRank*>(host.data());
+    for (int r = 0; r < B; ++r) { const int b = pl.order[r]; hr[r] = SpkRank{offsets[b], (int32_t)n_samples[b], b}; }
+    std::copy(pl.step_row0.begin(), pl.step_row0.end(), host.begin() + (size_t)B * (sizeof(SpkRank) / 4));
+    if (launch_spk_table(host.data(), words, table, s)) return 1;
+    const SpkRank* ranks = reinterpret_cast<const SpkRank*>(table);
+    const int* row0 = table + (int64_t)B * (sizeof(SpkRank) / 4);
+    if (launch_frame_window_packed(audio, ranks, row0, B, L, 400, 160, w.spk_window, frames, s)) return 1;
+    if (launch_gemm1(gemm_plain(frames, 400, w.spk_dft, spec, 402, (int)R, 402, 400), s, "spk_dft_gemm")) return 1;
+    L2S_SPK_TAP(0, spec, R * 402);
+    if (launch_power(spec, 402, R, 201, power, 204, s)) return 1;
+    L2S_SPK_TAP(1, power, R * 204);
+    if (launch_gemm1(gemm_plain(power, 204, w.spk_fbT, mel, 40, (int)R, 40, 204), s, "spk_mel_gemm")) return 1;
+    L2S_SPK_TAP(2, mel, R * 40);
+    const float* x = mel;
+    int xin = 40;
+    for (int l = 0; l < 3; ++l) {
+        GemmP g = gemm_plain(x, xin, w.spk_ih[l].W, pre, 1024, (int)R, 1024, xin);
+        g.shift = w.spk_ih[l].shift;
+        if (launch_gemm1(g, s, "spk_lstm_input_gemm")) return 1;
+        if (launch_fill(hf[0], (int64_t)Bp * 256, 0.f, s)) return 1;
+        if (launch_fill(hf[1], (int64_t)Bp * 256, 0.f, s)) return 1;
+        if (launch_fill(cf, (int64_t)Bp * 256, 0.f, s)) return 1;
+        float* out = hseq[l & 1];
+        for (int t = 0; t < L; ++t) {      // the unmasked cell launch on the step's own rows: state rows 0 .. step_rows[t] - 1 are the clips of those ranks
+            SkinnyBatch sb{};
+            SkinnyP p = sk_base(w.spk_hh[l], pl.step_rows[t]);
+            p.seg[0] = {hf[t & 1], 16}; p.nseg = 1;
+            p.epi = SK_LSTM; p.H = 256;
+            p.pre = pre + (int64_t)pl.step_row0[t] * 1024; p.ld_pre = 1024;
+            p.c_in = cf; p.c_out = cf;
+            p.h_out = hf[(t & 1) ^ 1]; p.h_out_K = 256; p.h_out_off = 0;
+            p.h_seq = out + (int64_t)pl.step_row0[t] * 256; p.ld_hseq = 256;
+            sb.p[0] = p; sb.ntiles[0] = 64; sb.count = 1;
+            if (launch_skinny(sb, s, "spk_lstm_step", m->opt)) return 1;
+        }
+        L2S_SPK_TAP(3 + l, out, R * 256);
+        x = out;
+        xin = 256;
+    }
+    // embeds = normalize(relu(linear(h_last))), h_last = top layer's output at each clip's own last frame, gathered into call order
+    if (launch_spk_last_hidden(x, ranks, row0, B, hlast, s)) return 1;
+    GemmP g = gemm_plain(hlast, 256, w.spk_linear.W, lin, 256, B, 256, 256);
+    g.shift = w.spk_linear.shift; g.act = ACT_RELU;
+    if (launch_gemm1(g, s, "spk_linear_gemm")) return 1;
+    L2S_SPK_TAP(6, lin, (int64_t)B * 256);
+    return launch_pool_norm_cat(lin, B, 1, 256, nullptr, 0, 1, nullptr, 0, emb, s);
+}
+
+// everything that can be refused is refused here, before the first launch: the outputs of a failed call are untouched
+static int speaker_packed_entry(l2s_model* m, const float* audio, const int64_t* offsets, const int64_t* n_samples, int B, float* emb, void* ws, int64_t ws_bytes,
+                                hipStream_t s L2S_SPK_TAPS_ARG) {
+    L2S_REQUIRE(audio && offsets && n_samples && emb && ws, "l2s speaker packed: null argument");
+    SpkPlan pl;
+    if (spk_packed_plan(n_samples, B, pl)) return 1;
+    for (int b = 0; b < B; ++b)
+        if (offsets[b] < 0) { set_error("l2s speaker packed: offsets[" + std::to_string(b) + "] = " + std::to_string(offsets[b]) + " is negative"); return 1; }
+    L2S_REQUIRE(m && m->finalized, "model not finalized (call l2s_model_finalize)");
+    L2S_REQUIRE(m->has_spk, "model holds no speaker_encoder.* weights");
+#ifdef L2S_DIAG
+    return speaker_packed_run(m, audio, offsets, n_samples, pl, B, emb, ws, ws_bytes, s, taps);
+#else
+    return speaker_packed_run(m, audio, offsets, n_samples, pl, B, emb, ws, ws_bytes, s);
+#endif
+}
+
 }  // namespace l2s
 
 // ================================================================================================ C ABI
@@ -1004,6 +1129,28 @@ int l2s_speaker_encoder_fwd(l2s_model* m, const float* audio, int B, int n_sampl
     L2S_REQUIRE(m->has_spk, "model holds no speaker_encoder.* weights");
     L2S_REQUIRE(audio && emb && ws && B > 0, "bad arguments");
     return speaker_run(m, audio, B, n_samples, emb, ws, ws_bytes, (hipStream_t)stream);
+}
+
+int l2s_speaker_packed_plan(const int64_t* n_samples, int B, int32_t* order, int32_t* step_rows, int32_t* step_row0, int* L_max, int64_t* R) {
+    L2S_REQUIRE(order && step_rows && step_row0 && L_max && R, "bad arguments");
+    SpkPlan pl;
+    if (spk_packed_plan(n_samples, B, pl)) return 1;
+    std::copy(pl.order.begin(), pl.order.end(), order);
+    std::copy(pl.step_rows.begin(), pl.step_rows.end(), step_rows);
+    std::copy(pl.step_row0.begin(), pl.step_row0.end(), step_row0);
+    *L_max = pl.L_max; *R = pl.R;
+    return 0;
+}
+
+int64_t l2s_speaker_workspace_bytes_packed(const int64_t* n_samples, int B) {
+    SpkPlan pl;
+    if (spk_packed_plan(n_samples, B, pl)) return -1;
+    return spk_ws_bytes_packed(pl, B);
+}
+
+int l2s_speaker_encoder_packed(l2s_model* m, const float* audio_packed, const int64_t* offsets, const int64_t* n_samples, int B, float* emb, void* ws,
+                               int64_t ws_bytes, void* stream) {
+    return speaker_packed_entry(m, audio_packed, offsets, n_samples, B, emb, ws, ws_bytes, (hipStream_t)stream);
 }
 
 int64_t l2s_face_workspace_bytes(int B, int H, int W) {
@@ -1441,6 +1588,11 @@ int l2s_op_speaker_taps(l2s_model* m, const float* audio, int B, int n_samples, 
     L2S_REQUIRE(m->has_spk, "model holds no speaker_encoder.* weights");
     L2S_REQUIRE(audio && taps && emb && ws && B > 0, "bad arguments");
     return speaker_run(m, audio, B, n_samples, emb, ws, ws_bytes, (hipStream_t)stream, taps);
+}
+int l2s_op_speaker_taps_packed(l2s_model* m, const float* audio_packed, const int64_t* offsets, const int64_t* n_samples, int B, float* const* taps, float* emb,
+                               void* ws, int64_t ws_bytes, void* stream) {
+    L2S_REQUIRE(taps, "bad arguments");
+    return speaker_packed_entry(m, audio_packed, offsets, n_samples, B, emb, ws, ws_bytes, (hipStream_t)stream, taps);
 }
 
 #endif

@@ -468,6 +468,16 @@ int launch_zero_slot_rows(float* z, int ldz, float* dis, int n, int B, int m, co
 int launch_step_attn_masked(const AttnP& at, const SkinnyP& pre2, int pre2_tiles, const int* lens, hipStream_t s, int lds_values = 1, int skip0 = 0);
 int launch_frame_window(const float* audio, int B, int N, int L, int n_fft, int hop, const float* window, float* frames, hipStream_t s);
 int launch_power(const float* spec, int lds, int64_t rows, int nf, float* power, int ldp, hipStream_t s);
+// ---- the voice tower over clips of unequal length (l2s_speaker_encoder_packed): the time-major compact layout - frame l of the clip of rank r (clips
+// by frame count descending) is row step_row0[l] + r.  Device table, int32 words: B x SpkRank, then step_row0[0 .. L_max]
+struct SpkRank { int64_t off; int32_t n; int32_t b; };         // the clip of one rank: float offset into the packed audio, samples, index in call order
+constexpr int SPK_CHUNK = 512;                                 // table words per table-writing launch (they travel in the kernel arguments)
+struct SpkChunk { int32_t v[SPK_CHUNK]; int n; };
+int launch_spk_table(const int32_t* words_host, int64_t n_words, int32_t* table, hipStream_t s);
+int launch_frame_window_packed(const float* audio_packed, const SpkRank* ranks, const int* step_row0, int B, int L_max, int n_fft, int hop, const float* window,
+                               float* frames, hipStream_t s);
+// h_last[b] = hseq[step_row0[L_b - 1] + rank(b)], 256 wide, in call order
+int launch_spk_last_hidden(const float* hseq, const SpkRank* ranks, const int* step_row0, int B, float* h_last, hipStream_t s);
 // ---------------------------------------------------------------- mel filterbank band tables (vocoder.hip; read by l2s_inverse_mel and l2s_mel_targets)
 constexpr int IM_MAXF = 576;      // 9 bins per lane
 constexpr int IM_MAXM = 128;      // 2 mel bands per lane

@@ -34,6 +34,7 @@ ABI_SYMBOLS = (
     "l2s_workspace_bytes_masked", "l2s_masked_bilstm_plan", "l2s_inference_masked", "l2s_forward_eval_masked", "l2s_decoder_prologue_masked", "l2s_decode_steps_masked",
     "l2s_ragged_plan", "l2s_workspace_bytes_ragged", "l2s_inference_ragged",
     "l2s_output_lengths", "l2s_inference", "l2s_inference_multi", "l2s_workspace_bytes_multi", "l2s_forward_eval", "l2s_forward_eval_multi", "l2s_model_set_option", "l2s_persist_available", "l2s_persist_timeouts", "l2s_set_thread_chains", "l2s_speaker_workspace_bytes", "l2s_speaker_encoder_fwd",
+    "l2s_speaker_packed_plan", "l2s_speaker_workspace_bytes_packed", "l2s_speaker_encoder_packed",
     "l2s_face_workspace_bytes", "l2s_face_encoder_fwd",
     "l2s_inverse_mel_workspace_bytes", "l2s_inverse_mel", "l2s_griffin_lim_workspace_bytes", "l2s_griffin_lim", "l2s_estoi_workspace_bytes", "l2s_estoi_workspace_bytes_long", "l2s_estoi",
     "l2s_set_option",
@@ -48,7 +49,7 @@ ABI_SYMBOLS = (
 # what include/l2s_diag.h adds: exported by libl2s_diag.so only
 DIAG_SYMBOLS = (
     "l2s_op_gemm", "l2s_op_conv1d", "l2s_op_gemm_ex", "l2s_op_conv1d_ex", "l2s_op_conv1d_bwd", "l2s_op_frontend", "l2s_op_launch_chain", "l2s_op_launch_chain2", "l2s_op_skinny_timeline", "l2s_op_attn_timeline", "l2s_op_flat_timeline", "l2s_op_pdecode_timeline", "l2s_op_gemm_x3_timeline", "l2s_op_fused_unit_timeline", "l2s_op_lstm_cell_chain", "l2s_op_step_attn_chain", "l2s_op_stamp_log",
-    "l2s_op_face_conv2d", "l2s_op_face_taps", "l2s_op_speaker_taps",
+    "l2s_op_face_conv2d", "l2s_op_face_taps", "l2s_op_speaker_taps", "l2s_op_speaker_taps_packed",
 )
 
 # run-time options only the diagnostic build accepts (block-form A/B switches of the same arithmetic, include/l2s_diag.h)
@@ -208,6 +209,14 @@ def _bind(L: ctypes.CDLL) -> None:
         L.l2s_mel_targets_workspace_bytes.restype = _i64
         L.l2s_mel_targets.argtypes = [_fp, ctypes.POINTER(_i64), ctypes.POINTER(_i64), _i, _fp, _i, _i, _i, _i, _i, ctypes.c_float, _i, _i64, _fp, _fp, _fp, _vp,
                                       _vp, _i64, _vp]
+    # the voice tower over clips of unequal length (include/l2s.h): likewise absent from a library built before it
+    # (tools/speaker_packed/time_speaker_packed.py times one next to this build)
+    if hasattr(L, "l2s_speaker_encoder_packed"):
+        _lens, _ns = ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(_i64)
+        L.l2s_speaker_packed_plan.argtypes = [_ns, _i, _lens, _lens, _lens, ctypes.POINTER(_i), ctypes.POINTER(_i64)]
+        L.l2s_speaker_workspace_bytes_packed.argtypes = [_ns, _i]
+        L.l2s_speaker_workspace_bytes_packed.restype = _i64
+        L.l2s_speaker_encoder_packed.argtypes = [_vp, _fp, _ns, _ns, _i, _fp, _vp, _i64, _vp]
 
 
 def _bind_diag(L: ctypes.CDLL) -> None:
@@ -231,6 +240,7 @@ def _bind_diag(L: ctypes.CDLL) -> None:
     L.l2s_op_face_conv2d.argtypes = [_fp, _i64, _i, _i, _i, _i, _fp, _fp, _fp, _fp, _i, _fp, _i, _i, _i, _i, _i, _i, _vp]
     L.l2s_op_face_taps.argtypes = [_vp, _fp, _i64, _i, _vp, _fp, _fp, _vp, _i64, _vp]
     L.l2s_op_speaker_taps.argtypes = [_vp, _fp, _i, _i, _vp, _fp, _vp, _i64, _vp]
+    L.l2s_op_speaker_taps_packed.argtypes = [_vp, _fp, ctypes.POINTER(_i64), ctypes.POINTER(_i64), _i, _vp, _fp, _vp, _i64, _vp]
 
 
 def check(rc: int, L: Optional[ctypes.CDLL] = None) -> None:
@@ -321,6 +331,37 @@ def ragged_plan(batch_B, batch_T, video_lengths):
     check(lib().l2s_ragged_plan(G, (i32 * G)(*[int(b) for b in batch_B]), (i32 * G)(*[int(t) for t in batch_T]), (i32 * max(n, 1))(*flat), f0, p0,
                                 ctypes.byref(N), ctypes.byref(Tmax)))
     return list(f0[:N.value + 1]), list(p0[:N.value + 1]), N.value, Tmax.value
+
+
+def speaker_packed_plan(samples):
+    """`l2s_speaker_packed_plan`: the time-major compact layout of the voice tower over clips of these sample counts, a pure host function of the
+    library.  Returns `(order, step_rows, step_row0, L_max, R)`: the clips by frame count L_b = n_b // 160 + 1 descending (ties in call order), the
+    clips still running at step t (L_max entries), its prefix sum (L_max + 1 entries) and R = sum L_b.  Frame l of the clip of rank r is row
+    `step_row0[l] + r`.  Raises `RuntimeError` with the library's message for lengths outside the limits."""
+    ns = [int(v) for v in samples]
+    B = len(ns)
+    lmax = max([n // 160 + 1 for n in ns if n > 0] or [1])
+    i32 = ctypes.c_int32
+    order, rows, row0 = (i32 * max(B, 1))(), (i32 * lmax)(), (i32 * (lmax + 1))()
+    L_max, R = _i(), _i64()
+    check(lib().l2s_speaker_packed_plan((_i64 * max(B, 1))(*ns), B, order, rows, row0, ctypes.byref(L_max), ctypes.byref(R)))
+    return list(order[:B]), list(rows[:L_max.value]), list(row0[:L_max.value + 1]), L_max.value, R.value
+
+
+def _host_ints(v, name: str):
+    """offsets / samples of a packed call: a host list, or an integer tensor that is already on the host (a device tensor would cost a sync)."""
+    if isinstance(v, torch.Tensor):
+        if v.is_cuda:
+            raise ValueError(f"{name} must stay on the host (the library plans its launches from it): got a device tensor")
+        if v.is_floating_point() or v.dtype == torch.bool:
+            raise TypeError(f"{name} must hold integers, got {v.dtype}")
+        v = v.tolist()
+    out = []
+    for x in v:
+        if isinstance(x, float) or isinstance(x, bool):
+            raise TypeError(f"{name} must hold integers, got {type(x).__name__}")
+        out.append(int(x))
+    return out
 
 
 class NativeModel:
@@ -633,6 +674,37 @@ class NativeModel:
             _dcheck(diag().l2s_op_speaker_taps(self._h, _ptr(audio), B, N, arr, _ptr(emb), _ptr(ws), ws.numel(), _stream()))
             return emb, outs
         self._check(self._L.l2s_speaker_encoder_fwd(self._h, _ptr(audio), B, N, _ptr(emb), _ptr(ws), ws.numel(), _stream()))
+        return emb
+
+    def speaker_encoder_packed(self, audio_packed: torch.Tensor, offsets, samples, taps: bool = False):
+        """`l2s_speaker_encoder_packed`: the voice tower over B clips of unequal length, each embedding what `speaker_encoder_fwd` gives for that clip
+        alone.  `audio_packed`: a device fp32 buffer of any shape; clip b is `samples[b]` floats at float offset `offsets[b]` of it (a padded (B, N)
+        tensor: offsets b * N).  `offsets` / `samples`: host lists or host integer tensors.  -> emb (B,256) in call order.  taps=True (diagnostic
+        library only): also the seven stage outputs of `l2s_op_speaker_taps_packed` in the compact layout of `speaker_packed_plan` - spec (R,402),
+        power (R,204), mel (R,40), the three hidden sequences (R,256), linear (B,256)."""
+        audio_packed = _f32(audio_packed)
+        off, ns = _host_ints(offsets, "offsets"), _host_ints(samples, "samples")
+        B = len(ns)
+        if B < 1 or len(off) != B:
+            raise ValueError(f"offsets and samples must hold one entry per clip (at least one): got {len(off)} and {B}")
+        last = max(o + n for o, n in zip(off, ns))
+        if last > audio_packed.numel():
+            raise ValueError(f"a clip ends at float {last} of a buffer of {audio_packed.numel()}")
+        L, dev = (diag() if taps else self._L), audio_packed.device
+        c_off, c_ns = (_i64 * B)(*off), (_i64 * B)(*ns)
+        need = int(L.l2s_speaker_workspace_bytes_packed(c_ns, B))
+        if need < 0:
+            check(1, L)
+        emb = torch.empty(B, 256, dtype=torch.float32, device=dev)
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        if taps:
+            R = sum(n // 160 + 1 for n in ns)
+            shapes = [(R, 402), (R, 204), (R, 40)] + [(R, 256)] * 3 + [(B, 256)]
+            outs = [torch.empty(s, dtype=torch.float32, device=dev) for s in shapes]
+            arr = (_vp * 7)(*[t.data_ptr() for t in outs])
+            _dcheck(L.l2s_op_speaker_taps_packed(self._h, _ptr(audio_packed), c_off, c_ns, B, arr, _ptr(emb), _ptr(ws), ws.numel(), _stream()))
+            return emb, outs
+        self._check(L.l2s_speaker_encoder_packed(self._h, _ptr(audio_packed), c_off, c_ns, B, _ptr(emb), _ptr(ws), ws.numel(), _stream()))
         return emb
 
     def _faces(self, faces: torch.Tensor):
