@@ -86,6 +86,15 @@ int l2s_op_speaker_taps(l2s_model* m, const float* audio, int B, int n_samples, 
  * in call order.  One body with the product entry point, as above */
 int l2s_op_speaker_taps_packed(l2s_model* m, const float* audio_packed, const int64_t* offsets, const int64_t* n_samples, int B, float* const* taps, float* emb,
                                void* ws, int64_t ws_bytes, void* stream);
+/* l2s_encoder_fwd plus stage taps: taps = 18 dev pointers (each may be NULL) receiving, with NF = B * T frames, channels last: [0] the front-end map
+ * (NF, H/4, H/4, 24); [1 + u] the output of ShuffleNet unit u = 0 .. 15 in its shuffled channel order, (NF, h, h, cout) with h = H/8 and cout = 116 for
+ * u = 0 - 3, ceil(H/16) and 232 for u = 4 - 11, ceil(H/32) and 464 for u = 12 - 15 - what the trunk's ping-pong buffers hold; [17] the conv_last output
+ * (NF * h * h, 768) before pooling.  Same kernels, same launches: each tap is a device-to-device copy put on the stream after the launch that wrote the
+ * buffer.  A unit interior to a stage-chain launch (option "trunk_chain": by default units 1 - 2 and 5 - 10, at 2 also 13 - 14) never reaches memory:
+ * a non-NULL pointer for it fails the call before anything is launched, with a message that names the unit.  ws_bytes >= l2s_workspace_bytes(B,T,H,W,1),
+ * else the call fails before it launches anything.  The padded call only (no ragged groups) */
+int l2s_op_encoder_taps(l2s_model* m, const float* video, int B, int T, int H, int W, float* const* taps, float* feat, void* ws, int64_t ws_bytes,
+                        void* stream);
 /* average duration (us) of the decoder LSTM-cell kernel over a chain of n_pairs x {layer 0, layer 1} launches bracketed by ONE pair
  * of HIP events on `stream` (bench.py's roofline figure; synchronises) */
 int l2s_op_lstm_cell_chain(l2s_model* m, int B, int n_pairs, void* ws, int64_t ws_bytes, void* stream, double* avg_us);

@@ -190,8 +190,42 @@ static FrameSrc frame_src(const float* video, int B) { FrameSrc f{}; f.p[0] = vi
 
 // rg (a ragged group, l2s_inference_ragged): the front-end and the trunk run on the rg->NF real frames of the group's clips, compact; vis comes out as
 // (rg->N, rg->Tmax, 1024) with zero rows past each clip's length.  B, T are then rg->N, rg->Tmax.
+// whether a run of `run` stride-1 units starting with U at map size h goes out as ONE stage-chain launch (a fused trunk: "fuse_trunk").  One statement of
+// the rule for encoder_run's loop and for the tap check that runs before the first launch; a macro, so that the loop compiles to the code it was
+#define S1_RUN_CHAINED(m, U, run, h) \
+    ((m)->opt.trunk_chain && ((h) >= 6 || (m)->opt.trunk_chain >= 2) && (m)->opt.trunk_x3 && (U).pw1_p3 && (U).pw2_p3 && (run) >= 2 && (run) <= S1_CHAIN_MAX)
+#ifdef L2S_DIAG      // stage taps (l2s_op_encoder_taps): a host-side copy of the buffer a launch has just written, device to device on the call's stream
+static int enc_tap(float* const* taps, int i, const float* src, int64_t n, hipStream_t s) {
+    if (taps && taps[i]) L2S_CHECK_HIP(hipMemcpyAsync(taps[i], src, (size_t)n * sizeof(float), hipMemcpyDeviceToDevice, s));
+    return 0;
+}
+static int enc_tap_interior(int u) {
+    set_error("l2s: encoder tap of unit " + std::to_string(u) + " asked for, but the unit is interior to a stage-chain launch and its output never reaches memory (option \"trunk_chain\")");
+    return 1;
+}
+// before the first launch: walks the units as encoder_run's loop does and refuses a tap of a unit that a stage-chain launch keeps on chip
+static int enc_taps_check(const l2s_model* m, float* const* taps, int h) {
+    if (!taps || !m->opt.fuse_trunk) return 0;
+    for (int u = 0; u < N_UNITS; ++u) {
+        const UnitW& U = m->w.unit[u];
+        if (U.stride2) { h = (h + 1) / 2; continue; }
+        int run = 1;
+        while (u + run < N_UNITS && !m->w.unit[u + run].stride2 && m->w.unit[u + run].half == U.half) ++run;
+        if (!S1_RUN_CHAINED(m, U, run, h)) continue;
+        for (int i = 0; i < run - 1; ++i)
+            if (taps[1 + u + i]) return enc_tap_interior(u + i);
+        u += run - 1;
+    }
+    return 0;
+}
+#define L2S_ENC_TAP(i, src, n) do { if (enc_tap(taps, i, src, n, s)) return 1; } while (0)
+#define L2S_ENC_TAPS_ARG , float* const* taps = nullptr
+#else
+#define L2S_ENC_TAP(i, src, n) do {} while (0)
+#define L2S_ENC_TAPS_ARG
+#endif
 static int encoder_run(l2s_model* m, const FrameSrc& video, int B, int T, int H, int W, const float* emb, float* vis,
-                       float* feat, void* ws, int64_t ws_bytes, hipStream_t s, const RaggedTab* rg = nullptr) {
+                       float* feat, void* ws, int64_t ws_bytes, hipStream_t s, const RaggedTab* rg = nullptr L2S_ENC_TAPS_ARG) {
     X3Scope x3scope(m->opt.infer_bf16 ? 0 : m->opt.gemm_x3);
     Bf16Scope bf16scope(m->opt.infer_bf16);      // the bf16 leg: bf16-operand GEMM / Conv1d kernels instead of the f32 / split-bf16 ones
     const Weights& w = m->w;
@@ -199,12 +233,16 @@ static int encoder_run(l2s_model* m, const FrameSrc& video, int B, int T, int H,
     Bump bp(ws, ws_bytes);
     float* a = bp.f(pl.act_a); float* b = bp.f(pl.act_b); float* t1 = bp.f(pl.t1); float* t2 = bp.f(pl.t2); float* last = bp.f(pl.last);
     L2S_REQUIRE(!bp.overflow, "encoder workspace too small");
+#ifdef L2S_DIAG
+    if (enc_taps_check(m, taps, pl.Hp)) return 1;
+#endif
     FrontendW fe = w.fe;
     if (!m->opt.frontend_x3) fe.w3 = nullptr;
     fe.pair = m->opt.frontend_x3 >= 2; fe.pipe = m->opt.frontend_x3 == 3;
     fe.solo = m->opt.frontend_solo && (m->opt.frontend_solo >= 2 || chains_hint() >= 2);
     if (!m->opt.infer_bf16) fe.w1 = nullptr;
     if (rg ? launch_frontend_ragged(fe, video, *rg, H, W, a, s) : launch_frontend(fe, video, B, T, H, W, a, s)) return 1;
+    L2S_ENC_TAP(0, a, (int64_t)pl.NF * pl.Hp * pl.Hp * STAGE_CH[0]);
     float* x = a; float* y = b;
     int h = pl.Hp;
     const int NF = pl.NF;
@@ -250,7 +288,7 @@ static int encoder_run(l2s_model* m, const FrameSrc& video, int B, int T, int H,
             // the run of stride-1 units that starts here (the rest of the stage) as ONE launch: the map stays on chip between the units
             int run = 1;
             while (u + run < N_UNITS && !w.unit[u + run].stride2 && w.unit[u + run].half == half) ++run;
-            if (m->opt.trunk_chain && (h >= 6 || m->opt.trunk_chain >= 2) && m->opt.trunk_x3 && U.pw1_p3 && U.pw2_p3 && run >= 2 && run <= S1_CHAIN_MAX) {
+            if (S1_RUN_CHAINED(m, U, run, h)) {
                 ShuffleS1P chain[S1_CHAIN_MAX];
                 for (int i = 0; i < run; ++i) chain[i] = s1_params(w.unit[u + i], x, y);
                 if (launch_shuffle_s1_chain(chain, run, s)) return 1;
@@ -266,6 +304,7 @@ static int encoder_run(l2s_model* m, const FrameSrc& video, int B, int T, int H,
             if (launch_dwconv(t1, NF, h, h, half, 0, half, 1, U.dw.w9, U.dw.scale, U.dw.shift, t2, half, 0, s)) return 1;
             if (launch_gemm1(pw_gemm(t2, half, 0, U.pw2, y, cout, 1, 2, px, half, half, ACT_RELU), s, "shuffle_pw_gemm")) return 1;
         }
+        L2S_ENC_TAP(1 + u, y, (int64_t)NF * h * h * cout);      // u: the unit whose output y now holds (the last one of a chain)
         std::swap(x, y);
     }
     const int64_t px = (int64_t)NF * h * h;
@@ -274,6 +313,7 @@ static int encoder_run(l2s_model* m, const FrameSrc& video, int B, int T, int H,
         if (!m->opt.gemm_x3_dma) pc.W3 = nullptr;
         if (launch_gemm1(pc, s, "conv_last_gemm")) return 1;
     }
+    L2S_ENC_TAP(N_UNITS + 1, last, px * LAST_CH);
     if (rg) return launch_pool_norm_cat_ragged(last, *rg, h * h, LAST_CH, emb, L2S_D_EMB, vis, L2S_D_VIS, s);
     if (launch_pool_norm_cat(last, NF, h * h, LAST_CH, emb, L2S_D_EMB, T, vis, L2S_D_VIS, feat, s)) return 1;
     return 0;
@@ -1582,6 +1622,13 @@ int l2s_op_face_taps(l2s_model* m, const float* faces, int64_t batch_stride, int
     L2S_REQUIRE(m->has_face, "model holds no vgg_face.* weights");
     L2S_REQUIRE(faces && taps && emb && ws && B > 0 && batch_stride >= (int64_t)3 * 160 * 160, "bad arguments");
     return face_run(m, faces, batch_stride, B, proj, emb, ws, ws_bytes, (hipStream_t)stream, taps);
+}
+int l2s_op_encoder_taps(l2s_model* m, const float* video, int B, int T, int H, int W, float* const* taps, float* feat, void* ws, int64_t ws_bytes, void* stream) {
+    L2S_ENC_READY(m);
+    L2S_REQUIRE(video && taps && feat && ws && B > 0 && T > 0, "bad arguments");
+    // the published size of the call, not what the encoder's carve happens to need
+    L2S_REQUIRE(ws_bytes >= l2s_workspace_bytes(B, T, H, W, 1), "encoder workspace too small");
+    return encoder_run(m, frame_src(video, B), B, T, H, W, nullptr, nullptr, feat, ws, ws_bytes, (hipStream_t)stream, nullptr, taps);
 }
 int l2s_op_speaker_taps(l2s_model* m, const float* audio, int B, int n_samples, float* const* taps, float* emb, void* ws, int64_t ws_bytes, void* stream) {
     L2S_MODEL_READY(m);

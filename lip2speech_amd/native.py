@@ -49,7 +49,7 @@ ABI_SYMBOLS = (
 # what include/l2s_diag.h adds: exported by libl2s_diag.so only
 DIAG_SYMBOLS = (
     "l2s_op_gemm", "l2s_op_conv1d", "l2s_op_gemm_ex", "l2s_op_conv1d_ex", "l2s_op_conv1d_bwd", "l2s_op_frontend", "l2s_op_launch_chain", "l2s_op_launch_chain2", "l2s_op_skinny_timeline", "l2s_op_attn_timeline", "l2s_op_flat_timeline", "l2s_op_pdecode_timeline", "l2s_op_gemm_x3_timeline", "l2s_op_fused_unit_timeline", "l2s_op_lstm_cell_chain", "l2s_op_step_attn_chain", "l2s_op_stamp_log",
-    "l2s_op_face_conv2d", "l2s_op_face_taps", "l2s_op_speaker_taps", "l2s_op_speaker_taps_packed",
+    "l2s_op_face_conv2d", "l2s_op_face_taps", "l2s_op_speaker_taps", "l2s_op_speaker_taps_packed", "l2s_op_encoder_taps",
 )
 
 # run-time options only the diagnostic build accepts (block-form A/B switches of the same arithmetic, include/l2s_diag.h)
@@ -241,6 +241,7 @@ def _bind_diag(L: ctypes.CDLL) -> None:
     L.l2s_op_face_taps.argtypes = [_vp, _fp, _i64, _i, _vp, _fp, _fp, _vp, _i64, _vp]
     L.l2s_op_speaker_taps.argtypes = [_vp, _fp, _i, _i, _vp, _fp, _vp, _i64, _vp]
     L.l2s_op_speaker_taps_packed.argtypes = [_vp, _fp, ctypes.POINTER(_i64), ctypes.POINTER(_i64), _i, _vp, _fp, _vp, _i64, _vp]
+    L.l2s_op_encoder_taps.argtypes = [_vp, _fp, _i, _i, _i, _i, _vp, _fp, _vp, _i64, _vp]
 
 
 def check(rc: int, L: Optional[ctypes.CDLL] = None) -> None:
@@ -364,6 +365,18 @@ def _host_ints(v, name: str):
     return out
 
 
+def encoder_tap_shapes(NF: int, H: int):
+    """Shapes of the 18 taps of l2s_op_encoder_taps (include/l2s_diag.h) for NF frames of H x H pixels.  Diagnostic only: encoder_fwd(taps=...) sizes
+    its tap tensors with it.  The widths and unit counts restate STAGE_CH = {24, 116, 232, 464}, LAST_CH = 768 and the 4 / 8 / 4 units per stage of
+    lip2speech_amd/csrc/l2s_model.h; the map halves, rounded up, at the first (stride-2) unit of each stage, as in encoder_run."""
+    h = H // 4
+    shapes = [(NF, h, h, 24)]
+    for cout, n in ((116, 4), (232, 8), (464, 4)):
+        h = (h + 1) // 2
+        shapes += [(NF, h, h, cout)] * n
+    return shapes + [(NF * h * h, 768)]
+
+
 class NativeModel:
     """Owns an ``l2s_model`` (the packed device weight blob)."""
 
@@ -413,12 +426,21 @@ class NativeModel:
         return ws
 
     # ------------------------------------------------------------------ stages
-    def encoder_fwd(self, video: torch.Tensor) -> torch.Tensor:
+    def encoder_fwd(self, video: torch.Tensor, taps=None):
+        """VideoExtractor.forward: video (B,3,T,H,W) -> feat (B,T,768).  taps = an iterable of tap indices (diagnostic library only): also the stage
+        outputs of l2s_op_encoder_taps, as (feat, {index: tensor}) - 0 the front-end map, 1 + u the output of ShuffleNet unit u (channels last, shuffled
+        order), 17 the conv_last output.  A unit interior to a stage-chain launch raises with the library's message."""
         video = _f32(video)
         B, C, T, H, W = video.shape
         assert C == 3, "frames are (B,3,T,H,W) RGB"
         feat = torch.empty(B, T, 768, dtype=torch.float32, device=video.device)
         ws = self.workspace(B, T, H, W, 1, video.device)
+        if taps is not None:
+            shapes = encoder_tap_shapes(B * T, H)
+            outs = {int(i): torch.empty(shapes[int(i)], dtype=torch.float32, device=video.device) for i in taps}
+            arr = (_vp * len(shapes))(*[outs[i].data_ptr() if i in outs else None for i in range(len(shapes))])
+            _dcheck(diag().l2s_op_encoder_taps(self._h, _ptr(video), B, T, H, W, arr, _ptr(feat), _ptr(ws), ws.numel(), _stream()))
+            return feat, outs
         self._check(self._L.l2s_encoder_fwd(self._h, _ptr(video), B, T, H, W, _ptr(feat), _ptr(ws), ws.numel(), _stream()))
         return feat
 
