@@ -490,8 +490,9 @@ int l2s_train_encoder_bwd(l2s_model* m, const float* video, int B, int T, int H,
  *                            output frames per block with the next slab's staging interleaved between the MFMAs, 2 = the same with a staging phase of its
  *                            own (same bits), 1 = one frame per block, 0 = the f32 MFMA kernel
  *   "trunk_x3"          (1)  the fused ShuffleNet units' pointwise convs on the split-bf16 path; 0 = f32 MFMA
- *   "lstm_x3"           (3)  the decode step's two LSTM launches on the split-bf16 path (1 / 2 / 3: four-wave / eight-wave / half-CU block forms of the
- *                            same arithmetic, same bits - 3 picks by l2s_set_thread_chains); 0 = f32 MFMAs (other bits, rounding-level)
+ *   "lstm_x3"           (4)  the decode step's two LSTM launches on the split-bf16 path (1 / 2 / 3: four-wave / eight-wave / half-CU block forms of the
+ *                            same arithmetic, same bits - 3 picks by l2s_set_thread_chains; 4 = as 3, with the K = 1024 launches as one 64 x 64 block
+ *                            per CU whose column halves share one activation panel); 0 = f32 MFMAs (other bits, rounding-level)
  *   "early_stop"        (0)  free-running inference (l2s_inference, l2s_inference_multi, l2s_decode_steps without teacher frames) ends the decode loop once
  *                            every clip of the call has stopped, instead of always running S steps as the reference does (decoder.py:412-435).  With
  *                            len_b = the clip's output_lengths entry, E_b = min(S, len_b + 10) and E = max E_b over the call's rows (all G x B of a group):

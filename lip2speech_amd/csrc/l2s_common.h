@@ -58,10 +58,12 @@ struct Options {
     int rc_shape = 0;           // "skinny_rc": register-blocked batch-row blocks for >= 64 rows: 0 = by tile count, 11 = never, 21 / 22 / 42 = force RT x CT
     int rc_jb = 0;              // "skinny_rc_jb": operand batching of the register-blocked blocks: 0 = 4x2 blocks one chunk per batch and four batches in flight, smaller shapes two chunks per batch and two in flight; 2 / 4 = that many chunks per batch, two in flight, every shape; 15 = 4x2 with five in flight
     int gemm_x3_dma = 1;        // "gemm_x3_dma": constant Conv1d / Linear weights of the split-bf16 GEMMs as pre-split planes fetched by LDS-DMA (ConvW::W3)
-    int lstm_x3 = 3;            // "lstm_x3": the decode step's LSTM launches on the bf16 matrix cores (exact three-way split, pre-split weight planes): 2 = eight-wave
-                                //   blocks, 1 = four-wave blocks, 3 (default) = as 2, but the 4x2 blocks (>= 192 rows) as four-wave blocks of at most 256 registers - half
-                                //   a compute unit, so that kernels of other launch chains run beside them (all the same bits), 0 = the f32 MFMA form
-    int half_min_mts = 12;      // "half_min_mts": with "lstm_x3" = 3 and chains overlapping, an LSTM launch takes the half-CU 4x2 form from this many 16-row tiles
+    int lstm_x3 = 4;            // "lstm_x3": the decode step's LSTM launches on the bf16 matrix cores (exact three-way split, pre-split weight planes): 2 = eight-wave
+                                //   blocks, 1 = four-wave blocks, 3 = as 2, but the 4x2 blocks (>= 192 rows) as four-wave blocks of at most 256 registers - half
+                                //   a compute unit, so that kernels of other launch chains run beside them (all the same bits), 0 = the f32 MFMA form;
+                                //   4 (default) = as 3, but the K = 1024 launches (the step's two) as ONE eight-wave block per CU of 64 rows x 64 gate columns
+                                //   whose two column halves share one activation panel through LDS (skinny_block_sp); every other launch as 3.  Same bits
+    int half_min_mts = 12;      // "half_min_mts": with "lstm_x3" >= 3 and chains overlapping, an LSTM launch takes the half-CU 4x2 form (or the shared-panel form) from this many 16-row tiles
                                 //   on (13: where 4x2 blocks give >= 224 blocks anyway; 12: also the 192-row launches of a six-batch group, whose 384 2x2
                                 //   eight-wave blocks otherwise fill every CU for two rounds - the driver's 20-step command cuts into 7 + 7 + 6 batches:
                                 //   3.14-3.18 -> 3.21-3.29 M in three A/B pairs; 8: no better there, worse at 128 / 160 rows); same bits

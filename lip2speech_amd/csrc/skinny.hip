@@ -163,6 +163,27 @@ __global__ __launch_bounds__(512, 1) void skinny_rc8x_kernel(const SkinnyBatch b
     skinny_block_rcs<RT, CT, typename SkLay<LAYID>::T, DEPTH, true, false, 8, true>(batch.p[g], blockIdx.x, blockIdx.y, red, batch.ntiles[g], mts);
     L2S_BLOCK_STAMP_END(1u, batch.p[g].c_out);
 }
+// One activation panel per CU (option "lstm_x3" = 4, skinny_block_sp): two column-neighbouring half-CU 4x2 blocks as ONE eight-wave block of 64 rows x 64
+// gate columns that fetches and splits every activation chunk once for both halves (dynamic LDS: 160 KB, one block per CU).  Same bits.
+template <int LAYID, bool ES = false>
+__global__ __launch_bounds__(512, 1) void skinny_sp_kernel(const SkinnyBatch batch, int mts) {
+    if constexpr (ES) L2S_ES_RETURN(batch);
+    extern __shared__ __attribute__((aligned(16))) float sp_lds[];
+    const int g = blockIdx.z;
+    L2S_BLOCK_STAMP_BEGIN();
+    skinny_block_sp<typename SkLay<LAYID>::T>(batch.p[g], blockIdx.x, blockIdx.y, sp_lds, batch.ntiles[g], mts);
+    L2S_BLOCK_STAMP_END(4u, batch.p[g].c_out);
+}
+template <int LAYID>
+static int launch_sp(const SkinnyBatch& bl, int maxt, int mts, hipStream_t s) {
+    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(skinny_sp_kernel<LAYID, false>), hipFuncAttributeMaxDynamicSharedMemorySize, SKP_LDS_BYTES);
+    L2S_CHECK_HIP(attr);
+    static const hipError_t attr_es = hipFuncSetAttribute(reinterpret_cast<const void*>(skinny_sp_kernel<LAYID, true>), hipFuncAttributeMaxDynamicSharedMemorySize, SKP_LDS_BYTES);
+    L2S_CHECK_HIP(attr_es);
+    SK_ES_LAUNCH(bl.es_end, skinny_sp_kernel, (LAYID), dim3(maxt / 4, (mts + 3) / 4, bl.count), dim3(512), SKP_LDS_BYTES, s, bl, mts);
+    L2S_CHECK_HIP(hipGetLastError());
+    return 0;
+}
 // weight planes of the split-bf16 LSTM blocks from the packed fp32 fragments ([tile][chunk][lane] float4): chunk pair ip of K slice s = chunks
 // (s + 16 ip, s + 16 ip + 8); out[tile][s][ip][plane][lane] = 8 bf16 (the lane's quad of the first chunk, then of the second)
 __global__ __launch_bounds__(256) void skx_planes_kernel(const float4* __restrict__ Wf, int ntiles, int NC, uint4* __restrict__ out) {
@@ -471,7 +492,7 @@ int launch_skinny(const SkinnyBatch& b, hipStream_t s, const char* name, const O
             auto blocks = [&](int rt, int ct) { int n = 0; for (int i = 0; i < bl.count; ++i) n += (bl.ntiles[i] + ct - 1) / ct; return n * ((mts + rt - 1) / rt); };
             // (a 4x4 block - 33 % fewer operand bytes per tile - is MFMA-bound at 30.4 us per block: 512 rows in 31.9 us against 33.0 us with 4x2
             //  blocks in two rounds, and 256 accumulator + operand registers with spills; not kept)
-            if (blocks(4, 2) >= 224 || (o.lstm_x3 == 3 && chains_hint() >= 2 && o.half_min_mts > 0 && mts >= o.half_min_mts && n_lstm_all)) shape = 42;
+            if (blocks(4, 2) >= 224 || (o.lstm_x3 >= 3 && chains_hint() >= 2 && o.half_min_mts > 0 && mts >= o.half_min_mts && n_lstm_all)) shape = 42;
             else if (blocks(2, 2) >= 224) shape = 22;
             else if (blocks(2, 1) >= 224) shape = 21;
         }
@@ -487,9 +508,17 @@ int launch_skinny(const SkinnyBatch& b, hipStream_t s, const char* name, const O
     // that kernels of different chains run side by side on the CUs; a chain that has the chip to itself keeps the eight-wave blocks (3-4 % faster
     // alone).  Same bits either way.
     const bool overlap = chains_hint() >= 2;
-    int x3 = (o.rc_jb == 0 && rc_kind == 2 && (rc_lay == 1 || rc_lay == 2 || rc_lay == 6)) ? o.lstm_x3 : 0;      // LSTM launches on the bf16 matrix cores (1: four waves, 2: eight, 3: half-CU 4x2 blocks when chains overlap)
-    if (x3 == 3 && !overlap) x3 = 2;
+    int x3 = (o.rc_jb == 0 && rc_kind == 2 && (rc_lay == 1 || rc_lay == 2 || rc_lay == 6)) ? o.lstm_x3 : 0;      // LSTM launches on the bf16 matrix cores (1: four waves, 2: eight, 3: half-CU 4x2 blocks when chains overlap, 4: shared-panel blocks where they apply, else as 3)
+    if (x3 >= 3 && !overlap) x3 = 2;
     for (int i = 0; i < bl.count; ++i) if (!bl.p[i].W3) x3 = 0;
+    if (x3 == 4) {
+        // one activation panel per CU (skinny_sp_kernel) under the conditions of the half-CU 4x2 form, for the K = 1024 layouts and whole 4-tile column
+        // blocks; every other launch takes the form "lstm_x3" = 3 gives it
+        bool sp = shape == 42 && !g_skinny_ts && o.half_min_mts > 0 && mts >= o.half_min_mts && (rc_lay == 2 || rc_lay == 6);
+        for (int i = 0; i < bl.count; ++i) sp = sp && bl.ntiles[i] > 0 && bl.ntiles[i] % 4 == 0;
+        if (sp) return rc_lay == 2 ? launch_sp<2>(bl, maxt, mts, s) : launch_sp<6>(bl, maxt, mts, s);
+        x3 = 3;
+    }
     // several groups, >= 128 rows (below that the 1x1 / 2x1 uniform grids with two blocks per CU are faster, tools/time_step_phases.py): per-group
     // block shapes in one flat grid of at most one block per CU ("skinny_flat", default on)
     if (!g_skinny_ts && bl.count > 1 && mts >= 8 && o.skinny_flat && !o.rc_shape && !o.rc_shape_multi && maxk <= 1024 && rc_kind == 1) {      // a forced block shape wins; LSTM groups (the BiLSTM's two directions) keep the uniform grid of four-wave blocks

@@ -862,6 +862,220 @@ __device__ __forceinline__ void skinny_block_rcs(const SkinnyP& p, int tp, int m
     L2S_STAMP(7);
 }
 
+// Shared activation panel (option "lstm_x3" = 4): ONE eight-wave block per CU owns 4 row tiles x 4 column tiles - the two column-neighbouring half-CU
+// 4x2 blocks (SEQ, X3) that used to share the CU, fused.  Waves w and w + 4 (the same SIMD) are the two column halves of K slices w and w + 4; each
+// keeps the half-CU form's accumulators and its own weight planes.  What they no longer do twice is the activations: per K step (one chunk pair of the
+// slice) each wave fetches and splits only TWO of the four row tiles (column half hc: row tiles 2 hc, 2 hc + 1) and publishes the six bf16 planes
+// through a two-deep LDS ring; after the step's barrier both read the step's twelve planes from the ring.  A launch's 64 column blocks of 64 x 32
+// become 32 of 64 x 64: the activation bytes through the CU load paths and the split VALU halve, the weight planes and the fabric traffic stay.
+// Every wave runs the same straight-line program (the half only moves addresses), so the waits of the K loop stay exact.
+// Same bits: per K slice the chunk pairs in order, two alternating accumulators, the six products smallest first, partial tiles summed slice-ascending
+// by the cell threads - the split of a quad does not depend on which wave performs it.
+// LDS (163 840 bytes, dynamic): [2 halves][32 partial tiles of slices 0-3] 64 KB | ring [2][4 wave pairs][4 row tiles][3 planes][64 lanes] 16 B = 96 KB;
+// the partial tiles of slices 4-7 (64 KB) go over the ring once the K loop is through.
+constexpr int SKP_LO_FLOATS = 2 * 32 * 256, SKP_RING_U4 = 2 * 4 * 12 * 64, SKP_LDS_BYTES = SKP_LO_FLOATS * 4 + SKP_RING_U4 * 16;
+static_assert(SKP_LDS_BYTES <= 160 * 1024 && SKP_RING_U4 * 16 >= SKP_LO_FLOATS * 4, "one block per CU; the second half of the partial tiles fits over the ring");
+template <class LAY, int DW = 2>
+__device__ __forceinline__ void skinny_block_sp(const SkinnyP& p, int tp, int mg, float* lds, int ntiles, int mts) {
+    static_assert(LAY::STATIC && LAY::NC % (2 * SK_WAVES) == 0, "static layout, whole chunk pairs per slice");
+    constexpr int RT = 4, CT = 2, NW = 4, NT = RT * CT, HR = 2;      // per column half: the half-CU 4x2 block; HR = row tiles a wave fetches and splits
+    constexpr int MAXC = LAY::NC / SK_WAVES, NPI = MAXC / 2, NST = 2 * NPI;      // NST = K steps of a wave: NPI chunk pairs of each of its two slices
+    constexpr int E0 = LAY::n0, E1 = E0 + LAY::n1, E2 = E1 + LAY::n2;
+    const float* const W = p.W;
+    const float* const sa0 = p.seg[0].a; const float* const sa1 = p.seg[1].a; const float* const sa2 = p.seg[2].a; const float* const sa3 = p.seg[3].a;
+    L2S_PIN_S("s"(W), "s"(sa0), "s"(sa1), "s"(sa2), "s"(sa3), "s"(ntiles), "s"(mts));
+    if (tp * 2 * CT >= ntiles) return;               // block-uniform: grid x is sized for the widest group of the launch
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wv8 = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int hc = wv8 >> 2, wave = wv8 & 3;         // column half; the wave's place in it (K slices wave and wave + 4)
+    const int tph = tp * 2 + hc;                     // the half's column block in units of CT tiles: the half-CU form's tp
+    const __amdgpu_buffer_rsrc_t rs_a0 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(sa0), 0, 0x7fffffff, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_a1 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(sa1), 0, 0x7fffffff, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_a2 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(sa2), 0, 0x7fffffff, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_a3 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(sa3), 0, 0x7fffffff, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_s1 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(LAY::SUM1 ? p.a_sum : W), 0, 0x7fffffff, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_w3 = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.W3), 0, 0x7fffffff, 0x00020000);
+    int wo3[CT];
+#pragma unroll
+    for (int i = 0; i < CT; ++i) wo3[i] = (((min(tph * CT + i, ntiles - 1) * SK_WAVES + wave) * NPI * 3) * 64 + lane) * 16;
+    int ao[4][HR];
+#pragma unroll
+    for (int r = 0; r < HR; ++r) {
+        const int rt = min(mg * RT + HR * hc + r, mts - 1);
+        ao[0][r] = ((rt * LAY::n0 + wave) * 64 + lane) * 16;
+        ao[1][r] = ((rt * LAY::n1 + wave) * 64 + lane) * 16;
+        ao[2][r] = ((rt * LAY::n2 + wave) * 64 + lane) * 16;
+        ao[3][r] = ((rt * LAY::n3 + wave) * 64 + lane) * 16;
+    }
+    uint4* const ring = reinterpret_cast<uint4*>(lds + SKP_LO_FLOATS);
+    uint4* const ring_rd = ring + wave * 12 * 64 + lane;                 // + buffer * 4 * 12 * 64 + (row tile * 3 + plane) * 64
+    uint4* const ring_wr = ring_rd + HR * hc * 3 * 64;
+    float4 a[NST][2][HR], a2[NST][2][HR];
+    uint4 w3[NST][CT][3];
+    // step st: chunk pair ip = st % NPI of K slice wave + NW * (st / NPI)
+    auto load_a = [&](auto sc) {
+        constexpr int st = decltype(sc)::value, hs = st / NPI, ip = st % NPI;
+#pragma unroll
+        for (int c = 0; c < 2; ++c) {
+            const int cj = SK_WAVES * (2 * ip + c) + NW * hs;            // a constant after unrolling
+            const int sg = cj >= E2 ? 3 : cj >= E1 ? 2 : cj >= E0 ? 1 : 0;
+            const int off = cj - (sg == 3 ? E2 : sg == 2 ? E1 : sg == 1 ? E0 : 0);
+            const __amdgpu_buffer_rsrc_t rs = sg == 3 ? rs_a3 : sg == 2 ? rs_a2 : sg == 1 ? rs_a1 : rs_a0;
+#pragma unroll
+            for (int r = 0; r < HR; ++r) a[st][c][r] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rs, ao[sg][r], off * 1024, 0));
+            if (LAY::SUM1 && sg == 1) {
+#pragma unroll
+                for (int r = 0; r < HR; ++r) a2[st][c][r] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rs_s1, ao[1][r], off * 1024, 0));
+            }
+        }
+    };
+    auto load_w = [&](auto sc) {
+        constexpr int st = decltype(sc)::value, hs = st / NPI, ip = st % NPI;
+#pragma unroll
+        for (int i = 0; i < CT; ++i)
+#pragma unroll
+            for (int pl = 0; pl < 3; ++pl)
+                w3[st][i][pl] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rs_w3, wo3[i], ((hs * NW * NPI + ip) * 3 + pl) * 1024, 0));
+    };
+    // split this wave's two row tiles of step st and publish their planes
+    auto publish = [&](auto sc) {
+        constexpr int st = decltype(sc)::value, hs = st / NPI, ip = st % NPI;
+#pragma unroll
+        for (int c = 0; c < 2; ++c) {
+            const int cj = SK_WAVES * (2 * ip + c) + NW * hs;
+            if (LAY::SUM1 && cj >= E0 && cj < E1) {
+#pragma unroll
+                for (int r = 0; r < HR; ++r) {
+                    a[st][c][r].x += a2[st][c][r].x; a[st][c][r].y += a2[st][c][r].y; a[st][c][r].z += a2[st][c][r].z; a[st][c][r].w += a2[st][c][r].w;
+                }
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < HR; ++r) {
+            skx_bf16x8 h, m, l;
+            skx_split8(a[st][0][r], a[st][1][r], h, m, l);
+            uint4* const o = ring_wr + (st & 1) * 4 * 12 * 64 + r * 3 * 64;
+            o[0] = __builtin_bit_cast(uint4, h); o[64] = __builtin_bit_cast(uint4, m); o[128] = __builtin_bit_cast(uint4, l);
+        }
+    };
+    __builtin_amdgcn_sched_barrier(0);
+    load_a(std::integral_constant<int, 0>{});
+    load_w(std::integral_constant<int, 0>{});
+    if constexpr (NST > 1) load_a(std::integral_constant<int, 1>{});
+    static_for<1, (DW < NST ? DW : NST)>([&](auto sc) { load_w(sc); });
+    __builtin_amdgcn_sched_barrier(0);
+
+    // ---- the cell threads' operands, under the loads already in flight: every request one load from an always-valid address, kept or dropped by a
+    // select (skinny_block_rcs).  Thread (q2 = wave (+ NW per round), t64) of a half owns (row t64>>2, unit t64&3) of the half's tile q2.
+    const int nB = p.B, H = p.H;
+    const float* const bias = p.bias; const float* const pre = p.pre; const int64_t ld_pre = p.ld_pre; const float* const c_in = p.c_in;
+    L2S_PIN_S("s"(nB), "s"(H), "s"(bias), "s"(pre), "s"(ld_pre), "s"(c_in));
+    const float* const bias_p = bias ? bias : W;
+    const float* const add_p = pre ? pre : W;
+    constexpr int NCR = NT / NW;
+    const int t64 = tid & 63;
+    float pf_c[NCR], pf_gb[NCR][4], pf_gp[NCR][4];
+    bool cell_on[NCR];
+#pragma unroll
+    for (int cr = 0; cr < NCR; ++cr) {
+        const int q2 = wave + NW * cr;
+        const int t2 = tph * CT + q2 % CT, rt2 = mg * RT + q2 / CT;
+        const int b2 = rt2 * 16 + (t64 >> 2);
+        cell_on[cr] = t2 < ntiles && rt2 < mts && b2 < nB;
+        const int t2c = min(t2, ntiles - 1), rt2c = min(rt2, mts - 1);
+        const int b2c = min(rt2c * 16 + (t64 >> 2), nB - 1), u2 = t64 & 3;
+        pf_c[cr] = c_in[frag16_index(b2c, t2c * 4 + u2, H)];
+        const float4 b4 = *reinterpret_cast<const float4*>(bias_p + (bias ? t2c * 16 + 4 * u2 : 0));
+        pf_gb[cr][0] = bias ? b4.x : 0.f; pf_gb[cr][1] = bias ? b4.y : 0.f; pf_gb[cr][2] = bias ? b4.z : 0.f; pf_gb[cr][3] = bias ? b4.w : 0.f;
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const float va = add_p[pre ? (int64_t)b2c * ld_pre + g * H + t2c * 4 + u2 : 0];
+            pf_gp[cr][g] = pre ? va : 0.f;
+        }
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    publish(std::integral_constant<int, 0>{});
+    if constexpr (NST > 2) load_a(std::integral_constant<int, 2>{});
+    __syncthreads();
+
+    float* const red_lo = lds + hc * 32 * 256;                                            // partial tiles of K slices 0-3 (slot = slice * NT + tile)
+    float* const red_hi = lds + SKP_LO_FLOATS + hc * 32 * 256;                            // of slices 4-7: over the ring, after the K loop
+    f32x4 acc[NT][2];
+#pragma unroll
+    for (int q = 0; q < NT; ++q) { acc[q][0] = f32x4{0.f, 0.f, 0.f, 0.f}; acc[q][1] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+    static_for<0, NST>([&](auto sc) {
+        constexpr int st = decltype(sc)::value, ip = st % NPI, px = ip & 1;
+        skx_bf16x8 pl[RT][3];
+#pragma unroll
+        for (int r = 0; r < RT; ++r)
+#pragma unroll
+            for (int k = 0; k < 3; ++k) pl[r][k] = __builtin_bit_cast(skx_bf16x8, ring_rd[(st & 1) * 4 * 12 * 64 + (r * 3 + k) * 64]);
+        if constexpr (st + 1 < NST) {                // the next step's planes go out before this step's MFMAs: the partner wave of the SIMD computes meanwhile
+            publish(std::integral_constant<int, st + 1>{});
+            if constexpr (st + 3 < NST) {
+                __builtin_amdgcn_sched_barrier(0);
+                load_a(std::integral_constant<int, st + 3>{});
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+        // smallest partial products first (the order of skinny_block_rcs per accumulator); tile-major inside a term
+#define L2S_SKP_TERM(A_, PL_)                                                                                                                  \
+        _Pragma("unroll") for (int r = 0; r < RT; ++r)                                                                                         \
+            _Pragma("unroll") for (int i = 0; i < CT; ++i)                                                                                     \
+                acc[r * CT + i][px] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pl[r][A_], __builtin_bit_cast(skx_bf16x8, w3[st][i][PL_]), acc[r * CT + i][px], 0, 0, 0);
+        L2S_SKP_TERM(2, 0) L2S_SKP_TERM(0, 2) L2S_SKP_TERM(1, 1) L2S_SKP_TERM(1, 0) L2S_SKP_TERM(0, 1) L2S_SKP_TERM(0, 0)
+#undef L2S_SKP_TERM
+        if constexpr (st + DW < NST) {
+            __builtin_amdgcn_sched_barrier(0);
+            load_w(std::integral_constant<int, st + DW>{});
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        if constexpr (st == NPI - 1) {               // the first slice is through: its partial tiles to the reduction buffer, accumulators from zero again
+            const int col = lane & 15, rb = 4 * (lane >> 4);
+#pragma unroll
+            for (int q = 0; q < NT; ++q) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) red_lo[sk_red_idx(wave * NT + q, rb + r, col)] = acc[q][0][r] + acc[q][1][r];
+                acc[q][0] = f32x4{0.f, 0.f, 0.f, 0.f}; acc[q][1] = f32x4{0.f, 0.f, 0.f, 0.f};
+            }
+        }
+        __syncthreads();                             // the next step's planes are in the ring; after the last step: every wave is through with the ring
+    });
+    {
+        const int col = lane & 15, rb = 4 * (lane >> 4);
+#pragma unroll
+        for (int q = 0; q < NT; ++q)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) red_hi[sk_red_idx(wave * NT + q, rb + r, col)] = acc[q][0][r] + acc[q][1][r];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int cr = 0; cr < NCR; ++cr) {
+        if (!cell_on[cr]) continue;
+        const int q2 = wave + NW * cr;
+        const int t2 = tph * CT + q2 % CT, rt2 = mg * RT + q2 / CT;
+        const int b2 = rt2 * 16 + (t64 >> 2), unit2 = t2 * 4 + (t64 & 3);
+        const int r2 = t64 >> 2, u2 = t64 & 3;
+        float g4[4];
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            float v = 0.f;
+#pragma unroll
+            for (int wv = 0; wv < SK_WAVES; ++wv) v += (wv < NW ? red_lo : red_hi)[sk_red_idx((wv & (NW - 1)) * NT + q2, r2, 4 * u2 + g)];
+            v += pf_gb[cr][g];
+            v += pf_gp[cr][g];
+            g4[g] = v;
+        }
+        const float gi = g4[0], gf = g4[1], gg = g4[2], go = g4[3];
+        const float cn = sigmoidf_(gf) * pf_c[cr] + sigmoidf_(gi) * tanhf(gg);
+        const float hn = sigmoidf_(go) * tanhf(cn);
+        p.c_out[frag16_index(b2, unit2, H)] = cn;
+        p.h_out[frag16_index(b2, p.h_out_off + unit2, p.h_out_K)] = hn;
+        if (p.h_seq) p.h_seq[(int64_t)b2 * p.ld_hseq + unit2] = hn;
+        if (p.h_plain) p.h_plain[(int64_t)b2 * p.ld_hplain + unit2] = hn;
+    }
+}
+
 __device__ __forceinline__ double wave_sum_d(double x) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);

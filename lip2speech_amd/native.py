@@ -94,6 +94,7 @@ def diag() -> ctypes.CDLL:
         if _diag is not _lib:
             for name, value in _process_defaults.items():      # the process defaults set so far hold for models of either library
                 check(_diag.l2s_set_option(name.encode(), value), _diag)
+            _replay_thread_chains(_diag)
     return _diag
 
 
@@ -910,6 +911,7 @@ class NativeModel:
         ws = self.workspace(B, 29, 96, 96, 300, torch.device("cuda", torch.cuda.current_device()))
         out = ctypes.c_double()
         D = diag()                          # diagnostic library; the model handle may come from either library
+        _replay_thread_chains(D)            # the chain launches the block forms of this thread's hint: the ones the caller's timed region launches
         check(D.l2s_op_lstm_cell_chain(self._h, B, n_pairs, _ptr(ws), ws.numel(), _stream(), ctypes.byref(out)), D)
         return float(out.value)
 
@@ -1073,9 +1075,21 @@ def set_option(name: str, value: int) -> None:
 def set_thread_chains(n: int) -> None:
     """Tell the library how many launch chains the caller keeps in flight, for the calling host thread (include/l2s.h l2s_set_thread_chains): with
     two or more the step kernels take half-CU block forms so that chains overlap on the CUs.  A scheduling hint - results are the same bits."""
+    _chains_tls.n = int(n)
     check(lib().l2s_set_thread_chains(int(n)))
     if _diag is not None and _diag is not _lib:      # the hint is thread-local state of each library
         check(_diag.l2s_set_thread_chains(int(n)), _diag)
+
+
+_chains_tls = threading.local()      # the calling thread's hint, kept here so that it reaches a diagnostic library that loads after it was given
+
+
+def _replay_thread_chains(D: ctypes.CDLL) -> None:
+    """Hand the calling thread's chains hint to the diagnostic library `D`: the hint is thread-local state of each library, and `D` may have been
+    loaded - by this thread or by another - after `set_thread_chains` ran here, so what `D` launches for this thread would be the forms of one chain."""
+    n = getattr(_chains_tls, "n", None)
+    if n is not None and D is not _lib:
+        check(D.l2s_set_thread_chains(n), D)
 
 
 def persist_available() -> bool:

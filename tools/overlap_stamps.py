@@ -6,7 +6,7 @@ launches of bench.py's timed region (half-CU block forms, 256 rows).  From the b
 start within 3 us of each other; its span = first entry .. last exit.  Reported per kernel kind: launches, mean span of a launch, and - over the window
 in which all chains are active - the UNION of the spans (time during which at least one launch of that kind is on the chip) per launch = what the chip
 spends on a launch of that kind when the chains overlap, and the mean number of launches in flight.  Usage: CHAINS=3 MODE=lstm|decode python
-tools/overlap_stamps.py [G]   -> profiles/r06_overlap_stamps.txt"""
+tools/overlap_stamps.py [G]   -> profiles/r06_overlap_stamps.txt, profiles/lstm_shared_panel_times.txt"""
 import os, sys, threading
 os.environ.setdefault("L2S_LIB", "diag")      # tools run on the diagnostic build (libl2s_diag.so: product ABI + include/l2s_diag.h)
 os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
@@ -19,7 +19,7 @@ G = int(sys.argv[1]) if len(sys.argv) > 1 else 8
 ROWS, T = 32 * G, 29
 S = int(os.environ.get("S", "150"))
 N = int(os.environ.get("PAIRS", "150"))
-KIND = {1: "LSTM launch (skinny_rc4h / rc8x)", 2: "first phase (skinny_flat)", 3: "attention + prenet2 (step_attn)"}
+KIND = {1: "LSTM launch (skinny_rc4h / rc8x)", 2: "first phase (skinny_flat)", 3: "attention + prenet2 (step_attn)", 4: "LSTM launch (skinny_sp)"}
 sd = synth.synth_state_dict()
 nm = native.NativeModel()
 nm.set_option("persist_decode", 0)
@@ -107,6 +107,9 @@ def analyse(title, n):
         d = (w[:, 1] - w[:, 0]) / 100.0
         print(f"   {KIND.get(k, k):34s} {len(w):5d} launches, {int(np.median(w[:, 3])):4d} blocks each: span of a launch mean {d.mean():6.2f} us (median {np.median(d):6.2f}, p90 {np.percentile(d, 90):6.2f}); "
               f"union of spans / launches = {u / len(w) / 100:5.2f} us per launch for the chip; {s_ / u:4.2f} launches of this kind in flight while one is")
+        inwin = (kind == k) & (t0 >= lo) & (t1 <= hi)
+        life = (t1[inwin] - t0[inwin]) / 100.0
+        print(f"   {'':34s} block lifetime (entry .. exit of one block) median {np.median(life):6.2f} us, p90 {np.percentile(life, 90):6.2f} us over {len(life)} blocks")
 
 
 MODE = os.environ.get("MODE", "lstm,decode").split(",")
