@@ -259,7 +259,7 @@ int l2s_inference(l2s_model* m, const float* video, const float* emb, const floa
  * Options: masked calls take the launch-per-phase route - "persist_decode" and "use_graph" do not apply to them - unless "persist_masked" is set
  * (below: free-running masked calls inside the persistent envelope then take the persistent forms); "early_stop", "fold_step_weights" and
  * "infer_bf16" compose.  The grouped (*_multi) entry points have no masked form: batches of unequal length share a launch chain through
- * l2s_inference_ragged ("ragged groups" below); the training (l2s_train_*) entry points have none either.
+ * l2s_inference_ragged and, on the evaluate route, l2s_forward_eval_ragged ("ragged groups" below); the training (l2s_train_*) entry points have none.
  * Workspace: l2s_workspace_bytes_masked (the unmasked size plus the device length table), for all four calls.
  * l2s_masked_bilstm_plan: the launch plan of the BiLSTM recurrence, a pure host function.  The recurrence stays T uniform launches (step s reads frame
  * s forward and frame T-1-s backward); capture_steps = the steps AFTER which a row kernel hands over the forward finals of the clips that ended there
@@ -320,6 +320,34 @@ int l2s_inference_ragged(l2s_model* m, int G, const float* const* video, const f
                          const int32_t* batch_B, const int32_t* batch_T, const int32_t* video_lengths,
                          int H, int W, int S, float* mel_post, int64_t* lengths,
                          float* attn, void* ws, int64_t ws_bytes, void* stream);
+
+/* The evaluate-shaped ragged group: Lip2Speech.forward(..., tf_ratio = 1) in eval() mode (evaluate.py:32-38; l2s_forward_eval_masked below) over G padded
+ * batches that differ in B_g, T_g AND in their step count S_g = melspecs.shape[2], as rows of ONE launch chain.  Free-running only: there are no teacher
+ * frames (at tf_ratio = 1 no step is teacher-forced; a teacher-forced batch keeps its own l2s_forward_eval_masked call).
+ *   video / emb / gumbel / batch_B / batch_T / video_lengths: exactly what l2s_inference_ragged takes; batch_S host (G), each in [1, L2S_MAX_STEPS].
+ *   Outputs are PACKED back to back in batch order: batch g's block starts at float offset *_off[g] of l2s_forward_eval_ragged_plan and has the layout
+ *   l2s_forward_eval_masked gives that batch alone - mel_cf and mel_post (B_g,80,S_g) at mel_off[g]; stop (B_g,S_g) at stop_off[g]; attn_logits
+ *   (B_g,S_g,T_g) at attn_off[g], tau * q.k, -INFINITY at columns t >= len_c; content_dis (B_g * l2s_min_T(T_g), 501) at dis_off[g], a clip's rows past
+ *   its l2s_min_T(len_c) slots zeros.  mel_cf, attn_logits and content_dis may be NULL.  Each tensor holds *_off[G] floats.
+ * Contract.  Batch g's blocks are what l2s_forward_eval_masked(batch g, S = S_g, teacher = NULL) returns: the same bits wherever the kernel choice is the
+ * same, rounding-level inside the 1e-3 gate elsewhere.  The choices that depend on the row count (the split-bf16 GEMM's tile threshold, the post-net's
+ * one-slice-per-tap form) are made on the rows of the WHOLE call - N * Tmax, N * Smax with Smax = max S_g - as l2s_inference_ragged makes them.  Frames
+ * t >= len_c are never read (the ragged front-end as it is).  The chain decodes every row for Smax steps: the steps j >= S_g of a shorter batch's rows are
+ * wasted work, and none of them reaches an output - the post-net (five same-padded Conv1d layers over time) sees zeros past every row's own S_g, as it does
+ * in the batch's own call, and only frames j < S_g are moved into the blocks.  When every S_g equals Smax nothing has to be zeroed and those launches are
+ * skipped.
+ * Limits and errors: those of l2s_inference_ragged, plus 1 <= S_g <= L2S_MAX_STEPS; every violation names the batch ("batch 1 has S = 301, outside [1, 300]")
+ * and is raised before the first launch - the outputs of a failed call are untouched.  "infer_bf16" set, "frontend_x3" other than 3 and "frontend_solo" are
+ * refused by name; "early_stop" (S comes from the target), "persist_*" and "use_graph" do not apply: the launch-per-phase route.
+ * l2s_forward_eval_ragged_plan (pure host): the four offset tables, G + 1 entries each, in floats, and N = sum B_g, Tmax, Smax.
+ * l2s_workspace_bytes_eval_ragged: l2s_workspace_bytes_ragged at S = Smax plus the staging buffers at pitch Smax / Tmax; -1 (and l2s_last_error) outside the limits. */
+int l2s_forward_eval_ragged_plan(int G, const int32_t* batch_B, const int32_t* batch_T, const int32_t* batch_S,
+                                 int64_t* mel_off, int64_t* stop_off, int64_t* attn_off, int64_t* dis_off, int* N, int* Tmax, int* Smax);
+int64_t l2s_workspace_bytes_eval_ragged(int G, const int32_t* batch_B, const int32_t* batch_T, const int32_t* batch_S, int H, int W);
+int l2s_forward_eval_ragged(l2s_model* m, int G, const float* const* video, const float* const* emb, const float* const* gumbel,
+                            const int32_t* batch_B, const int32_t* batch_T, const int32_t* batch_S, const int32_t* video_lengths,
+                            int H, int W, float* mel_cf, float* mel_post, float* stop, float* attn_logits, float* content_dis,
+                            void* ws, int64_t ws_bytes, void* stream);
 
 /* Lip2Speech.forward(..., tf_ratio) in eval() mode (model/model.py:23-40 + model/modules/decoder.py:320-379) - what evaluate.py:32-38 runs on
  * every batch at tf_ratio = 1 - as ONE launch chain: encoder, prologue, S = mels.shape[2] steps, post-net.

@@ -15,9 +15,10 @@ third-party, stochastic and out of scope here - these f
 ``honour_lengths=True`` (off by default, as the reference ignores lengths): the loader's ``video_lengths`` are passed on to the length-masked entry
 points (``l2s_inference_masked`` / ``l2s_forward_eval_masked``), and on the voice route the batch's audio lengths go to the speaker tower
 (``SpeakerEncoder.inference(audios, audio_lengths=...)``, ``l2s_speaker_encoder_packed``), so a clip's output no longer depends on what it was
-padded to or batched with - neither through the video nor through the embedding that conditions every decoder stage.  The masked entry points have no
-grouped form: the batches then run one call each, in loader order - unless ``demo_clips`` is also given ``group_lengths=True``: batches of unequal
-length then share launch chains as ragged groups (``l2s_inference_ragged``, ``Lip2Speech.inference_many_lengths``).
+padded to or batched with - neither through the video nor through the embedding that conditions every decoder stage.  By default the batches then run
+one masked call each, in loader order; with ``group_lengths=True`` as well, batches of unequal length share launch chains as ragged groups:
+``demo_clips`` through ``l2s_inference_ragged`` (``Lip2Speech.inference_many_lengths``), ``evaluate_mels`` / ``evaluate_net`` through
+``l2s_forward_eval_ragged`` (``Lip2Speech.forward_many_lengths``), where the batches differ in their mel length as well.
 """
 from __future__ import annotations
 
@@ -66,7 +67,7 @@ def demo_clips(net, batches: Iterable, speaker_encoder=None, speaker_embedding: 
     chain with ``n_inflight`` chains on the GPU (``Lip2Speech.inference_many``); yields ``(mel, lengths, attention)`` per clip, in order.
     ``encoding="face"``: the embedding comes from the model's face tower instead.  ``early_stop``: every group's decode loop ends once all of
     its clips have stopped (model option "early_stop", set once on ``net`` before the chains start); the yielded tensors are the same.
-    ``honour_lengths``: every batch goes through ``demo_clip`` with its ``video_lengths`` (the masked entry point has no grouped form).
+    ``honour_lengths``: every batch goes through ``demo_clip`` with its ``video_lengths``, one masked call per batch.
     ``group_lengths`` (with ``honour_lengths``; off by default): the batches - whatever their B and T - run ``group`` per launch chain as ragged
     groups instead (``Lip2Speech.inference_many_lengths``, ``l2s_inference_ragged``): the same clips out, each as it would come out alone.
     ``persist_frames``: as in ``demo_clip``, set once on ``net`` before the first clip (grouped calls themselves never take the persistent
@@ -140,10 +141,28 @@ def _voice_embedding(encoding, speaker_encoder, speaker_embedding, audios, devic
 
 
 def _evaluate_outputs(net, batches: Iterable, speaker_encoder, device, group: int, n_inflight: int, encoding: str = "voice",
-                      honour_lengths: bool = False):
+                      honour_lengths: bool = False, group_lengths: bool = False):
     """The eval-mode ``net(..., tf_ratio=1)`` of evaluate.py:32-38 for every collated batch (``train_collate_fn_pad`` layout), on the grouped
     path: yields ``(batch, outputs)`` in loader order.  ``honour_lengths``: one ``net(...)`` call per batch with the model's
-    ``honour_video_lengths`` switched on for the loop (``l2s_forward_eval_masked``; no grouped form)."""
+    ``honour_video_lengths`` switched on for the loop (``l2s_forward_eval_masked``).  ``group_lengths`` (with ``honour_lengths``; off by default):
+    the batches - whatever their B, T and mel length - run ``group`` per launch chain as ragged groups instead
+    (``Lip2Speech.forward_many_lengths``, ``l2s_forward_eval_ragged``): the same outputs, every clip as it would come out alone."""
+    if group_lengths and not honour_lengths:
+        raise ValueError("group_lengths groups the length-honouring calls: pass honour_lengths=True as well")
+    if honour_lengths and group_lengths:
+        kept = []
+
+        def ragged_calls():
+            for batch in batches:
+                (videos, vlen), (audios, alen), (melspecs, mlen, _gate), face_crops = batch
+                kept.append(batch)
+                with torch.no_grad():
+                    emb = _voice_embedding(encoding, speaker_encoder, None, audios, device, alen)
+                yield videos, face_crops, audios, melspecs, vlen, alen, mlen, 1, {"speaker_embedding": emb}
+
+        for out in net.forward_many_lengths(ragged_calls(), group=group, n_inflight=n_inflight):
+            yield kept.pop(0), out
+        return
     if honour_lengths:
         was = net.honour_video_lengths
         net.honour_video_lengths = True
@@ -171,26 +190,30 @@ def _evaluate_outputs(net, batches: Iterable, speaker_encoder, device, group: in
 
 
 def evaluate_mels(net, batches: Iterable, speaker_encoder=None, device="cuda", group: int = 8, n_inflight: int = 3,
-                  encoding: str = "voice", honour_lengths: bool = False) -> List[torch.Tensor]:
+                  encoding: str = "voice", honour_lengths: bool = False, group_lengths: bool = False) -> List[torch.Tensor]:
     """Post-net mels of ``net(..., tf_ratio=1)[1]`` for every collated batch (``train_collate_fn_pad`` layout; evaluate.py:32-38), ``group``
-    loader batches per launch chain (``l2s_forward_eval_multi``), ``n_inflight`` chains in flight."""
+    loader batches per launch chain (``l2s_forward_eval_multi``), ``n_inflight`` chains in flight.  ``honour_lengths`` / ``group_lengths``: as in
+    ``_evaluate_outputs`` - one masked call per batch, or ragged groups of ``group`` batches (``l2s_forward_eval_ragged``)."""
     was_training = net.training
     net.eval()
     try:
-        return [out[1] for _, out in _evaluate_outputs(net, batches, speaker_encoder, device, group, n_inflight, encoding, honour_lengths)]
+        return [out[1] for _, out in _evaluate_outputs(net, batches, speaker_encoder, device, group, n_inflight, encoding, honour_lengths, group_lengths)]
     finally:
         net.train(was_training)
 
 
 def evaluate_net(net, batches: Iterable, speaker_encoder=None, device="cuda", max_iters: int = 256, sampling_rate: int = None,
                  group: int = 8, n_inflight: int = 3, timings: Optional[dict] = None, vocoder_backend: str = "auto", metric: str = "auto",
-                 encoding: str = "voice", honour_lengths: bool = False) -> float:
+                 encoding: str = "voice", honour_lengths: bool = False, group_lengths: bool = False) -> float:
     """Mean ESTOI of the vocoded predictions against the ground-truth audio (reference: evaluate.py:22-51): `net(..., tf_ratio=1)[1]`
     -> `MelSpec2Audio` (InverseMelScale + Griffin-Lim, `max_iters` each) -> `stoi(gt, pred, fs, extended=True)` per clip.  Vocoder and
     metric are restatements of third-party algorithms (parity unpinned); the mels come from the HIP path, `group` loader batches per launch
     chain, and the next groups' chains run while this thread vocodes and scores.  `timings` (a dict) receives the wall seconds spent waiting
-    for the model, in the vocoder and in the metric.  `encoding="face"`: the speaker embedding comes from the model's face tower."""
+    for the model, in the vocoder and in the metric.  `encoding="face"`: the speaker embedding comes from the model's face tower.
+    `honour_lengths` / `group_lengths`: as in `evaluate_mels`."""
     _check_encoding(encoding)
+    if group_lengths and not honour_lengths:
+        raise ValueError("group_lengths groups the length-honouring calls: pass honour_lengths=True as well")
     import time
     from .datasets.spectrograms import MelSpec2Audio
     from .hparams import create_hparams
@@ -244,7 +267,7 @@ def evaluate_net(net, batches: Iterable, speaker_encoder=None, device="cuda", ma
         with torch.no_grad():
             t0 = time.perf_counter()
             pending = []
-            for batch, out in _evaluate_outputs(net, batches, speaker_encoder, device, group, n_inflight, encoding, honour_lengths):
+            for batch, out in _evaluate_outputs(net, batches, speaker_encoder, device, group, n_inflight, encoding, honour_lengths, group_lengths):
                 mel = out[1]
                 # a pass holds batches of one mel shape AND one audio width: batches padded to different audio lengths are then scored per
                 # equal-width run (on the device where the metric runs there) - a batch's score does not depend on which batches share its group

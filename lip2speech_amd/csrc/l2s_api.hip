@@ -817,15 +817,22 @@ static int postnet_layer(const Weights& w, int layer, const float* mel, const Po
     return launch_gemm1(p, s, "postnet_conv_gemm");
 }
 
-static int postnet_run(l2s_model* m, const float* mel, int B, int S, float* mel_post, float* mel_cf, void* ws, int64_t ws_bytes, hipStream_t s) {
+// ev (l2s_forward_eval_ragged; null for every other caller): row b decodes a batch of ev->clips[b].S <= S steps.  The caller has zeroed the rows j >= S_b
+// of mel; here the same rows of the outputs of layers 0..3 are zeroed, so that the next layer's taps read past a row's end the zeros its batch's own call
+// reads as padding (the same operands in the same K order: the same bits at j < S_b).  Rows j >= S_b of mel_post are the caller's to drop.
+static int postnet_run(l2s_model* m, const float* mel, int B, int S, float* mel_post, float* mel_cf, void* ws, int64_t ws_bytes, hipStream_t s,
+                       const EvalTab* ev = nullptr) {
     X3Scope x3scope(m->opt.infer_bf16 ? 0 : m->opt.gemm_x3);
     Bf16Scope bf16scope(m->opt.infer_bf16);      // the bf16 leg: bf16-operand GEMM / Conv1d kernels instead of the f32 / split-bf16 ones
     const Weights& w = m->w;
     Bump bp(ws, ws_bytes);
     PostBufs pb;
     L2S_REQUIRE(postnet_alloc(bp, B, S, pb) == 0, "postnet workspace too small");
-    for (int layer = 0; layer < 5; ++layer)
+    L2S_REQUIRE(!ev || (ev->N == B && ev->Smax == S), "postnet: the step table does not match the rows");
+    for (int layer = 0; layer < 5; ++layer) {
         if (postnet_layer(w, layer, mel, pb, mel_post, B, S, 0, S, s, m->opt.gemm_x3_dma != 0)) return 1;
+        if (ev && layer < 4 && launch_zero_rows_past_s(pb.x[layer], 512, *ev, s)) return 1;
+    }
     if (mel_cf && launch_transpose_bsc(mel, B, S, NM, mel_cf, s)) return 1;
     return 0;
 }
@@ -1218,6 +1225,9 @@ int l2s_output_lengths(const float* stop, int B, int S, int64_t* lengths, void* 
 struct PathOut {
     float* mel_post = nullptr; float* mel_cf = nullptr; float* stop = nullptr; int64_t* lengths = nullptr;
     float* attn = nullptr; int attn_logits = 0; float* content_dis = nullptr;
+    // l2s_forward_eval_ragged: the caller's buffer for the decoded row-major mel (B,S,80) - it moves the frames into its own blocks afterwards - and the
+    // per-row step counts of the post-net (postnet_run); null when every row has the call's S
+    float* mel = nullptr; const EvalTab* ev = nullptr;
 };
 
 static int path_run(l2s_model* m, const FrameSrc& video, const float* emb, const float* gumbel, int B, int T, int H, int W, int S,
@@ -1229,7 +1239,7 @@ static int path_run(l2s_model* m, const FrameSrc& video, const float* emb, const
     const ClipLens lens{video_lengths ? reinterpret_cast<int*>(bp.f(len_table_bytes(B) / 4)) : nullptr, video_lengths};      // the *_masked entry points (l2s_workspace_bytes_masked)
     float* vis = bp.f((int64_t)B * T * 1024);
     float* state = bp.f(l2s_state_floats(B, T));
-    float* mel = bp.f((int64_t)B * S * NM);
+    float* mel = o.mel ? o.mel : bp.f((int64_t)B * S * NM);
     float* stop = o.stop ? o.stop : bp.f((int64_t)B * S);
     L2S_REQUIRE(!bp.overflow, "workspace too small (l2s_workspace_bytes)");
     void* rest = (char*)ws + bp.off;
@@ -1241,7 +1251,8 @@ static int path_run(l2s_model* m, const FrameSrc& video, const float* emb, const
     const bool plain = !m->opt.overlap_postnet || g_prof_on || m->opt.graph || teacher || o.mel_cf || early || lens;      // "early_stop" and lengths take the plain route
     if (plain) {
         if (decode_run(m, state, B, T, S, teacher, teacher_mask, mel, stop, o.attn, o.attn_logits, rest, rest_bytes, s, early, lens)) return 1;
-        if (postnet_run(m, mel, B, S, o.mel_post, o.mel_cf, rest, rest_bytes, s)) return 1;
+        if (o.ev && launch_zero_rows_past_s(mel, NM, *o.ev, s)) return 1;      // the frames a shorter batch's rows decoded past their own S: zeros for the post-net's taps
+        if (postnet_run(m, mel, B, S, o.mel_post, o.mel_cf, rest, rest_bytes, s, o.ev)) return 1;
     } else {
         // The decode loop is a chain of small latency-bound launches that leaves most CUs idle, and the post-net of frame t
         // only needs mel frames t-10..t+10: run the post-net in time windows on a second stream while later steps decode.
@@ -1479,35 +1490,33 @@ int64_t l2s_workspace_bytes_ragged(int G, const int32_t* batch_B, const int32_t*
            align_up((int64_t)rg.N * content_lens(rg.Tmax, L) * VOC * 4, 256) + align_up((int64_t)rg.N * (int64_t)sizeof(RaggedClip), 256) + align_up(pairs * 4, 256);
 }
 
-int l2s_inference_ragged(l2s_model* m, int G, const float* const* video, const float* const* emb, const float* const* gumbel, const int32_t* batch_B,
-                         const int32_t* batch_T, const int32_t* video_lengths, int H, int W, int S, float* mel_post, int64_t* lengths, float* attn, void* ws,
-                         int64_t ws_bytes, void* stream) {
-    L2S_ENC_READY(m);
-    L2S_DEC_READY(m);
-    L2S_REQUIRE(video && emb && gumbel && video_lengths && mel_post && lengths && ws, "bad arguments");
-    // everything that can be refused is refused here, before the first launch: the outputs of a failed call are untouched
-    std::vector<RaggedClip> clips;
-    RaggedTab rg;
-    if (ragged_plan(G, batch_B, batch_T, video_lengths, clips, rg)) return 1;
-    L2S_REQUIRE(!m->opt.infer_bf16, "l2s_inference_ragged: option \"infer_bf16\" is set - the ragged front-end exists in the default form only");
-    L2S_REQUIRE(m->opt.frontend_x3 == 3, "l2s_inference_ragged: option \"frontend_x3\" is not 3 - the ragged front-end exists in the default form only");
-    L2S_REQUIRE(!m->opt.frontend_solo, "l2s_inference_ragged: option \"frontend_solo\" is set - the ragged front-end exists in the default form only");
+// What the two ragged entry points refuse beyond the plan, before the first launch (`fn` names the entry point in the message), and the frame sources
+static int ragged_refuse(l2s_model* m, const char* fn, int G, const float* const* video, const float* const* emb, const float* const* gumbel, int H, int W,
+                         FrameSrc& src) {
+    const std::string f(fn);
+    L2S_REQUIRE(!m->opt.infer_bf16, f + ": option \"infer_bf16\" is set - the ragged front-end exists in the default form only");
+    L2S_REQUIRE(m->opt.frontend_x3 == 3, f + ": option \"frontend_x3\" is not 3 - the ragged front-end exists in the default form only");
+    L2S_REQUIRE(!m->opt.frontend_solo, f + ": option \"frontend_solo\" is set - the ragged front-end exists in the default form only");
     L2S_REQUIRE(H == W && (H == 96 || H == 88), "frontend supports 96x96 and 88x88 mouth crops");
-    L2S_REQUIRE(S >= 1 && S <= L2S_MAX_STEPS, "S must be in [1, 300] (positional table)");
-    FrameSrc src{};
+    src = FrameSrc{};
     for (int g = 0; g < G; ++g) {
         if (!video[g] || !emb[g] || !gumbel[g] || (reinterpret_cast<uintptr_t>(video[g]) & 15u)) {
-            set_error("l2s_inference_ragged: batch " + std::to_string(g) + ": null pointer, or video not 16-byte aligned");
+            set_error(f + ": batch " + std::to_string(g) + ": null pointer, or video not 16-byte aligned");
             return 1;
         }
         src.p[g] = video[g];
     }
-    hipStream_t s = (hipStream_t)stream;
+    return 0;
+}
+
+// The operands of a ragged group at the front of its workspace: the gathered embeddings and Gumbel rows, the clip table and the front-end's pair map
+// (rg.clips / rg.pair_clip are set).  bp is left behind them.
+static int ragged_gather(int G, const float* const* emb, const float* const* gumbel, const int32_t* batch_B, const int32_t* batch_T,
+                         const std::vector<RaggedClip>& clips, RaggedTab& rg, Bump& bp, float*& emb_all, float*& gum_all, hipStream_t s) {
     int L[4];
     const int mT = content_lens(rg.Tmax, L), N = rg.N;
-    Bump bp(ws, ws_bytes);
-    float* emb_all = bp.f((int64_t)N * L2S_D_EMB);
-    float* gum_all = bp.f((int64_t)N * mT * VOC);
+    emb_all = bp.f((int64_t)N * L2S_D_EMB);
+    gum_all = bp.f((int64_t)N * mT * VOC);
     RaggedClip* clips_dev = reinterpret_cast<RaggedClip*>(bp.f((int64_t)N * (int64_t)(sizeof(RaggedClip) / sizeof(float))));
     int* pair_clip = reinterpret_cast<int*>(bp.f(rg.NP));
     L2S_REQUIRE(!bp.overflow, "workspace too small (l2s_workspace_bytes_ragged)");
@@ -1521,11 +1530,138 @@ int l2s_inference_ragged(l2s_model* m, int G, const float* const* video, const f
     }
     if (launch_ragged_table(clips.data(), N, clips_dev, pair_clip, s)) return 1;
     rg.clips = clips_dev; rg.pair_clip = pair_clip;
+    return 0;
+}
+
+int l2s_inference_ragged(l2s_model* m, int G, const float* const* video, const float* const* emb, const float* const* gumbel, const int32_t* batch_B,
+                         const int32_t* batch_T, const int32_t* video_lengths, int H, int W, int S, float* mel_post, int64_t* lengths, float* attn, void* ws,
+                         int64_t ws_bytes, void* stream) {
+    L2S_ENC_READY(m);
+    L2S_DEC_READY(m);
+    L2S_REQUIRE(video && emb && gumbel && video_lengths && mel_post && lengths && ws, "bad arguments");
+    // everything that can be refused is refused here, before the first launch: the outputs of a failed call are untouched
+    std::vector<RaggedClip> clips;
+    RaggedTab rg;
+    if (ragged_plan(G, batch_B, batch_T, video_lengths, clips, rg)) return 1;
+    FrameSrc src;
+    if (ragged_refuse(m, "l2s_inference_ragged", G, video, emb, gumbel, H, W, src)) return 1;
+    L2S_REQUIRE(S >= 1 && S <= L2S_MAX_STEPS, "S must be in [1, 300] (positional table)");
+    hipStream_t s = (hipStream_t)stream;
+    Bump bp(ws, ws_bytes);
+    float *emb_all, *gum_all;
+    if (ragged_gather(G, emb, gumbel, batch_B, batch_T, clips, rg, bp, emb_all, gum_all, s)) return 1;
     // the row-count-dependent kernel choices are made on the whole call's rows, as for one masked call of N clips: "rows of one batch" has no meaning here
     X3Group x3group(1);
     PathOut o;
     o.mel_post = mel_post; o.lengths = lengths; o.attn = attn;
-    return path_run(m, src, emb_all, gum_all, N, rg.Tmax, H, W, S, nullptr, nullptr, o, (char*)ws + bp.off, ws_bytes - bp.off, s, video_lengths, &rg);
+    return path_run(m, src, emb_all, gum_all, rg.N, rg.Tmax, H, W, S, nullptr, nullptr, o, (char*)ws + bp.off, ws_bytes - bp.off, s, video_lengths, &rg);
+}
+
+// ---- the evaluate-shaped ragged group: every batch also has its own step count S_g (forward() decodes melspecs.shape[2] steps; include/l2s.h).  Free-running
+// only.  The chain decodes all N rows for Smax = max S_g steps into staging buffers at pitch Smax / Tmax (the steps j >= S_g of a shorter batch's rows are
+// wasted work), the post-net sees zeros past every row's own S_g (postnet_run), and small kernels move the rows into the packed per-batch blocks.
+struct EvalPlan { std::vector<int64_t> mel_off, stop_off, attn_off, dis_off; int Smax = 0; bool uneven = false; };
+static int eval_ragged_plan(int G, const int32_t* batch_B, const int32_t* batch_T, const int32_t* batch_S, const int32_t* video_lengths,
+                            std::vector<RaggedClip>& clips, RaggedTab& rg, EvalPlan& pl) {
+    if (ragged_plan(G, batch_B, batch_T, video_lengths, clips, rg)) return 1;
+    L2S_REQUIRE(batch_S, "l2s ragged: batch_S is null");
+    pl = EvalPlan{};
+    pl.mel_off.assign(1, 0); pl.stop_off.assign(1, 0); pl.attn_off.assign(1, 0); pl.dis_off.assign(1, 0);
+    int L[4];
+    for (int g = 0; g < G; ++g) {
+        const int64_t B = batch_B[g], T = batch_T[g], S = batch_S[g];
+        if (S < 1 || S > L2S_MAX_STEPS) {
+            set_error("l2s ragged: batch " + std::to_string(g) + " has S = " + std::to_string(S) + ", outside [1, " + std::to_string(L2S_MAX_STEPS) + "]");
+            return 1;
+        }
+        pl.Smax = std::max(pl.Smax, (int)S);
+        pl.mel_off.push_back(pl.mel_off.back() + B * NM * S);
+        pl.stop_off.push_back(pl.stop_off.back() + B * S);
+        pl.attn_off.push_back(pl.attn_off.back() + B * S * T);
+        pl.dis_off.push_back(pl.dis_off.back() + B * content_lens((int)T, L) * VOC);
+    }
+    for (int g = 0; g < G; ++g) pl.uneven = pl.uneven || batch_S[g] != pl.Smax;
+    return 0;
+}
+
+int l2s_forward_eval_ragged_plan(int G, const int32_t* batch_B, const int32_t* batch_T, const int32_t* batch_S, int64_t* mel_off, int64_t* stop_off,
+                                 int64_t* attn_off, int64_t* dis_off, int* N, int* Tmax, int* Smax) {
+    L2S_REQUIRE(mel_off && stop_off && attn_off && dis_off && N && Tmax && Smax, "bad arguments");
+    std::vector<RaggedClip> clips;
+    RaggedTab rg;
+    EvalPlan pl;
+    if (eval_ragged_plan(G, batch_B, batch_T, batch_S, nullptr, clips, rg, pl)) return 1;
+    std::copy(pl.mel_off.begin(), pl.mel_off.end(), mel_off);
+    std::copy(pl.stop_off.begin(), pl.stop_off.end(), stop_off);
+    std::copy(pl.attn_off.begin(), pl.attn_off.end(), attn_off);
+    std::copy(pl.dis_off.begin(), pl.dis_off.end(), dis_off);
+    *N = rg.N; *Tmax = rg.Tmax; *Smax = pl.Smax;
+    return 0;
+}
+
+// the staging buffers of l2s_forward_eval_ragged behind the ragged group's own workspace: the row-major mel, the stop logits, the channel-first mel_post,
+// the attention logits and the content distribution at the staging pitches, and the step table
+static int64_t eval_ragged_staging_bytes(int N, int Tmax, int Smax) {
+    int L[4];
+    const int64_t rows = (int64_t)N * Smax;
+    return 2 * align_up(rows * NM * 4, 256) + align_up(rows * 4, 256) + align_up(rows * Tmax * 4, 256) +
+           align_up((int64_t)N * content_lens(Tmax, L) * VOC * 4, 256) + align_up((int64_t)N * (int64_t)sizeof(EvalClip), 256);
+}
+
+int64_t l2s_workspace_bytes_eval_ragged(int G, const int32_t* batch_B, const int32_t* batch_T, const int32_t* batch_S, int H, int W) {
+    std::vector<RaggedClip> clips;
+    RaggedTab rg;
+    EvalPlan pl;
+    if (eval_ragged_plan(G, batch_B, batch_T, batch_S, nullptr, clips, rg, pl)) return -1;
+    return l2s_workspace_bytes_ragged(G, batch_B, batch_T, H, W, pl.Smax) + eval_ragged_staging_bytes(rg.N, rg.Tmax, pl.Smax);
+}
+
+int l2s_forward_eval_ragged(l2s_model* m, int G, const float* const* video, const float* const* emb, const float* const* gumbel, const int32_t* batch_B,
+                            const int32_t* batch_T, const int32_t* batch_S, const int32_t* video_lengths, int H, int W, float* mel_cf, float* mel_post,
+                            float* stop, float* attn_logits, float* content_dis, void* ws, int64_t ws_bytes, void* stream) {
+    L2S_ENC_READY(m);
+    L2S_DEC_READY(m);
+    L2S_REQUIRE(video && emb && gumbel && video_lengths && mel_post && stop && ws, "bad arguments");
+    // everything that can be refused is refused here, before the first launch: the outputs of a failed call are untouched
+    std::vector<RaggedClip> clips;
+    RaggedTab rg;
+    EvalPlan pl;
+    if (eval_ragged_plan(G, batch_B, batch_T, batch_S, video_lengths, clips, rg, pl)) return 1;
+    FrameSrc src;
+    if (ragged_refuse(m, "l2s_forward_eval_ragged", G, video, emb, gumbel, H, W, src)) return 1;
+    hipStream_t s = (hipStream_t)stream;
+    int L[4];
+    const int N = rg.N, Tmax = rg.Tmax, Smax = pl.Smax, mTmax = content_lens(Tmax, L);
+    Bump bp(ws, ws_bytes);
+    float* mel_rm = bp.f((int64_t)N * Smax * NM);
+    float* post_st = bp.f((int64_t)N * NM * Smax);
+    float* stop_st = bp.f((int64_t)N * Smax);
+    float* attn_st = attn_logits ? bp.f((int64_t)N * Smax * Tmax) : nullptr;
+    float* dis_st = content_dis ? bp.f((int64_t)N * mTmax * VOC) : nullptr;
+    EvalClip* ev_dev = reinterpret_cast<EvalClip*>(bp.f((int64_t)N * (int64_t)(sizeof(EvalClip) / sizeof(float))));
+    L2S_REQUIRE(!bp.overflow, "workspace too small (l2s_workspace_bytes_eval_ragged)");
+    float *emb_all, *gum_all;
+    if (ragged_gather(G, emb, gumbel, batch_B, batch_T, clips, rg, bp, emb_all, gum_all, s)) return 1;
+    std::vector<EvalClip> evc;
+    evc.reserve(N);
+    for (const RaggedClip& k : clips)
+        evc.push_back(EvalClip{(int)batch_S[k.g], k.T, k.row, content_lens(k.T, L), (int)pl.mel_off[k.g], (int)pl.stop_off[k.g], (int)pl.attn_off[k.g],
+                               (int)pl.dis_off[k.g]});
+    if (launch_eval_table(evc.data(), N, ev_dev, s)) return 1;
+    const EvalTab ev{ev_dev, N, Smax, Tmax, mTmax};
+    // the row-count-dependent kernel choices (the split-bf16 thresholds, POST_TAPSPLIT_ROWS) are made on the rows of the whole call - N * Tmax, N * Smax -
+    // as for one masked call of N clips, like l2s_inference_ragged
+    X3Group x3group(1);
+    PathOut o;
+    o.mel_post = post_st; o.stop = stop_st; o.attn = attn_st; o.attn_logits = 1; o.content_dis = dis_st; o.mel = mel_rm;
+    o.ev = pl.uneven ? &ev : nullptr;      // every S_g = Smax (GRID: all clips are 3 s): nothing to zero
+    if (path_run(m, src, emb_all, gum_all, N, Tmax, H, W, Smax, nullptr, nullptr, o, (char*)ws + bp.off, ws_bytes - bp.off, s, video_lengths, &rg)) return 1;
+    if (launch_eval_scatter(EV_MEL_POST, post_st, ev, mel_post, s)) return 1;
+    if (launch_eval_scatter(EV_STOP, stop_st, ev, stop, s)) return 1;
+    if (mel_cf && launch_eval_mel_cf(mel_rm, ev, mel_cf, s)) return 1;
+    if (attn_logits && launch_eval_scatter(EV_ATTN, attn_st, ev, attn_logits, s)) return 1;
+    if (content_dis && launch_eval_scatter(EV_DIS, dis_st, ev, content_dis, s)) return 1;
+    return 0;
 }
 
 // ---- operator-level entry points

@@ -291,6 +291,18 @@ int launch_ragged_table(const RaggedClip* clips_host, int N, RaggedClip* clips_d
 // the ragged form of the default front-end (frontend3d_x3q_kernel): blockIdx.y = pair block; clip c's block j is block (0, 2j) of the clip alone at T = len
 // (same slabs, same order: same bits), read in place at pitch T_g, written to compact frames frame0 + 2j (+1).  Frames t >= len are never read.
 int launch_frontend_ragged(const FrontendW& w, const FrameSrc& video, const RaggedTab& rg, int H, int W, float* out, hipStream_t s);
+// ---- evaluate-shaped ragged groups (l2s_forward_eval_ragged; ragged_eval_kernels.hip): every batch also has its own step count S_g.  The chain decodes all
+// N rows for Smax steps at pitch Smax / Tmax; clip c's table entry says which of those rows are its own and where its batch's packed output blocks start.
+// Offsets are in floats and fit an int: the largest block set of a call is 256 clips x 300 steps x 300 frames = 23 040 000 floats.
+struct EvalClip { int S, T, row, mT, mel_off, stop_off, attn_off, dis_off; };      // S_g, T_g, row in its batch, min_T(T_g), start of ITS BATCH's mel / stop / attention / content_dis block
+constexpr int EVAL_CHUNK = 32;                                                     // clips per table-writing launch
+struct EvalChunk { EvalClip c[EVAL_CHUNK]; int n; };
+struct EvalTab { const EvalClip* clips; int N, Smax, Tmax, mTmax; };               // device table; clips, the staging pitches (steps, frames, content slots)
+enum EvalField { EV_STOP = 0, EV_ATTN = 1, EV_DIS = 2, EV_MEL_POST = 3 };
+int launch_eval_table(const EvalClip* clips_host, int N, EvalClip* clips_dev, hipStream_t s);
+int launch_zero_rows_past_s(float* x, int cols, const EvalTab& ev, hipStream_t s);      // x (N * Smax, cols) dense: rows j >= S_c of every clip become zeros
+int launch_eval_scatter(int field, const float* src, const EvalTab& ev, float* dst, hipStream_t s);      // a staged output (pitch Smax / Tmax / mTmax) -> the packed blocks
+int launch_eval_mel_cf(const float* mel, const EvalTab& ev, float* mel_cf, hipStream_t s);               // mel (N, Smax, 80) row-major -> the packed channel-first blocks
 // batch-statistics pass of the front-end conv (training): partials[(block*2 + k)*24 + ch], *nblocks blocks
 int launch_frontend_stats(const FrontendW& w, const float* video, int B, int T, int H, int W, float* partials /*[blocks][2][24]*/, int* nblocks, hipStream_t s, float* raw_out = nullptr);
 // raw_out (NF,H/2,W/2,24): the statistics pass also parks the raw conv map; launch_bn_apply on it + launch_frontend_pool then replace the second conv pass

@@ -298,7 +298,8 @@ class Lip2Speech(NativeBacked):
         if self.training:
             raise RuntimeError("forward_many is the evaluate path: call .eval() first (train() mode trains through forward / backward)")
         if self.honour_video_lengths:
-            raise NotImplementedError("honour_video_lengths: the grouped entry points have no length-masked form (include/l2s.h); call forward per batch")
+            raise NotImplementedError("honour_video_lengths: the grouped entry points have no length-masked form (include/l2s.h); call forward per batch, "
+                                      "or forward_many_lengths for free-running batches (tf_ratio = 1)")
         self.native_model()
 
         def prep(item):
@@ -306,6 +307,37 @@ class Lip2Speech(NativeBacked):
             video, face, _audio, mels, vlen, _alen, _mlen, tf = a
             return self._forward_job(video, face, mels, vlen, tf, **k)
         return self.pool(group, n_inflight).imap(calls, prep)
+
+    def forward_many_lengths(self, calls, group: int = 8, n_inflight: int = 3):
+        """Eval-mode `forward` WITH its `video_lengths` honoured over a stream of batches whose B, T and mel length differ - evaluate.py's loop over a
+        loader that pads every batch to its own longest clip and its own longest mel - with `group` batches, at most 256 clips, advanced per launch chain
+        as an evaluate-shaped ragged group (`l2s_forward_eval_ragged`) and `n_inflight` chains on the GPU at once: the twin of `inference_many_lengths`.
+        `calls`: as for `forward_many`; every call needs its `video_lengths` (B integers in [7, T]) and a `tf_ratio` whose scheduled-sampling draws force
+        no step (evaluate.py's tf_ratio = 1; the draws are made as `forward` makes them, so the host RNG is consumed alike) - a call that teacher-forces
+        a step raises `ValueError`: it keeps its own `forward` call.  Yields the reference's list of 7 per call, in order, each what `forward(*call)`
+        gives with `honour_video_lengths` on - every clip as it would come out alone.  Does not read the `honour_video_lengths` attribute."""
+        if self.training:
+            raise RuntimeError("forward_many_lengths is the evaluate path: call .eval() first (train() mode trains through forward / backward)")
+        self.native_model()
+
+        def prep(item):
+            a, k = self._call(item)
+            video, face, _audio, mels, vlen, _alen, _mlen, tf = a
+            return self._forward_ragged_job(video, face, mels, vlen, tf, **k)
+        return self.pool(group, n_inflight).imap(calls, prep)
+
+    def _forward_ragged_job(self, video_frames, face_frames, melspecs, video_lengths, tf_ratio, speaker_embedding=None, gumbel_noise=None):
+        """`_forward_job` as a job of the ragged evaluate route (`l2s_forward_eval_ragged`): the lengths are validated before the batch is staged on the
+        device, the scheduled-sampling draws are made as `forward` makes them and must force no step."""
+        if video_lengths is None:
+            raise ValueError("forward_many_lengths: every call needs video_lengths (use forward_many for batches whose lengths are ignored)")
+        lens = list(native.video_lengths_array(video_lengths, video_frames.shape[0], video_frames.shape[2]))
+        job = self._forward_job(video_frames, face_frames, melspecs, video_lengths, tf_ratio, speaker_embedding, gumbel_noise)
+        if job["mask"] is not None:
+            raise ValueError(f"forward_many_lengths: tf_ratio = {tf_ratio} teacher-forces a step - the ragged evaluate call is free-running (tf_ratio = 1); "
+                             "call forward for this batch")
+        job["entry"], job["video_lengths"] = "forward_ragged", lens
+        return job
 
     def _forward_train(self, video_frames, face_frames, melspecs, video_lengths, tf_ratio, speaker_embedding, gumbel_noise, dropout_masks=None):
         """The differentiable route (train.py:167-184): same outputs as `forward`, attached to autograd through `_HipTrainStep`.

@@ -33,6 +33,7 @@ ABI_SYMBOLS = (
     "l2s_encoder_fwd", "l2s_normalise_pad_frames", "l2s_build_visual", "l2s_decoder_prologue", "l2s_decode_steps", "l2s_postnet",
     "l2s_workspace_bytes_masked", "l2s_masked_bilstm_plan", "l2s_inference_masked", "l2s_forward_eval_masked", "l2s_decoder_prologue_masked", "l2s_decode_steps_masked",
     "l2s_ragged_plan", "l2s_workspace_bytes_ragged", "l2s_inference_ragged",
+    "l2s_forward_eval_ragged_plan", "l2s_workspace_bytes_eval_ragged", "l2s_forward_eval_ragged",
     "l2s_output_lengths", "l2s_inference", "l2s_inference_multi", "l2s_workspace_bytes_multi", "l2s_forward_eval", "l2s_forward_eval_multi", "l2s_model_set_option", "l2s_persist_available", "l2s_persist_timeouts", "l2s_set_thread_chains", "l2s_speaker_workspace_bytes", "l2s_speaker_encoder_fwd",
     "l2s_speaker_packed_plan", "l2s_speaker_workspace_bytes_packed", "l2s_speaker_encoder_packed",
     "l2s_face_workspace_bytes", "l2s_face_encoder_fwd",
@@ -202,6 +203,15 @@ def _bind(L: ctypes.CDLL) -> None:
         L.l2s_workspace_bytes_ragged.restype = _i64
         L.l2s_inference_ragged.argtypes = [_vp, _i, ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp), _lens, _lens, _lens, _i, _i, _i, _fp, _vp, _fp,
                                            _vp, _i64, _vp]
+    # the evaluate-shaped ragged group (include/l2s.h): likewise absent from a library built before it (tools/ragged/time_forward_ragged.py times one
+    # next to this build)
+    if hasattr(L, "l2s_forward_eval_ragged"):
+        _lens, _offs = ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(_i64)
+        L.l2s_forward_eval_ragged_plan.argtypes = [_i, _lens, _lens, _lens, _offs, _offs, _offs, _offs, ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_i)]
+        L.l2s_workspace_bytes_eval_ragged.argtypes = [_i, _lens, _lens, _lens, _i, _i]
+        L.l2s_workspace_bytes_eval_ragged.restype = _i64
+        L.l2s_forward_eval_ragged.argtypes = [_vp, _i, ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp), _lens, _lens, _lens, _lens, _i, _i,
+                                              _fp, _fp, _fp, _fp, _fp, _vp, _i64, _vp]
     # device-side mel targets (include/l2s.h): likewise absent from a library built before them
     if hasattr(L, "l2s_mel_targets"):
         L.l2s_mel_frames.argtypes = [_i64]
@@ -333,6 +343,36 @@ def ragged_plan(batch_B, batch_T, video_lengths):
     check(lib().l2s_ragged_plan(G, (i32 * G)(*[int(b) for b in batch_B]), (i32 * G)(*[int(t) for t in batch_T]), (i32 * max(n, 1))(*flat), f0, p0,
                                 ctypes.byref(N), ctypes.byref(Tmax)))
     return list(f0[:N.value + 1]), list(p0[:N.value + 1]), N.value, Tmax.value
+
+
+def _i32s(vals):
+    vals = [int(v) for v in vals]
+    return (ctypes.c_int32 * max(len(vals), 1))(*vals)
+
+
+def forward_eval_ragged_plan(batch_B, batch_T, batch_S):
+    """`l2s_forward_eval_ragged_plan`: where the packed outputs of an evaluate-shaped ragged group start, a pure host function of the library.  `batch_B` /
+    `batch_T` / `batch_S`: clips, padded length and decode steps of every batch.  Returns `(mel_off, stop_off, attn_off, dis_off, N, Tmax, Smax)`: four
+    lists of G + 1 float offsets - batch g's block is `[off[g], off[g + 1])` - and the clips, the longest padding and the most steps of the group.
+    Raises `RuntimeError` with the library's message for shapes outside the limits."""
+    G = len(batch_B)
+    if len(batch_T) != G or len(batch_S) != G:
+        raise ValueError(f"batch_B, batch_T and batch_S hold one entry per batch ({G}), got {len(batch_T)} and {len(batch_S)}")
+    offs = [(_i64 * (G + 1))() for _ in range(4)]
+    N, Tmax, Smax = _i(), _i(), _i()
+    check(lib().l2s_forward_eval_ragged_plan(G, _i32s(batch_B), _i32s(batch_T), _i32s(batch_S), *offs, ctypes.byref(N), ctypes.byref(Tmax), ctypes.byref(Smax)))
+    return tuple(list(o) for o in offs) + (N.value, Tmax.value, Smax.value)
+
+
+def workspace_bytes_eval_ragged(batch_B, batch_T, batch_S, H: int = 96, W: int = 96) -> int:
+    """`l2s_workspace_bytes_eval_ragged`: the workspace of an evaluate-shaped ragged group of these batch shapes, every frame real."""
+    G = len(batch_B)
+    if len(batch_T) != G or len(batch_S) != G:
+        raise ValueError(f"batch_B, batch_T and batch_S hold one entry per batch ({G}), got {len(batch_T)} and {len(batch_S)}")
+    need = int(lib().l2s_workspace_bytes_eval_ragged(G, _i32s(batch_B), _i32s(batch_T), _i32s(batch_S), H, W))
+    if need < 0:
+        check(1)
+    return need
 
 
 def speaker_packed_plan(samples):
@@ -641,21 +681,7 @@ class NativeModel:
         Returns, per batch, `(mel_post (B_g,80,S), lengths (B_g,), attn (B_g,S,T_g) or None)` - slices of the group's tensors; row b is what
         `inference(batch, video_lengths=)` gives for it."""
         G = len(batches)
-        if not 1 <= G <= MAX_GROUP:
-            raise ValueError(f"a ragged group holds 1..{MAX_GROUP} batches (L2S_MAX_GROUP), got {G}")
-        if len(video_lengths) != G:
-            raise ValueError(f"video_lengths must hold one sequence of lengths per batch ({G}), got {len(video_lengths)}")
-        shapes = [tuple(b[0].shape) for b in batches]
-        if any(len(sh) != 5 or sh[1] != 3 for sh in shapes) or any(sh[3:] != shapes[0][3:] for sh in shapes):
-            raise ValueError(f"the batches of a ragged group are (B,3,T,H,W) videos of one H x W, got {shapes}")
-        lens = [video_lengths_array(vl, sh[0], sh[2]) for vl, sh in zip(video_lengths, shapes)]      # ValueError / TypeError before anything reaches the device
-        N = sum(sh[0] for sh in shapes)
-        if N > MAX_RAGGED_CLIPS:
-            raise ValueError(f"a ragged group holds at most {MAX_RAGGED_CLIPS} clips (L2S_MAX_RAGGED_CLIPS), got {N}")
-        for b, sh in zip(batches, shapes):
-            m = sh[2] // 7      # l2s_min_T(T_g) for T_g >= 7 (the stride-7 branch of Content.agg)
-            if tuple(b[1].shape) != (sh[0], 256) or tuple(b[2].shape) != (sh[0] * m, 501):
-                raise ValueError(f"emb must be {(sh[0], 256)} and the gumbel noise {(sh[0] * m, 501)}, got {tuple(b[1].shape)} and {tuple(b[2].shape)}")
+        shapes, lens, N = self._ragged_check(batches, video_lengths)
         vids = [_f32(b[0]) for b in batches]
         embs = [_f32(b[1]) for b in batches]
         gums = [_f32(b[2]) for b in batches]
@@ -680,6 +706,75 @@ class NativeModel:
         for sh in shapes:
             out.append((mel_post[c:c + sh[0]], lengths[c:c + sh[0]], attn[c:c + sh[0], :, :sh[2]] if want_attn else None))
             c += sh[0]
+        return out
+
+    @staticmethod
+    def _ragged_check(batches, video_lengths):
+        """What the ragged entry points check before anything reaches the device: the group's limits, the shapes of every batch's operands and its
+        lengths (`ValueError` / `TypeError`).  Returns (video shapes, one int32 length array per batch, N)."""
+        G = len(batches)
+        if not 1 <= G <= MAX_GROUP:
+            raise ValueError(f"a ragged group holds 1..{MAX_GROUP} batches (L2S_MAX_GROUP), got {G}")
+        if len(video_lengths) != G:
+            raise ValueError(f"video_lengths must hold one sequence of lengths per batch ({G}), got {len(video_lengths)}")
+        shapes = [tuple(b[0].shape) for b in batches]
+        if any(len(sh) != 5 or sh[1] != 3 for sh in shapes) or any(sh[3:] != shapes[0][3:] for sh in shapes):
+            raise ValueError(f"the batches of a ragged group are (B,3,T,H,W) videos of one H x W, got {shapes}")
+        lens = [video_lengths_array(vl, sh[0], sh[2]) for vl, sh in zip(video_lengths, shapes)]      # ValueError / TypeError before anything reaches the device
+        N = sum(sh[0] for sh in shapes)
+        if N > MAX_RAGGED_CLIPS:
+            raise ValueError(f"a ragged group holds at most {MAX_RAGGED_CLIPS} clips (L2S_MAX_RAGGED_CLIPS), got {N}")
+        for b, sh in zip(batches, shapes):
+            m = sh[2] // 7      # l2s_min_T(T_g) for T_g >= 7 (the stride-7 branch of Content.agg)
+            if tuple(b[1].shape) != (sh[0], 256) or tuple(b[2].shape) != (sh[0] * m, 501):
+                raise ValueError(f"emb must be {(sh[0], 256)} and the gumbel noise {(sh[0] * m, 501)}, got {tuple(b[1].shape)} and {tuple(b[2].shape)}")
+        return shapes, lens, N
+
+    def forward_eval_ragged(self, batches, video_lengths, S):
+        """An evaluate-shaped ragged group (`l2s_forward_eval_ragged`): eval-mode `forward` at tf_ratio = 1 over up to 8 (video, emb, gumbel) batches that
+        differ in B, T and step count, at most 256 clips in all, as rows of ONE launch chain.  `video_lengths` = one sequence of B_g lengths in [7, T_g]
+        per batch, `S` = one step count in [1, 300] per batch (its `melspecs.shape[2]`).  Free-running: a teacher-forced batch keeps
+        `forward_eval(..., video_lengths=)`.  The chain decodes every row for max(S) steps; a shorter batch's extra steps reach no output.
+        Returns, per batch, `(mel (B_g,80,S_g), mel_post (B_g,80,S_g), stop (B_g,S_g), attention LOGITS (B_g,S_g,T_g), content_dis (B_g*min_T(T_g),501))` -
+        contiguous views of the group's five packed tensors, each what `forward_eval(batch, S_g, video_lengths=)` gives."""
+        G = len(batches)
+        shapes, lens, N = self._ragged_check(batches, video_lengths)
+        steps = S.detach().cpu().numpy() if isinstance(S, torch.Tensor) else np.asarray(S)
+        if steps.shape != (G,):
+            raise ValueError(f"S must hold one step count per batch - shape ({G},) - got {tuple(steps.shape)}")
+        if steps.dtype.kind not in "iu":
+            raise TypeError(f"S must hold integers, got {steps.dtype}")
+        bad = [(g, int(v)) for g, v in enumerate(steps) if v < 1 or v > 300]
+        if bad:
+            raise ValueError("S outside [1, 300]: " + ", ".join(f"batch {g}: {v}" for g, v in bad))
+        vids = [_f32(b[0]) for b in batches]
+        embs = [_f32(b[1]) for b in batches]
+        gums = [_f32(b[2]) for b in batches]
+        H, W = shapes[0][3:]
+        i32 = ctypes.c_int32
+        bB, bT, bS = (i32 * G)(*[sh[0] for sh in shapes]), (i32 * G)(*[sh[2] for sh in shapes]), (i32 * G)(*[int(v) for v in steps])
+        flat = (i32 * N)(*[v for l in lens for v in l])
+        offs = [(_i64 * (G + 1))() for _ in range(4)]
+        n_, t_, s_ = _i(), _i(), _i()
+        self._check(self._L.l2s_forward_eval_ragged_plan(G, bB, bT, bS, *offs, ctypes.byref(n_), ctypes.byref(t_), ctypes.byref(s_)))
+        mel_off, stop_off, attn_off, dis_off = (list(o) for o in offs)
+        need = int(self._L.l2s_workspace_bytes_eval_ragged(G, bB, bT, bS, H, W))
+        if need < 0:
+            self._check(1)
+        dev = vids[0].device
+        ws = self._workspace(need, dev)
+        new = lambda n: torch.empty(n, dtype=torch.float32, device=dev)      # noqa: E731
+        mel_cf, mel_post, stop, attn, dis = new(mel_off[G]), new(mel_off[G]), new(stop_off[G]), new(attn_off[G]), new(dis_off[G])
+        self.calls["l2s_forward_eval_ragged"] += 1
+        arr = lambda ts: (_vp * G)(*[t.data_ptr() for t in ts])      # noqa: E731
+        self._check(self._L.l2s_forward_eval_ragged(self._h, G, arr(vids), arr(embs), arr(gums), bB, bT, bS, flat, H, W, _ptr(mel_cf), _ptr(mel_post), _ptr(stop),
+                                                    _ptr(attn), _ptr(dis), _ptr(ws), ws.numel(), _stream()))
+        out = []
+        for g, sh in enumerate(shapes):
+            B, T, Sg = sh[0], sh[2], int(steps[g])
+            out.append((mel_cf[mel_off[g]:mel_off[g + 1]].view(B, 80, Sg), mel_post[mel_off[g]:mel_off[g + 1]].view(B, 80, Sg),
+                        stop[stop_off[g]:stop_off[g + 1]].view(B, Sg), attn[attn_off[g]:attn_off[g + 1]].view(B, Sg, T),
+                        dis[dis_off[g]:dis_off[g + 1]].view(B * (T // 7), 501)))
         return out
 
     def speaker_encoder_fwd(self, audio: torch.Tensor, taps: bool = False):

@@ -11,7 +11,9 @@ batch keeps the composition the single-process run would have used and results a
 length-masked entry points (``NativeModel.inference(..., video_lengths=)``, ``Lip2Speech.honour_video_lengths``;
 include/l2s.h "per-clip video lengths") a clip's output no longer depends on what shares its batch, and masked
 calls no longer have to go one batch per call: the pool's job entry "inference_ragged" (``Lip2Speech.inference_many_lengths``)
-runs batches of unequal B and T as rows of one launch chain (``l2s_inference_ragged``, include/l2s.h "ragged groups").
+runs batches of unequal B and T as rows of one launch chain (``l2s_inference_ragged``, include/l2s.h "ragged groups"), and
+"forward_ragged" (``Lip2Speech.forward_many_lengths``) does the same for the evaluate route, where the step count differs from
+batch to batch as well (``l2s_forward_eval_ragged``).
 """
 from __future__ import annotations
 
@@ -258,6 +260,8 @@ class InflightPool:
     def _job_key(job: dict):
         if job["entry"] == "inference_ragged":      # a ragged group takes batches of any B and T: the key ignores both
             return (job["entry"], int(job["video"].shape[3]), int(job["video"].shape[4]), int(job["S"]), bool(job.get("want_attn", False)))
+        if job["entry"] == "forward_ragged":        # the evaluate-shaped ragged group: every batch brings its own step count as well
+            return (job["entry"], int(job["video"].shape[3]), int(job["video"].shape[4]))
         mask = job.get("mask")
         return (job["entry"], tuple(job["video"].shape), int(job["S"]), bool(job.get("want_attn", False)),
                 bytes(bytearray(mask)) if mask is not None else None)
@@ -265,13 +269,13 @@ class InflightPool:
     @staticmethod
     def group_accepts(group_jobs: List[dict], job: dict, group: int) -> bool:
         """The grouping rule of `imap`, a pure function: may `job` join the running group `group_jobs`?  A group closes at `group` jobs and when the
-        key changes (`_job_key`: entry, shape, S, mask - for "inference_ragged" entry, H, W, S, want_attn only); a ragged group also when the next
-        batch would take its clips past 256 (L2S_MAX_RAGGED_CLIPS)."""
+        key changes (`_job_key`: entry, shape, S, mask - for "inference_ragged" entry, H, W, S, want_attn only, for "forward_ragged" entry, H, W); a
+        ragged group of either kind also when the next batch would take its clips past 256 (L2S_MAX_RAGGED_CLIPS)."""
         if not group_jobs:
             return True
         if len(group_jobs) >= group or InflightPool._job_key(job) != InflightPool._job_key(group_jobs[0]):
             return False
-        if job["entry"] == "inference_ragged":
+        if job["entry"] in ("inference_ragged", "forward_ragged"):
             return sum(int(j["video"].shape[0]) for j in group_jobs) + int(job["video"].shape[0]) <= 256
         return True
 
@@ -299,13 +303,17 @@ class InflightPool:
         if j0["entry"] == "inference_ragged":
             return self.model.inference_ragged([(j["video"], j["emb"], j["gumbel"]) for j in jobs], [j["video_lengths"] for j in jobs], S=j0["S"],
                                                want_attn=j0.get("want_attn", False))
+        if j0["entry"] == "forward_ragged":
+            return self.model.forward_eval_ragged([(j["video"], j["emb"], j["gumbel"]) for j in jobs], [j["video_lengths"] for j in jobs], [j["S"] for j in jobs])
         raise ValueError(f"unknown entry {j0['entry']!r}")
 
     def imap(self, items: Iterable, prepare: Callable, depth: int = 2) -> Iterator:
         """Streaming `map` for loader-driven callers (the reference's demo.py:60-90 / evaluate.py:22-51 loops take one batch per iteration):
         `items` is any iterable (a DataLoader), `prepare(item)` turns an item into a job - a dict with `entry` ("inference" =
         `Lip2Speech.inference`, "forward" = eval-mode `Lip2Speech.forward`, "inference_ragged" = `Lip2Speech.inference(video_lengths=)`: the job also
-        carries `video_lengths`, and jobs of ANY B and T share a chain - `l2s_inference_ragged`, at most 256 clips), device tensors `video`, `emb`, `gumbel`, the step count `S`, and
+        carries `video_lengths`, and jobs of ANY B and T share a chain - `l2s_inference_ragged`, at most 256 clips; "forward_ragged" = eval-mode
+        `Lip2Speech.forward` at tf_ratio = 1 with `honour_video_lengths`: likewise with `video_lengths`, and jobs of any B, T AND S share a chain -
+        `l2s_forward_eval_ragged`), device tensors `video`, `emb`, `gumbel`, the step count `S`, and
         optionally `want_attn` (inference), `teacher` + `mask` (forward: scheduled sampling) and `finish(result) -> value`.  Yields one value per
         item, IN ORDER, each bit-identical to the single-batch call.
 
