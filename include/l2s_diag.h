@@ -132,6 +132,14 @@ int l2s_op_launch_chain2(int kind, int n_launches, int blocks, int n_per_block, 
  * from the atomic counter at log_dev[0]; capacity in records; records past it are dropped (the counter keeps counting).  NULL switches it off. */
 int l2s_op_stamp_log(void* log_dev, int64_t capacity);
 
+/* Which kernel would launch_skinny (every launch of the decode step, of the BiLSTM recurrence and of the speaker LSTMs) pick?  The batch is described by
+ * integers: `groups` = count x 8 ints {chunks of 16 columns in each of the four K segments, output tiles, epilogue (0 plain, 1 frag16, 2 LSTM cell, 3 mel +
+ * stop), weight planes present, summed segment present}, B rows.  The options are those of model m (l2s_model_set_option; it need not be finalised);
+ * chains = launch chains in flight (l2s_set_thread_chains), stamped_* = the stamped build of l2s_op_skinny_timeline / l2s_op_flat_timeline armed.
+ * Writes one line into out[cap]: the kernel with its template arguments (without the early-stop flag), "grid=(x,y,z) block=N lds=BYTES" - or "ERROR "
+ * and the error text where the launch would be refused.  Launches nothing and needs no device. */
+int l2s_op_skinny_form(l2s_model* m, int count, const int* groups, int B, int chains, int stamped_skinny, int stamped_flat, char* out, int cap);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,6 +11,12 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#ifdef L2S_DIAG
+#include <cxxabi.h>
+#include <dlfcn.h>      // l2s_op_skinny_form names a kernel by its symbol
+#endif
 #include <functional>
 #include <cstring>
 #include <map>
@@ -1892,6 +1898,38 @@ int l2s_op_gemm_x3_timeline(void* ts_dev, int block) { gemm_x3_set_timeline((uns
 int l2s_op_fused_unit_timeline(void* ts_dev, int h) { shuffle_set_timeline((unsigned long long*)ts_dev, h); return 0; }
 int l2s_op_stamp_log(void* log_dev, int64_t capacity) {
     L2S_REQUIRE(set_stamp_log((unsigned long long*)log_dev, (long long)capacity) == 0, "stamp log: hipMemcpyToSymbol failed");
+    return 0;
+}
+
+// which kernel launch_skinny picks for a batch described by integers; no device is touched
+int l2s_op_skinny_form(l2s_model* m, int count, const int* groups, int B, int chains, int stamped_skinny, int stamped_flat, char* out, int cap) {
+    L2S_REQUIRE(m && groups && out && cap > 0 && count >= 1 && count <= SKINNY_MAX_GROUP && B >= 1, "bad arguments");
+    static float a[1];      // stands for every operand: the rule asks only whether W3 / a_sum are set
+    SkinnyBatch sb{};
+    for (int i = 0; i < count; ++i) {
+        const int* g = groups + 8 * i;      // nchunks[4], ntiles, epi, W3 set, a_sum set
+        SkinnyP& p = sb.p[i];
+        for (int j = 0; j < 4; ++j) { p.seg[j] = {a, g[j]}; p.K += 16 * g[j]; }
+        p.nseg = 4; p.B = B; p.epi = g[5]; p.W3 = g[6] ? a : nullptr; p.a_sum = g[7] ? a : nullptr;
+        sb.ntiles[i] = g[4];
+    }
+    sb.count = count;
+    dim3 grid; int block = 0, lds = 0;
+    g_err.clear();
+    const void* fn = skinny_form_kernel(sb, m->opt, chains, stamped_skinny != 0, stamped_flat != 0, grid, block, lds);
+    if (!fn && !g_err.empty()) { std::snprintf(out, cap, "ERROR %s", g_err.c_str()); return 0; }      // the text a caller of the refused launch reads from l2s_last_error
+    // The kernel is named by its symbol: this needs the kernel handles in the library's dynamic symbol table (default visibility, external linkage - true of
+    // this build, not under -fvisibility=hidden), no '>' in a kernel's parameter types, and the early-stop flag as the last template argument of every
+    // kernel template but the stamped "_timed" ones.  tests/test_skinny_form_host.py fails on every row if one of these stops holding.
+    Dl_info di{};
+    L2S_REQUIRE(fn && dladdr(fn, &di) && di.dli_sname, "the form names no kernel instance");
+    char* const dm = abi::__cxa_demangle(di.dli_sname, nullptr, nullptr, nullptr);      // "[void ]l2s::name<args, ES>(parameters)"
+    std::string k(dm ? dm : di.dli_sname);
+    std::free(dm);
+    k = k.substr(0, k.find('<') == std::string::npos ? k.find('(') : k.rfind('>') + 1);
+    k.erase(0, k.find("l2s::") + 5);
+    if (k.find("_timed") == std::string::npos) k = k.substr(0, k.rfind(", ")) + ">";      // every other batch-row kernel template ends in the early-stop flag
+    std::snprintf(out, cap, "%s grid=(%u,%u,%u) block=%d lds=%d", k.c_str(), grid.x, grid.y, grid.z, block, lds);
     return 0;
 }
 

@@ -419,7 +419,7 @@ struct SkinnyBatch { SkinnyP p[SKINNY_MAX_GROUP]; int ntiles[SKINNY_MAX_GROUP]; 
 #define L2S_ES_RETURN(arg) do { if ((arg).es_end && (arg).es_step >= *(arg).es_end) return; } while (0)
 int launch_skinny(const SkinnyBatch& b, hipStream_t s, const char* name, const Options& o = Options());
 int launch_skx_planes(const float* Wf, int ntiles, int K, void* out, hipStream_t s);      // bf16 planes of a packed LSTM weight (SkinnyP::W3): ntiles * K * 16 * 6 bytes
-bool skinny_sum_supported(const Options& o);           // launches with SkinnyP::a_sum need the straight-line four-wave blocks: default operand batching, no stamped build
+bool skinny_sum_supported(const Options& o);           // does LSTM layer 0's launch with SkinnyP::a_sum have a block form under these options (skinny.hip skinny_form, step 5)?
 void attn_set_timeline(unsigned long long* ts);        // non-null: the stamped attention kernel (tools/attn_timeline.py)
 void skinny_set_flat_timeline(unsigned long long* ts);   // non-null: the stamped build of the step's flat first phase (tools/flat_timeline.py)
 void skinny_set_timeline(unsigned long long* ts);      // non-null: launch the stamped measurement build (tools/skinny_timeline.py)
@@ -427,6 +427,9 @@ void skinny_set_timeline(unsigned long long* ts);      // non-null: launch the s
 int launch_probe(int kind, int blocks, int n_per_block, const float* in, float* out, hipStream_t s);      // libl2s_diag.so only, like every *_set_timeline above
 void skinny_set_flat_timeline(unsigned long long* ts);
 int set_stamp_log(unsigned long long* log, long long cap);      // the block-stamp log of the step kernels (skinny.hip; libl2s_diag.so only)
+// the kernel launch_skinny would launch for this (validated) batch - the ES = false entry of the dispatcher's row - with its launch shape; null, and the
+// error set as launch_skinny sets it, where it would refuse.  Launches nothing (skinny.hip; libl2s_diag.so only)
+const void* skinny_form_kernel(const SkinnyBatch& bl, const Options& o, int chains, bool stamped_skinny, bool stamped_flat, dim3& grid, int& block, int& lds);
 
 // ---------------------------------------------------------------- decoder helper kernels (decoder_kernels.hip)
 struct AttnP {

@@ -71,13 +71,7 @@ static int skinny_layout_of(const SkinnyP& p) {
 
 // Every step kernel exists twice: ES = false is the kernel as it always was; ES = true (option "early_stop", launched when the batch carries a control
 // block) returns at its top once its step is at or past the call's end step.  Two symbols rather than one run-time null test: the test's kernel-argument
-// load would sit in front of every other argument load of every launch, option on or off.
-#define SK_UNPACK(...) __VA_ARGS__
-#define SK_ES_LAUNCH(es, NAME, TARGS, ...)                                                        \
-    do {                                                                                          \
-        if (es) hipLaunchKernelGGL((NAME<SK_UNPACK TARGS, true>), __VA_ARGS__);                   \
-        else hipLaunchKernelGGL((NAME<SK_UNPACK TARGS, false>), __VA_ARGS__);                     \
-    } while (0)
+// load would sit in front of every other argument load of every launch, option on or off.  The twin is picked at the launch.
 
 // MAXC = chunks per wave the instance is unrolled for (K <= 128 * MAXC): the 24 operand registers per chunk pair are what sets the
 // kernel's VGPR count, so launches whose longest K is 512 / 1024 get their own, smaller instances
@@ -174,16 +168,6 @@ __global__ __launch_bounds__(512, 1) void skinny_sp_kernel(const SkinnyBatch bat
     skinny_block_sp<typename SkLay<LAYID>::T>(batch.p[g], blockIdx.x, blockIdx.y, sp_lds, batch.ntiles[g], mts);
     L2S_BLOCK_STAMP_END(4u, batch.p[g].c_out);
 }
-template <int LAYID>
-static int launch_sp(const SkinnyBatch& bl, int maxt, int mts, hipStream_t s) {
-    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(skinny_sp_kernel<LAYID, false>), hipFuncAttributeMaxDynamicSharedMemorySize, SKP_LDS_BYTES);
-    L2S_CHECK_HIP(attr);
-    static const hipError_t attr_es = hipFuncSetAttribute(reinterpret_cast<const void*>(skinny_sp_kernel<LAYID, true>), hipFuncAttributeMaxDynamicSharedMemorySize, SKP_LDS_BYTES);
-    L2S_CHECK_HIP(attr_es);
-    SK_ES_LAUNCH(bl.es_end, skinny_sp_kernel, (LAYID), dim3(maxt / 4, (mts + 3) / 4, bl.count), dim3(512), SKP_LDS_BYTES, s, bl, mts);
-    L2S_CHECK_HIP(hipGetLastError());
-    return 0;
-}
 // weight planes of the split-bf16 LSTM blocks from the packed fp32 fragments ([tile][chunk][lane] float4): chunk pair ip of K slice s = chunks
 // (s + 16 ip, s + 16 ip + 8); out[tile][s][ip][plane][lane] = 8 bf16 (the lane's quad of the first chunk, then of the second)
 __global__ __launch_bounds__(256) void skx_planes_kernel(const float4* __restrict__ Wf, int ntiles, int NC, uint4* __restrict__ out) {
@@ -211,44 +195,6 @@ int launch_skx_planes(const float* Wf, int ntiles, int K, void* out, hipStream_t
     return 0;
 }
 
-template <int RT, int CT, int DEPTH>
-static bool launch_rc4(const SkinnyBatch& bl, int lay, int kind, int maxt, int mts, hipStream_t s, int x3 = 0) {
-    const dim3 grid((maxt + CT - 1) / CT, (mts + RT - 1) / RT, bl.count), blk(256);
-    constexpr int HD = 3;       // operand slots in flight of the half-CU 4x2 form (four: its 256 registers spill)
-    if constexpr (RT * CT >= 8) {       // the half-CU form exists for the 4x2 block; the smaller shapes already leave room beside them
-        if (kind == 2 && x3 == 3 && (lay == 1 || lay == 2 || lay == 6)) {
-            if (lay == 1) SK_ES_LAUNCH(bl.es_end, skinny_rc4h_kernel, (RT, CT, 1, HD), grid, blk, 0, s, bl, mts);
-            else if (lay == 2) SK_ES_LAUNCH(bl.es_end, skinny_rc4h_kernel, (RT, CT, 2, HD), grid, blk, 0, s, bl, mts);
-            else SK_ES_LAUNCH(bl.es_end, skinny_rc4h_kernel, (RT, CT, 6, HD), grid, blk, 0, s, bl, mts);
-            return true;
-        }
-    }
-    if (kind == 2 && x3 >= 2 && (lay == 1 || lay == 2 || lay == 6)) {
-        if (lay == 1) SK_ES_LAUNCH(bl.es_end, skinny_rc8x_kernel, (RT, CT, 1, DEPTH), grid, dim3(512), 0, s, bl, mts);      // the BiLSTM recurrence (K = 512)
-        else if (lay == 2) SK_ES_LAUNCH(bl.es_end, skinny_rc8x_kernel, (RT, CT, 2, DEPTH), grid, dim3(512), 0, s, bl, mts);
-        else SK_ES_LAUNCH(bl.es_end, skinny_rc8x_kernel, (RT, CT, 6, DEPTH), grid, dim3(512), 0, s, bl, mts);
-        return true;
-    }
-    if (kind == 2 && x3 && (lay == 1 || lay == 2 || lay == 6)) {
-        if (lay == 1) SK_ES_LAUNCH(bl.es_end, skinny_rc4x_kernel, (RT, CT, 1, DEPTH), grid, blk, 0, s, bl, mts);
-        else if (lay == 2) SK_ES_LAUNCH(bl.es_end, skinny_rc4x_kernel, (RT, CT, 2, DEPTH), grid, blk, 0, s, bl, mts);
-        else SK_ES_LAUNCH(bl.es_end, skinny_rc4x_kernel, (RT, CT, 6, DEPTH), grid, blk, 0, s, bl, mts);
-        return true;
-    }
-    if (kind == 2) {
-        if (lay == 1) SK_ES_LAUNCH(bl.es_end, skinny_rc4_kernel, (RT, CT, 1, DEPTH, true), grid, blk, 0, s, bl, mts);
-        else if (lay == 2) SK_ES_LAUNCH(bl.es_end, skinny_rc4_kernel, (RT, CT, 2, DEPTH, true), grid, blk, 0, s, bl, mts);
-        else if (lay == 3) SK_ES_LAUNCH(bl.es_end, skinny_rc4_kernel, (RT, CT, 3, DEPTH, true), grid, blk, 0, s, bl, mts);
-        else if (lay == 5) SK_ES_LAUNCH(bl.es_end, skinny_rc4_kernel, (RT, CT, 5, DEPTH, true), grid, blk, 0, s, bl, mts);
-        else if (lay == 6) SK_ES_LAUNCH(bl.es_end, skinny_rc4_kernel, (RT, CT, 6, DEPTH, true), grid, blk, 0, s, bl, mts);
-        else return false;
-    } else if (kind == 1) {
-        if (lay == 1) SK_ES_LAUNCH(bl.es_end, skinny_rc4_kernel, (RT, CT, 1, DEPTH, false), grid, blk, 0, s, bl, mts);
-        else if (lay == 2) SK_ES_LAUNCH(bl.es_end, skinny_rc4_kernel, (RT, CT, 2, DEPTH, false), grid, blk, 0, s, bl, mts);
-        else return false;
-    } else return false;
-    return true;
-}
 #ifdef L2S_DIAG
 // measurement build of the 4x2 LSTM form: thread 0 of every block stamps its phases (8 x 64-bit per block, tools/skinny_timeline.py ROWS=256)
 template <int LAYID, bool X3 = false, int NW = 4>
@@ -258,64 +204,6 @@ __global__ __launch_bounds__(64 * NW, 1) void skinny_rcs_timed_kernel(const Skin
     skinny_block_rcs<4, 2, typename SkLay<LAYID>::T, 4, true, true, NW, X3>(batch.p[0], blockIdx.x, blockIdx.y, red, batch.ntiles[0], mts, ts + (int64_t)blk * 8);
 }
 #endif
-// lay: the K layout every group shares; kind: 2 = every group is an LSTM cell, 1 = none is
-template <int RT, int CT, int DEPTH>
-static bool launch_rcs(const SkinnyBatch& bl, int lay, int kind, int maxt, int mts, hipStream_t s) {
-    const dim3 grid((maxt + CT - 1) / CT, (mts + RT - 1) / RT, bl.count), blk(512);
-    if (kind == 2) {
-        if (lay == 1) SK_ES_LAUNCH(bl.es_end, skinny_rcs_kernel, (RT, CT, 1, DEPTH, 2, true), grid, blk, 0, s, bl, mts);
-        else if (lay == 2) SK_ES_LAUNCH(bl.es_end, skinny_rcs_kernel, (RT, CT, 2, DEPTH, 2, true), grid, blk, 0, s, bl, mts);
-        else if (lay == 3) SK_ES_LAUNCH(bl.es_end, skinny_rcs_kernel, (RT, CT, 3, DEPTH, 2, true), grid, blk, 0, s, bl, mts);
-        else if (lay == 5) SK_ES_LAUNCH(bl.es_end, skinny_rcs_kernel, (RT, CT, 5, DEPTH, 2, true), grid, blk, 0, s, bl, mts);
-        else return false;
-    } else if (kind == 1) {
-        if (lay == 1) SK_ES_LAUNCH(bl.es_end, skinny_rcs_kernel, (RT, CT, 1, DEPTH, 2, false), grid, blk, 0, s, bl, mts);
-        else if (lay == 2) SK_ES_LAUNCH(bl.es_end, skinny_rcs_kernel, (RT, CT, 2, DEPTH, 2, false), grid, blk, 0, s, bl, mts);
-        else return false;
-    } else return false;
-    return true;
-}
-
-template <int RT, int CT>
-static void launch_rc(const SkinnyBatch& bl, int cls, int maxt, int mts, hipStream_t s, int rc_jb, int lay, int kind, int x3 = 0) {
-    const dim3 grid((maxt + CT - 1) / CT, (mts + RT - 1) / RT, bl.count), blk(512);
-    // every group in one of the decode step's K layouts and no forced batching: the straight-line form (exact waits, DEPTH - 1 chunks in flight
-    // under every chunk's MFMAs)
-    // Default ("skinny_rc_jb" = 0) where every group has one of the decode step's K layouts: FOUR waves per block, one per SIMD, each playing two of
-    // the eight K slices, straight-line code with exact waits and four chunks in flight (skinny_block_rcs<.., NW = 4>).  With eight waves the two
-    // waves of a SIMD do not share the matrix pipe evenly: the older one runs ahead, the younger follows in its shadow and finishes ~4 us later,
-    // alone (stamped build, tools/skinny_timeline.py ROWS=256: block lifetime 14.3 us, kernel span 19.4 us at K = 1024); with one wave per SIMD the
-    // pipe is 90 % busy through the K loop and every block ends within 0.2 us of the others (span 12.4 us).  Same bits.
-    if (rc_jb == 0 && lay && launch_rc4<RT, CT, 4>(bl, lay, kind, maxt, mts, s, x3)) return;
-    if (rc_jb == 28 && lay && launch_rcs<RT, CT, (RT * CT >= 8 ? 4 : 6)>(bl, lay, kind, maxt, mts, s)) return;      // the same straight-line form on eight waves
-    if constexpr (RT * CT >= 8) {
-        // the 4x2 form holds 6 fragments per chunk and runs alone on its CU.  Default ("skinny_rc_jb" = 0): one-chunk operand batches, four in
-        // flight - the registers of two two-chunk batches, 1.5x the latency tolerance: 20.2 -> 19.4 us per LSTM launch at 256 rows; five in flight
-        // (15): 19.9; 2 / 4: the two-chunk batches, two in flight, of round 2.  (Two 2x2 blocks SHARING a CU - one-chunk batches, three in flight,
-        // 118 VGPRs - are slower, 21.2 us: the same CU then pulls 786 KB instead of 590 KB; what bounds these launches is bytes per CU.)
-        if (rc_jb == 2 || rc_jb == 4) {
-            if (cls == 4) SK_ES_LAUNCH(bl.es_end, skinny_rc_kernel, (RT, CT, 4, 2, 2, 2), grid, blk, 0, s, bl, mts);
-            else if (cls == 8) SK_ES_LAUNCH(bl.es_end, skinny_rc_kernel, (RT, CT, 8, 2, 2, 2), grid, blk, 0, s, bl, mts);
-            else SK_ES_LAUNCH(bl.es_end, skinny_rc_kernel, (RT, CT, 12, 2, 2, 2), grid, blk, 0, s, bl, mts);
-        } else if (rc_jb == 15) {
-            if (cls == 4) SK_ES_LAUNCH(bl.es_end, skinny_rc_kernel, (RT, CT, 4, 1, 2, 4), grid, blk, 0, s, bl, mts);
-            else if (cls == 8) SK_ES_LAUNCH(bl.es_end, skinny_rc_kernel, (RT, CT, 8, 1, 2, 5), grid, blk, 0, s, bl, mts);
-            else SK_ES_LAUNCH(bl.es_end, skinny_rc_kernel, (RT, CT, 12, 1, 2, 5), grid, blk, 0, s, bl, mts);
-        } else {
-            if (cls == 4) SK_ES_LAUNCH(bl.es_end, skinny_rc_kernel, (RT, CT, 4, 1, 2, 4), grid, blk, 0, s, bl, mts);
-            else if (cls == 8) SK_ES_LAUNCH(bl.es_end, skinny_rc_kernel, (RT, CT, 8, 1, 2, 4), grid, blk, 0, s, bl, mts);
-            else SK_ES_LAUNCH(bl.es_end, skinny_rc_kernel, (RT, CT, 12, 1, 2, 4), grid, blk, 0, s, bl, mts);
-        }
-    } else if (rc_jb == 4) {
-        if (cls == 4) SK_ES_LAUNCH(bl.es_end, skinny_rc_kernel, (RT, CT, 4, 4, 2, 2), grid, blk, 0, s, bl, mts);
-        else if (cls == 8) SK_ES_LAUNCH(bl.es_end, skinny_rc_kernel, (RT, CT, 8, 4, 2, 2), grid, blk, 0, s, bl, mts);
-        else SK_ES_LAUNCH(bl.es_end, skinny_rc_kernel, (RT, CT, 12, 4, 2, 2), grid, blk, 0, s, bl, mts);
-    } else {
-        if (cls == 4) SK_ES_LAUNCH(bl.es_end, skinny_rc_kernel, (RT, CT, 4, 2, 2, 2), grid, blk, 0, s, bl, mts);
-        else if (cls == 8) SK_ES_LAUNCH(bl.es_end, skinny_rc_kernel, (RT, CT, 8, 2, 2, 2), grid, blk, 0, s, bl, mts);
-        else SK_ES_LAUNCH(bl.es_end, skinny_rc_kernel, (RT, CT, 12, 2, 2, 2), grid, blk, 0, s, bl, mts);
-    }
-}
 
 // ---- balanced flat launch for phases that carry several GEMM groups (the step's first phase: prenet1 o fc_out, Q, content Q, fc_out+stop).
 // A (tiles x rows x groups) grid with ONE block shape leaves the chip unbalanced: at 256 rows the 2x2 grid has 280 live blocks for 256 CUs, so
@@ -414,24 +302,9 @@ static int plan_flat(const SkinnyBatch& bl, int mts, int cap, SkinnyFlat& fl, bo
     for (int k = n; k <= SKINNY_MAX_GROUP; ++k) fl.first[k] = pos;
     return best8 * 100 + best4;
 }
-#ifdef L2S_DIAG
-static unsigned long long* g_flat_ts = nullptr;
-void skinny_set_flat_timeline(unsigned long long* ts) { g_flat_ts = ts; }
-#endif
-template <int S8, int S4>
-static void launch_flat(const SkinnyBatch& bl, const SkinnyFlat& fl, int mts, hipStream_t s, int stat) {
-#ifdef L2S_DIAG
-    if (g_flat_ts && stat == 1) {
-        if constexpr (S8 == 22 && S4 == 42) { hipLaunchKernelGGL((skinny_flat_kernel<S8, S4, 1, true>), dim3(fl.first[SKINNY_MAX_GROUP]), dim3(512), 0, s, bl, fl, mts, g_flat_ts); return; }
-    }
-#endif
-    if (stat == 2) SK_ES_LAUNCH(bl.es_end, skinny_flat_kernel, (S8, S4, 2, false), dim3(fl.first[SKINNY_MAX_GROUP]), dim3(256), 0, s, bl, fl, mts, (unsigned long long*)nullptr);
-    else if (stat == 1) SK_ES_LAUNCH(bl.es_end, skinny_flat_kernel, (S8, S4, 1, false), dim3(fl.first[SKINNY_MAX_GROUP]), dim3(512), 0, s, bl, fl, mts, (unsigned long long*)nullptr);
-    else SK_ES_LAUNCH(bl.es_end, skinny_flat_kernel, (S8, S4, 0, false), dim3(fl.first[SKINNY_MAX_GROUP]), dim3(512), 0, s, bl, fl, mts, (unsigned long long*)nullptr);
-}
 
 #ifdef L2S_DIAG
-// measurement build of the same kernel: every block's thread 0 stamps its phases (8 stamps per block, block index = (z*gridDim.y + y)*gridDim.x + x)
+// measurement build of the general kernel: every block's thread 0 stamps its phases (8 stamps per block, block index = (z*gridDim.y + y)*gridDim.x + x)
 __global__ __launch_bounds__(512) void skinny_kernel_timed(const SkinnyBatch batch, unsigned long long* ts) {
     __shared__ float red[SK_RED_FLOATS];
     const int g = blockIdx.z;
@@ -443,32 +316,238 @@ __global__ __launch_bounds__(512) void skinny_kernel_timed(const SkinnyBatch bat
 }
 #endif
 #ifdef L2S_DIAG
-static unsigned long long* g_skinny_ts = nullptr;
-#else
-static constexpr unsigned long long* g_skinny_ts = nullptr;      // the product never launches a stamped build
-#endif
-// options (l2s_common.h Options): "skinny_static" = compile-time segment layouts: +2 % one batch at a time (23.6 -> 23.1 us/step), -3 % with four
-// batches in flight (1.60 -> 1.56 M mel-frames/s), off by default; "skinny_sized" = instances sized for the launch's longest K;
-// "skinny_split" / "skinny_split8" = operand loads of the K <= 1536 / K <= 1024 instance in this many batches
-#ifdef L2S_DIAG
+static unsigned long long *g_skinny_ts = nullptr, *g_flat_ts = nullptr;      // non-null: the stamped measurement builds run (tools/skinny_timeline.py, tools/flat_timeline.py)
 void skinny_set_timeline(unsigned long long* ts) { g_skinny_ts = ts; }
+void skinny_set_flat_timeline(unsigned long long* ts) { g_flat_ts = ts; }
+#else
+static constexpr unsigned long long *g_skinny_ts = nullptr, *g_flat_ts = nullptr;      // the product never launches a stamped build
 #endif
 
+// ---- which kernel a launch takes: skinny_form decides, skinny_dispatch launches what it decided
+enum SkFamily { SKF_REFUSED, SKF_GENERAL, SKF_SPLIT, SKF_RC, SKF_RCS, SKF_RC4, SKF_RC4X, SKF_RC8X, SKF_RC4H, SKF_SP, SKF_FLAT, SKF_GENERAL_TIMED, SKF_RCS_TIMED, SKF_FLAT_TIMED };
+struct SkForm {
+    SkFamily family;      // the kernel template (skinny_kernel, _kernel_split, _rc, _rcs, _rc4, _rc4x, _rc8x, _rc4h, _sp, _flat; the stamped builds) and the arguments it takes
+    // (else 0): RT x CT tiles per block, the shared K layout id, MAXC, JB (split: NB), waves per SIMD, operand slots in flight, waves per block, the flat grid's S8 / S4 / STATIC
+    int rt, ct, lay, maxc, jb, wps, depth, nw, s8, s4, stat;
+    bool lstm, x3;        // IS_LSTM (where the template takes it); the stamped 4x2 build's split-bf16 path
+    dim3 grid; int block, lds;       // threads; dynamic LDS bytes
+    SkinnyFlat flat;      // SKF_FLAT*: the groups' block ranges
+    const char* error;    // SKF_REFUSED: why
+};
 static bool skinny_shape_known(int shape) { return shape == 0 || shape == 11 || shape == 21 || shape == 22 || shape == 42; }
-// a forced "skinny_rc" / "skinny_rc_multi" outside {11, 21, 22, 42} falls through to skinny_kernel<cls>, which knows nothing of SkinnyP::a_sum: the
-// caller then keeps LSTM layer 0 on [content | prenet | o | h0] (K = 1280, hoist_vproj = 1)
-bool skinny_sum_supported(const Options& o) { return o.rc_jb == 0 && g_skinny_ts == nullptr && skinny_shape_known(o.rc_shape) && skinny_shape_known(o.rc_shape_multi); }
+// The rule, in the order it is applied, for a validated batch (launch_skinny).  Pure: no HIP call, no global; chains = launch chains the caller keeps in
+// flight (chains_hint()), stamped_* = a stamped build is armed.  The early-stop twin is not part of the form: the launch's bl.es_end picks it.
+// Options (l2s_common.h Options): "skinny_static" = compile-time segment layouts: +2 % one batch at a time (23.6 -> 23.1 us/step), -3 % with four
+// batches in flight (1.60 -> 1.56 M mel-frames/s), off by default; "skinny_sized" = instances sized for the launch's longest K;
+// "skinny_split" / "skinny_split8" = operand loads of the K <= 1536 / K <= 1024 instance in this many batches
+static SkForm skinny_form(const SkinnyBatch& bl, const Options& o, int chains, bool stamped_skinny, bool stamped_flat) {
+    SkForm f{};
+    const int n = bl.count, mts = (bl.p[0].B + 15) / 16;
+    int maxt = 0, maxk = 0, n_lstm = 0, lay = skinny_layout_of(bl.p[0]);
+    bool planes = true, any_sum = false, tiles4 = true, flat_lay = true;
+    for (int i = 0; i < n; ++i) {
+        const SkinnyP& p = bl.p[i];
+        const int l = skinny_layout_of(p);
+        maxt = std::max(maxt, bl.ntiles[i]); maxk = std::max(maxk, p.K); n_lstm += p.epi == SK_LSTM ? 1 : 0;
+        planes = planes && p.W3; any_sum = any_sum || p.a_sum; tiles4 = tiles4 && bl.ntiles[i] > 0 && bl.ntiles[i] % 4 == 0;
+        flat_lay = flat_lay && l == (p.K > 512 ? 2 : 1) && p.epi != SK_LSTM;
+        if (l != lay) lay = 0;      // one of the decode step's K layouts shared by every group of the launch, else 0
+    }
+    if (lay == 4) lay = 0;      // the 256-wide prenet layers: two chunks per slice, general blocks
+    const int cls = !o.skinny_sized ? 12 : maxk <= 512 ? 4 : maxk <= 1024 ? 8 : 12;
+    const int kind = n_lstm == n ? 2 : n_lstm == 0 ? 1 : 0;      // 2 = every group is an LSTM cell, 1 = none is
+    const bool half_rows = o.half_min_mts > 0 && mts >= o.half_min_mts;
+    // Block forms by how many launch chains the caller keeps in flight (l2s_set_thread_chains): with two or more, blocks of half a compute unit, so
+    // that kernels of different chains run side by side on the CUs; a chain that has the chip to itself keeps the eight-wave blocks (3-4 % faster
+    // alone).  Same bits either way.
+    const bool overlap = chains >= 2;
+    // 1. block shape: a forced one, else (many batch rows) the largest that still gives the chip one block per CU - 4x2 also where the half-CU form applies
+    int shape = (n > 1 && o.rc_shape_multi) ? o.rc_shape_multi : o.rc_shape;
+    if (shape == 0) {
+        shape = 11;
+        if (mts >= 4) {
+            auto blocks = [&](int rt, int ct) { int nb = 0; for (int i = 0; i < n; ++i) nb += (bl.ntiles[i] + ct - 1) / ct; return nb * ((mts + rt - 1) / rt); };
+            // (a 4x4 block - 33 % fewer operand bytes per tile - is MFMA-bound at 30.4 us per block: 512 rows in 31.9 us against 33.0 us with 4x2
+            //  blocks in two rounds, and 256 accumulator + operand registers with spills; not kept)
+            if (blocks(4, 2) >= 224 || (o.lstm_x3 >= 3 && overlap && half_rows && o.rc_jb == 0 && kind == 2 && planes)) shape = 42;
+            else if (blocks(2, 2) >= 224) shape = 22;
+            else if (blocks(2, 1) >= 224) shape = 21;
+        }
+    }
+    // 2. LSTM launches on the bf16 matrix cores (1: four waves, 2: eight, 3: half-CU 4x2 blocks when chains overlap, 4: shared-panel blocks where they apply, else as 3)
+    int x3 = (o.rc_jb == 0 && kind == 2 && planes && (lay == 1 || lay == 2 || lay == 6)) ? o.lstm_x3 : 0;
+    if (x3 >= 3 && !overlap) x3 = 2;
+    // 3. one activation panel per CU (skinny_sp_kernel) under the conditions of the half-CU 4x2 form, for the K = 1024 layouts and whole 4-tile column
+    //    blocks; every other launch takes the form "lstm_x3" = 3 gives it
+    if (x3 == 4 && shape == 42 && !stamped_skinny && half_rows && (lay == 2 || lay == 6) && tiles4) {
+        f.family = SKF_SP; f.lay = lay; f.grid = dim3(maxt / 4, (mts + 3) / 4, n); f.block = 512; f.lds = SKP_LDS_BYTES;
+        return f;
+    }
+    if (x3 == 4) x3 = 3;
+    // 4. several groups, >= 128 rows (below that the 1x1 / 2x1 uniform grids with two blocks per CU are faster, tools/time_step_phases.py): per-group
+    //    block shapes in one flat grid of at most one block per CU ("skinny_flat", default on).  A forced block shape wins; LSTM groups (the BiLSTM's two
+    //    directions) keep the uniform grid of four-wave blocks
+    if (!stamped_skinny && n > 1 && mts >= 8 && o.skinny_flat && !o.rc_shape && !o.rc_shape_multi && maxk <= 1024 && kind == 1) {
+        const bool half = o.flat_half != 0 && (o.flat_half >= 2 || overlap);
+        const int plan = plan_flat(bl, mts, half ? 512 : 256, f.flat, half, o.flat_xcd != 0);
+        if (plan) {
+            // STATIC: 0 = general blocks, 1 = straight-line eight-wave blocks (default: 12.4 us at 256 rows against 12.9 general), 2 = straight-line four-wave
+            // blocks ("skinny_rc_jb" = 44: 14.9 us - these blocks move 262 KB for 3.4 us of matrix work; eight waves keep more loads in flight)
+            f.s8 = plan / 100; f.s4 = plan % 100; f.stat = !flat_lay ? 0 : half ? 2 : o.rc_jb == 0 || o.rc_jb == 28 ? 1 : o.rc_jb == 44 ? 2 : 0;
+            f.family = stamped_flat && f.stat == 1 && plan == 2242 ? SKF_FLAT_TIMED : SKF_FLAT;
+            f.grid = dim3(f.flat.first[SKINNY_MAX_GROUP]); f.block = f.stat == 2 ? 256 : 512;
+            return f;
+        }
+    }
+    // 5. a summed segment (SkinnyP::a_sum) is formed by the straight-line four-wave LSTM blocks alone.  A forced "skinny_rc" / "skinny_rc_multi" outside {11, 21, 22,
+    //    42} would fall through to skinny_kernel<cls>, which knows nothing of it: the caller (skinny_sum_supported) then keeps LSTM layer 0 on K = 1280 (hoist_vproj = 1)
+    if (any_sum && !(lay == 6 && kind == 2 && o.rc_jb == 0 && !stamped_skinny && skinny_shape_known(o.rc_shape) && skinny_shape_known(o.rc_shape_multi) && skinny_shape_known(shape))) {
+        f.error = "skinny: a summed segment needs the straight-line LSTM blocks (shape 11 / 21 / 22 / 42, default operand batching)";
+        return f;
+    }
+    if (stamped_skinny) {      // 6. the stamped builds (tools/skinny_timeline.py ROWS=256): the 4x2 LSTM form of a single group, else the general blocks
+        const bool rcs = shape == 42 && n == 1 && kind == 2 && (lay == 2 || lay == 3);
+        f.family = rcs ? SKF_RCS_TIMED : SKF_GENERAL_TIMED; f.lay = rcs ? lay : 0; f.x3 = rcs && x3 != 0; f.nw = rcs && x3 != 2 ? 4 : 8;
+        f.grid = rcs ? dim3((maxt + 1) / 2, (mts + 3) / 4, 1) : dim3(maxt, mts, n); f.block = 64 * f.nw;
+        return f;
+    }
+    if (shape == 42 || shape == 22 || shape == 21 || shape == 11) {      // 7. register-blocked RT x CT blocks (skinny_dev.h skinny_block_rc / _rcs)
+        auto blocked = [&](SkFamily family, int nw) { f.family = family; f.rt = shape / 10; f.ct = shape % 10; f.nw = nw; f.grid = dim3((maxt + f.ct - 1) / f.ct, (mts + f.rt - 1) / f.rt, n); f.block = 64 * nw; };
+        if (o.rc_jb == 0 && lay && (kind == 2 || (kind == 1 && lay <= 2))) {
+            // Default ("skinny_rc_jb" = 0) where every group has one of the decode step's K layouts: FOUR waves per block, one per SIMD, each playing two of
+            // the eight K slices, straight-line code with exact waits and four chunks in flight (skinny_block_rcs<.., NW = 4>).  With eight waves the two
+            // waves of a SIMD do not share the matrix pipe evenly: the older one runs ahead, the younger follows in its shadow and finishes ~4 us later,
+            // alone (stamped build, tools/skinny_timeline.py ROWS=256: block lifetime 14.3 us, kernel span 19.4 us at K = 1024); with one wave per SIMD the
+            // pipe is 90 % busy through the K loop and every block ends within 0.2 us of the others (span 12.4 us).  Same bits.
+            // On the bf16 matrix cores: the half-CU form exists for the 4x2 block (the smaller shapes already leave room beside them); else eight waves ("lstm_x3" >= 2), else four
+            blocked(x3 == 3 && shape == 42 ? SKF_RC4H : x3 >= 2 ? SKF_RC8X : x3 ? SKF_RC4X : SKF_RC4, x3 >= 2 && !(x3 == 3 && shape == 42) ? 8 : 4);
+            f.lay = lay; f.x3 = x3 != 0; f.lstm = !x3 && kind == 2; f.depth = f.family == SKF_RC4H ? 3 : 4;
+            return f;
+        }
+        if (shape != 11 && o.rc_jb == 28 && lay && (kind == 2 ? lay != 6 : kind == 1 && lay <= 2)) {      // the same straight-line form on eight waves
+            blocked(SKF_RCS, 8);
+            f.lay = lay; f.lstm = kind == 2; f.depth = shape == 42 ? 4 : 6; f.wps = 2;
+            return f;
+        }
+        if (shape != 11) {
+            // the 4x2 form holds 6 fragments per chunk and runs alone on its CU.  Default ("skinny_rc_jb" = 0): one-chunk operand batches, four in
+            // flight - the registers of two two-chunk batches, 1.5x the latency tolerance: 20.2 -> 19.4 us per LSTM launch at 256 rows; five in flight
+            // (15): 19.9; 2 / 4: the two-chunk batches, two in flight, of round 2.  (Two 2x2 blocks SHARING a CU - one-chunk batches, three in flight,
+            // 118 VGPRs - are slower, 21.2 us: the same CU then pulls 786 KB instead of 590 KB; what bounds these launches is bytes per CU.)
+            blocked(SKF_RC, 8);
+            f.maxc = cls; f.wps = 2; f.jb = 2; f.depth = 2;
+            if (shape != 42) f.jb = o.rc_jb == 4 ? 4 : 2;
+            else if (o.rc_jb != 2 && o.rc_jb != 4) { f.jb = 1; f.depth = o.rc_jb == 15 && cls != 4 ? 5 : 4; }
+            return f;
+        }
+    }
+    // 8. 16 x 16 tiles, eight waves that split K: the general blocks, sized for the launch's longest K
+    if (any_sum) { f.error = "skinny: no block form of this launch sums u = prenet + o in its loader (SkinnyP::a_sum would be ignored)"; return f; }
+    const int nb = cls == 8 ? (o.skinny_split8 == 2 ? 2 : 1) : cls == 12 && (o.skinny_split == 2 || o.skinny_split == 3) ? o.skinny_split : 1;
+    f.family = nb > 1 ? SKF_SPLIT : SKF_GENERAL; f.maxc = cls; f.nw = 8; f.grid = dim3(maxt, mts, n); f.block = 512;
+    if (nb > 1) { f.jb = nb; f.wps = cls == 12 && nb == 2 ? 6 : 8; }
+    return f;
+}
+// does LSTM layer 0's launch with u = prenet + o summed by the loader (K = 1024, one group) have a form under these options?  Asked of the rule itself
+bool skinny_sum_supported(const Options& o) {
+    static float a[1]; SkinnyBatch b{};
+    b.p[0].seg[0] = {a, 16}; b.p[0].seg[1] = {a, 16}; b.p[0].seg[2] = {a, 32}; b.p[0].a_sum = a; b.p[0].K = 1024; b.p[0].B = 1; b.p[0].epi = SK_LSTM;
+    b.ntiles[0] = 128; b.count = 1;
+    return skinny_form(b, o, 1, g_skinny_ts != nullptr, false).family != SKF_REFUSED;
+}
+// One row per kernel instantiation a form can name: its two entry points (early-stop twin, plain; a stamped build has the plain one) and which parameters
+// the kernel takes - read off the kernel's own signature by sk_fn's overloads, so a kernel whose parameters change fits no row and does not compile.
+enum SkArgs { SKA_B, SKA_BM, SKA_BFMT, SKA_BT, SKA_BMT };      // batch [, flat plan] [, mts] [, stamps]
+struct SkFn { const void *es, *plain; SkArgs args; };
+using SkTs = unsigned long long*;
+#define sk_mk(es, plain, a) SkFn{reinterpret_cast<const void*>(es), reinterpret_cast<const void*>(plain), a}
+static SkFn sk_fn(void (*es)(SkinnyBatch), void (*plain)(SkinnyBatch)) { return sk_mk(es, plain, SKA_B); }
+static SkFn sk_fn(void (*es)(SkinnyBatch, int), void (*plain)(SkinnyBatch, int)) { return sk_mk(es, plain, SKA_BM); }
+static SkFn sk_fn(void (*es)(SkinnyBatch, SkinnyFlat, int, SkTs), void (*plain)(SkinnyBatch, SkinnyFlat, int, SkTs)) { return sk_mk(es, plain, SKA_BFMT); }
+static SkFn sk_fn(void (*es)(SkinnyBatch, SkTs), void (*plain)(SkinnyBatch, SkTs)) { return sk_mk(es, plain, SKA_BT); }
+static SkFn sk_fn(void (*es)(SkinnyBatch, int, SkTs), void (*plain)(SkinnyBatch, int, SkTs)) { return sk_mk(es, plain, SKA_BMT); }
+// a row's key: the family, the block shape RT * 10 + CT (flat grid: S8) and up to three of the family's arguments
+constexpr int sk_key(int family, int shape, int a = 0, int b = 0, int c = 0) { return (((family * 100 + shape) * 100 + a) * 10 + b) * 10 + c; }
+#define SK_ROW(key, NAME, ...) case key: return sk_fn(NAME<__VA_ARGS__, true>, NAME<__VA_ARGS__, false>);
+#define SK_X3_ROWS(FAM, NAME, RT, CT, DEPTH)      /* the split-bf16 LSTM blocks: layouts [32], [32|32], [16|16+16|32] */ \
+    SK_ROW(sk_key(FAM, RT * 10 + CT, 1), NAME, RT, CT, 1, DEPTH) SK_ROW(sk_key(FAM, RT * 10 + CT, 2), NAME, RT, CT, 2, DEPTH) SK_ROW(sk_key(FAM, RT * 10 + CT, 6), NAME, RT, CT, 6, DEPTH)
+#define SK_RC4_ROW(RT, CT, LAY, LSTM) SK_ROW(sk_key(SKF_RC4, RT * 10 + CT, LAY, LSTM), skinny_rc4_kernel, RT, CT, LAY, 4, LSTM != 0)
+#define SK_RC4_ROWS(RT, CT)      /* the four-wave straight-line forms of one block shape */ \
+    SK_X3_ROWS(SKF_RC8X, skinny_rc8x_kernel, RT, CT, 4) SK_X3_ROWS(SKF_RC4X, skinny_rc4x_kernel, RT, CT, 4)                                 \
+    SK_RC4_ROW(RT, CT, 1, 1) SK_RC4_ROW(RT, CT, 2, 1) SK_RC4_ROW(RT, CT, 3, 1) SK_RC4_ROW(RT, CT, 5, 1) SK_RC4_ROW(RT, CT, 6, 1) SK_RC4_ROW(RT, CT, 1, 0) SK_RC4_ROW(RT, CT, 2, 0)
+#define SK_RCS_ROW(RT, CT, LAY, LSTM, DEPTH) SK_ROW(sk_key(SKF_RCS, RT * 10 + CT, LAY, LSTM), skinny_rcs_kernel, RT, CT, LAY, DEPTH, 2, LSTM != 0)
+#define SK_RCS_ROWS(RT, CT, DEPTH)      /* the eight-wave straight-line form */ \
+    SK_RCS_ROW(RT, CT, 1, 1, DEPTH) SK_RCS_ROW(RT, CT, 2, 1, DEPTH) SK_RCS_ROW(RT, CT, 3, 1, DEPTH) SK_RCS_ROW(RT, CT, 5, 1, DEPTH) SK_RCS_ROW(RT, CT, 1, 0, DEPTH) SK_RCS_ROW(RT, CT, 2, 0, DEPTH)
+#define SK_RC_ROW(RT, CT, MAXC, JB, DEPTH) SK_ROW(sk_key(SKF_RC, RT * 10 + CT, MAXC, JB, DEPTH), skinny_rc_kernel, RT, CT, MAXC, JB, 2, DEPTH)
+#define SK_RC_ROWS(RT, CT, JB, DEPTH) SK_RC_ROW(RT, CT, 4, JB, DEPTH) SK_RC_ROW(RT, CT, 8, JB, DEPTH) SK_RC_ROW(RT, CT, 12, JB, DEPTH)
+#define SK_FLAT_ROWS(S8, S4) SK_ROW(sk_key(SKF_FLAT, S8, S4, 2), skinny_flat_kernel, S8, S4, 2, false) SK_ROW(sk_key(SKF_FLAT, S8, S4, 1), skinny_flat_kernel, S8, S4, 1, false) SK_ROW(sk_key(SKF_FLAT, S8, S4, 0), skinny_flat_kernel, S8, S4, 0, false)
+// The rows stand in the order the kernels have always had in the code object (instantiations are emitted in the order they are first named): where the
+// hot kernels of three chains land in the instruction cache depends on it.
+static SkFn sk_row(const SkForm& f) {
+    const bool flat = f.family == SKF_FLAT || f.family == SKF_FLAT_TIMED;
+    switch (sk_key(f.family, flat ? f.s8 : f.rt * 10 + f.ct, f.lay + f.maxc + f.s4, f.lstm + f.jb + f.stat, f.family == SKF_RC ? f.depth : f.family == SKF_RCS_TIMED ? f.x3 + (f.nw == 8) : 0)) {
+        case sk_key(SKF_SP, 0, 2): { const auto plain = skinny_sp_kernel<2, false>; return sk_fn(skinny_sp_kernel<2, true>, plain); }      // (named plain first, as ever)
+        case sk_key(SKF_SP, 0, 6): { const auto plain = skinny_sp_kernel<6, false>; return sk_fn(skinny_sp_kernel<6, true>, plain); }      // (named plain first, as ever)
+        SK_FLAT_ROWS(21, 21) SK_FLAT_ROWS(21, 22) SK_FLAT_ROWS(21, 42) SK_FLAT_ROWS(22, 21) SK_FLAT_ROWS(22, 22) SK_FLAT_ROWS(22, 42)      // the pairs plan_flat can return
+        SK_RC4_ROWS(1, 1)
+        SK_X3_ROWS(SKF_RC4H, skinny_rc4h_kernel, 4, 2, 3)      // three operand slots in flight (four: its 256 registers spill)
+        SK_RC4_ROWS(4, 2) SK_RCS_ROWS(4, 2, 4) SK_RC_ROWS(4, 2, 2, 2) SK_RC_ROW(4, 2, 4, 1, 4) SK_RC_ROW(4, 2, 8, 1, 5) SK_RC_ROW(4, 2, 12, 1, 5) SK_RC_ROW(4, 2, 8, 1, 4) SK_RC_ROW(4, 2, 12, 1, 4)
+        SK_RC4_ROWS(2, 2) SK_RCS_ROWS(2, 2, 6) SK_RC_ROWS(2, 2, 4, 2) SK_RC_ROWS(2, 2, 2, 2)
+        SK_RC4_ROWS(2, 1) SK_RCS_ROWS(2, 1, 6) SK_RC_ROWS(2, 1, 4, 2) SK_RC_ROWS(2, 1, 2, 2)
+        SK_ROW(sk_key(SKF_GENERAL, 0, 4), skinny_kernel, 4) SK_ROW(sk_key(SKF_SPLIT, 0, 8, 2), skinny_kernel_split, 8, 2, 8) SK_ROW(sk_key(SKF_GENERAL, 0, 8), skinny_kernel, 8)
+        SK_ROW(sk_key(SKF_SPLIT, 0, 12, 2), skinny_kernel_split, 12, 2, 6) SK_ROW(sk_key(SKF_SPLIT, 0, 12, 3), skinny_kernel_split, 12, 3, 8) SK_ROW(sk_key(SKF_GENERAL, 0, 12), skinny_kernel, 12)
+#ifdef L2S_DIAG
+        case sk_key(SKF_FLAT_TIMED, 22, 42, 1): return sk_fn(nullptr, skinny_flat_kernel<22, 42, 1, true>);
+        case sk_key(SKF_GENERAL_TIMED, 0): return sk_fn(nullptr, skinny_kernel_timed);
+        case sk_key(SKF_RCS_TIMED, 0, 3): return sk_fn(nullptr, skinny_rcs_timed_kernel<3>);
+        case sk_key(SKF_RCS_TIMED, 0, 2): return sk_fn(nullptr, skinny_rcs_timed_kernel<2>);
+        case sk_key(SKF_RCS_TIMED, 0, 2, 0, 1): return sk_fn(nullptr, skinny_rcs_timed_kernel<2, true>);
+        case sk_key(SKF_RCS_TIMED, 0, 2, 0, 2): return sk_fn(nullptr, skinny_rcs_timed_kernel<2, true, 8>);
+#endif
+        default: return SkFn{};
+    }
+}
+static int skinny_refused(const SkForm& f) { L2S_REQUIRE(f.family != SKF_REFUSED, f.error); return 0; }
+static int skinny_dispatch(const SkForm& f, const SkinnyBatch& bl, int mts, hipStream_t s) {
+    if (skinny_refused(f)) return 1;
+    const SkFn row = sk_row(f);
+    const void* const fn = bl.es_end && row.es ? row.es : row.plain;      // the early-stop twin where the launch carries a control block
+    L2S_REQUIRE(fn != nullptr, "skinny: the form names no kernel instance");
+    if (f.family == SKF_SP) {      // 160 KB of dynamic LDS: the limit of the four instantiations is raised once
+        static const hipError_t attr = [] {
+            hipError_t e = hipSuccess;
+            for (int lay : {2, 6})
+                for (const void* k : {sk_row(SkForm{SKF_SP, 0, 0, lay}).es, sk_row(SkForm{SKF_SP, 0, 0, lay}).plain}) e = std::max(e, hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, SKP_LDS_BYTES));
+            return e;
+        }();
+        L2S_CHECK_HIP(attr);
+    }
+    SkTs ts = f.family == SKF_FLAT ? nullptr : f.family == SKF_FLAT_TIMED ? g_flat_ts : g_skinny_ts;
+    void *const a_bl = const_cast<SkinnyBatch*>(&bl), *const a_fl = const_cast<SkinnyFlat*>(&f.flat);
+    void* args[SKA_BMT + 1][4] = {{a_bl}, {a_bl, &mts}, {a_bl, a_fl, &mts, &ts}, {a_bl, &ts}, {a_bl, &mts, &ts}};      // by SkArgs: exactly the kernel's parameters
+    (void)hipLaunchKernel(fn, f.grid, dim3(f.block), args[row.args], f.lds, s);      // a failed launch is reported by hipGetLastError below
+    L2S_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+#ifdef L2S_DIAG
+// for include/l2s_diag.h l2s_op_skinny_form: the kernel the dispatcher's row names for the form of this (validated) batch, with its launch shape; null
+// where the launch is refused, the error set as launch_skinny sets it.  Launches nothing.
+const void* skinny_form_kernel(const SkinnyBatch& bl, const Options& o, int chains, bool stamped_skinny, bool stamped_flat, dim3& grid, int& block, int& lds) {
+    const SkForm f = skinny_form(bl, o, chains, stamped_skinny, stamped_flat);
+    grid = f.grid; block = f.block; lds = f.lds;
+    return skinny_refused(f) ? nullptr : sk_row(f).plain;
+}
+#endif
 
 int launch_skinny(const SkinnyBatch& b, hipStream_t s, const char* name, const Options& o) {
     L2S_REQUIRE(b.count >= 1 && b.count <= SKINNY_MAX_GROUP, "skinny group size");
-    int maxt = 0, mts = 0;
+    int mts = 0;
     for (int i = 0; i < b.count; ++i) {
         const SkinnyP& p = b.p[i];
         int k = 0;
         for (int j = 0; j < 4; ++j) k += 16 * p.seg[j].nchunks;
         L2S_REQUIRE(k == p.K && p.K % 16 == 0 && p.K <= 16 * SK_WAVES * SK_MAXC, "skinny K segments");
         L2S_REQUIRE(p.B >= 1, "skinny B");
-        maxt = b.ntiles[i] > maxt ? b.ntiles[i] : maxt;
         int m = (p.B + 15) / 16;
         L2S_REQUIRE(mts == 0 || mts == m, "skinny groups must share B");
         mts = m;
@@ -479,98 +558,7 @@ int launch_skinny(const SkinnyBatch& b, hipStream_t s, const char* name, const O
         bl.p[i].layout = o.skinny_static ? skinny_layout_of(bl.p[i]) : 0;
     }
     ProfScope ps(name, s);
-    int maxk = 0;
-    for (int i = 0; i < bl.count; ++i) maxk = bl.p[i].K > maxk ? bl.p[i].K : maxk;
-    const int cls = !o.skinny_sized ? 12 : maxk <= 512 ? 4 : maxk <= 1024 ? 8 : 12;
-    // many batch rows: register-blocked blocks, the largest shape that still gives the chip one block per CU
-    int shape = (bl.count > 1 && o.rc_shape_multi) ? o.rc_shape_multi : o.rc_shape;
-    bool n_lstm_all = o.rc_jb == 0;       // every group an LSTM cell with pre-split planes: the launch can take the half-CU 4x2 form
-    for (int i = 0; i < bl.count; ++i) n_lstm_all = n_lstm_all && bl.p[i].epi == SK_LSTM && bl.p[i].W3;
-    if (shape == 0) {
-        shape = 11;
-        if (mts >= 4) {
-            auto blocks = [&](int rt, int ct) { int n = 0; for (int i = 0; i < bl.count; ++i) n += (bl.ntiles[i] + ct - 1) / ct; return n * ((mts + rt - 1) / rt); };
-            // (a 4x4 block - 33 % fewer operand bytes per tile - is MFMA-bound at 30.4 us per block: 512 rows in 31.9 us against 33.0 us with 4x2
-            //  blocks in two rounds, and 256 accumulator + operand registers with spills; not kept)
-            if (blocks(4, 2) >= 224 || (o.lstm_x3 >= 3 && chains_hint() >= 2 && o.half_min_mts > 0 && mts >= o.half_min_mts && n_lstm_all)) shape = 42;
-            else if (blocks(2, 2) >= 224) shape = 22;
-            else if (blocks(2, 1) >= 224) shape = 21;
-        }
-    }
-    // one of the decode step's K layouts shared by every group of the launch (1: [32], 2: [32|32], 3: [16|16|32|32] chunks), else 0
-    int rc_lay = skinny_layout_of(bl.p[0]);
-    for (int i = 1; i < bl.count; ++i) if (skinny_layout_of(bl.p[i]) != rc_lay) rc_lay = 0;
-    if (rc_lay == 4) rc_lay = 0;      // the 256-wide prenet layers: two chunks per slice, general blocks
-    int n_lstm = 0;
-    for (int i = 0; i < bl.count; ++i) n_lstm += bl.p[i].epi == SK_LSTM ? 1 : 0;
-    const int rc_kind = n_lstm == bl.count ? 2 : n_lstm == 0 ? 1 : 0;
-    // Block forms by how many launch chains the caller keeps in flight (l2s_set_thread_chains): with two or more, blocks of half a compute unit, so
-    // that kernels of different chains run side by side on the CUs; a chain that has the chip to itself keeps the eight-wave blocks (3-4 % faster
-    // alone).  Same bits either way.
-    const bool overlap = chains_hint() >= 2;
-    int x3 = (o.rc_jb == 0 && rc_kind == 2 && (rc_lay == 1 || rc_lay == 2 || rc_lay == 6)) ? o.lstm_x3 : 0;      // LSTM launches on the bf16 matrix cores (1: four waves, 2: eight, 3: half-CU 4x2 blocks when chains overlap, 4: shared-panel blocks where they apply, else as 3)
-    if (x3 >= 3 && !overlap) x3 = 2;
-    for (int i = 0; i < bl.count; ++i) if (!bl.p[i].W3) x3 = 0;
-    if (x3 == 4) {
-        // one activation panel per CU (skinny_sp_kernel) under the conditions of the half-CU 4x2 form, for the K = 1024 layouts and whole 4-tile column
-        // blocks; every other launch takes the form "lstm_x3" = 3 gives it
-        bool sp = shape == 42 && !g_skinny_ts && o.half_min_mts > 0 && mts >= o.half_min_mts && (rc_lay == 2 || rc_lay == 6);
-        for (int i = 0; i < bl.count; ++i) sp = sp && bl.ntiles[i] > 0 && bl.ntiles[i] % 4 == 0;
-        if (sp) return rc_lay == 2 ? launch_sp<2>(bl, maxt, mts, s) : launch_sp<6>(bl, maxt, mts, s);
-        x3 = 3;
-    }
-    // several groups, >= 128 rows (below that the 1x1 / 2x1 uniform grids with two blocks per CU are faster, tools/time_step_phases.py): per-group
-    // block shapes in one flat grid of at most one block per CU ("skinny_flat", default on)
-    if (!g_skinny_ts && bl.count > 1 && mts >= 8 && o.skinny_flat && !o.rc_shape && !o.rc_shape_multi && maxk <= 1024 && rc_kind == 1) {      // a forced block shape wins; LSTM groups (the BiLSTM's two directions) keep the uniform grid of four-wave blocks
-        SkinnyFlat fl{};
-        const bool half = o.flat_half != 0 && (o.flat_half >= 2 || chains_hint() >= 2);
-        const int plan = plan_flat(bl, mts, half ? 512 : 256, fl, half, o.flat_xcd != 0);
-        // 0 = general blocks, 1 = straight-line eight-wave blocks (default: 12.4 us at 256 rows against 12.9 general), 2 = straight-line four-wave
-        // blocks ("skinny_rc_jb" = 44: 14.9 us - these blocks move 262 KB for 3.4 us of matrix work; eight waves keep more loads in flight)
-        int stat = half ? 2 : o.rc_jb == 0 || o.rc_jb == 28 ? 1 : o.rc_jb == 44 ? 2 : 0;
-        for (int i = 0; i < bl.count; ++i) if (!(skinny_layout_of(bl.p[i]) == (bl.p[i].K > 512 ? 2 : 1) && bl.p[i].epi != SK_LSTM)) stat = 0;
-        if (plan) {
-            switch (plan) {
-                case 2121: launch_flat<21, 21>(bl, fl, mts, s, stat); break;
-                case 2122: launch_flat<21, 22>(bl, fl, mts, s, stat); break;
-                case 2142: launch_flat<21, 42>(bl, fl, mts, s, stat); break;
-                case 2221: launch_flat<22, 21>(bl, fl, mts, s, stat); break;
-                case 2222: launch_flat<22, 22>(bl, fl, mts, s, stat); break;
-                default: launch_flat<22, 42>(bl, fl, mts, s, stat); break;
-            }
-            L2S_CHECK_HIP(hipGetLastError());
-            return 0;
-        }
-    }
-    for (int i = 0; i < bl.count; ++i)
-        L2S_REQUIRE(!bl.p[i].a_sum || (rc_lay == 6 && rc_kind == 2 && skinny_sum_supported(o) && skinny_shape_known(shape) && shape != 0),
-                    "skinny: a summed segment needs the straight-line LSTM blocks (shape 11 / 21 / 22 / 42, default operand batching)");
-    bool any_sum = false;
-    for (int i = 0; i < bl.count; ++i) any_sum = any_sum || bl.p[i].a_sum;
-#ifdef L2S_DIAG
-    if (g_skinny_ts && shape == 42 && bl.count == 1 && rc_kind == 2 && (rc_lay == 2 || rc_lay == 3)) {
-        const dim3 grid((maxt + 1) / 2, (mts + 3) / 4, 1);
-        if (rc_lay == 3) hipLaunchKernelGGL(skinny_rcs_timed_kernel<3>, grid, dim3(256), 0, s, bl, mts, g_skinny_ts);
-        else if (x3 == 2) hipLaunchKernelGGL((skinny_rcs_timed_kernel<2, true, 8>), grid, dim3(512), 0, s, bl, mts, g_skinny_ts);
-        else if (x3) hipLaunchKernelGGL((skinny_rcs_timed_kernel<2, true>), grid, dim3(256), 0, s, bl, mts, g_skinny_ts);
-        else hipLaunchKernelGGL(skinny_rcs_timed_kernel<2>, grid, dim3(256), 0, s, bl, mts, g_skinny_ts);
-    }
-    else if (g_skinny_ts) hipLaunchKernelGGL(skinny_kernel_timed, dim3(maxt, mts, b.count), dim3(512), 0, s, bl, g_skinny_ts);
-    else
-#endif
-    if (shape == 11 && o.rc_jb == 0 && rc_lay && rc_kind && launch_rc4<1, 1, 4>(bl, rc_lay, rc_kind, maxt, mts, s, x3)) {}      // 16 x 16 tiles, four waves
-    else if (shape == 42) launch_rc<4, 2>(bl, cls, maxt, mts, s, o.rc_jb, rc_lay, rc_kind, x3);
-    else if (shape == 22) launch_rc<2, 2>(bl, cls, maxt, mts, s, o.rc_jb, rc_lay, rc_kind, x3);
-    else if (shape == 21) launch_rc<2, 1>(bl, cls, maxt, mts, s, o.rc_jb, rc_lay, rc_kind, x3);
-    else if (any_sum) L2S_REQUIRE(false, "skinny: no block form of this launch sums u = prenet + o in its loader (SkinnyP::a_sum would be ignored)");
-    else if (cls == 4) SK_ES_LAUNCH(bl.es_end, skinny_kernel, (4), dim3(maxt, mts, b.count), dim3(512), 0, s, bl);
-    else if (cls == 8 && o.skinny_split8 == 2) SK_ES_LAUNCH(bl.es_end, skinny_kernel_split, (8, 2, 8), dim3(maxt, mts, b.count), dim3(512), 0, s, bl);
-    else if (cls == 8) SK_ES_LAUNCH(bl.es_end, skinny_kernel, (8), dim3(maxt, mts, b.count), dim3(512), 0, s, bl);
-    else if (cls == 12 && o.skinny_split == 2) SK_ES_LAUNCH(bl.es_end, skinny_kernel_split, (12, 2, 6), dim3(maxt, mts, b.count), dim3(512), 0, s, bl);
-    else if (cls == 12 && o.skinny_split == 3) SK_ES_LAUNCH(bl.es_end, skinny_kernel_split, (12, 3, 8), dim3(maxt, mts, b.count), dim3(512), 0, s, bl);
-    else SK_ES_LAUNCH(bl.es_end, skinny_kernel, (12), dim3(maxt, mts, b.count), dim3(512), 0, s, bl);
-    L2S_CHECK_HIP(hipGetLastError());
-    return 0;
+    return skinny_dispatch(skinny_form(bl, o, chains_hint(), g_skinny_ts != nullptr, g_flat_ts != nullptr), bl, mts, s);
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -587,6 +575,20 @@ struct StepB {
 };
 
 constexpr int ATT_PRE2_MAXC = 2;      // prenet layer 2: K = 256 = 16 * 8 waves * 2 chunks
+// The block form of the attention launch, unmasked or masked (there chosen on the PADDED length: the LDS staging and the lane-per-frame soft-max need
+// T <= 32).  vl: projected values of a short clip fetched as 16-byte rows through LDS (attention_block<.., VLDS>): faster alone and at up to 128 rows per
+// launch (32 rows: 8.64 against 8.85 us inside the step), not at 256 (11.2 against 10.6 us event-bracketed, the pass 0.06 ms longer) - unless the caller
+// keeps several chains in flight: three 74-register blocks per CU leave room for other chains' kernels (+1.4 % at three chains): option 1 = by rows and chains, 2 = always.
+#define SK_UNPACK(...) __VA_ARGS__
+#define SK_ES_LAUNCH(es, NAME, TARGS, ...)                                                        \
+    do {                                                                                          \
+        if (es) hipLaunchKernelGGL((NAME<SK_UNPACK TARGS, true>), __VA_ARGS__);                   \
+        else hipLaunchKernelGGL((NAME<SK_UNPACK TARGS, false>), __VA_ARGS__);                     \
+    } while (0)
+static int step_attn_form(const AttnP& at, int lds_values, int skip0, int chains) {      // 0 = neither, 1 = vl, 2 = vl and skip0
+    const bool vl = lds_values && (lds_values >= 2 || at.B <= 128 || chains >= 2) && at.vp != nullptr && at.T <= 32;
+    return vl && skip0 && (skip0 >= 2 || chains >= 2) ? 2 : vl ? 1 : 0;
+}
 template <bool VL, bool SKIP0 = false, bool ES = false>
 __global__ __launch_bounds__(512) void step_attn_kernel(const StepB sb) {
     constexpr int SMF = ATT_SM_FLOATS + (VL && !SKIP0 ? ATT_VLDS_FLOATS : 0);
@@ -642,11 +644,10 @@ int launch_step_attn_masked(const AttnP& at, const SkinnyP& pre2, int pre2_tiles
     sb.pre2_tiles = pre2_tiles;
     sb.mts = (at.B + 15) / 16;
     ProfScope ps("step_attention_prenet2_masked", s);
-    // the block forms are chosen on the PADDED length (the LDS staging and the lane-per-frame soft-max need T <= 32), as launch_step_attn does
-    const bool vl = lds_values && (lds_values >= 2 || at.B <= 128 || chains_hint() >= 2) && at.vp != nullptr && at.T <= 32;
+    const int form = step_attn_form(at, lds_values, skip0, chains_hint());
     const dim3 grid(2 * at.B + pre2_tiles * sb.mts);
-    if (vl && skip0 && (skip0 >= 2 || chains_hint() >= 2)) SK_ES_LAUNCH(sb.at.es_end, step_attn_masked_kernel, (true, true), grid, dim3(512), 0, s, sb, lens);
-    else if (vl) SK_ES_LAUNCH(sb.at.es_end, step_attn_masked_kernel, (true, false), grid, dim3(512), 0, s, sb, lens);
+    if (form == 2) SK_ES_LAUNCH(sb.at.es_end, step_attn_masked_kernel, (true, true), grid, dim3(512), 0, s, sb, lens);
+    else if (form == 1) SK_ES_LAUNCH(sb.at.es_end, step_attn_masked_kernel, (true, false), grid, dim3(512), 0, s, sb, lens);
     else SK_ES_LAUNCH(sb.at.es_end, step_attn_masked_kernel, (false, false), grid, dim3(512), 0, s, sb, lens);
     L2S_CHECK_HIP(hipGetLastError());
     return 0;
@@ -680,17 +681,15 @@ int launch_step_attn(const AttnP& at, const SkinnyP& pre2, int pre2_tiles, hipSt
     sb.pre2_tiles = pre2_tiles;
     sb.mts = (at.B + 15) / 16;
     ProfScope ps("step_attention_prenet2", s);
-    // projected values of a short clip fetched as 16-byte rows through LDS (attention_block<.., VLDS>): faster alone and at up to 128 rows per launch
-    // (32 rows: 8.64 against 8.85 us inside the step), not at 256 (11.2 against 10.6 us event-bracketed, the pass 0.06 ms longer) - unless the caller keeps several
-    // chains in flight: three 74-register blocks per CU leave room for other chains' kernels (+1.4 % at three chains): option 1 = by rows and chains, 2 = always
-    const bool vl = lds_values && (lds_values >= 2 || at.B <= 128 || chains_hint() >= 2) && at.vp != nullptr && at.T <= 32;
+    const int form = step_attn_form(at, lds_values, skip0, chains_hint());
+    const dim3 grid(2 * at.B + pre2_tiles * sb.mts);
 #ifdef L2S_DIAG
-    if (g_attn_ts && vl) hipLaunchKernelGGL(step_attn_timed_kernel, dim3(2 * at.B + pre2_tiles * sb.mts), dim3(512), 0, s, sb, g_attn_ts);
+    if (g_attn_ts && form) hipLaunchKernelGGL(step_attn_timed_kernel, grid, dim3(512), 0, s, sb, g_attn_ts);
     else
 #endif
-    if (vl && skip0 && (skip0 >= 2 || chains_hint() >= 2)) SK_ES_LAUNCH(sb.at.es_end, step_attn_kernel, (true, true), dim3(2 * at.B + pre2_tiles * sb.mts), dim3(512), 0, s, sb);
-    else if (vl) SK_ES_LAUNCH(sb.at.es_end, step_attn_kernel, (true, false), dim3(2 * at.B + pre2_tiles * sb.mts), dim3(512), 0, s, sb);
-    else SK_ES_LAUNCH(sb.at.es_end, step_attn_kernel, (false, false), dim3(2 * at.B + pre2_tiles * sb.mts), dim3(512), 0, s, sb);
+    if (form == 2) SK_ES_LAUNCH(sb.at.es_end, step_attn_kernel, (true, true), grid, dim3(512), 0, s, sb);
+    else if (form == 1) SK_ES_LAUNCH(sb.at.es_end, step_attn_kernel, (true, false), grid, dim3(512), 0, s, sb);
+    else SK_ES_LAUNCH(sb.at.es_end, step_attn_kernel, (false, false), grid, dim3(512), 0, s, sb);
     L2S_CHECK_HIP(hipGetLastError());
     return 0;
 }
