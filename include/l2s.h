@@ -119,6 +119,32 @@ int l2s_mel_targets(const float* audio_packed, const int64_t* offsets, const int
                     int n_fft, int hop, int log_output, float mel_pad, int M_pad, int64_t A_pad, float* mels, float* gate, float* audio_pad,
                     int64_t* mel_lengths, void* ws, int64_t ws_bytes, void* stream);
 
+/* The face crops of the same boundary (datasets/grid/dataset.py:216-236 and its avspeech / wild twins; LRW's face crops, datasets/lrw/dataset.py:76-79): every
+ * frame of those loaders yields one aligned face of its OWN size; two drawn faces go through Resize((160,160)) and (x - 127.5) / 128 to the face tower, and the
+ * lower half of every face goes through Resize((96,96)), / 255 and the ImageNet Normalize to the model (frame_resize.hip).  torchvision is absent from the build
+ * image: the resize is its published tensor path as lip2speech_amd/datasets/lrw.py::face_recog_resize restates it - PARITY UNPINNED against the package.
+ *   packed_u8   dev: n uint8 RGB images, interleaved (H_i, W_i, 3), packed back to back, each starting on a 4-byte boundary; packed_bytes the buffer's size.
+ *               No byte outside [0, packed_bytes) is read, and none outside an image's own span rounded out to 4-byte boundaries
+ *   jobs        HOST array of n entries that may be freed on return: image (offset, H, W), source rectangle {y0, x0, h, w} inside it, flip (0 / 1: mirror the
+ *               rectangle's columns, then resize) and the output slot
+ *   mode        L2S_RESIZE_MOUTH: out dev (B,3,T,oh,ow), oh = ow in {96, 88}, slot = b T + t, value = ((u / 255) - mean_c) / std_c - the three operations of
+ *               l2s_normalise_pad_frames, the same bits for the same uint8 u.  L2S_RESIZE_FACE: out dev (B,2,3,160,160) as l2s_face_encoder_fwd reads it,
+ *               T = 2, slot = 2 b + k, value = (u - 127.5) / 128
+ *   u           bilinear, half-pixel centres, no antialias, fp32: src = (h / oh) (dst + 0.5) - 0.5 clamped at 0, the upper tap clamped at the rectangle's last
+ *               row / column; rounded half-to-even and clamped to [0, 255]
+ * Every element of out is written: a slot that no job names is exact zeros (the zero padding the *_masked entry points ask for).  A slot's bits do not depend on
+ * what else is in the call.  The table reaches the device in kernel arguments, L2S_RESIZE_JOBS_PER_LAUNCH slots per launch: no allocation, no synchronisation,
+ * no workspace.
+ * l2s_resize_check is the pure host check l2s_resize_normalise runs before anything is launched; its error names the job and the limit: offset not a multiple
+ * of 4 or image outside [0, packed_bytes); H or W outside [1, 4096]; rectangle empty or outside its image; flip not 0 / 1; slot outside [0, B T) or named
+ * twice; a mode or output size that is not built; B T above 2^24. */
+typedef struct l2s_resize_job { int64_t offset; int32_t H, W, y0, x0, h, w, flip, slot; } l2s_resize_job;
+enum { L2S_RESIZE_MOUTH = 0, L2S_RESIZE_FACE = 1 };
+#define L2S_RESIZE_JOBS_PER_LAUNCH 240
+int l2s_resize_check(const l2s_resize_job* jobs, int n, int64_t packed_bytes, int mode, int B, int T, int oh, int ow);
+int l2s_resize_normalise(const uint8_t* packed_u8, int64_t packed_bytes, const l2s_resize_job* jobs, int n, int mode, int B, int T, int oh, int ow,
+                         float* out, void* stream);
+
 /* VideoExtractor.forward (video.py:76-87): video dev (B,3,T,H,W) -> feat dev (B,T,768), L2-normalised.
  * H = W in {88, 96}. */
 int l2s_encoder_fwd(l2s_model* m, const float* video, int B, int T, int H, int W,

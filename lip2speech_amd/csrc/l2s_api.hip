@@ -1127,6 +1127,15 @@ int l2s_normalise_pad_frames(const uint8_t* packed_u8, const int64_t* offsets, c
     return launch_normalise_pad(packed_u8, offsets, frames, B, T, H, W, video, (hipStream_t)stream);
 }
 
+int l2s_resize_check(const l2s_resize_job* jobs, int n, int64_t packed_bytes, int mode, int B, int T, int oh, int ow) {
+    return resize_check(jobs, n, packed_bytes, mode, B, T, oh, ow);
+}
+
+int l2s_resize_normalise(const uint8_t* packed_u8, int64_t packed_bytes, const l2s_resize_job* jobs, int n, int mode, int B, int T, int oh, int ow, float* out,
+                         void* stream) {
+    return launch_resize_normalise(packed_u8, packed_bytes, jobs, n, mode, B, T, oh, ow, out, (hipStream_t)stream);
+}
+
 int l2s_build_visual(const float* feat, const float* emb, int B, int T, float* vis, void* stream) {
     L2S_REQUIRE(feat && emb && vis && B > 0 && T > 0, "bad arguments");
     hipStream_t s = (hipStream_t)stream;

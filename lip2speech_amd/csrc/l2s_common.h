@@ -9,6 +9,8 @@
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
+struct l2s_resize_job;      // include/l2s.h
+
 namespace l2s {
 
 // ---------------------------------------------------------------- error handling
@@ -312,6 +314,10 @@ int launch_frontend_pool(const float* z, const float* slope, int NF, int Hc, int
 // /255 then ImageNet mean/std, clips shorter than T zero-padded; offsets / frames are HOST arrays
 constexpr int MAX_COLLATE_CLIPS = 64;        // per launch (the clip table travels in the kernel arguments)
 int launch_normalise_pad(const uint8_t* packed, const int64_t* offsets, const int* frames, int B, int T, int H, int W, float* video, hipStream_t s);
+// face crops of unequal size (frame_resize.hip): the pure host check of a job table (include/l2s.h's l2s_resize_job), and the check plus the launches
+int resize_check(const ::l2s_resize_job* jobs, int n, int64_t packed_bytes, int mode, int B, int T, int oh, int ow);
+int launch_resize_normalise(const uint8_t* packed, int64_t packed_bytes, const ::l2s_resize_job* jobs, int n, int mode, int B, int T, int oh, int ow, float* out,
+                            hipStream_t s);
 // depthwise 3x3, pad 1, channel-last: in (N,Hi,Wi,ldi) channels [ci_off, ci_off+C) -> out (N,Ho,Wo,ldo) at co_off
 int launch_dwconv(const float* in, int N, int Hi, int Wi, int ldi, int ci_off, int C, int stride,
                   const float* w9 /*[9][C]*/, const float* scale, const float* shift,

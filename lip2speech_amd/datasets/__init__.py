@@ -13,7 +13,8 @@ from .spectrograms import MelSpec2Audio, MelSpectrogram  # noqa: F401
 from .lrw import LRW  # noqa: F401
 from .augmentation import FaceAugmentation  # noqa: F401
 from .unported import GRID, AVSpeech, WILD  # noqa: F401
-from .device import PackedAudio, PackedFrames, device_collate_fn_pad, device_collate_fn_pad_raw  # noqa: F401
+from .device import (PackedAudio, PackedFaces, PackedFrames, device_collate_fn_pad, device_collate_fn_pad_faces,  # noqa: F401
+                     device_collate_fn_pad_raw, faces_item_host)
 
 MEL_PAD = -11.5129      # ln(1e-5), the floor of the log-mel transform
 

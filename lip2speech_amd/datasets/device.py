@@ -12,10 +12,16 @@ The audio half has the same shape: `LRW(..., raw_audio=True)` skips the CPU mel 
 into one pinned fp32 buffer (`PackedAudio`) and `PackedAudio.to_device()` runs `l2s_mel_targets` - log-mel targets, gates, lengths and the
 zero-padded audio from one launch chain.  The audio, the gates and the lengths are exactly the host collate's; the mels are another order of
 the same fp32 sums than `torch.stft` + matmul, inside 8x the fp32 torch path's own error against fp64 (tests/test_mel_targets_gpu.py).
+
+The face crops of the loaders whose faces have no common size (reference: datasets/grid/dataset.py:216-236 and its avspeech / wild twins):
+an item is the list of a clip's aligned uint8 faces, the flip decision and the two drawn face indices; `PackedFaces` packs the images once
+into one pinned buffer and `PackedFaces.to_device()` runs `l2s_resize_normalise` twice on the one upload - the lower half of every face to the
+`(B,3,T,96,96)` video, the two drawn faces whole to the `(B,2,3,160,160)` face crops.  `faces_item_host` is the same tail in torch on the
+CPU: what a loader without the device does, and what the kernel is tested against (tests/test_frame_resize_gpu.py).
 """
 from __future__ import annotations
 
-from typing import List, Sequence
+from typing import List, Sequence, Tuple
 
 import torch
 
@@ -102,6 +108,103 @@ class PackedAudio:
             from .spectrograms import MelSpectrogram
             PackedAudio._transforms[device] = MelSpectrogram().to(device)
         return PackedAudio._transforms[device]
+
+
+def _resize_u8(x_u8: torch.Tensor, size: Tuple[int, int]) -> torch.Tensor:
+    """`transforms.Resize(size)` on a uint8 `(3,H,W)` tensor as `lrw.face_recog_resize` restates it (torchvision is absent here): bilinear,
+    half-pixel centres, no antialias, rounded back to uint8"""
+    x = torch.nn.functional.interpolate(x_u8[None].float(), size=size, mode="bilinear", align_corners=False)[0]
+    return x.round().clamp(0, 255).to(torch.uint8)
+
+
+def _chw(face) -> torch.Tensor:
+    """an aligned face as uint8 `(3,H,W)`: the reference's layout as it stands, `(H,W,3)` permuted (a face is at least 16 rows high, so a
+    first axis of 3 is the channels)"""
+    face = torch.as_tensor(face)
+    assert face.dtype == torch.uint8 and face.dim() == 3 and 3 in (face.shape[0], face.shape[2]), "a face is uint8 (3,H,W) or (H,W,3)"
+    return face if face.shape[0] == 3 else face.permute(2, 0, 1)
+
+
+def faces_item_host(faces, flip: bool, face_indices, size: int = 96):
+    """The tail of `GRID.__getitem__` (datasets/grid/dataset.py:225-236; the avspeech / wild loaders do the same) in torch on the CPU: the
+    aligned faces of one clip, uint8 `(3,H_i,W_i)` each with its own size -> `(lower_faces (T,3,size,size), face_crop (2,3,160,160))`.
+    `flip`: `FaceAugmentation`'s decision for the item (all faces mirrored); `face_indices`: the two drawn faces."""
+    from .lrw import IMAGENET_MEAN, IMAGENET_STD, face_recog_resize
+    faces = [_chw(f) for f in faces]
+    if flip:
+        faces = [torch.flip(f, dims=(-1,)) for f in faces]
+    face_crop = torch.stack([face_recog_resize(faces[int(i)]) for i in face_indices], dim=0)
+    mean, std = torch.tensor(IMAGENET_MEAN).view(3, 1, 1), torch.tensor(IMAGENET_STD).view(3, 1, 1)
+    lower = [(_resize_u8(f[:, f.shape[1] // 2:, :], (size, size)).float() / 255.0 - mean) / std for f in faces]
+    return (torch.stack(lower, dim=0) if lower else torch.zeros(0, 3, size, size)), face_crop
+
+
+class PackedFaces:
+    """B items of aligned faces packed back to back in one host buffer, every image interleaved `(H_i,W_i,3)` on a 4-byte boundary.  An item is
+    `(faces, flip, face_indices)`: the clip's faces (uint8 `(3,H_i,W_i)` as the reference holds them, or `(H_i,W_i,3)`), the item's flip decision
+    and its two face indices.  `mouth_jobs` / `face_jobs` are the job tables of `l2s_resize_normalise` (rows `(offset, H, W, y0, x0, h, w, flip,
+    slot)`): the lower half `[H // 2, H)` of face t of item b to mouth slot `(b, t)`, the whole of face `face_indices[k]` to face slot `(b, k)`."""
+
+    def __init__(self, items: Sequence, pin: bool = True):
+        assert len(items) > 0, "at least one item"
+        self.frames: List[int] = []
+        self.images: List[Tuple[int, int, int]] = []       # (offset, H, W) of every image, in item order
+        self.flips: List[int] = []
+        self.face_jobs: List[Tuple[int, ...]] = []
+        self._slots: List[Tuple[int, int]] = []            # (b, t) of every image
+        chw, total = [], 0
+        for b, (faces, flip, face_indices) in enumerate(items):
+            first = len(self.images)
+            self.frames.append(len(faces))
+            self.flips.append(int(bool(flip)))
+            for t, f in enumerate(faces):
+                f = _chw(f)
+                H, W = int(f.shape[1]), int(f.shape[2])
+                assert 1 <= H <= 4096 and 1 <= W <= 4096, "a face is at most 4096 x 4096"
+                chw.append(f)
+                self.images.append((total, H, W))
+                self._slots.append((b, t))
+                total += (H * W * 3 + 3) // 4 * 4
+            assert len(face_indices) == 2 and all(0 <= int(i) < len(faces) for i in face_indices), "two face indices inside the clip"
+            for k, i in enumerate(face_indices):
+                o, H, W = self.images[first + int(i)]
+                self.face_jobs.append((o, H, W, 0, 0, H, W, self.flips[b], 2 * b + k))
+        buf = torch.zeros(total, dtype=torch.uint8)        # the alignment gaps are zeros
+        if pin and torch.cuda.is_available():
+            buf = buf.pin_memory()
+        for f, (o, H, W) in zip(chw, self.images):
+            buf[o:o + H * W * 3] = f.permute(1, 2, 0).reshape(-1)
+        self.data = buf
+
+    @property
+    def lengths(self) -> torch.Tensor:
+        return torch.tensor(self.frames)
+
+    def mouth_jobs(self, T: int = None) -> List[Tuple[int, ...]]:
+        """the lower half of every face -> slot `b * T + t` (T defaults to the longest clip)"""
+        T = max(max(self.frames), 1) if T is None else int(T)
+        return [(o, H, W, H // 2, 0, H - H // 2, W, self.flips[b], b * T + t) for (o, H, W), (b, t) in zip(self.images, self._slots)]
+
+    def to_device(self, device="cuda", T: int = None, size: int = 96):
+        """-> `(video (B,3,T,size,size), face_crops (B,2,3,160,160))` fp32 on the device from ONE host-to-device copy and two calls; clips shorter
+        than T (default: the longest clip) are zero-padded."""
+        dev = self.data.to(device, non_blocking=True)
+        B = len(self.frames)
+        T = max(max(self.frames), 1) if T is None else int(T)
+        video = native.resize_normalise(dev, self.mouth_jobs(T), native.RESIZE_MOUTH, B, T, size)
+        return video, native.resize_normalise(dev, self.face_jobs, native.RESIZE_FACE, B)
+
+
+def device_collate_fn_pad_faces(batch):
+    """`device_collate_fn_pad_raw` for loaders whose items carry aligned faces of their own sizes: an item is
+    `((faces, flip, face_indices), speech, melspec, _[, path])` and the tuple is `((packed_faces, lengths), packed_audio, packed_audio,
+    packed_faces[, paths])` - ONE `PackedFaces` in the video and face positions; `packed_faces.to_device()` returns both,
+    `(video, face_crops)`."""
+    with_paths = len(batch[0]) == 5
+    faces = PackedFaces([b[0] for b in batch])
+    audio = PackedAudio([b[1] for b in batch])
+    out = ((faces, faces.lengths), audio, audio, faces)
+    return out + (tuple(b[4] for b in batch),) if with_paths else out
 
 
 def device_collate_fn_pad_raw(batch):

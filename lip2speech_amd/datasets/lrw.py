@@ -49,14 +49,17 @@ def face_recog_resize(frame_u8: torch.Tensor) -> torch.Tensor:
 
 
 class LRW(Dataset):
-    def __init__(self, rootpth, face_size=(96, 96), mode="train", demo=False, duration=1, face_augmentation=None, *args, raw_frames=False, raw_audio=False, **kwargs):
+    def __init__(self, rootpth, face_size=(96, 96), mode="train", demo=False, duration=1, face_augmentation=None, *args, raw_frames=False, raw_audio=False, raw_faces=False,
+                 **kwargs):
         """`raw_frames=True` (an extension): items carry the decoded uint8 clip `(T,H,W,3)` instead of the normalised fp32 one - the
         normalisation then runs on the device (`datasets.device.device_collate_fn_pad` + `PackedFrames.to_device`).  `raw_audio=True` (likewise):
         the CPU mel transform is skipped and the items' melspec slot is `None` - the targets then come from the device
-        (`datasets.device.device_collate_fn_pad_raw` + `PackedAudio.to_device`).  Extra positional / keyword arguments are accepted and ignored
+        (`datasets.device.device_collate_fn_pad_raw` + `PackedAudio.to_device`).  `raw_faces=True` (likewise): the item's face slot carries the two
+        drawn face frames as they were decoded, uint8 `(2,3,H,W)`, instead of the resized fp32 `face_crop` - the 160 x 160 resize then runs on the
+        device (`datasets.device.PackedFaces`, `l2s_resize_normalise`); without a face file the slot is the usual zeros.  Extra positional / keyword arguments are accepted and ignored
         (the reference forwards them to `Dataset.__init__`, which takes none)."""
         super().__init__()
-        self.raw_frames, self.raw_audio = raw_frames, raw_audio
+        self.raw_frames, self.raw_audio, self.raw_faces = raw_frames, raw_audio, raw_faces
         assert mode in ("train", "test", "val")
         self.rootpth, self.mode, self.demo = rootpth, mode, demo
         self.face_size, self.duration = face_size, duration
@@ -88,7 +91,8 @@ class LRW(Dataset):
         face_crop = torch.zeros(2, 3, 160, 160)
         if os.path.exists(face_path):
             faces = torch.from_numpy(np.ascontiguousarray(load_frames(face_path))).permute(0, 3, 1, 2)
-            face_crop = torch.stack([face_recog_resize(faces[int(i)]) for i in (draw * len(faces)).int()], dim=0)
+            drawn = [faces[int(i)] for i in (draw * len(faces)).int()]
+            face_crop = torch.stack(drawn if self.raw_faces else [face_recog_resize(f) for f in drawn], dim=0)
         if self.demo:
             return mouth, speech, melspec, face_crop, (face_path, audio_path)
         return mouth, speech, melspec, face_crop

@@ -30,6 +30,7 @@ ABI_SYMBOLS = (
     "l2s_model_create", "l2s_model_set_tensor", "l2s_model_finalize", "l2s_model_destroy",
     "l2s_min_T", "l2s_workspace_bytes", "l2s_state_floats", "l2s_state_offset",
     "l2s_mel_frames", "l2s_mel_targets_workspace_bytes", "l2s_mel_targets",
+    "l2s_resize_check", "l2s_resize_normalise",
     "l2s_encoder_fwd", "l2s_normalise_pad_frames", "l2s_build_visual", "l2s_decoder_prologue", "l2s_decode_steps", "l2s_postnet",
     "l2s_workspace_bytes_masked", "l2s_masked_bilstm_plan", "l2s_inference_masked", "l2s_forward_eval_masked", "l2s_decoder_prologue_masked", "l2s_decode_steps_masked",
     "l2s_ragged_plan", "l2s_workspace_bytes_ragged", "l2s_inference_ragged",
@@ -63,6 +64,15 @@ _lib = None
 _diag = None
 _process_defaults: Dict[str, int] = {}
 _vp, _i, _i64, _fp = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_void_p
+
+
+class ResizeJob(ctypes.Structure):
+    """`l2s_resize_job` (include/l2s.h): an image of the packed buffer, a source rectangle inside it, a flip bit and an output slot"""
+    _fields_ = [("offset", _i64)] + [(k, ctypes.c_int32) for k in ("H", "W", "y0", "x0", "h", "w", "flip", "slot")]
+
+
+RESIZE_MOUTH, RESIZE_FACE = 0, 1          # L2S_RESIZE_MOUTH / L2S_RESIZE_FACE
+RESIZE_JOBS_PER_LAUNCH = 240              # L2S_RESIZE_JOBS_PER_LAUNCH: output slots whose table one launch carries in its kernel arguments
 
 
 def _load(path: str) -> ctypes.CDLL:
@@ -220,6 +230,11 @@ def _bind(L: ctypes.CDLL) -> None:
         L.l2s_mel_targets_workspace_bytes.restype = _i64
         L.l2s_mel_targets.argtypes = [_fp, ctypes.POINTER(_i64), ctypes.POINTER(_i64), _i, _fp, _i, _i, _i, _i, _i, ctypes.c_float, _i, _i64, _fp, _fp, _fp, _vp,
                                       _vp, _i64, _vp]
+    # device-side face crops (include/l2s.h): likewise absent from a library built before them (tools/frame_resize/time_frame_resize.py times one next to this build)
+    if hasattr(L, "l2s_resize_normalise"):
+        _jobs = ctypes.POINTER(ResizeJob)
+        L.l2s_resize_check.argtypes = [_jobs, _i, _i64, _i, _i, _i, _i, _i]
+        L.l2s_resize_normalise.argtypes = [_vp, _i64, _jobs, _i, _i, _i, _i, _i, _i, _fp, _vp]
     # the voice tower over clips of unequal length (include/l2s.h): likewise absent from a library built before it
     # (tools/speaker_packed/time_speaker_packed.py times one next to this build)
     if hasattr(L, "l2s_speaker_encoder_packed"):
@@ -1044,6 +1059,41 @@ def normalise_pad_frames(packed_u8: torch.Tensor, offsets, frames, H: int = 96, 
     fr = (ctypes.c_int32 * B)(*[int(f) for f in frames])
     check(lib().l2s_normalise_pad_frames(packed_u8.data_ptr(), off, fr, B, T, H, W, _ptr(video), _stream()))
     return video
+
+
+_RESIZE_JOB_DTYPE = np.dtype([("offset", "<i8")] + [(k, "<i4") for k in ("H", "W", "y0", "x0", "h", "w", "flip", "slot")])
+
+
+def _resize_jobs(jobs):
+    """rows `(offset, H, W, y0, x0, h, w, flip, slot)` -> a pointer to as many `ResizeJob` (numpy holds the memory: the pointer keeps it alive)"""
+    rows = np.asarray(jobs, dtype=np.int64).reshape(-1, 9)
+    assert rows.size == 0 or (int(np.abs(rows[:, 1:]).max()) < 2 ** 31), "a job field other than the offset is a 32-bit integer"
+    arr = np.zeros(max(len(rows), 1), dtype=_RESIZE_JOB_DTYPE)
+    for k, name in enumerate(_RESIZE_JOB_DTYPE.names):
+        arr[name][:len(rows)] = rows[:, k]
+    ptr = arr.ctypes.data_as(ctypes.POINTER(ResizeJob))
+    ptr._rows = arr
+    return ptr
+
+
+def resize_check(jobs, packed_bytes: int, mode: int, B: int, T: int, size: int) -> None:
+    """`l2s_resize_check`: the pure host check of a job table (no device needed); raises with the job and the limit it breaks."""
+    check(lib().l2s_resize_check(_resize_jobs(jobs), len(jobs), int(packed_bytes), int(mode), int(B), int(T), int(size), int(size)))
+
+
+def resize_normalise(packed_u8: torch.Tensor, jobs, mode: int, B: int, T: int = 2, size: Optional[int] = None) -> torch.Tensor:
+    """`l2s_resize_normalise`: uint8 RGB images `(H_i,W_i,3)` of any size packed back to back on the device (each on a 4-byte boundary) ->
+    `mode = RESIZE_MOUTH`: the model's `(B,3,T,size,size)` input, size 96 (default) or 88, slot `b * T + t`, `/255` and ImageNet mean / std;
+    `mode = RESIZE_FACE`: the face tower's `(B,2,3,160,160)` input, slot `2 * b + k`, `(x - 127.5) / 128`.  `jobs`: rows
+    `(offset, H, W, y0, x0, h, w, flip, slot)` - image, source rectangle, mirror bit, output slot; slots that no job names come back as zeros."""
+    assert packed_u8.is_cuda and packed_u8.dtype == torch.uint8 and packed_u8.is_contiguous() and packed_u8.dim() == 1
+    face = int(mode) == RESIZE_FACE
+    size = (160 if face else 96) if size is None else int(size)
+    T = 2 if face else int(T)
+    resize_check(jobs, packed_u8.numel(), mode, B, T, size)       # before the output is allocated: its shape comes from the arguments under check
+    out = torch.empty((B, 2, 3, size, size) if face else (B, 3, T, size, size), dtype=torch.float32, device=packed_u8.device)
+    check(lib().l2s_resize_normalise(packed_u8.data_ptr(), packed_u8.numel(), _resize_jobs(jobs), len(jobs), int(mode), int(B), T, size, size, _ptr(out), _stream()))
+    return out
 
 
 MEL_PAD = -11.5129      # ln(1e-5) as the collates write it (datasets.MEL_PAD)
