@@ -140,6 +140,31 @@ int l2s_op_stamp_log(void* log_dev, int64_t capacity);
  * and the error text where the launch would be refused.  Launches nothing and needs no device. */
 int l2s_op_skinny_form(l2s_model* m, int count, const int* groups, int B, int chains, int stamped_skinny, int stamped_flat, char* out, int cap);
 
+/* One batch-row launch on its own: the operator-level entry of launch_skinny (tests/test_skinny_op_gpu.py; lip2speech_amd/native.py op_skinny packs plain
+ * tensors into these layouts).  A group is described as for l2s_op_skinny_form - nchunks[4], ntiles, epi; "W3 set" = planes != NULL, "a_sum set" =
+ * a_sum != NULL - plus what the launch reads and writes, all device pointers, with the meaning of the SkinnyP field of the same name (l2s_common.h):
+ *   seg_a[j]   frag16 [pad16(B)][16 * nchunks[j]] activations of K segment j (ignored where nchunks[j] == 0); a_sum like seg_a[1] or NULL
+ *   W          frag16 [16 * ntiles][K] weight, K = 16 * sum(nchunks); bias [16 * ntiles] or NULL (SK_LSTM: both in the packed row order 4 * unit + gate)
+ *   planes     NULL, or a buffer of ntiles * K * 16 * 6 bytes: the call derives the bf16 planes of W into it (launch_skx_planes, K % 256 == 0) on `stream`
+ *              and hands them to the launch as SkinnyP::W3
+ *   actw [N], add plain [B][ld_add], addrow [N] (each may be NULL); out plain [B][ldo] (SK_PLAIN) or frag16 with K = ldo (SK_FRAG)
+ *   SK_LSTM:   pre plain [B][ld_pre] in gate-major order gate * H + unit (or NULL), c_in / c_out frag16 (K = H), h_out frag16 (K = h_out_K) at column
+ *              h_out_off, h_seq plain [B][ld_hseq] and h_plain plain [B][ld_hplain] (each may be NULL)
+ *   SK_MEL:    mel plain [B][ld_mel_b], stop plain [B][ld_stop_b], stop_const [B], yfrag frag16 (K = 80) or NULL
+ * The struct holds its pointers first, then the 64-bit and the 32-bit integers, so that it has no padding. */
+typedef struct l2s_skinny_group {
+    const float* seg_a[4]; const float* a_sum; const float* W; void* planes; const float* bias; const float* actw; const float* add; const float* addrow;
+    float* out; const float* pre; const float* c_in; float* c_out; float* h_out; float* h_seq; float* h_plain;
+    float* mel; float* stop; const float* stop_const; float* yfrag;
+    int64_t ld_pre, ld_hseq, ld_mel_b, ld_stop_b;
+    int32_t nchunks[4], ntiles, epi, N, act, ldo, ld_add, H, h_out_K, h_out_off, ld_hplain;
+} l2s_skinny_group;
+/* B rows, `count` groups (1 - 4), the options of model m (it need not be finalised), the launch chains of l2s_set_thread_chains.  es_end != NULL: the
+ * early-stop twin of the kernel, which returns at its top when es_step >= *es_end (a device int); the stop bookkeeping (SkinnyP::es_ctl) stays off.
+ * The batch goes through launch_skinny - its validation, the form rule and the dispatch table of every product launch.  A refused launch returns
+ * non-zero with the text in l2s_last_error (the text l2s_op_skinny_form answers after "ERROR "). */
+int l2s_op_skinny(l2s_model* m, int count, const l2s_skinny_group* groups, int B, const int* es_end, int es_step, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1942,6 +1942,35 @@ int l2s_op_skinny_form(l2s_model* m, int count, const int* groups, int B, int ch
     return 0;
 }
 
+// one batch-row launch described by the caller (include/l2s_diag.h l2s_skinny_group): the batch is filled field by field and handed to launch_skinny
+int l2s_op_skinny(l2s_model* m, int count, const l2s_skinny_group* groups, int B, const int* es_end, int es_step, void* stream) {
+    L2S_REQUIRE(m && groups && count >= 1 && count <= SKINNY_MAX_GROUP && B >= 1, "bad arguments");
+    hipStream_t s = (hipStream_t)stream;
+    SkinnyBatch sb{};
+    for (int i = 0; i < count; ++i) {
+        const l2s_skinny_group& g = groups[i];
+        SkinnyP& p = sb.p[i];
+        for (int j = 0; j < 4; ++j) {
+            L2S_REQUIRE(g.nchunks[j] >= 0 && (g.nchunks[j] == 0 || g.seg_a[j]), "skinny op: a K segment without activations");
+            p.seg[j] = {g.seg_a[j], g.nchunks[j]}; p.K += 16 * g.nchunks[j];
+            if (g.nchunks[j]) p.nseg = j + 1;
+        }
+        L2S_REQUIRE(g.W && g.ntiles >= 1 && g.N >= 1 && g.N <= 16 * g.ntiles, "skinny op: weight / output columns");
+        p.a_sum = g.a_sum; p.W = g.W; p.bias = g.bias; p.actw = g.actw; p.add = g.add; p.ld_add = g.ld_add; p.addrow = g.addrow;
+        p.out = g.out; p.ldo = g.ldo; p.B = B; p.N = g.N; p.act = g.act; p.epi = g.epi;
+        p.pre = g.pre; p.ld_pre = g.ld_pre; p.c_in = g.c_in; p.c_out = g.c_out; p.h_out = g.h_out; p.h_out_K = g.h_out_K; p.h_out_off = g.h_out_off;
+        p.h_seq = g.h_seq; p.ld_hseq = g.ld_hseq; p.h_plain = g.h_plain; p.ld_hplain = g.ld_hplain; p.H = g.H;
+        p.mel = g.mel; p.ld_mel_b = g.ld_mel_b; p.stop = g.stop; p.ld_stop_b = g.ld_stop_b; p.stop_const = g.stop_const; p.yfrag = g.yfrag;
+        if (g.planes) {
+            if (launch_skx_planes(g.W, g.ntiles, p.K, g.planes, s)) return 1;
+            p.W3 = g.planes;
+        }
+        sb.ntiles[i] = g.ntiles;
+    }
+    sb.count = count; sb.es_end = es_end; sb.es_step = es_step;
+    return launch_skinny(sb, s, "op_skinny", m->opt);
+}
+
 int l2s_op_launch_chain(int kind, int n_launches, int blocks, int n_per_block, const float* in, float* out, void* stream) {
     for (int i = 0; i < n_launches; ++i)
         if (launch_probe(kind, blocks, n_per_block, in, out, (hipStream_t)stream)) return 1;

@@ -50,7 +50,7 @@ ABI_SYMBOLS = (
 )
 # what include/l2s_diag.h adds: exported by libl2s_diag.so only
 DIAG_SYMBOLS = (
-    "l2s_op_gemm", "l2s_op_conv1d", "l2s_op_gemm_ex", "l2s_op_conv1d_ex", "l2s_op_conv1d_bwd", "l2s_op_frontend", "l2s_op_launch_chain", "l2s_op_launch_chain2", "l2s_op_skinny_timeline", "l2s_op_attn_timeline", "l2s_op_flat_timeline", "l2s_op_pdecode_timeline", "l2s_op_gemm_x3_timeline", "l2s_op_fused_unit_timeline", "l2s_op_lstm_cell_chain", "l2s_op_step_attn_chain", "l2s_op_stamp_log", "l2s_op_skinny_form",
+    "l2s_op_gemm", "l2s_op_conv1d", "l2s_op_gemm_ex", "l2s_op_conv1d_ex", "l2s_op_conv1d_bwd", "l2s_op_frontend", "l2s_op_launch_chain", "l2s_op_launch_chain2", "l2s_op_skinny_timeline", "l2s_op_attn_timeline", "l2s_op_flat_timeline", "l2s_op_pdecode_timeline", "l2s_op_gemm_x3_timeline", "l2s_op_fused_unit_timeline", "l2s_op_lstm_cell_chain", "l2s_op_step_attn_chain", "l2s_op_stamp_log", "l2s_op_skinny_form", "l2s_op_skinny",
     "l2s_op_face_conv2d", "l2s_op_face_taps", "l2s_op_speaker_taps", "l2s_op_speaker_taps_packed", "l2s_op_encoder_taps",
 )
 
@@ -71,7 +71,15 @@ class ResizeJob(ctypes.Structure):
     _fields_ = [("offset", _i64)] + [(k, ctypes.c_int32) for k in ("H", "W", "y0", "x0", "h", "w", "flip", "slot")]
 
 
-RESIZE_MOUTH, RESIZE_FACE = 0, 1          # L2S_RESIZE_MOUTH / L2S_RESIZE_FACE
+class SkinnyGroup(ctypes.Structure):
+    """`l2s_skinny_group` (include/l2s_diag.h): one GEMM group of a batch-row launch of `l2s_op_skinny` - pointers, then 64-bit, then 32-bit integers"""
+    _fields_ = ([("seg_a", _vp * 4)] + [(k, _vp) for k in ("a_sum", "W", "planes", "bias", "actw", "add", "addrow", "out", "pre", "c_in", "c_out", "h_out", "h_seq",
+                                                            "h_plain", "mel", "stop", "stop_const", "yfrag")]
+                + [(k, _i64) for k in ("ld_pre", "ld_hseq", "ld_mel_b", "ld_stop_b")] + [("nchunks", ctypes.c_int32 * 4)]
+                + [(k, ctypes.c_int32) for k in ("ntiles", "epi", "N", "act", "ldo", "ld_add", "H", "h_out_K", "h_out_off", "ld_hplain")])
+
+
+RESIZE_MOUTH, RESIZE_FACE = 0, 1         # L2S_RESIZE_MOUTH / L2S_RESIZE_FACE
 RESIZE_JOBS_PER_LAUNCH = 240              # L2S_RESIZE_JOBS_PER_LAUNCH: output slots whose table one launch carries in its kernel arguments
 
 
@@ -264,6 +272,7 @@ def _bind_diag(L: ctypes.CDLL) -> None:
     L.l2s_op_lstm_cell_chain.argtypes = [_vp, _i, _i, _vp, _i64, _vp, ctypes.POINTER(ctypes.c_double)]
     L.l2s_op_stamp_log.argtypes = [_vp, _i64]
     L.l2s_op_skinny_form.argtypes = [_vp, _i, ctypes.POINTER(ctypes.c_int), _i, _i, _i, _i, ctypes.c_char_p, _i]
+    L.l2s_op_skinny.argtypes = [_vp, _i, ctypes.POINTER(SkinnyGroup), _i, _vp, _i, _vp]
     L.l2s_op_face_conv2d.argtypes = [_fp, _i64, _i, _i, _i, _i, _fp, _fp, _fp, _fp, _i, _fp, _i, _i, _i, _i, _i, _i, _vp]
     L.l2s_op_face_taps.argtypes = [_vp, _fp, _i64, _i, _vp, _fp, _fp, _vp, _i64, _vp]
     L.l2s_op_speaker_taps.argtypes = [_vp, _fp, _i, _i, _vp, _fp, _vp, _i64, _vp]
@@ -1181,6 +1190,147 @@ def op_conv1d(X, Wp, scale=None, shift=None, actw=None, taps=1, stride=1, pad=0,
     _dcheck(diag().l2s_op_conv1d_ex(_ptr(X), _ptr(Wp), _ptr(scale), _ptr(shift), _ptr(actw), _ptr(out), B, Tin, Cin, Cout,
                                  taps, stride, pad, act, (1 if x3 else 0) | (2 if bf16 else 0) | (4 if x3_narrow else 0) | (8 if x3_dma else 0), _stream()))
     return out
+
+
+SK_PLAIN, SK_FRAG, SK_LSTM, SK_MEL = range(4)      # SkinnyEpi (l2s_common.h)
+SKINNY_SENTINEL = -7777.0                          # what op_skinny fills every output buffer with before the launch
+
+
+def frag16_index(row, k, K):
+    """`frag16_index` of l2s_common.h, on ints or integer tensors: where element [row][k] of a row-major [R][K] matrix sits in its frag16 buffer"""
+    return (((row >> 4) * (K >> 4) + (k >> 4)) * 64 + ((k >> 2) & 3) * 16 + (row & 15)) * 4 + (k & 3)
+
+
+def _frag16_map(R: int, K: int, device) -> torch.Tensor:
+    assert K % 16 == 0, "frag16: K is a multiple of 16"
+    return frag16_index(torch.arange(R, device=device).view(-1, 1), torch.arange(K, device=device).view(1, -1), K)
+
+
+def frag16_pack(X: torch.Tensor, rows: Optional[int] = None) -> torch.Tensor:
+    """Row-major X [R][K] -> the flat frag16 buffer of pad16(max(R, rows)) rows; the padded rows are zero"""
+    R, K = X.shape
+    Rp = (max(R, rows or 0) + 15) // 16 * 16
+    out = X.new_zeros(Rp * K)
+    out[_frag16_map(R, K, X.device).reshape(-1)] = X.reshape(-1)
+    return out
+
+
+def frag16_unpack(F: torch.Tensor, R: int, K: int) -> torch.Tensor:
+    """The row-major [R][K] view of a flat frag16 buffer (R may include the padded rows)"""
+    return F[_frag16_map(R, K, F.device)]
+
+
+def lstm_perm_rows(H: int, device=None) -> torch.Tensor:
+    """`lstm_perm_row` of l2s_pack.hip for every packed row: entry np = 4 * unit + gate holds the PyTorch row gate * H + unit"""
+    n = torch.arange(4 * H, device=device)
+    return (n & 3) * H + (n >> 2)
+
+
+def op_skinny_prepare(groups, B: int):
+    """The device-side inputs of `op_skinny` for these groups, packed once (a caller that launches the same batch in several kernel forms passes the
+    result as `prepared`).  Activations and the previous cell go to frag16 with rows padded to 16 (zero), weights to frag16 with their rows - the output
+    columns - zero-padded to 16 * ntiles, SK_LSTM weights and bias permuted from PyTorch's gate * H + unit to 4 * unit + gate."""
+    Bp = (B + 15) // 16 * 16
+    prepared = []
+    for d in groups:
+        W = _f32(d["W"])
+        N, K = W.shape
+        Np = 16 * d["ntiles"]
+        assert N <= Np and len(d["a"]) <= 4 and sum(a.shape[1] for a in d["a"]) == K and all(a.shape[0] == B for a in d["a"])
+        bias = None if d.get("bias") is None else _f32(d["bias"])
+        if d["epi"] == SK_LSTM:
+            assert N == 4 * d["H"] == Np
+            perm = lstm_perm_rows(d["H"], W.device)
+            W, bias = W[perm], (None if bias is None else bias[perm])
+        Wp = W.new_zeros(Np, K)
+        Wp[:N] = W
+        p = {"a": [frag16_pack(_f32(a), Bp) for a in d["a"]], "W": frag16_pack(Wp), "bias": None}
+        if bias is not None:
+            p["bias"] = W.new_zeros(Np)
+            p["bias"][:N] = bias
+        for k in ("actw", "add", "addrow", "pre", "stop_const"):
+            p[k] = None if d.get(k) is None else _f32(d[k])
+        p["a_sum"] = None if d.get("a_sum") is None else frag16_pack(_f32(d["a_sum"]), Bp)
+        p["c_in"] = None if d.get("c_prev") is None else frag16_pack(_f32(d["c_prev"]), Bp)
+        p["planes"] = torch.empty(d["ntiles"] * K * 16 * 6, dtype=torch.uint8, device=W.device) if d.get("planes") else None
+        prepared.append(p)
+    return prepared
+
+
+def op_skinny(model, groups, B: int, es=None, refused: Optional[list] = None, prepared=None):
+    """One batch-row launch through `l2s_op_skinny` (diagnostic library) from plain row-major tensors.  `model`: the handle of a diag model whose options
+    choose the kernel form (the chains come from `set_thread_chains`).  `groups`: one dict per GEMM group -
+      "epi" (SK_*), "ntiles", "a": the K segments as [B][K_j] tensors, "W": [N][K] (SK_LSTM: [4H][K] in PyTorch's gate order i, f, g, o), optional "bias" [N],
+      "a_sum" [B][K_1], "planes" (True: the launch gets the bf16 planes of W), "act" (0 none, 1 ReLU, 2 SiLU, 3 sin(v) * actw), "actw" [N], "add" [B][N],
+      "addrow" [N], "ldo" (row pitch of the output, default N for SK_PLAIN and 16 * ntiles for SK_FRAG);
+      SK_LSTM: "H", "c_prev" [B][H], optional "pre" [B][4H], "h_out_K" / "h_out_off" (default H / 0), "h_seq" / "h_plain" (True: also the plain copies);
+      SK_MEL: "stop_const" [B], "yfrag" (True: also the frag16 copy of the frame).
+    `es` = (end, step): the early-stop twin of the kernel with *es_end = end and es_step = step.
+    Every output buffer is filled with SKINNY_SENTINEL first and returned WHOLE, unpacked to row-major with its padded rows and columns, so that a caller
+    sees unwritten elements and stray writes: per group a dict of "out" [pad16(B)][ldo]; "c_out" [pad16(B)][H], "h_out" [pad16(B)][h_out_K], "h_seq"
+    [pad16(B)][H + 8], "h_plain" [pad16(B)][H + 4]; "mel" [pad16(B)][88], "stop" [pad16(B)][2], "yfrag" [pad16(B)][80].
+    A refused launch raises RuntimeError with the library's text - or, with `refused` a list, appends the text to it and returns the untouched buffers."""
+    D = diag()
+    dev = torch.device("cuda")
+    Bp = (B + 15) // 16 * 16
+    prepared = prepared or op_skinny_prepare(groups, B)
+    arr = (SkinnyGroup * len(groups))()
+    bufs = []
+
+    def fill(*shape):
+        return torch.full(shape, SKINNY_SENTINEL, dtype=torch.float32, device=dev)
+
+    for g, d, p in zip(arr, groups, prepared):
+        N, H = d["W"].shape[0], d.get("H", 0)
+        for j, a in enumerate(p["a"]):
+            g.seg_a[j], g.nchunks[j] = a.data_ptr(), d["a"][j].shape[1] // 16
+        for k in ("a_sum", "W", "planes", "bias", "actw", "add", "addrow", "pre", "c_in", "stop_const"):
+            setattr(g, k, _ptr(p[k]))
+        g.ntiles, g.epi, g.N, g.act, g.H, g.ld_add, g.ld_pre = d["ntiles"], d["epi"], N, d.get("act", 0), H, N, 4 * H
+        b = {}
+        if d["epi"] == SK_PLAIN:
+            g.ldo = d.get("ldo", N)
+            b["out"] = fill(Bp, g.ldo)
+            g.out = b["out"].data_ptr()
+        elif d["epi"] == SK_FRAG:
+            g.ldo = d.get("ldo", 16 * d["ntiles"])
+            b["out"] = fill(Bp * g.ldo)
+            g.out = b["out"].data_ptr()
+        elif d["epi"] == SK_LSTM:
+            g.h_out_K, g.h_out_off = d.get("h_out_K", H), d.get("h_out_off", 0)
+            b["c_out"], b["h_out"] = fill(Bp * H), fill(Bp * g.h_out_K)
+            g.c_out, g.h_out = b["c_out"].data_ptr(), b["h_out"].data_ptr()
+            if d.get("h_seq"):
+                b["h_seq"], g.ld_hseq = fill(Bp, H + 8), H + 8
+                g.h_seq = b["h_seq"].data_ptr()
+            if d.get("h_plain"):
+                b["h_plain"], g.ld_hplain = fill(Bp, H + 4), H + 4
+                g.h_plain = b["h_plain"].data_ptr()
+        else:
+            b["mel"], b["stop"], g.ld_mel_b, g.ld_stop_b = fill(Bp, 88), fill(Bp, 2), 88, 2
+            g.mel, g.stop = b["mel"].data_ptr(), b["stop"].data_ptr()
+            if d.get("yfrag"):
+                b["yfrag"] = fill(Bp * 80)
+                g.yfrag = b["yfrag"].data_ptr()
+        bufs.append(b)
+    es_end = None if es is None else torch.tensor([es[0]], dtype=torch.int32, device=dev)
+    rc = D.l2s_op_skinny(model, len(groups), arr, B, _ptr(es_end), 0 if es is None else es[1], _stream())
+    if rc != 0:
+        text = D.l2s_last_error().decode("utf-8", "replace")
+        if refused is None:
+            raise RuntimeError("libl2s_diag: " + text)
+        refused.append(text)
+    frag_K = {"c_out": lambda g: g.H, "h_out": lambda g: g.h_out_K, "yfrag": lambda g: 80}
+    outs = []
+    for g, d, b in zip(arr, groups, bufs):
+        o = dict(b)
+        if d["epi"] == SK_FRAG:
+            o["out"] = frag16_unpack(b["out"], Bp, g.ldo)
+        for k, K_of in frag_K.items():
+            if k in b:
+                o[k] = frag16_unpack(b[k], Bp, K_of(g))
+        outs.append(o)
+    return outs
 
 
 def op_face_conv2d(x, w, scale, shift, stride=1, pad=(0, 0), res=None, relu=True, nchw=False) -> torch.Tensor:
