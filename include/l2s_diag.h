@@ -140,6 +140,14 @@ int l2s_op_stamp_log(void* log_dev, int64_t capacity);
  * and the error text where the launch would be refused.  Launches nothing and needs no device. */
 int l2s_op_skinny_form(l2s_model* m, int count, const int* groups, int B, int chains, int stamped_skinny, int stamped_flat, char* out, int cap);
 
+/* What the library launches at a call site of launch_skinny, in the integers of l2s_op_skinny_form: the step builders of csrc/decode_step.h - the ones
+ * the decode loop, the training forward, the prologue and the voice tower call - run for B rows on dummy operands, under the options of the finalised
+ * model m with the ones the site stands for laid over them ("fold_step_weights", "hoist_vproj").  site: a key of "sites" in
+ * tests/golden/skinny_forms.json (bilstm_step, phase_a_unfolded, phase_a_folded_step0, phase_a_folded, step_attention_proj, phase_d_k1536,
+ * phase_d_k1280, phase_d_k1024_sum, phase_d_k1024_unfolded, phase_e, step_fc_out_stop, spk_lstm_step).  Writes *count groups (at most 4) of 8 ints
+ * into groups[32].  Launches nothing (tests/test_step_sites_gpu.py). */
+int l2s_op_step_site(l2s_model* m, const char* site, int B, int* groups, int* count);
+
 /* One batch-row launch on its own: the operator-level entry of launch_skinny (tests/test_skinny_op_gpu.py; lip2speech_amd/native.py op_skinny packs plain
  * tensors into these layouts).  A group is described as for l2s_op_skinny_form - nchunks[4], ntiles, epi; "W3 set" = planes != NULL, "a_sum set" =
  * a_sum != NULL - plus what the launch reads and writes, all device pointers, with the meaning of the SkinnyP field of the same name (l2s_common.h):

@@ -8,6 +8,7 @@
 #include "l2s_common.h"
 #include "l2s_model.h"
 #include "pdecode.h"
+#include "decode_step.h"
 
 #include <algorithm>
 #include <cmath>
@@ -336,14 +337,6 @@ static GemmP conv_gemm(const float* X, int lda, int B, int Tin, int Cin, const C
     return p;
 }
 
-static SkinnyP sk_base(const SkW& sw, int B) {
-    SkinnyP p{};
-    p.W = sw.W; p.W3 = sw.W3; p.bias = sw.bias; p.actw = sw.actw;
-    p.B = B; p.N = sw.N; p.K = sw.K;
-    p.act = ACT_NONE; p.epi = SK_PLAIN;
-    return p;
-}
-
 // ---- per-clip video lengths (the *_masked entry points, include/l2s.h)
 static int check_lengths(const int32_t* video_lengths, int B, int T) {
     L2S_REQUIRE(video_lengths, "video_lengths is null");
@@ -462,17 +455,7 @@ static int prologue_run(l2s_model* m, const float* vis, const float* emb, const 
             ++rst_i;
             if (launch_bilstm_reset(hf[1][cur], cf[1], lens.dev, B, T - 1 - step, s_e, s)) return 1;
         }
-        for (int d = 0; d < 2; ++d) {
-            const int t = d == 0 ? step : T - 1 - step;
-            SkinnyP p = sk_base(w.whh[d], B);
-            p.seg[0] = {hf[d][cur], 32}; p.nseg = 1;
-            p.epi = SK_LSTM; p.H = 512;
-            p.pre = gin + (int64_t)t * 4096 + d * 2048; p.ld_pre = (int64_t)T * 4096;
-            p.c_in = cf[d]; p.c_out = cf[d];
-            p.h_out = hf[d][nxt]; p.h_out_K = 512; p.h_out_off = 0;
-            p.h_seq = rnn + (int64_t)t * 1024 + d * 512; p.ld_hseq = (int64_t)T * 1024;
-            sb.p[d] = p; sb.ntiles[d] = w.whh[d].tiles;
-        }
+        for (int d = 0; d < 2; ++d) bilstm_step_group(sb, d, w, true, B, T, d == 0 ? step : T - 1 - step, hf[d][cur], hf[d][nxt], cf[d], gin, rnn);
         sb.count = 2;
         if (launch_skinny(sb, s, "bilstm_step", m->opt)) return 1;
         if (cap_i < cap_steps.size() && cap_steps[cap_i] == step) {      // forward rows whose clip ended at frame `step`: their finals, now
@@ -586,10 +569,7 @@ static int prologue_run(l2s_model* m, const float* vis, const float* emb, const 
 // 12.0 ms: the GEMM blocks delay the latency-critical step launches); "use_graph" - replay the loop from a captured hipGraph (measured slower
 // than stream launches on MI355X: 15.0 vs 13.7 ms)
 
-struct DecodeBufs {
-    float *h0[2], *h1[2], *c0, *c1, *av, *p1, *cc, *uu, *yf, *p2f, *q, *qc, *p2;
-};
-
+// The launches of one step - groups, K segments, epilogues, tile counts - are built in decode_step.h; this loop overlays the early-stop control fields.
 // on_frames(n): called (if set) right after the launch that completes mel frames [0, n) has been enqueued on `s`
 static int decode_launches(l2s_model* m, float* state, int B, int T, int S, const float* teacher, const uint8_t* teacher_mask,
                            float* mel, float* stop, float* attn, int attn_logits, void* ws, int64_t ws_bytes, hipStream_t s, bool fold,
@@ -597,16 +577,9 @@ static int decode_launches(l2s_model* m, float* state, int B, int T, int S, cons
     const Weights& w = m->w;
     StateLayout sl = state_layout(B, T);
     const int Bp = pad16(B);
-    const bool vhoist = fold && m->opt.hoist_vproj && w.lstm0v.W && w.vproj.W;      // attention_proj applied to the values in the prologue (option "hoist_vproj")
-    const bool vsum = vhoist && m->opt.hoist_vproj >= 2 && skinny_sum_supported(m->opt);     // ... and u = prenet + o formed by LSTM0's operand loader (K = 1024)
+    const StepForm form = step_form(w, m->opt, fold);
     Bump bp(ws, ws_bytes);
-    DecodeBufs d;
-    for (int i = 0; i < 2; ++i) d.h0[i] = bp.f((int64_t)Bp * 512);
-    for (int i = 0; i < 2; ++i) d.h1[i] = bp.f((int64_t)Bp * 512);
-    d.c0 = bp.f((int64_t)Bp * 512); d.c1 = bp.f((int64_t)Bp * 512); d.av = bp.f((int64_t)Bp * 512);
-    d.p1 = bp.f((int64_t)Bp * 256); d.cc = bp.f((int64_t)Bp * 256); d.uu = bp.f((int64_t)Bp * 256); d.p2f = bp.f((int64_t)Bp * 256);
-    d.yf = bp.f((int64_t)Bp * 96);
-    d.q = bp.f((int64_t)B * 512); d.qc = bp.f((int64_t)B * 256); d.p2 = bp.f((int64_t)B * 256);
+    const StepBufs d = step_carve(bp, B);
     // option "early_stop" (free-running loops only): this call's control block, armed on the stream - chains in flight on other streams have their own
     EsCtl* const es = early ? reinterpret_cast<EsCtl*>(bp.f(B + 2)) : nullptr;
     L2S_REQUIRE(!bp.overflow, "decode workspace too small");
@@ -624,88 +597,51 @@ static int decode_launches(l2s_model* m, float* state, int B, int T, int S, cons
     for (float* z : zero256) if (launch_fill(z, (int64_t)Bp * 256, 0.f, s)) return 1;
     if (launch_to_frag(w.bos, 0, B, 80, d.yf, 80, 0, 1, s)) return 1;
 
-    auto fc_group = [&](int step, const float* h1buf, bool write_y) {
-        SkinnyP a = sk_base(w.fc, B);
-        a.seg[0] = {h1buf, 32}; a.nseg = 1; a.epi = SK_MEL;
-        a.mel = mel + (int64_t)step * NM; a.ld_mel_b = (int64_t)S * NM;
-        a.stop = stop + step; a.ld_stop_b = S; a.stop_const = state + sl.stopc; a.yfrag = write_y ? d.yf : nullptr;
+    const StepOut out{mel, stop, state + sl.stopc, S};
+    // early stop: every launch carries the step it belongs to; the fc / stop group that finishes step `step` keeps the stop bookkeeping
+    auto es_launch = [&](SkinnyBatch& sb, int step) { sb.es_end = es_end; sb.es_step = step - S; };
+    auto es_fc = [&](SkinnyP& a, int step) {
         if (es) { a.es_ctl = reinterpret_cast<int*>(es); a.es_end = std::min(S, step + 1 + ES_MARGIN) - S; }
-        return a;
     };
 
     for (int i = 0; i < S; ++i) {
-        const int cur = i & 1, nxt = cur ^ 1;
         const bool forced = teacher && teacher_mask && teacher_mask[i];
         if (forced)
             if (launch_to_frag(teacher + (int64_t)i * NM, S * NM, B, 80, d.yf, 80, 0, 0, s)) return 1;
         {   // phase A: prenet layer 1, Q (+PSine +pos[i]), content Q (+SiLU) [, mel frame + stop logit of step i-1]
-            SkinnyBatch sb{};
-            const bool from_frame = !fold || i == 0 || forced;      // prenet input is an explicit frame (BOS / teacher / unfolded y)
-            SkinnyP a = sk_base(from_frame ? w.pre1 : w.pre1f, B);
-            if (from_frame) a.seg[0] = {d.yf, 5}; else a.seg[0] = {d.h1[cur], 32};
-            a.nseg = 1; a.act = ACT_PSINE; a.epi = SK_FRAG; a.out = d.p1; a.ldo = 256;
-            SkinnyP b = sk_base(w.q, B);
-            b.seg[0] = {d.h0[cur], 32}; b.seg[1] = {d.h1[cur], 32}; b.nseg = 2; b.act = ACT_PSINE; b.epi = SK_PLAIN; b.out = d.q; b.ldo = 512;
-            b.addrow = w.pos + (int64_t)i * 512;
-            SkinnyP c = sk_base(w.cq, B);
-            c.seg[0] = {d.c0, 32}; c.seg[1] = {d.c1, 32}; c.nseg = 2; c.act = ACT_SILU; c.epi = SK_PLAIN; c.out = d.qc; c.ldo = 256;
-            sb.p[0] = a; sb.ntiles[0] = 16;
-            sb.p[1] = b; sb.ntiles[1] = w.q.tiles;
-            sb.p[2] = c; sb.ntiles[2] = w.cq.tiles;
-            sb.count = 3;
-            if (fold && i > 0) { sb.p[3] = fc_group(i - 1, d.h1[cur], false); sb.ntiles[3] = w.fc.tiles; sb.count = 4; }
+            SkinnyBatch sb = step_phase_a(form, w, d, B, i, step_from_frame(form, i, forced), out);
+            const bool rides = sb.count == 4;
+            if (rides) es_fc(sb.p[3], i - 1);
             // the folded launch also finishes step i - 1 (its mel frame and stop logit): it is skipped as part of THAT step, i.e. one step later
-            sb.es_end = es_end; sb.es_step = (fold && i > 0 ? i - 1 : i) - S;
+            es_launch(sb, rides ? i - 1 : i);
             if (launch_skinny(sb, s, fold ? "step_prenet1_q_cq_fc" : "step_prenet1_q_cq", m->opt)) return 1;
-            if (fold && i > 0 && on_frames && (*on_frames)(i)) return 1;
+            if (rides && on_frames && (*on_frames)(i)) return 1;
         }
         {   // phase B: attention + content attention per batch row; prenet layer 2
-            AttnP at{};
-            at.q = d.q; at.ldq = 512; at.k = state + sl.k; at.v = state + sl.v; at.tau = w.tau; at.av_frag = d.av;
-            if (fold && vhoist) at.vp = state + sl.vp;      // d.av then holds o = a @ V' (frag16, K = 256)
-            at.attn_out = attn ? attn + (int64_t)i * T : nullptr; at.ld_attn_b = (int64_t)S * T; at.attn_logits = attn_logits;
-            at.qc = d.qc; at.ldqc = 256; at.ckey = state + sl.ckey; at.cval = state + sl.cval; at.tau_c = w.tau_c; at.cc_frag = d.cc;
-            at.B = B; at.T = T; at.m = sl.m;
-            at.es_end = es_end; at.es_step = i - S;
-            SkinnyP pr = sk_base(w.pre2, B);
-            pr.seg[0] = {d.p1, 16}; pr.nseg = 1; pr.act = ACT_PSINE;
-            if (fold) { pr.epi = SK_FRAG; pr.out = d.p2f; pr.ldo = 256; }
-            else { pr.epi = SK_PLAIN; pr.out = d.p2; pr.ldo = 256; }
-            if (lens ? launch_step_attn_masked(at, pr, w.pre2.tiles, lens.dev, s, m->opt.attn_lds, m->opt.attn_skip0)
-                     : launch_step_attn(at, pr, w.pre2.tiles, s, m->opt.attn_lds, m->opt.attn_skip0)) return 1;
+            StepAttn b = step_phase_b(form, w, d, state, sl, B, T, i, S, attn, attn_logits);
+            b.at.es_end = es_end; b.at.es_step = i - S;
+            if (lens ? launch_step_attn_masked(b.at, b.pre2, b.pre2_tiles, lens.dev, s, m->opt.attn_lds, m->opt.attn_skip0)
+                     : launch_step_attn(b.at, b.pre2, b.pre2_tiles, s, m->opt.attn_lds, m->opt.attn_skip0)) return 1;
         }
         if (!fold) {   // phase C: u = prenet + attention_proj(a @ v)
-            SkinnyBatch sb{};
-            SkinnyP a = sk_base(w.aproj, B);
-            a.seg[0] = {d.av, 32}; a.nseg = 1; a.epi = SK_FRAG; a.out = d.uu; a.ldo = 256; a.add = d.p2; a.ld_add = 256;
-            sb.p[0] = a; sb.ntiles[0] = w.aproj.tiles; sb.count = 1;
-            sb.es_end = es_end; sb.es_step = i - S;
+            SkinnyBatch sb = step_phase_c(form, w, d, B);
+            es_launch(sb, i);
             if (launch_skinny(sb, s, "step_attention_proj", m->opt)) return 1;
         }
         {   // phase D: LSTM layer 0 on cat(content, u), h0  (folded: cat(content, prenet, a@v) against [W_ih | W_ih_u W_ap | W_hh])
-            SkinnyBatch sb{};
-            SkinnyP a = sk_base(fold ? (vsum ? w.lstm0 : vhoist ? w.lstm0v : w.lstm0f) : w.lstm0, B);
-            if (vsum) { a.seg[0] = {d.cc, 16}; a.seg[1] = {d.p2f, 16}; a.a_sum = d.av; a.seg[2] = {d.h0[cur], 32}; a.nseg = 3; }      // u = prenet + o, summed by the loader
-            else if (fold) { a.seg[0] = {d.cc, 16}; a.seg[1] = {d.p2f, 16}; a.seg[2] = {d.av, vhoist ? 16 : 32}; a.seg[3] = {d.h0[cur], 32}; a.nseg = 4; }
-            else { a.seg[0] = {d.cc, 16}; a.seg[1] = {d.uu, 16}; a.seg[2] = {d.h0[cur], 32}; a.nseg = 3; }
-            a.epi = SK_LSTM; a.H = 512; a.c_in = d.c0; a.c_out = d.c0; a.h_out = d.h0[nxt]; a.h_out_K = 512; a.h_out_off = 0;
-            sb.p[0] = a; sb.ntiles[0] = 128; sb.count = 1;
-            sb.es_end = es_end; sb.es_step = i - S;
+            SkinnyBatch sb = step_phase_d(form, w, d, B, i);
+            es_launch(sb, i);
             if (launch_skinny(sb, s, "step_lstm_cell", m->opt)) return 1;
         }
         {   // phase E: LSTM layer 1 on the new h0
-            SkinnyBatch sb{};
-            SkinnyP a = sk_base(w.lstm1, B);
-            a.seg[0] = {d.h0[nxt], 32}; a.seg[1] = {d.h1[cur], 32}; a.nseg = 2;
-            a.epi = SK_LSTM; a.H = 512; a.c_in = d.c1; a.c_out = d.c1; a.h_out = d.h1[nxt]; a.h_out_K = 512; a.h_out_off = 0;
-            sb.p[0] = a; sb.ntiles[0] = w.lstm1.tiles; sb.count = 1;
-            sb.es_end = es_end; sb.es_step = i - S;
+            SkinnyBatch sb = step_phase_e(form, w, d, B, i);
+            es_launch(sb, i);
             if (launch_skinny(sb, s, "step_lstm_cell", m->opt)) return 1;
         }
-        if (!fold || i == S - 1) {   // phase F: mel frame + stop logit (folded mode: only the last step needs its own launch)
-            SkinnyBatch sb{};
-            sb.p[0] = fc_group(i, d.h1[nxt], !fold); sb.ntiles[0] = w.fc.tiles; sb.count = 1;
-            sb.es_end = es_end; sb.es_step = i - S;
+        if (step_has_phase_f(form, i, S)) {   // phase F: mel frame + stop logit (folded mode: only the last step needs its own launch)
+            SkinnyBatch sb = step_phase_f(form, w, d, B, i, out);
+            es_fc(sb.p[0], i);
+            es_launch(sb, i);
             if (launch_skinny(sb, s, "step_fc_out_stop", m->opt)) return 1;
             if (on_frames && (*on_frames)(i + 1)) return 1;
         }
@@ -894,15 +830,7 @@ static int speaker_run(l2s_model* m, const float* audio, int B, int N, float* em
         if (launch_fill(cf, (int64_t)Bp * 256, 0.f, s)) return 1;
         float* out = hseq[l & 1];
         for (int t = 0; t < L; ++t) {
-            SkinnyBatch sb{};
-            SkinnyP p = sk_base(w.spk_hh[l], B);
-            p.seg[0] = {hf[t & 1], 16}; p.nseg = 1;
-            p.epi = SK_LSTM; p.H = 256;
-            p.pre = pre + (int64_t)t * 1024; p.ld_pre = (int64_t)L * 1024;
-            p.c_in = cf; p.c_out = cf;
-            p.h_out = hf[(t & 1) ^ 1]; p.h_out_K = 256; p.h_out_off = 0;
-            p.h_seq = out + (int64_t)t * 256; p.ld_hseq = (int64_t)L * 256;
-            sb.p[0] = p; sb.ntiles[0] = 64; sb.count = 1;
+            const SkinnyBatch sb = spk_lstm_step(w, l, B, hf[t & 1], hf[(t & 1) ^ 1], cf, pre + (int64_t)t * 1024, (int64_t)L * 1024, out + (int64_t)t * 256, (int64_t)L * 256);
             if (launch_skinny(sb, s, "spk_lstm_step", m->opt)) return 1;
         }
         L2S_SPK_TAP(3 + l, out, R * 256);
@@ -1001,15 +929,8 @@ static int speaker_packed_run(l2s_model* m, const float* audio, const int64_t* o
         if (launch_fill(cf, (int64_t)Bp * 256, 0.f, s)) return 1;
         float* out = hseq[l & 1];
         for (int t = 0; t < L; ++t) {      // the unmasked cell launch on the step's own rows: state rows 0 .. step_rows[t] - 1 are the clips of those ranks
-            SkinnyBatch sb{};
-            SkinnyP p = sk_base(w.spk_hh[l], pl.step_rows[t]);
-            p.seg[0] = {hf[t & 1], 16}; p.nseg = 1;
-            p.epi = SK_LSTM; p.H = 256;
-            p.pre = pre + (int64_t)pl.step_row0[t] * 1024; p.ld_pre = 1024;
-            p.c_in = cf; p.c_out = cf;
-            p.h_out = hf[(t & 1) ^ 1]; p.h_out_K = 256; p.h_out_off = 0;
-            p.h_seq = out + (int64_t)pl.step_row0[t] * 256; p.ld_hseq = 256;
-            sb.p[0] = p; sb.ntiles[0] = 64; sb.count = 1;
+            const SkinnyBatch sb = spk_lstm_step(w, l, pl.step_rows[t], hf[t & 1], hf[(t & 1) ^ 1], cf, pre + (int64_t)pl.step_row0[t] * 1024, 1024,
+                                                 out + (int64_t)pl.step_row0[t] * 256, 256);
             if (launch_skinny(sb, s, "spk_lstm_step", m->opt)) return 1;
         }
         L2S_SPK_TAP(3 + l, out, R * 256);
@@ -1830,38 +1751,22 @@ int l2s_op_lstm_cell_chain(l2s_model* m, int B, int n_pairs, void* ws, int64_t w
     hipStream_t s = (hipStream_t)stream;
     const Weights& w = m->w;
     const int Bp = pad16(B);
+    const StepForm form = step_form(w, m->opt, true);      // phases D and E of the folded step under the model's options (decode_step.h)
     Bump bp(ws, ws_bytes);
-    float* h0[2] = {bp.f((int64_t)Bp * 512), bp.f((int64_t)Bp * 512)};
-    float* h1[2] = {bp.f((int64_t)Bp * 512), bp.f((int64_t)Bp * 512)};
-    float* c0 = bp.f((int64_t)Bp * 512); float* c1 = bp.f((int64_t)Bp * 512); float* av = bp.f((int64_t)Bp * 512);
-    float* cc = bp.f((int64_t)Bp * 256); float* p2f = bp.f((int64_t)Bp * 256);
+    const StepBufs d = step_carve(bp, B);
     L2S_REQUIRE(!bp.overflow, "workspace too small");
-    for (float* z : {h0[0], h0[1], h1[0], h1[1], c0, c1, av}) if (launch_fill(z, (int64_t)Bp * 512, 0.f, s)) return 1;
-    for (float* z : {cc, p2f}) if (launch_fill(z, (int64_t)Bp * 256, 0.f, s)) return 1;
+    for (float* z : {d.h0[0], d.h0[1], d.h1[0], d.h1[1], d.c0, d.c1, d.av}) if (launch_fill(z, (int64_t)Bp * 512, 0.f, s)) return 1;
+    for (float* z : {d.cc, d.p2f}) if (launch_fill(z, (int64_t)Bp * 256, 0.f, s)) return 1;
     hipEvent_t e0, e1;
     L2S_CHECK_HIP(hipEventCreate(&e0));
     L2S_CHECK_HIP(hipEventCreate(&e1));
-    auto pair = [&](int cur) -> int {
-        const int nxt = cur ^ 1;
-        SkinnyBatch sb{};
-        const bool vhoist = m->opt.hoist_vproj && w.lstm0v.W && w.vproj.W;      // the layer-0 launch of the production step (decode_launches)
-        const bool vsum = vhoist && m->opt.hoist_vproj >= 2 && skinny_sum_supported(m->opt);
-        SkinnyP a = sk_base(vsum ? w.lstm0 : vhoist ? w.lstm0v : w.lstm0f, B);
-        if (vsum) { a.seg[0] = {cc, 16}; a.seg[1] = {p2f, 16}; a.a_sum = av; a.seg[2] = {h0[cur], 32}; a.nseg = 3; }
-        else { a.seg[0] = {cc, 16}; a.seg[1] = {p2f, 16}; a.seg[2] = {av, vhoist ? 16 : 32}; a.seg[3] = {h0[cur], 32}; a.nseg = 4; }
-        a.epi = SK_LSTM; a.H = 512; a.c_in = c0; a.c_out = c0; a.h_out = h0[nxt]; a.h_out_K = 512; a.h_out_off = 0;
-        sb.p[0] = a; sb.ntiles[0] = 128; sb.count = 1;
-        if (launch_skinny(sb, s, "step_lstm_cell", m->opt)) return 1;
-        SkinnyBatch sc{};
-        SkinnyP b = sk_base(w.lstm1, B);
-        b.seg[0] = {h0[nxt], 32}; b.seg[1] = {h1[cur], 32}; b.nseg = 2;
-        b.epi = SK_LSTM; b.H = 512; b.c_in = c1; b.c_out = c1; b.h_out = h1[nxt]; b.h_out_K = 512; b.h_out_off = 0;
-        sc.p[0] = b; sc.ntiles[0] = 128; sc.count = 1;
-        return launch_skinny(sc, s, "step_lstm_cell", m->opt);
+    auto pair = [&](int i) -> int {
+        if (launch_skinny(step_phase_d(form, w, d, B, i), s, "step_lstm_cell", m->opt)) return 1;
+        return launch_skinny(step_phase_e(form, w, d, B, i), s, "step_lstm_cell", m->opt);
     };
-    for (int i = 0; i < 8; ++i) if (pair(i & 1)) return 1;                   // warm-up
+    for (int i = 0; i < 8; ++i) if (pair(i)) return 1;                   // warm-up
     L2S_CHECK_HIP(hipEventRecord(e0, s));
-    for (int i = 0; i < n_pairs; ++i) if (pair(i & 1)) return 1;
+    for (int i = 0; i < n_pairs; ++i) if (pair(i)) return 1;
     L2S_CHECK_HIP(hipEventRecord(e1, s));
     L2S_CHECK_HIP(hipEventSynchronize(e1));
     float ms = 0.f;
@@ -1881,21 +1786,14 @@ int l2s_op_step_attn_chain(l2s_model* m, float* state, int B, int T, int n_launc
     const Weights& w = m->w;
     StateLayout sl = state_layout(B, T);
     const int Bp = pad16(B);
+    const StepForm form = step_form(w, m->opt, true);      // phase B of the folded step under the model's options (decode_step.h)
     Bump bp(ws, ws_bytes);
-    float* q = bp.f((int64_t)B * 512); float* qc = bp.f((int64_t)B * 256);
-    float* av = bp.f((int64_t)Bp * 512); float* cc = bp.f((int64_t)Bp * 256); float* p1 = bp.f((int64_t)Bp * 256); float* p2f = bp.f((int64_t)Bp * 256);
+    const StepBufs d = step_carve(bp, B);
     L2S_REQUIRE(!bp.overflow, "workspace too small");
-    if (launch_fill(q, (int64_t)B * 512, 0.f, s) || launch_fill(qc, (int64_t)B * 256, 0.f, s) || launch_fill(p1, (int64_t)Bp * 256, 0.f, s)) return 1;
+    if (launch_fill(d.q, (int64_t)B * 512, 0.f, s) || launch_fill(d.qc, (int64_t)B * 256, 0.f, s) || launch_fill(d.p1, (int64_t)Bp * 256, 0.f, s)) return 1;
     for (int i = 0; i < n_launches; ++i) {
-        AttnP at{};
-        at.q = q; at.ldq = 512; at.k = state + sl.k; at.v = state + sl.v; at.tau = w.tau; at.av_frag = av;
-        if (m->opt.hoist_vproj && w.vproj.W) at.vp = state + sl.vp;      // the production form: 256 value columns
-        at.attn_out = nullptr; at.ld_attn_b = 0; at.attn_logits = 0;
-        at.qc = qc; at.ldqc = 256; at.ckey = state + sl.ckey; at.cval = state + sl.cval; at.tau_c = w.tau_c; at.cc_frag = cc;
-        at.B = B; at.T = T; at.m = sl.m;
-        SkinnyP pr = sk_base(w.pre2, B);
-        pr.seg[0] = {p1, 16}; pr.nseg = 1; pr.act = ACT_PSINE; pr.epi = SK_FRAG; pr.out = p2f; pr.ldo = 256;
-        if (launch_step_attn(at, pr, w.pre2.tiles, s, m->opt.attn_lds, m->opt.attn_skip0)) return 1;
+        const StepAttn b = step_phase_b(form, w, d, state, sl, B, T, 0, 1, nullptr, 0);
+        if (launch_step_attn(b.at, b.pre2, b.pre2_tiles, s, m->opt.attn_lds, m->opt.attn_skip0)) return 1;
     }
     return 0;
 }
@@ -1939,6 +1837,47 @@ int l2s_op_skinny_form(l2s_model* m, int count, const int* groups, int B, int ch
     k.erase(0, k.find("l2s::") + 5);
     if (k.find("_timed") == std::string::npos) k = k.substr(0, k.rfind(", ")) + ">";      // every other batch-row kernel template ends in the early-stop flag
     std::snprintf(out, cap, "%s grid=(%u,%u,%u) block=%d lds=%d", k.c_str(), grid.x, grid.y, grid.z, block, lds);
+    return 0;
+}
+
+// the batch that the builders of decode_step.h make for a named call site, as l2s_op_skinny_form's integers; nothing is launched
+int l2s_op_step_site(l2s_model* m, const char* site, int B, int* groups, int* count) {
+    L2S_REQUIRE(m && m->finalized && site && groups && count && B >= 1, "bad arguments");
+    struct Site { const char* name; int fold, hoist, step; char phase; };      // hoist < 0: the model's own "hoist_vproj"
+    static const Site sites[] = {
+        {"bilstm_step", 1, -1, 0, 'L'}, {"phase_a_unfolded", 0, -1, 1, 'A'}, {"phase_a_folded_step0", 1, -1, 0, 'A'}, {"phase_a_folded", 1, -1, 1, 'A'},
+        {"step_attention_proj", 0, -1, 1, 'C'}, {"phase_d_k1536", 1, 0, 1, 'D'}, {"phase_d_k1280", 1, 1, 1, 'D'}, {"phase_d_k1024_sum", 1, 2, 1, 'D'},
+        {"phase_d_k1024_unfolded", 0, -1, 1, 'D'}, {"phase_e", 1, -1, 1, 'E'}, {"step_fc_out_stop", 1, -1, 1, 'F'}, {"spk_lstm_step", 1, -1, 0, 'S'}};
+    const Site* st = nullptr;
+    for (const Site& t : sites) if (!std::strcmp(site, t.name)) st = &t;
+    L2S_REQUIRE(st, "step site: unknown name");
+    L2S_REQUIRE(st->phase == 'S' ? m->has_spk : m->has_dec, "step site: the model holds no weights of that recurrence");
+    static float a[1];      // stands for every buffer, as in l2s_op_skinny_form
+    StepBufs d;
+    for (float** p : {&d.h0[0], &d.h0[1], &d.h1[0], &d.h1[1], &d.c0, &d.c1, &d.av, &d.p1, &d.cc, &d.uu, &d.p2f, &d.yf, &d.q, &d.qc, &d.p2}) *p = a;
+    Options o = m->opt;
+    if (st->hoist >= 0) o.hoist_vproj = st->hoist;
+    const Weights& w = m->w;
+    const StepForm form = step_form(w, o, st->fold != 0);
+    const StepOut out{a, a, a, 2};
+    const int i = st->step;
+    SkinnyBatch sb{};
+    switch (st->phase) {
+    case 'L': for (int dir = 0; dir < 2; ++dir) bilstm_step_group(sb, dir, w, true, B, 7, 0, a, a, a, a, a); sb.count = 2; break;
+    case 'A': sb = step_phase_a(form, w, d, B, i, step_from_frame(form, i, false), out); break;
+    case 'C': sb = step_phase_c(form, w, d, B); break;
+    case 'D': sb = step_phase_d(form, w, d, B, i); break;
+    case 'E': sb = step_phase_e(form, w, d, B, i); break;
+    case 'F': sb = step_phase_f(form, w, d, B, i, out); break;
+    default:  sb = spk_lstm_step(w, 0, B, a, a, a, a, 1024, a, 256); break;
+    }
+    for (int g = 0; g < sb.count; ++g) {
+        const SkinnyP& p = sb.p[g];
+        int* r = groups + 8 * g;      // nchunks[4], ntiles, epi, W3 set, a_sum set
+        for (int j = 0; j < 4; ++j) r[j] = j < p.nseg ? p.seg[j].nchunks : 0;
+        r[4] = sb.ntiles[g]; r[5] = p.epi; r[6] = p.W3 != nullptr; r[7] = p.a_sum != nullptr;
+    }
+    *count = sb.count;
     return 0;
 }
 

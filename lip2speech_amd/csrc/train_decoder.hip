@@ -7,6 +7,7 @@
 #include "../../include/l2s.h"
 #include "l2s_common.h"
 #include "l2s_model.h"
+#include "decode_step.h"
 
 #include <algorithm>
 
@@ -651,12 +652,6 @@ static int colsum(const float* x, int64_t rows, int C, float* partials, float* s
 
 namespace l2s {
 
-static SkinnyP tsk(const SkW& sw, int B) {
-    SkinnyP p{};
-    p.W = sw.W; p.bias = sw.bias; p.actw = sw.actw; p.B = B; p.N = sw.N; p.K = sw.K; p.act = ACT_NONE; p.epi = SK_PLAIN;
-    return p;
-}
-
 __global__ __launch_bounds__(256) void psine_fwd_kernel(const float* __restrict__ z, const float* __restrict__ w, int64_t rows, int C, float* __restrict__ out) {
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < rows * C; i += (int64_t)gridDim.x * 256) out[i] = sinf(z[i]) * w[i % C];
 }
@@ -675,111 +670,74 @@ static int decode_train_fwd(l2s_model* m, float* state, int B, int T, int S, con
     StepTape tp = step_tape(tape_base, B, S);
     const int Bp = pad16(B);
     Bump bp(ws, ws_bytes);
-    float* h0[2] = {bp.f((int64_t)Bp * 512), bp.f((int64_t)Bp * 512)};
-    float* h1[2] = {bp.f((int64_t)Bp * 512), bp.f((int64_t)Bp * 512)};
-    float* c0 = bp.f((int64_t)Bp * 512); float* c1 = bp.f((int64_t)Bp * 512); float* av = bp.f((int64_t)Bp * 512);
-    float* p1 = bp.f((int64_t)Bp * 256); float* cc = bp.f((int64_t)Bp * 256); float* uu = bp.f((int64_t)Bp * 256);
-    float* yf = bp.f((int64_t)Bp * 96);
-    float* q = bp.f((int64_t)B * 512); float* qc = bp.f((int64_t)B * 256); float* p2 = bp.f((int64_t)B * 256);
-    float* h0d = bp.f((int64_t)Bp * 512);
-    float* p2f = bp.f((int64_t)Bp * 256);
+    const StepBufs d = step_carve(bp, B);
+    float* h0d = bp.f((int64_t)Bp * 512);      // h0 after the inter-layer dropout: layer 1's input operand when drop.rnn is set
     L2S_REQUIRE(!bp.overflow, "training decode workspace too small");
     // The phase-merged step of inference (prenet1 o fc_out over h1, attention_proj folded into LSTM0's input weights) is used
     // here too when the merged matrices are valid (packed by the host, or re-merged on the device by l2s_train_refresh_weights): 4 launches per
     // step instead of 6.  The tape is the same (z1, z2, zq, zc, alpha, a@v, gates, cells, hidden states); u = attention_proj(a@v) + prenet is
     // only needed by the parameter gradients and is rebuilt for all steps at once after the loop.
     const bool fold = m->opt.fold != 0 && m->folded_valid && w.pre1f.W && w.lstm0f.W;
+    // the launches are those of inference (decode_step.h) in the training form: folded onto lstm0f or literal, f32 weights; the loop overlays the tape
+    // stores, the dropout masks and the dropped h0 operand
+    const StepForm form = step_form_train(fold);
+    const StepOut out{mel, stop, state + sl.stopc, S};
     // every buffer above starts at zero (padded rows of the fragments must not hold NaN garbage): ONE fill over the whole run, then the initial state
-    if (launch_fill(h0[0], bp.off / (int64_t)sizeof(float), 0.f, s)) return 1;
-    L2S_CHECK_HIP(hipMemcpyAsync(h0[0], state + sl.h, sizeof(float) * Bp * 512, hipMemcpyDeviceToDevice, s));
-    L2S_CHECK_HIP(hipMemcpyAsync(h1[0], state + sl.h + (int64_t)Bp * 512, sizeof(float) * Bp * 512, hipMemcpyDeviceToDevice, s));
-    if (launch_to_frag(w.bos, 0, B, 80, yf, 80, 0, 1, s)) return 1;
+    if (launch_fill(d.h0[0], bp.off / (int64_t)sizeof(float), 0.f, s)) return 1;
+    L2S_CHECK_HIP(hipMemcpyAsync(d.h0[0], state + sl.h, sizeof(float) * Bp * 512, hipMemcpyDeviceToDevice, s));
+    L2S_CHECK_HIP(hipMemcpyAsync(d.h1[0], state + sl.h + (int64_t)Bp * 512, sizeof(float) * Bp * 512, hipMemcpyDeviceToDevice, s));
+    if (launch_to_frag(w.bos, 0, B, 80, d.yf, 80, 0, 1, s)) return 1;
     // tape row 0 of the state sequences
-    if (launch_from_frag(h0[0], 512, B, 512, tp.h0, 512, 0, s)) return 1;
-    if (launch_from_frag(h1[0], 512, B, 512, tp.h1, 512, 0, s)) return 1;
+    if (launch_from_frag(d.h0[0], 512, B, 512, tp.h0, 512, 0, s)) return 1;
+    if (launch_from_frag(d.h1[0], 512, B, 512, tp.h1, 512, 0, s)) return 1;
     if (launch_fill(tp.c0, (int64_t)B * 512, 0.f, s)) return 1;
     if (launch_fill(tp.c1, (int64_t)B * 512, 0.f, s)) return 1;
 
     for (int i = 0; i < S; ++i) {
-        const int cur = i & 1, nxt = cur ^ 1;
         const int64_t r256 = (int64_t)i * B * 256, r512 = (int64_t)i * B * 512;
-        if (teacher && mask && mask[i])
-            if (launch_to_frag(teacher + (int64_t)i * NM_, S * NM_, B, 80, yf, 80, 0, 0, s)) return 1;
-        {
-            SkinnyBatch sb{}; TrainSkinnyBatch tb{};
-            const bool from_frame = !fold || i == 0 || (teacher && mask && mask[i]);      // prenet input is an explicit frame (BOS / teacher / unfolded y)
-            SkinnyP a = tsk(from_frame ? w.pre1 : w.pre1f, B);
-            if (from_frame) a.seg[0] = {yf, 5}; else a.seg[0] = {h1[cur], 32};
-            a.nseg = 1; a.act = ACT_PSINE; a.epi = SK_FRAG; a.out = p1; a.ldo = 256;
+        const bool forced = teacher && mask && mask[i];
+        if (forced)
+            if (launch_to_frag(teacher + (int64_t)i * NM_, S * NM_, B, 80, d.yf, 80, 0, 0, s)) return 1;
+        {      // phase A (folded, i > 0: the mel frame + stop logit of step i-1 ride in this launch)
+            const SkinnyBatch sb = step_phase_a(form, w, d, B, i, step_from_frame(form, i, forced), out);
+            TrainSkinnyBatch tb{};
             tb.t[0].zsave = tp.z1 + r256; tb.t[0].ld_z = 256;
             if (drop.prenet) { tb.t[0].out_mask = drop.prenet + r256; tb.t[0].ld_mask = 256; }
-            SkinnyP b = tsk(w.q, B);
-            b.seg[0] = {h0[cur], 32}; b.seg[1] = {h1[cur], 32}; b.nseg = 2; b.act = ACT_PSINE; b.out = q; b.ldo = 512;
-            b.addrow = w.pos + (int64_t)i * 512;
             tb.t[1].zsave = tp.zq + r512; tb.t[1].ld_z = 512;
-            SkinnyP c = tsk(w.cq, B);
-            c.seg[0] = {c0, 32}; c.seg[1] = {c1, 32}; c.nseg = 2; c.act = ACT_SILU; c.out = qc; c.ldo = 256;
             tb.t[2].zsave = tp.zc + r256; tb.t[2].ld_z = 256;
-            sb.p[0] = a; sb.ntiles[0] = 16; sb.p[1] = b; sb.ntiles[1] = w.q.tiles; sb.p[2] = c; sb.ntiles[2] = w.cq.tiles; sb.count = 3;
-            if (fold && i > 0) {          // mel frame + stop logit of step i-1 ride in this launch
-                SkinnyP f = tsk(w.fc, B);
-                f.seg[0] = {h1[cur], 32}; f.nseg = 1; f.epi = SK_MEL;
-                f.mel = mel + (int64_t)(i - 1) * NM_; f.ld_mel_b = (int64_t)S * NM_; f.stop = stop + (i - 1); f.ld_stop_b = S;
-                f.stop_const = state + sl.stopc; f.yfrag = nullptr;
-                sb.p[3] = f; sb.ntiles[3] = w.fc.tiles; sb.count = 4;
-            }
             if (launch_train_skinny(sb, tb, s, fold ? "train_step_prenet1_q_cq_fc" : "train_step_prenet1_q_cq")) return 1;
         }
-        {
+        {      // phase B
+            const StepAttn b = step_phase_b(form, w, d, state, sl, B, T, i, S, attn_logits, 1);
             TrainStepB sb{};
-            AttnP& at = sb.at;
-            at.q = q; at.ldq = 512; at.k = state + sl.k; at.v = state + sl.v; at.tau = w.tau; at.av_frag = av;
-            at.attn_out = attn_logits + (int64_t)i * T; at.ld_attn_b = (int64_t)S * T; at.attn_logits = 1;
-            at.qc = qc; at.ldqc = 256; at.ckey = state + sl.ckey; at.cval = state + sl.cval; at.tau_c = w.tau_c; at.cc_frag = cc;
-            at.B = B; at.T = T; at.m = sl.m;
+            sb.at = b.at; sb.pre2 = b.pre2; sb.pre2_tiles = b.pre2_tiles;
             if (drop.attn) { sb.att.logit_mask = drop.attn + (int64_t)i * B * T; sb.att.ld_lmask = T; }
             sb.att.alpha = tp.alpha + (int64_t)i * B * ATT_MAXM; sb.att.ld_alpha = ATT_MAXM; sb.att.av_plain = tp.av + r512; sb.att.cc_plain = tp.cc + r256;
-            sb.pre2 = tsk(w.pre2, B);
-            sb.pre2.seg[0] = {p1, 16}; sb.pre2.nseg = 1; sb.pre2.act = ACT_PSINE; sb.pre2.out = p2; sb.pre2.ldo = 256;
-            if (fold) { sb.pre2.epi = SK_FRAG; sb.pre2.out = p2f; }
             sb.pre2t.zsave = tp.z2 + r256; sb.pre2t.ld_z = 256;
-            sb.pre2_tiles = w.pre2.tiles;
             ProfScope ps("train_step_attention_prenet2", s);
-            hipLaunchKernelGGL(train_step_attn_kernel, dim3(2 * B + w.pre2.tiles * (Bp / 16)), dim3(512), 0, s, sb);
+            hipLaunchKernelGGL(train_step_attn_kernel, dim3(2 * B + sb.pre2_tiles * (Bp / 16)), dim3(512), 0, s, sb);
             L2S_CHECK_HIP(hipGetLastError());
         }
-        if (!fold) {
-            SkinnyBatch sb{}; TrainSkinnyBatch tb{};
-            SkinnyP a = tsk(w.aproj, B);
-            a.seg[0] = {av, 32}; a.nseg = 1; a.epi = SK_FRAG; a.out = uu; a.ldo = 256; a.add = p2; a.ld_add = 256;
+        if (!fold) {      // phase C
+            const SkinnyBatch sb = step_phase_c(form, w, d, B);
+            TrainSkinnyBatch tb{};
             tb.t[0].out_plain = tp.u + r256; tb.t[0].ld_out = 256;
-            sb.p[0] = a; sb.ntiles[0] = w.aproj.tiles; sb.count = 1;
             if (launch_train_skinny(sb, tb, s, "train_step_attention_proj")) return 1;
         }
-        for (int layer = 0; layer < 2; ++layer) {
-            SkinnyBatch sb{}; TrainSkinnyBatch tb{};
-            SkinnyP a = tsk(layer == 0 ? (fold ? w.lstm0f : w.lstm0) : w.lstm1, B);
-            if (layer == 0 && fold) { a.seg[0] = {cc, 16}; a.seg[1] = {p2f, 16}; a.seg[2] = {av, 32}; a.seg[3] = {h0[cur], 32}; a.nseg = 4; }
-            else if (layer == 0) { a.seg[0] = {cc, 16}; a.seg[1] = {uu, 16}; a.seg[2] = {h0[cur], 32}; a.nseg = 3; }
-            else { a.seg[0] = {drop.rnn ? h0d : h0[nxt], 32}; a.seg[1] = {h1[cur], 32}; a.nseg = 2; }
-            a.epi = SK_LSTM; a.H = 512;
+        for (int layer = 0; layer < 2; ++layer) {      // phases D and E
+            SkinnyBatch sb = layer == 0 ? step_phase_d(form, w, d, B, i) : step_phase_e(form, w, d, B, i);
+            TrainSkinnyBatch tb{};
+            SkinnyP& a = sb.p[0];
+            if (layer == 1 && drop.rnn) a.seg[0].a = h0d;
             if (layer == 0 && drop.rnn) { tb.t[0].h_drop = h0d; tb.t[0].h_drop_K = 512; tb.t[0].h_mask = drop.rnn + r512; tb.t[0].ld_hmask = 512; }
-            a.c_in = layer == 0 ? c0 : c1; a.c_out = a.c_in == c0 ? c0 : c1;
-            a.h_out = layer == 0 ? h0[nxt] : h1[nxt]; a.h_out_K = 512; a.h_out_off = 0;
             a.h_seq = (layer == 0 ? tp.h0 : tp.h1) + (int64_t)(i + 1) * B * 512; a.ld_hseq = 512;
             tb.t[0].gates = (layer == 0 ? tp.g0 : tp.g1) + (int64_t)i * B * 2048; tb.t[0].ld_gates = 2048;
             tb.t[0].c_new = (layer == 0 ? tp.c0 : tp.c1) + (int64_t)(i + 1) * B * 512; tb.t[0].ld_c = 512;
-            sb.p[0] = a; sb.ntiles[0] = 128; sb.count = 1;
             if (launch_train_skinny(sb, tb, s, "train_step_lstm_cell")) return 1;
         }
-        if (!fold || i == S - 1) {
-            SkinnyBatch sb{}; TrainSkinnyBatch tb{};
-            SkinnyP a = tsk(w.fc, B);
-            a.seg[0] = {h1[nxt], 32}; a.nseg = 1; a.epi = SK_MEL;
-            a.mel = mel + (int64_t)i * NM_; a.ld_mel_b = (int64_t)S * NM_; a.stop = stop + i; a.ld_stop_b = S;
-            a.stop_const = state + sl.stopc; a.yfrag = yf;
-            sb.p[0] = a; sb.ntiles[0] = w.fc.tiles; sb.count = 1;
-            if (launch_train_skinny(sb, tb, s, "train_step_fc_out_stop")) return 1;
+        if (step_has_phase_f(form, i, S)) {
+            const SkinnyBatch sb = step_phase_f(form, w, d, B, i, out);
+            if (launch_train_skinny(sb, TrainSkinnyBatch{}, s, "train_step_fc_out_stop")) return 1;
         }
     }
     if (fold) {      // u = attention_proj(a@v) + prenet for all S*B rows: PSine(z2) first, then the product with the prenet as its addend, in place
@@ -1168,16 +1126,10 @@ static int prologue_train_fwd(l2s_model* m, const float* vis, const float* emb, 
         SkinnyBatch sb{}; TrainSkinnyBatch tb{};
         const int cur = step & 1, nxt = cur ^ 1;
         for (int d = 0; d < 2; ++d) {
-            const int t = d == 0 ? step : T - 1 - step;
-            SkinnyP p = tsk(w.whh[d], B);
-            p.seg[0] = {hf[d][cur], 32}; p.nseg = 1; p.epi = SK_LSTM; p.H = 512;
-            p.pre = tp.gin + (int64_t)t * 4096 + d * 2048; p.ld_pre = (int64_t)T * 4096;
-            p.c_in = cf[d]; p.c_out = cf[d]; p.h_out = hf[d][nxt]; p.h_out_K = 512; p.h_out_off = 0;
-            p.h_seq = tp.rnn + (int64_t)t * 1024 + d * 512; p.ld_hseq = (int64_t)T * 1024;
-            p.h_plain = tp.hproc[d] + (int64_t)(step + 1) * B * 512; p.ld_hplain = 512;
+            bilstm_step_group(sb, d, w, false, B, T, d == 0 ? step : T - 1 - step, hf[d][cur], hf[d][nxt], cf[d], tp.gin, tp.rnn);
+            sb.p[d].h_plain = tp.hproc[d] + (int64_t)(step + 1) * B * 512; sb.p[d].ld_hplain = 512;
             tb.t[d].gates = tp.gates[d] + (int64_t)step * B * 2048; tb.t[d].ld_gates = 2048;
             tb.t[d].c_new = tp.cproc[d] + (int64_t)(step + 1) * B * 512; tb.t[d].ld_c = 512;
-            sb.p[d] = p; sb.ntiles[d] = w.whh[d].tiles;
         }
         sb.count = 2;
         if (launch_train_skinny(sb, tb, s, "train_bilstm_step")) return 1;

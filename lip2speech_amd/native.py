@@ -50,7 +50,7 @@ ABI_SYMBOLS = (
 )
 # what include/l2s_diag.h adds: exported by libl2s_diag.so only
 DIAG_SYMBOLS = (
-    "l2s_op_gemm", "l2s_op_conv1d", "l2s_op_gemm_ex", "l2s_op_conv1d_ex", "l2s_op_conv1d_bwd", "l2s_op_frontend", "l2s_op_launch_chain", "l2s_op_launch_chain2", "l2s_op_skinny_timeline", "l2s_op_attn_timeline", "l2s_op_flat_timeline", "l2s_op_pdecode_timeline", "l2s_op_gemm_x3_timeline", "l2s_op_fused_unit_timeline", "l2s_op_lstm_cell_chain", "l2s_op_step_attn_chain", "l2s_op_stamp_log", "l2s_op_skinny_form", "l2s_op_skinny",
+    "l2s_op_gemm", "l2s_op_conv1d", "l2s_op_gemm_ex", "l2s_op_conv1d_ex", "l2s_op_conv1d_bwd", "l2s_op_frontend", "l2s_op_launch_chain", "l2s_op_launch_chain2", "l2s_op_skinny_timeline", "l2s_op_attn_timeline", "l2s_op_flat_timeline", "l2s_op_pdecode_timeline", "l2s_op_gemm_x3_timeline", "l2s_op_fused_unit_timeline", "l2s_op_lstm_cell_chain", "l2s_op_step_attn_chain", "l2s_op_stamp_log", "l2s_op_skinny_form", "l2s_op_step_site", "l2s_op_skinny",
     "l2s_op_face_conv2d", "l2s_op_face_taps", "l2s_op_speaker_taps", "l2s_op_speaker_taps_packed", "l2s_op_encoder_taps",
 )
 
@@ -272,6 +272,7 @@ def _bind_diag(L: ctypes.CDLL) -> None:
     L.l2s_op_lstm_cell_chain.argtypes = [_vp, _i, _i, _vp, _i64, _vp, ctypes.POINTER(ctypes.c_double)]
     L.l2s_op_stamp_log.argtypes = [_vp, _i64]
     L.l2s_op_skinny_form.argtypes = [_vp, _i, ctypes.POINTER(ctypes.c_int), _i, _i, _i, _i, ctypes.c_char_p, _i]
+    L.l2s_op_step_site.argtypes = [_vp, ctypes.c_char_p, _i, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
     L.l2s_op_skinny.argtypes = [_vp, _i, ctypes.POINTER(SkinnyGroup), _i, _vp, _i, _vp]
     L.l2s_op_face_conv2d.argtypes = [_fp, _i64, _i, _i, _i, _i, _fp, _fp, _fp, _fp, _i, _fp, _i, _i, _i, _i, _i, _i, _vp]
     L.l2s_op_face_taps.argtypes = [_vp, _fp, _i64, _i, _vp, _fp, _fp, _vp, _i64, _vp]
@@ -1034,6 +1035,14 @@ class NativeModel:
         _replay_thread_chains(D)            # the chain launches the block forms of this thread's hint: the ones the caller's timed region launches
         check(D.l2s_op_lstm_cell_chain(self._h, B, n_pairs, _ptr(ws), ws.numel(), _stream(), ctypes.byref(out)), D)
         return float(out.value)
+
+    def step_site(self, site: str, B: int = 1) -> list:
+        """The batch the library builds at a call site of the batch-row launches (csrc/decode_step.h), as the groups of l2s_op_skinny_form:
+        [nchunks x 4, ntiles, epi, W3 set, a_sum set] each.  Nothing is launched."""
+        groups, count = (ctypes.c_int * 32)(), ctypes.c_int()
+        D = diag()
+        check(D.l2s_op_step_site(self._h, site.encode(), B, groups, ctypes.byref(count)), D)
+        return [list(groups[8 * g:8 * g + 8]) for g in range(count.value)]
 
     def op_frontend(self, video: torch.Tensor) -> torch.Tensor:
         video = _f32(video)
