@@ -173,6 +173,39 @@ typedef struct l2s_skinny_group {
  * non-zero with the text in l2s_last_error (the text l2s_op_skinny_form answers after "ERROR "). */
 int l2s_op_skinny(l2s_model* m, int count, const l2s_skinny_group* groups, int B, const int* es_end, int es_step, void* stream);
 
+/* One backward GEMM on its own: the operator-level entry of gemm_bwd.hip (tests/test_gemm_bwd_op_gpu.py; lip2speech_amd/native.py op_gemm_bwd).  The
+ * descriptor holds the integers of BwdGemmP (l2s_common.h) with the meaning they have there:
+ *   mode 0 (DX): C[m][j] = alpha * sum_r dZcol(m, r) * Wp[n(r)][tap(r) * Cin + j]   A = dZ (B,Tz,Nout) rows of lda, B = Wp [Nout][taps*Cin] rows of ldb,
+ *                M = B*Tx, N = Cin, K = taps*Nout, padp = taps - 1 - pad (stride 1)
+ *   mode 1 (DW): C[n][j] = alpha * sum_m dZ[m][n] * Xcol(m, j)                       A = dZ, B = X (B,Tx,Cin) rows of ldb, M = Nout, N = taps*Cin, K = B*Tz
+ *   C rows of ldc; with c_T > 0 row m of C starts at (m / c_T) * c_seq_stride + (m % c_T) * ldc; accumulate: C += instead of C =
+ * The 64-bit field comes first, so that the struct has no padding. */
+typedef struct l2s_gemm_bwd_desc {
+    int64_t c_seq_stride;
+    int32_t mode, M, N, K, lda, ldb, ldc, Tx, Tz, taps, stride, pad, padp, Nout, Cin, c_T, accumulate;
+    float alpha;
+} l2s_gemm_bwd_desc;
+/* What one call of a launch function of gemm_bwd.hip ran, as the launch recorder keeps it: entry 0 launch_gemm_bwd, 1 launch_gemm_bwd_splitk,
+ * 2 launch_gemm_bwd_dw_dx (then pair = 1, d[0] the DW half and d[1] the DX half; otherwise d[1] is zero); the K slices the caller asked for and the count
+ * that ran after clipping to the K tiles (1 = no partial matrices); vec / bf16: the <VEC, BF16> template arguments of the kernel instance; align: the
+ * addresses of A, B, C modulo 16 bytes, per descriptor; name: the launch's profile name */
+typedef struct l2s_gemm_bwd_record {
+    l2s_gemm_bwd_desc d[2];
+    int32_t entry, splits_asked, splits, vec, bf16, pair;
+    int32_t align[2][3];
+    char name[40];
+} l2s_gemm_bwd_record;
+/* d with its device pointers A, B, C through the product's launch functions and nothing else: d2 == NULL and splits == 0 -> launch_gemm_bwd; d2 == NULL
+ * and splits >= 1 -> launch_gemm_bwd_splitk (partials: splits * M * N floats); d2 != NULL -> launch_gemm_bwd_dw_dx with d the DW half, d2 (A2, B2, C2) the
+ * DX half and `splits` slices of the DW reduction.  bf16 != 0: bf16 operands (what option "train_bf16" runs).  ran (may be NULL) receives the record of
+ * the call - zeroes when the launch was refused; a refused launch returns non-zero with the rule in l2s_last_error */
+int l2s_op_gemm_bwd(const l2s_gemm_bwd_desc* d, const float* A, const float* B, float* C, const l2s_gemm_bwd_desc* d2, const float* A2, const float* B2,
+                    float* C2, int splits, float* partials, int bf16, l2s_gemm_bwd_record* ran, void* stream);
+/* The launch recorder of gemm_bwd.hip (host code, one mutex): cmd 1 = forget what was recorded and arm - from then on every call of the three launch
+ * functions, from any entry point of this library, appends its record; cmd 0 = disarm (the records stay); cmd 2 = copy the first `cap` records to out.
+ * *count (may be NULL) receives the number of records held */
+int l2s_op_gemm_bwd_recorder(int cmd, l2s_gemm_bwd_record* out, int cap, int* count);
+
 #ifdef __cplusplus
 }
 #endif

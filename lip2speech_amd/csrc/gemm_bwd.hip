@@ -11,6 +11,12 @@
 #include "gemm_dev.h"
 
 #include <algorithm>
+#ifdef L2S_DIAG
+#include <cstring>
+#include <mutex>
+#include <vector>
+#include "../../include/l2s_diag.h"
+#endif
 
 namespace l2s {
 
@@ -197,6 +203,51 @@ __global__ __launch_bounds__(256) void gemm_bwd_pair_kernel(const BwdGemmP pw, c
     else { id -= nw; gemm_bwd_block<BWD_DX, BF16, VEC>(px, id % xx, id / xx, 0, As, Bs); }
 }
 
+#ifdef L2S_DIAG
+// Launch recorder (libl2s_diag.so only, host code only): every call of the three launch functions below leaves one l2s_gemm_bwd_record - the descriptor as
+// the CALLER wrote it, the entry it came through, the slices asked for and used, the kernel instance - in a thread-local slot (what l2s_op_gemm_bwd reports
+// back), and appends it to a host buffer while the recorder is armed (l2s_op_gemm_bwd_recorder; tests/test_gemm_bwd_op_gpu.py replays the buffer).
+static std::mutex g_bwd_rec_mu;
+static bool g_bwd_rec_armed = false;
+static std::vector<l2s_gemm_bwd_record> g_bwd_recs;
+static thread_local l2s_gemm_bwd_record tl_bwd_last;
+static thread_local int tl_bwd_entry = 0, tl_bwd_asked = 0;      // set by launch_gemm_bwd_splitk around a call it hands on to launch_gemm_bwd
+static thread_local bool tl_bwd_inner = false;                   // the partial-matrix launch inside a split: the outer call writes the record
+
+static void bwd_desc_of(const BwdGemmP& p, l2s_gemm_bwd_desc& d, int32_t* align) {
+    d.c_seq_stride = p.c_seq_stride;
+    d.mode = p.mode; d.M = p.M; d.N = p.N; d.K = p.K; d.lda = p.lda; d.ldb = p.ldb; d.ldc = p.ldc;
+    d.Tx = p.Tx; d.Tz = p.Tz; d.taps = p.taps; d.stride = p.stride; d.pad = p.pad; d.padp = p.padp; d.Nout = p.Nout; d.Cin = p.Cin;
+    d.c_T = p.c_T; d.accumulate = p.accumulate; d.alpha = p.alpha;
+    align[0] = (int32_t)(reinterpret_cast<uintptr_t>(p.A) & 15u); align[1] = (int32_t)(reinterpret_cast<uintptr_t>(p.B) & 15u);
+    align[2] = (int32_t)(reinterpret_cast<uintptr_t>(p.C) & 15u);
+}
+static void bwd_record(int entry, int asked, int used, bool vec, const BwdGemmP& p, const BwdGemmP* px, const char* name) {
+    l2s_gemm_bwd_record r;
+    std::memset(&r, 0, sizeof r);
+    bwd_desc_of(p, r.d[0], r.align[0]);
+    if (px) bwd_desc_of(*px, r.d[1], r.align[1]);
+    r.entry = entry; r.splits_asked = asked; r.splits = used; r.vec = vec ? 1 : 0; r.bf16 = gemm_bf16_mode() != 0 ? 1 : 0; r.pair = px ? 1 : 0;
+    std::strncpy(r.name, name ? name : "", sizeof r.name - 1);
+    tl_bwd_last = r;
+    std::lock_guard<std::mutex> lk(g_bwd_rec_mu);
+    if (g_bwd_rec_armed) g_bwd_recs.push_back(r);
+}
+const l2s_gemm_bwd_record& gemm_bwd_last_record() { return tl_bwd_last; }
+void gemm_bwd_clear_last_record() { std::memset(&tl_bwd_last, 0, sizeof tl_bwd_last); }
+int gemm_bwd_recorder(int cmd, l2s_gemm_bwd_record* out, int cap, int* count) {
+    std::lock_guard<std::mutex> lk(g_bwd_rec_mu);
+    if (cmd == 1) { g_bwd_recs.clear(); g_bwd_rec_armed = true; }
+    else if (cmd == 0) g_bwd_rec_armed = false;
+    else if (cmd == 2) {
+        L2S_REQUIRE(cap == 0 || out != nullptr, "recorder: no buffer to read into");
+        for (int i = 0; i < cap && i < (int)g_bwd_recs.size(); ++i) out[i] = g_bwd_recs[i];
+    } else L2S_REQUIRE(false, "recorder: cmd is 0 (disarm), 1 (clear and arm) or 2 (read)");
+    if (count) *count = (int)g_bwd_recs.size();
+    return 0;
+}
+#endif
+
 static bool bwd_vec_ok(const BwdGemmP& p) {
     bool vec = al16(p.A) && al16(p.B) && p.lda % 4 == 0 && p.ldb % 4 == 0;
     if (p.mode == BWD_DX) vec = vec && p.Nout % 4 == 0 && p.N % 4 == 0 && p.Cin % 4 == 0;
@@ -223,6 +274,9 @@ int launch_gemm_bwd(const BwdGemmP& p, hipStream_t s, const char* name) {
            else { if (vec) L2S_BWD_LAUNCH(BWD_DW, false, true); else L2S_BWD_LAUNCH(BWD_DW, false, false); } }
 #undef L2S_BWD_LAUNCH
     L2S_CHECK_HIP(hipGetLastError());
+#ifdef L2S_DIAG
+    if (!tl_bwd_inner) bwd_record(tl_bwd_entry, tl_bwd_asked, p.ksplit > 1 ? p.ksplit : 1, vec, p, nullptr, name);
+#endif
     return 0;
 }
 
@@ -248,6 +302,13 @@ int64_t gemm_bwd_splitk_floats(const BwdGemmP& p, int splits) { return (int64_t)
 int launch_gemm_bwd_splitk(const BwdGemmP& p, int splits, float* partials, hipStream_t s, const char* name) {
     L2S_REQUIRE(p.c_T == 0, "split-K: plain row-major output only");
     const int nkt = (p.K + TK - 1) / TK;
+#ifdef L2S_DIAG
+    struct BwdEntryScope {      // the record of the launch below names this entry and the slices it was asked for
+        BwdEntryScope(int asked, bool inner) { tl_bwd_entry = 1; tl_bwd_asked = asked; tl_bwd_inner = inner; }
+        ~BwdEntryScope() { tl_bwd_entry = 0; tl_bwd_asked = 0; tl_bwd_inner = false; }
+    } entry_scope(splits, std::min(splits, nkt) > 1);
+    const int splits_asked = splits;
+#endif
     if (splits > nkt) splits = nkt;
     if (splits <= 1) return launch_gemm_bwd(p, s, name);
     BwdGemmP q = p;
@@ -257,12 +318,18 @@ int launch_gemm_bwd_splitk(const BwdGemmP& p, int splits, float* partials, hipSt
     hipLaunchKernelGGL(reduce_splits_kernel, dim3((unsigned)std::min<int64_t>((total + 255) / 256, 4096)), dim3(256), 0, s, partials, splits, q.c_split_stride, p.M, p.N,
                        p.N, p.C, p.ldc, p.accumulate);
     L2S_CHECK_HIP(hipGetLastError());
+#ifdef L2S_DIAG
+    bwd_record(1, splits_asked, splits, bwd_vec_ok(p), p, nullptr, name);
+#endif
     return 0;
 }
 
 int launch_gemm_bwd_dw_dx(const BwdGemmP& pdw, int splits, float* partials, const BwdGemmP& pdx, hipStream_t s, const char* name) {
     L2S_REQUIRE(pdw.mode == BWD_DW && pdx.mode == BWD_DX && pdw.c_T == 0 && pdx.ksplit <= 1 && pdw.taps == 1 && pdx.taps == 1, "dW + dX pair: 1x1 layers, plain outputs");
     const int nkt = (pdw.K + TK - 1) / TK;
+#ifdef L2S_DIAG
+    const int splits_asked = splits;
+#endif
     if (splits > nkt) splits = nkt;
     if (splits < 1) splits = 1;
     BwdGemmP qw = pdw, qx = pdx;
@@ -285,6 +352,9 @@ int launch_gemm_bwd_dw_dx(const BwdGemmP& pdw, int splits, float* partials, cons
                            pdw.N, pdw.N, pdw.C, pdw.ldc, pdw.accumulate);
     }
     L2S_CHECK_HIP(hipGetLastError());
+#ifdef L2S_DIAG
+    bwd_record(2, splits_asked, splits, vec, pdw, &pdx, name);
+#endif
     return 0;
 }
 

@@ -1659,6 +1659,35 @@ int l2s_op_conv1d_bwd(const float* dZ, const float* X, const float* Wp, float* d
     if (dWp && launch_gemm_bwd(bwd_dw(dZ, Cout, X, Cin, dWp, B, Tout, Tin, Cout, Cin, taps, stride, pad, false), (hipStream_t)stream, "op_conv1d_dw")) return 1;
     return 0;
 }
+// one backward GEMM through the launch functions of gemm_bwd.hip: the descriptor's integers go into a BwdGemmP as they stand - the vec rule, the slice
+// clipping and every refusal are the launch functions' own
+static BwdGemmP bwd_from_desc(const l2s_gemm_bwd_desc& d, const float* A, const float* B, float* C) {
+    BwdGemmP p{};
+    p.mode = d.mode; p.A = A; p.lda = d.lda; p.B = B; p.ldb = d.ldb; p.C = C; p.ldc = d.ldc; p.M = d.M; p.N = d.N; p.K = d.K;
+    p.Tx = d.Tx; p.Tz = d.Tz; p.taps = d.taps; p.stride = d.stride; p.pad = d.pad; p.padp = d.padp; p.Nout = d.Nout; p.Cin = d.Cin;
+    p.c_T = d.c_T; p.c_seq_stride = d.c_seq_stride; p.alpha = d.alpha; p.accumulate = d.accumulate;
+    return p;
+}
+int l2s_op_gemm_bwd(const l2s_gemm_bwd_desc* d, const float* A, const float* B, float* C, const l2s_gemm_bwd_desc* d2, const float* A2, const float* B2,
+                    float* C2, int splits, float* partials, int bf16, l2s_gemm_bwd_record* ran, void* stream) {
+    if (ran) std::memset(ran, 0, sizeof *ran);
+    L2S_REQUIRE(d && A && B && C && (d->mode == BWD_DX || d->mode == BWD_DW) && (!d2 || (A2 && B2 && C2)) && splits >= 0, "bad arguments");
+    L2S_REQUIRE(d->Tx > 0 && d->Tz > 0 && d->taps > 0 && d->Nout > 0 && d->Cin > 0 && (!d2 || (d2->Tx > 0 && d2->Tz > 0 && d2->taps > 0 && d2->Nout > 0 && d2->Cin > 0)),
+                "bad descriptor");
+    Bf16Scope bf16scope(bf16 ? 1 : 0);
+    gemm_bwd_clear_last_record();
+    const BwdGemmP p = bwd_from_desc(*d, A, B, C);
+    // the partial matrices a split writes: [slices after clipping][M][N] floats
+    const int nkt = (d->K + 31) / 32;
+    L2S_REQUIRE(std::min(splits, nkt) <= 1 || partials, "split-K needs a partials buffer");
+    int rc;
+    if (d2) rc = launch_gemm_bwd_dw_dx(p, splits, partials, bwd_from_desc(*d2, A2, B2, C2), (hipStream_t)stream, "op_gemm_bwd_dw_dx");
+    else if (splits >= 1) rc = launch_gemm_bwd_splitk(p, splits, partials, (hipStream_t)stream, "op_gemm_bwd_splitk");
+    else rc = launch_gemm_bwd(p, (hipStream_t)stream, "op_gemm_bwd");
+    if (ran) *ran = gemm_bwd_last_record();
+    return rc;
+}
+int l2s_op_gemm_bwd_recorder(int cmd, l2s_gemm_bwd_record* out, int cap, int* count) { return gemm_bwd_recorder(cmd, out, cap, count); }
 int l2s_op_frontend(l2s_model* m, const float* video, int B, int T, int H, int W, float* out, void* stream) {
     L2S_ENC_READY(m);
     FrontendW fe = m->w.fe;

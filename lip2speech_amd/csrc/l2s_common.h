@@ -10,6 +10,9 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 struct l2s_resize_job;      // include/l2s.h
+#ifdef L2S_DIAG
+struct l2s_gemm_bwd_record; // include/l2s_diag.h
+#endif
 
 namespace l2s {
 
@@ -220,6 +223,11 @@ int64_t gemm_bwd_splitk_floats(const BwdGemmP& p, int splits);
 int launch_gemm_bwd_splitk(const BwdGemmP& p, int splits, float* partials, hipStream_t s, const char* name);
 // weight gradient (split-K as above) and input gradient of one 1x1 layer in ONE launch (they share dZ and are independent)
 int launch_gemm_bwd_dw_dx(const BwdGemmP& pdw, int splits, float* partials, const BwdGemmP& pdx, hipStream_t s, const char* name);
+#ifdef L2S_DIAG      // launch recorder of the three functions above (include/l2s_diag.h l2s_gemm_bwd_record): host code of libl2s_diag.so only
+const ::l2s_gemm_bwd_record& gemm_bwd_last_record();      // what the calling thread's last launch ran; zeroes after gemm_bwd_clear_last_record
+void gemm_bwd_clear_last_record();
+int gemm_bwd_recorder(int cmd, ::l2s_gemm_bwd_record* out, int cap, int* count);
+#endif
 
 // Backward of a fused GEMM epilogue  y = act(z) [+ residual],  z = conv * s + shift  (s, shift = eval-mode BatchNorm and/or bias):
 //   dpre = dy * act'(z);  dconv = dpre * s;  per-column sums  r0 = sum dpre,  r1 = sum dpre * (z - beta)/gamma,

@@ -52,6 +52,7 @@ ABI_SYMBOLS = (
 DIAG_SYMBOLS = (
     "l2s_op_gemm", "l2s_op_conv1d", "l2s_op_gemm_ex", "l2s_op_conv1d_ex", "l2s_op_conv1d_bwd", "l2s_op_frontend", "l2s_op_launch_chain", "l2s_op_launch_chain2", "l2s_op_skinny_timeline", "l2s_op_attn_timeline", "l2s_op_flat_timeline", "l2s_op_pdecode_timeline", "l2s_op_gemm_x3_timeline", "l2s_op_fused_unit_timeline", "l2s_op_lstm_cell_chain", "l2s_op_step_attn_chain", "l2s_op_stamp_log", "l2s_op_skinny_form", "l2s_op_step_site", "l2s_op_skinny",
     "l2s_op_face_conv2d", "l2s_op_face_taps", "l2s_op_speaker_taps", "l2s_op_speaker_taps_packed", "l2s_op_encoder_taps",
+    "l2s_op_gemm_bwd", "l2s_op_gemm_bwd_recorder",
 )
 
 # run-time options only the diagnostic build accepts (block-form A/B switches of the same arithmetic, include/l2s_diag.h)
@@ -79,7 +80,22 @@ class SkinnyGroup(ctypes.Structure):
                 + [(k, ctypes.c_int32) for k in ("ntiles", "epi", "N", "act", "ldo", "ld_add", "H", "h_out_K", "h_out_off", "ld_hplain")])
 
 
-RESIZE_MOUTH, RESIZE_FACE = 0, 1         # L2S_RESIZE_MOUTH / L2S_RESIZE_FACE
+GEMM_BWD_INTS = ("mode", "M", "N", "K", "lda", "ldb", "ldc", "Tx", "Tz", "taps", "stride", "pad", "padp", "Nout", "Cin", "c_T", "accumulate")
+BWD_DX, BWD_DW = 0, 1                     # BwdMode of l2s_common.h
+
+
+class GemmBwdDesc(ctypes.Structure):
+    """`l2s_gemm_bwd_desc` (include/l2s_diag.h): the integers of one backward-GEMM descriptor - the 64-bit field, the 32-bit integers, alpha"""
+    _fields_ = [("c_seq_stride", _i64)] + [(k, ctypes.c_int32) for k in GEMM_BWD_INTS] + [("alpha", ctypes.c_float)]
+
+
+class GemmBwdRecord(ctypes.Structure):
+    """`l2s_gemm_bwd_record` (include/l2s_diag.h): what one call of a launch function of gemm_bwd.hip ran"""
+    _fields_ = ([("d", GemmBwdDesc * 2)] + [(k, ctypes.c_int32) for k in ("entry", "splits_asked", "splits", "vec", "bf16", "pair")]
+                + [("align", (ctypes.c_int32 * 3) * 2), ("name", ctypes.c_char * 40)])
+
+
+RESIZE_MOUTH, RESIZE_FACE = 0, 1        # L2S_RESIZE_MOUTH / L2S_RESIZE_FACE
 RESIZE_JOBS_PER_LAUNCH = 240              # L2S_RESIZE_JOBS_PER_LAUNCH: output slots whose table one launch carries in its kernel arguments
 
 
@@ -279,6 +295,8 @@ def _bind_diag(L: ctypes.CDLL) -> None:
     L.l2s_op_speaker_taps.argtypes = [_vp, _fp, _i, _i, _vp, _fp, _vp, _i64, _vp]
     L.l2s_op_speaker_taps_packed.argtypes = [_vp, _fp, ctypes.POINTER(_i64), ctypes.POINTER(_i64), _i, _vp, _fp, _vp, _i64, _vp]
     L.l2s_op_encoder_taps.argtypes = [_vp, _fp, _i, _i, _i, _i, _vp, _fp, _vp, _i64, _vp]
+    L.l2s_op_gemm_bwd.argtypes = [ctypes.POINTER(GemmBwdDesc), _fp, _fp, _fp, ctypes.POINTER(GemmBwdDesc), _fp, _fp, _fp, _i, _fp, _i, ctypes.POINTER(GemmBwdRecord), _vp]
+    L.l2s_op_gemm_bwd_recorder.argtypes = [_i, ctypes.POINTER(GemmBwdRecord), _i, ctypes.POINTER(_i)]
 
 
 def check(rc: int, L: Optional[ctypes.CDLL] = None) -> None:
@@ -1430,6 +1448,68 @@ def op_conv1d_bwd(dZ, X, Wp, taps=1, stride=1, pad=0, want_dx=True):
     dW = torch.empty_like(Wp)
     _dcheck(diag().l2s_op_conv1d_bwd(_ptr(dZ), _ptr(X), _ptr(Wp), _ptr(dX), _ptr(dW), B, Tin, Cin, Cout, taps, stride, pad, _stream()))
     return dX, dW
+
+
+def gemm_bwd_desc(**fields) -> GemmBwdDesc:
+    """A `GemmBwdDesc` from keyword integers (GEMM_BWD_INTS, c_seq_stride, alpha); alpha defaults to 1, every integer to 0"""
+    d = GemmBwdDesc()
+    d.alpha = 1.0
+    for k, v in fields.items():
+        assert k in GEMM_BWD_INTS or k in ("c_seq_stride", "alpha"), k
+        setattr(d, k, v)
+    return d
+
+
+def gemm_bwd_record_dict(r: GemmBwdRecord) -> dict:
+    """One launch record as plain Python: "d" (and, for a pair, "d2"): {field: value} of the descriptors, "align" / "align2": (A, B, C) addresses modulo
+    16 bytes, "entry" (0 launch_gemm_bwd, 1 launch_gemm_bwd_splitk, 2 launch_gemm_bwd_dw_dx), "splits_asked", "splits", "vec", "bf16", "pair" and "name" (the launch's profile name)"""
+    def desc(d):
+        out = {k: int(getattr(d, k)) for k in GEMM_BWD_INTS + ("c_seq_stride",)}
+        out["alpha"] = float(d.alpha)
+        return out
+    out = {k: int(getattr(r, k)) for k in ("entry", "splits_asked", "splits", "vec", "bf16", "pair")}
+    out.update(d=desc(r.d[0]), align=tuple(int(a) for a in r.align[0]), name=r.name.decode("utf-8", "replace"))
+    if out["pair"]:
+        out.update(d2=desc(r.d[1]), align2=tuple(int(a) for a in r.align[1]))
+    return out
+
+
+def _addr(t) -> Optional[int]:
+    return t if t is None or isinstance(t, int) else _ptr(t)
+
+
+def op_gemm_bwd(d: GemmBwdDesc, A, B, C, splits: int = 0, partials=None, bf16: bool = False, pair=None, refused: Optional[list] = None) -> dict:
+    """One backward GEMM through `l2s_op_gemm_bwd` (diagnostic library): descriptor `d` on the device operands A, B, C - tensors, or integer device
+    addresses where an operand starts inside a larger buffer.  splits = 0: launch_gemm_bwd; splits >= 1: launch_gemm_bwd_splitk with `partials`
+    (splits * M * N floats); pair = (d2, A2, B2, C2): launch_gemm_bwd_dw_dx with d the DW half and the pair the DX half.  Returns the record of what ran
+    (`gemm_bwd_record_dict`).  A refused launch raises RuntimeError with the library's text - or, with `refused` a list, appends the text to it."""
+    D = diag()
+    ran = GemmBwdRecord()
+    d2, A2, B2, C2 = pair if pair is not None else (None, None, None, None)
+    rc = D.l2s_op_gemm_bwd(ctypes.byref(d), _addr(A), _addr(B), _addr(C), ctypes.byref(d2) if d2 is not None else None, _addr(A2), _addr(B2), _addr(C2),
+                           int(splits), _addr(partials), 1 if bf16 else 0, ctypes.byref(ran), _stream())
+    if rc != 0:
+        text = D.l2s_last_error().decode("utf-8", "replace")
+        if refused is None:
+            raise RuntimeError("libl2s_diag: " + text)
+        refused.append(text)
+    return gemm_bwd_record_dict(ran)
+
+
+def gemm_bwd_recorder_arm() -> None:
+    """Forget the recorded backward-GEMM launches and record from now on: every call of launch_gemm_bwd / _splitk / _dw_dx made through the diagnostic
+    library, by any entry point (a model bound to `diag()` included)"""
+    _dcheck(diag().l2s_op_gemm_bwd_recorder(1, None, 0, None))
+
+
+def gemm_bwd_recorder_read(disarm: bool = True) -> list:
+    """The records since `gemm_bwd_recorder_arm`, in launch order, as `gemm_bwd_record_dict` dicts; disarms the recorder first unless told not to"""
+    D = diag()
+    n = _i(0)
+    _dcheck(D.l2s_op_gemm_bwd_recorder(0 if disarm else 2, None, 0, ctypes.byref(n)))
+    arr = (GemmBwdRecord * max(1, n.value))()
+    _dcheck(D.l2s_op_gemm_bwd_recorder(2, arr, n.value, ctypes.byref(n)))
+    return [gemm_bwd_record_dict(arr[i]) for i in range(min(n.value, len(arr)))]
 
 
 # ---------------------------------------------------------------------------------------------- profiling
