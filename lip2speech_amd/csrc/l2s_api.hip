@@ -9,6 +9,7 @@
 #include "l2s_model.h"
 #include "pdecode.h"
 #include "decode_step.h"
+#include "decoder_stages.h"
 
 #include <algorithm>
 #include <cmath>
@@ -185,14 +186,6 @@ static int64_t postnet_ws_floats(int B, int S) { return (int64_t)B * S * 512 * (
 
 // ------------------------------------------------------------------------------------------------ encoder
 
-static GemmP pw_gemm(const float* A, int lda, int a_off, const ConvW& c, float* C, int ldc, int c_off, int cstride,
-                     int64_t M, int N, int K, int act) {
-    GemmP p = gemm_plain(A + a_off, lda, c.W, C + c_off, ldc, (int)M, N, K);
-    p.scale = c.scale; p.shift = c.shift; p.actw = c.actw; p.act = act; p.c_cstride = cstride;
-    p.W3 = c.W3;
-    return p;
-}
-
 static FrameSrc frame_src(const float* video, int B) { FrameSrc f{}; f.p[0] = video; f.per = B; return f; }
 
 // rg (a ragged group, l2s_inference_ragged): the front-end and the trunk run on the rg->NF real frames of the group's clips, compact; vis comes out as
@@ -327,16 +320,6 @@ static int encoder_run(l2s_model* m, const FrameSrc& video, int B, int T, int H,
 }
 
 // ------------------------------------------------------------------------------------------------ decoder prologue
-static GemmP conv_gemm(const float* X, int lda, int B, int Tin, int Cin, const ConvW& c, int Cout, int taps, int stride, int pad,
-                       float* out, int ldc, int act) {
-    const int Tout = (Tin + 2 * pad - taps) / stride + 1;
-    GemmP p = gemm_plain(X, lda, c.W, out, ldc, B * Tout, Cout, taps * Cin);
-    p.Tout = Tout; p.Tin = Tin; p.taps = taps; p.stride = stride; p.pad = pad; p.Cin = Cin;
-    p.scale = c.scale; p.shift = c.shift; p.actw = c.actw; p.act = act;
-    p.W3 = c.W3;
-    return p;
-}
-
 // ---- per-clip video lengths (the *_masked entry points, include/l2s.h)
 static int check_lengths(const int32_t* video_lengths, int B, int T) {
     L2S_REQUIRE(video_lengths, "video_lengths is null");
@@ -374,29 +357,25 @@ static int prologue_run(l2s_model* m, const float* vis, const float* emb, const 
     Bf16Scope bf16scope(m->opt.infer_bf16);      // the bf16 leg: bf16-operand GEMM / Conv1d kernels instead of the f32 / split-bf16 ones
     const Weights& w = m->w;
     StateLayout sl = state_layout(B, T);
-    int L[4];
-    const int mT = content_lens(T, L);
+    ProBufs pb{};
+    int* const L = pb.L;
+    const int mT = pb.m = content_lens(T, L);
     L2S_REQUIRE(T >= 7 && T <= L2S_MAX_STEPS, "T must be in [7, 300] (Content.agg stride-7 branch; positional table)");
     const int BT = B * T, Bp = pad16(B);
     Bump bp(ws, ws_bytes);
-    float* gin = bp.f((int64_t)BT * 4096);
-    float* rnn = bp.f((int64_t)BT * 1024);
-    float* resid = bp.f((int64_t)BT * 512);
-    float* s_e = bp.f((int64_t)B * 512);
-    float* s_a = bp.f((int64_t)B * 512);
-    float* hf[2][2]; float* cf[2];
-    for (int d = 0; d < 2; ++d) { hf[d][0] = bp.f((int64_t)Bp * 512); hf[d][1] = bp.f((int64_t)Bp * 512); cf[d] = bp.f((int64_t)Bp * 512); }
-    float* cellcat = bp.f((int64_t)B * 1024);
-    float* cat = bp.f((int64_t)BT * 4608);
-    float* cmap[4];
-    for (int j = 0; j < 4; ++j) cmap[j] = bp.f((int64_t)B * L[j] * 512);
-    float* pooled = bp.f((int64_t)B * mT * 2560);
-    float* wv = bp.f((int64_t)B * mT * 256);
-    float* tA = bp.f((int64_t)B * mT * 256);
-    float* tB = bp.f((int64_t)B * mT * 256);
-    float* tC = bp.f((int64_t)B * mT * 256);
-    float* logits = bp.f((int64_t)B * mT * VOC);
-    float* z = bp.f((int64_t)B * mT * VOCP);
+    pb.gin = bp.f((int64_t)BT * 4096);
+    pb.rnn = bp.f((int64_t)BT * 1024);
+    pb.resid = bp.f((int64_t)BT * 512);
+    pb.s_e = bp.f((int64_t)B * 512);
+    pb.s_a = bp.f((int64_t)B * 512);
+    pro_carve_lstm(bp, B, pb);
+    pb.cellcat = bp.f((int64_t)B * 1024);
+    pb.cat = bp.f((int64_t)BT * 4608);
+    for (int j = 0; j < 4; ++j) pb.cmap[j] = bp.f((int64_t)B * L[j] * 512);
+    pb.pooled = bp.f((int64_t)B * mT * 2560);
+    for (float** t : {&pb.wv, &pb.tA, &pb.tB, &pb.tC}) *t = bp.f((int64_t)B * mT * 256);
+    pb.logits = bp.f((int64_t)B * mT * VOC);
+    pb.zsoft = bp.f((int64_t)B * mT * VOCP);
     float* part = bp.f(8 * std::max((int64_t)B * mT * 256, (int64_t)B * 512));
     int64_t tap_floats = 0;
     for (int j = 1; j < 4; ++j) tap_floats += (int64_t)CT_KS[j] * B * L[j] * 512;
@@ -410,38 +389,19 @@ static int prologue_run(l2s_model* m, const float* vis, const float* emb, const 
     float* pbx = pbi ? bp.f(pbilstm_ws_bytes() / 4 + 64) : nullptr;
     L2S_REQUIRE(!bp.overflow, "prologue workspace too small");
 
-    // residual_bottleneck, site embeddings
-    {
-        GemmP p = gemm_plain(vis, 1024, w.resid.W, resid, 512, BT, 512, 1024);
-        p.shift = w.resid.shift;
-        if (launch_gemm_splitk(p, 4, bott_part, s, "prologue_gemm")) return 1;          // 120 tiles: four K slices
-        GemmBatch gb{};
-        gb.p[0] = gemm_plain(emb, 256, w.enc_site.W, s_e, 512, B, 512, 256);
-        gb.p[0].shift = w.enc_site.shift; gb.p[0].act = ACT_PSINE; gb.p[0].actw = w.enc_site.actw;
-        gb.p[1] = gemm_plain(emb, 256, w.attn_site.W, s_a, 512, B, 512, 256);
-        gb.p[1].shift = w.attn_site.shift; gb.p[1].act = ACT_PSINE; gb.p[1].actw = w.attn_site.actw;
-        gb.count = 2;
-        if (launch_gemm(gb, s, "prologue_gemm")) return 1;
-    }
-    // BiLSTM input gates for both directions: (B*T,1024) x (1024,4096)
-    {
-        GemmP p = gemm_plain(vis, 1024, w.wih_cat, gin, 4096, BT, 4096, 1024);
-        p.shift = w.bih_cat;
-        if (m->opt.gemm_x3_dma) p.W3 = w.wih_cat3;
-        if (launch_gemm1(p, s, "bilstm_input_gemm")) return 1;
-    }
+    // every descriptor of this stage is built in decoder_stages.h; what follows picks the launcher of each and runs the masked and persistent branches
+    const Prologue pro{w, pb, state, sl, B, T, m->opt.gemm_x3_dma != 0};
+    // residual_bottleneck (120 tiles: four K slices), site embeddings, BiLSTM input gates
+    if (launch_gemm_splitk(pro.resid(vis), 4, bott_part, s, "prologue_gemm")) return 1;
+    if (launch_gemm(pro.sites(emb), s, "prologue_gemm")) return 1;
+    if (launch_gemm1(pro.bilstm_in(vis), s, "bilstm_input_gemm")) return 1;
     if (pbi) {
         PBiP q{};
-        q.Whh0 = w.whh[0].W; q.Whh1 = w.whh[1].W; q.gin = gin; q.s_e = s_e; q.rnn = rnn; q.h_state = state + sl.h; q.cellcat = cellcat; q.B = B; q.T = T;
+        q.Whh0 = w.whh[0].W; q.Whh1 = w.whh[1].W; q.gin = pb.gin; q.s_e = pb.s_e; q.rnn = pb.rnn; q.h_state = state + sl.h; q.cellcat = pb.cellcat; q.B = B; q.T = T;
         q.lens = lens.dev;      // masked: pair (direction, clip) runs its clip's own length; the masked steps below are those of the launch route
         if (launch_pbilstm(q, pbx, pbilstm_ws_bytes(), s)) return 1;
     } else {
-    // recurrence: h0 = c0 = s_e for both directions (decoder.py:386-389)
-    for (int d = 0; d < 2; ++d) {
-        if (launch_to_frag(s_e, 512, B, 512, hf[d][0], 512, 0, 0, s)) return 1;
-        if (launch_to_frag(s_e, 512, B, 512, cf[d], 512, 0, 0, s)) return 1;
-        if (launch_fill(hf[d][1], (int64_t)Bp * 512, 0.f, s)) return 1;
-    }
+    if (bilstm_start(pb, B, s)) return 1;
     std::vector<int> cap_steps, rst_steps;
     size_t cap_i = 0, rst_i = 0;
     if (lens) {
@@ -453,110 +413,50 @@ static int prologue_run(l2s_model* m, const float* vis, const float* emb, const 
         const int cur = step & 1, nxt = cur ^ 1;
         if (rst_i < rst_steps.size() && rst_steps[rst_i] == step) {      // backward rows whose clip ends at frame T-1-step start here, from s_e
             ++rst_i;
-            if (launch_bilstm_reset(hf[1][cur], cf[1], lens.dev, B, T - 1 - step, s_e, s)) return 1;
+            if (launch_bilstm_reset(pb.hf[1][cur], pb.cf[1], lens.dev, B, T - 1 - step, pb.s_e, s)) return 1;
         }
-        for (int d = 0; d < 2; ++d) bilstm_step_group(sb, d, w, true, B, T, d == 0 ? step : T - 1 - step, hf[d][cur], hf[d][nxt], cf[d], gin, rnn);
+        for (int d = 0; d < 2; ++d) bilstm_step_group(sb, d, w, true, B, T, d == 0 ? step : T - 1 - step, pb.hf[d][cur], pb.hf[d][nxt], pb.cf[d], pb.gin, pb.rnn);
         sb.count = 2;
         if (launch_skinny(sb, s, "bilstm_step", m->opt)) return 1;
         if (cap_i < cap_steps.size() && cap_steps[cap_i] == step) {      // forward rows whose clip ended at frame `step`: their finals, now
             ++cap_i;
-            if (launch_bilstm_capture(hf[0][nxt], cf[0], lens.dev, B, step, state + sl.h, cellcat, 1024, s)) return 1;
+            if (launch_bilstm_capture(pb.hf[0][nxt], pb.cf[0], lens.dev, B, step, state + sl.h, pb.cellcat, 1024, s)) return 1;
         }
     }
-    const int fin = T & 1;     // buffer holding the final hidden states
-    // decoder initial hidden = BiLSTM finals (fwd -> layer 0, bwd -> layer 1); kept in the state buffer as frag16
-    if (!lens) L2S_CHECK_HIP(hipMemcpyAsync(state + sl.h, hf[0][fin], sizeof(float) * Bp * 512, hipMemcpyDeviceToDevice, s));
-    L2S_CHECK_HIP(hipMemcpyAsync(state + sl.h + (int64_t)Bp * 512, hf[1][fin], sizeof(float) * Bp * 512, hipMemcpyDeviceToDevice, s));
-    // encoder_cell = E_C(cat(c_fwd, c_bwd))
-    if (!lens && launch_from_frag(cf[0], 512, B, 512, cellcat, 1024, 0, s)) return 1;
-    if (launch_from_frag(cf[1], 512, B, 512, cellcat, 1024, 512, s)) return 1;
+    if (bilstm_finals(pb, state, sl, B, T, !lens, s)) return 1;      // a masked call has captured the forward finals row by row
     }
-    {
-        GemmP p = gemm_plain(cellcat, 1024, w.e_c.W, state + sl.ecell, 512, B, 512, 1024);
-        p.shift = w.e_c.shift;
-        if (launch_gemm_splitk(p, 8, part, s, "prologue_gemm")) return 1;      // B rows x 512 columns = 8 tiles: split K = 1024 eight ways
-        if (launch_stop_const(state + sl.ecell, w.stop_tail, w.stop_bias, B, state + sl.stopc, s)) return 1;
-    }
+    // encoder_cell = E_C(cat(c_fwd, c_bwd)): B rows x 512 columns = 8 tiles: split K = 1024 eight ways
+    if (launch_gemm_splitk(pro.e_c(), 8, part, s, "prologue_gemm")) return 1;
+    if (launch_stop_const(state + sl.ecell, w.stop_tail, w.stop_bias, B, state + sl.stopc, s)) return 1;
     // enc = encoder_proj(rnn_out) + s_a (broadcast over T) + residual  -> cat[:, 0:512] and the state
-    {
-        GemmP p = gemm_plain(rnn, 1024, w.enc_proj.W, cat, 4608, BT, 512, 1024);
-        p.shift = w.enc_proj.shift;
-        p.R1 = resid; p.ldr1 = 512; p.r1_mod = 0;
-        p.R2 = s_a; p.ldr2 = 512; p.r2_div = T;     // attention_site embedding, broadcast over the T frames of a clip
-        if (launch_gemm_splitk(p, 4, bott_part, s, "prologue_gemm")) return 1;
-        // with lengths: rows t >= len_b become zeros on the way (the K / V convolutions below then read past a clip's end what a solo call reads as padding)
-        if (lens ? launch_mask_copy_rows(cat, 4608, state + sl.enc, 512, lens.dev, B, T, 512, s)
-                 : launch_copy_cols(cat, 4608, 0, state + sl.enc, 512, 0, 1, BT, 512, s)) return 1;
-    }
+    if (launch_gemm_splitk(pro.enc_proj(), 4, bott_part, s, "prologue_gemm")) return 1;
+    // with lengths: rows t >= len_b become zeros on the way (the K / V convolutions below then read past a clip's end what a solo call reads as padding)
+    if (lens ? launch_mask_copy_rows(pb.cat, PRO_CAT, state + sl.enc, 512, lens.dev, B, T, 512, s)
+             : launch_copy_cols(pb.cat, PRO_CAT, 0, state + sl.enc, 512, 0, 1, BT, 512, s)) return 1;
     // MultiHopConv branches of K and V (8 convs, one grouped launch), then the two bottlenecks (+PSine +pos)
     {
         // longest K first: the groups are dispatched in order, and the 11-tap convs (K = 5632) would otherwise start last and run alone
         GemmBatch gb{};
-        int g = 0;
         for (int j = 3; j >= 0; --j)
-            for (int kv = 0; kv < 2; ++kv)
-                gb.p[g++] = conv_gemm(cat, 4608, B, T, 512, w.mh_branch[kv][j], 512, MH_KS[j], 1, MH_KS[j] / 2,
-                                      cat + 512 + (kv * 4 + j) * 512, 4608, ACT_SILU);
-        gb.count = 8;
-        if (!m->opt.gemm_x3_dma) for (int i = 0; i < 8; ++i) gb.p[i].W3 = nullptr;
+            for (int kv = 0; kv < 2; ++kv) gb.p[gb.count++] = pro.mh_branch(kv, j);
         if (launch_gemm(gb, s, "multihop_conv_gemm")) return 1;
-        GemmBatch bb{};
-        for (int kv = 0; kv < 2; ++kv) {
-            GemmP p = gemm_plain(cat, 4608, w.mh_bott[kv].W, state + (kv == 0 ? sl.k : sl.v), 512, BT, 512, 2560);
-            if (kv == 1) { p.a_split = 512; p.a_gap = 2048; }     // V reads [x | V branches]
-            p.shift = w.mh_bott[kv].shift; p.act = ACT_PSINE; p.actw = w.mh_bott[kv].actw;
-            p.R1 = w.pos; p.ldr1 = 512; p.r1_mod = T;             // + pos_table[t]
-            bb.p[kv] = p;
-        }
-        bb.count = 2;
         // 2 x 120 tiles with K = 2560 is one block per CU and 80 dependent K iterations: four K slices each
-        if (launch_gemm_splitk_group(bb, 4, bott_part, s, "multihop_bottleneck_gemm")) return 1;
+        if (launch_gemm_splitk_group(pro.mh_bott(), 4, bott_part, s, "multihop_bottleneck_gemm")) return 1;
         // V' = V W_ap^T + b_ap: attention_proj (decoder.py:420) applied to the values once per clip instead of to a @ v at every step
-        if (w.vproj.W) {
-            GemmP p = gemm_plain(state + sl.v, 512, w.vproj.W, state + sl.vp, 256, BT, 256, 512);
-            p.shift = w.vproj.shift;
-            if (launch_gemm1(p, s, "prologue_gemm")) return 1;
-        }
+        if (w.vproj.W && launch_gemm1(pro.vproj(), s, "prologue_gemm")) return 1;
     }
     // Content.encode (decoder.py:239-260)
     {
-        GemmBatch gb{};
-        for (int j = 0; j < 4; ++j)      // K = 512 * ks is the same for every branch here; rows shrink with ks - largest map first
-            gb.p[j] = conv_gemm(cat, 4608, B, T, 512, w.ct_branch[j], 512, CT_KS[j], CT_KS[j], 0, cmap[j], 512, ACT_SILU);
-        gb.count = 4;
         // (4..29) x B rows by 512 columns: 16-120 tiles per branch with K up to 3584 - one slice per tap instead (16 slices, 472 tiles of K = 512)
-        if (launch_gemm_tapsplit(gb, tap_part, s, "content_agg_gemm")) return 1;
-        PoolCatP pc{};
-        pc.x[0] = cat; pc.L[0] = T; pc.ld[0] = 4608;
-        for (int j = 0; j < 4; ++j) { pc.x[j + 1] = cmap[j]; pc.L[j + 1] = L[j]; pc.ld[j + 1] = 512; }
-        pc.nmaps = 5; pc.B = B; pc.m = mT; pc.C = 512; pc.out = pooled;
-        if (lens) {
-            PoolDiv pd{};
-            pd.div[0] = 1;
-            for (int j = 0; j < 4; ++j) pd.div[j + 1] = CT_KS[j];
-            if (launch_pool_cat_masked(pc, pd, lens.dev, s)) return 1;
-        } else if (launch_pool_cat(pc, s)) return 1;
-        const int R = B * mT;
-        GemmP p = gemm_plain(pooled, 2560, w.ct_bott.W, wv, 256, R, 256, 2560);
-        p.shift = w.ct_bott.shift;
-        if (launch_gemm_splitk(p, 8, part, s, "content_gemm")) return 1;       // 4B rows x 256 columns = 8 tiles with K = 2560
-        GemmBatch g1{};
-        g1.p[0] = gemm_plain(wv, 256, w.ct_k0.W, tA, 256, R, 256, 256); g1.p[0].shift = w.ct_k0.shift; g1.p[0].act = ACT_SILU;
-        g1.p[1] = gemm_plain(wv, 256, w.ct_fc0.W, tB, 256, R, 256, 256); g1.p[1].shift = w.ct_fc0.shift; g1.p[1].act = ACT_SILU;
-        g1.count = 2;
-        if (launch_gemm(g1, s, "content_gemm")) return 1;
-        GemmBatch g2{};
-        g2.p[0] = gemm_plain(tA, 256, w.ct_k2.W, state + sl.ckey, 256, R, 256, 256); g2.p[0].shift = w.ct_k2.shift; g2.p[0].act = ACT_SILU;
-        g2.p[1] = gemm_plain(tB, 256, w.ct_fc2.W, tC, 256, R, 256, 256); g2.p[1].shift = w.ct_fc2.shift; g2.p[1].act = ACT_SILU;
-        g2.count = 2;
-        if (launch_gemm(g2, s, "content_gemm")) return 1;
-        GemmP p3 = gemm_plain(tC, 256, w.ct_fc4.W, logits, VOC, R, VOC, 256);
-        p3.shift = w.ct_fc4.shift; p3.act = ACT_SILU;
-        if (launch_gemm1(p3, s, "content_gemm")) return 1;
-        if (launch_gumbel_softmax(logits, gumbel, R, VOC, 0.1f, z, VOCP, content_dis, s)) return 1;
-        if (lens && launch_zero_slot_rows(z, VOCP, content_dis, VOC, B, mT, lens.dev, s)) return 1;      // slots i >= m_b: zero z (so zero values) and zero content_dis
-        GemmP p4 = gemm_plain(z, VOCP, w.ct_emb.W, state + sl.cval, 256, R, 256, VOCP);
-        if (launch_gemm1(p4, s, "content_gemm")) return 1;
+        if (launch_gemm_tapsplit(pro.ct_branches(), tap_part, s, "content_agg_gemm")) return 1;
+        if (lens ? launch_pool_cat_masked(pro.pool_cat(), pro.pool_div(), lens.dev, s) : launch_pool_cat(pro.pool_cat(), s)) return 1;
+        if (launch_gemm_splitk(pro.ct_bott(), 8, part, s, "content_gemm")) return 1;       // 4B rows x 256 columns = 8 tiles with K = 2560
+        if (launch_gemm(pro.ct_pair0(), s, "content_gemm")) return 1;
+        if (launch_gemm(pro.ct_pair2(), s, "content_gemm")) return 1;
+        if (launch_gemm1(pro.ct_fc4(), s, "content_gemm")) return 1;
+        if (launch_gumbel_softmax(pb.logits, gumbel, pro.R(), VOC, 0.1f, pb.zsoft, VOCP, content_dis, s)) return 1;
+        if (lens && launch_zero_slot_rows(pb.zsoft, VOCP, content_dis, VOC, B, mT, lens.dev, s)) return 1;      // slots i >= m_b: zero z (so zero values) and zero content_dis
+        if (launch_gemm1(pro.ct_emb(), s, "content_gemm")) return 1;
     }
     // decoder cell state starts at zero (decoder.py:406)
     if (launch_fill(state + sl.c, (int64_t)Bp * 512 * 2, 0.f, s)) return 1;
@@ -741,21 +641,15 @@ static int postnet_alloc(Bump& bp, int B, int S, PostBufs& pb) {
 // Layer i reads buffer i (mel for i = 0) and writes buffer i+1 (mel_post, channel-first, for i = 4).
 static int postnet_layer(const Weights& w, int layer, const float* mel, const PostBufs& pb, float* mel_post, int B, int S, int t0, int t1, hipStream_t s, bool dma_weights) {
     if (t1 <= t0) return 0;
-    float* const* bufs = pb.x;
-    const float* in = layer == 0 ? mel : bufs[layer - 1];
-    const int cin = layer == 0 ? NM : 512;
-    GemmP p = conv_gemm(in, cin, B, S, cin, w.post[layer], layer == 4 ? NM : 512, 5, 1, 2, layer == 4 ? mel_post : bufs[layer], layer == 4 ? NM : 512,
-                        layer == 4 ? ACT_NONE : ACT_PSINE);
-    p.M = B * (t1 - t0); p.Tout = t1 - t0; p.win_T = S; p.win_off = t0;
-    if (layer >= 1 && layer <= 3) { p.R1 = in; p.ldr1 = 512; p.r1_mod = 0; }
-    if (layer == 4) { p.R1 = mel; p.ldr1 = NM; p.r1_mod = 0; p.c_tr_T = S; }
-    if (!dma_weights) p.W3 = nullptr;
-    if (pb.part && t0 == 0 && t1 == S) {
-        p.win_T = 0; p.win_off = 0; p.W3 = nullptr;
+    const bool tapsplit = pb.part && t0 == 0 && t1 == S;
+    // the full-range descriptor is decoder_stages.h's; the weight planes go with the plain route only, and so does the time window
+    GemmP p = post_layer(w, layer, layer == 0 ? mel : pb.x[layer - 1], layer == 4 ? mel_post : pb.x[layer], mel, B, S, dma_weights && !tapsplit);
+    if (tapsplit) {
         GemmBatch gb{};
         gb.p[0] = p; gb.count = 1;
         return launch_gemm_tapsplit(gb, pb.part, s, "postnet_conv_gemm");
     }
+    p.M = B * (t1 - t0); p.Tout = t1 - t0; p.win_T = S; p.win_off = t0;
     return launch_gemm1(p, s, "postnet_conv_gemm");
 }
 

@@ -8,6 +8,7 @@
 #include "l2s_common.h"
 #include "l2s_model.h"
 #include "decode_step.h"
+#include "decoder_stages.h"
 
 #include <algorithm>
 
@@ -187,32 +188,36 @@ static BnLayer dec_bn_layer(const l2s_model* m, const std::string& bn_key, const
 // dropout masks of the post-net (decoder.py:152,154), channel-last like the activations: layers 0..3 (B*S,512) each, layer 4 (B*S,80)
 static const float* post_mask(const float* drop, int B, int S, int l) { return drop ? drop + (int64_t)l * B * S * 512 : nullptr; }
 
+// A conv group in front of batch-statistics BatchNorms: the statistics pass of the same convs (raw sums of group q to stats + q * stats_group, the
+// products parked at the Zout addresses), this batch's scale / shift of L[q] from rows[q] rows, then the fused epilogue over the parked products - not a
+// second conv
+static int launch_gemm_batch_stats(const l2s_model* m, GemmBatch gb, float* stats, int64_t stats_group, const BnLayer* L, const int* rows, hipStream_t s,
+                                   const char* stats_name, const char* epilogue_name) {
+    GemmBatch sb = gb;
+    for (int q = 0; q < gb.count; ++q) { sb.p[q].stats = stats + q * stats_group; sb.p[q].stats_raw = 1; sb.p[q].scale = nullptr; sb.p[q].shift = nullptr; }
+    if (launch_gemm(sb, s, stats_name)) return 1;
+    for (int q = 0; q < gb.count; ++q) {
+        if (bn_stats_finalize(stats + q * stats_group, (rows[q] + 63) / 64, 2 * L[q].C, rows[q], L[q], m->bn_momentum, s)) return 1;
+        gb.p[q].scale = L[q].scale; gb.p[q].shift = L[q].shift;
+    }
+    return launch_gemm_finish(gb, s, epilogue_name);
+}
+
 static int postnet_train_fwd(l2s_model* m, const float* mel, int B, int S, float* tape, float* mel_post, const float* drop, hipStream_t s) {
-    const Weights& w = m->w;
     PostTape t = post_tape(tape, B, S);
     for (int l = 0; l < 5; ++l) {
-        const float* in = l == 0 ? mel : t.x[l - 1];
-        const int cin = l == 0 ? NM_ : 512, cout = l == 4 ? NM_ : 512;
-        GemmP p = gemm_plain(in, cin, w.post[l].W, l == 4 ? mel_post : t.x[l], cout, B * S, cout, 5 * cin);
-        p.Tout = S; p.Tin = S; p.taps = 5; p.stride = 1; p.pad = 2; p.Cin = cin;
-        p.scale = w.post[l].scale; p.shift = w.post[l].shift;
+        // the layer is inference's (decoder_stages.h) on the f32 weights; the tape store and the dropout mask are laid over it
+        GemmBatch gb{};
+        GemmP& p = gb.p[0] = post_layer(m->w, l, l == 0 ? mel : t.x[l - 1], l == 4 ? mel_post : t.x[l], mel, B, S);
+        gb.count = 1;
         p.Zout = t.z[l];
-        if (l < 4) { p.act = ACT_PSINE; p.actw = w.post[l].actw; }
-        if (l >= 1 && l <= 3) { p.R1 = in; p.ldr1 = 512; }
-        if (l == 4) { p.R1 = mel; p.ldr1 = NM_; p.c_tr_T = S; }
-        p.mask = post_mask(drop, B, S, l); p.ldmask = cout; p.mask_pre = l == 4;     // the mel residual is added outside the Postnet module
-        if (m->bn_batch) {                     // batch statistics: stats pass of the same conv, then this batch's scale/shift in the fused epilogue
+        p.mask = post_mask(drop, B, S, l); p.ldmask = p.N; p.mask_pre = l == 4;     // the mel residual is added outside the Postnet module
+        if (m->bn_batch) {
             const std::string c = "decoder.postnet.convolutions." + std::to_string(l);
-            GemmP q = p; q.stats = t.stats; q.stats_raw = 1; q.scale = nullptr; q.shift = nullptr;
-            if (launch_gemm1(q, s, "train_postnet_conv_stats")) return 1;
-            BnLayer L = dec_bn_layer(m, c + ".1", c + ".0.conv.bias", t.bn + l * 1024, cout);
-            if (bn_stats_finalize(t.stats, (B * S + 63) / 64, 2 * cout, (int64_t)B * S, L, m->bn_momentum, s)) return 1;
-            p.scale = L.scale; p.shift = L.shift;
-            GemmBatch fb{}; fb.p[0] = p; fb.count = 1;          // the product is parked at z_l: the epilogue runs over it, not a second conv
-            if (launch_gemm_finish(fb, s, "train_postnet_conv_epilogue")) return 1;
-            continue;
-        }
-        if (launch_gemm1(p, s, "train_postnet_conv_gemm")) return 1;
+            const BnLayer L = dec_bn_layer(m, c + ".1", c + ".0.conv.bias", t.bn + l * 1024, p.N);
+            const int rows = B * S;
+            if (launch_gemm_batch_stats(m, gb, t.stats, 0, &L, &rows, s, "train_postnet_conv_stats", "train_postnet_conv_epilogue")) return 1;
+        } else if (launch_gemm(gb, s, "train_postnet_conv_gemm")) return 1;
     }
     return 0;
 }
@@ -1034,20 +1039,15 @@ static int decode_train_bwd(l2s_model* m, float* state, int B, int T, int S, con
 // =====================================================================================================================
 namespace l2s {
 
-struct ProTape {
-    float *resid, *z_se, *s_e, *z_sa, *s_a;                 // (BT,512), (B,512) x 4
-    float *gin;                                             // (BT,4096) BiLSTM input gates (both directions)
-    float *rnn;                                             // (B,T,1024) BiLSTM outputs
+struct ProTape : ProBufs {                                  // the activations both prologues have (decoder_stages.h; hf / cf come from the workspace), and:
+    float *z_se, *z_sa;                                     // (B,512) pre-PSine site embeddings
     float *gates[2], *cproc[2], *hproc[2];                  // per direction, in processing order: (T,B,2048), (T+1,B,512), (T+1,B,512)
-    float *cellcat;                                         // (B,1024)
-    float *cat;                                             // (BT,4608) [x | K branches | V branches] (post-activation)
     float *zcat;                                            // (BT,4608): pre-SiLU (post-BN) of the 8 MultiHop branches, same columns as cat
     float *zkv[2];                                          // (BT,512) pre-PSine bottleneck outputs
-    float *zagg[4], *cmap[4];                               // (B*L_j,512)
-    float *pooled, *wv, *zk0, *tA, *zk2, *zf0, *tB, *zf2, *tC, *zf4, *logits, *zsoft, *dis;
+    float *zagg[4];                                         // (B*L_j,512)
+    float *zk0, *zk2, *zf0, *zf2, *zf4, *dis;
     float* bn;                                              // batch-statistics BatchNorm: (scale, shift) of the 8 MultiHop + 4 content branches, 1024 floats each
     float* stats; int64_t stats_group;                      // statistics scratch: one region of stats_group floats per grouped conv
-    int L[4], m;
 };
 static int64_t pro_tape_floats(int B, int T) {
     int L[4]; const int m = content_lens(T, L);
@@ -1078,19 +1078,6 @@ static ProTape pro_tape(float* base, int B, int T) {
     return t;
 }
 
-static GemmP tconv(const float* X, int lda, int B, int Tin, int Cin, const ConvW& c, int Cout, int taps, int stride, int pad, float* out, int ldc, int act, float* zout) {
-    const int Tout = (Tin + 2 * pad - taps) / stride + 1;
-    GemmP p = gemm_plain(X, lda, c.W, out, ldc, B * Tout, Cout, taps * Cin);
-    p.Tout = Tout; p.Tin = Tin; p.taps = taps; p.stride = stride; p.pad = pad; p.Cin = Cin;
-    p.scale = c.scale; p.shift = c.shift; p.actw = c.actw; p.act = act; p.Zout = zout;
-    return p;
-}
-static GemmP tlin(const float* A, int lda, const ConvW& c, float* out, int ldc, int M, int N, int K, int act, float* zout) {
-    GemmP p = gemm_plain(A, lda, c.W, out, ldc, M, N, K);
-    p.shift = c.shift; p.actw = c.actw; p.act = act; p.Zout = zout;
-    return p;
-}
-
 static int64_t pro_fwd_ws_floats(int B) { return (int64_t)pad16(B) * 512 * 6 + 64 * 8; }
 
 static int prologue_train_fwd(l2s_model* m, const float* vis, const float* emb, const float* gumbel, int B, int T, float* state, float* content_dis,
@@ -1101,24 +1088,20 @@ static int prologue_train_fwd(l2s_model* m, const float* vis, const float* emb, 
     L2S_REQUIRE(T >= 7 && T <= L2S_MAX_STEPS, "T must be in [7, 300]");
     const int BT = B * T, Bp = pad16(B), R = B * tp.m;
     Bump bp(ws, ws_bytes);
-    float* hf[2][2]; float* cf[2];
-    for (int d = 0; d < 2; ++d) { hf[d][0] = bp.f((int64_t)Bp * 512); hf[d][1] = bp.f((int64_t)Bp * 512); cf[d] = bp.f((int64_t)Bp * 512); }
+    pro_carve_lstm(bp, B, tp);
     L2S_REQUIRE(!bp.overflow, "training prologue workspace too small");
+    // the launches are those of inference (decoder_stages.h) on the f32 weights, each as ONE plain launch; laid over them: the Zout tape stores, the
+    // tape of the recurrence and the batch-statistics path of the two conv groups
+    const Prologue pro{w, tp, state, sl, B, T, false};
+    if (launch_gemm1(pro.resid(vis), s, "train_prologue_gemm")) return 1;
     {
-        GemmP p = gemm_plain(vis, 1024, w.resid.W, tp.resid, 512, BT, 512, 1024); p.shift = w.resid.shift;
-        if (launch_gemm1(p, s, "train_prologue_gemm")) return 1;
-        GemmBatch gb{};
-        gb.p[0] = tlin(emb, 256, w.enc_site, tp.s_e, 512, B, 512, 256, ACT_PSINE, tp.z_se);
-        gb.p[1] = tlin(emb, 256, w.attn_site, tp.s_a, 512, B, 512, 256, ACT_PSINE, tp.z_sa);
-        gb.count = 2;
+        GemmBatch gb = pro.sites(emb);
+        gb.p[0].Zout = tp.z_se; gb.p[1].Zout = tp.z_sa;
         if (launch_gemm(gb, s, "train_prologue_gemm")) return 1;
-        GemmP g = gemm_plain(vis, 1024, w.wih_cat, tp.gin, 4096, BT, 4096, 1024); g.shift = w.bih_cat;
-        if (launch_gemm1(g, s, "train_bilstm_input_gemm")) return 1;
     }
+    if (launch_gemm1(pro.bilstm_in(vis), s, "train_bilstm_input_gemm")) return 1;
+    if (bilstm_start(tp, B, s)) return 1;
     for (int d = 0; d < 2; ++d) {
-        if (launch_to_frag(tp.s_e, 512, B, 512, hf[d][0], 512, 0, 0, s)) return 1;
-        if (launch_to_frag(tp.s_e, 512, B, 512, cf[d], 512, 0, 0, s)) return 1;
-        if (launch_fill(hf[d][1], (int64_t)Bp * 512, 0.f, s)) return 1;
         L2S_CHECK_HIP(hipMemcpyAsync(tp.hproc[d], tp.s_e, sizeof(float) * B * 512, hipMemcpyDeviceToDevice, s));
         L2S_CHECK_HIP(hipMemcpyAsync(tp.cproc[d], tp.s_e, sizeof(float) * B * 512, hipMemcpyDeviceToDevice, s));
     }
@@ -1126,7 +1109,7 @@ static int prologue_train_fwd(l2s_model* m, const float* vis, const float* emb, 
         SkinnyBatch sb{}; TrainSkinnyBatch tb{};
         const int cur = step & 1, nxt = cur ^ 1;
         for (int d = 0; d < 2; ++d) {
-            bilstm_step_group(sb, d, w, false, B, T, d == 0 ? step : T - 1 - step, hf[d][cur], hf[d][nxt], cf[d], tp.gin, tp.rnn);
+            bilstm_step_group(sb, d, w, false, B, T, d == 0 ? step : T - 1 - step, tp.hf[d][cur], tp.hf[d][nxt], tp.cf[d], tp.gin, tp.rnn);
             sb.p[d].h_plain = tp.hproc[d] + (int64_t)(step + 1) * B * 512; sb.p[d].ld_hplain = 512;
             tb.t[d].gates = tp.gates[d] + (int64_t)step * B * 2048; tb.t[d].ld_gates = 2048;
             tb.t[d].c_new = tp.cproc[d] + (int64_t)(step + 1) * B * 512; tb.t[d].ld_c = 512;
@@ -1134,88 +1117,49 @@ static int prologue_train_fwd(l2s_model* m, const float* vis, const float* emb, 
         sb.count = 2;
         if (launch_train_skinny(sb, tb, s, "train_bilstm_step")) return 1;
     }
-    const int fin = T & 1;
-    L2S_CHECK_HIP(hipMemcpyAsync(state + sl.h, hf[0][fin], sizeof(float) * Bp * 512, hipMemcpyDeviceToDevice, s));
-    L2S_CHECK_HIP(hipMemcpyAsync(state + sl.h + (int64_t)Bp * 512, hf[1][fin], sizeof(float) * Bp * 512, hipMemcpyDeviceToDevice, s));
-    if (launch_from_frag(cf[0], 512, B, 512, tp.cellcat, 1024, 0, s)) return 1;
-    if (launch_from_frag(cf[1], 512, B, 512, tp.cellcat, 1024, 512, s)) return 1;
-    {
-        GemmP p = gemm_plain(tp.cellcat, 1024, w.e_c.W, state + sl.ecell, 512, B, 512, 1024); p.shift = w.e_c.shift;
-        if (launch_gemm1(p, s, "train_prologue_gemm")) return 1;
-        if (launch_stop_const(state + sl.ecell, w.stop_tail, w.stop_bias, B, state + sl.stopc, s)) return 1;
-        GemmP e = gemm_plain(tp.rnn, 1024, w.enc_proj.W, tp.cat, 4608, BT, 512, 1024);
-        e.shift = w.enc_proj.shift; e.R1 = tp.resid; e.ldr1 = 512; e.R2 = tp.s_a; e.ldr2 = 512; e.r2_div = T;
-        if (launch_gemm1(e, s, "train_prologue_gemm")) return 1;
-        if (launch_copy_cols(tp.cat, 4608, 0, state + sl.enc, 512, 0, 1, BT, 512, s)) return 1;
-    }
+    if (bilstm_finals(tp, state, sl, B, T, true, s)) return 1;
+    if (launch_gemm1(pro.e_c(), s, "train_prologue_gemm")) return 1;
+    if (launch_stop_const(state + sl.ecell, w.stop_tail, w.stop_bias, B, state + sl.stopc, s)) return 1;
+    if (launch_gemm1(pro.enc_proj(), s, "train_prologue_gemm")) return 1;
+    if (launch_copy_cols(tp.cat, PRO_CAT, 0, state + sl.enc, 512, 0, 1, BT, 512, s)) return 1;
+    BnLayer bn[8]; int rows[8];
     {
         GemmBatch gb{};
-        for (int kv = 0; kv < 2; ++kv)
-            for (int j = 0; j < 4; ++j)
-                gb.p[kv * 4 + j] = tconv(tp.cat, 4608, B, T, 512, w.mh_branch[kv][j], 512, MH_KS[j], 1, MH_KS[j] / 2, tp.cat + 512 + (kv * 4 + j) * 512, 4608, ACT_SILU, nullptr);
+        for (int q = 0; q < 8; ++q) {      // K branches, then V branches: the order of the statistics regions and of the bn slots
+            gb.p[q] = pro.mh_branch(q / 4, q % 4);
+            gb.p[q].Zout = tp.zcat + (gb.p[q].C - tp.cat);       // Zout shares C's addressing
+            const std::string c = std::string("decoder.") + (q < 4 ? "K" : "V") + ".0.conv." + std::to_string(q % 4);
+            if (m->bn_batch) bn[q] = dec_bn_layer(m, c + ".1", c + ".0.bias", tp.bn + q * 1024, 512);
+            rows[q] = BT;
+        }
         gb.count = 8;
-        for (int q = 0; q < 8; ++q) gb.p[q].Zout = tp.zcat + 512 + q * 512;       // Zout shares C's addressing (ld 4608)
-        if (m->bn_batch) {
-            GemmBatch sbt = gb;
-            for (int q = 0; q < 8; ++q) { sbt.p[q].stats = tp.stats + q * tp.stats_group; sbt.p[q].stats_raw = 1; sbt.p[q].scale = nullptr; sbt.p[q].shift = nullptr; }
-            if (launch_gemm(sbt, s, "train_multihop_conv_stats")) return 1;
-            for (int q = 0; q < 8; ++q) {
-                const std::string c = std::string("decoder.") + (q < 4 ? "K" : "V") + ".0.conv." + std::to_string(q % 4);
-                BnLayer L = dec_bn_layer(m, c + ".1", c + ".0.bias", tp.bn + q * 1024, 512);
-                if (bn_stats_finalize(tp.stats + q * tp.stats_group, (BT + 63) / 64, 1024, BT, L, m->bn_momentum, s)) return 1;
-                gb.p[q].scale = L.scale; gb.p[q].shift = L.shift;
-            }
-        }
-        if (m->bn_batch ? launch_gemm_finish(gb, s, "train_multihop_conv_epilogue") : launch_gemm(gb, s, "train_multihop_conv_gemm")) return 1;
-        GemmBatch bb{};
-        for (int kv = 0; kv < 2; ++kv) {
-            GemmP p = gemm_plain(tp.cat, 4608, w.mh_bott[kv].W, state + (kv == 0 ? sl.k : sl.v), 512, BT, 512, 2560);
-            if (kv == 1) { p.a_split = 512; p.a_gap = 2048; }
-            p.shift = w.mh_bott[kv].shift; p.act = ACT_PSINE; p.actw = w.mh_bott[kv].actw; p.R1 = w.pos; p.ldr1 = 512; p.r1_mod = T; p.Zout = tp.zkv[kv];
-            bb.p[kv] = p;
-        }
-        bb.count = 2;
+        if (m->bn_batch ? launch_gemm_batch_stats(m, gb, tp.stats, tp.stats_group, bn, rows, s, "train_multihop_conv_stats", "train_multihop_conv_epilogue")
+                        : launch_gemm(gb, s, "train_multihop_conv_gemm")) return 1;
+        GemmBatch bb = pro.mh_bott();
+        for (int kv = 0; kv < 2; ++kv) bb.p[kv].Zout = tp.zkv[kv];
         if (launch_gemm(bb, s, "train_multihop_bottleneck_gemm")) return 1;
     }
     {
-        GemmBatch gb{};
-        for (int j = 0; j < 4; ++j)
-            gb.p[j] = tconv(tp.cat, 4608, B, T, 512, w.ct_branch[j], 512, CT_KS[j], CT_KS[j], 0, tp.cmap[j], 512, ACT_SILU, tp.zagg[j]);
-        gb.count = 4;
-        if (m->bn_batch) {
-            GemmBatch sbt = gb;
-            for (int j = 0; j < 4; ++j) { sbt.p[j].stats = tp.stats + j * tp.stats_group; sbt.p[j].stats_raw = 1; sbt.p[j].scale = nullptr; sbt.p[j].shift = nullptr; }
-            if (launch_gemm(sbt, s, "train_content_agg_stats")) return 1;
-            for (int j = 0; j < 4; ++j) {
-                const std::string c = "decoder.content.agg." + std::to_string(j);
-                const int rows = B * tp.L[j];
-                BnLayer L = dec_bn_layer(m, c + ".1", c + ".0.bias", tp.bn + (8 + j) * 1024, 512);
-                if (bn_stats_finalize(tp.stats + j * tp.stats_group, (rows + 63) / 64, 1024, rows, L, m->bn_momentum, s)) return 1;
-                gb.p[j].scale = L.scale; gb.p[j].shift = L.shift;
-            }
+        GemmBatch gb = pro.ct_branches();
+        for (int j = 0; j < 4; ++j) {
+            gb.p[j].Zout = tp.zagg[j];
+            const std::string c = "decoder.content.agg." + std::to_string(j);
+            if (m->bn_batch) bn[j] = dec_bn_layer(m, c + ".1", c + ".0.bias", tp.bn + (8 + j) * 1024, 512);
+            rows[j] = B * tp.L[j];
         }
-        if (m->bn_batch ? launch_gemm_finish(gb, s, "train_content_agg_epilogue") : launch_gemm(gb, s, "train_content_agg_gemm")) return 1;
-        PoolCatP pc{};
-        pc.x[0] = tp.cat; pc.L[0] = T; pc.ld[0] = 4608;
-        for (int j = 0; j < 4; ++j) { pc.x[j + 1] = tp.cmap[j]; pc.L[j + 1] = tp.L[j]; pc.ld[j + 1] = 512; }
-        pc.nmaps = 5; pc.B = B; pc.m = tp.m; pc.C = 512; pc.out = tp.pooled;
-        if (launch_pool_cat(pc, s)) return 1;
-        if (launch_gemm1(tlin(tp.pooled, 2560, w.ct_bott, tp.wv, 256, R, 256, 2560, ACT_NONE, nullptr), s, "train_content_gemm")) return 1;
-        GemmBatch g1{};
-        g1.p[0] = tlin(tp.wv, 256, w.ct_k0, tp.tA, 256, R, 256, 256, ACT_SILU, tp.zk0);
-        g1.p[1] = tlin(tp.wv, 256, w.ct_fc0, tp.tB, 256, R, 256, 256, ACT_SILU, tp.zf0);
-        g1.count = 2;
+        if (m->bn_batch ? launch_gemm_batch_stats(m, gb, tp.stats, tp.stats_group, bn, rows, s, "train_content_agg_stats", "train_content_agg_epilogue")
+                        : launch_gemm(gb, s, "train_content_agg_gemm")) return 1;
+        if (launch_pool_cat(pro.pool_cat(), s)) return 1;
+        if (launch_gemm1(pro.ct_bott(), s, "train_content_gemm")) return 1;
+        GemmBatch g1 = pro.ct_pair0(), g2 = pro.ct_pair2();
+        GemmP p3 = pro.ct_fc4();
+        g1.p[0].Zout = tp.zk0; g1.p[1].Zout = tp.zf0; g2.p[0].Zout = tp.zk2; g2.p[1].Zout = tp.zf2; p3.Zout = tp.zf4;
         if (launch_gemm(g1, s, "train_content_gemm")) return 1;
-        GemmBatch g2{};
-        g2.p[0] = tlin(tp.tA, 256, w.ct_k2, state + sl.ckey, 256, R, 256, 256, ACT_SILU, tp.zk2);
-        g2.p[1] = tlin(tp.tB, 256, w.ct_fc2, tp.tC, 256, R, 256, 256, ACT_SILU, tp.zf2);
-        g2.count = 2;
         if (launch_gemm(g2, s, "train_content_gemm")) return 1;
-        GemmP p3 = tlin(tp.tC, 256, w.ct_fc4, tp.logits, VOC, R, VOC, 256, ACT_SILU, tp.zf4);
         if (launch_gemm1(p3, s, "train_content_gemm")) return 1;
         if (launch_gumbel_softmax(tp.logits, gumbel, R, VOC, 0.1f, tp.zsoft, VOCP, content_dis ? content_dis : tp.dis, s)) return 1;
         if (content_dis) L2S_CHECK_HIP(hipMemcpyAsync(tp.dis, content_dis, sizeof(float) * R * VOC, hipMemcpyDeviceToDevice, s));
-        if (launch_gemm1(gemm_plain(tp.zsoft, VOCP, w.ct_emb.W, state + sl.cval, 256, R, 256, VOCP), s, "train_content_gemm")) return 1;
+        if (launch_gemm1(pro.ct_emb(), s, "train_content_gemm")) return 1;
     }
     if (launch_fill(state + sl.c, (int64_t)Bp * 512 * 2, 0.f, s)) return 1;
     return 0;

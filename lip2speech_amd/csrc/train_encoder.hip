@@ -12,6 +12,7 @@
 #include "../../include/l2s.h"
 #include "l2s_common.h"
 #include "l2s_model.h"
+#include "decoder_stages.h"
 
 #include <algorithm>
 #include <string>
@@ -78,12 +79,6 @@ static int64_t enc_tape_layout(EncTape* t, float* base, int B, int T, int H) {
     return o + 64;
 }
 
-static GemmP pw(const float* A, int lda, int a_off, const ConvW& c, float* C, int ldc, int c_off, int cstride, int64_t M, int N, int K) {
-    GemmP p = gemm_plain(A + a_off, lda, c.W, C + c_off, ldc, (int)M, N, K);
-    p.scale = c.scale; p.shift = c.shift; p.act = ACT_RELU; p.c_cstride = cstride;
-    return p;
-}
-
 static int encoder_train_fwd(l2s_model* m, const float* video, int B, int T, int H, int W, const float* emb, float* vis, float* feat, float* tape_base,
                              hipStream_t s) {
     const Weights& w = m->w;
@@ -139,20 +134,20 @@ static int encoder_train_fwd(l2s_model* m, const float* video, int B, int T, int
         if (U.stride2) {
             const int cin = U.cin;
             if (run_dw(x, h, cin, cin, 2, U.b1_dw, tp.b1[u], id + 0, p + "banch1.1")) return 1;
-            if (run_pw(pw(tp.b1[u], cin, 0, U.b1_pw, y, cout, 0, 2, out_px, half, cin), tp.yz[u], id + 1, p + "banch1.3", "train_shuffle_pw_gemm")) return 1;
-            if (run_pw(pw(x, cin, 0, U.pw1, tp.t1[u], half, 0, 1, in_px, half, cin), tp.t1z[u], id + 2, p + "banch2.1", "train_shuffle_pw_gemm")) return 1;
+            if (run_pw(pw_gemm(tp.b1[u], cin, 0, U.b1_pw, y, cout, 0, 2, out_px, half, cin, ACT_RELU, false), tp.yz[u], id + 1, p + "banch1.3", "train_shuffle_pw_gemm")) return 1;
+            if (run_pw(pw_gemm(x, cin, 0, U.pw1, tp.t1[u], half, 0, 1, in_px, half, cin, ACT_RELU, false), tp.t1z[u], id + 2, p + "banch2.1", "train_shuffle_pw_gemm")) return 1;
             if (run_dw(tp.t1[u], h, half, half, 2, U.dw, tp.t2[u], id + 3, p + "banch2.4")) return 1;
-            if (run_pw(pw(tp.t2[u], half, 0, U.pw2, y, cout, 1, 2, out_px, half, half), tp.yz[u] + 1, id + 4, p + "banch2.6", "train_shuffle_pw_gemm")) return 1;
+            if (run_pw(pw_gemm(tp.t2[u], half, 0, U.pw2, y, cout, 1, 2, out_px, half, half, ACT_RELU, false), tp.yz[u] + 1, id + 4, p + "banch2.6", "train_shuffle_pw_gemm")) return 1;
         } else {
             if (launch_copy_cols(x, cout, 0, y, cout, 0, 2, in_px, half, s)) return 1;
-            if (run_pw(pw(x, cout, half, U.pw1, tp.t1[u], half, 0, 1, in_px, half, half), tp.t1z[u], id + 2, p + "banch2.1", "train_shuffle_pw_gemm")) return 1;
+            if (run_pw(pw_gemm(x, cout, half, U.pw1, tp.t1[u], half, 0, 1, in_px, half, half, ACT_RELU, false), tp.t1z[u], id + 2, p + "banch2.1", "train_shuffle_pw_gemm")) return 1;
             if (run_dw(tp.t1[u], h, half, half, 1, U.dw, tp.t2[u], id + 3, p + "banch2.4")) return 1;
-            if (run_pw(pw(tp.t2[u], half, 0, U.pw2, y, cout, 1, 2, in_px, half, half), tp.yz[u] + 1, id + 4, p + "banch2.6", "train_shuffle_pw_gemm")) return 1;
+            if (run_pw(pw_gemm(tp.t2[u], half, 0, U.pw2, y, cout, 1, 2, in_px, half, half, ACT_RELU, false), tp.yz[u] + 1, id + 4, p + "banch2.6", "train_shuffle_pw_gemm")) return 1;
         }
     }
     const int hl = tp.h[N_UNITS];
     const int64_t px = (int64_t)NF * hl * hl;
-    if (run_pw(pw(tp.x[N_UNITS], STAGE_CH[3], 0, w.conv_last, tp.last, LAST_CH, 0, 1, px, LAST_CH, STAGE_CH[3]), tp.lastz, 81, "trunk.1.1", "train_conv_last_gemm")) return 1;
+    if (run_pw(pw_gemm(tp.x[N_UNITS], STAGE_CH[3], 0, w.conv_last, tp.last, LAST_CH, 0, 1, px, LAST_CH, STAGE_CH[3], ACT_RELU, false), tp.lastz, 81, "trunk.1.1", "train_conv_last_gemm")) return 1;
     if (launch_pool_norm_cat(tp.last, NF, hl * hl, LAST_CH, emb, L2S_D_EMB, T, vis, L2S_D_VIS, feat, s)) return 1;
     return 0;
 }

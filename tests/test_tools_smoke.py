@@ -19,6 +19,7 @@ RUNS = {
     "gemm_x3_timeline.py": (["1024", "512", "512"], {}),
     "hash_encoder.py": ([], {}),
     "hash_inference.py": ([], {}),
+    "hash_stage_routes.py": ([], {}),
     "hash_step_routes.py": ([], {}),
     "hash_train_step.py": ([], {}),
     "kernel_resources.py": ([os.path.join(ROOT, "lip2speech_amd", "csrc", "decoder_kernels.hip")], {}),
