@@ -79,9 +79,12 @@ int64_t l2s_state_floats(int B, int T);
  *   L2S_ST_H / L2S_ST_C   decoder LSTM state, 2 layers, fragment layout
  *   L2S_ST_ENC    (B,T,512)   encoder_outputs after encoder_proj + site + residual
  *   L2S_ST_VP     (B,T,256)   V' = values W_ap^T + b_ap: attention_proj (decoder.py:420) applied to the values once, so that the step's
- *                             a @ V' IS attention_proj(a @ v) (the attention weights sum to one) */
+ *                             a @ V' IS attention_proj(a @ v) (the attention weights sum to one)
+ *   L2S_ST_CP     (B,2048,p)  P = content values W_ih0[:, content]^T, the content columns of LSTM layer 0 applied to the values once: rows in the packed
+ *                             order 4 * unit + gate, slot j fastest at pitch p = m rounded up to 4 (zeros past m).  Clips of at most 8 content slots
+ *                             (T <= 62); longer clips have no table (the field is empty) */
 enum { L2S_ST_K = 0, L2S_ST_V = 1, L2S_ST_CKEY = 2, L2S_ST_CVAL = 3, L2S_ST_ECELL = 4,
-       L2S_ST_H = 5, L2S_ST_C = 6, L2S_ST_ENC = 7, L2S_ST_STOPC = 8, L2S_ST_VP = 9 };
+       L2S_ST_H = 5, L2S_ST_C = 6, L2S_ST_ENC = 7, L2S_ST_STOPC = 8, L2S_ST_VP = 9, L2S_ST_CP = 10 };
 int64_t l2s_state_offset(int B, int T, int field);
 
 /* ---- stages ---------------------------------------------------------------------------------------- */

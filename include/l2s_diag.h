@@ -27,7 +27,9 @@ extern "C" {
  *   "fuse_s2"           (1)  stride-2 ShuffleNet units as one fused kernel each (needs fuse_trunk); 0 = dw/pw + pw/dw/pw launches
  *   "overlap_postnet"   (0)  l2s_inference: windowed post-net on a second stream under the decode loop
  *   "gemm_x3_dma"       (1)  constant weights of the split-bf16 GEMMs as pre-split bf16 planes by LDS-DMA; 0 = load + split + LDS store in the staging waves
- *   "hoist_vproj"       (2)  attention_proj applied to the VALUES once per clip in the prologue: 2 = LSTM0 on [content | prenet + o | h0] (K = 1024), 1 = on
+ *   "hoist_vproj"       (3)  attention_proj applied to the VALUES once per clip in the prologue: 3 = also the content columns of LSTM0 applied to the content
+ *                            values once per clip: LSTM0 on [prenet + o | h0] (K = 768), the content term added by the cell threads from the state's
+ *                            L2S_ST_CP table (clips of at most 8 content slots; longer clips run 2), 2 = LSTM0 on [content | prenet + o | h0] (K = 1024), 1 = on
  *                            [content | prenet | o | h0] (K = 1280), 0 = a @ v through the pre-multiplied W_ih W_ap (K = 1536)
  *   "attn_lds"          (1)  attention blocks with the projected values staged through LDS: 1 = at up to 128 rows and whenever chains overlap, 2 = always, 0 = never
  *   "flat_half"         (1)  the step's first launch on four-wave half-CU blocks when chains overlap; 2 = always, 0 = never
@@ -144,7 +146,8 @@ int l2s_op_skinny_form(l2s_model* m, int count, const int* groups, int B, int ch
  * the decode loop, the training forward, the prologue and the voice tower call - run for B rows on dummy operands, under the options of the finalised
  * model m with the ones the site stands for laid over them ("fold_step_weights", "hoist_vproj").  site: a key of "sites" in
  * tests/golden/skinny_forms.json (bilstm_step, phase_a_unfolded, phase_a_folded_step0, phase_a_folded, step_attention_proj, phase_d_k1536,
- * phase_d_k1280, phase_d_k1024_sum, phase_d_k1024_unfolded, phase_e, step_fc_out_stop, spk_lstm_step).  Writes *count groups (at most 4) of 8 ints
+ * phase_d_k1280, phase_d_k1024_sum, phase_d_k1024_unfolded, phase_e, step_fc_out_stop, spk_lstm_step) or phase_d_k768_hoist ("hoist_vproj" = 3, the
+ * integers of tests/test_content_hoist_gpu.py).  Writes *count groups (at most 4) of 8 ints
  * into groups[32].  Launches nothing (tests/test_step_sites_gpu.py). */
 int l2s_op_step_site(l2s_model* m, const char* site, int B, int* groups, int* count);
 
@@ -172,6 +175,10 @@ typedef struct l2s_skinny_group {
  * The batch goes through launch_skinny - its validation, the form rule and the dispatch table of every product launch.  A refused launch returns
  * non-zero with the text in l2s_last_error (the text l2s_op_skinny_form answers after "ERROR "). */
 int l2s_op_skinny(l2s_model* m, int count, const l2s_skinny_group* groups, int B, const int* es_end, int es_step, void* stream);
+/* The same for ONE SK_LSTM group on the K = 768 layout of the decode step (nchunks = {0, 16, 32, 0} with a_sum: option "hoist_vproj" = 3) with the hoisted
+ * content term: hoist_p [B][16 * ntiles][hoist_pitch] (rows in the packed order 4 * unit + gate), hoist_alpha [B][8] (zeros past the clip's slots),
+ * hoist_pitch 4 or 8.  The cell threads add sum_j alpha[b][j] * P[b][row][j] (fmaf chain, j ascending) after the K-slice partials and before the bias. */
+int l2s_op_skinny_hoist(l2s_model* m, const l2s_skinny_group* group, const float* hoist_p, const float* hoist_alpha, int hoist_pitch, int B, void* stream);
 
 /* One backward GEMM on its own: the operator-level entry of gemm_bwd.hip (tests/test_gemm_bwd_op_gpu.py; lip2speech_amd/native.py op_gemm_bwd).  The
  * descriptor holds the integers of BwdGemmP (l2s_common.h) with the meaning they have there:

@@ -12,11 +12,12 @@ namespace l2s {
 
 // ---------------------------------------------------------------- the step's buffers
 // frag16 (rows padded to 16): h0/h1 ping-pong, c0, c1, av (a @ v, or o = a @ V'), p1, cc (content), uu (u of the literal step), p2f, yf (the frame
-// fed back, K = 96); plain [B][.]: q, qc, p2 (prenet of the literal step)
+// fed back, K = 96); plain [B][.]: q, qc, p2 (prenet of the literal step), al (content soft-max weights, CONTENT_HOIST_MAX_M per row: the K = 768 form only)
 struct StepBufs {
-    float *h0[2], *h1[2], *c0, *c1, *av, *p1, *cc, *uu, *p2f, *yf, *q, *qc, *p2;
+    float *h0[2], *h1[2], *c0, *c1, *av, *p1, *cc, *uu, *p2f, *yf, *q, *qc, *p2, *al;
 };
-inline StepBufs step_carve(Bump& bp, int B) {      // h0[0] first: training zero-fills the whole run from there
+constexpr int64_t step_alpha_floats(int B) { return (int64_t)B * CONTENT_HOIST_MAX_M; }
+inline StepBufs step_carve(Bump& bp, int B, bool alpha = false) {      // h0[0] first: training zero-fills the whole run from there; alpha: inference carves al, last
     const int64_t Bp = pad16(B);
     StepBufs d;
     for (int i = 0; i < 2; ++i) d.h0[i] = bp.f(Bp * 512);
@@ -25,6 +26,7 @@ inline StepBufs step_carve(Bump& bp, int B) {      // h0[0] first: training zero
     d.p1 = bp.f(Bp * 256); d.cc = bp.f(Bp * 256); d.uu = bp.f(Bp * 256); d.p2f = bp.f(Bp * 256);
     d.yf = bp.f(Bp * 96);
     d.q = bp.f((int64_t)B * 512); d.qc = bp.f((int64_t)B * 256); d.p2 = bp.f((int64_t)B * 256);
+    d.al = alpha ? bp.f(step_alpha_floats(B)) : nullptr;
     return d;
 }
 
@@ -34,18 +36,23 @@ enum Lstm0Operand {
     L0_K1536,        // w.lstm0f on [content | prenet | a @ v | h0]: attention_proj pre-multiplied into W_ih
     L0_K1280,        // w.lstm0v on [content | prenet | o | h0], o = a @ V' (V' from the prologue)
     L0_K1024_SUM,    // w.lstm0 on [content | prenet + o | h0]: the sum formed by the operand loader (SkinnyP::a_sum)
+    L0_K768,         // w.lstm0c on [prenet + o | h0]: the content columns hoisted too - the attention launch stores alpha instead of content = alpha @ value,
+                     //   the cell threads add sum_j alpha_j P_j with P = value W_ih[:, content]^T from the prologue (the state's cp table)
 };
 struct StepForm {
     bool fold;               // phase-merged 4-launch step (option "fold_step_weights") or the literal 6 phases
     Lstm0Operand lstm0;
     bool planes;             // the groups carry their weights' bf16 planes (SkW::W3): inference does, training stays on the f32 forms
-    bool vproj() const { return lstm0 == L0_K1280 || lstm0 == L0_K1024_SUM; }      // the attention launch writes o = a @ V' (K = 256) into av
+    bool vproj() const { return lstm0 == L0_K1280 || lstm0 == L0_K1024_SUM || lstm0 == L0_K768; }      // the attention launch writes o = a @ V' (K = 256) into av
+    bool choist() const { return lstm0 == L0_K768; }
 };
-// inference and the chain microbenches: option "hoist_vproj" picks LSTM0's operand layout of the folded step
-inline StepForm step_form(const Weights& w, const Options& o, bool fold) {
+// inference and the chain microbenches: option "hoist_vproj" picks LSTM0's operand layout of the folded step; m = content slots of the call's clips (T / 7)
+inline StepForm step_form(const Weights& w, const Options& o, bool fold, int m) {
     const bool vhoist = fold && o.hoist_vproj && w.lstm0v.W && w.vproj.W;
     const bool vsum = vhoist && o.hoist_vproj >= 2 && skinny_sum_supported(o);
-    return {fold, !fold ? L0_LITERAL : vsum ? L0_K1024_SUM : vhoist ? L0_K1280 : L0_K1536, true};
+    // 3: the step is folded, the summed-segment form exists, the K = 768 planes exist, and the clip's table is worth reading (CONTENT_HOIST_MAX_M, l2s_common.h)
+    const bool chst = vsum && o.hoist_vproj >= 3 && w.lstm0c.W && w.lstm0c.W3 && w.cproj.W && m >= 1 && m <= CONTENT_HOIST_MAX_M;
+    return {fold, !fold ? L0_LITERAL : chst ? L0_K768 : vsum ? L0_K1024_SUM : vhoist ? L0_K1280 : L0_K1536, true};
 }
 // training: folded onto lstm0f (its backward pass knows that layout), or literal; no planes
 inline StepForm step_form_train(bool fold) { return {fold, fold ? L0_K1536 : L0_LITERAL, false}; }
@@ -117,6 +124,7 @@ inline StepAttn step_phase_b(const StepForm& f, const Weights& w, const StepBufs
     if (f.vproj()) at.vp = state + sl.vp;      // d.av then holds o = a @ V' (frag16, K = 256)
     at.attn_out = attn ? attn + (int64_t)i * T : nullptr; at.ld_attn_b = (int64_t)S * T; at.attn_logits = attn_logits;
     at.qc = d.qc; at.ldqc = 256; at.ckey = state + sl.ckey; at.cval = state + sl.cval; at.tau_c = w.tau_c; at.cc_frag = d.cc;
+    if (f.choist()) at.alpha_out = d.al;       // the content blocks store alpha; d.cc is not written (nor read)
     at.B = B; at.T = T; at.m = sl.m;
     SkinnyP& pr = r.pre2;
     pr = sk_base(w.pre2, B, f.planes);
@@ -134,12 +142,16 @@ inline SkinnyBatch step_phase_c(const StepForm& f, const Weights& w, const StepB
     return sk_batch1(a, w.aproj.tiles);
 }
 
-// phase D of step i: LSTM layer 0, h0[cur] -> h0[nxt], on the operand layout of the form
-inline SkinnyBatch step_phase_d(const StepForm& f, const Weights& w, const StepBufs& d, int B, int i) {
+// phase D of step i: LSTM layer 0, h0[cur] -> h0[nxt], on the operand layout of the form.  cp / cp_pitch: the call's P table (StateLayout::cp; L0_K768 only)
+inline SkinnyBatch step_phase_d(const StepForm& f, const Weights& w, const StepBufs& d, int B, int i, const float* cp = nullptr, int cp_pitch = 0) {
     const int cur = i & 1, nxt = cur ^ 1;
-    SkinnyP a = sk_base(f.lstm0 == L0_K1536 ? w.lstm0f : f.lstm0 == L0_K1280 ? w.lstm0v : w.lstm0, B, f.planes);
+    SkinnyP a = sk_base(f.lstm0 == L0_K1536 ? w.lstm0f : f.lstm0 == L0_K1280 ? w.lstm0v : f.lstm0 == L0_K768 ? w.lstm0c : w.lstm0, B, f.planes);
     a.seg[0] = {d.cc, 16};
     switch (f.lstm0) {
+    case L0_K768:      // segment 0 stays, empty: the summed segment is segment 1 in every layout that has one
+        a.seg[0] = {d.p2f, 0}; a.seg[1] = {d.p2f, 16}; a.a_sum = d.av; a.seg[2] = {d.h0[cur], 32}; a.nseg = 3;
+        a.hoist_p = cp; a.hoist_alpha = d.al; a.hoist_pitch = cp_pitch;
+        break;
     case L0_LITERAL:   a.seg[1] = {d.uu, 16}; a.seg[2] = {d.h0[cur], 32}; a.nseg = 3; break;
     case L0_K1024_SUM: a.seg[1] = {d.p2f, 16}; a.a_sum = d.av; a.seg[2] = {d.h0[cur], 32}; a.nseg = 3; break;
     case L0_K1280:     a.seg[1] = {d.p2f, 16}; a.seg[2] = {d.av, 16}; a.seg[3] = {d.h0[cur], 32}; a.nseg = 4; break;

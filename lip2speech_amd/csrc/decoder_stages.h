@@ -116,6 +116,15 @@ struct Prologue {
     GemmBatch ct_pair2() const { return gemm_pair(ct_lin(b.tA, w.ct_k2, state + sl.ckey), ct_lin(b.tB, w.ct_fc2, b.tC)); }            // k2 | fc2
     GemmP ct_fc4() const { return lin_gemm(b.tC, 256, w.ct_fc4, b.logits, VOC, R(), VOC, 256, ACT_SILU); }
     GemmP ct_emb() const { return gemm_plain(b.zsoft, VOCP, w.ct_emb.W, state + sl.cval, 256, R(), 256, VOCP); }
+    // P = value W_ih[:, content]^T (decoder.py:262-271 feeds alpha @ value straight into the LSTM: no bias, no nonlinearity in between), stored as
+    // P[b][packed gate row][j], j fastest at pitch cp_pitch = ceil4(m): a clip's m value rows are read as a one-tap sequence of cp_pitch output rows (the rows
+    // past m read as padding: zeros, like the rows of a masked clip's unused slots, whose values are zero) and stored channel-first per clip.  K = 256: always
+    // the f32 tile kernel, whose rows do not depend on each other - a clip's table is the same bits alone, padded or in a group
+    GemmP cproj() const {
+        GemmP p = lin_gemm(state + sl.cval, 256, w.cproj, state + sl.cp, 2048, B * sl.cp_pitch, 2048, 256, ACT_NONE);
+        p.Tout = sl.cp_pitch; p.Tin = b.m; p.c_tr_T = sl.cp_pitch;
+        return p;
+    }
 };
 
 // the BiLSTM starts from h0 = c0 = s_e in both directions (decoder.py:386-389); the other half of the h ping-pong starts at zero

@@ -179,7 +179,7 @@ static int64_t prologue_ws_floats(int B, int T) {
 }
 static int64_t decode_ws_floats(int B) {
     int64_t Bp = pad16(B);
-    return Bp * (512 * 4 + 512 * 2 + 512 + 256 * 4 + 96) + (int64_t)B * (512 + 256 + 256) + 64 * 24 + (B + 2 + 64) /* EsCtl */ + (B <= 8 ? pdecode_ws_bytes(B) / 4 + 64 : 0);
+    return Bp * (512 * 4 + 512 * 2 + 512 + 256 * 4 + 96) + (int64_t)B * (512 + 256 + 256) + step_alpha_floats(B) + 64 * 25 + (B + 2 + 64) /* EsCtl */ + (B <= 8 ? pdecode_ws_bytes(B) / 4 + 64 : 0);
 }
 constexpr int POST_TAPSPLIT_ROWS = 640;      // a batch with at most this many post-net rows (one or two clips of 300 frames) runs its Conv1d layers one K slice per tap
 static int64_t postnet_ws_floats(int B, int S) { return (int64_t)B * S * 512 * ((int64_t)B * S <= POST_TAPSPLIT_ROWS * MAX_GROUP ? 9 : 4) + 64 * 7; }
@@ -457,6 +457,8 @@ static int prologue_run(l2s_model* m, const float* vis, const float* emb, const 
         if (launch_gumbel_softmax(pb.logits, gumbel, pro.R(), VOC, 0.1f, pb.zsoft, VOCP, content_dis, s)) return 1;
         if (lens && launch_zero_slot_rows(pb.zsoft, VOCP, content_dis, VOC, B, mT, lens.dev, s)) return 1;      // slots i >= m_b: zero z (so zero values) and zero content_dis
         if (launch_gemm1(pro.ct_emb(), s, "content_gemm")) return 1;
+        // the content columns of LSTM layer 0 applied to the values once per call (option "hoist_vproj" = 3): clips short enough to have a table (StateLayout::cp)
+        if (w.cproj.W && sl.cp_pitch && launch_gemm1(pro.cproj(), s, "content_hoist_gemm")) return 1;
     }
     // decoder cell state starts at zero (decoder.py:406)
     if (launch_fill(state + sl.c, (int64_t)Bp * 512 * 2, 0.f, s)) return 1;
@@ -477,9 +479,9 @@ static int decode_launches(l2s_model* m, float* state, int B, int T, int S, cons
     const Weights& w = m->w;
     StateLayout sl = state_layout(B, T);
     const int Bp = pad16(B);
-    const StepForm form = step_form(w, m->opt, fold);
+    const StepForm form = step_form(w, m->opt, fold, sl.m);
     Bump bp(ws, ws_bytes);
-    const StepBufs d = step_carve(bp, B);
+    const StepBufs d = step_carve(bp, B, true);
     // option "early_stop" (free-running loops only): this call's control block, armed on the stream - chains in flight on other streams have their own
     EsCtl* const es = early ? reinterpret_cast<EsCtl*>(bp.f(B + 2)) : nullptr;
     L2S_REQUIRE(!bp.overflow, "decode workspace too small");
@@ -529,7 +531,7 @@ static int decode_launches(l2s_model* m, float* state, int B, int T, int S, cons
             if (launch_skinny(sb, s, "step_attention_proj", m->opt)) return 1;
         }
         {   // phase D: LSTM layer 0 on cat(content, u), h0  (folded: cat(content, prenet, a@v) against [W_ih | W_ih_u W_ap | W_hh])
-            SkinnyBatch sb = step_phase_d(form, w, d, B, i);
+            SkinnyBatch sb = step_phase_d(form, w, d, B, i, state + sl.cp, sl.cp_pitch);
             es_launch(sb, i);
             if (launch_skinny(sb, s, "step_lstm_cell", m->opt)) return 1;
         }
@@ -922,6 +924,7 @@ int64_t l2s_state_offset(int B, int T, int field) {
         case L2S_ST_ENC: return s.enc;
         case L2S_ST_STOPC: return s.stopc;
         case L2S_ST_VP: return s.vp;
+        case L2S_ST_CP: return s.cp;
     }
     return -1;
 }
@@ -1674,17 +1677,21 @@ int l2s_op_lstm_cell_chain(l2s_model* m, int B, int n_pairs, void* ws, int64_t w
     hipStream_t s = (hipStream_t)stream;
     const Weights& w = m->w;
     const int Bp = pad16(B);
-    const StepForm form = step_form(w, m->opt, true);      // phases D and E of the folded step under the model's options (decode_step.h)
+    constexpr int CHAIN_M = 4;                             // the chain has no clips: the content slots of the benchmark's 29-frame clips stand for them
+    const StepForm form = step_form(w, m->opt, true, CHAIN_M);      // phases D and E of the folded step under the model's options (decode_step.h)
     Bump bp(ws, ws_bytes);
-    const StepBufs d = step_carve(bp, B);
+    const StepBufs d = step_carve(bp, B, true);
+    const int cp_pitch = content_hoist_pitch(CHAIN_M);
+    float* const cp = form.choist() ? bp.f((int64_t)B * 2048 * cp_pitch) : nullptr;      // the K = 768 form reads its table and its soft-max weights: zeros, like the state
     L2S_REQUIRE(!bp.overflow, "workspace too small");
     for (float* z : {d.h0[0], d.h0[1], d.h1[0], d.h1[1], d.c0, d.c1, d.av}) if (launch_fill(z, (int64_t)Bp * 512, 0.f, s)) return 1;
     for (float* z : {d.cc, d.p2f}) if (launch_fill(z, (int64_t)Bp * 256, 0.f, s)) return 1;
+    if (cp && (launch_fill(cp, (int64_t)B * 2048 * cp_pitch, 0.f, s) || launch_fill(d.al, step_alpha_floats(B), 0.f, s))) return 1;
     hipEvent_t e0, e1;
     L2S_CHECK_HIP(hipEventCreate(&e0));
     L2S_CHECK_HIP(hipEventCreate(&e1));
     auto pair = [&](int i) -> int {
-        if (launch_skinny(step_phase_d(form, w, d, B, i), s, "step_lstm_cell", m->opt)) return 1;
+        if (launch_skinny(step_phase_d(form, w, d, B, i, cp, cp_pitch), s, "step_lstm_cell", m->opt)) return 1;
         return launch_skinny(step_phase_e(form, w, d, B, i), s, "step_lstm_cell", m->opt);
     };
     for (int i = 0; i < 8; ++i) if (pair(i)) return 1;                   // warm-up
@@ -1709,9 +1716,9 @@ int l2s_op_step_attn_chain(l2s_model* m, float* state, int B, int T, int n_launc
     const Weights& w = m->w;
     StateLayout sl = state_layout(B, T);
     const int Bp = pad16(B);
-    const StepForm form = step_form(w, m->opt, true);      // phase B of the folded step under the model's options (decode_step.h)
+    const StepForm form = step_form(w, m->opt, true, sl.m);      // phase B of the folded step under the model's options (decode_step.h)
     Bump bp(ws, ws_bytes);
-    const StepBufs d = step_carve(bp, B);
+    const StepBufs d = step_carve(bp, B, true);
     L2S_REQUIRE(!bp.overflow, "workspace too small");
     if (launch_fill(d.q, (int64_t)B * 512, 0.f, s) || launch_fill(d.qc, (int64_t)B * 256, 0.f, s) || launch_fill(d.p1, (int64_t)Bp * 256, 0.f, s)) return 1;
     for (int i = 0; i < n_launches; ++i) {
@@ -1766,22 +1773,23 @@ int l2s_op_skinny_form(l2s_model* m, int count, const int* groups, int B, int ch
 // the batch that the builders of decode_step.h make for a named call site, as l2s_op_skinny_form's integers; nothing is launched
 int l2s_op_step_site(l2s_model* m, const char* site, int B, int* groups, int* count) {
     L2S_REQUIRE(m && m->finalized && site && groups && count && B >= 1, "bad arguments");
-    struct Site { const char* name; int fold, hoist, step; char phase; };      // hoist < 0: the model's own "hoist_vproj"
+    struct Site { const char* name; int fold, hoist, step; char phase; };      // hoist < 0: the model's own "hoist_vproj"; the sites stand for 29-frame clips (four content slots)
     static const Site sites[] = {
         {"bilstm_step", 1, -1, 0, 'L'}, {"phase_a_unfolded", 0, -1, 1, 'A'}, {"phase_a_folded_step0", 1, -1, 0, 'A'}, {"phase_a_folded", 1, -1, 1, 'A'},
         {"step_attention_proj", 0, -1, 1, 'C'}, {"phase_d_k1536", 1, 0, 1, 'D'}, {"phase_d_k1280", 1, 1, 1, 'D'}, {"phase_d_k1024_sum", 1, 2, 1, 'D'},
-        {"phase_d_k1024_unfolded", 0, -1, 1, 'D'}, {"phase_e", 1, -1, 1, 'E'}, {"step_fc_out_stop", 1, -1, 1, 'F'}, {"spk_lstm_step", 1, -1, 0, 'S'}};
+        {"phase_d_k1024_unfolded", 0, -1, 1, 'D'}, {"phase_e", 1, -1, 1, 'E'}, {"step_fc_out_stop", 1, -1, 1, 'F'}, {"spk_lstm_step", 1, -1, 0, 'S'},
+        {"phase_d_k768_hoist", 1, 3, 1, 'D'}};
     const Site* st = nullptr;
     for (const Site& t : sites) if (!std::strcmp(site, t.name)) st = &t;
     L2S_REQUIRE(st, "step site: unknown name");
     L2S_REQUIRE(st->phase == 'S' ? m->has_spk : m->has_dec, "step site: the model holds no weights of that recurrence");
     static float a[1];      // stands for every buffer, as in l2s_op_skinny_form
     StepBufs d;
-    for (float** p : {&d.h0[0], &d.h0[1], &d.h1[0], &d.h1[1], &d.c0, &d.c1, &d.av, &d.p1, &d.cc, &d.uu, &d.p2f, &d.yf, &d.q, &d.qc, &d.p2}) *p = a;
+    for (float** p : {&d.h0[0], &d.h0[1], &d.h1[0], &d.h1[1], &d.c0, &d.c1, &d.av, &d.p1, &d.cc, &d.uu, &d.p2f, &d.yf, &d.q, &d.qc, &d.p2, &d.al}) *p = a;
     Options o = m->opt;
     if (st->hoist >= 0) o.hoist_vproj = st->hoist;
     const Weights& w = m->w;
-    const StepForm form = step_form(w, o, st->fold != 0);
+    const StepForm form = step_form(w, o, st->fold != 0, 4);
     const StepOut out{a, a, a, 2};
     const int i = st->step;
     SkinnyBatch sb{};
@@ -1789,7 +1797,7 @@ int l2s_op_step_site(l2s_model* m, const char* site, int B, int* groups, int* co
     case 'L': for (int dir = 0; dir < 2; ++dir) bilstm_step_group(sb, dir, w, true, B, 7, 0, a, a, a, a, a); sb.count = 2; break;
     case 'A': sb = step_phase_a(form, w, d, B, i, step_from_frame(form, i, false), out); break;
     case 'C': sb = step_phase_c(form, w, d, B); break;
-    case 'D': sb = step_phase_d(form, w, d, B, i); break;
+    case 'D': sb = step_phase_d(form, w, d, B, i, a, 4); break;
     case 'E': sb = step_phase_e(form, w, d, B, i); break;
     case 'F': sb = step_phase_f(form, w, d, B, i, out); break;
     default:  sb = spk_lstm_step(w, 0, B, a, a, a, a, 1024, a, 256); break;
@@ -1805,10 +1813,7 @@ int l2s_op_step_site(l2s_model* m, const char* site, int B, int* groups, int* co
 }
 
 // one batch-row launch described by the caller (include/l2s_diag.h l2s_skinny_group): the batch is filled field by field and handed to launch_skinny
-int l2s_op_skinny(l2s_model* m, int count, const l2s_skinny_group* groups, int B, const int* es_end, int es_step, void* stream) {
-    L2S_REQUIRE(m && groups && count >= 1 && count <= SKINNY_MAX_GROUP && B >= 1, "bad arguments");
-    hipStream_t s = (hipStream_t)stream;
-    SkinnyBatch sb{};
+static int op_skinny_batch(int count, const l2s_skinny_group* groups, int B, hipStream_t s, SkinnyBatch& sb) {
     for (int i = 0; i < count; ++i) {
         const l2s_skinny_group& g = groups[i];
         SkinnyP& p = sb.p[i];
@@ -1829,7 +1834,24 @@ int l2s_op_skinny(l2s_model* m, int count, const l2s_skinny_group* groups, int B
         }
         sb.ntiles[i] = g.ntiles;
     }
-    sb.count = count; sb.es_end = es_end; sb.es_step = es_step;
+    sb.count = count;
+    return 0;
+}
+int l2s_op_skinny(l2s_model* m, int count, const l2s_skinny_group* groups, int B, const int* es_end, int es_step, void* stream) {
+    L2S_REQUIRE(m && groups && count >= 1 && count <= SKINNY_MAX_GROUP && B >= 1, "bad arguments");
+    hipStream_t s = (hipStream_t)stream;
+    SkinnyBatch sb{};
+    if (op_skinny_batch(count, groups, B, s, sb)) return 1;
+    sb.es_end = es_end; sb.es_step = es_step;
+    return launch_skinny(sb, s, "op_skinny", m->opt);
+}
+// the same for ONE LSTM group that carries the hoisted content term (SkinnyP::hoist_p / hoist_alpha / hoist_pitch)
+int l2s_op_skinny_hoist(l2s_model* m, const l2s_skinny_group* group, const float* hoist_p, const float* hoist_alpha, int hoist_pitch, int B, void* stream) {
+    L2S_REQUIRE(m && group && hoist_p && hoist_alpha && B >= 1, "bad arguments");
+    hipStream_t s = (hipStream_t)stream;
+    SkinnyBatch sb{};
+    if (op_skinny_batch(1, group, B, s, sb)) return 1;
+    sb.p[0].hoist_p = hoist_p; sb.p[0].hoist_alpha = hoist_alpha; sb.p[0].hoist_pitch = hoist_pitch;
     return launch_skinny(sb, s, "op_skinny", m->opt);
 }
 

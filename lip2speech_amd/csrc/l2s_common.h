@@ -77,7 +77,10 @@ struct Options {
                                 //   kernels run beside them; same bits
     int attn_lds = 1;           // "attn_lds": the step's attention blocks fetch keys / projected values by buffer loads, the values as 16-byte rows through LDS:
                                 //   1 = at up to 128 rows per launch, 2 = always, 0 = never
-    int hoist_vproj = 2;        // "hoist_vproj": the phase-merged step reads o = a @ V' with V' = V W_ap^T + b_ap computed once in the prologue: 2 = LSTM0 on
+    int hoist_vproj = 3;        // "hoist_vproj": the phase-merged step reads o = a @ V' with V' = V W_ap^T + b_ap computed once in the prologue: 3 (default) = as 2,
+                                //   and the content columns leave the step too: LSTM0 on [prenet + o | h0] (K = 768), W_ih[:, content] (alpha @ value) added by the
+                                //   cell threads as sum_j alpha_j P_j with P = value W_ih[:, content]^T from the prologue (clips of at most CONTENT_HOIST_MAX_M
+                                //   content slots; longer clips run 2, same bits as 2), 2 = LSTM0 on
                                 //   [content | prenet + o | h0] (K = 1024, the sum formed by the operand loader: the reference's own u = prenet + o), 1 = on
                                 //   [content | prenet | o | h0] through a second copy of W_ih's u columns (K = 1280; every block form), 0 = a @ v through the
                                 //   pre-multiplied W_ih W_ap (K = 1536)
@@ -420,7 +423,17 @@ struct SkinnyP {
     const float* stop_const;           // [B]
     float* yfrag;                      // frag16, K = 80
     int* es_ctl; int es_end;           // option "early_stop" (else null): the call's EsCtl block; the end step (minus S) to store once the last clip has crossed at this step
+    // SK_LSTM on the K = 768 layout of the decode step (option "hoist_vproj" = 3; else null): the content term of the gates, hoisted out of the GEMM
+    const float* hoist_p;              // P[b][packed gate row 4 * unit + gate][hoist_pitch] = value_j . W_ih[row, content] (the prologue's table; slots past m_b zero)
+    const float* hoist_alpha;          // alpha[b][CONTENT_HOIST_MAX_M]: the step's content soft-max weights, zeros past m_b (the attention launch)
+    int hoist_pitch;                   // floats per gate row of P: the clip's content slots rounded up to 4 (4 or 8)
 };
+// The longest clip (content slots m = T / 7) whose calls take the hoisted content term: a cell thread reads ceil4(m) floats of P per gate and step in place of
+// the 256 content columns of the GEMM - 4 m bytes x 2048 gates x rows per launch against 256 columns x 2048 x 6 bytes of weight planes once per 64 rows plus the
+// rows' 1 KB of activations.  At m = 4 (T = 29) that is 8.4 MB more and about 5 MB less through the fabric per 256-row launch for a quarter fewer K steps; from
+// m = 9 on (three 16-byte requests per gate, 25 MB) the table read outgrows what the columns cost, so longer clips keep the K = 1024 form.
+constexpr int CONTENT_HOIST_MAX_M = 8;
+inline int content_hoist_pitch(int m) { return m <= CONTENT_HOIST_MAX_M ? (m + 3) / 4 * 4 : 0; }      // 0: no table for this clip length
 // Option "early_stop" on the launch-per-phase loop: a per-call control block in the call's own workspace.  The SK_MEL epilogue notes a clip's FIRST stop
 // crossing; the one that completes the count lowers the end step (ordinary vector atomics).  Every step kernel carries its step index and returns at its
 // top once that index is at or past the end - a uniform branch on a kernel argument that is null when the option is off.  Steps are kept RELATIVE to S
@@ -459,6 +472,7 @@ struct AttnP {
     const float* cval;                // [B][m][256]
     const float* tau_c;
     float* cc_frag;                   // frag16, K = 256
+    float* alpha_out;                 // option "hoist_vproj" = 3 (else null): alpha[b][CONTENT_HOIST_MAX_M] is stored, zeros past the clip's slots, INSTEAD of cc = alpha @ value
     int B, T, m;
     const int* es_end; int es_step;   // option "early_stop" (else null): the launch returns at once when es_step (step - S) >= *es_end (EsCtl::end_rel)
 };

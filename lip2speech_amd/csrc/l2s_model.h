@@ -87,6 +87,8 @@ struct Weights {
     SkW lstm0v;                        // LSTM0 over [content | prenet | o | h0] (K = 1280), o = a @ V' with V' = V W_ap^T + b_ap hoisted into the prologue:
                                        //   [W_ih[:, :256] | W_ih[:, 256:] | W_ih[:, 256:] | W_hh], the plain LSTM0 bias
     ConvW vproj;                       // attention_proj as a row-major [256][512] GEMM weight + bias (the prologue's V' = V W_ap^T + b_ap)
+    SkW lstm0c;                        // LSTM0 over [prenet + o | h0] (K = 768): [W_ih[:, 256:] | W_hh], the plain LSTM0 bias - the content columns hoisted into the prologue:
+    ConvW cproj;                       //   W_ih[:, :256] as a row-major [2048][256] GEMM weight, rows in the packed order 4 * unit + gate (P = value W_ih[:, content]^T)
     const float* stop_tail = nullptr; const float* stop_bias = nullptr;
     const float* bos = nullptr; const float* tau = nullptr; const float* tau_c = nullptr;
     // postnet
@@ -178,7 +180,7 @@ inline int content_lens(int T, int L[4]) {
     return m;
 }
 
-struct StateLayout { int64_t k, v, ckey, cval, ecell, h, c, enc, stopc, vp, total; int m; };
+struct StateLayout { int64_t k, v, ckey, cval, ecell, h, c, enc, stopc, vp, cp, total; int m, cp_pitch; };
 inline StateLayout state_layout(int B, int T) {
     StateLayout s{};
     int L[4];
@@ -195,6 +197,10 @@ inline StateLayout state_layout(int B, int T) {
     s.enc = take((int64_t)B * T * 512);
     s.stopc = take(B);
     s.vp = take((int64_t)B * T * 256);      // V' = V W_ap^T + b_ap (decoder.py:420 applied to the values once instead of to a @ v every step)
+    // P[b][packed gate row][cp_pitch] = value_j . W_ih[row, content]: the content columns of LSTM layer 0 applied to the clip's values once (option
+    // "hoist_vproj" = 3; clips of at most CONTENT_HOIST_MAX_M content slots, else empty); last, so that every earlier field keeps its offset
+    s.cp_pitch = content_hoist_pitch(s.m);
+    s.cp = take((int64_t)B * 2048 * s.cp_pitch);
     s.total = o;
     return s;
 }

@@ -350,6 +350,21 @@ static void pack_decoder(Packer& P, Weights& w) {
         if (l == 0) lstm0_bias = o;
         P.sum_rec.push_back({Dk + "decoder_rnn.bias_ih_" + sl, Dk + "decoder_rnn.bias_hh_" + sl, 2048, 512, o});
         s.N = 2048; s.K = 1024; s.tiles = 128;
+        if (l == 0) {
+            // layer 0 without its content columns (K = 768), and those columns as the GEMM weight of the prologue's P = value W_ih[:, content]^T, rows in the
+            // packed order: verbatim copies of the parameters only (the device-side refresh keeps them current by itself), the plain LSTM0 bias
+            P.frag16(2048, 768, [&](int np, float* row) {
+                int r = lstm_perm_row(np, 512);
+                std::memcpy(row, wi->data() + (int64_t)r * 512 + 256, sizeof(float) * 256);      // u = prenet + o columns of W_ih
+                std::memcpy(row + 256, wh->data() + (int64_t)r * 512, sizeof(float) * 512);      // h0 columns
+                return true;
+            }, &w.lstm0c.W);
+            P.bind(&w.lstm0c.bias, lstm0_bias);
+            w.lstm0c.N = 2048; w.lstm0c.K = 768; w.lstm0c.tiles = 128;
+            int64_t c = P.blob.alloc((int64_t)2048 * 256);
+            for (int np = 0; np < 2048; ++np) std::memcpy(&P.blob.data[c + (int64_t)np * 256], wi->data() + (int64_t)lstm_perm_row(np, 512) * 512, sizeof(float) * 256);
+            P.bind(&w.cproj.W, c);
+        }
     }
     {   // fc_out (80 rows) + stop-token row over h1 (row 80) in one weight: [96][512]
         auto wf = P.get(Dk + "fc_out.linear_layer.weight", (int64_t)NM * D), bf = P.get(Dk + "fc_out.linear_layer.bias", NM);
@@ -607,12 +622,12 @@ static int derive_planes(const std::vector<PlaneItem>& items, PlaneBytesFn bytes
     return 0;
 }
 
-// the decoder LSTM weights (layer 0 in its unmerged [content | u | h0] form, layer 1) and the BiLSTM's two directions, from the packed fp32
+// the decoder LSTM weights (layer 0 in its unmerged [content | u | h0] form and without its content columns, layer 1) and the BiLSTM's two directions, from the packed fp32
 // fragments, for the split-bf16 LSTM blocks (option "lstm_x3")
 static int derive_lstm_planes(l2s_model* m, hipStream_t s) {
     Weights& w = m->w;
     std::vector<PlaneItem> items;
-    for (SkW* k : {&w.lstm0, &w.lstm1, &w.whh[0], &w.whh[1]}) {
+    for (SkW* k : {&w.lstm0, &w.lstm1, &w.whh[0], &w.whh[1], &w.lstm0c}) {
         k->W3 = nullptr;
         items.push_back({k->W, k->tiles, k->K, &k->W3});
     }

@@ -58,6 +58,8 @@ int set_stamp_log(unsigned long long* log, long long cap) {
 //   4: [16]            K = 256   prenet layers, speaker LSTM recurrences (launch_skinny runs this layout on the general blocks: the LSTM epilogue there)
 //   5: [16|16|16|32]   K = 1280  LSTM0 on [content | prenet | a.V' | h0] (attention_proj hoisted into the prologue)
 //   6: [16|16+16|32]   K = 1024  LSTM0 on [content | prenet + a.V' | h0]: segment 1 summed from two sources by the loader (SkinnyP::a_sum)
+//   7: [0|16+16|32]    K = 768   LSTM0 on [prenet + a.V' | h0] (segment 0 empty, so that the summed segment stays segment 1): the content term comes from
+//                                the prologue's table and is added by the cell threads (SkinnyP::hoist_p; option "hoist_vproj" = 3)
 static int skinny_layout_of(const SkinnyP& p) {
     const int n0 = p.seg[0].nchunks, n1 = p.seg[1].nchunks, n2 = p.seg[2].nchunks, n3 = p.seg[3].nchunks;
     if (n0 == 32 && n1 == 0 && n2 == 0 && n3 == 0) return 1;
@@ -66,6 +68,7 @@ static int skinny_layout_of(const SkinnyP& p) {
     if (n0 == 16 && n1 == 0 && n2 == 0 && n3 == 0) return 4;
     if (n0 == 16 && n1 == 16 && n2 == 16 && n3 == 32) return 5;
     if (n0 == 16 && n1 == 16 && n2 == 32 && n3 == 0 && p.a_sum) return 6;
+    if (n0 == 0 && n1 == 16 && n2 == 32 && n3 == 0 && p.a_sum) return 7;
     return 0;
 }
 
@@ -112,6 +115,7 @@ template <> struct SkLay<2> { using T = SegLay<32, 32, 0, 0>; };
 template <> struct SkLay<3> { using T = SegLay<16, 16, 32, 32>; };
 template <> struct SkLay<5> { using T = SegLay<16, 16, 16, 32>; };
 template <> struct SkLay<6> { using T = SegLay<16, 16, 32, 0, true>; };
+template <> struct SkLay<7> { using T = SegLay<0, 16, 32, 0, true, true>; };
 template <int RT, int CT, int LAYID, int DEPTH, int WPS, bool IS_LSTM, bool ES = false>
 __global__ __launch_bounds__(512, WPS) void skinny_rcs_kernel(const SkinnyBatch batch, int mts) {
     if constexpr (ES) L2S_ES_RETURN(batch);
@@ -375,11 +379,11 @@ static SkForm skinny_form(const SkinnyBatch& bl, const Options& o, int chains, b
         }
     }
     // 2. LSTM launches on the bf16 matrix cores (1: four waves, 2: eight, 3: half-CU 4x2 blocks when chains overlap, 4: shared-panel blocks where they apply, else as 3)
-    int x3 = (o.rc_jb == 0 && kind == 2 && planes && (lay == 1 || lay == 2 || lay == 6)) ? o.lstm_x3 : 0;
+    int x3 = (o.rc_jb == 0 && kind == 2 && planes && (lay == 1 || lay == 2 || lay == 6 || lay == 7)) ? o.lstm_x3 : 0;
     if (x3 >= 3 && !overlap) x3 = 2;
     // 3. one activation panel per CU (skinny_sp_kernel) under the conditions of the half-CU 4x2 form, for the K = 1024 layouts and whole 4-tile column
     //    blocks; every other launch takes the form "lstm_x3" = 3 gives it
-    if (x3 == 4 && shape == 42 && !stamped_skinny && half_rows && (lay == 2 || lay == 6) && tiles4) {
+    if (x3 == 4 && shape == 42 && !stamped_skinny && half_rows && (lay == 2 || lay == 6 || lay == 7) && tiles4) {
         f.family = SKF_SP; f.lay = lay; f.grid = dim3(maxt / 4, (mts + 3) / 4, n); f.block = 512; f.lds = SKP_LDS_BYTES;
         return f;
     }
@@ -401,7 +405,7 @@ static SkForm skinny_form(const SkinnyBatch& bl, const Options& o, int chains, b
     }
     // 5. a summed segment (SkinnyP::a_sum) is formed by the straight-line four-wave LSTM blocks alone.  A forced "skinny_rc" / "skinny_rc_multi" outside {11, 21, 22,
     //    42} would fall through to skinny_kernel<cls>, which knows nothing of it: the caller (skinny_sum_supported) then keeps LSTM layer 0 on K = 1280 (hoist_vproj = 1)
-    if (any_sum && !(lay == 6 && kind == 2 && o.rc_jb == 0 && !stamped_skinny && skinny_shape_known(o.rc_shape) && skinny_shape_known(o.rc_shape_multi) && skinny_shape_known(shape))) {
+    if (any_sum && !((lay == 6 || lay == 7) && kind == 2 && o.rc_jb == 0 && !stamped_skinny && skinny_shape_known(o.rc_shape) && skinny_shape_known(o.rc_shape_multi) && skinny_shape_known(shape))) {
         f.error = "skinny: a summed segment needs the straight-line LSTM blocks (shape 11 / 21 / 22 / 42, default operand batching)";
         return f;
     }
@@ -424,7 +428,7 @@ static SkForm skinny_form(const SkinnyBatch& bl, const Options& o, int chains, b
             f.lay = lay; f.x3 = x3 != 0; f.lstm = !x3 && kind == 2; f.depth = f.family == SKF_RC4H ? 3 : 4;
             return f;
         }
-        if (shape != 11 && o.rc_jb == 28 && lay && (kind == 2 ? lay != 6 : kind == 1 && lay <= 2)) {      // the same straight-line form on eight waves
+        if (shape != 11 && o.rc_jb == 28 && lay && (kind == 2 ? lay < 6 : kind == 1 && lay <= 2)) {      // the same straight-line form on eight waves
             blocked(SKF_RCS, 8);
             f.lay = lay; f.lstm = kind == 2; f.depth = shape == 42 ? 4 : 6; f.wps = 2;
             return f;
@@ -471,6 +475,8 @@ constexpr int sk_key(int family, int shape, int a = 0, int b = 0, int c = 0) { r
 #define SK_ROW(key, NAME, ...) case key: return sk_fn(NAME<__VA_ARGS__, true>, NAME<__VA_ARGS__, false>);
 #define SK_X3_ROWS(FAM, NAME, RT, CT, DEPTH)      /* the split-bf16 LSTM blocks: layouts [32], [32|32], [16|16+16|32] */ \
     SK_ROW(sk_key(FAM, RT * 10 + CT, 1), NAME, RT, CT, 1, DEPTH) SK_ROW(sk_key(FAM, RT * 10 + CT, 2), NAME, RT, CT, 2, DEPTH) SK_ROW(sk_key(FAM, RT * 10 + CT, 6), NAME, RT, CT, 6, DEPTH)
+#define SK_X3_ROW7(FAM, NAME, RT, CT, DEPTH) SK_ROW(sk_key(FAM, RT * 10 + CT, 7), NAME, RT, CT, 7, DEPTH)      /* the K = 768 layout [0|16+16|32] with the hoisted content term */
+#define SK_RC4_ROWS7(RT, CT) SK_X3_ROW7(SKF_RC8X, skinny_rc8x_kernel, RT, CT, 4) SK_X3_ROW7(SKF_RC4X, skinny_rc4x_kernel, RT, CT, 4) SK_RC4_ROW(RT, CT, 7, 1)
 #define SK_RC4_ROW(RT, CT, LAY, LSTM) SK_ROW(sk_key(SKF_RC4, RT * 10 + CT, LAY, LSTM), skinny_rc4_kernel, RT, CT, LAY, 4, LSTM != 0)
 #define SK_RC4_ROWS(RT, CT)      /* the four-wave straight-line forms of one block shape */ \
     SK_X3_ROWS(SKF_RC8X, skinny_rc8x_kernel, RT, CT, 4) SK_X3_ROWS(SKF_RC4X, skinny_rc4x_kernel, RT, CT, 4)                                 \
@@ -496,6 +502,9 @@ static SkFn sk_row(const SkForm& f) {
         SK_RC4_ROWS(2, 1) SK_RCS_ROWS(2, 1, 6) SK_RC_ROWS(2, 1, 4, 2) SK_RC_ROWS(2, 1, 2, 2)
         SK_ROW(sk_key(SKF_GENERAL, 0, 4), skinny_kernel, 4) SK_ROW(sk_key(SKF_SPLIT, 0, 8, 2), skinny_kernel_split, 8, 2, 8) SK_ROW(sk_key(SKF_GENERAL, 0, 8), skinny_kernel, 8)
         SK_ROW(sk_key(SKF_SPLIT, 0, 12, 2), skinny_kernel_split, 12, 2, 6) SK_ROW(sk_key(SKF_SPLIT, 0, 12, 3), skinny_kernel_split, 12, 3, 8) SK_ROW(sk_key(SKF_GENERAL, 0, 12), skinny_kernel, 12)
+        // the K = 768 layout's instances, named last: the kernels above keep their order in the code object
+        case sk_key(SKF_SP, 0, 7): { const auto plain = skinny_sp_kernel<7, false>; return sk_fn(skinny_sp_kernel<7, true>, plain); }
+        SK_X3_ROW7(SKF_RC4H, skinny_rc4h_kernel, 4, 2, 3) SK_RC4_ROWS7(4, 2) SK_RC4_ROWS7(2, 2) SK_RC4_ROWS7(2, 1) SK_RC4_ROWS7(1, 1)
 #ifdef L2S_DIAG
         case sk_key(SKF_FLAT_TIMED, 22, 42, 1): return sk_fn(nullptr, skinny_flat_kernel<22, 42, 1, true>);
         case sk_key(SKF_GENERAL_TIMED, 0): return sk_fn(nullptr, skinny_kernel_timed);
@@ -513,10 +522,10 @@ static int skinny_dispatch(const SkForm& f, const SkinnyBatch& bl, int mts, hipS
     const SkFn row = sk_row(f);
     const void* const fn = bl.es_end && row.es ? row.es : row.plain;      // the early-stop twin where the launch carries a control block
     L2S_REQUIRE(fn != nullptr, "skinny: the form names no kernel instance");
-    if (f.family == SKF_SP) {      // 160 KB of dynamic LDS: the limit of the four instantiations is raised once
+    if (f.family == SKF_SP) {      // 160 KB of dynamic LDS: the limit of the six instantiations is raised once
         static const hipError_t attr = [] {
             hipError_t e = hipSuccess;
-            for (int lay : {2, 6})
+            for (int lay : {2, 6, 7})
                 for (const void* k : {sk_row(SkForm{SKF_SP, 0, 0, lay}).es, sk_row(SkForm{SKF_SP, 0, 0, lay}).plain}) e = std::max(e, hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, SKP_LDS_BYTES));
             return e;
         }();
@@ -551,6 +560,10 @@ int launch_skinny(const SkinnyBatch& b, hipStream_t s, const char* name, const O
         int m = (p.B + 15) / 16;
         L2S_REQUIRE(mts == 0 || mts == m, "skinny groups must share B");
         mts = m;
+        // the hoisted content term goes with the K = 768 layout and with nothing else: a table no block form would add, or a layout without its table, is refused
+        const bool lay7 = skinny_layout_of(p) == 7;
+        L2S_REQUIRE(lay7 ? (p.hoist_p && p.hoist_alpha && (p.hoist_pitch == 4 || p.hoist_pitch == 8) && p.epi == SK_LSTM && !p.pre && p.N == 16 * b.ntiles[i]) : !p.hoist_p,
+                    "skinny: the hoisted content term (SkinnyP::hoist_p, pitch 4 or 8) belongs to the LSTM launch on [0 | 16 + 16 | 32] chunks");
     }
     SkinnyBatch bl = b;
     for (int i = 0; i < bl.count; ++i) {
@@ -585,11 +598,16 @@ constexpr int ATT_PRE2_MAXC = 2;      // prenet layer 2: K = 256 = 16 * 8 waves 
         if (es) hipLaunchKernelGGL((NAME<SK_UNPACK TARGS, true>), __VA_ARGS__);                   \
         else hipLaunchKernelGGL((NAME<SK_UNPACK TARGS, false>), __VA_ARGS__);                     \
     } while (0)
+#define SK_CH_LAUNCH(ch, es, NAME, VL, S0, ...)                                                   \
+    do {                                                                                          \
+        if (ch) SK_ES_LAUNCH(es, NAME, (VL, S0, true), __VA_ARGS__);                              \
+        else SK_ES_LAUNCH(es, NAME, (VL, S0, false), __VA_ARGS__);                                \
+    } while (0)
 static int step_attn_form(const AttnP& at, int lds_values, int skip0, int chains) {      // 0 = neither, 1 = vl, 2 = vl and skip0
     const bool vl = lds_values && (lds_values >= 2 || at.B <= 128 || chains >= 2) && at.vp != nullptr && at.T <= 32;
     return vl && skip0 && (skip0 >= 2 || chains >= 2) ? 2 : vl ? 1 : 0;
 }
-template <bool VL, bool SKIP0 = false, bool ES = false>
+template <bool VL, bool SKIP0 = false, bool CH = false, bool ES = false>      // CH: the content blocks store alpha instead of alpha @ value (AttnP::alpha_out)
 __global__ __launch_bounds__(512) void step_attn_kernel(const StepB sb) {
     constexpr int SMF = ATT_SM_FLOATS + (VL && !SKIP0 ? ATT_VLDS_FLOATS : 0);
     __shared__ __attribute__((aligned(16))) float sm[SMF > SK_RED_FLOATS ? SMF : SK_RED_FLOATS];
@@ -601,7 +619,7 @@ __global__ __launch_bounds__(512) void step_attn_kernel(const StepB sb) {
     if (bid < nb) {
         attention_block<false, false, VL, SKIP0>(sb.at, bid, sm);
     } else if (bid < 2 * nb) {
-        content_block(sb.at, bid - nb, sm);
+        content_block<false, false, CH>(sb.at, bid - nb, sm);
     } else {
         const int j = bid - 2 * nb;
         const int tile = j % ptiles, mt = j / ptiles;
@@ -612,7 +630,7 @@ __global__ __launch_bounds__(512) void step_attn_kernel(const StepB sb) {
 
 // The same grid with per-row lengths (the *_masked entry points): lens[b] = len_b frames, lens[B + b] = m_b content slots of clip b inside rows laid
 // out for the padded T / m.  The length is block-uniform (one scalar load per block); the prenet blocks are the unmasked ones.
-template <bool VL, bool SKIP0 = false, bool ES = false>
+template <bool VL, bool SKIP0 = false, bool CH = false, bool ES = false>
 __global__ __launch_bounds__(512) void step_attn_masked_kernel(const StepB sb, const int* __restrict__ lens) {
     constexpr int SMF = ATT_SM_FLOATS + (VL && !SKIP0 ? ATT_VLDS_FLOATS : 0);
     __shared__ __attribute__((aligned(16))) float sm[SMF > SK_RED_FLOATS ? SMF : SK_RED_FLOATS];
@@ -627,7 +645,7 @@ __global__ __launch_bounds__(512) void step_attn_masked_kernel(const StepB sb, c
     } else if (bid < 2 * nb) {
         const int mb = min(max(lens[bid], 1), sb.at.m);             // lens[B + b] with b = bid - B
         L2S_PIN_S("s"(mb));
-        content_block<false, true>(sb.at, bid - nb, sm, nullptr, mb);
+        content_block<false, true, CH>(sb.at, bid - nb, sm, nullptr, mb);
     } else {
         const int j = bid - 2 * nb;
         const int tile = j % ptiles, mt = j / ptiles;
@@ -637,6 +655,7 @@ __global__ __launch_bounds__(512) void step_attn_masked_kernel(const StepB sb, c
 
 int launch_step_attn_masked(const AttnP& at, const SkinnyP& pre2, int pre2_tiles, const int* lens, hipStream_t s, int lds_values, int skip0) {
     L2S_REQUIRE(at.T <= ATT_MAXT && at.m >= 1 && at.m <= ATT_MAXM && lens, "attention sizes");
+    L2S_REQUIRE(!at.alpha_out || at.m <= CONTENT_HOIST_MAX_M, "attention: stored content weights are for clips of at most CONTENT_HOIST_MAX_M slots");
     L2S_REQUIRE(pre2.K <= 16 * SK_WAVES * ATT_PRE2_MAXC, "prenet layer 2 is a 256-wide layer");
     StepB sb;
     sb.at = at;
@@ -646,9 +665,10 @@ int launch_step_attn_masked(const AttnP& at, const SkinnyP& pre2, int pre2_tiles
     ProfScope ps("step_attention_prenet2_masked", s);
     const int form = step_attn_form(at, lds_values, skip0, chains_hint());
     const dim3 grid(2 * at.B + pre2_tiles * sb.mts);
-    if (form == 2) SK_ES_LAUNCH(sb.at.es_end, step_attn_masked_kernel, (true, true), grid, dim3(512), 0, s, sb, lens);
-    else if (form == 1) SK_ES_LAUNCH(sb.at.es_end, step_attn_masked_kernel, (true, false), grid, dim3(512), 0, s, sb, lens);
-    else SK_ES_LAUNCH(sb.at.es_end, step_attn_masked_kernel, (false, false), grid, dim3(512), 0, s, sb, lens);
+    const bool ch = at.alpha_out != nullptr;
+    if (form == 2) SK_CH_LAUNCH(ch, sb.at.es_end, step_attn_masked_kernel, true, true, grid, dim3(512), 0, s, sb, lens);
+    else if (form == 1) SK_CH_LAUNCH(ch, sb.at.es_end, step_attn_masked_kernel, true, false, grid, dim3(512), 0, s, sb, lens);
+    else SK_CH_LAUNCH(ch, sb.at.es_end, step_attn_masked_kernel, false, false, grid, dim3(512), 0, s, sb, lens);
     L2S_CHECK_HIP(hipGetLastError());
     return 0;
 }
@@ -674,6 +694,7 @@ void attn_set_timeline(unsigned long long* ts) { g_attn_ts = ts; }
 #endif
 int launch_step_attn(const AttnP& at, const SkinnyP& pre2, int pre2_tiles, hipStream_t s, int lds_values, int skip0) {
     L2S_REQUIRE(at.T <= ATT_MAXT && at.m >= 1 && at.m <= ATT_MAXM, "attention sizes");
+    L2S_REQUIRE(!at.alpha_out || at.m <= CONTENT_HOIST_MAX_M, "attention: stored content weights are for clips of at most CONTENT_HOIST_MAX_M slots");
     L2S_REQUIRE(pre2.K <= 16 * SK_WAVES * ATT_PRE2_MAXC, "prenet layer 2 is a 256-wide layer");
     StepB sb;
     sb.at = at;
@@ -683,13 +704,14 @@ int launch_step_attn(const AttnP& at, const SkinnyP& pre2, int pre2_tiles, hipSt
     ProfScope ps("step_attention_prenet2", s);
     const int form = step_attn_form(at, lds_values, skip0, chains_hint());
     const dim3 grid(2 * at.B + pre2_tiles * sb.mts);
+    const bool ch = at.alpha_out != nullptr;
 #ifdef L2S_DIAG
-    if (g_attn_ts && form) hipLaunchKernelGGL(step_attn_timed_kernel, grid, dim3(512), 0, s, sb, g_attn_ts);
+    if (g_attn_ts && form && !ch) hipLaunchKernelGGL(step_attn_timed_kernel, grid, dim3(512), 0, s, sb, g_attn_ts);
     else
 #endif
-    if (form == 2) SK_ES_LAUNCH(sb.at.es_end, step_attn_kernel, (true, true), grid, dim3(512), 0, s, sb);
-    else if (form == 1) SK_ES_LAUNCH(sb.at.es_end, step_attn_kernel, (true, false), grid, dim3(512), 0, s, sb);
-    else SK_ES_LAUNCH(sb.at.es_end, step_attn_kernel, (false, false), grid, dim3(512), 0, s, sb);
+    if (form == 2) SK_CH_LAUNCH(ch, sb.at.es_end, step_attn_kernel, true, true, grid, dim3(512), 0, s, sb);
+    else if (form == 1) SK_CH_LAUNCH(ch, sb.at.es_end, step_attn_kernel, true, false, grid, dim3(512), 0, s, sb);
+    else SK_CH_LAUNCH(ch, sb.at.es_end, step_attn_kernel, false, false, grid, dim3(512), 0, s, sb);
     L2S_CHECK_HIP(hipGetLastError());
     return 0;
 }

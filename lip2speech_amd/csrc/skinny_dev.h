@@ -87,10 +87,11 @@ __device__ __forceinline__ f32x4 mfma4(const float4& a, const float4& w, f32x4 a
 // chunk belongs to is then a constant, and the block's load-issue phase loses its per-chunk compare / branch / 64-bit address chains
 // (24 loads used to sit behind ~250 scalar instructions and ~50 branches per wave).  SegRuntime keeps the general path.
 struct SegRuntime { static constexpr bool STATIC = false; static constexpr int n0 = 0, n1 = 0, n2 = 0, n3 = 0, NC = 0; };
-template <int A0, int A1, int A2, int A3, bool SUM1_ = false>
+template <int A0, int A1, int A2, int A3, bool SUM1_ = false, bool HOIST_ = false>
 struct SegLay {
     static constexpr bool STATIC = true;
     static constexpr bool SUM1 = SUM1_;          // segment 1 has a second source (SkinnyP::a_sum) added by the loader
+    static constexpr bool HOIST = HOIST_;        // LSTM cells add the hoisted content term sum_j alpha_j P_j to their gates (SkinnyP::hoist_p; sk_hoist_* below)
     static constexpr int n0 = A0, n1 = A1, n2 = A2, n3 = A3, NC = A0 + A1 + A2 + A3;
     static_assert(A0 % SK_WAVES == 0 && A1 % SK_WAVES == 0 && A2 % SK_WAVES == 0 && A3 % SK_WAVES == 0, "segment boundaries on wave multiples");
 };
@@ -566,6 +567,65 @@ __device__ __forceinline__ void skx_split8(const float4& a, const float4& b, skx
 // {4u + g} (four rows per half, their low column bits made distinct by the XOR) - neither side shares a bank.  The [16][17] layout cost every
 // write and every gate read a second LDS cycle (SQ_LDS_BANK_CONFLICT = half of SQ_LDS_IDX_ACTIVE in the LSTM launches).
 __device__ __forceinline__ int sk_red_idx(int slot, int row, int col) { return slot * 256 + ((row ^ ((row >> 2) & 1)) << 4) + (col ^ ((row >> 1) & 3)); }
+// The hoisted content term of an LSTM cell's gates (LAY::HOIST; option "hoist_vproj" = 3): W_ih[:, content] (alpha @ value) = sum_j alpha_j P_j with
+// P_j = W_ih[:, content] value_j, the prologue's table.  A cell thread requests its row's alpha and the first four terms of its four gates (five 16-byte
+// buffer loads from always-valid addresses: nothing conditional between the operand loads and the MFMAs, one 32-bit offset per stream) and folds them - one
+// fmaf chain per gate, j ascending from zero - at a later point of the K loop where they have landed anyway (the loads return in order, and that point
+// waits for a younger one), so that they hold registers only in between.  A thread with two cells requests the second cell's terms where it folds the first's:
+// twenty registers in flight, not forty (the 4x2 and shared-panel blocks have none to spare).  Slots 4 - 7 (pitch 8: clips of 35 - 62 frames) are fetched
+// and folded by the cell thread in its epilogue, behind a block-uniform branch (no branch inside the K loop; those clips pay one more round trip per block).  The sum enters a gate AFTER the eight K-slice partials and BEFORE the bias, in every block form: the
+// forms keep giving the same bits as each other.
+struct SkHoist { float4 al; float4 p[4]; };
+__device__ __forceinline__ SkHoist sk_hoist_request(__amdgpu_buffer_rsrc_t rs_p, __amdgpu_buffer_rsrc_t rs_a, int pitch, int b, int row0, int N) {
+    const int po = (b * N + row0) * pitch * 4;      // bytes: at most 256 clips x 2048 rows x 8 slots
+    SkHoist h;
+    h.al = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rs_a, b * (CONTENT_HOIST_MAX_M * 4), 0, 0));
+#pragma unroll
+    for (int g = 0; g < 4; ++g) h.p[g] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rs_p, po, g * pitch * 4, 0));
+    return h;
+}
+__device__ __forceinline__ void sk_hoist_fold(const SkHoist& h, float out[4]) {
+#pragma unroll
+    for (int g = 0; g < 4; ++g) out[g] = fmaf(h.al.w, h.p[g].w, fmaf(h.al.z, h.p[g].z, fmaf(h.al.y, h.p[g].y, fmaf(h.al.x, h.p[g].x, 0.f))));
+}
+// slots 4 - 7 (pitch 8), by the cell thread in its epilogue: the chain goes on where sk_hoist_fold left it
+__device__ __forceinline__ void sk_hoist_fold_hi(__amdgpu_buffer_rsrc_t rs_p, __amdgpu_buffer_rsrc_t rs_a, int pitch, int b, int row0, int N, float out[4]) {
+    if (pitch > 4) {
+        const int po = (b * N + row0) * pitch * 4;
+        const float4 a1 = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rs_a, b * (CONTENT_HOIST_MAX_M * 4), 16, 0));
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const float4 q = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rs_p, po, g * pitch * 4 + 16, 0));
+            out[g] = fmaf(a1.w, q.w, fmaf(a1.z, q.z, fmaf(a1.y, q.y, fmaf(a1.x, q.x, out[g]))));
+        }
+    }
+}
+
+#define L2S_RCS_CELL_OPERANDS()      /* the cell threads' operand requests: straight-line text, at the block's start or (hoisted term) inside the K loop */ \
+_Pragma("unroll") \
+    for (int cr = 0; cr < NCR; ++cr) { \
+        const int q2 = (tid >> 6) + NW * cr; \
+        const int t2 = tp * CT + q2 % CT, rt2 = mg * RT + q2 / CT; \
+        const int b2 = rt2 * 16 + (t64 >> 2); \
+        cell_on[cr] = IS_LSTM && q2 < NT && t2 < ntiles && rt2 < mts && b2 < nB; \
+        if constexpr (IS_LSTM) { \
+            const int q2c = min(q2, NT - 1); \
+            const int t2c = min(tp * CT + q2c % CT, ntiles - 1), rt2c = min(mg * RT + q2c / CT, mts - 1); \
+            const int b2c = min(rt2c * 16 + (t64 >> 2), nB - 1), u2 = t64 & 3; \
+            pf_c[cr] = c_in[frag16_index(b2c, t2c * 4 + u2, H)]; \
+            const float4 b4 = *reinterpret_cast<const float4*>(bias_p + (bias ? t2c * 16 + 4 * u2 : 0)); \
+            pf_gb[cr][0] = bias ? b4.x : 0.f; pf_gb[cr][1] = bias ? b4.y : 0.f; pf_gb[cr][2] = bias ? b4.z : 0.f; pf_gb[cr][3] = bias ? b4.w : 0.f; \
+_Pragma("unroll") \
+            for (int g = 0; g < 4; ++g) { \
+                if constexpr (LAY::HOIST) { pf_gp[cr][g] = 0.f; continue; } \
+                const float va = add_p[pre ? (int64_t)b2c * ld_pre + g * H + t2c * 4 + u2 : 0]; \
+                pf_gp[cr][g] = pre ? va : 0.f; \
+            } \
+        } else { \
+            pf_c[cr] = 0.f; \
+        } \
+    }
+
 // SEQ (four waves): a wave plays its two K slices ONE AFTER THE OTHER instead of chunk by chunk in turn - the first slice's partial tiles go to the
 // reduction buffer as soon as its chunks are through and the accumulators start again from zero for the second.  Per slice the chunks, their order
 // and the two alternating accumulators are the interleaved form's, so every partial sum that reaches the reduction is the same bits; what changes
@@ -578,6 +638,7 @@ __device__ __forceinline__ void skinny_block_rcs(const SkinnyP& p, int tp, int m
     static_assert(NW == 8 || NW == 4, "eight waves, or four that each play two");
     static_assert(!X3 || (IS_LSTM && (LAY::NC / SK_WAVES) % 2 == 0), "the split-bf16 form: LSTM blocks, whole chunk pairs per slice");
     static_assert(!SEQ || NW == 4, "slices one after the other: the four-wave form");
+    static_assert(!LAY::HOIST || (IS_LSTM && !TRAIN), "the hoisted content term: the inference step's LSTM cells");
     constexpr int VW = SK_WAVES / NW, NH = NW / 4;       // K slices per real wave; 256-thread epilogue teams
     constexpr int VA = SEQ ? 1 : VW;                     // accumulator sets per wave
     L2S_STAMP(0);
@@ -691,28 +752,23 @@ __device__ __forceinline__ void skinny_block_rcs(const SkinnyP& p, int tp, int m
     const int t64 = tid & 63;
     float pf_c[NCR], pf_gb[IS_LSTM ? NCR : 1][4], pf_gp[IS_LSTM ? NCR : 1][4];
     bool cell_on[NCR];
-#pragma unroll
-    for (int cr = 0; cr < NCR; ++cr) {
-        const int q2 = (tid >> 6) + NW * cr;
-        const int t2 = tp * CT + q2 % CT, rt2 = mg * RT + q2 / CT;
-        const int b2 = rt2 * 16 + (t64 >> 2);
-        cell_on[cr] = IS_LSTM && q2 < NT && t2 < ntiles && rt2 < mts && b2 < nB;
-        if constexpr (IS_LSTM) {
-            const int q2c = min(q2, NT - 1);
-            const int t2c = min(tp * CT + q2c % CT, ntiles - 1), rt2c = min(mg * RT + q2c / CT, mts - 1);
-            const int b2c = min(rt2c * 16 + (t64 >> 2), nB - 1), u2 = t64 & 3;
-            pf_c[cr] = c_in[frag16_index(b2c, t2c * 4 + u2, H)];
-            const float4 b4 = *reinterpret_cast<const float4*>(bias_p + (bias ? t2c * 16 + 4 * u2 : 0));      // the unit's four gate rows are adjacent (permuted weight rows)
-            pf_gb[cr][0] = bias ? b4.x : 0.f; pf_gb[cr][1] = bias ? b4.y : 0.f; pf_gb[cr][2] = bias ? b4.z : 0.f; pf_gb[cr][3] = bias ? b4.w : 0.f;
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const float va = add_p[pre ? (int64_t)b2c * ld_pre + g * H + t2c * 4 + u2 : 0];
-                pf_gp[cr][g] = pre ? va : 0.f;
-            }
-        } else {
-            pf_c[cr] = 0.f;
-        }
-    }
+    static_assert(!LAY::HOIST || NCR <= 2, "the hoisted term: at most two cells per thread");
+    const float* const hp = LAY::HOIST ? p.hoist_p : W; const float* const ha = LAY::HOIST ? p.hoist_alpha : W; const int hpitch = LAY::HOIST ? p.hoist_pitch : 0;
+    if constexpr (LAY::HOIST) L2S_PIN_S("s"(hp), "s"(ha), "s"(hpitch));
+    const __amdgpu_buffer_rsrc_t rs_hp = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(hp), 0, 0x7fffffff, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_ha = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(ha), 0, 0x7fffffff, 0x00020000);
+    SkHoist hreq;
+    float hsum[LAY::HOIST ? NCR : 1][4];
+    auto hoist_at = [&](int cr, int& hb, int& hrow) {      // cell cr of this thread: its (clamped) row, its unit's first packed gate row
+        const int q2c = min((tid >> 6) + NW * cr, NT - 1);
+        const int t2c = min(tp * CT + q2c % CT, ntiles - 1), rt2c = min(mg * RT + q2c / CT, mts - 1);
+        hb = min(rt2c * 16 + (t64 >> 2), nB - 1); hrow = t2c * 16 + 4 * (t64 & 3);
+    };
+    auto hoist_request = [&](int cr) { int hb, hrow; hoist_at(cr, hb, hrow); hreq = sk_hoist_request(rs_hp, rs_ha, hpitch, hb, hrow, N); };
+    auto hoist_fold = [&](int cr) { sk_hoist_fold(hreq, hsum[cr]); };
+    auto hoist_fold_hi = [&](int cr) { int hb, hrow; hoist_at(cr, hb, hrow); sk_hoist_fold_hi(rs_hp, rs_ha, hpitch, hb, hrow, N, hsum[cr]); };
+    // with the hoisted term the cell operands are requested in the K loop, after the first cell's terms are folded: the 4x2 blocks cannot hold both from here on
+    if constexpr (LAY::HOIST) { hoist_request(0); } else { L2S_RCS_CELL_OPERANDS() }
     __builtin_amdgcn_sched_barrier(0);
     L2S_STAMP(2);
 
@@ -768,6 +824,13 @@ __device__ __forceinline__ void skinny_block_rcs(const SkinnyP& p, int tp, int m
             load_chunk(std::integral_constant<int, j + PRE>{});
             __builtin_amdgcn_sched_barrier(0);
         }
+        if constexpr (LAY::HOIST && j == (PRE < TC ? PRE : TC - 1)) {      // this chunk was requested after the first cell's terms: they have landed
+            hoist_fold(0);
+            __builtin_amdgcn_sched_barrier(0);
+            if constexpr (NCR > 1) hoist_request(1);
+            L2S_RCS_CELL_OPERANDS()
+            __builtin_amdgcn_sched_barrier(0);
+        }
         if constexpr (SEQ && jj == MAXC - 1 && hs + 1 < VW) {      // this slice is through: its partial tiles to the reduction buffer, accumulators from zero again
             const int col = lane & 15, rb = 4 * (lane >> 4);
 #pragma unroll
@@ -780,6 +843,7 @@ __device__ __forceinline__ void skinny_block_rcs(const SkinnyP& p, int tp, int m
         if constexpr (TIMED && j == 0) { asm volatile("s_nop 0" :: "v"(acc[0][0][0][0])); L2S_STAMP(3); }      // first operands landed, first chunk computed
     });
     if constexpr (TIMED) { asm volatile("s_nop 0" :: "v"(acc[0][0][0][0]), "v"(acc[NT - 1][1][VA - 1][0])); }
+    if constexpr (LAY::HOIST && NCR > 1) hoist_fold(1);
     L2S_STAMP(4);
     // D layout: col = lane&15, row = 4*(lane>>4) + r
     {
@@ -833,11 +897,13 @@ __device__ __forceinline__ void skinny_block_rcs(const SkinnyP& p, int tp, int m
         const int b2 = rt2 * 16 + (t64 >> 2), unit2 = t2 * 4 + (t64 & 3);
         const int r2 = t64 >> 2, u2 = t64 & 3;
         float g4[4];
+        if constexpr (LAY::HOIST) hoist_fold_hi(cr);
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
             float v = 0.f;
 #pragma unroll
             for (int wv = 0; wv < SK_WAVES; ++wv) v += red[sk_red_idx(wv * NT + q2, r2, 4 * u2 + g)];
+            if constexpr (LAY::HOIST) v += hsum[cr][g];      // the content term: after the K-slice partials, before the bias
             v += pf_gb[cr][g];
             v += pf_gp[cr][g];
             g4[g] = v;
@@ -861,6 +927,26 @@ __device__ __forceinline__ void skinny_block_rcs(const SkinnyP& p, int tp, int m
     if constexpr (TIMED) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
     L2S_STAMP(7);
 }
+
+#define L2S_SP_CELL_OPERANDS()      /* the same for skinny_block_sp */ \
+_Pragma("unroll") \
+    for (int cr = 0; cr < NCR; ++cr) { \
+        const int q2 = wave + NW * cr; \
+        const int t2 = tph * CT + q2 % CT, rt2 = mg * RT + q2 / CT; \
+        const int b2 = rt2 * 16 + (t64 >> 2); \
+        cell_on[cr] = t2 < ntiles && rt2 < mts && b2 < nB; \
+        const int t2c = min(t2, ntiles - 1), rt2c = min(rt2, mts - 1); \
+        const int b2c = min(rt2c * 16 + (t64 >> 2), nB - 1), u2 = t64 & 3; \
+        pf_c[cr] = c_in[frag16_index(b2c, t2c * 4 + u2, H)]; \
+        const float4 b4 = *reinterpret_cast<const float4*>(bias_p + (bias ? t2c * 16 + 4 * u2 : 0)); \
+        pf_gb[cr][0] = bias ? b4.x : 0.f; pf_gb[cr][1] = bias ? b4.y : 0.f; pf_gb[cr][2] = bias ? b4.z : 0.f; pf_gb[cr][3] = bias ? b4.w : 0.f; \
+_Pragma("unroll") \
+        for (int g = 0; g < 4; ++g) { \
+            if constexpr (LAY::HOIST) { pf_gp[cr][g] = 0.f; continue; } \
+            const float va = add_p[pre ? (int64_t)b2c * ld_pre + g * H + t2c * 4 + u2 : 0]; \
+            pf_gp[cr][g] = pre ? va : 0.f; \
+        } \
+    }
 
 // Shared activation panel (option "lstm_x3" = 4): ONE eight-wave block per CU owns 4 row tiles x 4 column tiles - the two column-neighbouring half-CU
 // 4x2 blocks (SEQ, X3) that used to share the CU, fused.  Waves w and w + 4 (the same SIMD) are the two column halves of K slices w and w + 4; each
@@ -970,29 +1056,30 @@ __device__ __forceinline__ void skinny_block_sp(const SkinnyP& p, int tp, int mg
     const int nB = p.B, H = p.H;
     const float* const bias = p.bias; const float* const pre = p.pre; const int64_t ld_pre = p.ld_pre; const float* const c_in = p.c_in;
     L2S_PIN_S("s"(nB), "s"(H), "s"(bias), "s"(pre), "s"(ld_pre), "s"(c_in));
+    const float* const hp = LAY::HOIST ? p.hoist_p : W; const float* const ha = LAY::HOIST ? p.hoist_alpha : W;
+    const int hpitch = LAY::HOIST ? p.hoist_pitch : 0, hN = LAY::HOIST ? p.N : 0;
+    if constexpr (LAY::HOIST) L2S_PIN_S("s"(hp), "s"(ha), "s"(hpitch), "s"(hN));
+    const __amdgpu_buffer_rsrc_t rs_hp = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(hp), 0, 0x7fffffff, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_ha = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(ha), 0, 0x7fffffff, 0x00020000);
     const float* const bias_p = bias ? bias : W;
     const float* const add_p = pre ? pre : W;
     constexpr int NCR = NT / NW;
     const int t64 = tid & 63;
     float pf_c[NCR], pf_gb[NCR][4], pf_gp[NCR][4];
     bool cell_on[NCR];
-#pragma unroll
-    for (int cr = 0; cr < NCR; ++cr) {
+    static_assert(NCR == 2, "two cells per thread: the second one's hoisted terms are requested where the first one's are folded");
+    SkHoist hreq;
+    float hsum[LAY::HOIST ? NCR : 1][4];
+    auto hoist_at = [&](int cr, int& hb, int& hrow) {      // cell cr of this thread: its (clamped) row, its unit's first packed gate row
         const int q2 = wave + NW * cr;
-        const int t2 = tph * CT + q2 % CT, rt2 = mg * RT + q2 / CT;
-        const int b2 = rt2 * 16 + (t64 >> 2);
-        cell_on[cr] = t2 < ntiles && rt2 < mts && b2 < nB;
-        const int t2c = min(t2, ntiles - 1), rt2c = min(rt2, mts - 1);
-        const int b2c = min(rt2c * 16 + (t64 >> 2), nB - 1), u2 = t64 & 3;
-        pf_c[cr] = c_in[frag16_index(b2c, t2c * 4 + u2, H)];
-        const float4 b4 = *reinterpret_cast<const float4*>(bias_p + (bias ? t2c * 16 + 4 * u2 : 0));
-        pf_gb[cr][0] = bias ? b4.x : 0.f; pf_gb[cr][1] = bias ? b4.y : 0.f; pf_gb[cr][2] = bias ? b4.z : 0.f; pf_gb[cr][3] = bias ? b4.w : 0.f;
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const float va = add_p[pre ? (int64_t)b2c * ld_pre + g * H + t2c * 4 + u2 : 0];
-            pf_gp[cr][g] = pre ? va : 0.f;
-        }
-    }
+        const int t2c = min(tph * CT + q2 % CT, ntiles - 1), rt2c = min(mg * RT + q2 / CT, mts - 1);
+        hb = min(rt2c * 16 + (t64 >> 2), nB - 1); hrow = t2c * 16 + 4 * (t64 & 3);
+    };
+    auto hoist_request = [&](int cr) { int hb, hrow; hoist_at(cr, hb, hrow); hreq = sk_hoist_request(rs_hp, rs_ha, hpitch, hb, hrow, hN); };
+    auto hoist_fold = [&](int cr) { sk_hoist_fold(hreq, hsum[cr]); };
+    auto hoist_fold_hi = [&](int cr) { int hb, hrow; hoist_at(cr, hb, hrow); sk_hoist_fold_hi(rs_hp, rs_ha, hpitch, hb, hrow, hN, hsum[cr]); };
+    // with the hoisted term the cell operands are requested with the second cell's terms, in the K loop: the block has no registers to hold both from here on
+    if constexpr (LAY::HOIST) { hoist_request(0); } else { L2S_SP_CELL_OPERANDS() }
     __builtin_amdgcn_sched_barrier(0);
     publish(std::integral_constant<int, 0>{});
     if constexpr (NST > 2) load_a(std::integral_constant<int, 2>{});
@@ -1030,6 +1117,10 @@ __device__ __forceinline__ void skinny_block_sp(const SkinnyP& p, int tp, int mg
             load_w(std::integral_constant<int, st + DW>{});
             __builtin_amdgcn_sched_barrier(0);
         }
+        if constexpr (LAY::HOIST && st == (DW < NST ? DW : NST - 1)) {      // this step's planes were requested after the first cell's terms: they have landed
+            hoist_fold(0);
+            __builtin_amdgcn_sched_barrier(0); hoist_request(1); L2S_SP_CELL_OPERANDS() __builtin_amdgcn_sched_barrier(0);
+        }
         if constexpr (st == NPI - 1) {               // the first slice is through: its partial tiles to the reduction buffer, accumulators from zero again
             const int col = lane & 15, rb = 4 * (lane >> 4);
 #pragma unroll
@@ -1048,6 +1139,7 @@ __device__ __forceinline__ void skinny_block_sp(const SkinnyP& p, int tp, int mg
 #pragma unroll
             for (int r = 0; r < 4; ++r) red_hi[sk_red_idx(wave * NT + q, rb + r, col)] = acc[q][0][r] + acc[q][1][r];
     }
+    if constexpr (LAY::HOIST) hoist_fold(1);
     __syncthreads();
 #pragma unroll
     for (int cr = 0; cr < NCR; ++cr) {
@@ -1057,11 +1149,13 @@ __device__ __forceinline__ void skinny_block_sp(const SkinnyP& p, int tp, int mg
         const int b2 = rt2 * 16 + (t64 >> 2), unit2 = t2 * 4 + (t64 & 3);
         const int r2 = t64 >> 2, u2 = t64 & 3;
         float g4[4];
+        if constexpr (LAY::HOIST) hoist_fold_hi(cr);
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
             float v = 0.f;
 #pragma unroll
             for (int wv = 0; wv < SK_WAVES; ++wv) v += (wv < NW ? red_lo : red_hi)[sk_red_idx((wv & (NW - 1)) * NT + q2, r2, 4 * u2 + g)];
+            if constexpr (LAY::HOIST) v += hsum[cr][g];      // the content term: after the K-slice partials, before the bias (as in skinny_block_rcs)
             v += pf_gb[cr][g];
             v += pf_gp[cr][g];
             g4[g] = v;
@@ -1367,9 +1461,13 @@ __device__ __forceinline__ void content_block_long(const AttnP& p, int b, float*
 // Content.forward (decoder.py:262-271) for one batch row: alpha = softmax_m(SiLU(..)*tau_c . key), cc = alpha @ value
 // (m <= 16: two key rows per wave and the values in registers; longer clips take content_block_long)
 // ML: the clip uses the first `mb` <= m of its m slots (rows laid out for m): soft-max and alpha @ value over those, as a solo call with m = mb
-template <bool TRAIN = false, bool ML = false>
+// CH (option "hoist_vproj" = 3; m <= CONTENT_HOIST_MAX_M): the block stores its soft-max weights alpha[b][0 .. CONTENT_HOIST_MAX_M) - the expression the fmaf
+// chain below multiplies by, zeros past the clip's slots - INSTEAD of cc = alpha @ value: the values are not fetched; LSTM layer 0's cell threads
+// add W_ih[:, content] cc as sum_j alpha_j P_j (sk_hoist_fold)
+template <bool TRAIN = false, bool ML = false, bool CH = false>
 __device__ __forceinline__ void content_block(const AttnP& p, int b, float* sm, const AttnTrain* tr = nullptr, int mb = 0) {
-    if (p.m > 16) { content_block_long<TRAIN, ML>(p, b, sm, tr, mb); return; }
+    static_assert(!CH || !TRAIN, "the stored soft-max weights: the inference step");
+    if (!CH && p.m > 16) { content_block_long<TRAIN, ML>(p, b, sm, tr, mb); return; }
     float* qs = sm;                  // 256
     float* csc = sm + 512;           // 16
     const int tid = threadIdx.x, lane = tid & 63;
@@ -1391,8 +1489,10 @@ __device__ __forceinline__ void content_block(const AttnP& p, int b, float* sm, 
         if (i < me) kk[r] = *reinterpret_cast<const float4*>(keyb + (int64_t)i * 256);
     }
     float vals[16];
+    if constexpr (!CH) {
 #pragma unroll
-    for (int i = 0; i < 16; ++i) vals[i] = i < me ? valb[(int64_t)i * 256] : 0.f;
+        for (int i = 0; i < 16; ++i) vals[i] = i < me ? valb[(int64_t)i * 256] : 0.f;
+    }
     if (tid < 256) qs[tid] = qv * tau_c;
     __syncthreads();
     const float* q4 = qs + lane * 4;
@@ -1411,6 +1511,10 @@ __device__ __forceinline__ void content_block(const AttnP& p, int b, float* sm, 
         for (int i = 0; i < me; ++i) cmx = fmaxf(cmx, csc[i]);
         float csum = 0.f;
         for (int i = 0; i < me; ++i) csum += expf(csc[i] - cmx);
+        if constexpr (CH) {
+            if (tid < CONTENT_HOIST_MAX_M) p.alpha_out[(int64_t)b * CONTENT_HOIST_MAX_M + tid] = tid < me ? expf(csc[min(tid, me - 1)] - cmx) / csum : 0.f;
+            return;
+        }
         float o = 0.f;
 #pragma unroll
         for (int i = 0; i < 16; ++i)

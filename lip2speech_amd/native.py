@@ -50,7 +50,7 @@ ABI_SYMBOLS = (
 )
 # what include/l2s_diag.h adds: exported by libl2s_diag.so only
 DIAG_SYMBOLS = (
-    "l2s_op_gemm", "l2s_op_conv1d", "l2s_op_gemm_ex", "l2s_op_conv1d_ex", "l2s_op_conv1d_bwd", "l2s_op_frontend", "l2s_op_launch_chain", "l2s_op_launch_chain2", "l2s_op_skinny_timeline", "l2s_op_attn_timeline", "l2s_op_flat_timeline", "l2s_op_pdecode_timeline", "l2s_op_gemm_x3_timeline", "l2s_op_fused_unit_timeline", "l2s_op_lstm_cell_chain", "l2s_op_step_attn_chain", "l2s_op_stamp_log", "l2s_op_skinny_form", "l2s_op_step_site", "l2s_op_skinny",
+    "l2s_op_gemm", "l2s_op_conv1d", "l2s_op_gemm_ex", "l2s_op_conv1d_ex", "l2s_op_conv1d_bwd", "l2s_op_frontend", "l2s_op_launch_chain", "l2s_op_launch_chain2", "l2s_op_skinny_timeline", "l2s_op_attn_timeline", "l2s_op_flat_timeline", "l2s_op_pdecode_timeline", "l2s_op_gemm_x3_timeline", "l2s_op_fused_unit_timeline", "l2s_op_lstm_cell_chain", "l2s_op_step_attn_chain", "l2s_op_stamp_log", "l2s_op_skinny_form", "l2s_op_step_site", "l2s_op_skinny", "l2s_op_skinny_hoist",
     "l2s_op_face_conv2d", "l2s_op_face_taps", "l2s_op_speaker_taps", "l2s_op_speaker_taps_packed", "l2s_op_encoder_taps",
     "l2s_op_gemm_bwd", "l2s_op_gemm_bwd_recorder",
 )
@@ -59,7 +59,7 @@ DIAG_SYMBOLS = (
 DIAG_OPTIONS = frozenset(("overlap_postnet", "fuse_trunk", "fuse_s2", "skinny_static", "skinny_sized", "skinny_split", "skinny_split8", "skinny_rc", "skinny_rc_jb",
                           "skinny_rc_multi", "skinny_flat", "hoist_vproj", "attn_lds", "flat_half", "half_min_mts", "gemm_x3_dma", "flat_xcd", "attn_skip0", "trunk_chain", "frontend_solo"))
 
-ST_K, ST_V, ST_CKEY, ST_CVAL, ST_ECELL, ST_H, ST_C, ST_ENC, ST_STOPC = range(9)
+ST_K, ST_V, ST_CKEY, ST_CVAL, ST_ECELL, ST_H, ST_C, ST_ENC, ST_STOPC, ST_VP, ST_CP = range(11)
 
 _lib = None
 _diag = None
@@ -290,6 +290,7 @@ def _bind_diag(L: ctypes.CDLL) -> None:
     L.l2s_op_skinny_form.argtypes = [_vp, _i, ctypes.POINTER(ctypes.c_int), _i, _i, _i, _i, ctypes.c_char_p, _i]
     L.l2s_op_step_site.argtypes = [_vp, ctypes.c_char_p, _i, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
     L.l2s_op_skinny.argtypes = [_vp, _i, ctypes.POINTER(SkinnyGroup), _i, _vp, _i, _vp]
+    L.l2s_op_skinny_hoist.argtypes = [_vp, ctypes.POINTER(SkinnyGroup), _vp, _vp, _i, _i, _vp]
     L.l2s_op_face_conv2d.argtypes = [_fp, _i64, _i, _i, _i, _i, _fp, _fp, _fp, _fp, _i, _fp, _i, _i, _i, _i, _i, _i, _vp]
     L.l2s_op_face_taps.argtypes = [_vp, _fp, _i64, _i, _vp, _fp, _fp, _vp, _i64, _vp]
     L.l2s_op_speaker_taps.argtypes = [_vp, _fp, _i, _i, _vp, _fp, _vp, _i64, _vp]
@@ -1293,6 +1294,8 @@ def op_skinny(model, groups, B: int, es=None, refused: Optional[list] = None, pr
       SK_LSTM: "H", "c_prev" [B][H], optional "pre" [B][4H], "h_out_K" / "h_out_off" (default H / 0), "h_seq" / "h_plain" (True: also the plain copies);
       SK_MEL: "stop_const" [B], "yfrag" (True: also the frag16 copy of the frame).
     `es` = (end, step): the early-stop twin of the kernel with *es_end = end and es_step = step.
+    A single SK_LSTM group with "hoist_p" [B][4H][pitch] (rows in PyTorch's gate order, permuted here like W) and "hoist_alpha" [B][8] goes through
+    `l2s_op_skinny_hoist`: the K = 768 layout of the decode step ("a": [B][0], [B][256], [B][512] with "a_sum") with the hoisted content term.
     Every output buffer is filled with SKINNY_SENTINEL first and returned WHOLE, unpacked to row-major with its padded rows and columns, so that a caller
     sees unwritten elements and stray writes: per group a dict of "out" [pad16(B)][ldo]; "c_out" [pad16(B)][H], "h_out" [pad16(B)][h_out_K], "h_seq"
     [pad16(B)][H + 8], "h_plain" [pad16(B)][H + 4]; "mel" [pad16(B)][88], "stop" [pad16(B)][2], "yfrag" [pad16(B)][80].
@@ -1341,7 +1344,14 @@ def op_skinny(model, groups, B: int, es=None, refused: Optional[list] = None, pr
                 g.yfrag = b["yfrag"].data_ptr()
         bufs.append(b)
     es_end = None if es is None else torch.tensor([es[0]], dtype=torch.int32, device=dev)
-    rc = D.l2s_op_skinny(model, len(groups), arr, B, _ptr(es_end), 0 if es is None else es[1], _stream())
+    if groups[0].get("hoist_p") is not None:
+        assert len(groups) == 1 and es is None and groups[0]["epi"] == SK_LSTM
+        hp = _f32(groups[0]["hoist_p"])[:, lstm_perm_rows(groups[0]["H"], dev)].contiguous()
+        ha = _f32(groups[0]["hoist_alpha"])
+        assert ha.shape == (B, 8) and hp.shape[:2] == (B, 4 * groups[0]["H"]) and hp.shape[2] in (4, 8)
+        rc = D.l2s_op_skinny_hoist(model, arr, _ptr(hp), _ptr(ha), hp.shape[2], B, _stream())
+    else:
+        rc = D.l2s_op_skinny(model, len(groups), arr, B, _ptr(es_end), 0 if es is None else es[1], _stream())
     if rc != 0:
         text = D.l2s_last_error().decode("utf-8", "replace")
         if refused is None:
