@@ -2,4 +2,4 @@
 corpus loaders live in ``datasets.lrw`` / ``.grid`` / ``.avspeech`` / ``.wild`` like the reference's sub-packages).
 NOTE: a HuggingFace ``datasets`` wheel is installed in this image - the repository root must come first on sys.path."""
 from lip2speech_amd.datasets import (FaceAugmentation, LRW, MelSpec2Audio, MelSpectrogram,  # noqa: F401
-                                     test_collate_fn_pad, train_collate_fn_pad)
+                                     align_and_crop_face, test_collate_fn_pad, train_collate_fn_pad)

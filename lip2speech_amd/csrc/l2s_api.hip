@@ -954,6 +954,12 @@ int l2s_resize_normalise(const uint8_t* packed_u8, int64_t packed_bytes, const l
     return launch_resize_normalise(packed_u8, packed_bytes, jobs, n, mode, B, T, oh, ow, out, (hipStream_t)stream);
 }
 
+int l2s_align_check(const l2s_align_job* jobs, int n, int64_t packed_bytes) { return align_check(jobs, n, packed_bytes); }
+
+int l2s_align_faces(const uint8_t* packed_in, int64_t packed_bytes, const l2s_align_job* jobs, int n, uint8_t* packed_out, void* stream) {
+    return launch_align_faces(packed_in, packed_bytes, jobs, n, packed_out, (hipStream_t)stream);
+}
+
 int l2s_build_visual(const float* feat, const float* emb, int B, int T, float* vis, void* stream) {
     L2S_REQUIRE(feat && emb && vis && B > 0 && T > 0, "bad arguments");
     hipStream_t s = (hipStream_t)stream;

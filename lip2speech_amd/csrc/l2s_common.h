@@ -10,6 +10,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 struct l2s_resize_job;      // include/l2s.h
+struct l2s_align_job;
 #ifdef L2S_DIAG
 struct l2s_gemm_bwd_record; // include/l2s_diag.h
 #endif
@@ -329,6 +330,9 @@ int launch_normalise_pad(const uint8_t* packed, const int64_t* offsets, const in
 int resize_check(const ::l2s_resize_job* jobs, int n, int64_t packed_bytes, int mode, int B, int T, int oh, int ow);
 int launch_resize_normalise(const uint8_t* packed, int64_t packed_bytes, const ::l2s_resize_job* jobs, int n, int mode, int B, int T, int oh, int ow, float* out,
                             hipStream_t s);
+// face alignment before those crops (face_align.hip): the pure host check of a job table (include/l2s.h's l2s_align_job), and the check plus the launches
+int align_check(const ::l2s_align_job* jobs, int n, int64_t packed_bytes);
+int launch_align_faces(const uint8_t* packed_in, int64_t packed_bytes, const ::l2s_align_job* jobs, int n, uint8_t* packed_out, hipStream_t s);
 // depthwise 3x3, pad 1, channel-last: in (N,Hi,Wi,ldi) channels [ci_off, ci_off+C) -> out (N,Ho,Wo,ldo) at co_off
 int launch_dwconv(const float* in, int N, int Hi, int Wi, int ldi, int ci_off, int C, int stride,
                   const float* w9 /*[9][C]*/, const float* scale, const float* shift,

@@ -18,6 +18,10 @@ an item is the list of a clip's aligned uint8 faces, the flip decision and the t
 into one pinned buffer and `PackedFaces.to_device()` runs `l2s_resize_normalise` twice on the one upload - the lower half of every face to the
 `(B,3,T,96,96)` video, the two drawn faces whole to the `(B,2,3,160,160)` face crops.  `faces_item_host` is the same tail in torch on the
 CPU: what a loader without the device does, and what the kernel is tested against (tests/test_frame_resize_gpu.py).
+
+The step before those crops, the rotation of every face-box crop by its eye-line angle (reference: datasets/face_utils.py:12-103): an item that comes as
+`(crops, flip, face_indices, landmarks)` is rotated on the device, by one `l2s_align_faces` call on the same upload before the two resize calls -
+bit-identical to rotating the crops on the host with `face_utils.align_and_crop_face` (tests/test_face_align_gpu.py).
 """
 from __future__ import annotations
 
@@ -26,6 +30,7 @@ from typing import List, Sequence, Tuple
 import torch
 
 from .. import native
+from .face_utils import eye_angle_degrees, rotation_inverse_map
 
 
 class PackedFrames:
@@ -143,7 +148,12 @@ class PackedFaces:
     """B items of aligned faces packed back to back in one host buffer, every image interleaved `(H_i,W_i,3)` on a 4-byte boundary.  An item is
     `(faces, flip, face_indices)`: the clip's faces (uint8 `(3,H_i,W_i)` as the reference holds them, or `(H_i,W_i,3)`), the item's flip decision
     and its two face indices.  `mouth_jobs` / `face_jobs` are the job tables of `l2s_resize_normalise` (rows `(offset, H, W, y0, x0, h, w, flip,
-    slot)`): the lower half `[H // 2, H)` of face t of item b to mouth slot `(b, t)`, the whole of face `face_indices[k]` to face slot `(b, k)`."""
+    slot)`): the lower half `[H // 2, H)` of face t of item b to mouth slot `(b, t)`, the whole of face `face_indices[k]` to face slot `(b, k)`.
+
+    An item may also be `(crops, flip, face_indices, landmarks)`: the UNROTATED face-box crops and the landmarks of the same frames
+    (`face_utils.face_box_crops`).  Its images get one row each in `align_jobs`, the table of `l2s_align_faces` (rows `(offset, H, W, m0, .., m5)` with
+    the map `rotation_inverse_map(eye_angle_degrees(landmarks), H, W)`), and `to_device` rotates them on the device before the two resize calls - what
+    `face_utils.align_and_crop_face` does per frame on the host, to the bit."""
 
     def __init__(self, items: Sequence, pin: bool = True):
         assert len(items) > 0, "at least one item"
@@ -151,9 +161,14 @@ class PackedFaces:
         self.images: List[Tuple[int, int, int]] = []       # (offset, H, W) of every image, in item order
         self.flips: List[int] = []
         self.face_jobs: List[Tuple[int, ...]] = []
+        self.align_jobs: List[Tuple] = []
         self._slots: List[Tuple[int, int]] = []            # (b, t) of every image
         chw, total = [], 0
-        for b, (faces, flip, face_indices) in enumerate(items):
+        for b, item in enumerate(items):
+            assert len(item) in (3, 4), "an item is (faces, flip, face_indices) or (crops, flip, face_indices, landmarks)"
+            faces, flip, face_indices = item[:3]
+            landmarks = item[3] if len(item) == 4 else None
+            assert landmarks is None or len(landmarks) == len(faces), "one landmark set per crop"
             first = len(self.images)
             self.frames.append(len(faces))
             self.flips.append(int(bool(flip)))
@@ -164,6 +179,8 @@ class PackedFaces:
                 chw.append(f)
                 self.images.append((total, H, W))
                 self._slots.append((b, t))
+                if landmarks is not None:
+                    self.align_jobs.append((total, H, W) + tuple(rotation_inverse_map(eye_angle_degrees(landmarks[t]), H, W)))
                 total += (H * W * 3 + 3) // 4 * 4
             assert len(face_indices) == 2 and all(0 <= int(i) < len(faces) for i in face_indices), "two face indices inside the clip"
             for k, i in enumerate(face_indices):
@@ -187,8 +204,11 @@ class PackedFaces:
 
     def to_device(self, device="cuda", T: int = None, size: int = 96):
         """-> `(video (B,3,T,size,size), face_crops (B,2,3,160,160))` fp32 on the device from ONE host-to-device copy and two calls; clips shorter
-        than T (default: the longest clip) are zero-padded."""
+        than T (default: the longest clip) are zero-padded.  Items that came with landmarks are rotated first, by one `l2s_align_faces` call on the
+        upload; the images of the other items of such a batch are carried over as they are."""
         dev = self.data.to(device, non_blocking=True)
+        if self.align_jobs:
+            dev = native.align_faces(dev, self.align_jobs, out=dev.clone() if len(self.align_jobs) < len(self.images) else None)
         B = len(self.frames)
         T = max(max(self.frames), 1) if T is None else int(T)
         video = native.resize_normalise(dev, self.mouth_jobs(T), native.RESIZE_MOUTH, B, T, size)
@@ -197,7 +217,8 @@ class PackedFaces:
 
 def device_collate_fn_pad_faces(batch):
     """`device_collate_fn_pad_raw` for loaders whose items carry aligned faces of their own sizes: an item is
-    `((faces, flip, face_indices), speech, melspec, _[, path])` and the tuple is `((packed_faces, lengths), packed_audio, packed_audio,
+    `((faces, flip, face_indices), speech, melspec, _[, path])` - or `((crops, flip, face_indices, landmarks), ...)` with unrotated face-box crops,
+    which `PackedFaces` has the device rotate - and the tuple is `((packed_faces, lengths), packed_audio, packed_audio,
     packed_faces[, paths])` - ONE `PackedFaces` in the video and face positions; `packed_faces.to_device()` returns both,
     `(video, face_crops)`."""
     with_paths = len(batch[0]) == 5

@@ -30,7 +30,7 @@ ABI_SYMBOLS = (
     "l2s_model_create", "l2s_model_set_tensor", "l2s_model_finalize", "l2s_model_destroy",
     "l2s_min_T", "l2s_workspace_bytes", "l2s_state_floats", "l2s_state_offset",
     "l2s_mel_frames", "l2s_mel_targets_workspace_bytes", "l2s_mel_targets",
-    "l2s_resize_check", "l2s_resize_normalise",
+    "l2s_resize_check", "l2s_resize_normalise", "l2s_align_check", "l2s_align_faces",
     "l2s_encoder_fwd", "l2s_normalise_pad_frames", "l2s_build_visual", "l2s_decoder_prologue", "l2s_decode_steps", "l2s_postnet",
     "l2s_workspace_bytes_masked", "l2s_masked_bilstm_plan", "l2s_inference_masked", "l2s_forward_eval_masked", "l2s_decoder_prologue_masked", "l2s_decode_steps_masked",
     "l2s_ragged_plan", "l2s_workspace_bytes_ragged", "l2s_inference_ragged",
@@ -72,6 +72,11 @@ class ResizeJob(ctypes.Structure):
     _fields_ = [("offset", _i64)] + [(k, ctypes.c_int32) for k in ("H", "W", "y0", "x0", "h", "w", "flip", "slot")]
 
 
+class AlignJob(ctypes.Structure):
+    """`l2s_align_job` (include/l2s.h): an image of the packed buffer and the six float64 of its destination-to-source map"""
+    _fields_ = [("offset", _i64), ("H", ctypes.c_int32), ("W", ctypes.c_int32), ("m", ctypes.c_double * 6)]
+
+
 class SkinnyGroup(ctypes.Structure):
     """`l2s_skinny_group` (include/l2s_diag.h): one GEMM group of a batch-row launch of `l2s_op_skinny` - pointers, then 64-bit, then 32-bit integers"""
     _fields_ = ([("seg_a", _vp * 4)] + [(k, _vp) for k in ("a_sum", "W", "planes", "bias", "actw", "add", "addrow", "out", "pre", "c_in", "c_out", "h_out", "h_seq",
@@ -97,6 +102,7 @@ class GemmBwdRecord(ctypes.Structure):
 
 RESIZE_MOUTH, RESIZE_FACE = 0, 1        # L2S_RESIZE_MOUTH / L2S_RESIZE_FACE
 RESIZE_JOBS_PER_LAUNCH = 240              # L2S_RESIZE_JOBS_PER_LAUNCH: output slots whose table one launch carries in its kernel arguments
+ALIGN_JOBS_PER_LAUNCH = 56                # L2S_ALIGN_JOBS_PER_LAUNCH: 64-byte align jobs whose table one launch carries in its kernel arguments
 
 
 def _load(path: str) -> ctypes.CDLL:
@@ -259,6 +265,11 @@ def _bind(L: ctypes.CDLL) -> None:
         _jobs = ctypes.POINTER(ResizeJob)
         L.l2s_resize_check.argtypes = [_jobs, _i, _i64, _i, _i, _i, _i, _i]
         L.l2s_resize_normalise.argtypes = [_vp, _i64, _jobs, _i, _i, _i, _i, _i, _i, _fp, _vp]
+    # device-side face alignment (include/l2s.h): likewise absent from a library built before it
+    if hasattr(L, "l2s_align_faces"):
+        _ajobs = ctypes.POINTER(AlignJob)
+        L.l2s_align_check.argtypes = [_ajobs, _i, _i64]
+        L.l2s_align_faces.argtypes = [_vp, _i64, _ajobs, _i, _vp, _vp]
     # the voice tower over clips of unequal length (include/l2s.h): likewise absent from a library built before it
     # (tools/speaker_packed/time_speaker_packed.py times one next to this build)
     if hasattr(L, "l2s_speaker_encoder_packed"):
@@ -1130,6 +1141,42 @@ def resize_normalise(packed_u8: torch.Tensor, jobs, mode: int, B: int, T: int = 
     resize_check(jobs, packed_u8.numel(), mode, B, T, size)       # before the output is allocated: its shape comes from the arguments under check
     out = torch.empty((B, 2, 3, size, size) if face else (B, 3, T, size, size), dtype=torch.float32, device=packed_u8.device)
     check(lib().l2s_resize_normalise(packed_u8.data_ptr(), packed_u8.numel(), _resize_jobs(jobs), len(jobs), int(mode), int(B), T, size, size, _ptr(out), _stream()))
+    return out
+
+
+_ALIGN_JOB_DTYPE = np.dtype([("offset", "<i8"), ("H", "<i4"), ("W", "<i4"), ("m", "<f8", (6,))])
+
+
+def _align_jobs(jobs):
+    """rows `(offset, H, W, m0, .., m5)` (or `AlignJob`s) -> a pointer to as many `AlignJob` (numpy holds the memory: the pointer keeps it alive)"""
+    rows = [(j.offset, j.H, j.W) + tuple(j.m) if isinstance(j, AlignJob) else tuple(j) for j in jobs]
+    assert all(len(r) == 9 for r in rows), "an align job is (offset, H, W, m0, m1, m2, m3, m4, m5)"
+    ints = np.asarray([r[:3] for r in rows], dtype=np.int64).reshape(-1, 3)
+    assert ints.size == 0 or int(np.abs(ints[:, 1:]).max()) < 2 ** 31, "H and W are 32-bit integers"
+    arr = np.zeros(max(len(rows), 1), dtype=_ALIGN_JOB_DTYPE)
+    arr["offset"][:len(rows)], arr["H"][:len(rows)], arr["W"][:len(rows)] = ints[:, 0], ints[:, 1], ints[:, 2]
+    arr["m"][:len(rows)] = np.asarray([r[3:] for r in rows], dtype=np.float64).reshape(-1, 6)
+    ptr = arr.ctypes.data_as(ctypes.POINTER(AlignJob))
+    ptr._rows = arr
+    return ptr
+
+
+def align_check(jobs, packed_bytes: int) -> None:
+    """`l2s_align_check`: the pure host check of an align job table (no device needed); raises with the job and the limit it breaks."""
+    check(lib().l2s_align_check(_align_jobs(jobs), len(jobs), int(packed_bytes)))
+
+
+def align_faces(packed_u8: torch.Tensor, jobs, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """`l2s_align_faces`: uint8 RGB images `(H_i,W_i,3)` packed back to back on the device (each on a 4-byte boundary) -> a packed buffer of the same
+    size and layout in which every image a job names is warped by the job's destination-to-source map (`warpAffine`, bilinear, border 0 - the rotation of
+    `datasets.face_utils.align_and_crop_face` with `rotation_inverse_map`).  `jobs`: rows `(offset, H, W, m0, .., m5)` or `AlignJob`s.  Bytes outside every
+    named image's span rounded up to 4 bytes keep what `out` held; without `out` they are uninitialised."""
+    assert packed_u8.is_cuda and packed_u8.dtype == torch.uint8 and packed_u8.is_contiguous() and packed_u8.dim() == 1
+    align_check(jobs, packed_u8.numel())
+    if out is None:
+        out = torch.empty_like(packed_u8)
+    assert out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and out.shape == packed_u8.shape and out.device == packed_u8.device
+    check(lib().l2s_align_faces(packed_u8.data_ptr(), packed_u8.numel(), _align_jobs(jobs), len(jobs), out.data_ptr(), _stream()))
     return out
 
 
