@@ -284,6 +284,46 @@ int64_t l2s_estoi_workspace_bytes_long(int N, int n_resampled);
 int l2s_estoi(const float* clean, const float* pred, int N, int n_samples, const float* fir, int n_fir, int up, int down, int n_pre_remove,
               int n_resampled, const int* band_lo_hi_host, float* score, void* ws, int64_t ws_bytes, void* stream);
 
+/* The same three stages over N clips of UNEQUAL length in one launch chain: every clip comes out as the entry point above computes it ALONE at its own length
+ * (N = 1, L = L_b, rows_per_call = 1; N = 1, n_samples = n_samples[b]) - the same bits, whatever shares the call and in whatever order.  PARITY UNPINNED against
+ * torchaudio and pystoi, as above.  L / n_samples / n_fir / n_resampled / mel_offset / mel_pitch are HOST arrays of N entries that may be freed on return.
+ * One layout rule between the stages: clips back to back in clip order, clip b's block exactly the array its solo call uses, block offsets the prefix sums of
+ * L_b - init (L_b, n_freqs) at row sum_{c<b} L_c, spec (n_freqs, L_b) and init_angles (513, L_b, 2) at frame offset sum_{c<b} L_c.  The mel input is the
+ * exception, so that the packed blocks l2s_forward_eval_ragged writes and a padded (N, n_mels, L_max) tensor are both read in place: band m, frame l of clip b
+ * is mel[mel_offset[b] + m mel_pitch[b] + l] (floats from one base pointer of mel_floats floats; frames past L_b are never read).
+ * l2s_inverse_mel_ragged: the gradient scale -2 / L_b, the loss mean and the two stopping rules run over the clip's own rows, and the second pass re-runs only the
+ *   clips that stopped early; loss_per_iter dev (N, iters) or NULL and iters_run dev int (N) or NULL are per clip; the band tables are built once per call.
+ * l2s_griffin_lim_ragged: a clip takes the kernel form its solo call takes (up to 77 frames, up to 121, the tile form above): at most two launches for the short
+ *   clips plus one launch per iteration over the (clip, tile) pairs of the long clips only.  wave dev (N, wave_pitch): clip b's hop (L_b - 1) samples at the row
+ *   start, exact zeros behind them; every element is written.
+ * l2s_estoi_ragged: clean / pred dev (N, pitch), clip b its first n_samples[b] floats (nothing behind them is read).  ONE filter table serves the call:
+ *   scipy's resample_poly plans for different input lengths differ only in their trailing zeros, so clip b uses the first n_fir[b] taps of fir (n_fir_max taps,
+ *   the longest clip's plan) with its own n_resampled[b]; up / down / n_pre_remove do not depend on the length.  fir = NULL (n_fir ignored) when fs is 10 kHz.
+ *   A clip takes the short or the long form by its own n_resampled[b].  score dev (N).
+ * The tables reach the device through the workspace, written on the stream by a kernel that carries them in its arguments (960 integers per launch): no
+ * allocation, no host synchronisation, no copy from host memory.
+ * Limits, each refused by the pure host checks l2s_*_ragged_check (which the entry points run before anything is launched; the error names the clip):
+ * N in [1, 65 535]; L_b in [5, 2^20] and sum L_b <= 2^24; n_fft = win = 1024, hop = 256; at most 128 mel bands, 576 bins, 2048 filterbank non-zeros;
+ * mel_offset[b] >= 0, mel_pitch[b] >= L_b and mel_offset[b] + (n_mels - 1) mel_pitch[b] + L_b <= mel_floats; wave_pitch >= hop (L_b - 1) and pitch >=
+ * n_samples[b] (rows that do not overlap); n_resampled[b] in [1, 48 256]; n_fir[b] in [1, n_fir_max].  A null table is refused.
+ * The workspace sizers are never below the sum of the solo sizers over the clips and grow with sum L_b; -1 (with l2s_last_error) for a table they refuse. */
+int l2s_inverse_mel_ragged_check(const int* L, const int64_t* mel_offset, const int64_t* mel_pitch, int N, int64_t mel_floats, int n_mels, int n_freqs,
+                                 int fb_nnz, int iters);
+int64_t l2s_inverse_mel_ragged_workspace_bytes(const int* L, int N, int n_mels, int n_freqs, int iters);
+int l2s_inverse_mel_ragged(const float* mel, int64_t mel_floats, const int64_t* mel_offset, const int64_t* mel_pitch, const int* L, int N, int log_input,
+                           const float* fb, int fb_nnz, const float* init, int n_mels, int n_freqs, int iters, float* spec, float* loss_per_iter,
+                           int* iters_run, void* ws, int64_t ws_bytes, void* stream);
+int l2s_griffin_lim_ragged_check(const int* L, int N, int n_fft, int hop, int iters, int64_t wave_pitch);
+int64_t l2s_griffin_lim_ragged_workspace_bytes(const int* L, int N);
+int l2s_griffin_lim_ragged(const float* power_spec, const float* init_angles, const int* L, int N, int n_fft, int hop, int iters, float momentum,
+                           float* wave, int64_t wave_pitch, void* ws, int64_t ws_bytes, void* stream);
+int l2s_estoi_ragged_check(const int* n_samples, const int* n_fir, const int* n_resampled, int N, int64_t pitch, int has_fir, int n_fir_max, int up, int down,
+                           int n_pre_remove);
+int64_t l2s_estoi_ragged_workspace_bytes(const int* n_resampled, int N);
+int l2s_estoi_ragged(const float* clean, const float* pred, int64_t pitch, const int* n_samples, int N, const float* fir, int n_fir_max, const int* n_fir,
+                     int up, int down, int n_pre_remove, const int* n_resampled, const int* band_lo_hi_host, float* score, void* ws, int64_t ws_bytes,
+                     void* stream);
+
 /* decoder.py:429-435: lengths[b] = first i+1 with stop logit > 0, else S.  lengths dev (B) int64. */
 int l2s_output_lengths(const float* stop, int B, int S, int64_t* lengths, void* stream);
 

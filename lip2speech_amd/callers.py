@@ -204,16 +204,27 @@ def evaluate_mels(net, batches: Iterable, speaker_encoder=None, device="cuda", g
 
 def evaluate_net(net, batches: Iterable, speaker_encoder=None, device="cuda", max_iters: int = 256, sampling_rate: int = None,
                  group: int = 8, n_inflight: int = 3, timings: Optional[dict] = None, vocoder_backend: str = "auto", metric: str = "auto",
-                 encoding: str = "voice", honour_lengths: bool = False, group_lengths: bool = False) -> float:
+                 encoding: str = "voice", honour_lengths: bool = False, group_lengths: bool = False, vocode_lengths: bool = False,
+                 vocoder_generator=None) -> float:
     """Mean ESTOI of the vocoded predictions against the ground-truth audio (reference: evaluate.py:22-51): `net(..., tf_ratio=1)[1]`
     -> `MelSpec2Audio` (InverseMelScale + Griffin-Lim, `max_iters` each) -> `stoi(gt, pred, fs, extended=True)` per clip.  Vocoder and
     metric are restatements of third-party algorithms (parity unpinned); the mels come from the HIP path, `group` loader batches per launch
     chain, and the next groups' chains run while this thread vocodes and scores.  `timings` (a dict) receives the wall seconds spent waiting
     for the model, in the vocoder and in the metric.  `encoding="face"`: the speaker embedding comes from the model's face tower.
-    `honour_lengths` / `group_lengths`: as in `evaluate_mels`."""
+    `honour_lengths` / `group_lengths`: as in `evaluate_mels`.
+    `vocode_lengths` (with `honour_lengths`; off by default): the tail honours the lengths too (`_evaluate_net_vocode_lengths`) - clip b of a batch is vocoded
+    over its own `melspec_lengths[b]` frames and scored over its own samples against its own ground truth, as `demo.py` treats a clip, and a pass holds
+    up to `group` batches whatever their mel and audio widths.  `vocoder_generator` (that route only): the generator the vocoder's start iterates are
+    drawn from, clip by clip in loader order - with it a clip's score depends on neither its batch nor its pass; None draws from the device's default
+    generator, which the model's Gumbel noise shares."""
     _check_encoding(encoding)
     if group_lengths and not honour_lengths:
         raise ValueError("group_lengths groups the length-honouring calls: pass honour_lengths=True as well")
+    if vocode_lengths and not honour_lengths:
+        raise ValueError("vocode_lengths vocodes and scores every clip at its own length: pass honour_lengths=True as well")
+    if vocode_lengths:
+        return _evaluate_net_vocode_lengths(net, batches, speaker_encoder, device, max_iters, sampling_rate, group, n_inflight, timings, vocoder_backend, metric,
+                                            encoding, group_lengths, vocoder_generator)
     import time
     from .datasets.spectrograms import MelSpec2Audio
     from .hparams import create_hparams
@@ -286,6 +297,107 @@ def evaluate_net(net, batches: Iterable, speaker_encoder=None, device="cuda", ma
     if timings is not None:
         timings.update(t)
     return sum(scores) / max(1, len(scores))
+
+
+def _evaluate_net_vocode_lengths(net, batches, speaker_encoder, device, max_iters, sampling_rate, group, n_inflight, timings, vocoder_backend, metric,
+                                 encoding, group_lengths, generator) -> float:
+    """`evaluate_net(honour_lengths=True, vocode_lengths=True)`: the model half as `_evaluate_outputs` runs it; then, per pass of up to `group` loader batches
+    (whatever their shapes), ONE ragged vocoder call (`MelSpec2Audio.forward(lengths=...)`: `l2s_inverse_mel_ragged` + `l2s_griffin_lim_ragged`) over every
+    clip's own L_b = `melspec_lengths[b]` frames and ONE ragged metric call (`estoi_device(lengths=...)`: `l2s_estoi_ragged`) over every clip's own
+    n_b = min(audio_lengths[b], hop (L_b - 1)) samples.  Each clip is vocoded and scored as it would be alone, so its score does not depend on which clips
+    share its pass.  `metric="host"`: the numpy `stoi` scores the same per-clip slices.  `timings` also receives the per-clip scores ("scores")."""
+    import time
+    from .datasets.spectrograms import MelSpec2Audio
+    from .hparams import create_hparams
+    from .metrics import FS, estoi_device, stoi
+    hp = create_hparams()
+    fs = sampling_rate or hp.sampling_rate
+    vocoder = MelSpec2Audio(hp, max_iters=max_iters, backend=vocoder_backend).to(device)
+    scores = []
+    t = {"model_wait_s": 0.0, "vocoder_s": 0.0, "estoi_s": 0.0, "clips": 0}
+
+    def vocode_and_score(pending):
+        t1 = time.perf_counter()
+        mlens = [int(v) for _, _, mlen, _ in pending for v in mlen]
+        n_clips, l_max = len(mlens), max(mlens)
+        mel = pending[0][3].new_zeros(n_clips, pending[0][3].shape[1], l_max)       # the pass's clips in one padded tensor: what pads it is never read
+        row = 0
+        for _, _, _, m in pending:
+            w = min(m.shape[2], l_max)
+            mel[row: row + m.shape[0], :, :w] = m[:, :, :w]
+            row += m.shape[0]
+        pred_dev = vocoder(mel, generator=generator, lengths=mlens)
+        alens = [int(v) for _, alen, _, _ in pending for v in alen]
+        n = [min(a, vocoder.hop * (L - 1)) for a, L in zip(alens, mlens)]
+        on_device = metric != "host" and pred_dev.is_cuda and max(-(-v * FS // fs) for v in n) <= native.ESTOI_MAX_SAMPLES
+        if metric == "hip" and not on_device:
+            raise RuntimeError(f"evaluate_net(metric='hip'): needs device predictions and clips of at most {native.ESTOI_MAX_SAMPLES} samples at 10 kHz (4.8 s)")
+        pitch = max(n)
+        if on_device:
+            torch.cuda.synchronize()
+            t2 = time.perf_counter()
+            gt_dev = pred_dev.new_zeros(n_clips, pitch)
+            row = 0
+            for audios, _, _, _ in pending:
+                w = min(audios.shape[1], pitch)
+                gt_dev[row: row + audios.shape[0], :w] = audios[:, :w].to(pred_dev.device, non_blocking=True)
+                row += audios.shape[0]
+            scores.extend(float(v) for v in estoi_device(gt_dev, pred_dev[:, :pitch].contiguous(), fs, lengths=n).cpu())
+            native.check_persist_timeouts()
+        else:
+            pred = pred_dev.cpu().numpy()
+            t2 = time.perf_counter()
+            row = 0
+            for audios, _, _, _ in pending:
+                gt = audios.numpy() if not audios.is_cuda else audios.cpu().numpy()
+                for i in range(gt.shape[0]):
+                    scores.append(stoi(gt[i, :n[row + i]], pred[row + i, :n[row + i]], fs, extended=True))
+                row += gt.shape[0]
+        t3 = time.perf_counter()
+        t["vocoder_s"] += t2 - t1
+        t["estoi_s"] += t3 - t2
+        t["clips"] += n_clips
+
+    was_training = net.training
+    net.eval()
+    try:
+        with torch.no_grad():
+            t0 = time.perf_counter()
+            pending = []
+            for batch, out in _evaluate_outputs(net, batches, speaker_encoder, device, group, n_inflight, encoding, True, group_lengths):
+                if len(pending) == max(1, group):       # nothing else ends a pass: batches of any mel and audio width share it
+                    t["model_wait_s"] += time.perf_counter() - t0
+                    vocode_and_score(pending)
+                    pending = []
+                    t0 = time.perf_counter()
+                pending.append((batch[1][0], batch[1][1], batch[2][1], out[1]))
+            t["model_wait_s"] += time.perf_counter() - t0
+            if pending:
+                vocode_and_score(pending)
+    finally:
+        net.train(was_training)
+    if timings is not None:
+        timings.update(t)
+        timings["scores"] = list(scores)
+    return sum(scores) / max(1, len(scores))
+
+
+def vocode_clips(mels, max_iters: int = 256, generator=None, backend: str = "auto"):
+    """The vocoder of demo.py over the clips `demo_clips` yields: `mels` a list of (1, n_mels, n_i) log-mels of unequal length -> a list of (hop (n_i - 1),)
+    waveforms from ONE ragged vocoder pass (`MelSpec2Audio.forward(lengths=...)`), each what `MelSpec2Audio(max_iters=max_iters, backend=backend)(mel_i,
+    generator)` returns for the clips in list order on the same generator."""
+    from .datasets.spectrograms import MelSpec2Audio
+    mels = list(mels)
+    if not mels:
+        return []
+    lengths = [int(m.shape[-1]) for m in mels]
+    vocoder = MelSpec2Audio(max_iters=max_iters, backend=backend).to(mels[0].device)
+    padded = mels[0].new_zeros(len(mels), mels[0].shape[-2], max(lengths))
+    for i, m in enumerate(mels):
+        padded[i, :, :lengths[i]] = m.reshape(m.shape[-2], lengths[i])
+    with torch.no_grad():
+        wave = vocoder(padded, generator=generator, lengths=lengths)
+    return [wave[i, :vocoder.hop * (n - 1)] for i, n in enumerate(lengths)]
 
 
 def reconstruction_losses(outputs, targets) -> dict:

@@ -9,6 +9,10 @@
 #include "../../include/l2s.h"
 
 #include <math.h>
+#include <string.h>
+
+#include <algorithm>
+#include <vector>
 
 namespace l2s {
 
@@ -33,6 +37,10 @@ struct InvMelP {
     float* loss_rows;        // [iters][N*L] or null
     const int* iters_call;   // per call: iterations to run in THIS pass (null: `iters` for all); a call whose entry equals `iters` is skipped when `second`
     int N, L, n_mels, n_freqs, rows_per_call, iters, log_input, second;
+    // the ragged form only (RAG): clip n is its own call of row_off[n + 1] - row_off[n] rows; its mel frame l, band m is mel[mel_off[n] + m mel_pitch[n] + l]
+    const int* row_off;      // ws: [N + 1] prefix sums of the clips' frame counts
+    const int64_t* mel_off;  // ws: [N]
+    const int64_t* mel_pitch;// ws: [N]
 };
 
 // one block: band structure of the filterbank + its non-zeros in the two orders the SGD walks them
@@ -76,13 +84,16 @@ int launch_mel_bands(const float* fb, int n_freqs, int n_mels, int* tab, float* 
     return 0;
 }
 
+// RAG: row -> (clip, frame) by a search of the prefix table; L, the gradient scale, the mel address and the clip's block of `spec` are the clip's own, and
+// the arithmetic of the row is the other instantiation's at N = 1, L = L_b, rows_per_call = 1
+template <bool RAG>
 __global__ __launch_bounds__(IM_ROWS * 64) void inverse_mel_kernel(const InvMelP p) {
     __shared__ float s_fwd[IM_NNZ], s_bwd[IM_NNZ];
     __shared__ float s_specs[IM_ROWS][IM_MAXF];
     __shared__ float s_diffs[IM_ROWS][IM_MAXM];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int L = p.L, M = p.n_mels, F = p.n_freqs;
+    const int M = p.n_mels, F = p.n_freqs;
     {
         const int nf = p.tab[3 * (M + F)], nb = p.tab[3 * (M + F) + 1];
         for (int i = tid; i < nf && i < IM_NNZ; i += IM_ROWS * 64) s_fwd[i] = p.fwd[i];
@@ -90,17 +101,37 @@ __global__ __launch_bounds__(IM_ROWS * 64) void inverse_mel_kernel(const InvMelP
     }
     __syncthreads();                                   // the only block barrier: from here on every wave runs its own row
     const int64_t row = (int64_t)blockIdx.x * IM_ROWS + wave;
-    if (row >= (int64_t)p.N * L) return;
+    const int64_t rows_total = RAG ? (int64_t)p.row_off[p.N] : (int64_t)p.N * p.L;
+    if (row >= rows_total) return;
     float* s_spec = s_specs[wave];
     float* s_diff = s_diffs[wave];
-    const int n = (int)(row / L), l = (int)(row - (int64_t)n * L);
-    const int call = (int)(row / ((int64_t)p.rows_per_call * L));
+    int L, n, l, call;
+    const float* mel_row;                              // band m of this row's frame: mel_row[m * mel_pitch]
+    int64_t mel_pitch;
+    float* spec_out;                                   // bin f of this row's frame: spec_out[f * L]
+    if constexpr (RAG) {
+        int lo = 0, hi = p.N;                          // the clip whose rows hold `row`: row_off[lo] <= row < row_off[lo + 1] (wave-uniform: scalar loads)
+        while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (p.row_off[mid] <= row) lo = mid; else hi = mid; }
+        n = call = lo;
+        const int r0 = p.row_off[n];
+        L = p.row_off[n + 1] - r0; l = (int)row - r0;
+        mel_pitch = p.mel_pitch[n];
+        mel_row = p.mel + p.mel_off[n] + l;
+        spec_out = p.spec + (int64_t)r0 * F + l;
+    } else {
+        L = p.L;
+        n = (int)(row / L); l = (int)(row - (int64_t)n * L);
+        call = (int)(row / ((int64_t)p.rows_per_call * L));
+        mel_pitch = L;
+        mel_row = p.mel + (int64_t)n * M * L + l;
+        spec_out = p.spec + (int64_t)n * F * L + l;
+    }
     int iters = p.iters;
     if (p.iters_call) {
         iters = p.iters_call[call];
         if (p.second && iters >= p.iters) return;             // this call ran to the end in the first pass
     }
-    const float gscale = -2.0f / (float)(p.rows_per_call * L);
+    const float gscale = -2.0f / (float)((RAG ? 1 : p.rows_per_call) * L);
     float spec[9], vel[9];
     int mlo[9], mcnt[9], boff[9];
 #pragma unroll
@@ -117,7 +148,7 @@ __global__ __launch_bounds__(IM_ROWS * 64) void inverse_mel_kernel(const InvMelP
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
         const int m = lane + 64 * i;
-        float t = m < M ? p.mel[((int64_t)n * M + m) * L + l] : 0.f;
+        float t = m < M ? mel_row[(int64_t)m * mel_pitch] : 0.f;
         if (p.log_input && m < M) t = expf(t);
         target[i] = t;
         flo[i] = m < M ? p.tab[3 * m] : 0;
@@ -141,7 +172,7 @@ __global__ __launch_bounds__(IM_ROWS * 64) void inverse_mel_kernel(const InvMelP
         if (p.loss_rows) {
 #pragma unroll
             for (int o = 32; o > 0; o >>= 1) lsum += __shfl_xor(lsum, o);
-            if (lane == 0) p.loss_rows[(int64_t)it * ((int64_t)p.N * L) + row] = lsum;
+            if (lane == 0) p.loss_rows[(int64_t)it * rows_total + row] = lsum;
         }
 #pragma unroll
         for (int j = 0; j < 9; ++j) {
@@ -156,21 +187,25 @@ __global__ __launch_bounds__(IM_ROWS * 64) void inverse_mel_kernel(const InvMelP
 #pragma unroll
     for (int j = 0; j < 9; ++j) {
         const int f = lane + 64 * j;
-        if (f < F) p.spec[((int64_t)n * F + f) * L + l] = spec[j];
+        if (f < F) spec_out[(int64_t)f * L] = spec[j];
     }
 }
 
 // per call: the mean loss of every iteration (rows summed in index order, fp64) -> the iteration count the reference's stopping rules leave
-__global__ __launch_bounds__(256) void inverse_mel_stop_kernel(const float* loss_rows, int rows_total, int rows_call, int iters, int* iters_call, float* loss_out) {
+// row_off (the ragged form; else null): call c is the rows [row_off[c], row_off[c + 1])
+__global__ __launch_bounds__(256) void inverse_mel_stop_kernel(const float* loss_rows, int rows_total, int rows_call, int iters, int* iters_call, float* loss_out,
+                                                               const int* row_off) {
     __shared__ double red[256];
     __shared__ int stop_at;
     const int call = blockIdx.x, tid = threadIdx.x;
+    const int64_t row0 = row_off ? (int64_t)row_off[call] : (int64_t)call * rows_call;
+    if (row_off) rows_call = row_off[call + 1] - row_off[call];
     if (tid == 0) stop_at = iters;
     float prev = INFINITY;
     __syncthreads();
     for (int it = 0; it < iters; ++it) {
         double s = 0.0;
-        const float* lr = loss_rows + (int64_t)it * rows_total + (int64_t)call * rows_call;
+        const float* lr = loss_rows + (int64_t)it * rows_total + row0;
         for (int r = tid; r < rows_call; r += 256) s += (double)lr[r];
         red[tid] = s;
         __syncthreads();
@@ -207,24 +242,32 @@ struct GriffinP {
     float* wave;             // (N, hop (L-1)) out
     int N, L, iters;
     float momentum;          // 0.99 / 1.99
+    // the ragged form only (RAG): block j runs clip list[j]; the clip's frames are [frame_off[clip], frame_off[clip + 1]) of the packed arrays (three
+    // workspace slots per frame there, whatever the form) and its waveform row starts at wave + clip wave_pitch
+    const int* frame_off;    // ws: [N + 1] prefix sums of the clips' frame counts
+    const int* list;         // ws: the clips this launch's form takes
+    int64_t wave_pitch;
 };
 
-template <int NW, int YCAP>
+// RAG: the clip, its L and its blocks of the packed arrays come from the tables; the rest of the row past the clip's samples is written as zeros
+template <int NW, int YCAP, bool RAG>
 __global__ __launch_bounds__(NW * 64) void griffin_lim_kernel(const GriffinP p) {
     __shared__ __attribute__((aligned(16))) float y[YCAP];
     __shared__ __attribute__((aligned(16))) float2 scratch[NW][GL_LDK];
     __shared__ float w2[GL_NFFT];                                  // window^2 for the overlap-add envelope
-    const int clip = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+    const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int L = p.L, ylen = GL_HOP * (L - 1);
+    const int clip = RAG ? p.list[blockIdx.x] : (int)blockIdx.x;
+    const int L = RAG ? p.frame_off[clip + 1] - p.frame_off[clip] : p.L, ylen = GL_HOP * (L - 1);
+    const int64_t f0 = RAG ? (int64_t)p.frame_off[clip] : (int64_t)clip * L;      // the clip's first frame in the packed arrays
     float2* sc = scratch[wave];
-    float* mag = p.mag + (int64_t)clip * L * GL_LDK;
-    float2* reb0 = p.reb + (int64_t)clip * 2 * L * GL_LDK;
+    float* mag = p.mag + f0 * GL_LDK;
+    float2* reb0 = p.reb + f0 * (RAG ? 3 : 2) * GL_LDK;
     float2* reb1 = reb0 + (int64_t)L * GL_LDK;
     // ---- prologue: frame-major copies of sqrt(power) and of the start angles; window constants
     {
-        const float* pw = p.power + (int64_t)clip * GL_NBIN * L;
-        const float2* in = reinterpret_cast<const float2*>(p.init) + (int64_t)clip * GL_NBIN * L;
+        const float* pw = p.power + f0 * GL_NBIN;
+        const float2* in = reinterpret_cast<const float2*>(p.init) + f0 * GL_NBIN;
         for (int i = tid; i < GL_NBIN * L; i += NW * 64) {
             const int k = i / L, t = i - k * L;
             mag[(int64_t)t * GL_LDK + k] = sqrtf(fmaxf(pw[i], 0.f));
@@ -318,8 +361,10 @@ __global__ __launch_bounds__(NW * 64) void griffin_lim_kernel(const GriffinP p) 
         __threadfence_block();                                       // the spectra go through global memory: this block's own stores, re-read by other waves
         __syncthreads();
     }
-    float* out = p.wave + (int64_t)clip * ylen;
+    float* out = p.wave + (int64_t)clip * (RAG ? p.wave_pitch : (int64_t)ylen);
     for (int i = tid; i < ylen; i += NW * 64) out[i] = y[i];
+    if constexpr (RAG)
+        for (int64_t i = ylen + tid; i < p.wave_pitch; i += NW * 64) out[i] = 0.f;
 }
 
 // =====================================================================================================================================
@@ -343,33 +388,57 @@ struct GriffinTileP {
     float* wave;             // (N, hop (L-1)) out
     int N, L, it, iters;
     float momentum;          // 0.99 / 1.99
+    // the ragged form only (RAG): a 1-D grid over the (clip, tile) pairs of the n_long clips in `list`; block x is tile x - tile_off[j] of clip list[j]
+    const int* frame_off;    // ws: [N + 1] prefix sums of the clips' frame counts
+    const int* list;         // ws: [n_long] the clips past 121 frames, in clip order
+    const int* tile_off;     // ws: [n_long + 1] prefix sums of their tile counts
+    int n_long;
+    int64_t wave_pitch;
 };
 
-// frame-major copies of sqrt(power) and of the start angles (what the short kernel's prologue writes), the angles into slot 2
-__global__ __launch_bounds__(256) void griffin_lim_tile_prologue_kernel(const float* power, const float* init, float* mag_all, float2* reb_all, int L) {
-    const int clip = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
+// frame-major copies of sqrt(power) and of the start angles (what the short kernel's prologue writes), the angles into slot 2.
+// frame_off / list (the ragged form; else null): block row y is clip list[y] with its own L (the grid's x is sized by the longest)
+__global__ __launch_bounds__(256) void griffin_lim_tile_prologue_kernel(const float* power, const float* init, float* mag_all, float2* reb_all, int L,
+                                                                        const int* frame_off, const int* list) {
+    const int clip = list ? list[blockIdx.y] : (int)blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
+    if (list) L = frame_off[clip + 1] - frame_off[clip];
     if (i >= GL_NBIN * L) return;
+    const int64_t f0 = list ? (int64_t)frame_off[clip] : (int64_t)clip * L;
     const int k = i / L, t = i - k * L;
-    const float* pw = power + (int64_t)clip * GL_NBIN * L;
-    const float2* in = reinterpret_cast<const float2*>(init) + (int64_t)clip * GL_NBIN * L;
-    mag_all[((int64_t)clip * L + t) * GL_LDK + k] = sqrtf(fmaxf(pw[i], 0.f));
-    reb_all[(((int64_t)clip * 3 + 2) * L + t) * GL_LDK + k] = in[i];
+    const float* pw = power + f0 * GL_NBIN;
+    const float2* in = reinterpret_cast<const float2*>(init) + f0 * GL_NBIN;
+    mag_all[(f0 + t) * GL_LDK + k] = sqrtf(fmaxf(pw[i], 0.f));
+    reb_all[(f0 * 3 + 2 * (int64_t)L + t) * GL_LDK + k] = in[i];
 }
 
-template <int NW, int F>
+// RAG: (clip, tile) by a search of the tile prefix table - block-uniform, so the lookup lives in scalar registers; the last tile of a clip also writes the
+// zeros past the clip's samples on the last iteration
+template <int NW, int F, bool RAG>
 __global__ __launch_bounds__(NW * 64) void griffin_lim_tile_kernel(const GriffinTileP p) {
     constexpr int YCAP = (F + 3) * GL_HOP;                           // (F - 1) hop + n_fft samples; the clip-end extensions stay below it (F >= 2)
     static_assert(F >= 2, "a tile's sample range is sized for at least two frames");
     __shared__ __attribute__((aligned(16))) float y[YCAP];
     __shared__ __attribute__((aligned(16))) float2 scratch[NW][GL_LDK];
     __shared__ float w2[GL_NFFT];
-    const int clip = blockIdx.y, tid = threadIdx.x, lane = tid & 63;
+    const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int L = p.L, ylen = GL_HOP * (L - 1), it = p.it;
-    const int t0 = blockIdx.x * F, t1 = t0 + F < L ? t0 + F : L;
+    int clip = blockIdx.y, tile = blockIdx.x, L = p.L;
+    int64_t f0;                                                      // the clip's first frame in the packed workspace
+    if constexpr (RAG) {
+        int lo = 0, hi = p.n_long;                                   // tile_off[lo] <= blockIdx.x < tile_off[lo + 1]
+        while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (p.tile_off[mid] <= (int)blockIdx.x) lo = mid; else hi = mid; }
+        tile = (int)blockIdx.x - p.tile_off[lo];
+        clip = p.list[lo];
+        f0 = p.frame_off[clip];
+        L = p.frame_off[clip + 1] - p.frame_off[clip];
+    } else {
+        f0 = (int64_t)clip * L;
+    }
+    const int ylen = GL_HOP * (L - 1), it = p.it;
+    const int t0 = tile * F, t1 = t0 + F < L ? t0 + F : L;
     float2* sc = scratch[wave];
-    const float* mag = p.mag + (int64_t)clip * L * GL_LDK;
-    float2* reb = p.reb + (int64_t)clip * 3 * L * GL_LDK;
+    const float* mag = p.mag + f0 * GL_LDK;
+    float2* reb = p.reb + f0 * 3 * GL_LDK;
     const float2* cur = reb + (int64_t)((it + 2) % 3) * L * GL_LDK;  // rebuilt[it - 1] (it = 0: the start angles)
     const float2* prv = reb + (int64_t)((it + 1) % 3) * L * GL_LDK;  // rebuilt[it - 2]; not read for it < 2
     // ---- the samples [lo, hi) this block holds: what its forward transforms read, the reflect padding's mirrored indices included
@@ -439,9 +508,11 @@ __global__ __launch_bounds__(NW * 64) void griffin_lim_tile_kernel(const Griffin
     }
     __syncthreads();
     if (it == p.iters) {                                             // the waveform: this tile's own partition
-        float* out = p.wave + (int64_t)clip * ylen;
+        float* out = p.wave + (int64_t)clip * (RAG ? p.wave_pitch : (int64_t)ylen);
         const int o1 = t1 * GL_HOP < ylen ? t1 * GL_HOP : ylen;
         for (int i = t0 * GL_HOP + tid; i < o1; i += NW * 64) out[i] = y[i - lo];
+        if constexpr (RAG)
+            if (t1 == L) for (int64_t i = ylen + tid; i < p.wave_pitch; i += NW * 64) out[i] = 0.f;
         return;
     }
     // ---------------- phase B: rebuilt[it] = stft(y) (centre, reflect) for the tile's own frames
@@ -474,6 +545,14 @@ __global__ __launch_bounds__(NW * 64) void griffin_lim_tile_kernel(const Griffin
 constexpr int ES_FRAME = 256, ES_HOP = 128, ES_NFFT = 512, ES_BANDS = 15, ES_SEG = 30, ES_MAXFRAMES = 128, ES_MAXLEN = ES_HOP * (ES_MAXFRAMES + 1);
 constexpr int ES_NBIN = ES_NFFT / 2 + 1;
 
+// the ragged forms only (RAG): block (or grid layer) j scores clip list[j] and uses workspace slot j; the clip's signals are the first n_samples[clip] floats
+// of row clip (pitch floats apart), its filter the first n_fir[clip] taps of the call's one table, its resampled length n_res[clip]
+struct EstoiRag {
+    const int* n_samples; const int* n_fir; const int* n_res;      // ws: [N] each
+    const int* list;                                               // ws: the clips this launch's form takes
+    int64_t pitch;
+};
+
 struct EstoiP {
     const float* clean; const float* pred;    // (N, n_samples)
     const float* fir;                          // resampling filter h (already scaled by `up`, pre-padded), n_fir taps; null when fs == 10000
@@ -482,8 +561,10 @@ struct EstoiP {
     float* pw;                                 // ws: (N, 2, ES_MAXFRAMES, ES_NBIN) power spectra of the frames
     float* score;                              // (N)
     int N, n_samples, n_fir, up, down, n_pre_remove, n_res;
+    EstoiRag rag;
 };
 
+template <bool RAG>
 __global__ __launch_bounds__(1024) void estoi_kernel(const EstoiP p) {
     __shared__ float sig[2][ES_MAXLEN];                               // the silent-frame-free signals (x = clean, y = pred); later: row statistics + contributions
     __shared__ float tob[2][ES_BANDS][ES_MAXFRAMES];
@@ -493,23 +574,26 @@ __global__ __launch_bounds__(1024) void estoi_kernel(const EstoiP p) {
     __shared__ int keep_pos[ES_MAXFRAMES];
     __shared__ float red[1024];
     __shared__ int n_keep_s;
-    const int clip = blockIdx.x, tid = threadIdx.x;
-    float* rs = p.rs + (int64_t)clip * 2 * ES_MAXLEN;
-    float* pw = p.pw + (int64_t)clip * 2 * ES_MAXFRAMES * ES_NBIN;
-    const int nr = p.n_res;
+    const int slot = blockIdx.x, tid = threadIdx.x;
+    const int clip = RAG ? p.rag.list[slot] : slot;
+    float* rs = p.rs + (int64_t)slot * 2 * ES_MAXLEN;
+    float* pw = p.pw + (int64_t)slot * 2 * ES_MAXFRAMES * ES_NBIN;
+    const int nr = RAG ? p.rag.n_res[clip] : p.n_res;
+    const int n_samples = RAG ? p.rag.n_samples[clip] : p.n_samples, n_fir = RAG ? p.rag.n_fir[clip] : p.n_fir;
+    const int64_t pitch = RAG ? p.rag.pitch : (int64_t)p.n_samples;
     constexpr float EPS = 2.220446049250313e-16f;
     // ---- tables
     for (int i = tid; i < ES_NFFT; i += 1024) { float s, c; sincospif((float)i / 256.0f, &s, &c); twd[i] = make_float2(c, -s); }      // exp(-2 pi i n / 512)
     for (int i = tid; i < ES_FRAME; i += 1024) win[i] = 0.5f - 0.5f * cospif(2.0f * (float)(i + 1) / (float)(ES_FRAME + 1));          // np.hanning(258)[1:-1]
     // ---- resample (upfirdn, zero-padded ends): out[n] = sum_i x[i] h[(n + n_pre_remove) down - i up]
     for (int s = 0; s < 2; ++s) {
-        const float* x = (s ? p.pred : p.clean) + (int64_t)clip * p.n_samples;
+        const float* x = (s ? p.pred : p.clean) + (int64_t)clip * pitch;
         for (int n = tid; n < nr; n += 1024) {
             float acc;
             if (p.fir) {
                 const int64_t c = (int64_t)(n + p.n_pre_remove) * p.down;
-                int64_t ihi = c / p.up; if (ihi > p.n_samples - 1) ihi = p.n_samples - 1;
-                int64_t ilo = c - (p.n_fir - 1) <= 0 ? 0 : (c - (p.n_fir - 1) + p.up - 1) / p.up;
+                int64_t ihi = c / p.up; if (ihi > n_samples - 1) ihi = n_samples - 1;
+                int64_t ilo = c - (n_fir - 1) <= 0 ? 0 : (c - (n_fir - 1) + p.up - 1) / p.up;
                 double a = 0.0;
                 for (int64_t i = ilo; i <= ihi; ++i) a += (double)x[i] * (double)p.fir[c - i * p.up];
                 acc = (float)a;
@@ -644,26 +728,31 @@ struct EstoiLongP {
     float* pw;                                 // ws: (N, 2, ESL_MAXFRAMES, ES_NBIN) power spectra of the frames
     float* score;                              // (N)
     int N, n_samples, n_fir, up, down, n_pre_remove, n_res;
+    EstoiRag rag;
 };
 
+template <bool RAG>
 __global__ __launch_bounds__(256) void estoi_resample_kernel(const EstoiLongP p) {
-    const int n = blockIdx.x * 256 + threadIdx.x, s = blockIdx.y, clip = blockIdx.z;
-    if (n >= p.n_res) return;
-    const float* x = (s ? p.pred : p.clean) + (int64_t)clip * p.n_samples;
+    const int n = blockIdx.x * 256 + threadIdx.x, s = blockIdx.y, slot = blockIdx.z;
+    const int clip = RAG ? p.rag.list[slot] : slot;
+    if (n >= (RAG ? p.rag.n_res[clip] : p.n_res)) return;            // the ragged grid's x is sized by the longest clip
+    const int n_samples = RAG ? p.rag.n_samples[clip] : p.n_samples, n_fir = RAG ? p.rag.n_fir[clip] : p.n_fir;
+    const float* x = (s ? p.pred : p.clean) + (int64_t)clip * (RAG ? p.rag.pitch : (int64_t)p.n_samples);
     float acc;
     if (p.fir) {                               // upfirdn, zero-padded ends: out[n] = sum_i x[i] h[(n + n_pre_remove) down - i up]
         const int64_t c = (int64_t)(n + p.n_pre_remove) * p.down;
-        int64_t ihi = c / p.up; if (ihi > p.n_samples - 1) ihi = p.n_samples - 1;
-        int64_t ilo = c - (p.n_fir - 1) <= 0 ? 0 : (c - (p.n_fir - 1) + p.up - 1) / p.up;
+        int64_t ihi = c / p.up; if (ihi > n_samples - 1) ihi = n_samples - 1;
+        int64_t ilo = c - (n_fir - 1) <= 0 ? 0 : (c - (n_fir - 1) + p.up - 1) / p.up;
         double a = 0.0;
         for (int64_t i = ilo; i <= ihi; ++i) a += (double)x[i] * (double)p.fir[c - i * p.up];
         acc = (float)a;
     } else {
         acc = x[n];
     }
-    p.rs[((int64_t)clip * 2 + s) * ESL_MAXLEN + n] = acc;
+    p.rs[((int64_t)slot * 2 + s) * ESL_MAXLEN + n] = acc;
 }
 
+template <bool RAG>
 __global__ __launch_bounds__(1024) void estoi_long_kernel(const EstoiLongP p) {
     __shared__ float buf[2 * ESL_MAXFRAMES * ES_BANDS * 2];           // ESL_CHUNK frames of one signal for the spectra; later the row statistics
     __shared__ float tob[2][ES_BANDS][ESL_MAXFRAMES];
@@ -674,11 +763,12 @@ __global__ __launch_bounds__(1024) void estoi_long_kernel(const EstoiLongP p) {
     __shared__ float red[1024];
     __shared__ int n_keep_s;
     static_assert(ES_HOP * (ESL_CHUNK + 1) <= 2 * ESL_MAXFRAMES * ES_BANDS * 2, "the staged frames fit the buffer the row statistics use later");
-    const int clip = blockIdx.x, tid = threadIdx.x;
-    const float* rs = p.rs + (int64_t)clip * 2 * ESL_MAXLEN;
-    float* oa = p.oa + (int64_t)clip * 2 * ESL_MAXLEN;
-    float* pw = p.pw + (int64_t)clip * 2 * ESL_MAXFRAMES * ES_NBIN;
-    const int nr = p.n_res;
+    const int slot = blockIdx.x, tid = threadIdx.x;
+    const int clip = RAG ? p.rag.list[slot] : slot;
+    const float* rs = p.rs + (int64_t)slot * 2 * ESL_MAXLEN;
+    float* oa = p.oa + (int64_t)slot * 2 * ESL_MAXLEN;
+    float* pw = p.pw + (int64_t)slot * 2 * ESL_MAXFRAMES * ES_NBIN;
+    const int nr = RAG ? p.rag.n_res[clip] : p.n_res;
     constexpr float EPS = 2.220446049250313e-16f;
     for (int i = tid; i < ES_NFFT; i += 1024) { float s, c; sincospif((float)i / 256.0f, &s, &c); twd[i] = make_float2(c, -s); }
     for (int i = tid; i < ES_FRAME; i += 1024) win[i] = 0.5f - 0.5f * cospif(2.0f * (float)(i + 1) / (float)(ES_FRAME + 1));
@@ -792,6 +882,48 @@ __global__ __launch_bounds__(1024) void estoi_long_kernel(const EstoiLongP p) {
     if (tid == 0) p.score[clip] = red[0] / (float)nseg;
 }
 
+// =====================================================================================================================================
+// The ragged forms (l2s_*_ragged): clips of unequal length in one launch chain.  The per-clip tables (lengths, prefix sums, the clips each kernel form takes)
+// are built on the host and reach the WORKSPACE through this kernel's arguments, RAG_CHUNK integers per launch, in stream order: no allocation, no copy from
+// host memory, no synchronisation, and every block of every later launch can search the whole table (the tile form's (clip, tile) lookup needs all of it).
+// =====================================================================================================================================
+constexpr int RAG_CHUNK = 960;
+struct RagChunk { int v[RAG_CHUNK]; };
+
+__global__ __launch_bounds__(256) void ragged_table_kernel(int* dst, const RagChunk c, int n) {
+    for (int i = threadIdx.x; i < n; i += 256) dst[i] = c.v[i];
+}
+
+static void upload_table(int* dst, const std::vector<int>& t, hipStream_t s) {
+    for (size_t i0 = 0; i0 < t.size(); i0 += RAG_CHUNK) {
+        RagChunk c;
+        const int n = (int)std::min<size_t>(RAG_CHUNK, t.size() - i0);
+        memcpy(c.v, t.data() + i0, (size_t)n * sizeof(int));
+        hipLaunchKernelGGL(ragged_table_kernel, dim3(1), dim3(256), 0, s, dst + i0, c, n);
+    }
+}
+
+static int clip_error(const char* fn, int b, const std::string& what) {
+    set_error(std::string("l2s: ") + fn + ": clip " + std::to_string(b) + ": " + what);
+    return 1;
+}
+
+constexpr int RAG_MAX_CLIPS = 65535, RAG_MAX_FRAMES = 1 << 20, RAG_MAX_SUM_FRAMES = 1 << 24;
+
+// N in range, the length table present, every L_b in [5, 2^20] and their sum at most 2^24 (row and frame indices stay 32-bit)
+static int ragged_lengths_check(const char* fn, const int* L, int N) {
+    if (N < 1 || N > RAG_MAX_CLIPS) { set_error(std::string("l2s: ") + fn + ": N = " + std::to_string(N) + " clips is outside [1, 65535]"); return 1; }
+    if (!L) { set_error(std::string("l2s: ") + fn + ": null table of clip lengths"); return 1; }
+    int64_t sum = 0;
+    for (int b = 0; b < N; ++b) {
+        if (L[b] < 5) return clip_error(fn, b, std::to_string(L[b]) + " frames: at least 5 are needed");
+        if (L[b] > RAG_MAX_FRAMES) return clip_error(fn, b, std::to_string(L[b]) + " frames: at most 2^20 per clip");
+        sum += L[b];
+        if (sum > RAG_MAX_SUM_FRAMES) return clip_error(fn, b, "the clips up to this one hold more than 2^24 frames");
+    }
+    return 0;
+}
+
 }  // namespace l2s
 
 using namespace l2s;
@@ -825,13 +957,13 @@ int l2s_inverse_mel(const float* mel, int log_input, const float* fb, int fb_nnz
     int* iters_call = iters_run ? iters_run : (int*)w;
     ProfScope ps("vocoder_inverse_mel", s);
     if (launch_mel_bands(fb, n_freqs, n_mels, tab, fwd, bwd, s)) return 1;
-    InvMelP p{mel, init, tab, fwd, bwd, spec, iters > 0 ? loss_rows : nullptr, nullptr, N, L, n_mels, n_freqs, rows_per_call, iters, log_input, 0};
+    InvMelP p{mel, init, tab, fwd, bwd, spec, iters > 0 ? loss_rows : nullptr, nullptr, N, L, n_mels, n_freqs, rows_per_call, iters, log_input, 0, nullptr, nullptr, nullptr};
     const unsigned blocks = (unsigned)((rows + IM_ROWS - 1) / IM_ROWS);
-    hipLaunchKernelGGL(inverse_mel_kernel, dim3(blocks), dim3(IM_ROWS * 64), 0, s, p);
+    hipLaunchKernelGGL(inverse_mel_kernel<false>, dim3(blocks), dim3(IM_ROWS * 64), 0, s, p);
     if (iters > 0) {
-        hipLaunchKernelGGL(inverse_mel_stop_kernel, dim3(calls), dim3(256), 0, s, loss_rows, (int)rows, rows_per_call * L, iters, iters_call, loss_per_iter);
+        hipLaunchKernelGGL(inverse_mel_stop_kernel, dim3(calls), dim3(256), 0, s, loss_rows, (int)rows, rows_per_call * L, iters, iters_call, loss_per_iter, (const int*)nullptr);
         p.loss_rows = nullptr; p.iters_call = iters_call; p.second = 1;
-        hipLaunchKernelGGL(inverse_mel_kernel, dim3(blocks), dim3(IM_ROWS * 64), 0, s, p);      // only the calls a stopping rule ended early re-run
+        hipLaunchKernelGGL(inverse_mel_kernel<false>, dim3(blocks), dim3(IM_ROWS * 64), 0, s, p);      // only the calls a stopping rule ended early re-run
     }
     L2S_CHECK_HIP(hipGetLastError());
     return 0;
@@ -855,14 +987,15 @@ int l2s_griffin_lim(const float* power_spec, const float* init_angles, int N, in
     float2* reb = (float2*)(w + (int64_t)N * L * GL_LDK * 4);
     ProfScope ps("vocoder_griffin_lim", s);
     if (GL_HOP * (L - 1) <= 30720) {
-        GriffinP p{power_spec, init_angles, mag, reb, wave, N, L, iters, momentum / (1.0f + momentum)};
-        if (GL_HOP * (L - 1) <= 19456) hipLaunchKernelGGL((griffin_lim_kernel<12, 19456>), dim3(N), dim3(768), 0, s, p);
-        else hipLaunchKernelGGL((griffin_lim_kernel<8, 30720>), dim3(N), dim3(512), 0, s, p);
+        GriffinP p{power_spec, init_angles, mag, reb, wave, N, L, iters, momentum / (1.0f + momentum), nullptr, nullptr, 0};
+        if (GL_HOP * (L - 1) <= 19456) hipLaunchKernelGGL((griffin_lim_kernel<12, 19456, false>), dim3(N), dim3(768), 0, s, p);
+        else hipLaunchKernelGGL((griffin_lim_kernel<8, 30720, false>), dim3(N), dim3(512), 0, s, p);
     } else {                                       // 122 frames and more: one launch per iteration over (tile, clip)
-        hipLaunchKernelGGL(griffin_lim_tile_prologue_kernel, dim3((GL_NBIN * L + 255) / 256, N), dim3(256), 0, s, power_spec, init_angles, mag, reb, L);
-        GriffinTileP p{mag, reb, wave, N, L, 0, iters, momentum / (1.0f + momentum)};
+        hipLaunchKernelGGL(griffin_lim_tile_prologue_kernel, dim3((GL_NBIN * L + 255) / 256, N), dim3(256), 0, s, power_spec, init_angles, mag, reb, L,
+                           (const int*)nullptr, (const int*)nullptr);
+        GriffinTileP p{mag, reb, wave, N, L, 0, iters, momentum / (1.0f + momentum), nullptr, nullptr, nullptr, 0, 0};
         for (p.it = 0; p.it <= iters; ++p.it)
-            hipLaunchKernelGGL((griffin_lim_tile_kernel<GLT_NW, GLT_F>), dim3((L + GLT_F - 1) / GLT_F, N), dim3(GLT_NW * 64), 0, s, p);
+            hipLaunchKernelGGL((griffin_lim_tile_kernel<GLT_NW, GLT_F, false>), dim3((L + GLT_F - 1) / GLT_F, N), dim3(GLT_NW * 64), 0, s, p);
     }
     L2S_CHECK_HIP(hipGetLastError());
     return 0;
@@ -892,15 +1025,231 @@ int l2s_estoi(const float* clean, const float* pred, int N, int n_samples, const
     ProfScope ps("metric_estoi", s);
     if (n_resampled <= ES_MAXLEN) {
         float* pw = rs + (int64_t)N * 2 * ES_MAXLEN;
-        EstoiP p{clean, pred, fir, bands, bands + ES_BANDS, rs, pw, score, N, n_samples, n_fir, up, down, n_pre_remove, n_resampled};
-        hipLaunchKernelGGL(estoi_kernel, dim3(N), dim3(1024), 0, s, p);
+        EstoiP p{clean, pred, fir, bands, bands + ES_BANDS, rs, pw, score, N, n_samples, n_fir, up, down, n_pre_remove, n_resampled, EstoiRag{}};
+        hipLaunchKernelGGL(estoi_kernel<false>, dim3(N), dim3(1024), 0, s, p);
     } else {                                       // the long form: the signals in the workspace, the resampler a kernel of its own
         L2S_REQUIRE(N <= 65535, "estoi: at most 65 535 clips per call");
         float* oa = rs + (int64_t)N * 2 * ESL_MAXLEN;
         float* pw = oa + (int64_t)N * 2 * ESL_MAXLEN;
-        EstoiLongP p{clean, pred, fir, bands, bands + ES_BANDS, rs, oa, pw, score, N, n_samples, n_fir, up, down, n_pre_remove, n_resampled};
-        hipLaunchKernelGGL(estoi_resample_kernel, dim3((n_resampled + 255) / 256, 2, N), dim3(256), 0, s, p);
-        hipLaunchKernelGGL(estoi_long_kernel, dim3(N), dim3(1024), 0, s, p);
+        EstoiLongP p{clean, pred, fir, bands, bands + ES_BANDS, rs, oa, pw, score, N, n_samples, n_fir, up, down, n_pre_remove, n_resampled, EstoiRag{}};
+        hipLaunchKernelGGL(estoi_resample_kernel<false>, dim3((n_resampled + 255) / 256, 2, N), dim3(256), 0, s, p);
+        hipLaunchKernelGGL(estoi_long_kernel<false>, dim3(N), dim3(1024), 0, s, p);
+    }
+    L2S_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------------------------------ ragged forms
+int l2s_inverse_mel_ragged_check(const int* L, const int64_t* mel_offset, const int64_t* mel_pitch, int N, int64_t mel_floats, int n_mels, int n_freqs,
+                                 int fb_nnz, int iters) {
+    const char* fn = "inverse_mel_ragged";
+    if (ragged_lengths_check(fn, L, N)) return 1;
+    L2S_REQUIRE(mel_offset && mel_pitch, "inverse_mel_ragged: null table of mel offsets or pitches");
+    L2S_REQUIRE(n_mels > 0 && n_mels <= IM_MAXM && n_freqs > 0 && n_freqs <= IM_MAXF, "inverse_mel_ragged: at most 128 mel bands and 576 frequency bins");
+    L2S_REQUIRE(fb_nnz > 0 && fb_nnz <= IM_NNZ, "inverse_mel_ragged: the filterbank's non-zero count (host-side, exact) must be given and at most 2048");
+    L2S_REQUIRE(iters >= 0 && mel_floats >= 0, "inverse_mel_ragged: sizes");
+    for (int b = 0; b < N; ++b) {
+        if (mel_offset[b] < 0) return clip_error(fn, b, "mel offset " + std::to_string(mel_offset[b]) + " is negative");
+        if (mel_pitch[b] < L[b]) return clip_error(fn, b, "mel pitch " + std::to_string(mel_pitch[b]) + " is below its " + std::to_string(L[b]) + " frames");
+        if (mel_pitch[b] > ((int64_t)1 << 40)) return clip_error(fn, b, "mel pitch " + std::to_string(mel_pitch[b]) + " is above 2^40");
+        const int64_t end = mel_offset[b] + (int64_t)(n_mels - 1) * mel_pitch[b] + L[b];
+        if (end > mel_floats)
+            return clip_error(fn, b, "its mel (offset " + std::to_string(mel_offset[b]) + ", pitch " + std::to_string(mel_pitch[b]) + ", " + std::to_string(L[b]) +
+                              " frames) is read up to float " + std::to_string(end) + ", past the buffer of " + std::to_string(mel_floats));
+    }
+    return 0;
+}
+
+// never below the sum of the solo sizers (N = 1, L = L_b): a caller that sized for a loop of solo calls has enough
+int64_t l2s_inverse_mel_ragged_workspace_bytes(const int* L, int N, int n_mels, int n_freqs, int iters) {
+    if (ragged_lengths_check("inverse_mel_ragged", L, N)) return -1;
+    int64_t bytes = 256 + 2 * im_align((int64_t)N * 8) + im_align(((int64_t)N + 1) * 4);
+    for (int b = 0; b < N; ++b) bytes += l2s_inverse_mel_workspace_bytes(1, L[b], n_mels, n_freqs, 1, iters);
+    return bytes;
+}
+
+int l2s_inverse_mel_ragged(const float* mel, int64_t mel_floats, const int64_t* mel_offset, const int64_t* mel_pitch, const int* L, int N, int log_input,
+                           const float* fb, int fb_nnz, const float* init, int n_mels, int n_freqs, int iters, float* spec, float* loss_per_iter,
+                           int* iters_run, void* ws, int64_t ws_bytes, void* stream) {
+    if (l2s_inverse_mel_ragged_check(L, mel_offset, mel_pitch, N, mel_floats, n_mels, n_freqs, fb_nnz, iters)) return 1;
+    L2S_REQUIRE(mel && fb && init && spec && ws, "inverse_mel_ragged: null argument");
+    L2S_REQUIRE(ws_bytes >= l2s_inverse_mel_ragged_workspace_bytes(L, N, n_mels, n_freqs, iters), "inverse_mel_ragged: workspace too small");
+    hipStream_t s = (hipStream_t)stream;
+    std::vector<int> t((size_t)4 * N + (size_t)N + 1);           // mel_offset and mel_pitch as int64 (two ints each), then the row prefix sums
+    memcpy(t.data(), mel_offset, (size_t)N * 8);
+    memcpy(t.data() + 2 * (size_t)N, mel_pitch, (size_t)N * 8);
+    int64_t rows = 0;
+    for (int b = 0; b < N; ++b) { t[4 * (size_t)N + b] = (int)rows; rows += L[b]; }
+    t[4 * (size_t)N + N] = (int)rows;
+    char* w = (char*)(((uintptr_t)ws + 255) / 256 * 256);
+    int* tab = (int*)w; w += im_align((3 * (int64_t)(n_mels + n_freqs) + 2) * 4);
+    float* fwd = (float*)w; w += im_align(IM_NNZ * 4);
+    float* bwd = (float*)w; w += im_align(IM_NNZ * 4);
+    float* loss_rows = (float*)w; w += im_align(rows * (iters > 0 ? iters : 1) * 4);
+    int* iters_ws = (int*)w; w += im_align((int64_t)N * 4);
+    int* table = (int*)w;                                        // 256-byte aligned: the int64 arrays come first
+    const int64_t* d_off = (const int64_t*)table;
+    const int64_t* d_pitch = d_off + N;
+    const int* d_row_off = table + 4 * (size_t)N;
+    int* iters_call = iters_run ? iters_run : iters_ws;
+    ProfScope ps("vocoder_inverse_mel_ragged", s);
+    upload_table(table, t, s);
+    if (launch_mel_bands(fb, n_freqs, n_mels, tab, fwd, bwd, s)) return 1;      // once per call, whatever N
+    InvMelP p{mel, init, tab, fwd, bwd, spec, iters > 0 ? loss_rows : nullptr, nullptr, N, 0, n_mels, n_freqs, 1, iters, log_input, 0, d_row_off, d_off, d_pitch};
+    const unsigned blocks = (unsigned)((rows + IM_ROWS - 1) / IM_ROWS);
+    hipLaunchKernelGGL(inverse_mel_kernel<true>, dim3(blocks), dim3(IM_ROWS * 64), 0, s, p);
+    if (iters > 0) {
+        hipLaunchKernelGGL(inverse_mel_stop_kernel, dim3(N), dim3(256), 0, s, loss_rows, (int)rows, 0, iters, iters_call, loss_per_iter, d_row_off);
+        p.loss_rows = nullptr; p.iters_call = iters_call; p.second = 1;
+        hipLaunchKernelGGL(inverse_mel_kernel<true>, dim3(blocks), dim3(IM_ROWS * 64), 0, s, p);      // only the clips a stopping rule ended early re-run
+    }
+    L2S_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+int l2s_griffin_lim_ragged_check(const int* L, int N, int n_fft, int hop, int iters, int64_t wave_pitch) {
+    const char* fn = "griffin_lim_ragged";
+    L2S_REQUIRE(n_fft == GL_NFFT && hop == GL_HOP, "griffin_lim_ragged: built for n_fft = win_length = 1024, hop 256 (hparams.py)");
+    if (ragged_lengths_check(fn, L, N)) return 1;
+    L2S_REQUIRE(iters >= 0, "griffin_lim_ragged: sizes");
+    for (int b = 0; b < N; ++b)
+        if ((int64_t)GL_HOP * (L[b] - 1) > wave_pitch)
+            return clip_error(fn, b, "its " + std::to_string((int64_t)GL_HOP * (L[b] - 1)) + " samples do not fit the row pitch of " + std::to_string(wave_pitch) +
+                              ": the rows of wave would overlap");
+    return 0;
+}
+
+int64_t l2s_griffin_lim_ragged_workspace_bytes(const int* L, int N) {
+    if (ragged_lengths_check("griffin_lim_ragged", L, N)) return -1;
+    int64_t frames = 0;
+    for (int b = 0; b < N; ++b) frames += L[b];
+    // three slots of rebuilt spectra per frame whatever the clip's form (one block offset serves every form), and the solo sizers' 512 bytes per clip:
+    // never below their sum
+    return 512 + im_align((3 * (int64_t)N + 3) * 4) + frames * GL_LDK * 4 + frames * 3 * GL_LDK * 8 + 512 * (int64_t)N;
+}
+
+int l2s_griffin_lim_ragged(const float* power_spec, const float* init_angles, const int* L, int N, int n_fft, int hop, int iters, float momentum,
+                           float* wave, int64_t wave_pitch, void* ws, int64_t ws_bytes, void* stream) {
+    if (l2s_griffin_lim_ragged_check(L, N, n_fft, hop, iters, wave_pitch)) return 1;
+    L2S_REQUIRE(power_spec && init_angles && wave && ws, "griffin_lim_ragged: null argument");
+    L2S_REQUIRE(ws_bytes >= l2s_griffin_lim_ragged_workspace_bytes(L, N), "griffin_lim_ragged: workspace too small");
+    hipStream_t s = (hipStream_t)stream;
+    // table: frame_off[N + 1] | clips of the 12-wave form | of the 8-wave form | of the tile form | tile_off[n_long + 1]
+    std::vector<int> t((size_t)N + 1), l12, l8, ll, toff;
+    int64_t frames = 0;
+    int long_max = 0, tiles = 0;
+    for (int b = 0; b < N; ++b) {
+        t[b] = (int)frames; frames += L[b];
+        const int ylen = GL_HOP * (L[b] - 1);
+        if (ylen <= 19456) l12.push_back(b);
+        else if (ylen <= 30720) l8.push_back(b);
+        else { toff.push_back(tiles); tiles += (L[b] + GLT_F - 1) / GLT_F; ll.push_back(b); long_max = std::max(long_max, L[b]); }
+    }
+    t[N] = (int)frames;
+    const int n12 = (int)l12.size(), n8 = (int)l8.size(), nl = (int)ll.size();
+    if (nl) toff.push_back(tiles);
+    t.insert(t.end(), l12.begin(), l12.end());
+    t.insert(t.end(), l8.begin(), l8.end());
+    t.insert(t.end(), ll.begin(), ll.end());
+    t.insert(t.end(), toff.begin(), toff.end());
+    char* w = (char*)(((uintptr_t)ws + 255) / 256 * 256);
+    int* table = (int*)w; w += im_align((3 * (int64_t)N + 3) * 4);
+    float* mag = (float*)w;
+    float2* reb = (float2*)(w + frames * GL_LDK * 4);
+    const int* d_off = table;
+    const int* d12 = table + N + 1;
+    const int* d8 = d12 + n12;
+    const int* dl = d8 + n8;
+    const int* dt = dl + nl;
+    ProfScope ps("vocoder_griffin_lim_ragged", s);
+    upload_table(table, t, s);
+    const float mom = momentum / (1.0f + momentum);
+    if (n12) {
+        GriffinP p{power_spec, init_angles, mag, reb, wave, N, 0, iters, mom, d_off, d12, wave_pitch};
+        hipLaunchKernelGGL((griffin_lim_kernel<12, 19456, true>), dim3(n12), dim3(768), 0, s, p);
+    }
+    if (n8) {
+        GriffinP p{power_spec, init_angles, mag, reb, wave, N, 0, iters, mom, d_off, d8, wave_pitch};
+        hipLaunchKernelGGL((griffin_lim_kernel<8, 30720, true>), dim3(n8), dim3(512), 0, s, p);
+    }
+    if (nl) {                                      // one launch per iteration over the (clip, tile) pairs of the long clips only
+        hipLaunchKernelGGL(griffin_lim_tile_prologue_kernel, dim3((GL_NBIN * long_max + 255) / 256, nl), dim3(256), 0, s, power_spec, init_angles, mag, reb, 0, d_off, dl);
+        GriffinTileP p{mag, reb, wave, N, 0, 0, iters, mom, d_off, dl, dt, nl, wave_pitch};
+        for (p.it = 0; p.it <= iters; ++p.it)
+            hipLaunchKernelGGL((griffin_lim_tile_kernel<GLT_NW, GLT_F, true>), dim3(tiles), dim3(GLT_NW * 64), 0, s, p);
+    }
+    L2S_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+int l2s_estoi_ragged_check(const int* n_samples, const int* n_fir, const int* n_resampled, int N, int64_t pitch, int has_fir, int n_fir_max, int up, int down,
+                           int n_pre_remove) {
+    const char* fn = "estoi_ragged";
+    if (N < 1 || N > RAG_MAX_CLIPS) { set_error("l2s: estoi_ragged: N = " + std::to_string(N) + " clips is outside [1, 65535]"); return 1; }
+    L2S_REQUIRE(n_samples && n_resampled && (!has_fir || n_fir), "estoi_ragged: null table of sample counts, filter lengths or resampled lengths");
+    L2S_REQUIRE(!has_fir || (n_fir_max > 0 && up > 0 && down > 0 && n_pre_remove >= 0), "estoi_ragged: resampler arguments");
+    for (int b = 0; b < N; ++b) {
+        if (n_samples[b] < 1) return clip_error(fn, b, std::to_string(n_samples[b]) + " samples: at least one is needed");
+        if (n_samples[b] > pitch)
+            return clip_error(fn, b, "its " + std::to_string(n_samples[b]) + " samples do not fit the row pitch of " + std::to_string(pitch) + ": the rows would overlap");
+        if (n_resampled[b] < 1 || n_resampled[b] > ESL_MAXLEN)
+            return clip_error(fn, b, std::to_string(n_resampled[b]) + " samples at 10 kHz: outside [1, 48256] (4.8 s)");
+        if (has_fir && (n_fir[b] < 1 || n_fir[b] > n_fir_max))
+            return clip_error(fn, b, "its filter of " + std::to_string(n_fir[b]) + " taps is not a prefix of the call's table of " + std::to_string(n_fir_max));
+        if (!has_fir && n_resampled[b] != n_samples[b]) return clip_error(fn, b, "without a resampling filter n_resampled must equal n_samples");
+    }
+    return 0;
+}
+
+// the sum of the solo sizers (each clip's form by its own n_resampled) plus the tables
+int64_t l2s_estoi_ragged_workspace_bytes(const int* n_resampled, int N) {
+    if (N < 1 || N > RAG_MAX_CLIPS || !n_resampled) { set_error("l2s: estoi_ragged: N outside [1, 65535] or a null table of resampled lengths"); return -1; }
+    int64_t bytes = 256 + im_align((4 * (int64_t)N + 2 * ES_BANDS) * 4);
+    for (int b = 0; b < N; ++b) bytes += l2s_estoi_workspace_bytes_long(1, n_resampled[b]);
+    return bytes;
+}
+
+int l2s_estoi_ragged(const float* clean, const float* pred, int64_t pitch, const int* n_samples, int N, const float* fir, int n_fir_max, const int* n_fir,
+                     int up, int down, int n_pre_remove, const int* n_resampled, const int* band_lo_hi_host, float* score, void* ws, int64_t ws_bytes,
+                     void* stream) {
+    if (l2s_estoi_ragged_check(n_samples, n_fir, n_resampled, N, pitch, fir != nullptr, n_fir_max, up, down, n_pre_remove)) return 1;
+    L2S_REQUIRE(clean && pred && score && ws && band_lo_hi_host, "estoi_ragged: null argument");
+    L2S_REQUIRE(ws_bytes >= l2s_estoi_ragged_workspace_bytes(n_resampled, N), "estoi_ragged: workspace too small");
+    for (int b = 0; b < ES_BANDS; ++b)
+        L2S_REQUIRE(band_lo_hi_host[b] >= 0 && band_lo_hi_host[b] <= band_lo_hi_host[ES_BANDS + b] && band_lo_hi_host[ES_BANDS + b] <= ES_NBIN &&
+                    (b == 0 || band_lo_hi_host[b] >= band_lo_hi_host[b - 1]), "estoi_ragged: band edges");
+    hipStream_t s = (hipStream_t)stream;
+    // table: n_samples[N] | n_fir[N] | n_resampled[N] | clips of the short form, then of the long form [N] | band edges [30]
+    std::vector<int> t((size_t)4 * N + 2 * ES_BANDS), ls, ll;
+    int long_max = 0;
+    for (int b = 0; b < N; ++b) {
+        t[b] = n_samples[b]; t[(size_t)N + b] = fir ? n_fir[b] : 0; t[2 * (size_t)N + b] = n_resampled[b];
+        if (n_resampled[b] <= ES_MAXLEN) ls.push_back(b); else { ll.push_back(b); long_max = std::max(long_max, n_resampled[b]); }
+    }
+    const int ns = (int)ls.size(), nl = (int)ll.size();
+    std::copy(ls.begin(), ls.end(), t.begin() + 3 * (size_t)N);
+    std::copy(ll.begin(), ll.end(), t.begin() + 3 * (size_t)N + ns);
+    std::copy(band_lo_hi_host, band_lo_hi_host + 2 * ES_BANDS, t.begin() + 4 * (size_t)N);
+    char* w = (char*)(((uintptr_t)ws + 255) / 256 * 256);
+    int* table = (int*)w; w += im_align((4 * (int64_t)N + 2 * ES_BANDS) * 4);
+    const int* bands = table + 4 * (size_t)N;
+    float* rs_s = (float*)w;                                                  // short slots: (ns, 2, ES_MAXLEN) then (ns, 2, ES_MAXFRAMES, ES_NBIN)
+    float* pw_s = rs_s + (int64_t)ns * 2 * ES_MAXLEN;
+    float* rs_l = pw_s + (int64_t)ns * 2 * ES_MAXFRAMES * ES_NBIN;            // long slots: rs, oa (nl, 2, ESL_MAXLEN) each, then the spectra
+    float* oa_l = rs_l + (int64_t)nl * 2 * ESL_MAXLEN;
+    float* pw_l = oa_l + (int64_t)nl * 2 * ESL_MAXLEN;
+    ProfScope ps("metric_estoi_ragged", s);
+    upload_table(table, t, s);
+    if (ns) {
+        EstoiP p{clean, pred, fir, bands, bands + ES_BANDS, rs_s, pw_s, score, N, 0, 0, up, down, n_pre_remove, 0,
+                 EstoiRag{table, table + N, table + 2 * (size_t)N, table + 3 * (size_t)N, pitch}};
+        hipLaunchKernelGGL(estoi_kernel<true>, dim3(ns), dim3(1024), 0, s, p);
+    }
+    if (nl) {
+        EstoiLongP p{clean, pred, fir, bands, bands + ES_BANDS, rs_l, oa_l, pw_l, score, N, 0, 0, up, down, n_pre_remove, 0,
+                     EstoiRag{table, table + N, table + 2 * (size_t)N, table + 3 * (size_t)N + ns, pitch}};
+        hipLaunchKernelGGL(estoi_resample_kernel<true>, dim3((long_max + 255) / 256, 2, nl), dim3(256), 0, s, p);
+        hipLaunchKernelGGL(estoi_long_kernel<true>, dim3(nl), dim3(1024), 0, s, p);
     }
     L2S_CHECK_HIP(hipGetLastError());
     return 0;

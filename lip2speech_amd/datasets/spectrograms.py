@@ -112,13 +112,87 @@ class MelSpec2Audio(torch.nn.Module):
             raise RuntimeError("MelSpec2Audio(backend='hip'): needs device tensors, n_fft = win = 1024, hop 256 and at least 5 frames per clip")
         return ok and self.backend in ("auto", "hip")
 
+    # -- clips of unequal length (`lengths=`): every clip exactly as the solo call `self(melspec[b:b+1, :, :L_b], generator)` computes it
+    @staticmethod
+    def _check_lengths(t: torch.Tensor, lengths) -> list:
+        lengths = [int(v) for v in lengths]
+        if len(lengths) != t.shape[0] or not lengths or min(lengths) < 2 or max(lengths) > t.shape[-1]:
+            raise ValueError(f"lengths: one frame count in [2, {t.shape[-1]}] per clip of the batch of {t.shape[0]}, got {lengths}")
+        return lengths
+
+    def _use_hip_lengths(self, t: torch.Tensor, lengths) -> bool:
+        """The ragged kernels take the call when every clip is inside the solo kernels' envelope (at least 5 frames)."""
+        return self._use_hip(t, min(lengths))
+
+    def _draw_init(self, t: torch.Tensor, L: int, generator) -> torch.Tensor:
+        return torch.rand(1, L, self.fb.shape[0], device=t.device, dtype=t.dtype, generator=generator)      # what the solo inverse_mel draws
+
+    def _draw_angles(self, t: torch.Tensor, L: int, generator) -> torch.Tensor:
+        return torch.rand(1, self.fb.shape[0], L, 2, device=t.device, dtype=t.dtype, generator=generator)   # what the solo griffin_lim draws
+
+    @staticmethod
+    def _pad_blocks(flat: torch.Tensor, lengths, rows: int) -> torch.Tensor:
+        """Packed per-clip (rows, L_b) blocks -> (N, rows, max L_b), zeros past each clip."""
+        out = flat.new_zeros(len(lengths), rows, max(lengths))
+        o = 0
+        for b, L in enumerate(lengths):
+            out[b, :, :L] = flat[o: o + rows * L].view(rows, L)
+            o += rows * L
+        return out
+
+    def _inverse_mel_lengths(self, mel: torch.Tensor, generator, lengths) -> torch.Tensor:
+        """`inverse_mel(lengths=...)`: mel (N, n_mels, L_pad), clip b its first lengths[b] frames -> (N, n_freqs, max L_b), clip b as the solo call on
+        `mel[b:b+1, :, :L_b]` computes it (its own gradient scale, loss mean and stopping rules), zeros behind; the start iterates are drawn clip by clip."""
+        lengths = self._check_lengths(mel, lengths)
+        if self._use_hip_lengths(mel, lengths):
+            from .. import native
+            init = torch.cat([self._draw_init(mel, L, generator)[0] for L in lengths], dim=0)
+            return self._pad_blocks(native.inverse_mel_ragged(mel, lengths, self.fb, self.fb_nnz, init, self.max_iters), lengths, self.fb.shape[0])
+        out = mel.new_zeros(len(lengths), self.fb.shape[0], max(lengths))
+        for b, L in enumerate(lengths):
+            out[b, :, :L] = self.inverse_mel(mel[b:b + 1, :, :L], generator)[0]
+        return out
+
+    def _griffin_lim_lengths(self, power_spec: torch.Tensor, generator, lengths) -> torch.Tensor:
+        """`griffin_lim(lengths=...)`: power_spec (N, n_freqs, L_pad) -> (N, hop * (max L_b - 1)), clip b as the solo call on `power_spec[b:b+1, :, :L_b]`
+        computes it, exact zeros behind its hop * (L_b - 1) samples; the start angles are drawn clip by clip."""
+        lengths = self._check_lengths(power_spec, lengths)
+        if self._use_hip_lengths(power_spec, lengths):
+            from .. import native
+            ang = torch.cat([self._draw_angles(power_spec, L, generator).reshape(-1) for L in lengths])
+            packed = torch.cat([power_spec[b, :, :L].reshape(-1) for b, L in enumerate(lengths)])
+            return native.griffin_lim_ragged(packed, ang, lengths, self.max_iters, None, self.n_fft, self.hop, 0.99)
+        out = power_spec.new_zeros(len(lengths), self.hop * (max(lengths) - 1))
+        for b, L in enumerate(lengths):
+            out[b, :self.hop * (L - 1)] = self.griffin_lim(power_spec[b:b + 1, :, :L], generator)[0]
+        return out
+
+    def _forward_lengths(self, melspec: torch.Tensor, generator, lengths) -> torch.Tensor:
+        """`forward(lengths=...)`.  A solo call draws its clip's start spectrum, then its start angles: the draws here come in that order, clip by clip, so
+        both routes are the loop of solo calls on the same generator - the torch route literally, the kernels in two ragged launch chains."""
+        lengths = self._check_lengths(melspec, lengths)
+        if self._use_hip_lengths(melspec, lengths):
+            from .. import native
+            mel = spectral_de_normalize(melspec.to(torch.float32))
+            drawn = [(self._draw_init(mel, L, generator)[0], self._draw_angles(mel, L, generator).reshape(-1)) for L in lengths]
+            spec = native.inverse_mel_ragged(mel, lengths, self.fb, self.fb_nnz, torch.cat([d[0] for d in drawn], dim=0), self.max_iters)
+            return native.griffin_lim_ragged(spec, torch.cat([d[1] for d in drawn]), lengths, self.max_iters, None, self.n_fft, self.hop, 0.99)
+        out = torch.zeros(len(lengths), self.hop * (max(lengths) - 1), device=melspec.device, dtype=torch.float32)
+        for b, L in enumerate(lengths):
+            out[b, :self.hop * (L - 1)] = self(melspec[b:b + 1, :, :L], generator)[0]
+        return out
+
     # -- torchaudio.transforms.InverseMelScale.forward (0.9.0)
-    def inverse_mel(self, mel: torch.Tensor, generator=None, rows_per_call: int = None) -> torch.Tensor:
+    def inverse_mel(self, mel: torch.Tensor, generator=None, rows_per_call: int = None, lengths=None) -> torch.Tensor:
         """mel (B, n_mels, L) power-mel -> power spectrogram (B, n_freqs, L) >= 0.  The reference's loop reads its loss on the host every
         iteration (`new_loss.item()`) for the two stopping rules; here the rules are evaluated on the device and freeze the iterate from the
         stopping iteration on, so the 256 iterations are enqueued without a single host synchronisation and end at the same iterate.
         `rows_per_call`: the rows are G independent calls of that many rows each (several loader batches vocoded in one pass): the loss mean,
-        the 1/(B*L) gradient scale and the stopping rules are per call, exactly as G separate calls would have them."""
+        the 1/(B*L) gradient scale and the stopping rules are per call, exactly as G separate calls would have them.
+        `lengths` (a host sequence, one frame count per clip; not with `rows_per_call`): every clip is its own call over its own frames (`_inverse_mel_lengths`)."""
+        if lengths is not None:
+            assert rows_per_call is None, "lengths makes every clip its own call"
+            return self._inverse_mel_lengths(mel, generator, lengths)
         N, _, L = mel.shape
         R = rows_per_call or N
         assert N % R == 0, "rows_per_call must divide the batch"
@@ -145,7 +219,9 @@ class MelSpec2Audio(torch.nn.Module):
         return spec.reshape(N, L, -1).transpose(1, 2)
 
     # -- torchaudio.functional.griffinlim (0.9.0): power 2, momentum 0.99, rand_init
-    def griffin_lim(self, power_spec: torch.Tensor, generator=None) -> torch.Tensor:
+    def griffin_lim(self, power_spec: torch.Tensor, generator=None, lengths=None) -> torch.Tensor:
+        if lengths is not None:
+            return self._griffin_lim_lengths(power_spec, generator, lengths)
         mag = power_spec.clamp(min=0).sqrt()                                      # (B, n_freqs, L)
         B, _, L = mag.shape
         length = self.hop * (L - 1)
@@ -165,7 +241,14 @@ class MelSpec2Audio(torch.nn.Module):
             prev = rebuilt
         return istft(mag * ang)
 
-    def forward(self, melspec: torch.Tensor, generator=None, rows_per_call: int = None) -> torch.Tensor:
-        """(B, n_mels, L) log-mel -> (B, hop*(L-1)) waveform.  `rows_per_call`: see `inverse_mel` (Griffin-Lim is per clip anyway)."""
+    def forward(self, melspec: torch.Tensor, generator=None, rows_per_call: int = None, lengths=None) -> torch.Tensor:
+        """(B, n_mels, L) log-mel -> (B, hop*(L-1)) waveform.  `rows_per_call`: see `inverse_mel` (Griffin-Lim is per clip anyway).
+        `lengths` (a host sequence, one frame count per clip): -> (B, hop * (max L_b - 1)), clip b exactly the solo call `self(melspec[b:b+1, :, :L_b],
+        generator)` in a loop over b on the same generator (pad frames are never read), exact zeros behind its hop * (L_b - 1) samples.  With
+        backend "auto" the kernels take device tensors when every L_b >= 5 (`l2s_inverse_mel_ragged`, `l2s_griffin_lim_ragged`: two launch chains for
+        the whole batch)."""
+        if lengths is not None:
+            assert rows_per_call is None, "lengths makes every clip its own call"
+            return self._forward_lengths(melspec, generator, lengths)
         mel = spectral_de_normalize(melspec.to(torch.float32))
         return self.griffin_lim(self.inverse_mel(mel, generator, rows_per_call), generator)

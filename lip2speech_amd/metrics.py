@@ -181,11 +181,39 @@ def band_edges():
 
 
 _plans = {}
+_ragged_fir = {}        # (fs, device) -> (n_in the filter was planned for, device FIR): the longest plan so far serves every call (its prefixes are the shorter plans)
+_ragged_sizes = {}      # (n_in, fs) -> (taps of that length's own plan, its output length)
 
 
-def estoi_device(clean, pred, fs_sig: int):
+def _estoi_device_ragged(clean, pred, fs_sig: int, lengths):
+    """`estoi_device` with per-clip sample counts: one `l2s_estoi_ragged` call, one FIR table.  `resample_poly_plan(n, ...)` for different n differ only in the
+    trailing zero pad (n_pre_pad and n_pre_remove depend on up / down alone), so clip b uses the first taps of the longest plan, as many as its own plan has."""
+    import torch
+    from . import native
+    lengths = [int(v) for v in lengths]
+    assert clean.shape == pred.shape and len(lengths) == clean.shape[0], (clean.shape, pred.shape, len(lengths))
+    sizes = []
+    for n in lengths:
+        if (n, int(fs_sig)) not in _ragged_sizes:
+            h, _, _, _, n_out = resample_poly_plan(n, FS, fs_sig)
+            _ragged_sizes[n, int(fs_sig)] = (0 if h is None else len(h), n_out)
+        sizes.append(_ragged_sizes[n, int(fs_sig)])
+    key = (int(fs_sig), str(clean.device))
+    n_max = max(lengths)
+    if key not in _ragged_fir or _ragged_fir[key][0] < n_max:
+        h, up, down, n_pre, _ = resample_poly_plan(n_max, FS, fs_sig)
+        _ragged_fir[key] = (n_max, None if h is None else torch.from_numpy(h.astype(np.float32)).to(clean.device), up, down, n_pre)
+    _, fir, up, down, n_pre = _ragged_fir[key]
+    return native.estoi_ragged(clean, pred, lengths, fir, None if fir is None else [s[0] for s in sizes], up, down, n_pre, [s[1] for s in sizes], band_edges())
+
+
+def estoi_device(clean, pred, fs_sig: int, lengths=None):
     """ESTOI of every row of `pred` against the same row of `clean` (device tensors (N, n_samples)) by the HIP kernel behind `l2s_estoi`:
-    the algorithm of `stoi(x, y, fs_sig, extended=True)` above, one block per clip.  Returns a device tensor (N,)."""
+    the algorithm of `stoi(x, y, fs_sig, extended=True)` above, one block per clip.  Returns a device tensor (N,).
+    `lengths` (a host sequence, one sample count per clip): row b is scored over its first lengths[b] samples only, exactly as this function scores
+    `clean[b:b+1, :lengths[b]]` against `pred[b:b+1, :lengths[b]]` alone - whatever lies behind them (`l2s_estoi_ragged`, one call)."""
+    if lengths is not None:
+        return _estoi_device_ragged(clean, pred, fs_sig, lengths)
     import torch
     from . import native
     n = int(clean.shape[1])

@@ -39,6 +39,9 @@ ABI_SYMBOLS = (
     "l2s_speaker_packed_plan", "l2s_speaker_workspace_bytes_packed", "l2s_speaker_encoder_packed",
     "l2s_face_workspace_bytes", "l2s_face_encoder_fwd",
     "l2s_inverse_mel_workspace_bytes", "l2s_inverse_mel", "l2s_griffin_lim_workspace_bytes", "l2s_griffin_lim", "l2s_estoi_workspace_bytes", "l2s_estoi_workspace_bytes_long", "l2s_estoi",
+    "l2s_inverse_mel_ragged_check", "l2s_inverse_mel_ragged_workspace_bytes", "l2s_inverse_mel_ragged",
+    "l2s_griffin_lim_ragged_check", "l2s_griffin_lim_ragged_workspace_bytes", "l2s_griffin_lim_ragged",
+    "l2s_estoi_ragged_check", "l2s_estoi_ragged_workspace_bytes", "l2s_estoi_ragged",
     "l2s_set_option",
     "l2s_train_scratch_bytes", "l2s_loss", "l2s_grad_norm", "l2s_adamw_amsgrad_step",
     "l2s_train_steps_tape_floats", "l2s_train_steps_weights_floats", "l2s_train_steps_ws_bytes", "l2s_train_steps_pack_weights",
@@ -222,6 +225,22 @@ def _bind(L: ctypes.CDLL) -> None:
     if hasattr(L, "l2s_estoi_workspace_bytes_long"):
         L.l2s_estoi_workspace_bytes_long.argtypes = [_i, _i]
         L.l2s_estoi_workspace_bytes_long.restype = _i64
+    # the ragged forms of the vocoder and the metric (include/l2s.h): likewise absent from a library built before them
+    # (tools/vocoder_ragged/time_vocoder_ragged.py times one next to this build)
+    if hasattr(L, "l2s_griffin_lim_ragged"):
+        _ints, _offs = ctypes.POINTER(ctypes.c_int), ctypes.POINTER(_i64)
+        L.l2s_inverse_mel_ragged_check.argtypes = [_ints, _offs, _offs, _i, _i64, _i, _i, _i, _i]
+        L.l2s_inverse_mel_ragged_workspace_bytes.argtypes = [_ints, _i, _i, _i, _i]
+        L.l2s_inverse_mel_ragged_workspace_bytes.restype = _i64
+        L.l2s_inverse_mel_ragged.argtypes = [_fp, _i64, _offs, _offs, _ints, _i, _i, _fp, _i, _fp, _i, _i, _i, _fp, _fp, _vp, _vp, _i64, _vp]
+        L.l2s_griffin_lim_ragged_check.argtypes = [_ints, _i, _i, _i, _i, _i64]
+        L.l2s_griffin_lim_ragged_workspace_bytes.argtypes = [_ints, _i]
+        L.l2s_griffin_lim_ragged_workspace_bytes.restype = _i64
+        L.l2s_griffin_lim_ragged.argtypes = [_fp, _fp, _ints, _i, _i, _i, _i, ctypes.c_float, _fp, _i64, _vp, _i64, _vp]
+        L.l2s_estoi_ragged_check.argtypes = [_ints, _ints, _ints, _i, _i64, _i, _i, _i, _i, _i]
+        L.l2s_estoi_ragged_workspace_bytes.argtypes = [_ints, _i]
+        L.l2s_estoi_ragged_workspace_bytes.restype = _i64
+        L.l2s_estoi_ragged.argtypes = [_fp, _fp, _i64, _ints, _i, _fp, _i, _ints, _i, _i, _i, _ints, _ints, _fp, _vp, _i64, _vp]
     L.l2s_profile_enable.argtypes = [_i]
     L.l2s_profile_get.argtypes = [_i, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(_i64), ctypes.POINTER(ctypes.c_double)]
     # per-clip video lengths: the unmasked signature plus the host length array.  A library of the same ABI version built before these entry points
@@ -1642,4 +1661,111 @@ def estoi(clean: torch.Tensor, pred: torch.Tensor, fir: Optional[torch.Tensor], 
     score = torch.empty(N, dtype=torch.float32, device=clean.device)
     check(L.l2s_estoi(clean.data_ptr(), pred.data_ptr(), N, n, _ptr(fir), 0 if fir is None else fir.numel(), up, down, n_pre_remove, n_resampled,
                       bands, score.data_ptr(), ws.data_ptr(), ws.numel(), _stream()))
+    return score
+
+
+# ------------------------------------------------------------------------------------- the same three stages over clips of unequal length (include/l2s.h)
+def _ints(values) -> Optional[ctypes.Array]:
+    """A host int table for the *_ragged entry points (None stays a null pointer: the host checks refuse it)."""
+    return None if values is None else (ctypes.c_int * len(values))(*[int(v) for v in values])
+
+
+def _int64s(values) -> Optional[ctypes.Array]:
+    return None if values is None else (_i64 * len(values))(*[int(v) for v in values])
+
+
+def padded_mel_layout(N: int, n_mels: int, L_pad: int):
+    """(offsets, pitches) of a contiguous padded (N, n_mels, L_pad) mel tensor, as `inverse_mel_ragged` takes them."""
+    return [b * n_mels * L_pad for b in range(N)], [L_pad] * N
+
+
+def inverse_mel_ragged_check(lengths, offsets, pitches, mel_floats: int, n_mels: int, n_freqs: int, fb_nnz: int, iters: int, N: Optional[int] = None) -> None:
+    """`l2s_inverse_mel_ragged_check`: the pure host check (no device needed); raises with the clip and the limit it breaks."""
+    check(lib().l2s_inverse_mel_ragged_check(_ints(lengths), _int64s(offsets), _int64s(pitches), len(lengths) if N is None else N, int(mel_floats), n_mels, n_freqs,
+                                             int(fb_nnz), iters))
+
+
+def inverse_mel_ragged_workspace_bytes(lengths, n_mels: int, n_freqs: int, iters: int) -> int:
+    return int(lib().l2s_inverse_mel_ragged_workspace_bytes(_ints(lengths), len(lengths), n_mels, n_freqs, iters))
+
+
+def inverse_mel_ragged(mel: torch.Tensor, lengths, fb: torch.Tensor, fb_nnz: int, init: torch.Tensor, iters: int, offsets=None, pitches=None,
+                       log_input: bool = False, want_loss: bool = False):
+    """`l2s_inverse_mel_ragged`: clip b = lengths[b] frames read at mel.flatten()[offsets[b] + m * pitches[b] + l] (default: mel is a padded
+    (N, n_mels, L_pad) tensor, whatever its pad frames hold); init (sum L_b, n_freqs), clips back to back -> spec, flat: clip b's (n_freqs, L_b) block at
+    float n_freqs * sum_{c<b} L_c [, loss (N, iters), iterations run per clip (N,) int32].  Every clip as `inverse_mel` computes it alone."""
+    mel, fb, init = _f32(mel), _f32(fb), _f32(init)
+    lengths = [int(v) for v in lengths]
+    N, (F, M) = len(lengths), fb.shape
+    if offsets is None:
+        assert mel.dim() == 3 and mel.shape[0] == N and mel.shape[1] == M, mel.shape
+        offsets, pitches = padded_mel_layout(N, M, mel.shape[2])
+    inverse_mel_ragged_check(lengths, offsets, pitches, mel.numel(), M, F, fb_nnz, iters)
+    R = sum(lengths)
+    assert tuple(init.shape) == (R, F), (init.shape, R, F)
+    L = lib()
+    ws = torch.empty(int(L.l2s_inverse_mel_ragged_workspace_bytes(_ints(lengths), N, M, F, iters)), dtype=torch.uint8, device=mel.device)
+    spec = torch.empty(R * F, dtype=torch.float32, device=mel.device)
+    loss = torch.empty(N, max(iters, 1), dtype=torch.float32, device=mel.device) if want_loss else None
+    ran = torch.empty(N, dtype=torch.int32, device=mel.device) if want_loss else None
+    check(L.l2s_inverse_mel_ragged(mel.data_ptr(), mel.numel(), _int64s(offsets), _int64s(pitches), _ints(lengths), N, int(log_input), fb.data_ptr(), int(fb_nnz),
+                                   init.data_ptr(), M, F, iters, spec.data_ptr(), _ptr(loss), _ptr(ran), ws.data_ptr(), ws.numel(), _stream()))
+    return (spec, loss, ran) if want_loss else spec
+
+
+def griffin_lim_ragged_check(lengths, iters: int, wave_pitch: int, n_fft: int = 1024, hop: int = 256, N: Optional[int] = None) -> None:
+    """`l2s_griffin_lim_ragged_check`: the pure host check; raises with the clip and the limit it breaks."""
+    check(lib().l2s_griffin_lim_ragged_check(_ints(lengths), len(lengths) if N is None else N, n_fft, hop, iters, int(wave_pitch)))
+
+
+def griffin_lim_ragged_workspace_bytes(lengths) -> int:
+    return int(lib().l2s_griffin_lim_ragged_workspace_bytes(_ints(lengths), len(lengths)))
+
+
+def griffin_lim_ragged(power_spec: torch.Tensor, init_angles: torch.Tensor, lengths, iters: int, wave_pitch: Optional[int] = None, n_fft: int = 1024,
+                       hop: int = 256, momentum: float = 0.99, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """`l2s_griffin_lim_ragged`: power_spec flat, clip b's (n_fft/2+1, L_b) block at float 513 * sum_{c<b} L_c (what `inverse_mel_ragged` returns);
+    init_angles flat float, clip b's (513, L_b, 2) block likewise -> wave (N, wave_pitch), default pitch hop * (max L_b - 1): clip b's hop * (L_b - 1)
+    samples, then exact zeros.  Every clip as `griffin_lim` computes it alone.  `out`: a contiguous (N, wave_pitch) tensor to write instead."""
+    power_spec, ang = _f32(power_spec), _f32(torch.view_as_real(init_angles) if init_angles.is_complex() else init_angles)
+    lengths = [int(v) for v in lengths]
+    N, R = len(lengths), sum(lengths)
+    pitch = int(wave_pitch) if wave_pitch is not None else (out.shape[1] if out is not None else hop * (max(lengths) - 1))
+    griffin_lim_ragged_check(lengths, iters, pitch, n_fft, hop)
+    assert power_spec.numel() == R * (n_fft // 2 + 1) and ang.numel() == 2 * power_spec.numel(), (power_spec.shape, ang.shape, R)
+    L = lib()
+    ws = torch.empty(int(L.l2s_griffin_lim_ragged_workspace_bytes(_ints(lengths), N)), dtype=torch.uint8, device=power_spec.device)
+    wave = out if out is not None else torch.empty(N, pitch, dtype=torch.float32, device=power_spec.device)
+    assert tuple(wave.shape) == (N, pitch) and wave.dtype == torch.float32
+    check(L.l2s_griffin_lim_ragged(power_spec.data_ptr(), ang.data_ptr(), _ints(lengths), N, n_fft, hop, iters, momentum, _ptr(wave), pitch, ws.data_ptr(),
+                                   ws.numel(), _stream()))
+    return wave
+
+
+def estoi_ragged_check(n_samples, n_fir, n_resampled, pitch: int, has_fir: bool, n_fir_max: int, up: int, down: int, n_pre_remove: int,
+                       N: Optional[int] = None) -> None:
+    """`l2s_estoi_ragged_check`: the pure host check; raises with the clip and the limit it breaks."""
+    check(lib().l2s_estoi_ragged_check(_ints(n_samples), _ints(n_fir), _ints(n_resampled), (len(n_samples) if n_samples is not None else 0) if N is None else N,
+                                       int(pitch), int(has_fir), int(n_fir_max), up, down, n_pre_remove))
+
+
+def estoi_ragged_workspace_bytes(n_resampled) -> int:
+    return int(lib().l2s_estoi_ragged_workspace_bytes(_ints(n_resampled), len(n_resampled)))
+
+
+def estoi_ragged(clean: torch.Tensor, pred: torch.Tensor, n_samples, fir: Optional[torch.Tensor], n_fir, up: int, down: int, n_pre_remove: int, n_resampled,
+                 band_lo_hi) -> torch.Tensor:
+    """`l2s_estoi_ragged`: clean / pred (N, pitch) on the device, clip b its first n_samples[b] samples -> ESTOI per clip (N,), each as `estoi` scores the clip
+    alone.  `fir`: the longest clip's padded polyphase filter (device) or None; clip b uses its first n_fir[b] taps and resamples to n_resampled[b]."""
+    clean, pred = _f32(clean), _f32(pred)
+    N, pitch = clean.shape
+    assert pred.shape == clean.shape and len(n_samples) == N
+    n_fir_max = 0 if fir is None else fir.numel()
+    estoi_ragged_check(n_samples, n_fir, n_resampled, pitch, fir is not None, n_fir_max, up, down, n_pre_remove)
+    L = lib()
+    bands = (ctypes.c_int * 30)(*[int(v) for v in band_lo_hi])
+    ws = torch.empty(int(L.l2s_estoi_ragged_workspace_bytes(_ints(n_resampled), N)), dtype=torch.uint8, device=clean.device)
+    score = torch.empty(N, dtype=torch.float32, device=clean.device)
+    check(L.l2s_estoi_ragged(clean.data_ptr(), pred.data_ptr(), pitch, _ints(n_samples), N, _ptr(fir), n_fir_max, _ints(n_fir), up, down, n_pre_remove,
+                             _ints(n_resampled), bands, score.data_ptr(), ws.data_ptr(), ws.numel(), _stream()))
     return score

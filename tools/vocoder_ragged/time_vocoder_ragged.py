@@ -1,0 +1,175 @@
+"""What the ragged forms of the device vocoder and metric buy (include/l2s.h `l2s_inverse_mel_ragged`, `l2s_griffin_lim_ragged`, `l2s_estoi_ragged`;
+vocoder.hip) - the tail of evaluate.py / demo.py, NOT on the mel-frames/s path.  Log-mels of unequal length in, waveforms and ESTOI scores out, the vocoder at
+ITERS + ITERS iterations, three routes over the same clips:
+  (a) solo calls back to back: per clip `MelSpec2Audio(backend="hip")(mel[b:b+1, :, :L_b])` and `estoi_device` on its own samples - what a user of
+      `demo_clips` pays today, and the definition of the other two routes' results;
+  (b) today's padded call per loader batch: `MelSpec2Audio(backend="hip")(mel_batch)` out to the batch's longest clip and `estoi_device` on the padded pairs -
+      what `evaluate_net(honour_lengths=True)` does (it computes something else for every clip but the longest: shown for its time only);
+  (c) one ragged call for everything: `MelSpec2Audio(backend="hip")(mel, lengths=...)` and `estoi_device(..., lengths=...)`.
+Workload one: CLIPS clips of FRAMES mel frames (one GRID batch); workload two: BATCHES such batches.
+EXPECTATION, stated before measuring: (c) beats (a) by roughly the launch count (a long clip's solo vocoder is ~ITERS tile launches, and (c) makes one chain of
+them for all clips); (c) beats (b) on the many-batch workload by running one chain sized by the real frames instead of one chain per batch.
+Then the DEFAULT path: `l2s_griffin_lim` and `l2s_estoi` at DEFAULT_SHAPE from this build and from every library in `ALT_LIBS=name=path[,name=path...]`
+(the parent commit's build) in the same process, with a bit comparison: the solo entry points must not have moved outside the spread.
+ROUNDS interleaved rounds, the variants rotating inside a round, wall clock around REPS synchronised calls; per variant the median of the rounds and the span.
+-> profiles/vocoder_ragged_times.txt (stdout)
+
+Lives in a sub-directory of tools/ (like vocoder_long/): the flat tools/ inventory is pinned by tests/test_tools_smoke.py."""
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, ROOT)
+import numpy as np
+import torch
+
+from lip2speech_amd import metrics, native
+from lip2speech_amd.datasets.spectrograms import MelSpec2Audio, MelSpectrogram
+
+ROUNDS = int(os.environ.get("ROUNDS", 7))
+REPS = int(os.environ.get("REPS", 1))
+ITERS = int(os.environ.get("ITERS", 256))
+CLIPS = int(os.environ.get("CLIPS", 16))
+BATCHES = int(os.environ.get("BATCHES", 8))
+F_LO, F_HI = (int(v) for v in os.environ.get("FRAMES", "63-188").split("-"))
+DEF_N, DEF_L = (int(v) for v in os.environ.get("DEFAULT_SHAPE", "16x188").split("x"))
+FS = 16000
+
+
+def timed(fn, reps):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(reps):
+        fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) / reps * 1e3
+
+
+def rounds(variants):
+    t = [[] for _ in variants]
+    for r in range(ROUNDS):
+        order = list(range(len(variants)))
+        order = order[r % len(order):] + order[:r % len(order)]
+        for i in order:
+            t[i].append(timed(variants[i][1], REPS))
+    return t
+
+
+def report(variants, t):
+    med = [statistics.median(x) for x in t]
+    for (name, _), x, m in zip(variants, t, med):
+        print(f"{name:<58} {m:10.2f} ms  (span {min(x):10.2f} .. {max(x):10.2f}, spread {max(x) - min(x):8.2f})   x{m / med[0]:7.4f} of the first")
+    return med
+
+
+def workload(title, n_batches):
+    rng = np.random.default_rng(n_batches)
+    lengths = [[int(v) for v in rng.integers(F_LO, F_HI + 1, CLIPS)] for _ in range(n_batches)]
+    for ls in lengths:
+        ls[0], ls[-1] = F_HI, F_LO                                   # every batch is padded to the longest clip, as a GRID batch is
+    flat = [L for ls in lengths for L in ls]
+    n_flat = [256 * (L - 1) for L in flat]
+    t = np.arange(256 * (F_HI - 1)) / FS
+    clean = np.stack([np.sin(2 * np.pi * (110 + 7 * i) * t) * (0.5 + 0.5 * np.sin(2 * np.pi * 3.1 * t)) + 0.3 * rng.standard_normal(len(t)) for i in range(len(flat))])
+    clean_dev = torch.from_numpy(clean.astype(np.float32) * 0.1).cuda()
+    for i, n in enumerate(n_flat):
+        clean_dev[i, n:] = 0
+    mel = MelSpectrogram(backend="torch").cuda()(clean_dev)[:, :, :F_HI].contiguous()
+    voc = MelSpec2Audio(max_iters=ITERS, backend="hip").cuda()
+    g = torch.Generator(device="cuda")
+    solo_mels = [mel[i:i + 1, :, :L].contiguous() for i, L in enumerate(flat)]
+    solo_clean = [clean_dev[i:i + 1, :n].contiguous() for i, n in enumerate(n_flat)]
+    keep = {}
+
+    def solo_route():
+        g.manual_seed(1)
+        waves = [voc(m, generator=g) for m in solo_mels]
+        keep["a"] = waves
+        return torch.cat([metrics.estoi_device(c, w, FS) for c, w in zip(solo_clean, waves)]).cpu().numpy()
+
+    def padded_route():
+        g.manual_seed(1)
+        out = []
+        for k in range(n_batches):
+            rows = slice(k * CLIPS, (k + 1) * CLIPS)
+            pred = voc(mel[rows], generator=g)
+            out.append(metrics.estoi_device(clean_dev[rows, :pred.shape[1]].contiguous(), pred, FS))
+        return torch.cat(out).cpu().numpy()
+
+    def ragged_route():
+        pred = voc(mel, generator=g.manual_seed(1), lengths=flat)
+        keep["c"] = pred
+        return metrics.estoi_device(clean_dev[:, :pred.shape[1]].contiguous(), pred, FS, lengths=n_flat).cpu().numpy()
+
+    variants = [("(a) solo calls back to back", solo_route), ("(b) padded call per batch", padded_route), ("(c) one ragged call", ragged_route)]
+    sa, sb, sc = solo_route(), padded_route(), ragged_route()                # warm-up of the three routes
+    print(f"\n== {title}: {n_batches} x {CLIPS} clips of {F_LO}-{F_HI} mel frames ({sum(flat)} frames, {n_batches * CLIPS * F_HI} padded), {ITERS} + {ITERS} iterations")
+    same = all(torch.equal(keep["c"][i, :n], keep["a"][i][0]) and not keep["c"][i, n:].any() for i, n in enumerate(n_flat))
+    print(f"waveforms of (c) bit-identical to (a): {same}; scores of (c) bit-identical to (a): {np.array_equal(sa, sc)}")
+    print(f"mean ESTOI: (a) {sa.mean():.4f}  (b) {sb.mean():.4f}  (c) {sc.mean():.4f}   ((b) scores padded pairs: another quantity for all but the longest clips)")
+    tt = rounds(variants)
+    med = report(variants, tt)
+    print(f"(a) / (c) = {med[0] / med[2]:.2f}, whole span of (c) below the whole span of (a): {max(tt[2]) < min(tt[0])}")
+    print(f"(b) / (c) = {med[1] / med[2]:.2f}, whole span of (c) below the whole span of (b): {max(tt[2]) < min(tt[1])}")
+
+
+def default_path(alts):
+    """The solo entry points at DEFAULT_SHAPE, this build against the other builds: the same bits and the same time."""
+    N, L = DEF_N, DEF_L
+    n = 256 * (L - 1)
+    g = torch.Generator(device="cuda")
+    power = torch.rand(N, 513, L, device="cuda", generator=g.manual_seed(2)) ** 4 * 3.0
+    ang = torch.rand(N, 513, L, 2, device="cuda", generator=g.manual_seed(3))
+    clean = torch.randn(N, n, device="cuda", generator=g.manual_seed(4)) * 0.1
+    pred = clean + 0.05 * torch.randn(N, n, device="cuda", generator=g.manual_seed(5))
+    h, up, down, n_pre, n_out = metrics.resample_poly_plan(n, metrics.FS, FS)
+    fir = torch.from_numpy(h.astype(np.float32)).cuda()
+    import ctypes
+    bands = (ctypes.c_int * 30)(*metrics.band_edges())
+
+    def gl_call(lib):
+        ws = torch.empty(int(lib.l2s_griffin_lim_workspace_bytes(N, L)), dtype=torch.uint8, device="cuda")
+        wave = torch.empty(N, n, device="cuda")
+
+        def call():
+            native.check(lib.l2s_griffin_lim(power.data_ptr(), ang.data_ptr(), N, L, 1024, 256, ITERS, 0.99, wave.data_ptr(), ws.data_ptr(), ws.numel(),
+                                             torch.cuda.current_stream().cuda_stream), lib)
+            return wave
+        return call
+
+    def es_call(lib):
+        ws = torch.empty(int(lib.l2s_estoi_workspace_bytes_long(N, n_out)), dtype=torch.uint8, device="cuda")
+        score = torch.empty(N, device="cuda")
+
+        def call():
+            native.check(lib.l2s_estoi(clean.data_ptr(), pred.data_ptr(), N, n, fir.data_ptr(), fir.numel(), up, down, n_pre, n_out, bands, score.data_ptr(),
+                                       ws.data_ptr(), ws.numel(), torch.cuda.current_stream().cuda_stream), lib)
+            return score
+        return call
+
+    print(f"\n== the default path: l2s_griffin_lim at {N} x {L} ({ITERS} iterations) and l2s_estoi at {N} x {n} samples, this build"
+          + (f" against {', '.join(nm for nm, _ in alts)}" if alts else " (ALT_LIBS not given: nothing to compare with)"))
+    for what, make in (("l2s_griffin_lim", gl_call), ("l2s_estoi", es_call)):
+        variants = [(f"{what}, this build", make(native.lib()))] + [(f"{what}, {nm}", make(lib)) for nm, lib in alts]
+        ref = variants[0][1]().clone()
+        for nm, fn in variants[1:]:
+            print(f"{nm}: output bit-identical to this build's: {torch.equal(fn(), ref)}")
+        tt = rounds(variants)
+        med = report(variants, tt)
+        for (nm, _), x, m in list(zip(variants, tt, med))[1:]:
+            print(f"this build's span ({min(tt[0]):.3f} .. {max(tt[0]):.3f} ms) overlaps the span of {nm} ({min(x):.3f} .. {max(x):.3f}): "
+                  f"{min(tt[0]) <= max(x) and min(x) <= max(tt[0])}")
+
+
+def main():
+    alts = [(a.split("=")[0], native._load(a.split("=")[1])) for a in os.environ.get("ALT_LIBS", "").split(",") if a]
+    print(f"{ROUNDS} interleaved rounds, wall clock around {REPS} synchronised call(s); median of the rounds, span = min .. max")
+    workload("one batch", 1)
+    workload(f"{BATCHES} batches", BATCHES)
+    default_path(alts)
+
+
+if __name__ == "__main__":
+    main()
