@@ -4,11 +4,9 @@ and two clips of lengths 13 / 220 (persistent decode loop), the 22- / 28- / 29-c
 off and on alternating inside a round, HIP events around the REPS calls; per case the median of the rounds and their spread (max - min).
 `DECODE=1` also prints the decode loop's own share from the library's per-kernel event profile (l2s_profile_*; a run of its own: the brackets
 serialise the launches).
--> profiles/early_stop_times.txt (stdout)
-
-Lives in a sub-directory of tools/ (like face_tower/): the flat tools/ inventory is pinned by tests/test_tools_smoke.py."""
+`ROUNDS=`, `REPS=`.
+-> profiles/early_stop_times.txt (stdout)"""
 import os
-import statistics
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -19,6 +17,7 @@ import torch
 
 import early_stop_common as es
 from lip2speech_amd import native, synth
+from tools import abtime
 
 REPS = int(os.environ.get("REPS", 10))
 ROUNDS = int(os.environ.get("ROUNDS", 7))
@@ -33,36 +32,22 @@ def model_for(g, persist):
     sd = dict(synth.synth_state_dict())
     sd["decoder.stop_token_layer.linear_layer.weight"] = g["stop_weight"]
     sd["decoder.stop_token_layer.linear_layer.bias"] = g["stop_bias"]
-    nm = native.NativeModel()
-    nm.set_option("persist_decode", persist)
-    nm.load({k: v.cuda() for k, v in sd.items()}, list(sd.keys()))
-    return nm
-
-
-def timed(fn):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(REPS):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / REPS
+    return abtime.synth_model(state_dict=sd, persist_decode=persist)
 
 
 def ab(name, nm, fn, E):
-    t = {0: [], 1: []}
-    for v in (0, 1):
-        nm.set_option("early_stop", v)
-        fn()
-    torch.cuda.synchronize()
-    for r in range(ROUNDS):
-        for v in ((0, 1) if r % 2 == 0 else (1, 0)):
+    def with_option(v):          # the option is the model's own: every call of a variant sets it first
+        def call():
             nm.set_option("early_stop", v)
-            t[v].append(timed(fn))
+            return fn()
+        return call
+
+    variants = [("    early_stop off", with_option(0)), ("    early_stop on", with_option(1))]
+    t, _ = abtime.rounds(variants, ROUNDS, REPS)
     nm.set_option("early_stop", 0)
-    off, on = statistics.median(t[0]), statistics.median(t[1])
-    so, sn = max(t[0]) - min(t[0]), max(t[1]) - min(t[1])
-    print(f"{name:<44} E={E:3d}  off {off:8.3f} ms (spread {so:5.3f})   on {on:8.3f} ms (spread {sn:5.3f})   on/off {on / off:5.3f}   saved {off - on:7.3f} ms")
+    print(f"{name:<44} E={E:3d}")
+    off, on = abtime.report(variants, t)
+    print(f"    on/off {on / off:5.3f}   saved {off - on:7.3f} ms")
 
 
 def main():

@@ -7,53 +7,26 @@ No earlier code does this work on the device (the reference rotates each frame w
 Workloads: 16 clips x 75 faces of 130 x 130 (GRID-like) and 32 x 29 of 96 x 96.  The upload is outside the timed region.  The native calls are timed through
 ctypes with the job tables built once (`native.align_faces` builds its table per call in Python: listed separately).  ROUNDS interleaved rounds of REPS warm calls
 each, the variants rotating inside a round, HIP events around the REPS calls; per variant the median of the rounds and the spread.
--> profiles/face_align_times.txt (stdout)
-
-Lives in a sub-directory of tools/ (like frame_resize/): the flat tools/ inventory is pinned by tests/test_tools_smoke.py."""
+`SHAPES=BxTxS[,BxTxS...]`: other workloads of B clips x T faces of S x S; `ROUNDS=`, `REPS=`.
+-> profiles/face_align_times.txt (stdout)"""
 import os
-import statistics
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import numpy as np
 import torch
 
 from lip2speech_amd import native
 from lip2speech_amd.datasets import PackedFaces
 from lip2speech_amd.datasets.face_utils import rotation_inverse_map, warp_affine_u8
+from tools import abtime
 
 REPS = int(os.environ.get("REPS", 20))
 ROUNDS = int(os.environ.get("ROUNDS", 7))
 WORKLOADS = (("GRID-like", 16, 75, 130), ("LRW-like", 32, 29, 96))
+if os.environ.get("SHAPES"):
+    WORKLOADS = [(s, *(int(v) for v in s.split("x"))) for s in os.environ["SHAPES"].split(",")]
 PEAK = 8e12
-
-
-def timed(fn):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(REPS):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / REPS
-
-
-def rounds(variants):
-    t = [[] for _ in variants]
-    for r in range(ROUNDS):
-        order = list(range(len(variants)))
-        order = order[r % len(order):] + order[:r % len(order)]
-        for i in order:
-            t[i].append(timed(variants[i][1]))
-    return t
-
-
-def report(variants, t, extra=lambda name, m: ""):
-    med = [statistics.median(x) for x in t]
-    for (name, _), x, m in zip(variants, t, med):
-        print(f"{name:<64} {m * 1e3:9.1f} us  (spread {(max(x) - min(x)) * 1e3:7.1f}, min {min(x) * 1e3:9.1f}, max {max(x) * 1e3:9.1f}){extra(name, m)}")
-    return med
 
 
 def align_call(buf, out, jobs):
@@ -99,7 +72,8 @@ def workload(title, B, T, S):
                 ("(b) l2s_resize_normalise, mouth + face calls alone", lambda: (mouth(), face())),
                 ("(c) all three: align, mouth, face", lambda: (align(), mouth(), face())),
                 ("    native.align_faces (table built per call in Python)", lambda: native.align_faces(buf, jobs, out=out))]
-    report(variants, rounds(variants), lambda name, m: f"   (d) {moved / m / 1e9:7.2f} TB/s = {moved / m * 1e3 / PEAK * 100:5.1f} % of 8 TB/s" if name.startswith("(a)") else "")
+    abtime.report(variants, abtime.rounds(variants, ROUNDS, REPS)[0], unit="us",
+                  extra=lambda name, m: f"   (d) {moved / m / 1e9:7.2f} TB/s = {moved / m * 1e3 / PEAK * 100:5.1f} % of 8 TB/s" if name.startswith("(a)") else "")
 
 
 def main():

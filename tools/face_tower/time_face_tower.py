@@ -2,9 +2,8 @@
 torch-ROCm's own fp32 F.conv2d chain on the same weights (the CPU-side restatement tests/face_tower_torch.py, run on the device) as the
 yardstick.  TFLOP/s counts the executed FLOPs of the layer table (2 x MAC of every conv + the tail's Linears); "frac" = that rate over
 the split-bf16 pipe's fp32-equivalent ceiling (2.5 PFLOP/s bf16 dense / 6 products = 416.7 TFLOP/s).
--> profiles/face_tower_times.txt (stdout only; tools/face_tower/profile_face_tower.sh runs it under rocprofv3 for the per-kernel breakdown)
-
-Lives in a sub-directory of tools/ (like membw/ and persist/): the flat tools/ inventory is pinned by tests/test_tools_smoke.py."""
+`SIZES=1,8,32` the batch sizes, `REPS=`, `YARDSTICK=0` the HIP tower only.
+-> profiles/face_tower_times.txt (stdout only; tools/face_tower/profile_face_tower.sh runs it under rocprofv3 for the per-kernel breakdown)"""
 import os
 import sys
 
@@ -16,6 +15,7 @@ import torch
 import face_tower_torch as ft
 from lip2speech_amd import synth
 from model.modules import FaceRecognizer
+from tools import abtime
 
 REPS = int(os.environ.get("REPS", 20))
 SIZES = [int(b) for b in os.environ.get("SIZES", "1,8,32").split(",")]
@@ -39,19 +39,6 @@ def macs_per_face():
     return conv[0], 1792 * 512 + 512 * 512 + 512 * 256
 
 
-def timed(fn):
-    for _ in range(3):
-        fn()
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(REPS):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / REPS
-
-
 def main():
     sd = synth.synth_face_state_dict()
     fr = FaceRecognizer()
@@ -67,12 +54,12 @@ def main():
     for B in SIZES:
         crops = synth.synth_faces(B).cuda()
         x = crops[:, 0]
-        ms = timed(lambda: nm.face_encoder_fwd(x))
+        ms = abtime.timed(lambda: nm.face_encoder_fwd(x), REPS, warm=3)
         if not YARDSTICK:
             print(f"{B:4d} {ms:9.3f}")
             continue
         with torch.no_grad():
-            ms_t = timed(lambda: tower.inference(x))
+            ms_t = abtime.timed(lambda: tower.inference(x), REPS, warm=3)
             d = (nm.face_encoder_fwd(x) - tower.inference(x)).abs().max().item()
         tf = B * flop / (ms * 1e-3) / 1e12
         print(f"{B:4d} {ms:9.3f} {tf:8.1f} {tf * 1e12 / X3_CEIL:6.3f} {ms_t:14.3f} {ms_t / ms:9.2f} {d:11.2e}")

@@ -7,53 +7,26 @@
 Workloads: 16 clips x 75 faces of 130 x 130 (GRID-like) and 32 x 29 of 96 x 96.  The uploads are outside the timed region on both sides.  The native calls are
 timed through ctypes with the job table built once (`native.resize_normalise` builds it per call in Python: listed separately).  ROUNDS interleaved rounds of
 REPS warm calls each, the variants rotating inside a round, HIP events around the REPS calls; per variant the median of the rounds and the spread.
--> profiles/frame_resize_times.txt (stdout)
-
-Lives in a sub-directory of tools/ (like ragged/): the flat tools/ inventory is pinned by tests/test_tools_smoke.py."""
+`SHAPES=BxTxS[,BxTxS...]`: other workloads of B clips x T faces of S x S; `ROUNDS=`, `REPS=`.
+-> profiles/frame_resize_times.txt (stdout)"""
 import ctypes
 import os
-import statistics
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import torch
 import torch.nn.functional as F
 
 from lip2speech_amd import native
 from lip2speech_amd.datasets import PackedFaces, PackedFrames
+from tools import abtime
 
 REPS = int(os.environ.get("REPS", 20))
 ROUNDS = int(os.environ.get("ROUNDS", 7))
 WORKLOADS = (("GRID-like", 16, 75, 130), ("LRW-like", 32, 29, 96))
+if os.environ.get("SHAPES"):
+    WORKLOADS = [(s, *(int(v) for v in s.split("x"))) for s in os.environ["SHAPES"].split(",")]
 PEAK = 8e12
-
-
-def timed(fn):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(REPS):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / REPS
-
-
-def rounds(variants):
-    t = [[] for _ in variants]
-    for r in range(ROUNDS):
-        order = list(range(len(variants)))
-        order = order[r % len(order):] + order[:r % len(order)]
-        for i in order:
-            t[i].append(timed(variants[i][1]))
-    return t
-
-
-def report(variants, t, extra=lambda name, m: ""):
-    med = [statistics.median(x) for x in t]
-    for (name, _), x, m in zip(variants, t, med):
-        print(f"{name:<64} {m * 1e3:9.1f} us  (spread {(max(x) - min(x)) * 1e3:7.1f}, min {min(x) * 1e3:9.1f}, max {max(x) * 1e3:9.1f})   x{m / med[0]:6.3f} of the first{extra(name, m)}")
-    return med
 
 
 def resize_call(buf, jobs, mode, B, T, size):
@@ -91,12 +64,11 @@ def identity(title, B, T, alt):
                 ("(a) l2s_resize_normalise at identity size", resize_call(buf, jobs, native.RESIZE_MOUTH, B, T, 96))]
     if alt is not None:
         variants.append(("(a) l2s_normalise_pad_frames, ALT_LIB (the parent commit's build)", pad_call(alt, buf, pf.offsets, pf.frames, T)))
-    outs = [fn() for _, fn in variants]
-    torch.cuda.synchronize()
+    t, outs = abtime.rounds(variants, ROUNDS, REPS)
     moved = B * T * 96 * 96 * 3 * (1 + 4)
     print(f"\n== identity, {title}: B = {B} x {T} frames of 96 x 96; {moved / 1e6:.1f} MB read + written; {-(-B * T // native.RESIZE_JOBS_PER_LAUNCH)} launches "
           f"against {-(-B // 64)}; bit-identical outputs: {all(torch.equal(outs[0], o) for o in outs[1:])}")
-    report(variants, rounds(variants), lambda name, m: f"   {moved / m / 1e9:7.2f} TB/s = {moved / m * 1e3 / PEAK * 100:5.1f} % of 8 TB/s")
+    abtime.report(variants, t, unit="us", ratio="the first", extra=lambda name, m: f"   {moved / m / 1e9:7.2f} TB/s = {moved / m * 1e3 / PEAK * 100:5.1f} % of 8 TB/s")
 
 
 def torch_route(faces, idx, B, T, mean, std):
@@ -127,21 +99,20 @@ def crops_workload(title, B, T, S):
                 ("(b) native.resize_normalise x 2 (tables built per call in Python)",
                  lambda: (native.resize_normalise(buf, packed.mouth_jobs(T), native.RESIZE_MOUTH, B, T), native.resize_normalise(buf, packed.face_jobs, native.RESIZE_FACE, B))),
                 ("    the mouth call alone", mouth), ("    the face call alone", face)]
-    outs = [fn() for _, fn in variants[:2]]
-    torch.cuda.synchronize()
+    t, outs = abtime.rounds(variants, ROUNDS, REPS)
     diff = [float((a - b).abs().max()) for a, b in zip(outs[0], outs[1])]
     read = B * T * (S - S // 2) * S * 3 + B * 2 * S * S * 3
     moved = read + (B * T * 3 * 96 * 96 + B * 2 * 3 * 160 * 160) * 4
     print(f"\n== crops, {title}: B = {B} x {T} faces of {S} x {S}; {buf.numel() / 1e6:.1f} MB uploaded, {moved / 1e6:.1f} MB read + written by the two calls; "
           f"max |d| against the torch route: video {diff[0]:.3e}, face crops {diff[1]:.3e} (one LSB is {1 / 255 / 0.225:.3e} / {1 / 128:.3e})")
-    report(variants, rounds(variants), lambda name, m: f"   (c) {moved / m / 1e9:7.2f} TB/s = {moved / m * 1e3 / PEAK * 100:5.1f} % of 8 TB/s" if "l2s_resize" in name else "")
+    abtime.report(variants, t, unit="us", ratio="the first",
+                  extra=lambda name, m: f"   (c) {moved / m / 1e9:7.2f} TB/s = {moved / m * 1e3 / PEAK * 100:5.1f} % of 8 TB/s" if "l2s_resize" in name else "")
 
 
 def main():
-    alt_path = os.environ.get("ALT_LIB")
-    alt = native._load(alt_path) if alt_path else None
+    alt_name, alt = next(iter(abtime.libs_from_env("ALT_LIB", native._load)), (None, None))
     print(f"{ROUNDS} interleaved rounds x {REPS} warm calls, HIP events; median of the rounds, spread = max - min"
-          + (f"; ALT_LIB = {os.path.basename(alt_path)}" if alt else "; ALT_LIB not given: this build only (encoder_kernels.hip, which holds normalise_pad_kernel, is the parent commit's)"))
+          + (f"; ALT_LIB = {alt_name}" if alt else "; ALT_LIB not given: this build only (encoder_kernels.hip, which holds normalise_pad_kernel, is the parent commit's)"))
     for title, B, T, S in WORKLOADS:
         identity(title, B, T, alt)
     for w in WORKLOADS:

@@ -9,18 +9,17 @@ without it only this build is timed.  Per shape one untimed round on each build,
 build every round's figure, the median of the rounds and the spread (max - min), then the sum over the shapes.  Last, outside the sum and on this
 build alone, 7 424 x 512 on the wide tile against the narrow one (116 tiles against 232, one round of blocks each): the case the tile choice
 (x3_wide in gemm_x3.hip) decides by its cost ratio.
--> profiles/gemm_x3_shape_times.txt (stdout)
-
-Lives in a sub-directory of tools/ (like masked_lengths/ and early_stop/): the flat tools/ inventory is pinned by tests/test_tools_smoke.py."""
+`CLIPS=` (256) scales every shape's row count; `ROUNDS=`, `REPS=`.
+-> profiles/gemm_x3_shape_times.txt (stdout)"""
 import os
 import statistics
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import torch
 
 from lip2speech_amd import native
+from tools import abtime
 
 REPS = int(os.environ.get("REPS", 10))
 ROUNDS = int(os.environ.get("ROUNDS", 7))
@@ -49,15 +48,19 @@ def gemm_case(name, M, N, K, flags):
     return name, [run]
 
 
-def timed(fns, L):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(REPS):
-        for fn in fns:
-            fn(L)
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) * 1e3 / REPS
+def lower(t):
+    """the verdict of this tool: this build's median under the parent's by more than the larger of the two spreads (t: parent's rounds, this build's)"""
+    spread = max(max(x) - min(x) for x in t)
+    return "LOWER by more than the larger spread" if statistics.median(t[0]) - statistics.median(t[1]) > spread else "not lower by more than the larger spread"
+
+
+def show(name, variants, t):
+    print(name)
+    med = abtime.report(variants, t, unit="us", ratio="the first" if len(variants) == 2 else None)
+    if len(variants) == 2:
+        print(f"    this / parent {med[1] / med[0]:5.3f}  {lower(t)}")
+    for (bname, _), x in zip(variants, t):
+        print(f"    {bname:<12} rounds: " + " ".join(f"{v * 1e3:8.1f}" for v in x))
 
 
 def main():
@@ -71,55 +74,27 @@ def main():
              multihop,
              gemm_case(f"BiLSTM input GEMM {rows} x 4096 x 1024 (dma)", rows, 4096, 1024, 9),
              gemm_case(f"conv_last {rows} x 768 x 464 (dma)", rows, 768, 464, 9)]
-    builds = [("this build", native.diag())]
-    parent_path = os.environ.get("PARENT_DIAG_LIB")
-    if parent_path:
-        builds.insert(0, ("parent build", native._load(parent_path)))
+    builds = [("parent build", lib) for _, lib in abtime.libs_from_env("PARENT_DIAG_LIB", native._load)][:1] + [("this build", native.diag())]
     print(f"{ROUNDS} interleaved rounds x {REPS} warm calls, HIP events; us per call: median of the rounds (spread = max - min)")
-    t = {(c, b): [] for c in range(len(cases)) for b in range(len(builds))}
-    for c, (name, fns) in enumerate(cases):
-        for _, L in builds:                     # warm-up of every shape on every build: one untimed round (a single call leaves the first timed
-            timed(fns, L)                       # round of a shape 7-17 % slow on either build, the clock still settling)
-        for r in range(ROUNDS):
-            for b in (range(len(builds)) if r % 2 == 0 else reversed(range(len(builds)))):
-                t[(c, b)].append(timed(fns, builds[b][1]))
+
+    def on_builds(fns):
+        return [(bname, lambda L=L: [fn(L) for fn in fns]) for bname, L in builds]
+
     total = [[0.0] * ROUNDS for _ in builds]
-    for c, (name, _) in enumerate(cases):
-        line = f"{name:<78}"
-        for b, (bname, _) in enumerate(builds):
-            x = t[(c, b)]
-            total[b] = [a + v for a, v in zip(total[b], x)]
-            line += f"  {bname} {statistics.median(x):8.1f} ({max(x) - min(x):5.1f})"
-        if len(builds) == 2:
-            mp, mt = statistics.median(t[(c, 0)]), statistics.median(t[(c, 1)])
-            spread = max(max(t[(c, b)]) - min(t[(c, b)]) for b in range(2))
-            line += f"  this / parent {mt / mp:5.3f}  {'LOWER by more than the larger spread' if mp - mt > spread else 'not lower by more than the larger spread'}"
-        print(line)
-        for b, (bname, _) in enumerate(builds):
-            print(f"    {bname:<12} rounds: " + " ".join(f"{v:8.1f}" for v in t[(c, b)]))
-    line = f"{'sum over the six shapes (round by round)':<78}"
-    for b, (bname, _) in enumerate(builds):
-        line += f"  {bname} {statistics.median(total[b]):8.1f} ({max(total[b]) - min(total[b]):5.1f})"
-    if len(builds) == 2:
-        mp, mt = statistics.median(total[0]), statistics.median(total[1])
-        spread = max(max(x) - min(x) for x in total)
-        line += f"  this / parent {mt / mp:5.3f}  {'LOWER by more than the larger spread' if mp - mt > spread else 'not lower by more than the larger spread'}"
-    print(line)
-    for b, (bname, _) in enumerate(builds):
-        print(f"    {bname:<12} rounds: " + " ".join(f"{v:8.1f}" for v in total[b]))
+    for name, fns in cases:
+        # warm-up of every shape on every build: one untimed round (a single call leaves the first timed round of a shape 7-17 % slow on either
+        # build, the clock still settling)
+        t, _ = abtime.rounds(on_builds(fns), ROUNDS, REPS, warm=REPS)
+        total = [[a + v for a, v in zip(tot, x)] for tot, x in zip(total, t)]
+        show(name, on_builds(fns), t)
+    show("sum over the six shapes (round by round)", on_builds([]), total)
     # the tile choice's margin case on this build: flags 1 = the wide tile wherever it fits, 1 | 4 = the narrow tile everywhere (in-kernel weight split in both)
     L = builds[-1][1]
     for K in (512, 2560):
-        forms = [gemm_case("", rows, 512, K, f)[1] for f in (1, 5)]
-        for fns in forms:
-            fns[0](L)
-        torch.cuda.synchronize()
-        x = [[], []]
-        for r in range(ROUNDS):
-            for f in ((0, 1) if r % 2 == 0 else (1, 0)):
-                x[f].append(timed(forms[f], L))
-        print(f"tile choice, this build, {rows} x 512 x {K}: wide tile {statistics.median(x[0]):7.1f} ({max(x[0]) - min(x[0]):4.1f})  narrow tile {statistics.median(x[1]):7.1f} "
-              f"({max(x[1]) - min(x[1]):4.1f})  wide / narrow {statistics.median(x[0]) / statistics.median(x[1]):5.3f}")
+        variants = [(form, lambda fn=gemm_case("", rows, 512, K, f)[1][0]: fn(L)) for form, f in (("wide tile", 1), ("narrow tile", 5))]
+        print(f"tile choice, this build, {rows} x 512 x {K}:")
+        wide, narrow = abtime.report(variants, abtime.rounds(variants, ROUNDS, REPS)[0], unit="us")
+        print(f"    wide / narrow {wide / narrow:5.3f}")
 
 
 if __name__ == "__main__":

@@ -4,19 +4,16 @@ batch - B = 16 clips with lengths uniform in [25, 75] zero-padded to the batch m
 copy / pooling, the length-masked attention blocks, and the launch-per-phase route.  A second line gives the masked call at the clips' true lengths.
 `PARENT_LIB=<path to a libl2s_hip.so built from the parent commit>`: that build's unmasked call is timed in the same process, interleaved with this
 build's (has the default path moved?).  ROUNDS interleaved rounds of REPS warm calls each, the variants rotating inside a round, HIP events around the
-REPS calls; per variant the median of the rounds and the spread (max - min).
--> profiles/masked_lengths_times.txt (stdout)
-
-Lives in a sub-directory of tools/ (like face_tower/ and early_stop/): the flat tools/ inventory is pinned by tests/test_tools_smoke.py."""
+REPS calls; per variant the median of the rounds and the spread (max - min).  `B=`, `S=`, `ROUNDS=`, `REPS=`.
+-> profiles/masked_lengths_times.txt (stdout)"""
 import os
-import statistics
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import torch
 
 from lip2speech_amd import native, synth
+from tools import abtime
 
 REPS = int(os.environ.get("REPS", 10))
 ROUNDS = int(os.environ.get("ROUNDS", 7))
@@ -25,55 +22,27 @@ S = int(os.environ.get("S", 300))
 LO, HI = 25, 75
 
 
-def model(library=None):
-    sd = synth.synth_state_dict()
-    nm = native.NativeModel(library)
-    nm.load({k: v.cuda() for k, v in sd.items()}, list(sd.keys()))
-    return nm
-
-
-def timed(fn):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(REPS):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / REPS
-
-
 def main():
     lens = [int(v) for v in synth.synth_clip_lengths(B, LO, HI, "masked-times")]
     T = max(lens)
     video = synth.synth_padded_video(B, lens, tag="masked-times").cuda()
     emb = synth.synth_speaker_embedding(B, tag="masked-times").cuda()
     gum = synth.synth_gumbel(B * native.min_T(T), tag="masked-times").cuda()
-    this = model()
+    this = abtime.synth_model()
     variants = [("this build, l2s_inference", lambda: this.inference(video, emb, gum, S=S)),
                 ("this build, l2s_inference_masked, all lengths = T", lambda: this.inference(video, emb, gum, S=S, video_lengths=[T] * B)),
                 ("this build, l2s_inference_masked, true lengths", lambda: this.inference(video, emb, gum, S=S, video_lengths=lens))]
-    parent_path = os.environ.get("PARENT_LIB")
-    if parent_path:
-        parent = model(native._load(parent_path))
+    parent = next((abtime.synth_model(lib) for _, lib in abtime.libs_from_env("PARENT_LIB", native._load)), None)
+    if parent is not None:
         variants.insert(0, ("parent build, l2s_inference", lambda: parent.inference(video, emb, gum, S=S)))
     print(f"B = {B} clips, lengths {sorted(lens)} zero-padded to T = {T}, S = {S}; {ROUNDS} interleaved rounds x {REPS} warm calls, HIP events; "
           f"median of the rounds, spread = max - min")
-    outs = [fn() for _, fn in variants]          # warm-up of every shape and route
-    torch.cuda.synchronize()
-    ref = outs[1 if parent_path else 0]
+    t, outs = abtime.rounds(variants, ROUNDS, REPS)          # the warm-up call covers every shape and route
+    ref = outs[1 if parent is not None else 0]
     for (name, _), o in zip(variants, outs):
         print(f"  {name:<52} mel_post bit-identical to this build's l2s_inference: {torch.equal(o[0], ref[0])}")
-    t = [[] for _ in variants]
-    for r in range(ROUNDS):
-        order = list(range(len(variants)))
-        order = order[r % len(order):] + order[:r % len(order)]
-        for i in order:
-            t[i].append(timed(variants[i][1]))
-    med = [statistics.median(x) for x in t]
-    base = med[1 if parent_path else 0]
-    for (name, _), x, m in zip(variants, t, med):
-        print(f"{name:<52} {m:8.3f} ms  (spread {max(x) - min(x):5.3f}, min {min(x):8.3f}, max {max(x):8.3f})   x{m / base:5.3f} of this build's l2s_inference")
-    if parent_path:
+    med = abtime.report(variants, t, ratio="this build's l2s_inference", base=1 if parent is not None else 0)
+    if parent is not None:
         lo, hi = min(t[0]), max(t[0])
         print(f"default path: this build's l2s_inference median {med[1]:.3f} ms; the parent build's rounds span [{lo:.3f}, {hi:.3f}] ms -> "
               f"{'inside' if lo <= med[1] <= hi else 'OUTSIDE'} the parent's spread")

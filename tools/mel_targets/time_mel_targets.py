@@ -6,45 +6,24 @@
       process - the waves-per-block A/B.
 Shapes: B = 32 x 18 560 samples (LRW's clips) and B = 16 x 48 000 (GRID's 3 s).  The uploads are outside the timed region on both sides (the bytes are the same).
 ROUNDS interleaved rounds of REPS warm calls each, the variants rotating inside a round, HIP events around the REPS calls; per variant the median of the
-rounds and the spread.
--> profiles/mel_targets_times.txt (stdout)
-
-Lives in a sub-directory of tools/ (like ragged/): the flat tools/ inventory is pinned by tests/test_tools_smoke.py."""
+rounds and the spread.  `SHAPES=Bxn[,Bxn...]`: other workloads of B clips x n samples; `ROUNDS=`, `REPS=`.
+-> profiles/mel_targets_times.txt (stdout)"""
 import ctypes
 import os
-import statistics
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import torch
 
 from lip2speech_amd import native
 from lip2speech_amd.datasets import MEL_PAD, MelSpectrogram, PackedAudio
+from tools import abtime
 
 REPS = int(os.environ.get("REPS", 20))
 ROUNDS = int(os.environ.get("ROUNDS", 7))
 WORKLOADS = (("LRW", 32, 18560), ("GRID, 3 s", 16, 48000))
-
-
-def timed(fn):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(REPS):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / REPS
-
-
-def rounds(variants):
-    t = [[] for _ in variants]
-    for r in range(ROUNDS):
-        order = list(range(len(variants)))
-        order = order[r % len(order):] + order[:r % len(order)]
-        for i in order:
-            t[i].append(timed(variants[i][1]))
-    return t
+if os.environ.get("SHAPES"):
+    WORKLOADS = [(s, *(int(v) for v in s.split("x"))) for s in os.environ["SHAPES"].split(",")]
 
 
 def torch_route(mt, waves):
@@ -100,26 +79,20 @@ def workload(title, B, n, alt):
                 ("(b) the same through ctypes, this build", hip_call(native.lib(), buf, packed.offsets, packed.samples, mt.fb, mt.fb_nnz))]
     if alt is not None:
         variants.append(("(c) ALT_LIB build, one call", hip_call(alt, buf, packed.offsets, packed.samples, mt.fb, mt.fb_nnz)))
-    outs = [fn() for _, fn in variants]          # warm-up of every route
-    torch.cuda.synchronize()
+    t, outs = abtime.rounds(variants, ROUNDS, REPS)          # the warm-up call covers every route
     frames = B * (n // 256 + 1)
     print(f"\n== {title}: B = {B} x {n} samples, {frames} frames")
     print(f"(b) against (a): audio and gate identical: {torch.equal(outs[0][0], outs[2][2]) and torch.equal(outs[0][2], outs[2][1])}; "
           f"max |d log-mel| = {float((outs[0][1] - outs[2][0]).abs().max()):.3e}")
     if alt is not None:
         print(f"(c) against (b): log-mels bit-identical: {torch.equal(outs[4][1], outs[3][1])}")
-    t = rounds(variants)
-    med = [statistics.median(x) for x in t]
-    for (name, _), x, m in zip(variants, t, med):
-        print(f"{name:<52} {m * 1e3:9.1f} us  (spread {(max(x) - min(x)) * 1e3:7.1f}, min {min(x) * 1e3:9.1f}, max {max(x) * 1e3:9.1f})   "
-              f"{frames / m / 1e3:8.2f} M frames/s   x{m / med[0]:6.3f} of (a)")
+    abtime.report(variants, t, unit="us", ratio="(a)", extra=lambda name, m: f"   {frames / m / 1e3:8.2f} M frames/s")
 
 
 def main():
-    alt_path = os.environ.get("ALT_LIB")
-    alt = native._load(alt_path) if alt_path else None
+    alt_name, alt = next(iter(abtime.libs_from_env("ALT_LIB", native._load)), (None, None))
     print(f"{ROUNDS} interleaved rounds x {REPS} warm calls, HIP events; median of the rounds, spread = max - min"
-          + (f"; ALT_LIB = {os.path.basename(alt_path)}" if alt else "; ALT_LIB not given: this build only"))
+          + (f"; ALT_LIB = {alt_name}" if alt else "; ALT_LIB not given: this build only"))
     for w in WORKLOADS:
         workload(*w, alt)
 

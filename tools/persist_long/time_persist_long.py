@@ -4,19 +4,16 @@ route) against a model with it at 75 (they take pdecode.hip's long forms; 29-fra
 `PARENT_LIB=<path to a libl2s_hip.so built from the parent commit>`: that build's call is timed in the same process for the T = 29 rows, interleaved
 with this build's (has the short path moved?).  Per (B, T): ROUNDS interleaved rounds of REPS warm calls each, the variants rotating inside a round,
 HIP events around the REPS calls; per variant the median of the rounds and the spread (max - min).  A row says "faster" only where the whole span of
-the option-on rounds lies below the whole span of the option-off rounds.
--> profiles/persist_long_times.txt (stdout)
-
-Lives in a sub-directory of tools/ (like masked_lengths/ and early_stop/): the flat tools/ inventory is pinned by tests/test_tools_smoke.py."""
+the option-on rounds lies below the whole span of the option-off rounds.  `BS=1,2,4`, `TS=29,50,75`, `S=`, `ROUNDS=`, `REPS=`.
+-> profiles/persist_long_times.txt (stdout)"""
 import os
-import statistics
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import torch
 
 from lip2speech_amd import native, synth
+from tools import abtime
 
 REPS = int(os.environ.get("REPS", 5))
 ROUNDS = int(os.environ.get("ROUNDS", 7))
@@ -26,30 +23,10 @@ TS = [int(v) for v in os.environ.get("TS", "29,50,75").split(",")]
 FRAMES = 75
 
 
-def model(library=None, **options):
-    sd = synth.synth_state_dict()
-    nm = native.NativeModel(library)
-    for k, v in options.items():
-        nm.set_option(k, v)
-    nm.load({k: v.cuda() for k, v in sd.items()}, list(sd.keys()))
-    return nm
-
-
-def timed(fn):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(REPS):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / REPS
-
-
 def main():
-    off = model(persist_decode=4)
-    on = model(persist_decode=4, persist_frames=FRAMES)
-    parent_path = os.environ.get("PARENT_LIB")
-    parent = model(native._load(parent_path), persist_decode=4) if parent_path else None
+    off = abtime.synth_model(persist_decode=4)
+    on = abtime.synth_model(persist_decode=4, persist_frames=FRAMES)
+    parent = next((abtime.synth_model(lib, persist_decode=4) for _, lib in abtime.libs_from_env("PARENT_LIB", native._load)), None)
     print(f"l2s_inference, S = {S}, persist_decode = 4; persistent forms available on this device: {native.persist_available()}; "
           f"{ROUNDS} interleaved rounds x {REPS} warm calls, HIP events; ms per call: median of the rounds (spread = max - min)")
     for B in BS:
@@ -60,16 +37,9 @@ def main():
             variants = [("persist_frames = 32", lambda: off.inference(video, emb, gum, S=S)), (f"persist_frames = {FRAMES}", lambda: on.inference(video, emb, gum, S=S))]
             if parent is not None and T <= 32:
                 variants.append(("parent build", lambda: parent.inference(video, emb, gum, S=S)))
-            outs = [fn() for _, fn in variants]          # warm-up of every shape and route
-            torch.cuda.synchronize()
-            t = [[] for _ in variants]
-            for r in range(ROUNDS):
-                order = list(range(len(variants)))
-                order = order[r % len(order):] + order[:r % len(order)]
-                for i in order:
-                    t[i].append(timed(variants[i][1]))
-            med = [statistics.median(x) for x in t]
-            cells = "   ".join(f"{name}: {m:7.3f} (spread {max(x) - min(x):5.3f})" for (name, _), x, m in zip(variants, t, med))
+            t, outs = abtime.rounds(variants, ROUNDS, REPS)          # the warm-up call covers every shape and route
+            print(f"B = {B} T = {T:3d}")
+            med = abtime.report(variants, t)
             if T <= 32:
                 same = all(torch.equal(o[0], outs[0][0]) for o in outs)
                 verdict = f"short forms on every variant, same bits: {same}"
@@ -77,10 +47,10 @@ def main():
                     lo, hi = min(t[2]), max(t[2])
                     verdict += f"; this build's median {'inside' if lo <= med[1] <= hi else 'OUTSIDE'} the parent's rounds [{lo:.3f}, {hi:.3f}]"
             else:
-                faster = max(t[1]) < min(t[0])
+                faster = abtime.wholly_under(t[1], t[0])
                 verdict = (f"x{med[0] / med[1]:.2f}, {(med[0] - med[1]) * 1e3 / S:5.2f} us per step saved, "
                            f"{'faster beyond the spread' if faster else 'NOT faster beyond the spread'}; same bits as the launch route: {torch.equal(outs[0][0], outs[1][0])}")
-            print(f"B = {B} T = {T:3d}   {cells}   {verdict}")
+            print(f"    {verdict}")
     torch.cuda.synchronize()
     print(f"persistent launches that gave up: {native.persist_timeouts()}")
 

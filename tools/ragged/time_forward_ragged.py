@@ -9,59 +9,24 @@ the chain decodes every row for Smax steps.
 Default path: with PARENT_LIB, l2s_forward_eval_multi at G = 8, B = 32, T = 29, S = 77 from both builds, interleaved: it must not move outside the spread.
 ROUNDS interleaved rounds of REPS warm calls each, the variants rotating inside a round, HIP events around the REPS calls; per variant the median of the
 rounds and the spread.  No ratio is fixed in advance: the tool writes what it measures and says so when (b)'s rounds do not lie wholly under (a)'s.
+`G=` batches per group (8), `CLIPS=` clips per batch and `LENS=lo-hi` the length range (one workload of that shape instead of the two above; the default
+path then runs at CLIPS clips per batch too), `ROUNDS=`, `REPS=`.
 -> profiles/forward_ragged_times.txt (stdout)"""
 import os
-import statistics
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import torch
 
 from lip2speech_amd import native, synth
+from tools import abtime
 
 REPS = int(os.environ.get("REPS", 5))
 ROUNDS = int(os.environ.get("ROUNDS", 7))
-G = 8
+G = int(os.environ.get("G", 8))
 WORKLOADS = (("config 4's shape", 16, 25, 75), ("config 5's shape", 32, 26, 50))
-
-
-def model(library=None):
-    sd = synth.synth_state_dict()
-    nm = native.NativeModel(library)
-    nm.load({k: v.cuda() for k, v in sd.items()}, list(sd.keys()))
-    return nm
-
-
-def timed(fn):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(REPS):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / REPS
-
-
-def rounds(variants):
-    t = [[] for _ in variants]
-    for r in range(ROUNDS):
-        order = list(range(len(variants)))
-        order = order[r % len(order):] + order[:r % len(order)]
-        for i in order:
-            t[i].append(timed(variants[i][1]))
-    return t
-
-
-def report(variants, t):
-    med = [statistics.median(x) for x in t]
-    for (name, _), x, m in zip(variants, t, med):
-        print(f"{name:<58} {m:8.3f} ms  (spread {max(x) - min(x):6.3f}, min {min(x):8.3f}, max {max(x):8.3f})")
-    return med
-
-
-def inside(t, med, i, j):
-    return min(t[j]) <= med[i] <= max(t[j]) or min(t[i]) <= med[j] <= max(t[i])
+if os.environ.get("CLIPS") or os.environ.get("LENS"):
+    WORKLOADS = (("CLIPS / LENS", int(os.environ.get("CLIPS", 16)), *(int(v) for v in os.environ.get("LENS", "25-75").split("-"))),)
 
 
 def workload(title, B, lo, hi, this, parent):
@@ -84,44 +49,39 @@ def workload(title, B, lo, hi, this, parent):
     def masked8(nm):
         return lambda: [nm.forward_eval(*bt, s, video_lengths=l) for bt, s, l in zip(batches, Ss, lens)]
 
-    variants = [("(a) this build, 8 x l2s_forward_eval_masked", masked8(this)),
+    variants = [(f"(a) this build, {G} x l2s_forward_eval_masked", masked8(this)),
                 ("(b) this build, 1 x l2s_forward_eval_ragged", lambda: this.forward_eval_ragged(batches, lens, Ss))]
     if parent is not None:
-        variants.append(("(a) parent build, 8 x l2s_forward_eval_masked", masked8(parent)))
-    outs = [fn() for _, fn in variants]          # warm-up of every shape and route
-    torch.cuda.synchronize()
+        variants.append((f"(a) parent build, {G} x l2s_forward_eval_masked", masked8(parent)))
+    t, outs = abtime.rounds(variants, ROUNDS, REPS)          # the warm-up call covers every shape and route
     same = all(all(torch.equal(x, y) for x, y in zip(a, b)) for a, b in zip(outs[0], outs[1]))
     worst = max(float((a[1] - b[1]).abs().max()) for a, b in zip(outs[0], outs[1]))
     print(f"(b) against (a): all five outputs bit-identical: {same} (max |d mel_post| = {worst:.3e}; the kernel choice depends on the row count at these sizes, DESIGN.md section 8)")
-    t = rounds(variants)
-    med = report(variants, t)
+    med = abtime.report(variants, t)
     print(f"(b) rounds span [{min(t[1]):.3f}, {max(t[1]):.3f}] ms, (a) rounds span [{min(t[0]):.3f}, {max(t[0]):.3f}] ms -> "
-          f"{'(b) lies wholly under (a)' if max(t[1]) < min(t[0]) else 'the spans OVERLAP: no gain outside the spread'}; (a) / (b) = {med[0] / med[1]:.2f}; "
+          f"{'(b) lies wholly under (a)' if abtime.wholly_under(t[1], t[0]) else 'the spans OVERLAP: no gain outside the spread'}; (a) / (b) = {med[0] / med[1]:.2f}; "
           f"per batch {med[0] / G:.3f} -> {med[1] / G:.3f} ms")
     if parent is not None:
-        print(f"today's route, 8 x l2s_forward_eval_masked: this build {med[0]:.3f} ms, parent build {med[2]:.3f} ms -> a median "
-              f"{'inside' if inside(t, med, 0, 2) else 'OUTSIDE'} the other's spread")
+        print(f"today's route, {G} x l2s_forward_eval_masked: this build {med[0]:.3f} ms, parent build {med[2]:.3f} ms -> a median "
+              f"{'inside' if abtime.median_inside(t[0], t[2]) else 'OUTSIDE'} the other's spread")
 
 
 def default_path(this, parent):
-    B, T, S = 32, 29, 77
+    B, T, S = int(os.environ.get("CLIPS", 32)), 29, 77
     batches = [(synth.synth_video(B, T, tag=f"fwd-multi-{g}").cuda(), synth.synth_speaker_embedding(B, tag=f"fwd-multi-{g}").cuda(),
                 synth.synth_gumbel(B * native.min_T(T), tag=f"fwd-multi-{g}").cuda()) for g in range(G)]
     variants = [("this build, l2s_forward_eval_multi", lambda: this.forward_eval_multi(batches, S)),
                 ("parent build, l2s_forward_eval_multi", lambda: parent.forward_eval_multi(batches, S))]
-    outs = [fn() for _, fn in variants]
-    torch.cuda.synchronize()
+    t, outs = abtime.rounds(variants, ROUNDS, REPS)
     same = all(all(torch.equal(x, y) for x, y in zip(a, b)) for a, b in zip(outs[0], outs[1]))
     print(f"\n== default path: l2s_forward_eval_multi, G = {G}, B = {B}, T = {T}, S = {S}; both builds bit-identical: {same}")
-    t = rounds(variants)
-    med = report(variants, t)
-    print(f"-> a median {'inside' if inside(t, med, 0, 1) else 'OUTSIDE'} the other's spread")
+    abtime.report(variants, t)
+    print(f"-> a median {'inside' if abtime.median_inside(t[0], t[1]) else 'OUTSIDE'} the other's spread")
 
 
 def main():
-    this = model()
-    parent_path = os.environ.get("PARENT_LIB")
-    parent = model(native._load(parent_path)) if parent_path else None
+    this = abtime.synth_model()
+    parent = next((abtime.synth_model(lib) for _, lib in abtime.libs_from_env("PARENT_LIB", native._load)), None)
     print(f"{ROUNDS} interleaved rounds x {REPS} warm calls, HIP events; median of the rounds, spread = max - min"
           + ("" if parent else "; PARENT_LIB not given: this build only, default path not measured"))
     for w in WORKLOADS:

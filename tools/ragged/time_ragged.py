@@ -10,41 +10,25 @@ frames), and the front-end / trunk time of (a) and (b) from the launch profile (
 Default path: with PARENT_LIB, the parent's l2s_inference (first batch) and l2s_inference_multi (variant c) next to this build's, interleaved.
 ROUNDS interleaved rounds of REPS warm calls each, the variants rotating inside a round, HIP events around the REPS calls; per variant the median of
 the rounds and the spread.  Acceptance (the criterion of "persist_frames"): the whole span of (b)'s rounds lies under the whole span of (a)'s.
--> profiles/ragged_times.txt (stdout)
-
-Lives in a sub-directory of tools/ (like masked_lengths/): the flat tools/ inventory is pinned by tests/test_tools_smoke.py."""
+`G=` batches per group (8), `CLIPS=` clips per batch and `LENS=lo-hi` the length range (one workload of that shape instead of the two above), `S=`,
+`ROUNDS=`, `REPS=`.
+-> profiles/ragged_times.txt (stdout)"""
 import os
-import statistics
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import torch
 
 from lip2speech_amd import native, synth
+from tools import abtime
 
 REPS = int(os.environ.get("REPS", 10))
 ROUNDS = int(os.environ.get("ROUNDS", 7))
 S = int(os.environ.get("S", 300))
-G = 8
+G = int(os.environ.get("G", 8))
 WORKLOADS = (("config 4's shape", 16, 25, 75), ("config 5's shape", 32, 26, 50))
-
-
-def model(library=None):
-    sd = synth.synth_state_dict()
-    nm = native.NativeModel(library)
-    nm.load({k: v.cuda() for k, v in sd.items()}, list(sd.keys()))
-    return nm
-
-
-def timed(fn):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(REPS):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / REPS
+if os.environ.get("CLIPS") or os.environ.get("LENS"):
+    WORKLOADS = (("CLIPS / LENS", int(os.environ.get("CLIPS", 16)), *(int(v) for v in os.environ.get("LENS", "25-75").split("-"))),)
 
 
 def encoder_ms(fn):
@@ -60,16 +44,6 @@ def encoder_ms(fn):
     fe = sum(ms for name, _, ms in prof if name.startswith("frontend3d_conv"))
     trunk = sum(ms for name, _, ms in prof if name.startswith("shuffle_") or name == "conv_last_gemm")
     return fe, trunk
-
-
-def rounds(variants):
-    t = [[] for _ in variants]
-    for r in range(ROUNDS):
-        order = list(range(len(variants)))
-        order = order[r % len(order):] + order[:r % len(order)]
-        for i in order:
-            t[i].append(timed(variants[i][1]))
-    return t
 
 
 def workload(title, B, lo, hi, this, parent):
@@ -96,39 +70,33 @@ def workload(title, B, lo, hi, this, parent):
     def masked8(nm):
         return lambda: [nm.inference(*bt, S=S, video_lengths=l) for bt, l in zip(batches, lens)]
 
-    variants = [("(a) this build, 8 x l2s_inference_masked", masked8(this)),
+    variants = [(f"(a) this build, {G} x l2s_inference_masked", masked8(this)),
                 ("(b) this build, 1 x l2s_inference_ragged", lambda: this.inference_ragged(batches, lens, S=S)),
                 ("(c) this build, l2s_inference_multi, re-padded (other results)", lambda: this.inference_multi(common, S=S)),
                 ("    this build, l2s_inference, first batch", lambda: this.inference(*batches[0], S=S))]
     if parent is not None:
-        variants += [("(a) parent build, 8 x l2s_inference_masked", masked8(parent)),
+        variants += [(f"(a) parent build, {G} x l2s_inference_masked", masked8(parent)),
                      ("(c) parent build, l2s_inference_multi, re-padded", lambda: parent.inference_multi(common, S=S)),
                      ("    parent build, l2s_inference, first batch", lambda: parent.inference(*batches[0], S=S))]
-    outs = [fn() for _, fn in variants]          # warm-up of every shape and route
-    torch.cuda.synchronize()
+    t, outs = abtime.rounds(variants, ROUNDS, REPS)          # the warm-up call covers every shape and route
     same = all(torch.equal(a[0], b[0]) and torch.equal(a[1], b[1]) for a, b in zip(outs[0], outs[1]))
     worst = max(float((a[0] - b[0]).abs().max()) for a, b in zip(outs[0], outs[1]))
     print(f"(b) against (a): mel_post and lengths bit-identical: {same} (max |d mel_post| = {worst:.3e}; the kernel choice depends on the row count at these sizes, DESIGN.md section 8)")
-    t = rounds(variants)
-    med = [statistics.median(x) for x in t]
-    for (name, _), x, m in zip(variants, t, med):
-        print(f"{name:<66} {m:8.3f} ms  (spread {max(x) - min(x):6.3f}, min {min(x):8.3f}, max {max(x):8.3f})   x{m / med[0]:5.3f} of (a)")
+    med = abtime.report(variants, t, ratio="(a)")
     print(f"acceptance: (b) rounds span [{min(t[1]):.3f}, {max(t[1]):.3f}] ms, (a) rounds span [{min(t[0]):.3f}, {max(t[0]):.3f}] ms -> "
-          f"{'(b) lies wholly under (a)' if max(t[1]) < min(t[0]) else 'the spans OVERLAP'}; (a) / (b) = {med[0] / med[1]:.2f}")
+          f"{'(b) lies wholly under (a)' if abtime.wholly_under(t[1], t[0]) else 'the spans OVERLAP'}; (a) / (b) = {med[0] / med[1]:.2f}")
     if parent is not None:
-        for mine, theirs, what in ((0, 4, "8 x l2s_inference_masked"), (2, 5, "l2s_inference_multi"), (3, 6, "l2s_inference")):
-            inside = min(t[theirs]) <= med[mine] <= max(t[theirs]) or min(t[mine]) <= med[theirs] <= max(t[mine])
+        for mine, theirs, what in ((0, 4, f"{G} x l2s_inference_masked"), (2, 5, "l2s_inference_multi"), (3, 6, "l2s_inference")):
             print(f"default path, {what}: this build {med[mine]:.3f} ms (rounds [{min(t[mine]):.3f}, {max(t[mine]):.3f}]), parent build {med[theirs]:.3f} ms "
-                  f"(rounds [{min(t[theirs]):.3f}, {max(t[theirs]):.3f}]) -> a median {'inside' if inside else 'OUTSIDE'} the other's spread")
+                  f"(rounds [{min(t[theirs]):.3f}, {max(t[theirs]):.3f}]) -> a median {'inside' if abtime.median_inside(t[mine], t[theirs]) else 'OUTSIDE'} the other's spread")
     fe_a, tr_a = encoder_ms(variants[0][1])
     fe_b, tr_b = encoder_ms(variants[1][1])
     print(f"launch profile (one call, event brackets around every launch): front-end (a) {fe_a:.3f} ms -> (b) {fe_b:.3f} ms; trunk (a) {tr_a:.3f} ms -> (b) {tr_b:.3f} ms")
 
 
 def main():
-    this = model()
-    parent_path = os.environ.get("PARENT_LIB")
-    parent = model(native._load(parent_path)) if parent_path else None
+    this = abtime.synth_model()
+    parent = next((abtime.synth_model(lib) for _, lib in abtime.libs_from_env("PARENT_LIB", native._load)), None)
     print(f"{ROUNDS} interleaved rounds x {REPS} warm calls, HIP events; median of the rounds, spread = max - min"
           + ("" if parent else "; PARENT_LIB not given: this build only"))
     for w in WORKLOADS:

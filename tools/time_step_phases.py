@@ -6,6 +6,7 @@ os.environ.setdefault("L2S_LIB", "diag")      # tools run on the diagnostic buil
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from lip2speech_amd import native, synth
+from tools import abtime
 
 G = int(sys.argv[1]) if len(sys.argv) > 1 else 8
 opts = [dict((kv.split("=")[0], int(kv.split("=")[1])) for kv in a.split(",")) for a in sys.argv[2:]]      # "a=1,b=2" = one setting with two options
@@ -23,12 +24,7 @@ def run(setting):
     for _ in range(2):
         out = nm.inference_multi(batches, S=S)
     torch.cuda.synchronize()
-    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    ev0.record()
-    for _ in range(3):
-        out = nm.inference_multi(batches, S=S)
-    ev1.record(); torch.cuda.synchronize()
-    ms = ev0.elapsed_time(ev1) / 3
+    ms = abtime.timed(lambda: nm.inference_multi(batches, S=S), 3)
     native.profile_enable(True); native.profile_reset()
     nm.inference_multi(batches, S=S)
     torch.cuda.synchronize()

@@ -7,6 +7,7 @@ os.environ.setdefault("L2S_LIB", "diag")      # tools run on the diagnostic buil
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests"))
 from lip2speech_amd import native, synth
+from tools import abtime
 sd = {k: v for k, v in synth.synth_state_dict().items() if k.startswith("encoder.")}
 B = int(os.environ.get("B", 256))
 v = synth.synth_video(32, 29, tag="bench").cuda().repeat(max(1, B // 32), 1, 1, 1, 1)[:B]
@@ -17,11 +18,7 @@ for x3 in ((1, 0) if os.environ.get("REVERSE") else (0, 1)):
     for _ in range(3): f = nm.encoder_fwd(v)
     feats[x3] = f.clone()
     torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(5): nm.encoder_fwd(v)
-    e1.record(); torch.cuda.synchronize()
-    print(f"trunk_x3={x3}: encoder {e0.elapsed_time(e1) / 5:.3f} ms per {B} clips")
+    print(f"trunk_x3={x3}: encoder {abtime.timed(lambda: nm.encoder_fwd(v), 5):.3f} ms per {B} clips")
     native.profile_enable(True); native.profile_reset()
     nm.encoder_fwd(v); torch.cuda.synchronize()
     tot = 0.0

@@ -8,21 +8,18 @@
 Shapes: N = 1 x 300 frames (a demo clip at the decoder's limit), N = 16 x 188 (a GRID batch), N = 32 x 188.
 ROUNDS interleaved rounds, the variants rotating inside a round, wall clock around REPS synchronised calls (the host metric is host work); per variant
 the median of the rounds and the whole span.
--> profiles/vocoder_long_times.txt (stdout)
-
-Lives in a sub-directory of tools/ (like mel_targets/): the flat tools/ inventory is pinned by tests/test_tools_smoke.py."""
+`SHAPES=NxL[,NxL...]`: other shapes; `ROUNDS=`, `REPS=`, `ITERS=`.
+-> profiles/vocoder_long_times.txt (stdout)"""
 import os
-import statistics
 import sys
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import numpy as np
 import torch
 
 from lip2speech_amd import metrics, native
 from lip2speech_amd.datasets.spectrograms import MelSpec2Audio, MelSpectrogram
+from tools import abtime
 
 ROUNDS = int(os.environ.get("ROUNDS", 5))
 REPS = int(os.environ.get("REPS", 2))
@@ -31,32 +28,6 @@ WORKLOADS = [("demo clip", 1, 300), ("GRID batch", 16, 188), ("two GRID batches"
 if os.environ.get("SHAPES"):                      # "N x L,N x L": other shapes (the smoke test runs one small one)
     WORKLOADS = [(s, int(s.split("x")[0]), int(s.split("x")[1])) for s in os.environ["SHAPES"].split(",")]
 FS = 16000
-
-
-def timed(fn, reps):
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(reps):
-        fn()
-    torch.cuda.synchronize()
-    return (time.perf_counter() - t0) / reps * 1e3
-
-
-def rounds(variants):
-    t = [[] for _ in variants]
-    for r in range(ROUNDS):
-        order = list(range(len(variants)))
-        order = order[r % len(order):] + order[:r % len(order)]
-        for i in order:
-            t[i].append(timed(variants[i][1], variants[i][2]))
-    return t
-
-
-def report(variants, t):
-    med = [statistics.median(x) for x in t]
-    for (name, _, _), x, m in zip(variants, t, med):
-        print(f"{name:<58} {m:10.2f} ms  (span {min(x):10.2f} .. {max(x):10.2f}, spread {max(x) - min(x):8.2f})   x{m / med[0]:7.4f} of the first")
-    return med
 
 
 def griffin_lim_call(L, power, ang):
@@ -91,25 +62,24 @@ def workload(title, N, L, alts):
         pred = voc_h(mel, generator=g.manual_seed(1))
         return metrics.estoi_device(clean_dev, pred, FS).cpu().numpy()
 
-    variants = [("(a) torch vocoder + host ESTOI", torch_route, 1), ("(b) hip vocoder + device ESTOI", hip_route, REPS)]
-    sa, sb = torch_route(), hip_route()                                   # warm-up of both routes
+    variants = [("(a) torch vocoder + host ESTOI", torch_route), ("(b) hip vocoder + device ESTOI", hip_route)]
+    tt, (sa, sb) = abtime.rounds(variants, ROUNDS, (1, REPS), clock="host")          # the warm-up call covers both routes
     print(f"\n== {title}: N = {N} x {L} mel frames ({n} samples, {-(-n * 10000 // FS)} at 10 kHz), {ITERS} + {ITERS} iterations")
     print(f"mean ESTOI of the vocoded clips: (a) {sa.mean():.4f}  (b) {sb.mean():.4f}")
-    tt = rounds(variants)
-    report(variants, tt)
-    print(f"whole span of (b) below the whole span of (a): {max(tt[1]) < min(tt[0])}")
+    abtime.report(variants, tt, ratio="the first")
+    print(f"whole span of (b) below the whole span of (a): {abtime.wholly_under(tt[1], tt[0])}")
     power = torch.rand(N, 513, L, device="cuda", generator=g.manual_seed(2)) ** 4 * 3.0
     ang = torch.rand(N, 513, L, 2, device="cuda", generator=g.manual_seed(3))
-    gl = [("(c) l2s_griffin_lim alone, this build", griffin_lim_call(native.lib(), power, ang), REPS)]
-    gl += [(f"(c) l2s_griffin_lim alone, {name}", griffin_lim_call(lib, power, ang), REPS) for name, lib in alts]
-    ref = gl[0][1]().clone()
-    for name, fn, _ in gl[1:]:
-        print(f"{name}: waveform bit-identical to this build's: {torch.equal(fn(), ref)}")
-    report(gl, rounds(gl))
+    gl = [("(c) l2s_griffin_lim alone, this build", griffin_lim_call(native.lib(), power, ang))]
+    gl += [(f"(c) l2s_griffin_lim alone, {name}", griffin_lim_call(lib, power, ang)) for name, lib in alts]
+    tt, waves = abtime.rounds(gl, ROUNDS, REPS, clock="host")          # waves: each build's own buffer, which every call of it rewrites
+    for (name, _), wave in zip(gl[1:], waves[1:]):
+        print(f"{name}: waveform bit-identical to this build's: {torch.equal(wave, waves[0])}")
+    abtime.report(gl, tt, ratio="the first")
 
 
 def main():
-    alts = [(a.split("=")[0], native._load(a.split("=")[1])) for a in os.environ.get("ALT_LIBS", "").split(",") if a]
+    alts = abtime.libs_from_env("ALT_LIBS", native._load)
     print(f"{ROUNDS} interleaved rounds, wall clock around synchronised calls ((a) 1 call, the others {REPS}); median of the rounds, span = min .. max"
           + (f"; ALT_LIBS = {', '.join(n for n, _ in alts)}" if alts else "; ALT_LIBS not given: this build only"))
     for w in WORKLOADS:

@@ -12,21 +12,18 @@ them for all clips); (c) beats (b) on the many-batch workload by running one cha
 Then the DEFAULT path: `l2s_griffin_lim` and `l2s_estoi` at DEFAULT_SHAPE from this build and from every library in `ALT_LIBS=name=path[,name=path...]`
 (the parent commit's build) in the same process, with a bit comparison: the solo entry points must not have moved outside the spread.
 ROUNDS interleaved rounds, the variants rotating inside a round, wall clock around REPS synchronised calls; per variant the median of the rounds and the span.
--> profiles/vocoder_ragged_times.txt (stdout)
-
-Lives in a sub-directory of tools/ (like vocoder_long/): the flat tools/ inventory is pinned by tests/test_tools_smoke.py."""
+`CLIPS=`, `BATCHES=`, `FRAMES=lo-hi`, `DEFAULT_SHAPE=NxL`, `ROUNDS=`, `REPS=`, `ITERS=`.
+-> profiles/vocoder_ragged_times.txt (stdout)"""
 import os
-import statistics
 import sys
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import numpy as np
 import torch
 
 from lip2speech_amd import metrics, native
 from lip2speech_amd.datasets.spectrograms import MelSpec2Audio, MelSpectrogram
+from tools import abtime
 
 ROUNDS = int(os.environ.get("ROUNDS", 7))
 REPS = int(os.environ.get("REPS", 1))
@@ -36,32 +33,6 @@ BATCHES = int(os.environ.get("BATCHES", 8))
 F_LO, F_HI = (int(v) for v in os.environ.get("FRAMES", "63-188").split("-"))
 DEF_N, DEF_L = (int(v) for v in os.environ.get("DEFAULT_SHAPE", "16x188").split("x"))
 FS = 16000
-
-
-def timed(fn, reps):
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(reps):
-        fn()
-    torch.cuda.synchronize()
-    return (time.perf_counter() - t0) / reps * 1e3
-
-
-def rounds(variants):
-    t = [[] for _ in variants]
-    for r in range(ROUNDS):
-        order = list(range(len(variants)))
-        order = order[r % len(order):] + order[:r % len(order)]
-        for i in order:
-            t[i].append(timed(variants[i][1], REPS))
-    return t
-
-
-def report(variants, t):
-    med = [statistics.median(x) for x in t]
-    for (name, _), x, m in zip(variants, t, med):
-        print(f"{name:<58} {m:10.2f} ms  (span {min(x):10.2f} .. {max(x):10.2f}, spread {max(x) - min(x):8.2f})   x{m / med[0]:7.4f} of the first")
-    return med
 
 
 def workload(title, n_batches):
@@ -104,15 +75,14 @@ def workload(title, n_batches):
         return metrics.estoi_device(clean_dev[:, :pred.shape[1]].contiguous(), pred, FS, lengths=n_flat).cpu().numpy()
 
     variants = [("(a) solo calls back to back", solo_route), ("(b) padded call per batch", padded_route), ("(c) one ragged call", ragged_route)]
-    sa, sb, sc = solo_route(), padded_route(), ragged_route()                # warm-up of the three routes
+    tt, (sa, sb, sc) = abtime.rounds(variants, ROUNDS, REPS, clock="host")          # the warm-up call covers the three routes
     print(f"\n== {title}: {n_batches} x {CLIPS} clips of {F_LO}-{F_HI} mel frames ({sum(flat)} frames, {n_batches * CLIPS * F_HI} padded), {ITERS} + {ITERS} iterations")
     same = all(torch.equal(keep["c"][i, :n], keep["a"][i][0]) and not keep["c"][i, n:].any() for i, n in enumerate(n_flat))
     print(f"waveforms of (c) bit-identical to (a): {same}; scores of (c) bit-identical to (a): {np.array_equal(sa, sc)}")
     print(f"mean ESTOI: (a) {sa.mean():.4f}  (b) {sb.mean():.4f}  (c) {sc.mean():.4f}   ((b) scores padded pairs: another quantity for all but the longest clips)")
-    tt = rounds(variants)
-    med = report(variants, tt)
-    print(f"(a) / (c) = {med[0] / med[2]:.2f}, whole span of (c) below the whole span of (a): {max(tt[2]) < min(tt[0])}")
-    print(f"(b) / (c) = {med[1] / med[2]:.2f}, whole span of (c) below the whole span of (b): {max(tt[2]) < min(tt[1])}")
+    med = abtime.report(variants, tt, ratio="the first")
+    print(f"(a) / (c) = {med[0] / med[2]:.2f}, whole span of (c) below the whole span of (a): {abtime.wholly_under(tt[2], tt[0])}")
+    print(f"(b) / (c) = {med[1] / med[2]:.2f}, whole span of (c) below the whole span of (b): {abtime.wholly_under(tt[2], tt[1])}")
 
 
 def default_path(alts):
@@ -153,18 +123,17 @@ def default_path(alts):
           + (f" against {', '.join(nm for nm, _ in alts)}" if alts else " (ALT_LIBS not given: nothing to compare with)"))
     for what, make in (("l2s_griffin_lim", gl_call), ("l2s_estoi", es_call)):
         variants = [(f"{what}, this build", make(native.lib()))] + [(f"{what}, {nm}", make(lib)) for nm, lib in alts]
-        ref = variants[0][1]().clone()
-        for nm, fn in variants[1:]:
-            print(f"{nm}: output bit-identical to this build's: {torch.equal(fn(), ref)}")
-        tt = rounds(variants)
-        med = report(variants, tt)
+        tt, outs = abtime.rounds(variants, ROUNDS, REPS, clock="host")          # outs: each build's own buffer, which every call of it rewrites
+        for (nm, _), out in zip(variants[1:], outs[1:]):
+            print(f"{nm}: output bit-identical to this build's: {torch.equal(out, outs[0])}")
+        med = abtime.report(variants, tt, ratio="the first")
         for (nm, _), x, m in list(zip(variants, tt, med))[1:]:
             print(f"this build's span ({min(tt[0]):.3f} .. {max(tt[0]):.3f} ms) overlaps the span of {nm} ({min(x):.3f} .. {max(x):.3f}): "
                   f"{min(tt[0]) <= max(x) and min(x) <= max(tt[0])}")
 
 
 def main():
-    alts = [(a.split("=")[0], native._load(a.split("=")[1])) for a in os.environ.get("ALT_LIBS", "").split(",") if a]
+    alts = abtime.libs_from_env("ALT_LIBS", native._load)
     print(f"{ROUNDS} interleaved rounds, wall clock around {REPS} synchronised call(s); median of the rounds, span = min .. max")
     workload("one batch", 1)
     workload(f"{BATCHES} batches", BATCHES)
