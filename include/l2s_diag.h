@@ -212,6 +212,14 @@ int l2s_op_gemm_bwd(const l2s_gemm_bwd_desc* d, const float* A, const float* B, 
  * functions, from any entry point of this library, appends its record; cmd 0 = disarm (the records stay); cmd 2 = copy the first `cap` records to out.
  * *count (may be NULL) receives the number of records held */
 int l2s_op_gemm_bwd_recorder(int cmd, l2s_gemm_bwd_record* out, int cap, int* count);
+/* The carrier of the per-clip tables (csrc/host_table.h) alone: dst[0 .. n) = host_words[0 .. n) on the stream, through kernel arguments, L2S_TABLE_CHUNK
+ * words per launch.  host_words may be freed or overwritten as soon as the call returns */
+#define L2S_TABLE_CHUNK 960
+int l2s_op_upload_table(const int32_t* host_words, int64_t n, int32_t* dst, void* stream);
+/* The table builder of csrc/host_table.h on a two-segment table: n_a int32 words, then n_b int64 values (aligned to 8 bytes).  Returns the segments' word
+ * offsets and the total; fill == 0 is the sizers' mode (no data read; dst must be NULL); with dst the built table is uploaded through the carrier */
+int l2s_op_table_layout(const int32_t* a, int64_t n_a, const int64_t* b, int64_t n_b, int fill, int32_t* dst, int64_t* off_a, int64_t* off_b, int64_t* words,
+                        void* stream);
 
 #ifdef __cplusplus
 }

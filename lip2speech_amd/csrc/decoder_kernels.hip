@@ -277,20 +277,6 @@ int launch_frame_window(const float* audio, int B, int N, int L, int n_fft, int 
 // ---- the same front-end over clips of unequal length packed into one buffer (l2s_speaker_encoder_packed), rows in the time-major compact layout:
 // frames[(step_row0[l] + r)*400 + j] = reflect_r(l*160 + j - 200) * hann[j] for the clip of rank r, reflected at ITS OWN 0 and n_r - 1 and read
 // from audio + off_r - nothing outside [off_r, off_r + n_r) is touched.
-// The table, carried to the device in kernel arguments like the length table of the masked entry points (no host buffer outlives the call)
-__global__ __launch_bounds__(64) void spk_table_kernel(const SpkChunk c, int32_t* __restrict__ table) {
-    for (int i = threadIdx.x; i < c.n; i += 64) table[i] = c.v[i];
-}
-int launch_spk_table(const int32_t* words_host, int64_t n_words, int32_t* table, hipStream_t s) {
-    for (int64_t base = 0; base < n_words; base += SPK_CHUNK) {
-        SpkChunk c{};
-        c.n = (int)std::min<int64_t>(SPK_CHUNK, n_words - base);
-        for (int i = 0; i < c.n; ++i) c.v[i] = words_host[base + i];
-        hipLaunchKernelGGL(spk_table_kernel, dim3(1), dim3(64), 0, s, c, table + base);
-    }
-    L2S_CHECK_HIP(hipGetLastError());
-    return 0;
-}
 
 // One block per (rank, frame) of the B x L_max grid, lanes along j: a block's reads are one contiguous run of the clip (but for the reflected ends) and
 // its writes one contiguous row.  Which table: a block is handed (r, l) by its index, so ranks[r] (16 bytes) and step_row0[l] are two INDEPENDENT

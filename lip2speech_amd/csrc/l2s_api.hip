@@ -5,7 +5,7 @@
 #ifdef L2S_DIAG
 #include "../../include/l2s_diag.h"
 #endif
-#include "l2s_common.h"
+#include "host_table.h"
 #include "l2s_model.h"
 #include "pdecode.h"
 #include "decode_step.h"
@@ -341,7 +341,7 @@ static void masked_bilstm_plan(const int32_t* video_lengths, int B, int T, std::
     }
     for (std::vector<int>* v : {&capture, &reset}) { std::sort(v->begin(), v->end()); v->erase(std::unique(v->begin(), v->end()), v->end()); }
 }
-static int64_t len_table_bytes(int B) { return align_up((int64_t)2 * B * (int64_t)sizeof(int), 256); }
+static int64_t len_table_bytes(int B) { return align_up(len_table_words(B) * 4, 256); }
 
 // The envelope of the persistent latency forms (pdecode.hip), the part that the prologue and the decode loop share: the options allow them for this
 // call, it is no grouped call, and its clips fit the decode loop's forms.  Each stage adds its own terms and then asks pdecode_gate(T), once.
@@ -778,7 +778,10 @@ static int spk_packed_plan(const int64_t* n_samples, int B, SpkPlan& pl) {
     for (int t = 0; t < pl.L_max; ++t) pl.step_row0[t + 1] = pl.step_row0[t] + pl.step_rows[t];
     return 0;
 }
-static int64_t spk_table_words(int B, int L_max) { return (int64_t)B * (int64_t)(sizeof(SpkRank) / 4) + L_max + 1; }
+// the device table: B x SpkRank in rank order (written by the caller through the returned host pointer), then step_row0
+struct SpkTable { int64_t ranks, row0; };
+static SpkTable spk_table(HostTable& t, int B, int L_max, const int32_t* step_row0) { return SpkTable{t.rec<SpkRank>(nullptr, B), t.i32(step_row0, L_max + 1)}; }
+static int64_t spk_table_words(int B, int L_max) { HostTable t(false); spk_table(t, B, L_max, nullptr); return t.words(); }
 static int64_t spk_ws_bytes_packed(const SpkPlan& pl, int B) {
     const int64_t f = pl.R * (400 + 402 + 204 + 40 + 1024 + 256 * 2) + (int64_t)pad16(B) * 256 * 3 + (int64_t)B * 256 * 2 + 64 * 16;
     return f * (int64_t)sizeof(float) + align_up(spk_table_words(B, pl.L_max) * 4, 256) + (1 << 12);
@@ -796,17 +799,15 @@ static int speaker_packed_run(l2s_model* m, const float* audio, const int64_t* o
     float* pre = bp.f(R * 1024); float* hseq[2] = {bp.f(R * 256), bp.f(R * 256)};
     float* hf[2] = {bp.f((int64_t)Bp * 256), bp.f((int64_t)Bp * 256)}; float* cf = bp.f((int64_t)Bp * 256);
     float* hlast = bp.f((int64_t)B * 256); float* lin = bp.f((int64_t)B * 256);
-    const int64_t words = spk_table_words(B, L);
-    int32_t* table = reinterpret_cast<int32_t*>(bp.f(words));
+    int32_t* table = reinterpret_cast<int32_t*>(bp.f(spk_table_words(B, L)));
     L2S_REQUIRE(!bp.overflow && ws_bytes >= spk_ws_bytes_packed(pl, B), "speaker-encoder workspace too small (l2s_speaker_workspace_bytes_packed)");
-    // the device table: B x SpkRank in rank order, then step_row0
-    std::vector<int32_t> host((size_t)words);
-    SpkRank* hr = reinterpret_cast<SpkRank*>(host.data());
+    HostTable t;
+    const SpkTable st = spk_table(t, B, L, pl.step_row0.data());
+    SpkRank* hr = t.host<SpkRank>(st.ranks);
     for (int r = 0; r < B; ++r) { const int b = pl.order[r]; hr[r] = SpkRank{offsets[b], (int32_t)n_samples[b], b}; }
-    std::copy(pl.step_row0.begin(), pl.step_row0.end(), host.begin() + (size_t)B * (sizeof(SpkRank) / 4));
-    if (launch_spk_table(host.data(), words, table, s)) return 1;
-    const SpkRank* ranks = reinterpret_cast<const SpkRank*>(table);
-    const int* row0 = table + (int64_t)B * (sizeof(SpkRank) / 4);
+    if (t.upload(table, s)) return 1;
+    const SpkRank* ranks = table_seg<SpkRank>(table, st.ranks);
+    const int* row0 = table + st.row0;
     if (launch_frame_window_packed(audio, ranks, row0, B, L, 400, 160, w.spk_window, frames, s)) return 1;
     if (launch_gemm1(gemm_plain(frames, 400, w.spk_dft, spec, 402, (int)R, 402, 400), s, "spk_dft_gemm")) return 1;
     L2S_SPK_TAP(0, spec, R * 402);
@@ -1326,7 +1327,7 @@ int64_t l2s_workspace_bytes_ragged(int G, const int32_t* batch_B, const int32_t*
     for (int g = 0; g < G; ++g) { frames += (int64_t)batch_B[g] * batch_T[g]; pairs += (int64_t)batch_B[g] * ((batch_T[g] + 1) / 2); }
     int L[4];
     return path_ws_bytes((int)frames, rg.N, rg.Tmax, H, S) + len_table_bytes(rg.N) + 256 + align_up((int64_t)rg.N * L2S_D_EMB * 4, 256) +
-           align_up((int64_t)rg.N * content_lens(rg.Tmax, L) * VOC * 4, 256) + align_up((int64_t)rg.N * (int64_t)sizeof(RaggedClip), 256) + align_up(pairs * 4, 256);
+           align_up((int64_t)rg.N * content_lens(rg.Tmax, L) * VOC * 4, 256) + align_up(ragged_table_words(rg.N) * 4, 256) + align_up(pairs * 4, 256);
 }
 
 // What the two ragged entry points refuse beyond the plan, before the first launch (`fn` names the entry point in the message), and the frame sources
@@ -1356,7 +1357,7 @@ static int ragged_gather(int G, const float* const* emb, const float* const* gum
     const int mT = content_lens(rg.Tmax, L), N = rg.N;
     emb_all = bp.f((int64_t)N * L2S_D_EMB);
     gum_all = bp.f((int64_t)N * mT * VOC);
-    RaggedClip* clips_dev = reinterpret_cast<RaggedClip*>(bp.f((int64_t)N * (int64_t)(sizeof(RaggedClip) / sizeof(float))));
+    RaggedClip* clips_dev = reinterpret_cast<RaggedClip*>(bp.f(ragged_table_words(N)));
     int* pair_clip = reinterpret_cast<int*>(bp.f(rg.NP));
     L2S_REQUIRE(!bp.overflow, "workspace too small (l2s_workspace_bytes_ragged)");
     // the small per-batch operands are gathered, the frames are read in place.  Clip c owns mT Gumbel rows of the group's buffer and uses the first
@@ -1444,7 +1445,7 @@ static int64_t eval_ragged_staging_bytes(int N, int Tmax, int Smax) {
     int L[4];
     const int64_t rows = (int64_t)N * Smax;
     return 2 * align_up(rows * NM * 4, 256) + align_up(rows * 4, 256) + align_up(rows * Tmax * 4, 256) +
-           align_up((int64_t)N * content_lens(Tmax, L) * VOC * 4, 256) + align_up((int64_t)N * (int64_t)sizeof(EvalClip), 256);
+           align_up((int64_t)N * content_lens(Tmax, L) * VOC * 4, 256) + align_up(eval_table_words(N) * 4, 256);
 }
 
 int64_t l2s_workspace_bytes_eval_ragged(int G, const int32_t* batch_B, const int32_t* batch_T, const int32_t* batch_S, int H, int W) {
@@ -1477,7 +1478,7 @@ int l2s_forward_eval_ragged(l2s_model* m, int G, const float* const* video, cons
     float* stop_st = bp.f((int64_t)N * Smax);
     float* attn_st = attn_logits ? bp.f((int64_t)N * Smax * Tmax) : nullptr;
     float* dis_st = content_dis ? bp.f((int64_t)N * mTmax * VOC) : nullptr;
-    EvalClip* ev_dev = reinterpret_cast<EvalClip*>(bp.f((int64_t)N * (int64_t)(sizeof(EvalClip) / sizeof(float))));
+    EvalClip* ev_dev = reinterpret_cast<EvalClip*>(bp.f(eval_table_words(N)));
     L2S_REQUIRE(!bp.overflow, "workspace too small (l2s_workspace_bytes_eval_ragged)");
     float *emb_all, *gum_all;
     if (ragged_gather(G, emb, gumbel, batch_B, batch_T, clips, rg, bp, emb_all, gum_all, s)) return 1;
@@ -1591,6 +1592,17 @@ int l2s_op_gemm_bwd(const l2s_gemm_bwd_desc* d, const float* A, const float* B, 
     return rc;
 }
 int l2s_op_gemm_bwd_recorder(int cmd, l2s_gemm_bwd_record* out, int cap, int* count) { return gemm_bwd_recorder(cmd, out, cap, count); }
+int l2s_op_upload_table(const int32_t* host_words, int64_t n, int32_t* dst, void* stream) {
+    L2S_REQUIRE(host_words && dst && n >= 0, "bad arguments");
+    return table_upload(dst, host_words, n, (hipStream_t)stream);
+}
+int l2s_op_table_layout(const int32_t* a, int64_t n_a, const int64_t* b, int64_t n_b, int fill, int32_t* dst, int64_t* off_a, int64_t* off_b, int64_t* words,
+                        void* stream) {
+    L2S_REQUIRE(n_a >= 0 && n_b >= 0 && off_a && off_b && words && (fill ? a && b : !dst), "bad arguments");
+    HostTable t(fill != 0);
+    *off_a = t.i32(a, n_a); *off_b = t.i64(b, n_b); *words = t.words();
+    return dst ? t.upload(dst, (hipStream_t)stream) : 0;
+}
 int l2s_op_frontend(l2s_model* m, const float* video, int B, int T, int H, int W, float* out, void* stream) {
     L2S_ENC_READY(m);
     FrontendW fe = m->w.fe;

@@ -296,12 +296,11 @@ inline int launch_frontend(const FrontendW& w, const float* video, int B, int T,
 }
 // ---- ragged groups (l2s_inference_ragged): the clips of up to MAX_GROUP padded batches, each with its own B_g and T_g, as rows of ONE launch chain; the
 // encoder works on the real frames only.  Clip c (batch order) owns the compact frames frame0 .. frame0 + len - 1 and the front-end pair blocks
-// pair0 .. pair0 + ceil(len / 2) - 1.  The device table is written from kernel arguments (launch_ragged_table), like the length table of the masked calls.
+// pair0 .. pair0 + ceil(len / 2) - 1.  The device table is N x RaggedClip (host_table.h).
 struct RaggedClip { int g, row, T, len, frame0, pair0; };      // source tensor, row in it, ITS frame pitch T_g, frames of the clip, first compact frame, first pair block
-constexpr int RAGGED_CHUNK = 32;                               // clips per table-writing launch
-struct RaggedChunk { RaggedClip c[RAGGED_CHUNK]; int n; };
 struct RaggedTab { const RaggedClip* clips; const int* pair_clip; int N, Tmax, NF, NP; };      // device table and pair map; clips, row pitch of the decoder, sum len, sum ceil(len / 2)
-int launch_ragged_table(const RaggedClip* clips_host, int N, RaggedClip* clips_dev, int* pair_clip_dev, hipStream_t s);      // masked_kernels.hip
+int64_t ragged_table_words(int N);                                                                                           // masked_kernels.hip
+int launch_ragged_table(const RaggedClip* clips_host, int N, RaggedClip* clips_dev, int* pair_clip_dev, hipStream_t s);      // the table, then the pair map
 // the ragged form of the default front-end (frontend3d_x3q_kernel): blockIdx.y = pair block; clip c's block j is block (0, 2j) of the clip alone at T = len
 // (same slabs, same order: same bits), read in place at pitch T_g, written to compact frames frame0 + 2j (+1).  Frames t >= len are never read.
 int launch_frontend_ragged(const FrontendW& w, const FrameSrc& video, const RaggedTab& rg, int H, int W, float* out, hipStream_t s);
@@ -309,10 +308,9 @@ int launch_frontend_ragged(const FrontendW& w, const FrameSrc& video, const Ragg
 // N rows for Smax steps at pitch Smax / Tmax; clip c's table entry says which of those rows are its own and where its batch's packed output blocks start.
 // Offsets are in floats and fit an int: the largest block set of a call is 256 clips x 300 steps x 300 frames = 23 040 000 floats.
 struct EvalClip { int S, T, row, mT, mel_off, stop_off, attn_off, dis_off; };      // S_g, T_g, row in its batch, min_T(T_g), start of ITS BATCH's mel / stop / attention / content_dis block
-constexpr int EVAL_CHUNK = 32;                                                     // clips per table-writing launch
-struct EvalChunk { EvalClip c[EVAL_CHUNK]; int n; };
 struct EvalTab { const EvalClip* clips; int N, Smax, Tmax, mTmax; };               // device table; clips, the staging pitches (steps, frames, content slots)
 enum EvalField { EV_STOP = 0, EV_ATTN = 1, EV_DIS = 2, EV_MEL_POST = 3 };
+int64_t eval_table_words(int N);
 int launch_eval_table(const EvalClip* clips_host, int N, EvalClip* clips_dev, hipStream_t s);
 int launch_zero_rows_past_s(float* x, int cols, const EvalTab& ev, hipStream_t s);      // x (N * Smax, cols) dense: rows j >= S_c of every clip become zeros
 int launch_eval_scatter(int field, const float* src, const EvalTab& ev, float* dst, hipStream_t s);      // a staged output (pitch Smax / Tmax / mTmax) -> the packed blocks
@@ -501,8 +499,7 @@ int launch_output_lengths(const float* stop, int B, int S, int64_t* lengths, hip
 // option "early_stop": mel_post[b][:][j] = 0 and attn[b][j][:] = 0 (attn may be null) for j >= lengths[b]
 int launch_mask_by_lengths(const int64_t* lengths, int B, int S, int T, float* mel_post, float* attn, hipStream_t s);
 // ---- per-clip video lengths (masked_kernels.hip; the *_masked entry points).  The device length table is 2*B int32: len_b, then m_b = l2s_min_T(len_b)
-constexpr int LEN_CHUNK = 64;                                  // lengths per table-writing launch (they travel in the kernel arguments)
-struct LenChunk { int len[LEN_CHUNK]; int n; };
+int64_t len_table_words(int B);
 int launch_len_table(const int32_t* lens_host, int B, int* table, hipStream_t s);
 // forward BiLSTM rows with len_b - 1 == t: h (frag16) -> h_dst_frag (same row), c (frag16) -> c_dst[b*ld_c + unit]
 int launch_bilstm_capture(const float* h_frag, const float* c_frag, const int* lens, int B, int t, float* h_dst_frag, float* c_dst, int ld_c, hipStream_t s);
@@ -518,11 +515,8 @@ int launch_step_attn_masked(const AttnP& at, const SkinnyP& pre2, int pre2_tiles
 int launch_frame_window(const float* audio, int B, int N, int L, int n_fft, int hop, const float* window, float* frames, hipStream_t s);
 int launch_power(const float* spec, int lds, int64_t rows, int nf, float* power, int ldp, hipStream_t s);
 // ---- the voice tower over clips of unequal length (l2s_speaker_encoder_packed): the time-major compact layout - frame l of the clip of rank r (clips
-// by frame count descending) is row step_row0[l] + r.  Device table, int32 words: B x SpkRank, then step_row0[0 .. L_max]
+// by frame count descending) is row step_row0[l] + r.  Device table (host_table.h): B x SpkRank, then step_row0[0 .. L_max]
 struct SpkRank { int64_t off; int32_t n; int32_t b; };         // the clip of one rank: float offset into the packed audio, samples, index in call order
-constexpr int SPK_CHUNK = 512;                                 // table words per table-writing launch (they travel in the kernel arguments)
-struct SpkChunk { int32_t v[SPK_CHUNK]; int n; };
-int launch_spk_table(const int32_t* words_host, int64_t n_words, int32_t* table, hipStream_t s);
 int launch_frame_window_packed(const float* audio_packed, const SpkRank* ranks, const int* step_row0, int B, int L_max, int n_fft, int hop, const float* window,
                                float* frames, hipStream_t s);
 // h_last[b] = hseq[step_row0[L_b - 1] + rank(b)], 256 wide, in call order

@@ -2,49 +2,37 @@
 // clip b computes alone at T = len_b.  The LSTM cell kernels, the GEMMs and the convolutions are the unmasked ones; these kernels move, reset or
 // zero the rows whose clip starts or ends inside the padded length.  (The length-masked attention blocks are in skinny.hip.)
 //   length table (device, int32): lens[0..B) = len_b, lens[B..2B) = m_b = l2s_min_T(len_b)
-#include "l2s_common.h"
+#include "host_table.h"
 
 namespace l2s {
 
-// ---- the length table, carried to the device in kernel arguments (no host buffer has to outlive the call; works under stream capture)
-__global__ __launch_bounds__(64) void len_table_kernel(const LenChunk c, int* __restrict__ table, int B, int base) {
-    const int i = threadIdx.x;
-    if (i < c.n) {
-        table[base + i] = c.len[i];
-        table[B + base + i] = c.len[i] / 7;      // min over the strided Content.agg branches (kernels 1, 3, 5, 7): the stride-7 one
-    }
+// ---- the length table (host_table.h): len_b, then m_b = the min over the strided Content.agg branches (kernels 1, 3, 5, 7): the stride-7 one
+static void len_table(HostTable& t, const int32_t* lens_host, int B) {
+    t.i32(lens_host, B);
+    int32_t* m = t.host<int32_t>(t.i32(nullptr, B));
+    for (int b = 0; m && b < B; ++b) m[b] = lens_host[b] / 7;
 }
+int64_t len_table_words(int B) { HostTable t(false); len_table(t, nullptr, B); return t.words(); }
 
 int launch_len_table(const int32_t* lens_host, int B, int* table, hipStream_t s) {
-    for (int base = 0; base < B; base += LEN_CHUNK) {
-        LenChunk c{};
-        c.n = std::min(LEN_CHUNK, B - base);
-        for (int i = 0; i < c.n; ++i) c.len[i] = lens_host[base + i];
-        hipLaunchKernelGGL(len_table_kernel, dim3(1), dim3(64), 0, s, c, table, B, base);
-    }
-    L2S_CHECK_HIP(hipGetLastError());
-    return 0;
+    HostTable t;
+    len_table(t, lens_host, B);
+    return t.upload(table, s);
 }
 
-// ---- the clip table of a ragged group (l2s_inference_ragged), carried the same way, and the pair map of its front-end: pair_clip[pair0[c] + j] = c
-__global__ __launch_bounds__(64) void ragged_table_kernel(const RaggedChunk c, RaggedClip* __restrict__ clips, int base) {
-    const int i = threadIdx.x;
-    if (i < c.n) clips[base + i] = c.c[i];
-}
-
+// ---- the clip table of a ragged group (l2s_inference_ragged), and the pair map of its front-end: pair_clip[pair0[c] + j] = c
 __global__ __launch_bounds__(64) void ragged_pair_map_kernel(const RaggedClip* __restrict__ clips, int* __restrict__ pair_clip) {
     const int c = blockIdx.x;
     const RaggedClip k = clips[c];
     for (int j = threadIdx.x; j < (k.len + 1) / 2; j += 64) pair_clip[k.pair0 + j] = c;
 }
 
+int64_t ragged_table_words(int N) { HostTable t(false); t.rec<RaggedClip>(nullptr, N); return t.words(); }
+
 int launch_ragged_table(const RaggedClip* clips_host, int N, RaggedClip* clips_dev, int* pair_clip_dev, hipStream_t s) {
-    for (int base = 0; base < N; base += RAGGED_CHUNK) {
-        RaggedChunk c{};
-        c.n = std::min(RAGGED_CHUNK, N - base);
-        for (int i = 0; i < c.n; ++i) c.c[i] = clips_host[base + i];
-        hipLaunchKernelGGL(ragged_table_kernel, dim3(1), dim3(64), 0, s, c, clips_dev, base);
-    }
+    HostTable t;
+    t.rec(clips_host, N);
+    if (t.upload(reinterpret_cast<int32_t*>(clips_dev), s)) return 1;
     hipLaunchKernelGGL(ragged_pair_map_kernel, dim3(N), dim3(64), 0, s, clips_dev, pair_clip_dev);
     L2S_CHECK_HIP(hipGetLastError());
     return 0;

@@ -6,27 +6,19 @@
 //   - the staged outputs are moved into the packed per-batch blocks, each with the layout l2s_forward_eval_masked gives that batch alone.
 // Per-clip table (EvalClip, l2s_common.h): S_c, T_g, the row in its batch, min_T(T_g) and the float offsets of its batch's four blocks.
 #include "../../include/l2s.h"      // L2S_N_MELS, L2S_VOCAB
-#include "l2s_common.h"
+#include "host_table.h"
 
 #include <algorithm>
 
 namespace l2s {
 
-// ---- the table, carried to the device in kernel arguments (no host buffer has to outlive the call), like launch_ragged_table
-__global__ __launch_bounds__(64) void eval_table_kernel(const EvalChunk c, EvalClip* __restrict__ clips, int base) {
-    const int i = threadIdx.x;
-    if (i < c.n) clips[base + i] = c.c[i];
-}
+// ---- the table (host_table.h)
+int64_t eval_table_words(int N) { HostTable t(false); t.rec<EvalClip>(nullptr, N); return t.words(); }
 
 int launch_eval_table(const EvalClip* clips_host, int N, EvalClip* clips_dev, hipStream_t s) {
-    for (int base = 0; base < N; base += EVAL_CHUNK) {
-        EvalChunk c{};
-        c.n = std::min(EVAL_CHUNK, N - base);
-        for (int i = 0; i < c.n; ++i) c.c[i] = clips_host[base + i];
-        hipLaunchKernelGGL(eval_table_kernel, dim3(1), dim3(64), 0, s, c, clips_dev, base);
-    }
-    L2S_CHECK_HIP(hipGetLastError());
-    return 0;
+    HostTable t;
+    t.rec(clips_host, N);
+    return t.upload(reinterpret_cast<int32_t*>(clips_dev), s);
 }
 
 // ---- rows j >= S_c of x (N * Smax rows of cols floats, dense, 16-byte aligned) become zeros.  Block (tile of ZERO_ROWS rows, clip); a block whose rows

@@ -5,7 +5,7 @@
 // lip2speech_amd/datasets/spectrograms.py and lip2speech_amd/metrics.py - PARITY UNPINNED against the third-party packages; the kernels
 // are tested against those restatements with the random initial iterates passed in explicitly.
 #include "fft_dev.h"
-#include "l2s_common.h"
+#include "host_table.h"
 #include "../../include/l2s.h"
 
 #include <math.h>
@@ -884,25 +884,9 @@ __global__ __launch_bounds__(1024) void estoi_long_kernel(const EstoiLongP p) {
 
 // =====================================================================================================================================
 // The ragged forms (l2s_*_ragged): clips of unequal length in one launch chain.  The per-clip tables (lengths, prefix sums, the clips each kernel form takes)
-// are built on the host and reach the WORKSPACE through this kernel's arguments, RAG_CHUNK integers per launch, in stream order: no allocation, no copy from
-// host memory, no synchronisation, and every block of every later launch can search the whole table (the tile form's (clip, tile) lookup needs all of it).
+// are built on the host and reach the WORKSPACE through the carrier of host_table.h: every block of every later launch can search the whole table (the tile
+// form's (clip, tile) lookup needs all of it).
 // =====================================================================================================================================
-constexpr int RAG_CHUNK = 960;
-struct RagChunk { int v[RAG_CHUNK]; };
-
-__global__ __launch_bounds__(256) void ragged_table_kernel(int* dst, const RagChunk c, int n) {
-    for (int i = threadIdx.x; i < n; i += 256) dst[i] = c.v[i];
-}
-
-static void upload_table(int* dst, const std::vector<int>& t, hipStream_t s) {
-    for (size_t i0 = 0; i0 < t.size(); i0 += RAG_CHUNK) {
-        RagChunk c;
-        const int n = (int)std::min<size_t>(RAG_CHUNK, t.size() - i0);
-        memcpy(c.v, t.data() + i0, (size_t)n * sizeof(int));
-        hipLaunchKernelGGL(ragged_table_kernel, dim3(1), dim3(256), 0, s, dst + i0, c, n);
-    }
-}
-
 static int clip_error(const char* fn, int b, const std::string& what) {
     set_error(std::string("l2s: ") + fn + ": clip " + std::to_string(b) + ": " + what);
     return 1;
@@ -937,6 +921,14 @@ int64_t l2s_inverse_mel_workspace_bytes(int N, int L, int n_mels, int n_freqs, i
     return 256 + im_align((3 * (int64_t)(n_mels + n_freqs) + 2) * 4) + 2 * im_align(IM_NNZ * 4) + im_align(rows * (iters > 0 ? iters : 1) * 4) + im_align((int64_t)calls * 4);
 }
 
+// the buffers both forms of the inverse mel carve first: the band tables of launch_mel_bands and the per-row losses; `end` is what follows them
+struct InvMelWs { int* tab; float *fwd, *bwd, *loss_rows; char* end; };
+static InvMelWs inverse_mel_carve(void* ws, int n_mels, int n_freqs, int64_t rows, int iters) {
+    char* w = (char*)(((uintptr_t)ws + 255) / 256 * 256);
+    const int64_t fwd = im_align((3 * (int64_t)(n_mels + n_freqs) + 2) * 4), bwd = fwd + im_align(IM_NNZ * 4), loss = bwd + im_align(IM_NNZ * 4);
+    return InvMelWs{(int*)w, (float*)(w + fwd), (float*)(w + bwd), (float*)(w + loss), w + loss + im_align(rows * (iters > 0 ? iters : 1) * 4)};
+}
+
 int l2s_inverse_mel(const float* mel, int log_input, const float* fb, int fb_nnz, const float* init, int N, int L, int n_mels, int n_freqs, int rows_per_call,
                     int iters, float* spec, float* loss_per_iter, int* iters_run, void* ws, int64_t ws_bytes, void* stream) {
     L2S_REQUIRE(mel && fb && init && spec && ws, "inverse_mel: null argument");
@@ -949,19 +941,15 @@ int l2s_inverse_mel(const float* mel, int log_input, const float* fb, int fb_nnz
     hipStream_t s = (hipStream_t)stream;
     const int calls = N / rows_per_call;
     const int64_t rows = (int64_t)N * L;
-    char* w = (char*)(((uintptr_t)ws + 255) / 256 * 256);
-    int* tab = (int*)w; w += im_align((3 * (int64_t)(n_mels + n_freqs) + 2) * 4);
-    float* fwd = (float*)w; w += im_align(IM_NNZ * 4);
-    float* bwd = (float*)w; w += im_align(IM_NNZ * 4);
-    float* loss_rows = (float*)w; w += im_align(rows * (iters > 0 ? iters : 1) * 4);
-    int* iters_call = iters_run ? iters_run : (int*)w;
+    const InvMelWs c = inverse_mel_carve(ws, n_mels, n_freqs, rows, iters);
+    int* iters_call = iters_run ? iters_run : (int*)c.end;
     ProfScope ps("vocoder_inverse_mel", s);
-    if (launch_mel_bands(fb, n_freqs, n_mels, tab, fwd, bwd, s)) return 1;
-    InvMelP p{mel, init, tab, fwd, bwd, spec, iters > 0 ? loss_rows : nullptr, nullptr, N, L, n_mels, n_freqs, rows_per_call, iters, log_input, 0, nullptr, nullptr, nullptr};
+    if (launch_mel_bands(fb, n_freqs, n_mels, c.tab, c.fwd, c.bwd, s)) return 1;
+    InvMelP p{mel, init, c.tab, c.fwd, c.bwd, spec, iters > 0 ? c.loss_rows : nullptr, nullptr, N, L, n_mels, n_freqs, rows_per_call, iters, log_input, 0, nullptr, nullptr, nullptr};
     const unsigned blocks = (unsigned)((rows + IM_ROWS - 1) / IM_ROWS);
     hipLaunchKernelGGL(inverse_mel_kernel<false>, dim3(blocks), dim3(IM_ROWS * 64), 0, s, p);
     if (iters > 0) {
-        hipLaunchKernelGGL(inverse_mel_stop_kernel, dim3(calls), dim3(256), 0, s, loss_rows, (int)rows, rows_per_call * L, iters, iters_call, loss_per_iter, (const int*)nullptr);
+        hipLaunchKernelGGL(inverse_mel_stop_kernel, dim3(calls), dim3(256), 0, s, c.loss_rows, (int)rows, rows_per_call * L, iters, iters_call, loss_per_iter, (const int*)nullptr);
         p.loss_rows = nullptr; p.iters_call = iters_call; p.second = 1;
         hipLaunchKernelGGL(inverse_mel_kernel<false>, dim3(blocks), dim3(IM_ROWS * 64), 0, s, p);      // only the calls a stopping rule ended early re-run
     }
@@ -1007,6 +995,13 @@ int64_t l2s_estoi_workspace_bytes_long(int N, int n_resampled) {
     return 512 + 256 + (int64_t)N * 4 * ESL_MAXLEN * 4 + (int64_t)N * 2 * ESL_MAXFRAMES * ES_NBIN * 4;
 }
 
+static int band_edges_check(const char* fn, const int* band_lo_hi_host) {
+    for (int b = 0; b < ES_BANDS; ++b)
+        L2S_REQUIRE(band_lo_hi_host[b] >= 0 && band_lo_hi_host[b] <= band_lo_hi_host[ES_BANDS + b] && band_lo_hi_host[ES_BANDS + b] <= ES_NBIN &&
+                    (b == 0 || band_lo_hi_host[b] >= band_lo_hi_host[b - 1]), std::string(fn) + ": band edges");
+    return 0;
+}
+
 int l2s_estoi(const float* clean, const float* pred, int N, int n_samples, const float* fir, int n_fir, int up, int down, int n_pre_remove, int n_resampled,
               const int* band_lo_hi_host, float* score, void* ws, int64_t ws_bytes, void* stream) {
     L2S_REQUIRE(clean && pred && score && ws && band_lo_hi_host, "estoi: null argument");
@@ -1014,14 +1009,12 @@ int l2s_estoi(const float* clean, const float* pred, int N, int n_samples, const
     L2S_REQUIRE(n_resampled > 0 && n_resampled <= ESL_MAXLEN, "estoi: at most 48 256 samples at 10 kHz per clip (4.8 s)");
     L2S_REQUIRE(fir ? (n_fir > 0 && up > 0 && down > 0 && n_pre_remove >= 0) : n_resampled == n_samples, "estoi: resampler arguments");
     L2S_REQUIRE(ws_bytes >= l2s_estoi_workspace_bytes_long(N, n_resampled), "estoi: workspace too small");
-    for (int b = 0; b < ES_BANDS; ++b)
-        L2S_REQUIRE(band_lo_hi_host[b] >= 0 && band_lo_hi_host[b] <= band_lo_hi_host[ES_BANDS + b] && band_lo_hi_host[ES_BANDS + b] <= ES_NBIN &&
-                    (b == 0 || band_lo_hi_host[b] >= band_lo_hi_host[b - 1]), "estoi: band edges");
+    if (band_edges_check("estoi", band_lo_hi_host)) return 1;
     hipStream_t s = (hipStream_t)stream;
     char* w = (char*)(((uintptr_t)ws + 255) / 256 * 256);
     int* bands = (int*)w;
     float* rs = (float*)(w + 256);
-    L2S_CHECK_HIP(hipMemcpyAsync(bands, band_lo_hi_host, 2 * ES_BANDS * sizeof(int), hipMemcpyHostToDevice, s));
+    if (table_upload(bands, band_lo_hi_host, 2 * ES_BANDS, s)) return 1;
     ProfScope ps("metric_estoi", s);
     if (n_resampled <= ES_MAXLEN) {
         float* pw = rs + (int64_t)N * 2 * ES_MAXLEN;
@@ -1060,10 +1053,18 @@ int l2s_inverse_mel_ragged_check(const int* L, const int64_t* mel_offset, const 
     return 0;
 }
 
+// table: mel_offset[N] | mel_pitch[N] (int64) | the row prefix sums [N + 1] (written by the caller)
+struct ImTable { int64_t off, pitch, row_off; };
+static ImTable im_table(HostTable& t, int N, const int64_t* mel_offset, const int64_t* mel_pitch) {
+    return ImTable{t.i64(mel_offset, N), t.i64(mel_pitch, N), t.i32(nullptr, (int64_t)N + 1)};
+}
+
 // never below the sum of the solo sizers (N = 1, L = L_b): a caller that sized for a loop of solo calls has enough
 int64_t l2s_inverse_mel_ragged_workspace_bytes(const int* L, int N, int n_mels, int n_freqs, int iters) {
     if (ragged_lengths_check("inverse_mel_ragged", L, N)) return -1;
-    int64_t bytes = 256 + 2 * im_align((int64_t)N * 8) + im_align(((int64_t)N + 1) * 4);
+    HostTable t(false);
+    im_table(t, N, nullptr, nullptr);
+    int64_t bytes = 256 + im_align(t.words() * 4) + 512;      // 512: this size once rounded the table's three segments up one by one, and never shrinks
     for (int b = 0; b < N; ++b) bytes += l2s_inverse_mel_workspace_bytes(1, L[b], n_mels, n_freqs, 1, iters);
     return bytes;
 }
@@ -1075,27 +1076,22 @@ int l2s_inverse_mel_ragged(const float* mel, int64_t mel_floats, const int64_t* 
     L2S_REQUIRE(mel && fb && init && spec && ws, "inverse_mel_ragged: null argument");
     L2S_REQUIRE(ws_bytes >= l2s_inverse_mel_ragged_workspace_bytes(L, N, n_mels, n_freqs, iters), "inverse_mel_ragged: workspace too small");
     hipStream_t s = (hipStream_t)stream;
-    std::vector<int> t((size_t)4 * N + (size_t)N + 1);           // mel_offset and mel_pitch as int64 (two ints each), then the row prefix sums
-    memcpy(t.data(), mel_offset, (size_t)N * 8);
-    memcpy(t.data() + 2 * (size_t)N, mel_pitch, (size_t)N * 8);
+    HostTable t;
+    const ImTable o = im_table(t, N, mel_offset, mel_pitch);
+    int* row_off = t.host<int>(o.row_off);
     int64_t rows = 0;
-    for (int b = 0; b < N; ++b) { t[4 * (size_t)N + b] = (int)rows; rows += L[b]; }
-    t[4 * (size_t)N + N] = (int)rows;
-    char* w = (char*)(((uintptr_t)ws + 255) / 256 * 256);
-    int* tab = (int*)w; w += im_align((3 * (int64_t)(n_mels + n_freqs) + 2) * 4);
-    float* fwd = (float*)w; w += im_align(IM_NNZ * 4);
-    float* bwd = (float*)w; w += im_align(IM_NNZ * 4);
-    float* loss_rows = (float*)w; w += im_align(rows * (iters > 0 ? iters : 1) * 4);
-    int* iters_ws = (int*)w; w += im_align((int64_t)N * 4);
-    int* table = (int*)w;                                        // 256-byte aligned: the int64 arrays come first
-    const int64_t* d_off = (const int64_t*)table;
-    const int64_t* d_pitch = d_off + N;
-    const int* d_row_off = table + 4 * (size_t)N;
-    int* iters_call = iters_run ? iters_run : iters_ws;
+    for (int b = 0; b < N; ++b) { row_off[b] = (int)rows; rows += L[b]; }
+    row_off[N] = (int)rows;
+    const InvMelWs c = inverse_mel_carve(ws, n_mels, n_freqs, rows, iters);
+    float* loss_rows = c.loss_rows;
+    int* table = (int*)(c.end + im_align((int64_t)N * 4));       // 256-byte aligned, behind the iteration counts
+    const int64_t *d_off = table_seg<int64_t>(table, o.off), *d_pitch = table_seg<int64_t>(table, o.pitch);
+    const int* d_row_off = table + o.row_off;
+    int* iters_call = iters_run ? iters_run : (int*)c.end;
     ProfScope ps("vocoder_inverse_mel_ragged", s);
-    upload_table(table, t, s);
-    if (launch_mel_bands(fb, n_freqs, n_mels, tab, fwd, bwd, s)) return 1;      // once per call, whatever N
-    InvMelP p{mel, init, tab, fwd, bwd, spec, iters > 0 ? loss_rows : nullptr, nullptr, N, 0, n_mels, n_freqs, 1, iters, log_input, 0, d_row_off, d_off, d_pitch};
+    if (t.upload(table, s)) return 1;
+    if (launch_mel_bands(fb, n_freqs, n_mels, c.tab, c.fwd, c.bwd, s)) return 1;      // once per call, whatever N
+    InvMelP p{mel, init, c.tab, c.fwd, c.bwd, spec, iters > 0 ? loss_rows : nullptr, nullptr, N, 0, n_mels, n_freqs, 1, iters, log_input, 0, d_row_off, d_off, d_pitch};
     const unsigned blocks = (unsigned)((rows + IM_ROWS - 1) / IM_ROWS);
     hipLaunchKernelGGL(inverse_mel_kernel<true>, dim3(blocks), dim3(IM_ROWS * 64), 0, s, p);
     if (iters > 0) {
@@ -1119,13 +1115,21 @@ int l2s_griffin_lim_ragged_check(const int* L, int N, int n_fft, int hop, int it
     return 0;
 }
 
+// table: frame_off[N + 1] | clips of the 12-wave form | of the 8-wave form | of the tile form | tile_off[n_long + 1]
+struct GlTable { int64_t frame_off, c12, c8, cl, tile_off; };
+static GlTable gl_table(HostTable& t, int N, const int* frame_off, const int* c12, int n12, const int* c8, int n8, const int* cl, int nl, const int* tile_off) {
+    return GlTable{t.i32(frame_off, (int64_t)N + 1), t.i32(c12, n12), t.i32(c8, n8), t.i32(cl, nl), t.i32(tile_off, nl ? nl + 1 : 0)};
+}
+// the table's slot: the largest table (every clip takes the tile form) and the one spare word this size has always counted
+static int64_t gl_table_bytes(int N) { HostTable t(false); gl_table(t, N, nullptr, nullptr, 0, nullptr, 0, nullptr, N, nullptr); return im_align((t.words() + 1) * 4); }
+
 int64_t l2s_griffin_lim_ragged_workspace_bytes(const int* L, int N) {
     if (ragged_lengths_check("griffin_lim_ragged", L, N)) return -1;
     int64_t frames = 0;
     for (int b = 0; b < N; ++b) frames += L[b];
     // three slots of rebuilt spectra per frame whatever the clip's form (one block offset serves every form), and the solo sizers' 512 bytes per clip:
     // never below their sum
-    return 512 + im_align((3 * (int64_t)N + 3) * 4) + frames * GL_LDK * 4 + frames * 3 * GL_LDK * 8 + 512 * (int64_t)N;
+    return 512 + gl_table_bytes(N) + frames * GL_LDK * 4 + frames * 3 * GL_LDK * 8 + 512 * (int64_t)N;
 }
 
 int l2s_griffin_lim_ragged(const float* power_spec, const float* init_angles, const int* L, int N, int n_fft, int hop, int iters, float momentum,
@@ -1134,35 +1138,28 @@ int l2s_griffin_lim_ragged(const float* power_spec, const float* init_angles, co
     L2S_REQUIRE(power_spec && init_angles && wave && ws, "griffin_lim_ragged: null argument");
     L2S_REQUIRE(ws_bytes >= l2s_griffin_lim_ragged_workspace_bytes(L, N), "griffin_lim_ragged: workspace too small");
     hipStream_t s = (hipStream_t)stream;
-    // table: frame_off[N + 1] | clips of the 12-wave form | of the 8-wave form | of the tile form | tile_off[n_long + 1]
-    std::vector<int> t((size_t)N + 1), l12, l8, ll, toff;
+    std::vector<int> foff((size_t)N + 1), l12, l8, ll, toff;
     int64_t frames = 0;
     int long_max = 0, tiles = 0;
     for (int b = 0; b < N; ++b) {
-        t[b] = (int)frames; frames += L[b];
+        foff[b] = (int)frames; frames += L[b];
         const int ylen = GL_HOP * (L[b] - 1);
         if (ylen <= 19456) l12.push_back(b);
         else if (ylen <= 30720) l8.push_back(b);
         else { toff.push_back(tiles); tiles += (L[b] + GLT_F - 1) / GLT_F; ll.push_back(b); long_max = std::max(long_max, L[b]); }
     }
-    t[N] = (int)frames;
+    foff[N] = (int)frames;
     const int n12 = (int)l12.size(), n8 = (int)l8.size(), nl = (int)ll.size();
     if (nl) toff.push_back(tiles);
-    t.insert(t.end(), l12.begin(), l12.end());
-    t.insert(t.end(), l8.begin(), l8.end());
-    t.insert(t.end(), ll.begin(), ll.end());
-    t.insert(t.end(), toff.begin(), toff.end());
+    HostTable t;
+    const GlTable o = gl_table(t, N, foff.data(), l12.data(), n12, l8.data(), n8, ll.data(), nl, toff.data());
     char* w = (char*)(((uintptr_t)ws + 255) / 256 * 256);
-    int* table = (int*)w; w += im_align((3 * (int64_t)N + 3) * 4);
+    int* table = (int*)w; w += gl_table_bytes(N);
     float* mag = (float*)w;
     float2* reb = (float2*)(w + frames * GL_LDK * 4);
-    const int* d_off = table;
-    const int* d12 = table + N + 1;
-    const int* d8 = d12 + n12;
-    const int* dl = d8 + n8;
-    const int* dt = dl + nl;
+    const int *d_off = table + o.frame_off, *d12 = table + o.c12, *d8 = table + o.c8, *dl = table + o.cl, *dt = table + o.tile_off;
     ProfScope ps("vocoder_griffin_lim_ragged", s);
-    upload_table(table, t, s);
+    if (t.upload(table, s)) return 1;
     const float mom = momentum / (1.0f + momentum);
     if (n12) {
         GriffinP p{power_spec, init_angles, mag, reb, wave, N, 0, iters, mom, d_off, d12, wave_pitch};
@@ -1201,10 +1198,18 @@ int l2s_estoi_ragged_check(const int* n_samples, const int* n_fir, const int* n_
     return 0;
 }
 
+// table: n_samples[N] | n_fir[N] (null: zeros) | n_resampled[N] | clips of the short form [ns], then of the long form [N - ns] | band edges [30]
+struct EsTable { int64_t n_samples, n_fir, n_resampled, c_short, c_long, bands; };
+static EsTable es_table(HostTable& t, int N, const int* n_samples, const int* n_fir, const int* n_resampled, const int* c_short, int ns, const int* c_long,
+                        const int* band_lo_hi) {
+    return EsTable{t.i32(n_samples, N), t.i32(n_fir, N), t.i32(n_resampled, N), t.i32(c_short, ns), t.i32(c_long, N - ns), t.i32(band_lo_hi, 2 * ES_BANDS)};
+}
+static int64_t es_table_bytes(int N) { HostTable t(false); es_table(t, N, nullptr, nullptr, nullptr, nullptr, N, nullptr, nullptr); return im_align(t.words() * 4); }
+
 // the sum of the solo sizers (each clip's form by its own n_resampled) plus the tables
 int64_t l2s_estoi_ragged_workspace_bytes(const int* n_resampled, int N) {
     if (N < 1 || N > RAG_MAX_CLIPS || !n_resampled) { set_error("l2s: estoi_ragged: N outside [1, 65535] or a null table of resampled lengths"); return -1; }
-    int64_t bytes = 256 + im_align((4 * (int64_t)N + 2 * ES_BANDS) * 4);
+    int64_t bytes = 256 + es_table_bytes(N);
     for (int b = 0; b < N; ++b) bytes += l2s_estoi_workspace_bytes_long(1, n_resampled[b]);
     return bytes;
 }
@@ -1215,39 +1220,34 @@ int l2s_estoi_ragged(const float* clean, const float* pred, int64_t pitch, const
     if (l2s_estoi_ragged_check(n_samples, n_fir, n_resampled, N, pitch, fir != nullptr, n_fir_max, up, down, n_pre_remove)) return 1;
     L2S_REQUIRE(clean && pred && score && ws && band_lo_hi_host, "estoi_ragged: null argument");
     L2S_REQUIRE(ws_bytes >= l2s_estoi_ragged_workspace_bytes(n_resampled, N), "estoi_ragged: workspace too small");
-    for (int b = 0; b < ES_BANDS; ++b)
-        L2S_REQUIRE(band_lo_hi_host[b] >= 0 && band_lo_hi_host[b] <= band_lo_hi_host[ES_BANDS + b] && band_lo_hi_host[ES_BANDS + b] <= ES_NBIN &&
-                    (b == 0 || band_lo_hi_host[b] >= band_lo_hi_host[b - 1]), "estoi_ragged: band edges");
+    if (band_edges_check("estoi_ragged", band_lo_hi_host)) return 1;
     hipStream_t s = (hipStream_t)stream;
-    // table: n_samples[N] | n_fir[N] | n_resampled[N] | clips of the short form, then of the long form [N] | band edges [30]
-    std::vector<int> t((size_t)4 * N + 2 * ES_BANDS), ls, ll;
+    std::vector<int> ls, ll;
     int long_max = 0;
     for (int b = 0; b < N; ++b) {
-        t[b] = n_samples[b]; t[(size_t)N + b] = fir ? n_fir[b] : 0; t[2 * (size_t)N + b] = n_resampled[b];
         if (n_resampled[b] <= ES_MAXLEN) ls.push_back(b); else { ll.push_back(b); long_max = std::max(long_max, n_resampled[b]); }
     }
     const int ns = (int)ls.size(), nl = (int)ll.size();
-    std::copy(ls.begin(), ls.end(), t.begin() + 3 * (size_t)N);
-    std::copy(ll.begin(), ll.end(), t.begin() + 3 * (size_t)N + ns);
-    std::copy(band_lo_hi_host, band_lo_hi_host + 2 * ES_BANDS, t.begin() + 4 * (size_t)N);
+    HostTable t;
+    const EsTable o = es_table(t, N, n_samples, fir ? n_fir : nullptr, n_resampled, ls.data(), ns, ll.data(), band_lo_hi_host);
     char* w = (char*)(((uintptr_t)ws + 255) / 256 * 256);
-    int* table = (int*)w; w += im_align((4 * (int64_t)N + 2 * ES_BANDS) * 4);
-    const int* bands = table + 4 * (size_t)N;
+    int* table = (int*)w; w += es_table_bytes(N);
+    const int* bands = table + o.bands;
     float* rs_s = (float*)w;                                                  // short slots: (ns, 2, ES_MAXLEN) then (ns, 2, ES_MAXFRAMES, ES_NBIN)
     float* pw_s = rs_s + (int64_t)ns * 2 * ES_MAXLEN;
     float* rs_l = pw_s + (int64_t)ns * 2 * ES_MAXFRAMES * ES_NBIN;            // long slots: rs, oa (nl, 2, ESL_MAXLEN) each, then the spectra
     float* oa_l = rs_l + (int64_t)nl * 2 * ESL_MAXLEN;
     float* pw_l = oa_l + (int64_t)nl * 2 * ESL_MAXLEN;
     ProfScope ps("metric_estoi_ragged", s);
-    upload_table(table, t, s);
+    if (t.upload(table, s)) return 1;
     if (ns) {
         EstoiP p{clean, pred, fir, bands, bands + ES_BANDS, rs_s, pw_s, score, N, 0, 0, up, down, n_pre_remove, 0,
-                 EstoiRag{table, table + N, table + 2 * (size_t)N, table + 3 * (size_t)N, pitch}};
+                 EstoiRag{table + o.n_samples, table + o.n_fir, table + o.n_resampled, table + o.c_short, pitch}};
         hipLaunchKernelGGL(estoi_kernel<true>, dim3(ns), dim3(1024), 0, s, p);
     }
     if (nl) {
         EstoiLongP p{clean, pred, fir, bands, bands + ES_BANDS, rs_l, oa_l, pw_l, score, N, 0, 0, up, down, n_pre_remove, 0,
-                     EstoiRag{table, table + N, table + 2 * (size_t)N, table + 3 * (size_t)N + ns, pitch}};
+                     EstoiRag{table + o.n_samples, table + o.n_fir, table + o.n_resampled, table + o.c_long, pitch}};
         hipLaunchKernelGGL(estoi_resample_kernel<true>, dim3((long_max + 255) / 256, 2, nl), dim3(256), 0, s, p);
         hipLaunchKernelGGL(estoi_long_kernel<true>, dim3(nl), dim3(1024), 0, s, p);
     }

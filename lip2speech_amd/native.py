@@ -55,7 +55,7 @@ ABI_SYMBOLS = (
 DIAG_SYMBOLS = (
     "l2s_op_gemm", "l2s_op_conv1d", "l2s_op_gemm_ex", "l2s_op_conv1d_ex", "l2s_op_conv1d_bwd", "l2s_op_frontend", "l2s_op_launch_chain", "l2s_op_launch_chain2", "l2s_op_skinny_timeline", "l2s_op_attn_timeline", "l2s_op_flat_timeline", "l2s_op_pdecode_timeline", "l2s_op_gemm_x3_timeline", "l2s_op_fused_unit_timeline", "l2s_op_lstm_cell_chain", "l2s_op_step_attn_chain", "l2s_op_stamp_log", "l2s_op_skinny_form", "l2s_op_step_site", "l2s_op_skinny", "l2s_op_skinny_hoist",
     "l2s_op_face_conv2d", "l2s_op_face_taps", "l2s_op_speaker_taps", "l2s_op_speaker_taps_packed", "l2s_op_encoder_taps",
-    "l2s_op_gemm_bwd", "l2s_op_gemm_bwd_recorder",
+    "l2s_op_gemm_bwd", "l2s_op_gemm_bwd_recorder", "l2s_op_upload_table", "l2s_op_table_layout",
 )
 
 # run-time options only the diagnostic build accepts (block-form A/B switches of the same arithmetic, include/l2s_diag.h)
@@ -328,6 +328,9 @@ def _bind_diag(L: ctypes.CDLL) -> None:
     L.l2s_op_encoder_taps.argtypes = [_vp, _fp, _i, _i, _i, _i, _vp, _fp, _vp, _i64, _vp]
     L.l2s_op_gemm_bwd.argtypes = [ctypes.POINTER(GemmBwdDesc), _fp, _fp, _fp, ctypes.POINTER(GemmBwdDesc), _fp, _fp, _fp, _i, _fp, _i, ctypes.POINTER(GemmBwdRecord), _vp]
     L.l2s_op_gemm_bwd_recorder.argtypes = [_i, ctypes.POINTER(GemmBwdRecord), _i, ctypes.POINTER(_i)]
+    if hasattr(L, "l2s_op_upload_table"):
+        L.l2s_op_upload_table.argtypes = [_vp, _i64, _vp, _vp]
+        L.l2s_op_table_layout.argtypes = [_vp, _i64, _vp, _i64, _i, _vp, ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(_i64), _vp]
 
 
 def check(rc: int, L: Optional[ctypes.CDLL] = None) -> None:
@@ -1586,6 +1589,27 @@ def gemm_bwd_recorder_read(disarm: bool = True) -> list:
     arr = (GemmBwdRecord * max(1, n.value))()
     _dcheck(D.l2s_op_gemm_bwd_recorder(2, arr, n.value, ctypes.byref(n)))
     return [gemm_bwd_record_dict(arr[i]) for i in range(min(n.value, len(arr)))]
+
+
+TABLE_CHUNK = 960                         # L2S_TABLE_CHUNK (include/l2s_diag.h): words of a per-clip table that one launch carries in its kernel arguments
+
+
+def op_upload_table(host_words: ctypes.Array, n: int, dst: torch.Tensor, offset: int = 0) -> None:
+    """`l2s_op_upload_table`: dst (int32, device).flatten()[offset : offset + n] = host_words[:n] (a ctypes int32 array) on the current stream"""
+    assert dst.dtype == torch.int32 and dst.is_contiguous() and 0 <= offset and offset + n <= dst.numel() and n <= len(host_words)
+    _dcheck(diag().l2s_op_upload_table(ctypes.addressof(host_words), int(n), dst.data_ptr() + 4 * offset, _stream()))
+
+
+def op_table_layout(a, b, fill: bool = True, dst: Optional[torch.Tensor] = None):
+    """`l2s_op_table_layout`: the builder's (offset of the int32 segment, offset of the int64 segment, total words) for len(a) int32 words followed by
+    len(b) int64 values; fill=False: sizes only; with dst (int32, device, 8-byte aligned) the table is uploaded to its front"""
+    off_a, off_b, words = _i64(), _i64(), _i64()
+    ha, hb = (ctypes.c_int32 * max(1, len(a)))(*[int(v) for v in a]), (_i64 * max(1, len(b)))(*[int(v) for v in b])
+    for d in (None, dst) if dst is not None else (None,):      # sizes first: the upload only once the table is known to fit dst
+        assert d is None or (fill and d.dtype == torch.int32 and d.data_ptr() % 8 == 0 and words.value <= d.numel())
+        _dcheck(diag().l2s_op_table_layout(ctypes.addressof(ha) if fill else None, len(a), ctypes.addressof(hb) if fill else None, len(b), 1 if fill else 0,
+                                           _ptr(d), ctypes.byref(off_a), ctypes.byref(off_b), ctypes.byref(words), _stream() if d is not None else None))
+    return off_a.value, off_b.value, words.value
 
 
 # ---------------------------------------------------------------------------------------------- profiling

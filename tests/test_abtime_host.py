@@ -59,6 +59,7 @@ def test_verdicts():
     assert abtime.median_inside([1.0, 2.0, 2.0], [2.0, 3.0, 3.0])                           # touching: a's median on b's edge
     assert abtime.median_inside([1.0, 1.0, 9.0], [4.0, 5.0, 6.0])                           # either way round: b's median inside a's spread
     assert not abtime.median_inside([1.0, 1.0, 3.5], [3.0, 4.0, 4.0])                       # spans overlap, neither median inside
+    assert abtime.not_above(mid, high) and abtime.not_above(low, high) and not abtime.not_above(high, low)      # inside, below, above
 
 
 def test_libs_from_env(monkeypatch):

@@ -236,6 +236,29 @@ def test_split_bf16_postnet_form(case, ragged_abc):
         assert g.shape == w.shape and torch.equal(torch.isfinite(g), fin) and d < MEL_TOL
 
 
+def test_clip_table_crosses_a_chunk_of_the_carrier(synth_sd):
+    """The per-clip table travels in kernel arguments, native.TABLE_CHUNK words per launch (csrc/host_table.h), and a clip's record is 8 words: one clip more
+    than a launch carries, so the last clip's record is written by the second launch.  121 clips of 7 frames at 88 x 88 in eight batches of 16 and 15, S = 3
+    and 4 by turns.  Row by row against the masked call on every batch alone; the group's 121 rows take other GEMM and post-net forms than a batch's 16 (the
+    choices follow the rows of the call), so the rows are held to the gate, as C is in test_split_bf16_postnet_form."""
+    N = native.TABLE_CHUNK // 8 + 1
+    assert N <= native.MAX_RAGGED_CLIPS
+    sizes = [N // 8 + (g < N % 8) for g in range(8)]
+    nm = pc.native_model(synth_sd)
+    bts = []
+    for g, B in enumerate(sizes):
+        bts.append({"lens": [7] * B, "T": 7, "S": 3 + g % 2, "m": 1, "video": synth.synth_video(B, 7, 88, 88, tag=f"chunk-{g}"),
+                    "emb": synth.synth_speaker_embedding(B, tag=f"chunk-{g}"), "gumbel": synth.synth_gumbel(B, tag=f"chunk-{g}")})
+    group = _ragged(nm, bts)
+    for g, (bt, got) in enumerate(zip(bts, group)):
+        want = _masked(nm, bt)
+        for name, a, w in zip(NAMES, got, want):
+            fin = torch.isfinite(w)
+            d = float((a - w)[fin].abs().max())
+            print(f"batch {g} ({len(bt['lens'])} clips, S = {bt['S']}) in the group of {N} against the masked call: {name} max |d| = {d:.3e}")
+            assert a.shape == w.shape and torch.equal(torch.isfinite(a), fin) and d < MEL_TOL
+
+
 def test_route(case):
     """One ragged front-end launch for the group, Smax decode steps, the five zero-fill launches exactly when the step counts differ, and no persistent
     kernel even with the persistent options set."""

@@ -81,6 +81,11 @@ def median_inside(a, b):
     return min(b) <= ma <= max(b) or min(a) <= mb <= max(a)
 
 
+def not_above(a, b):
+    """the median of a lies inside the span of b's rounds, or below it: "no slower than" """
+    return statistics.median(a) <= max(b)
+
+
 def synth_model(library=None, state_dict=None, **options):
     """A NativeModel of `library` (default: the package's own) with the options set, loaded with `state_dict` (default: synth.synth_state_dict())."""
     from lip2speech_amd import native, synth

@@ -3,7 +3,7 @@ batch - B = 16 clips with lengths uniform in [25, 75] zero-padded to the batch m
 = T, so that both calls do the same arithmetic and the difference is the masking machinery: the length table, the BiLSTM row kernels, the masked
 copy / pooling, the length-masked attention blocks, and the launch-per-phase route.  A second line gives the masked call at the clips' true lengths.
 `PARENT_LIB=<path to a libl2s_hip.so built from the parent commit>`: that build's unmasked call is timed in the same process, interleaved with this
-build's (has the default path moved?).  ROUNDS interleaved rounds of REPS warm calls each, the variants rotating inside a round, HIP events around the
+build's (has the default path moved?), and so is its masked call at the true lengths (has the masked route moved?).  ROUNDS interleaved rounds of REPS warm calls each, the variants rotating inside a round, HIP events around the
 REPS calls; per variant the median of the rounds and the spread (max - min).  `B=`, `S=`, `ROUNDS=`, `REPS=`.
 -> profiles/masked_lengths_times.txt (stdout)"""
 import os
@@ -35,6 +35,7 @@ def main():
     parent = next((abtime.synth_model(lib) for _, lib in abtime.libs_from_env("PARENT_LIB", native._load)), None)
     if parent is not None:
         variants.insert(0, ("parent build, l2s_inference", lambda: parent.inference(video, emb, gum, S=S)))
+        variants.append(("parent build, l2s_inference_masked, true lengths", lambda: parent.inference(video, emb, gum, S=S, video_lengths=lens)))
     print(f"B = {B} clips, lengths {sorted(lens)} zero-padded to T = {T}, S = {S}; {ROUNDS} interleaved rounds x {REPS} warm calls, HIP events; "
           f"median of the rounds, spread = max - min")
     t, outs = abtime.rounds(variants, ROUNDS, REPS)          # the warm-up call covers every shape and route
@@ -46,6 +47,8 @@ def main():
         lo, hi = min(t[0]), max(t[0])
         print(f"default path: this build's l2s_inference median {med[1]:.3f} ms; the parent build's rounds span [{lo:.3f}, {hi:.3f}] ms -> "
               f"{'inside' if lo <= med[1] <= hi else 'OUTSIDE'} the parent's spread")
+        print(f"masked route, true lengths: both builds bit-identical: {torch.equal(outs[3][0], outs[4][0])}; this build's median {med[3]:.3f} ms, the parent "
+              f"build's rounds span [{min(t[4]):.3f}, {max(t[4]):.3f}] ms -> {'inside or below' if abtime.not_above(t[3], t[4]) else 'ABOVE'} the parent's span")
 
 
 if __name__ == "__main__":

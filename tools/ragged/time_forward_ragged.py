@@ -53,6 +53,7 @@ def workload(title, B, lo, hi, this, parent):
                 ("(b) this build, 1 x l2s_forward_eval_ragged", lambda: this.forward_eval_ragged(batches, lens, Ss))]
     if parent is not None:
         variants.append((f"(a) parent build, {G} x l2s_forward_eval_masked", masked8(parent)))
+        variants.append(("(b) parent build, 1 x l2s_forward_eval_ragged", lambda: parent.forward_eval_ragged(batches, lens, Ss)))
     t, outs = abtime.rounds(variants, ROUNDS, REPS)          # the warm-up call covers every shape and route
     same = all(all(torch.equal(x, y) for x, y in zip(a, b)) for a, b in zip(outs[0], outs[1]))
     worst = max(float((a[1] - b[1]).abs().max()) for a, b in zip(outs[0], outs[1]))
@@ -64,6 +65,9 @@ def workload(title, B, lo, hi, this, parent):
     if parent is not None:
         print(f"today's route, {G} x l2s_forward_eval_masked: this build {med[0]:.3f} ms, parent build {med[2]:.3f} ms -> a median "
               f"{'inside' if abtime.median_inside(t[0], t[2]) else 'OUTSIDE'} the other's spread")
+        same = all(all(torch.equal(x, y) for x, y in zip(a, b)) for a, b in zip(outs[1], outs[3]))
+        print(f"ragged route, 1 x l2s_forward_eval_ragged: both builds bit-identical: {same}; this build {med[1]:.3f} ms, parent build {med[3]:.3f} ms (rounds "
+              f"[{min(t[3]):.3f}, {max(t[3]):.3f}]) -> {'inside or below' if abtime.not_above(t[1], t[3]) else 'ABOVE'} the parent's span")
 
 
 def default_path(this, parent):

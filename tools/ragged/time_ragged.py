@@ -77,7 +77,8 @@ def workload(title, B, lo, hi, this, parent):
     if parent is not None:
         variants += [(f"(a) parent build, {G} x l2s_inference_masked", masked8(parent)),
                      ("(c) parent build, l2s_inference_multi, re-padded", lambda: parent.inference_multi(common, S=S)),
-                     ("    parent build, l2s_inference, first batch", lambda: parent.inference(*batches[0], S=S))]
+                     ("    parent build, l2s_inference, first batch", lambda: parent.inference(*batches[0], S=S)),
+                     ("(b) parent build, 1 x l2s_inference_ragged", lambda: parent.inference_ragged(batches, lens, S=S))]
     t, outs = abtime.rounds(variants, ROUNDS, REPS)          # the warm-up call covers every shape and route
     same = all(torch.equal(a[0], b[0]) and torch.equal(a[1], b[1]) for a, b in zip(outs[0], outs[1]))
     worst = max(float((a[0] - b[0]).abs().max()) for a, b in zip(outs[0], outs[1]))
@@ -89,6 +90,9 @@ def workload(title, B, lo, hi, this, parent):
         for mine, theirs, what in ((0, 4, f"{G} x l2s_inference_masked"), (2, 5, "l2s_inference_multi"), (3, 6, "l2s_inference")):
             print(f"default path, {what}: this build {med[mine]:.3f} ms (rounds [{min(t[mine]):.3f}, {max(t[mine]):.3f}]), parent build {med[theirs]:.3f} ms "
                   f"(rounds [{min(t[theirs]):.3f}, {max(t[theirs]):.3f}]) -> a median {'inside' if abtime.median_inside(t[mine], t[theirs]) else 'OUTSIDE'} the other's spread")
+        same = all(torch.equal(a[0], b[0]) and torch.equal(a[1], b[1]) for a, b in zip(outs[1], outs[7]))
+        print(f"ragged route, 1 x l2s_inference_ragged: both builds bit-identical: {same}; this build {med[1]:.3f} ms, parent build {med[7]:.3f} ms (rounds "
+              f"[{min(t[7]):.3f}, {max(t[7]):.3f}]) -> {'inside or below' if abtime.not_above(t[1], t[7]) else 'ABOVE'} the parent's span")
     fe_a, tr_a = encoder_ms(variants[0][1])
     fe_b, tr_b = encoder_ms(variants[1][1])
     print(f"launch profile (one call, event brackets around every launch): front-end (a) {fe_a:.3f} ms -> (b) {fe_b:.3f} ms; trunk (a) {tr_a:.3f} ms -> (b) {tr_b:.3f} ms")

@@ -2,7 +2,7 @@
 once per batch, NOT on the mel-frames/s path:
   (a) `l2s_speaker_encoder_fwd` on the clips zero-padded to the longest (B x L_max rows; what every caller ran before, and the default still);
   (b) `l2s_speaker_encoder_packed` on the same clips packed back to back (R = sum L_b rows; the same 3 x L_max step launches);
-  (c) with `PARENT_LIB=<path to a build of the parent commit's library>`: (a) from that build, in the same process - the default path has not moved.
+  (c) with `PARENT_LIB=<path to a build of the parent commit's library>`: (a) and (b) from that build, in the same process - neither path has moved.
 Shapes: 16 clips of 16 000 - 48 000 samples (1 - 3 s, evenly spread) padded to 48 000, and 32 clips of 16 640 - 32 000.  Uploads and workspace allocation
 are outside the timed region.  ROUNDS interleaved rounds of REPS warm calls each, the variants rotating inside a round, HIP events around the REPS calls;
 per variant the median of the rounds and the spread.  `SHAPES=Bxlo-hi[,Bxlo-hi...]`: other workloads of B clips of lo - hi samples; `ROUNDS=`, `REPS=`.
@@ -64,6 +64,7 @@ def workload(title, B, lo, hi, nm, parent):
     variants = [("(a) l2s_speaker_encoder_fwd, padded", padded_call(nm, audio)), ("(b) l2s_speaker_encoder_packed", packed_call(nm, buf, off, ns))]
     if parent is not None:
         variants.append(("(c) PARENT_LIB: l2s_speaker_encoder_fwd, padded", padded_call(parent, audio)))
+        variants.append(("(c) PARENT_LIB: l2s_speaker_encoder_packed", packed_call(parent, buf, off, ns)))
     t, outs = abtime.rounds(variants, ROUNDS, REPS)          # outs: each route's own embedding buffer, which every call of it rewrites
     R, L_max = sum(n // 160 + 1 for n in ns), N // 160 + 1
     print(f"\n== {title}: B = {B}, {min(ns)} - {N} samples; padded rows B x L_max = {B * L_max}, compact rows R = {R} ({R / (B * L_max):.3f}); {3 * L_max} step launches either way")
@@ -73,6 +74,9 @@ def workload(title, B, lo, hi, nm, parent):
     if parent is not None:
         print(f"(c) against (a): embeddings bit-identical: {torch.equal(outs[2], outs[0])}")
     abtime.report(variants, t, unit="us", ratio="(a)")
+    if parent is not None:
+        print(f"(c) packed against (b): embeddings bit-identical: {torch.equal(outs[3], outs[1])}; this build's median "
+              f"{'inside or below' if abtime.not_above(t[1], t[3]) else 'ABOVE'} the span of the parent's rounds")
 
 
 def main():

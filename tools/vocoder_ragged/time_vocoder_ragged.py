@@ -10,7 +10,8 @@ Workload one: CLIPS clips of FRAMES mel frames (one GRID batch); workload two: B
 EXPECTATION, stated before measuring: (c) beats (a) by roughly the launch count (a long clip's solo vocoder is ~ITERS tile launches, and (c) makes one chain of
 them for all clips); (c) beats (b) on the many-batch workload by running one chain sized by the real frames instead of one chain per batch.
 Then the DEFAULT path: `l2s_griffin_lim` and `l2s_estoi` at DEFAULT_SHAPE from this build and from every library in `ALT_LIBS=name=path[,name=path...]`
-(the parent commit's build) in the same process, with a bit comparison: the solo entry points must not have moved outside the spread.
+(the parent commit's build; `PARENT_LIB=path` adds one named "parent build") in the same process, with a bit comparison: the solo entry points must not have
+moved outside the spread.  Route (c) of both workloads is run from every such library too: same bits, and this build's median inside or below its span.
 ROUNDS interleaved rounds, the variants rotating inside a round, wall clock around REPS synchronised calls; per variant the median of the rounds and the span.
 `CLIPS=`, `BATCHES=`, `FRAMES=lo-hi`, `DEFAULT_SHAPE=NxL`, `ROUNDS=`, `REPS=`, `ITERS=`.
 -> profiles/vocoder_ragged_times.txt (stdout)"""
@@ -35,7 +36,18 @@ DEF_N, DEF_L = (int(v) for v in os.environ.get("DEFAULT_SHAPE", "16x188").split(
 FS = 16000
 
 
-def workload(title, n_batches):
+def from_library(lib, fn):
+    """fn with `lib` as the library the package's own callers (native.lib()) reach"""
+    def call():
+        keep, native._lib = native._lib, lib
+        try:
+            return fn()
+        finally:
+            native._lib = keep
+    return call
+
+
+def workload(title, n_batches, alts=()):
     rng = np.random.default_rng(n_batches)
     lengths = [[int(v) for v in rng.integers(F_LO, F_HI + 1, CLIPS)] for _ in range(n_batches)]
     for ls in lengths:
@@ -69,13 +81,14 @@ def workload(title, n_batches):
             out.append(metrics.estoi_device(clean_dev[rows, :pred.shape[1]].contiguous(), pred, FS))
         return torch.cat(out).cpu().numpy()
 
-    def ragged_route():
+    def ragged_route(key="c"):
         pred = voc(mel, generator=g.manual_seed(1), lengths=flat)
-        keep["c"] = pred
+        keep[key] = pred
         return metrics.estoi_device(clean_dev[:, :pred.shape[1]].contiguous(), pred, FS, lengths=n_flat).cpu().numpy()
 
     variants = [("(a) solo calls back to back", solo_route), ("(b) padded call per batch", padded_route), ("(c) one ragged call", ragged_route)]
-    tt, (sa, sb, sc) = abtime.rounds(variants, ROUNDS, REPS, clock="host")          # the warm-up call covers the three routes
+    variants += [(f"(c) one ragged call, {nm}", from_library(lib, lambda nm=nm: ragged_route(nm))) for nm, lib in alts]
+    tt, (sa, sb, sc, *s_alt) = abtime.rounds(variants, ROUNDS, REPS, clock="host")          # the warm-up call covers the three routes
     print(f"\n== {title}: {n_batches} x {CLIPS} clips of {F_LO}-{F_HI} mel frames ({sum(flat)} frames, {n_batches * CLIPS * F_HI} padded), {ITERS} + {ITERS} iterations")
     same = all(torch.equal(keep["c"][i, :n], keep["a"][i][0]) and not keep["c"][i, n:].any() for i, n in enumerate(n_flat))
     print(f"waveforms of (c) bit-identical to (a): {same}; scores of (c) bit-identical to (a): {np.array_equal(sa, sc)}")
@@ -83,6 +96,9 @@ def workload(title, n_batches):
     med = abtime.report(variants, tt, ratio="the first")
     print(f"(a) / (c) = {med[0] / med[2]:.2f}, whole span of (c) below the whole span of (a): {abtime.wholly_under(tt[2], tt[0])}")
     print(f"(b) / (c) = {med[1] / med[2]:.2f}, whole span of (c) below the whole span of (b): {abtime.wholly_under(tt[2], tt[1])}")
+    for (nm, _), s, x in zip(alts, s_alt, tt[3:]):
+        print(f"(c) from {nm}: waveforms and scores bit-identical to this build's: {torch.equal(keep[nm], keep['c']) and np.array_equal(s, sc)}; this build's median "
+              f"{med[2]:.3f} ms, its rounds span [{min(x):.3f}, {max(x):.3f}] ms -> {'inside or below' if abtime.not_above(tt[2], x) else 'ABOVE'} its span")
 
 
 def default_path(alts):
@@ -133,10 +149,10 @@ def default_path(alts):
 
 
 def main():
-    alts = abtime.libs_from_env("ALT_LIBS", native._load)
+    alts = abtime.libs_from_env("ALT_LIBS", native._load) + [("parent build", lib) for _, lib in abtime.libs_from_env("PARENT_LIB", native._load)]
     print(f"{ROUNDS} interleaved rounds, wall clock around {REPS} synchronised call(s); median of the rounds, span = min .. max")
-    workload("one batch", 1)
-    workload(f"{BATCHES} batches", BATCHES)
+    workload("one batch", 1, alts)
+    workload(f"{BATCHES} batches", BATCHES, alts)
     default_path(alts)
 
 
