@@ -174,6 +174,53 @@ typedef struct l2s_align_job { int64_t offset; int32_t H, W; double m[6]; } l2s_
 int l2s_align_check(const l2s_align_job* jobs, int n, int64_t packed_bytes);
 int l2s_align_faces(const uint8_t* packed_in, int64_t packed_bytes, const l2s_align_job* jobs, int n, uint8_t* packed_out, void* stream);
 
+/* JPEG decoding, the step before all of the above for the loaders whose frames are stored compressed (datasets/lrw/dataset.py:62-70 and the in-the-wild loader:
+ * bz2 pickles of JPEG byte strings, decoded with cv2.imdecode per frame on the host): the compressed strings are uploaded as they are and decoded on the device
+ * (jpeg_decode.hip).  libjpeg's default decoder is integer arithmetic throughout - jidctint "islow" IDCT, triangle ("fancy") chroma upsampling, fixed-point
+ * YCbCr -> RGB - and lip2speech_amd/datasets/jpeg.py restates it: Pillow / libjpeg-turbo is PINNED against that restatement bit for bit, and the kernels agree
+ * with it to the bit; parity with cv2.imdecode stays UNPINNED (OpenCV is absent from the build image).
+ * The subset: baseline sequential (SOF0), 8-bit samples, 8-bit quantisation tables, ONE interleaved scan of one component (grey: R = G = B) or of three read as
+ * YCbCr with sampling 2x2 / 1x1 / 1x1 (4:2:0) or all 1x1 (4:4:4); restart intervals (DRI / RSTn); H and W in [1, 4096].
+ * l2s_jpeg_plan (pure host): n streams in ONE host buffer, stream i the sizes[i] bytes at offsets[i].  Per image its record: the span of the entropy-coded data
+ *   (scan_offset, absolute in the buffer; scan_bytes, up to the marker that ends it; eoi = 1 if that marker is EOI), H, W, layout, the restart interval in MCUs and
+ *   the index of its TABLE SET.  A table set is what the scan's components use - per component its 64 quantisers in natural order and its DC / AC table ids, and
+ *   per Huffman table the derived lookup the kernel wants (lut: the 8-bit window -> length << 8 | symbol, 0 where the code is longer; maxcode / valoff per length
+ *   for those; the values) - deduplicated across the call by content into sets[0 .. *n_sets); sets_cap is the room (n always suffices).  Refused, with
+ *   "image i" and the reason, before anything else happens: progressive (SOF2), extended (SOF1), lossless and arithmetic-coded frames; 12-bit samples; 16-bit
+ *   quantisation tables; four components; other sampling factors; more than one scan; DNL; an Adobe APP14 marker with transform 0 or component ids R, G, B; a
+ *   table that the scan names and nothing defined; a header that runs past the stream; H or W outside [1, 4096].  A stream that stops inside its scan is NOT
+ *   refused: eoi = 0, and the decode reports it in status.
+ * l2s_jpeg_workspace_bytes: the workspace of a decode call of these records (-1 and an error for records l2s_jpeg_decode would refuse).
+ * l2s_jpeg_decode:
+ *   streams      dev: the compressed streams in one buffer, exactly as planned (4-byte aligned base); stream_bytes its size.  No byte outside
+ *                [0, stream_bytes) is read, and of the buffer only the images' scan spans rounded out to 4-byte boundaries
+ *   images, sets HOST arrays (the plan's, or the caller's own: every field is checked) that may be freed on return; out_offsets HOST (n) likewise
+ *   packed_out   dev: image i is written as interleaved (H_i, W_i, 3) uint8 at out_offsets[i], a multiple of 4 - the layout l2s_normalise_pad_frames,
+ *                l2s_resize_normalise and l2s_align_faces read, so a clip of T frames is T images at consecutive offsets.  An image writes its span rounded up
+ *                to 4 bytes (clipped to the buffer), the pad bytes as zeros; every other byte of packed_out is left untouched; none outside [0, packed_bytes)
+ *                is written
+ *   status       dev (n) int32 or NULL: 0 for a stream that decoded cleanly, else the OR of L2S_JPEG_STATUS_*: a bit pattern that is no Huffman code; data that
+ *                ends (at the span's end, or at a marker) before the last block, or no EOI after the scan; a restart marker that is missing or out of
+ *                sequence; a coefficient run past the end of its block; whole bytes of data left over after the last block of the image or of a restart
+ *                interval.  The pixels of such an image are unspecified, and in bounds
+ * An image's bytes do not depend on what else is in the call.  Every loop of the kernels is bounded by counts from the records, never by the data.  The records,
+ * the table sets and the work list reach the device through the workspace, written in stream order from kernel arguments (the carrier of csrc/host_table.h: a
+ * table set alone is 4 040 bytes, the 4 KB of arguments hold none next to anything else): no allocation, no host synchronisation, no copy from host memory; it
+ * works under stream capture.  Refused on the host before anything is launched, with the image and the limit: a record outside the ranges above or outside the
+ * stream buffer; an output offset that is negative, no multiple of 4 or whose image does not fit packed_bytes; two output spans that overlap (rounded up to 4
+ * bytes); stream buffer, packed_out, status and workspace that overlap one another; a workspace smaller than l2s_jpeg_workspace_bytes. */
+typedef struct l2s_jpeg_image { int64_t scan_offset; int32_t scan_bytes, H, W, layout, restart, table_set, eoi, reserved; } l2s_jpeg_image;
+typedef struct l2s_jpeg_huff { uint16_t lut[256]; int32_t maxcode[18]; int32_t valoff[18]; uint8_t vals[256]; } l2s_jpeg_huff;
+/* quant[c]: component c's quantisers, natural order; dc[c] / ac[c]: its table ids (0 / 1); huff[id] the DC tables, huff[2 + id] the AC tables */
+typedef struct l2s_jpeg_tables { uint16_t quant[3][64]; uint8_t dc[4], ac[4]; l2s_jpeg_huff huff[4]; } l2s_jpeg_tables;
+enum { L2S_JPEG_GREY = 0, L2S_JPEG_444 = 1, L2S_JPEG_420 = 2 };
+enum { L2S_JPEG_STATUS_CODE = 1, L2S_JPEG_STATUS_END = 2, L2S_JPEG_STATUS_RESTART = 4, L2S_JPEG_STATUS_RUN = 8, L2S_JPEG_STATUS_EXTRA = 16 };
+int l2s_jpeg_plan(const uint8_t* streams, const int64_t* offsets, const int64_t* sizes, int n, l2s_jpeg_image* images, l2s_jpeg_tables* sets, int sets_cap,
+                  int* n_sets);
+int64_t l2s_jpeg_workspace_bytes(const l2s_jpeg_image* images, int n, int n_sets);
+int l2s_jpeg_decode(const uint8_t* streams, int64_t stream_bytes, const l2s_jpeg_image* images, int n, const l2s_jpeg_tables* sets, int n_sets,
+                    const int64_t* out_offsets, uint8_t* packed_out, int64_t packed_bytes, int32_t* status, void* ws, int64_t ws_bytes, void* stream);
+
 /* VideoExtractor.forward (video.py:76-87): video dev (B,3,T,H,W) -> feat dev (B,T,768), L2-normalised.
  * H = W in {88, 96}. */
 int l2s_encoder_fwd(l2s_model* m, const float* video, int B, int T, int H, int W,

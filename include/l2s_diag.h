@@ -220,6 +220,12 @@ int l2s_op_upload_table(const int32_t* host_words, int64_t n, int32_t* dst, void
  * offsets and the total; fill == 0 is the sizers' mode (no data read; dst must be NULL); with dst the built table is uploaded through the carrier */
 int l2s_op_table_layout(const int32_t* a, int64_t n_a, const int64_t* b, int64_t n_b, int fill, int32_t* dst, int64_t* off_a, int64_t* off_b, int64_t* words,
                         void* stream);
+/* The entropy decoder of csrc/jpeg_decode.hip on the HOST: the host instantiation of the one __host__ __device__ function the entropy kernel runs per lane, over
+ * the records and table sets of l2s_jpeg_plan; streams (4-byte aligned) is a HOST buffer here.  coefs (16-byte aligned, coef_count int16): per image its
+ * blocks x 64 quantised coefficients, image after image - per component a plane of whole MCUs, 64 int16 per block in natural order, the workspace layout;
+ * status (n): the word l2s_jpeg_decode reports.  Corrupt streams are tested through this entry point alone: no device is touched */
+int l2s_op_jpeg_entropy_host(const uint8_t* streams, int64_t stream_bytes, const l2s_jpeg_image* images, int n, const l2s_jpeg_tables* sets, int n_sets,
+                             int16_t* coefs, int64_t coef_count, int32_t* status);
 
 #ifdef __cplusplus
 }

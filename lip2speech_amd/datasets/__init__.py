@@ -13,8 +13,9 @@ from .spectrograms import MelSpec2Audio, MelSpectrogram  # noqa: F401
 from .lrw import LRW  # noqa: F401
 from .augmentation import FaceAugmentation  # noqa: F401
 from .unported import GRID, AVSpeech, WILD  # noqa: F401
-from .device import (PackedAudio, PackedFaces, PackedFrames, device_collate_fn_pad, device_collate_fn_pad_faces,  # noqa: F401
-                     device_collate_fn_pad_raw, faces_item_host)
+from .device import (PackedAudio, PackedFaces, PackedFrames, PackedJpegFrames, device_collate_fn_pad, device_collate_fn_pad_faces,  # noqa: F401
+                     device_collate_fn_pad_jpeg, device_collate_fn_pad_raw, faces_item_host)
+from .jpeg import decode_jpeg_host, parse_jpeg  # noqa: F401
 from .face_utils import align_and_crop_face, face_box_crops  # noqa: F401
 
 MEL_PAD = -11.5129      # ln(1e-5), the floor of the log-mel transform

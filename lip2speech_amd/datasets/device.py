@@ -22,11 +22,18 @@ CPU: what a loader without the device does, and what the kernel is tested agains
 The step before those crops, the rotation of every face-box crop by its eye-line angle (reference: datasets/face_utils.py:12-103): an item that comes as
 `(crops, flip, face_indices, landmarks)` is rotated on the device, by one `l2s_align_faces` call on the same upload before the two resize calls -
 bit-identical to rotating the crops on the host with `face_utils.align_and_crop_face` (tests/test_face_align_gpu.py).
+
+The step before all of these for the loaders that store JPEG byte strings (reference: datasets/lrw/dataset.py:62-70 and the in-the-wild loader): with
+`LRW(..., raw_jpeg=True)` nothing is decoded on the host; `device_collate_fn_pad_jpeg` packs the COMPRESSED strings into one pinned buffer (about 1.7 KB per
+mouth frame instead of 27.6 KB), `PackedJpegFrames.to_device()` uploads it and runs `l2s_jpeg_decode` into a device buffer in `PackedFrames`' layout, then
+`l2s_normalise_pad_frames` - bit-identical to `PackedFrames` on the frames `datasets.jpeg.decode_jpeg_host` (Pillow's bits) decodes
+(tests/test_jpeg_decode_gpu.py).  `PackedFaces` takes faces that are JPEG strings the same way.
 """
 from __future__ import annotations
 
 from typing import List, Sequence, Tuple
 
+import numpy as np
 import torch
 
 from .. import native
@@ -61,6 +68,74 @@ class PackedFrames:
         """-> `(B,3,T,H,W)` fp32 on the device, normalised and zero-padded (T defaults to the longest clip)."""
         dev = self.data.to(device, non_blocking=True)
         return native.normalise_pad_frames(dev, self.offsets, self.frames, self.H, self.W, T)
+
+
+def _jpeg_string(x):
+    """a JPEG stream as a 1-D uint8 numpy array, or None if x is not one: bytes, bytearray, or a uint8 array / tensor of shape (n,) or - what cv2.imencode
+    returns and the corpus files hold - (n, 1)"""
+    if isinstance(x, (bytes, bytearray)):
+        return np.frombuffer(x, dtype=np.uint8)
+    if isinstance(x, torch.Tensor):
+        x = x.numpy() if x.dtype == torch.uint8 and not x.is_cuda else None
+    if isinstance(x, np.ndarray) and x.dtype == np.uint8 and (x.ndim == 1 or (x.ndim == 2 and x.shape[1] == 1)):
+        return np.ascontiguousarray(x).reshape(-1)
+    return None
+
+
+def _pack_streams(strings, pin: bool):
+    """JPEG streams -> (one host buffer that holds them back to back, exactly as they are; their offsets; their sizes)"""
+    sizes = [int(s.size) for s in strings]
+    offsets = [0] * len(sizes)
+    for i in range(1, len(sizes)):
+        offsets[i] = offsets[i - 1] + sizes[i - 1]
+    buf = torch.empty(sum(sizes), dtype=torch.uint8)
+    if pin and torch.cuda.is_available():
+        buf = buf.pin_memory()
+    view = buf.numpy()
+    for s, o, n in zip(strings, offsets, sizes):
+        view[o:o + n] = s
+    return buf, offsets, sizes
+
+
+class PackedJpegFrames:
+    """B clips of JPEG byte strings (bytes or 1-D uint8 arrays; one frame size per batch, H W a multiple of 4 so that a clip's decoded frames follow one
+    another on 4-byte boundaries) packed back to back, COMPRESSED, in one host buffer, and planned once (`native.jpeg_plan`: headers, table sets; a stream
+    outside the supported subset raises here, with its index).  `offsets` / `frames` / `H` / `W` are those of `PackedFrames` on the decoded clips;
+    `image_offsets`: every frame's offset in that layout."""
+
+    def __init__(self, clips: Sequence, pin: bool = True):
+        assert len(clips) > 0, "at least one clip"
+        strings = [_jpeg_string(s) for c in clips for s in c]
+        assert all(s is not None for s in strings), "a frame is a JPEG byte string: bytes or a 1-D uint8 array"
+        assert len(strings) > 0, "at least one frame"
+        self.frames: List[int] = [len(c) for c in clips]
+        self.data, self.stream_offsets, self.stream_sizes = _pack_streams(strings, pin)
+        self.plan = native.jpeg_plan(self.data, self.stream_offsets, self.stream_sizes)
+        self.H, self.W = self.plan.sizes[0]
+        assert all(hw == (self.H, self.W) for hw in self.plan.sizes), "one crop size per batch"
+        assert (self.H * self.W) % 4 == 0, "H W must be a multiple of 4: a clip's frames follow one another without gaps, each on a 4-byte boundary"
+        frame_bytes = self.H * self.W * 3
+        self.offsets: List[int] = []
+        self.image_offsets: List[int] = []
+        total = 0
+        for n in self.frames:
+            self.offsets.append(total)
+            self.image_offsets.extend(total + t * frame_bytes for t in range(n))
+            total += n * frame_bytes
+        self.packed_bytes = total
+
+    @property
+    def lengths(self) -> torch.Tensor:
+        return torch.tensor(self.frames)
+
+    def decode(self, device="cuda") -> torch.Tensor:
+        """-> the decoded clips on the device, the bytes of `PackedFrames(decoded clips).data`: ONE upload of the compressed bytes, one `l2s_jpeg_decode`"""
+        dev = self.data.to(device, non_blocking=True)
+        return native.jpeg_decode(dev, self.plan, self.image_offsets, packed_bytes=self.packed_bytes)
+
+    def to_device(self, device="cuda", T: int = None) -> torch.Tensor:
+        """-> `(B,3,T,H,W)` fp32 on the device, normalised and zero-padded (T defaults to the longest clip): the bits of `PackedFrames.to_device`"""
+        return native.normalise_pad_frames(self.decode(device), self.offsets, self.frames, self.H, self.W, T)
 
 
 class PackedAudio:
@@ -153,10 +228,21 @@ class PackedFaces:
     An item may also be `(crops, flip, face_indices, landmarks)`: the UNROTATED face-box crops and the landmarks of the same frames
     (`face_utils.face_box_crops`).  Its images get one row each in `align_jobs`, the table of `l2s_align_faces` (rows `(offset, H, W, m0, .., m5)` with
     the map `rotation_inverse_map(eye_angle_degrees(landmarks), H, W)`), and `to_device` rotates them on the device before the two resize calls - what
-    `face_utils.align_and_crop_face` does per frame on the host, to the bit."""
+    `face_utils.align_and_crop_face` does per frame on the host, to the bit.
+
+    A face may also be a JPEG byte string (bytes or a 1-D uint8 array): its size comes from its header, the strings travel compressed in a second buffer
+    (`jpeg_data`, planned once: `jpeg_plan`; `jpeg_offsets` their images' offsets in the packed layout), and `to_device` decodes them into the packed buffer
+    with one `l2s_jpeg_decode` before anything else runs; the job tables are those of the decoded faces."""
 
     def __init__(self, items: Sequence, pin: bool = True):
         assert len(items) > 0, "at least one item"
+        strings = [s for s in (_jpeg_string(f) for item in items for f in item[0]) if s is not None]
+        self.jpeg_data = self.jpeg_plan = None
+        self.jpeg_offsets: List[int] = []
+        if strings:
+            self.jpeg_data, stream_offsets, stream_sizes = _pack_streams(strings, pin)
+            self.jpeg_plan = native.jpeg_plan(self.jpeg_data, stream_offsets, stream_sizes)
+        jpeg_sizes = iter(self.jpeg_plan.sizes if strings else ())
         self.frames: List[int] = []
         self.images: List[Tuple[int, int, int]] = []       # (offset, H, W) of every image, in item order
         self.flips: List[int] = []
@@ -173,8 +259,12 @@ class PackedFaces:
             self.frames.append(len(faces))
             self.flips.append(int(bool(flip)))
             for t, f in enumerate(faces):
-                f = _chw(f)
-                H, W = int(f.shape[1]), int(f.shape[2])
+                if _jpeg_string(f) is not None:
+                    f, (H, W) = None, next(jpeg_sizes)
+                    self.jpeg_offsets.append(total)
+                else:
+                    f = _chw(f)
+                    H, W = int(f.shape[1]), int(f.shape[2])
                 assert 1 <= H <= 4096 and 1 <= W <= 4096, "a face is at most 4096 x 4096"
                 chw.append(f)
                 self.images.append((total, H, W))
@@ -190,7 +280,8 @@ class PackedFaces:
         if pin and torch.cuda.is_available():
             buf = buf.pin_memory()
         for f, (o, H, W) in zip(chw, self.images):
-            buf[o:o + H * W * 3] = f.permute(1, 2, 0).reshape(-1)
+            if f is not None:
+                buf[o:o + H * W * 3] = f.permute(1, 2, 0).reshape(-1)
         self.data = buf
 
     @property
@@ -206,7 +297,12 @@ class PackedFaces:
         """-> `(video (B,3,T,size,size), face_crops (B,2,3,160,160))` fp32 on the device from ONE host-to-device copy and two calls; clips shorter
         than T (default: the longest clip) are zero-padded.  Items that came with landmarks are rotated first, by one `l2s_align_faces` call on the
         upload; the images of the other items of such a batch are carried over as they are."""
-        dev = self.data.to(device, non_blocking=True)
+        if self.jpeg_plan is None:
+            dev = self.data.to(device, non_blocking=True)
+        else:                                              # the compressed faces: decoded into the packed buffer, next to the faces that came decoded (if any)
+            some = len(self.jpeg_offsets) < len(self.images)
+            dev = native.jpeg_decode(self.jpeg_data.to(device, non_blocking=True), self.jpeg_plan, self.jpeg_offsets,
+                                     out=self.data.to(device, non_blocking=True) if some else None, packed_bytes=self.data.numel())
         if self.align_jobs:
             dev = native.align_faces(dev, self.align_jobs, out=dev.clone() if len(self.align_jobs) < len(self.images) else None)
         B = len(self.frames)
@@ -225,6 +321,20 @@ def device_collate_fn_pad_faces(batch):
     faces = PackedFaces([b[0] for b in batch])
     audio = PackedAudio([b[1] for b in batch])
     out = ((faces, faces.lengths), audio, audio, faces)
+    return out + (tuple(b[4] for b in batch),) if with_paths else out
+
+
+def device_collate_fn_pad_jpeg(batch):
+    """`device_collate_fn_pad_raw` for `LRW(raw_jpeg=True, raw_audio=True)`, whose items carry JPEG byte strings: the tuple is
+    `((PackedJpegFrames, lengths), packed_audio, packed_audio, faces[, paths])`.  `faces`: ONE `PackedFaces` of the items' two drawn face strings
+    (`faces.to_device()[1]` is the `(B,2,3,160,160)` face crops), or, for a loader without face files, the stacked zeros as before."""
+    with_paths = len(batch[0]) == 5
+    frames = PackedJpegFrames([b[0] for b in batch])
+    audio = PackedAudio([b[1] for b in batch])
+    have = [not isinstance(b[3], torch.Tensor) for b in batch]
+    assert all(have) or not any(have), "either every item of a batch has a face file or none has"
+    faces = PackedFaces([(b[3], False, (0, 1)) for b in batch]) if all(have) else torch.stack([b[3] for b in batch], dim=0)
+    out = ((frames, frames.lengths), audio, audio, faces)
     return out + (tuple(b[4] for b in batch),) if with_paths else out
 
 

@@ -25,12 +25,17 @@ IMAGENET_MEAN = (0.485, 0.456, 0.406)
 IMAGENET_STD = (0.229, 0.224, 0.225)
 
 
+def load_jpeg_strings(path: str) -> list:
+    """-> the file's JPEG byte strings, undecoded, one `bytes` per frame"""
+    with bz2.BZ2File(path, "r") as f:
+        blobs = pickle.load(f)
+    return [np.asarray(b).tobytes() for b in blobs]
+
+
 def load_frames(path: str) -> np.ndarray:
     """-> uint8 (T, H, W, 3) RGB"""
     from PIL import Image
-    with bz2.BZ2File(path, "r") as f:
-        blobs = pickle.load(f)
-    return np.stack([np.asarray(Image.open(io.BytesIO(np.asarray(b).tobytes())).convert("RGB")) for b in blobs])
+    return np.stack([np.asarray(Image.open(io.BytesIO(b)).convert("RGB")) for b in load_jpeg_strings(path)])
 
 
 def normalise_mouth(frames_u8: np.ndarray) -> torch.Tensor:
@@ -50,16 +55,19 @@ def face_recog_resize(frame_u8: torch.Tensor) -> torch.Tensor:
 
 class LRW(Dataset):
     def __init__(self, rootpth, face_size=(96, 96), mode="train", demo=False, duration=1, face_augmentation=None, *args, raw_frames=False, raw_audio=False, raw_faces=False,
-                 **kwargs):
+                 raw_jpeg=False, **kwargs):
         """`raw_frames=True` (an extension): items carry the decoded uint8 clip `(T,H,W,3)` instead of the normalised fp32 one - the
         normalisation then runs on the device (`datasets.device.device_collate_fn_pad` + `PackedFrames.to_device`).  `raw_audio=True` (likewise):
         the CPU mel transform is skipped and the items' melspec slot is `None` - the targets then come from the device
         (`datasets.device.device_collate_fn_pad_raw` + `PackedAudio.to_device`).  `raw_faces=True` (likewise): the item's face slot carries the two
         drawn face frames as they were decoded, uint8 `(2,3,H,W)`, instead of the resized fp32 `face_crop` - the 160 x 160 resize then runs on the
-        device (`datasets.device.PackedFaces`, `l2s_resize_normalise`); without a face file the slot is the usual zeros.  Extra positional / keyword arguments are accepted and ignored
+        device (`datasets.device.PackedFaces`, `l2s_resize_normalise`); without a face file the slot is the usual zeros.  `raw_jpeg=True` (likewise): nothing is
+        decoded on the host - the item's first element is the list of the clip's mouth JPEG byte strings and its face slot the list of the two drawn faces'
+        strings (the other 27 are never decoded; without a face file the usual zeros); the decode then runs on the device
+        (`datasets.device.device_collate_fn_pad_jpeg`, `PackedJpegFrames`, `PackedFaces`, `l2s_jpeg_decode`).  Extra positional / keyword arguments are accepted and ignored
         (the reference forwards them to `Dataset.__init__`, which takes none)."""
         super().__init__()
-        self.raw_frames, self.raw_audio, self.raw_faces = raw_frames, raw_audio, raw_faces
+        self.raw_frames, self.raw_audio, self.raw_faces, self.raw_jpeg = raw_frames, raw_audio, raw_faces, raw_jpeg
         assert mode in ("train", "test", "val")
         self.rootpth, self.mode, self.demo = rootpth, mode, demo
         self.face_size, self.duration = face_size, duration
@@ -81,15 +89,21 @@ class LRW(Dataset):
 
     def __getitem__(self, idx):
         face_path, mouth_path, audio_path = self.items[idx]
-        frames = load_frames(mouth_path)
-        mouth = torch.from_numpy(np.ascontiguousarray(frames)) if self.raw_frames else normalise_mouth(frames)
+        if self.raw_jpeg:
+            mouth = load_jpeg_strings(mouth_path)
+        else:
+            frames = load_frames(mouth_path)
+            mouth = torch.from_numpy(np.ascontiguousarray(frames)) if self.raw_frames else normalise_mouth(frames)
         speech = torch.from_numpy(np.load(audio_path)["data"][np.newaxis])
         melspec = None if self.raw_audio else self.melspec_g(speech).squeeze(0)
         # two random face frames resized to 160x160 feed the third-party face tower (dataset.py:139-141).  The tower is outside this path,
         # but the draw is part of an epoch's RNG consumption: `torch.rand(2)` is taken exactly where the reference takes it, face file or not
         draw = torch.rand(2)
         face_crop = torch.zeros(2, 3, 160, 160)
-        if os.path.exists(face_path):
+        if os.path.exists(face_path) and self.raw_jpeg:
+            blobs = load_jpeg_strings(face_path)
+            face_crop = [blobs[int(i)] for i in (draw * len(blobs)).int()]
+        elif os.path.exists(face_path):
             faces = torch.from_numpy(np.ascontiguousarray(load_frames(face_path))).permute(0, 3, 1, 2)
             drawn = [faces[int(i)] for i in (draw * len(faces)).int()]
             face_crop = torch.stack(drawn if self.raw_faces else [face_recog_resize(f) for f in drawn], dim=0)

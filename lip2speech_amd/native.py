@@ -31,6 +31,7 @@ ABI_SYMBOLS = (
     "l2s_min_T", "l2s_workspace_bytes", "l2s_state_floats", "l2s_state_offset",
     "l2s_mel_frames", "l2s_mel_targets_workspace_bytes", "l2s_mel_targets",
     "l2s_resize_check", "l2s_resize_normalise", "l2s_align_check", "l2s_align_faces",
+    "l2s_jpeg_plan", "l2s_jpeg_workspace_bytes", "l2s_jpeg_decode",
     "l2s_encoder_fwd", "l2s_normalise_pad_frames", "l2s_build_visual", "l2s_decoder_prologue", "l2s_decode_steps", "l2s_postnet",
     "l2s_workspace_bytes_masked", "l2s_masked_bilstm_plan", "l2s_inference_masked", "l2s_forward_eval_masked", "l2s_decoder_prologue_masked", "l2s_decode_steps_masked",
     "l2s_ragged_plan", "l2s_workspace_bytes_ragged", "l2s_inference_ragged",
@@ -55,7 +56,7 @@ ABI_SYMBOLS = (
 DIAG_SYMBOLS = (
     "l2s_op_gemm", "l2s_op_conv1d", "l2s_op_gemm_ex", "l2s_op_conv1d_ex", "l2s_op_conv1d_bwd", "l2s_op_frontend", "l2s_op_launch_chain", "l2s_op_launch_chain2", "l2s_op_skinny_timeline", "l2s_op_attn_timeline", "l2s_op_flat_timeline", "l2s_op_pdecode_timeline", "l2s_op_gemm_x3_timeline", "l2s_op_fused_unit_timeline", "l2s_op_lstm_cell_chain", "l2s_op_step_attn_chain", "l2s_op_stamp_log", "l2s_op_skinny_form", "l2s_op_step_site", "l2s_op_skinny", "l2s_op_skinny_hoist",
     "l2s_op_face_conv2d", "l2s_op_face_taps", "l2s_op_speaker_taps", "l2s_op_speaker_taps_packed", "l2s_op_encoder_taps",
-    "l2s_op_gemm_bwd", "l2s_op_gemm_bwd_recorder", "l2s_op_upload_table", "l2s_op_table_layout",
+    "l2s_op_gemm_bwd", "l2s_op_gemm_bwd_recorder", "l2s_op_upload_table", "l2s_op_table_layout", "l2s_op_jpeg_entropy_host",
 )
 
 # run-time options only the diagnostic build accepts (block-form A/B switches of the same arithmetic, include/l2s_diag.h)
@@ -78,6 +79,21 @@ class ResizeJob(ctypes.Structure):
 class AlignJob(ctypes.Structure):
     """`l2s_align_job` (include/l2s.h): an image of the packed buffer and the six float64 of its destination-to-source map"""
     _fields_ = [("offset", _i64), ("H", ctypes.c_int32), ("W", ctypes.c_int32), ("m", ctypes.c_double * 6)]
+
+
+class JpegImage(ctypes.Structure):
+    """`l2s_jpeg_image` (include/l2s.h): what `l2s_jpeg_plan` finds in one stream's headers"""
+    _fields_ = [("scan_offset", _i64)] + [(k, ctypes.c_int32) for k in ("scan_bytes", "H", "W", "layout", "restart", "table_set", "eoi", "reserved")]
+
+
+class JpegHuff(ctypes.Structure):
+    """`l2s_jpeg_huff` (include/l2s.h): the derived lookup of one Huffman table"""
+    _fields_ = [("lut", ctypes.c_uint16 * 256), ("maxcode", ctypes.c_int32 * 18), ("valoff", ctypes.c_int32 * 18), ("vals", ctypes.c_uint8 * 256)]
+
+
+class JpegTables(ctypes.Structure):
+    """`l2s_jpeg_tables` (include/l2s.h): a table set - per component its quantisers and table ids, and the four Huffman tables"""
+    _fields_ = [("quant", (ctypes.c_uint16 * 64) * 3), ("dc", ctypes.c_uint8 * 4), ("ac", ctypes.c_uint8 * 4), ("huff", JpegHuff * 4)]
 
 
 class SkinnyGroup(ctypes.Structure):
@@ -106,6 +122,8 @@ class GemmBwdRecord(ctypes.Structure):
 RESIZE_MOUTH, RESIZE_FACE = 0, 1        # L2S_RESIZE_MOUTH / L2S_RESIZE_FACE
 RESIZE_JOBS_PER_LAUNCH = 240              # L2S_RESIZE_JOBS_PER_LAUNCH: output slots whose table one launch carries in its kernel arguments
 ALIGN_JOBS_PER_LAUNCH = 56                # L2S_ALIGN_JOBS_PER_LAUNCH: 64-byte align jobs whose table one launch carries in its kernel arguments
+JPEG_GREY, JPEG_444, JPEG_420 = 0, 1, 2   # L2S_JPEG_*: an image's layout
+JPEG_STATUS_CODE, JPEG_STATUS_END, JPEG_STATUS_RESTART, JPEG_STATUS_RUN, JPEG_STATUS_EXTRA = 1, 2, 4, 8, 16      # L2S_JPEG_STATUS_*
 
 
 def _load(path: str) -> ctypes.CDLL:
@@ -289,6 +307,13 @@ def _bind(L: ctypes.CDLL) -> None:
         _ajobs = ctypes.POINTER(AlignJob)
         L.l2s_align_check.argtypes = [_ajobs, _i, _i64]
         L.l2s_align_faces.argtypes = [_vp, _i64, _ajobs, _i, _vp, _vp]
+    # device-side JPEG decode (include/l2s.h): likewise absent from a library built before it
+    if hasattr(L, "l2s_jpeg_decode"):
+        _imgs, _sets = ctypes.POINTER(JpegImage), ctypes.POINTER(JpegTables)
+        L.l2s_jpeg_plan.argtypes = [_vp, ctypes.POINTER(_i64), ctypes.POINTER(_i64), _i, _imgs, _sets, _i, ctypes.POINTER(_i)]
+        L.l2s_jpeg_workspace_bytes.argtypes = [_imgs, _i, _i]
+        L.l2s_jpeg_workspace_bytes.restype = _i64
+        L.l2s_jpeg_decode.argtypes = [_vp, _i64, _imgs, _i, _sets, _i, ctypes.POINTER(_i64), _vp, _i64, _vp, _vp, _i64, _vp]
     # the voice tower over clips of unequal length (include/l2s.h): likewise absent from a library built before it
     # (tools/speaker_packed/time_speaker_packed.py times one next to this build)
     if hasattr(L, "l2s_speaker_encoder_packed"):
@@ -331,6 +356,8 @@ def _bind_diag(L: ctypes.CDLL) -> None:
     if hasattr(L, "l2s_op_upload_table"):
         L.l2s_op_upload_table.argtypes = [_vp, _i64, _vp, _vp]
         L.l2s_op_table_layout.argtypes = [_vp, _i64, _vp, _i64, _i, _vp, ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(_i64), _vp]
+    if hasattr(L, "l2s_op_jpeg_entropy_host"):
+        L.l2s_op_jpeg_entropy_host.argtypes = [_vp, _i64, ctypes.POINTER(JpegImage), _i, ctypes.POINTER(JpegTables), _i, _vp, _i64, _vp]
 
 
 def check(rc: int, L: Optional[ctypes.CDLL] = None) -> None:
@@ -1200,6 +1227,82 @@ def align_faces(packed_u8: torch.Tensor, jobs, out: Optional[torch.Tensor] = Non
     assert out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and out.shape == packed_u8.shape and out.device == packed_u8.device
     check(lib().l2s_align_faces(packed_u8.data_ptr(), packed_u8.numel(), _align_jobs(jobs), len(jobs), out.data_ptr(), _stream()))
     return out
+
+
+class JpegPlan:
+    """What `l2s_jpeg_plan` found in n streams of one host buffer: `images` (a ctypes array of n `JpegImage`), `sets` (of `n_sets` `JpegTables`), and the
+    buffer's size.  `sizes`: `(H, W)` per image; `blocks`: 8 x 8 blocks per image, whole MCUs of every component."""
+
+    def __init__(self, images, sets, n_sets: int, stream_bytes: int):
+        self.images, self.sets, self.n, self.n_sets, self.stream_bytes = images, sets, len(images), int(n_sets), int(stream_bytes)
+
+    @property
+    def sizes(self):
+        return [(int(r.H), int(r.W)) for r in self.images]
+
+    @property
+    def blocks(self):
+        out = []
+        for r in self.images:
+            m = 16 if r.layout == JPEG_420 else 8
+            out.append(((r.H + m - 1) // m) * ((r.W + m - 1) // m) * {JPEG_GREY: 1, JPEG_444: 3, JPEG_420: 6}[int(r.layout)])
+        return out
+
+    def workspace_bytes(self) -> int:
+        nb = lib().l2s_jpeg_workspace_bytes(self.images, self.n, self.n_sets)
+        check(0 if nb >= 0 else 1)
+        return int(nb)
+
+
+def jpeg_plan(streams, offsets, sizes) -> JpegPlan:
+    """`l2s_jpeg_plan` (pure host): `streams`, a uint8 host buffer (numpy array or CPU tensor) that holds n JPEG streams, stream i the `sizes[i]` bytes at
+    `offsets[i]` -> their records and deduplicated table sets.  Raises with the image and the reason for a stream outside the supported subset."""
+    buf = streams.numpy() if isinstance(streams, torch.Tensor) else np.asarray(streams)
+    assert buf.dtype == np.uint8 and buf.ndim == 1 and buf.flags.c_contiguous, "the stream buffer is a contiguous 1-D uint8 array"
+    n = len(offsets)
+    assert len(sizes) == n and all(0 <= int(o) and 0 <= int(z) and int(o) + int(z) <= buf.size for o, z in zip(offsets, sizes)), "streams inside the buffer"
+    images, sets, n_sets = (JpegImage * n)(), np.empty(max(n, 1) * ctypes.sizeof(JpegTables), dtype=np.uint8), _i(0)
+    check(lib().l2s_jpeg_plan(buf.ctypes.data, _int64s(offsets), _int64s(sizes), n, images, sets.ctypes.data_as(ctypes.POINTER(JpegTables)), n, ctypes.byref(n_sets)))
+    kept = (JpegTables * max(n_sets.value, 1)).from_buffer_copy(sets[:max(n_sets.value, 1) * ctypes.sizeof(JpegTables)].tobytes())
+    return JpegPlan(images, kept, n_sets.value, buf.size)
+
+
+def jpeg_decode(streams_u8: torch.Tensor, plan: JpegPlan, out_offsets, out: Optional[torch.Tensor] = None, packed_bytes: Optional[int] = None,
+                status: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """`l2s_jpeg_decode`: the planned streams, uploaded as they are, -> image i as interleaved uint8 `(H_i, W_i, 3)` at byte `out_offsets[i]` (a multiple
+    of 4) of the packed buffer `out` (default: a new one of `packed_bytes`, default the last image's end rounded up to 4; bytes outside the images' spans
+    then are uninitialised) - the layout `normalise_pad_frames`, `resize_normalise` and `align_faces` read.  `status`: int32 `(n)` on the device, 0 per
+    stream that decoded cleanly."""
+    assert streams_u8.is_cuda and streams_u8.dtype == torch.uint8 and streams_u8.is_contiguous() and streams_u8.dim() == 1 and streams_u8.numel() == plan.stream_bytes
+    assert len(out_offsets) == plan.n
+    if out is None:
+        if packed_bytes is None:
+            packed_bytes = max([(int(o) + H * W * 3 + 3) // 4 * 4 for o, (H, W) in zip(out_offsets, plan.sizes)] or [0])
+        out = torch.empty(int(packed_bytes), dtype=torch.uint8, device=streams_u8.device)
+    assert out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and out.dim() == 1 and out.device == streams_u8.device
+    assert status is None or (status.is_cuda and status.dtype == torch.int32 and status.is_contiguous() and status.numel() == plan.n)
+    ws_bytes = plan.workspace_bytes()
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=streams_u8.device)
+    check(lib().l2s_jpeg_decode(streams_u8.data_ptr(), streams_u8.numel(), plan.images, plan.n, plan.sets, plan.n_sets, _int64s(out_offsets), out.data_ptr(),
+                                out.numel(), _ptr(status), ws.data_ptr(), ws_bytes, _stream()))
+    return out
+
+
+def op_jpeg_entropy_host(streams, plan: JpegPlan, sentinel_words: int = 0):
+    """`l2s_op_jpeg_entropy_host` (diagnostic library, no device): the entropy decoder's host instantiation over the plan's records -> `(coefs, status)`, numpy:
+    int16 `(sum of blocks, 64)` image after image, int32 `(n)`.  With `sentinel_words` also the int16 words placed after the coefficient buffer, as they are after
+    the call (written as 0x5A5A before it)."""
+    buf = streams.numpy() if isinstance(streams, torch.Tensor) else np.asarray(streams)
+    assert buf.dtype == np.uint8 and buf.ndim == 1 and buf.flags.c_contiguous and buf.size == plan.stream_bytes and buf.ctypes.data % 4 == 0
+    count = sum(plan.blocks) * 64
+    raw = np.zeros(count * 2 + sentinel_words * 2 + 64, dtype=np.uint8)
+    skip = (-raw.ctypes.data) % 64                     # the coefficient buffer starts on a 64-byte boundary
+    coefs = raw[skip:skip + (count + sentinel_words) * 2].view(np.int16)
+    coefs[count:] = 0x5A5A
+    status = np.zeros(max(plan.n, 1), dtype=np.int32)
+    _dcheck(diag().l2s_op_jpeg_entropy_host(buf.ctypes.data, buf.size, plan.images, plan.n, plan.sets, plan.n_sets, coefs.ctypes.data, count, status.ctypes.data))
+    out = (coefs[:count].reshape(-1, 64).copy(), status[:plan.n])
+    return out + (coefs[count:].copy(),) if sentinel_words else out
 
 
 MEL_PAD = -11.5129      # ln(1e-5) as the collates write it (datasets.MEL_PAD)
