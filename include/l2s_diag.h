@@ -35,6 +35,8 @@ extern "C" {
  *   "flat_half"         (1)  the step's first launch on four-wave half-CU blocks when chains overlap; 2 = always, 0 = never
  *   "half_min_mts"      (12) with "lstm_x3" >= 3 and chains overlapping: an all-LSTM launch takes the half-CU 4x2 / shared-panel form from this many 16-row tiles on
  *   "trunk_chain"       (1)  the stride-1 units of ShuffleNet stages 2 and 3 as ONE launch per stage (the map stays on chip between the units); 2 = stage 4 too, 0 = one launch per unit
+ *   "post_wino"         (1)  post-net layers 1-3 (Conv1d 512 -> 512, 5 taps) in their Winograd F(4,5) form - input transform, eight K = 512 products in one grouped
+ *                            split-bf16 launch, output transform - on the plain full-range route: 1 = from 4 096 rows per batch on, 2 = at any row count, 0 = never
  *   "frontend_solo"     (0)  when chains overlap, the front-end conv one block per CU (an LDS pad) so that other chains' step kernels run beside it: measured -8 %, off
  *   "flat_xcd"          (1)  the step's first launch with an XCD-affine block -> tile map (an XCD = one row half x one column quarter of a group); 0 = row-major
  *   "attn_skip0"        (1)  when chains overlap, attention blocks fetch only the projected-value rows whose soft-max weight is not exactly zero; 2 = always, 0 = never
@@ -220,6 +222,9 @@ int l2s_op_upload_table(const int32_t* host_words, int64_t n, int32_t* dst, void
  * offsets and the total; fill == 0 is the sizers' mode (no data read; dst must be NULL); with dst the built table is uploaded through the carrier */
 int l2s_op_table_layout(const int32_t* a, int64_t n_a, const int64_t* b, int64_t n_b, int fill, int32_t* dst, int64_t* off_a, int64_t* off_b, int64_t* words,
                         void* stream);
+/* The matrices of the post-net's Winograd F(4,5) route (csrc/post_wino.h; option "post_wino"), row-major doubles: AT (4 x 8), G (8 x 5), BT (8 x 8), with
+ * AT ((G g) * (BT d)) = the four outputs y[i] = sum_k g[k] d[i + k] of a 5-tap filter over an 8-frame tile.  Pure host code: no device is touched */
+int l2s_op_post_wino_matrices(double* AT, double* G, double* BT);
 /* The entropy decoder of csrc/jpeg_decode.hip on the HOST: the host instantiation of the one __host__ __device__ function the entropy kernel runs per lane, over
  * the records and table sets of l2s_jpeg_plan; streams (4-byte aligned) is a HOST buffer here.  coefs (16-byte aligned, coef_count int16): per image its
  * blocks x 64 quantised coefficients, image after image - per component a plane of whole MCUs, 64 int16 per block in natural order, the workspace layout;

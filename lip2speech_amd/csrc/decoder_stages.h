@@ -5,6 +5,7 @@
 #pragma once
 #include "l2s_common.h"
 #include "l2s_model.h"
+#include "post_wino.h"
 
 namespace l2s {
 
@@ -155,6 +156,19 @@ inline GemmP post_layer(const Weights& w, int layer, const float* in, float* out
     if (layer >= 1 && layer <= 3) { p.R1 = in; p.ldr1 = 512; }
     if (layer == 4) { p.R1 = mel; p.ldr1 = NM; p.c_tr_T = S; }
     return p;
+}
+// layers 1-3 in their Winograd F(4,5) form (post_wino.h): the eight point-wise products M_p = V_p U_p^T, rows = tile rows (clips x ceil(S / 4)), N = K = 512,
+// plain store.  Always the split-bf16 family (x3 bit 8); planes: the U_p's bf16 planes travel too
+inline GemmBatch post_wino_products(const Weights& w, int layer, const float* V, float* M, int rows, bool planes) {
+    GemmBatch gb{};
+    for (int p = 0; p < WINO_P; ++p) {
+        GemmP& g = gb.p[p];
+        g = gemm_plain(V + (int64_t)p * rows * 512, 512, wino_u(w.post_wino[layer], 512, p), M + (int64_t)p * rows * 512, 512, rows, 512, 512);
+        g.x3 |= 8;
+        if (planes) g.W3 = wino_u3(w.post_wino[layer], 512, p);
+    }
+    gb.count = WINO_P;
+    return gb;
 }
 
 }  // namespace l2s

@@ -587,7 +587,7 @@ bool gemm_x3_member_ok(const GemmP& p) {
                      (p.a_split % 4 == 0) && (p.a_gap % 4 == 0) && (p.taps == 1 || p.Cin >= XK) &&
                      (int64_t)((p.M + p.Tout - 1) / p.Tout) * p.Tin * p.lda * 4 < (1ll << 31) && (int64_t)p.N * (p.ldw ? p.ldw : p.K) * 4 < (1ll << 31);
     if (!ok4 || p.stats) return false;
-    if (p.x3 & 2) return true;                                 // forced (operator tests run every addressable shape)
+    if (p.x3 & (2 | 8)) return true;                           // forced (operator tests run every addressable shape; the Winograd products of the post-net)
     const int m_unit = p.M / (p.x3_group > 1 ? p.x3_group : 1);
     const int64_t t_unit = (int64_t)((m_unit + XM - 1) / XM) * ((p.N + XN - 1) / XN);
     // short K (the post-net's first layer: K = 400; conv_last: K = 464) only pays with many rows per batch: 9600 x 512 x 400 runs 42 us against 52 on
@@ -604,7 +604,7 @@ bool gemm_x3_eligible(const GemmBatch& b) {
         const int m_unit = p.M / (p.x3_group > 1 ? p.x3_group : 1);                    // rows of ONE batch of a grouped launch
         tiles += (int64_t)((m_unit + XM - 1) / XM) * ((p.N + XN - 1) / XN);
     }
-    return tiles >= (b.count > 1 ? 150 : 100) || (b.p[0].x3 & 2);
+    return tiles >= (b.count > 1 ? 150 : 100) || (b.p[0].x3 & (2 | 8));
 }
 
 #ifdef L2S_DIAG      // the stamped measurement builds exist in libl2s_diag.so only (include/l2s_diag.h l2s_op_gemm_x3_timeline)

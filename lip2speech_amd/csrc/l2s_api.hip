@@ -10,6 +10,7 @@
 #include "pdecode.h"
 #include "decode_step.h"
 #include "decoder_stages.h"
+#include "post_wino.h"
 
 #include <algorithm>
 #include <cmath>
@@ -53,7 +54,8 @@ int set_option_field(Options& o, const char* name, int value) {
         {"skinny_static", &Options::skinny_static}, {"skinny_sized", &Options::skinny_sized}, {"skinny_split", &Options::skinny_split},
         {"skinny_split8", &Options::skinny_split8}, {"skinny_rc", &Options::rc_shape}, {"skinny_rc_jb", &Options::rc_jb}, {"skinny_rc_multi", &Options::rc_shape_multi},
         {"skinny_flat", &Options::skinny_flat}, {"hoist_vproj", &Options::hoist_vproj}, {"attn_lds", &Options::attn_lds}, {"flat_half", &Options::flat_half},
-        {"half_min_mts", &Options::half_min_mts}, {"gemm_x3_dma", &Options::gemm_x3_dma}, {"trunk_chain", &Options::trunk_chain}, {"frontend_solo", &Options::frontend_solo}, {"flat_xcd", &Options::flat_xcd}, {"attn_skip0", &Options::attn_skip0}};
+        {"half_min_mts", &Options::half_min_mts}, {"gemm_x3_dma", &Options::gemm_x3_dma}, {"trunk_chain", &Options::trunk_chain}, {"frontend_solo", &Options::frontend_solo}, {"flat_xcd", &Options::flat_xcd}, {"attn_skip0", &Options::attn_skip0},
+        {"post_wino", &Options::post_wino}};
     for (auto& t : diag)
         if (!std::strcmp(name, t.name)) { o.*(t.field) = value; return 0; }
 #endif
@@ -182,7 +184,24 @@ static int64_t decode_ws_floats(int B) {
     return Bp * (512 * 4 + 512 * 2 + 512 + 256 * 4 + 96) + (int64_t)B * (512 + 256 + 256) + step_alpha_floats(B) + 64 * 25 + (B + 2 + 64) /* EsCtl */ + (B <= 8 ? pdecode_ws_bytes(B) / 4 + 64 : 0);
 }
 constexpr int POST_TAPSPLIT_ROWS = 640;      // a batch with at most this many post-net rows (one or two clips of 300 frames) runs its Conv1d layers one K slice per tap
-static int64_t postnet_ws_floats(int B, int S) { return (int64_t)B * S * 512 * ((int64_t)B * S <= POST_TAPSPLIT_ROWS * MAX_GROUP ? 9 : 4) + 64 * 7; }
+constexpr int POST_WINO_ROWS = 4096;         // a batch with at least this many post-net rows runs layers 1-3 in their Winograd F(4,5) form (option "post_wino")
+// the Winograd route's V and M: eight point planes of B * ceil(S / 4) tile rows each - 2x a layer buffer apiece, rounded up to whole tiles
+static int64_t post_wino_floats(int B, int S) { return (int64_t)WINO_P * B * wino_tiles(S) * 512; }
+// does postnet_run take the Winograd route for these rows?  Decided on the rows of ONE batch, as the tap split is, so that a batch meets the same arithmetic alone
+// and in a group (a model with "overlap_postnet" keeps the direct layer: postnet_run is where its windowed route lands under profiling, graphs or a teacher)
+static bool post_wino_route(const l2s_model* m, int B, int S) {
+    return !m->opt.infer_bf16 && m->opt.gemm_x3 && !m->opt.overlap_postnet && m->w.post_wino[1] &&
+           (m->opt.post_wino >= 2 || (m->opt.post_wino == 1 && (int64_t)B * S / gemm_x3_group() >= POST_WINO_ROWS));
+}
+// Option "early_stop": how far past a clip's stop crossing the loop must decode so that the kept frames of the post-net have the bits of the full call.  A
+// direct layer's frame j reads j - 2 .. j + 2 (ES_MARGIN = 5 x 2); a Winograd layer's tile mixes its eight input frames in every point plane, so in bits
+// frame j depends on up to five frames either side: 2 + 3 x 5 + 2 when the call's post-net takes that route.  Thread-local, set by l2s_inference's body
+constexpr int ES_MARGIN_WINO = 2 * (ES_POST_TAPS / 2) + 3 * (WINO_P - WINO_M + 1);
+static int& es_margin() { static thread_local int margin = ES_MARGIN; return margin; }
+struct EsMarginScope { int prev; explicit EsMarginScope(int v) : prev(es_margin()) { es_margin() = v; } ~EsMarginScope() { es_margin() = prev; } };
+static int64_t postnet_ws_floats(int B, int S) {
+    return (int64_t)B * S * 512 * ((int64_t)B * S <= POST_TAPSPLIT_ROWS * MAX_GROUP ? 9 : 4) + 2 * post_wino_floats(B, S) + 64 * 9;
+}
 
 // ------------------------------------------------------------------------------------------------ encoder
 
@@ -503,7 +522,7 @@ static int decode_launches(l2s_model* m, float* state, int B, int T, int S, cons
     // early stop: every launch carries the step it belongs to; the fc / stop group that finishes step `step` keeps the stop bookkeeping
     auto es_launch = [&](SkinnyBatch& sb, int step) { sb.es_end = es_end; sb.es_step = step - S; };
     auto es_fc = [&](SkinnyP& a, int step) {
-        if (es) { a.es_ctl = reinterpret_cast<int*>(es); a.es_end = std::min(S, step + 1 + ES_MARGIN) - S; }
+        if (es) { a.es_ctl = reinterpret_cast<int*>(es); a.es_end = std::min(S, step + 1 + es_margin()) - S; }
     };
 
     for (int i = 0; i < S; ++i) {
@@ -590,7 +609,7 @@ static int decode_run(l2s_model* m, float* state, int B, int T, int S, const flo
         p.h_init = state + sl.h; p.stop_const = state + sl.stopc;
         p.mel = mel; p.stop = stop; p.attn = attn; p.attn_logits = attn_logits;
         p.B = B; p.T = T; p.m = sl.m; p.S = S;
-        p.early = early ? ES_MARGIN : 0;
+        p.early = early ? es_margin() : 0;
         return launch_pdecode(p, ws, ws_bytes, s, lens);
     }
     const bool use_graph = m->opt.graph && !teacher && !g_prof_on && !early && !lens;      // "early_stop" and per-clip lengths take the plain route: a replayed graph knows no control block / length table of this call
@@ -628,7 +647,7 @@ static int decode_run(l2s_model* m, float* state, int B, int T, int S, const flo
 }
 
 // ------------------------------------------------------------------------------------------------ postnet
-struct PostBufs { float* x[4]; float* part = nullptr; };
+struct PostBufs { float* x[4]; float* part = nullptr; float* wv = nullptr; float* wm = nullptr; };      // wv, wm: the Winograd route's V and M
 
 static int postnet_alloc(Bump& bp, int B, int S, PostBufs& pb) {
     for (int i = 0; i < 4; ++i) pb.x[i] = bp.f((int64_t)B * S * 512);
@@ -636,13 +655,23 @@ static int postnet_alloc(Bump& bp, int B, int S, PostBufs& pb) {
     // launch + a finish kernel that adds the taps in order (launch_gemm_tapsplit; 40 -> 200 tiles).  Decided on the rows of ONE batch, so that a batch
     // meets the same arithmetic alone and in a group.
     pb.part = ((int64_t)B * S / gemm_x3_group() <= POST_TAPSPLIT_ROWS) ? bp.f((int64_t)B * S * 512 * 5) : nullptr;
+    pb.wv = bp.f(post_wino_floats(B, S)); pb.wm = bp.f(post_wino_floats(B, S));
     return bp.overflow ? 1 : 0;
 }
 
 // One post-net layer (decoder.py:143-156) over the frames [t0, t1) of every sequence; layer 0..4.
 // Layer i reads buffer i (mel for i = 0) and writes buffer i+1 (mel_post, channel-first, for i = 4).
-static int postnet_layer(const Weights& w, int layer, const float* mel, const PostBufs& pb, float* mel_post, int B, int S, int t0, int t1, hipStream_t s, bool dma_weights) {
+// wino: layers 1-3 of a full-range call in their Winograd F(4,5) form (post_wino_route): input transform, the eight products as ONE grouped launch of the
+// split-bf16 family (whatever the rows: wide and narrow tile give the same bits), output transform with the layer's epilogue.
+static int postnet_layer(const Weights& w, int layer, const float* mel, const PostBufs& pb, float* mel_post, int B, int S, int t0, int t1, hipStream_t s, bool dma_weights,
+                         bool wino = false) {
     if (t1 <= t0) return 0;
+    if (wino && layer >= 1 && layer <= 3 && t0 == 0 && t1 == S) {
+        L2S_REQUIRE(w.post_wino[layer] && pb.wv && pb.wm, "post-net: no Winograd weights / workspace");
+        if (launch_post_wino_in(pb.x[layer - 1], B, S, 512, pb.wv, s)) return 1;
+        if (launch_gemm(post_wino_products(w, layer, pb.wv, pb.wm, B * wino_tiles(S), dma_weights), s, "postnet_conv_gemm")) return 1;
+        return launch_post_wino_out(pb.wm, B, S, 512, w.post[layer].scale, w.post[layer].shift, w.post[layer].actw, pb.x[layer - 1], pb.x[layer], s);
+    }
     const bool tapsplit = pb.part && t0 == 0 && t1 == S;
     // the full-range descriptor is decoder_stages.h's; the weight planes go with the plain route only, and so does the time window
     GemmP p = post_layer(w, layer, layer == 0 ? mel : pb.x[layer - 1], layer == 4 ? mel_post : pb.x[layer], mel, B, S, dma_weights && !tapsplit);
@@ -667,8 +696,9 @@ static int postnet_run(l2s_model* m, const float* mel, int B, int S, float* mel_
     PostBufs pb;
     L2S_REQUIRE(postnet_alloc(bp, B, S, pb) == 0, "postnet workspace too small");
     L2S_REQUIRE(!ev || (ev->N == B && ev->Smax == S), "postnet: the step table does not match the rows");
+    const bool wino = post_wino_route(m, B, S);
     for (int layer = 0; layer < 5; ++layer) {
-        if (postnet_layer(w, layer, mel, pb, mel_post, B, S, 0, S, s, m->opt.gemm_x3_dma != 0)) return 1;
+        if (postnet_layer(w, layer, mel, pb, mel_post, B, S, 0, S, s, m->opt.gemm_x3_dma != 0, wino)) return 1;
         if (ev && layer < 4 && launch_zero_rows_past_s(pb.x[layer], 512, *ev, s)) return 1;
     }
     if (mel_cf && launch_transpose_bsc(mel, B, S, NM, mel_cf, s)) return 1;
@@ -1090,6 +1120,7 @@ static int path_run(l2s_model* m, const FrameSrc& video, const float* emb, const
     const bool early = m->opt.early_stop != 0 && !teacher && o.lengths;      // l2s_inference(_multi); l2s_forward_eval's S comes from the target
     const bool plain = !m->opt.overlap_postnet || g_prof_on || m->opt.graph || teacher || o.mel_cf || early || lens;      // "early_stop" and lengths take the plain route
     if (plain) {
+        EsMarginScope margin(post_wino_route(m, B, S) ? ES_MARGIN_WINO : ES_MARGIN);      // an early stop leaves the post-net the frames its route reads
         if (decode_run(m, state, B, T, S, teacher, teacher_mask, mel, stop, o.attn, o.attn_logits, rest, rest_bytes, s, early, lens)) return 1;
         if (o.ev && launch_zero_rows_past_s(mel, NM, *o.ev, s)) return 1;      // the frames a shorter batch's rows decoded past their own S: zeros for the post-net's taps
         if (postnet_run(m, mel, B, S, o.mel_post, o.mel_cf, rest, rest_bytes, s, o.ev)) return 1;
@@ -1602,6 +1633,13 @@ int l2s_op_table_layout(const int32_t* a, int64_t n_a, const int64_t* b, int64_t
     HostTable t(fill != 0);
     *off_a = t.i32(a, n_a); *off_b = t.i64(b, n_b); *words = t.words();
     return dst ? t.upload(dst, (hipStream_t)stream) : 0;
+}
+int l2s_op_post_wino_matrices(double* AT, double* G, double* BT) {      // host only: the constants the three transform kernels are compiled with
+    L2S_REQUIRE(AT && G && BT, "bad arguments");
+    for (int i = 0; i < WINO_M; ++i) for (int p = 0; p < WINO_P; ++p) AT[i * WINO_P + p] = WINO_AT[i][p];
+    for (int p = 0; p < WINO_P; ++p) for (int k = 0; k < WINO_R; ++k) G[p * WINO_R + k] = WINO_G[p][k];
+    for (int p = 0; p < WINO_P; ++p) for (int i = 0; i < WINO_P; ++i) BT[p * WINO_P + i] = WINO_BT[p][i];
+    return 0;
 }
 int l2s_op_frontend(l2s_model* m, const float* video, int B, int T, int H, int W, float* out, void* stream) {
     L2S_ENC_READY(m);

@@ -114,6 +114,10 @@ struct Options {
                                 //   not exactly zero (28.4 -> 23.5 MB per launch; same bits); 2 = also for a chain alone (one more round trip in the block: slower there), 0 = never
     int early_stop = 0;         // "early_stop": free-running inference ends the decode loop once every clip of the call has crossed its stop token, plus the post-net's
                                 //   receptive margin (ES_MARGIN steps); frames at or past a clip's length come back as exact zeros (include/l2s.h)
+    int post_wino = 1;          // "post_wino" (diagnostic A/B): post-net layers 1-3 in their Winograd F(4,5) form (post_wino.h: eight K = 512 products per layer in place of
+                                //   one K = 2560 product, 0.4x the matrix work; another association of the same sums): 1 = on the plain full-range route from
+                                //   POST_WINO_ROWS rows per batch on, 2 = at any row count, 0 = never.  The tap-split and windowed routes, "infer_bf16", "gemm_x3" = 0 and
+                                //   training keep the direct layer
     int infer_bf16 = 0;         // "infer_bf16": the bf16 leg of inference / evaluate: front-end conv, GEMMs and Conv1d stacks of encoder, prologue, post-net and
                                 //   voice tower with bf16 operands (fp32 accumulation); the recurrent loops, the fused ShuffleNet units and all statistics stay fp32
 };
@@ -151,7 +155,8 @@ struct GemmP {
     const void* W3;       // W as pre-split bf16 planes [ceil32(K) / 16][3 planes][N][16 k], zeros past K (launch_gemm_planes; N % 256 == 0, K % 16 == 0, ldw == 0) or null: the
                           //   128x256x32 split-bf16 tile then brings its weight operand in by LDS-DMA instead of load + split + ds_write
     int x3;               // bit 1: run on the split-bf16 kernel (gemm_x3.hip) when the whole launch group is eligible; bit 2: whatever its size
-                          //   (operator tests); bit 4: the 128x128x32 tile only; set from gemm_x3_mode()
+                          //   (operator tests); bit 4: the 128x128x32 tile only; set from gemm_x3_mode(); bit 8: always the split-bf16 family, the tile by
+                          //   the usual cost rule (the post-net's Winograd products: no row threshold may hand them to the f32 kernel)
     int x3_group;         // batches sharing this launch (grouped inference): the size thresholds of the kernel choice look at M / x3_group,
                           //   so a batch meets the same kernels alone and in a group (results stay bit-identical)
     float* stats;         // training, batch-statistics BatchNorm: STATS PASS - nothing is stored; per-column sums of the raw product
@@ -442,7 +447,8 @@ inline int content_hoist_pitch(int m) { return m <= CONTENT_HOIST_MAX_M ? (m + 3
 // (end_rel = end - S <= 0, es_step = step - S < 0), so that one memset to zero arms the block: "run to S".
 struct EsCtl { int end_rel; int count; int crossed[1]; };      // crossed[B]
 constexpr int ES_POST_LAYERS = 5, ES_POST_TAPS = 5;
-constexpr int ES_MARGIN = ES_POST_LAYERS * (ES_POST_TAPS / 2);      // post-net frame j reads pre-post-net frames j - 10 .. j + 10 (five Conv1d layers, kernel 5, pad 2)
+constexpr int ES_MARGIN = ES_POST_LAYERS * (ES_POST_TAPS / 2);      // post-net frame j reads pre-post-net frames j - 10 .. j + 10 (five Conv1d layers, kernel 5, pad 2);
+                                                                    //   19 where layers 1-3 run in Winograd form (l2s_api.hip ES_MARGIN_WINO)
 constexpr int SKINNY_MAX_GROUP = 4;
 struct SkinnyBatch { SkinnyP p[SKINNY_MAX_GROUP]; int ntiles[SKINNY_MAX_GROUP]; int count; const int* es_end; int es_step; };
 #define L2S_ES_RETURN(arg) do { if ((arg).es_end && (arg).es_step >= *(arg).es_end) return; } while (0)

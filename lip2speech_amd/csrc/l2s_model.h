@@ -93,6 +93,7 @@ struct Weights {
     const float* bos = nullptr; const float* tau = nullptr; const float* tau_c = nullptr;
     // postnet
     ConvW post[5];
+    const void* post_wino[5] = {};   // layers 1-3: the Winograd F(4,5) form of post[i].W (post_wino.h wino_u / wino_u3), derived on the device (derive_all_planes); else null
     // speaker encoder (audio.py:110-150): mel40 front-end tables + 3-layer LSTM(256) + Linear
     const float* spk_window = nullptr; const float* spk_dft = nullptr; const float* spk_fbT = nullptr;   // [400], [402][400], [40][204]
     ConvW spk_ih[3];                 // input weights [1024][in] with shift = b_ih + b_hh
@@ -134,7 +135,8 @@ struct l2s_model {
     bool folded_valid = true;                                 // the phase-merged step weights match the current parameters
     float* merge_scratch = nullptr;                           // device: the two products of the device-side re-merge (l2s_train_refresh_weights)
     void* gemm_planes = nullptr;                              // device: bf16 planes of the post-net's Conv1d weights, the BiLSTM input matrix and conv_last (option "gemm_x3_dma"); rebuilt like lstm_planes
-    void* unit_planes = nullptr;                              // device: bf16 operand planes of the fused ShuffleNet units' pointwise convs (option "trunk_x3"); rebuilt like lstm_planes
+    void* wino_weights = nullptr;                             // device: the transformed weights of post-net layers 1-3 (fp32 and bf16 planes; option "post_wino"); rebuilt like lstm_planes
+    void* unit_planes = nullptr;                           // device: bf16 operand planes of the fused ShuffleNet units' pointwise convs (option "trunk_x3"); rebuilt like lstm_planes
     void* lstm_planes = nullptr;                              // device: bf16 planes of the decoder LSTM weights (split-bf16 LSTM blocks, option "lstm_x3"); rebuilt
                                                               //   from the packed fp32 fragments after every pack / device-side refresh
     // training: BatchNorm layers normalise with batch statistics and update their running statistics (nn.Module.train()); off = running statistics

@@ -4,6 +4,7 @@
 // packer and the refresh kernels both call.
 #include "l2s_common.h"
 #include "l2s_model.h"
+#include "post_wino.h"
 
 #include <algorithm>
 #include <cmath>
@@ -602,7 +603,7 @@ static int pack_host(l2s_model* m, Packer& P) {
 static int build_refresh_map(l2s_model* m, const Packer& P, hipStream_t stream);
 
 // ------------------------------------------------------------------------------------------------ derived bf16 planes
-// Three pools of bf16 operand planes are derived on the device from the packed fp32 weights, after every pack and every device-side refresh.
+// Four pools of derived operands (three of bf16 operand planes, one of the post-net's Winograd weights with their planes) are derived on the device from the packed fp32 weights, after every pack and every device-side refresh.
 // One item = one weight (a x b: tiles x K for the LSTM fragments, N x K otherwise) and the slot that receives its planes.
 struct PlaneItem { const float* W; int a, b; const void** slot; };
 typedef int64_t (*PlaneBytesFn)(int a, int b);
@@ -668,11 +669,23 @@ static int derive_unit_planes(l2s_model* m, hipStream_t s) {
     return derive_planes(items, su_planes_bytes, launch_su_planes, &m->unit_planes, s);
 }
 
+// post-net layers 1-3 in their Winograd F(4,5) form (option "post_wino"): per layer the eight transformed matrices U_p in fp32 - for the split-bf16 GEMM's
+// staged-weights form - and their bf16 planes - the exact split of the stored U_p, for its LDS-DMA form - from the packed fp32 [512][5 * 512] weight
+static int derive_wino_weights(l2s_model* m, hipStream_t s) {
+    Weights& w = m->w;
+    for (int i = 0; i < 5; ++i) w.post_wino[i] = nullptr;
+    if (!m->has_dec) return 0;
+    std::vector<PlaneItem> items;
+    for (int i = 1; i <= 3; ++i) items.push_back({w.post[i].W, D, D, &w.post_wino[i]});
+    return derive_planes(items, [](int C, int) { return wino_weights_bytes(C); }, [](const float* W, int C, int, void* out, hipStream_t st) { return launch_post_wino_weights(W, C, out, st); },
+                         &m->wino_weights, s);
+}
+
 // fresh (after a pack: the blob moved, the parts may have changed): every pool is freed and derived anew; otherwise (after a device-side
 // refresh: the planes are splits of the old weights) the pools that exist are refilled in place
 static int derive_all_planes(l2s_model* m, hipStream_t s, bool fresh) {
-    struct { void** pool; int (*derive)(l2s_model*, hipStream_t); } kinds[3] = {
-        {&m->lstm_planes, derive_lstm_planes}, {&m->gemm_planes, derive_gemm_planes}, {&m->unit_planes, derive_unit_planes}};
+    struct { void** pool; int (*derive)(l2s_model*, hipStream_t); } kinds[4] = {
+        {&m->lstm_planes, derive_lstm_planes}, {&m->gemm_planes, derive_gemm_planes}, {&m->unit_planes, derive_unit_planes}, {&m->wino_weights, derive_wino_weights}};
     for (auto& k : kinds) {
         if (fresh && *k.pool) { (void)hipFree(*k.pool); *k.pool = nullptr; }
         if ((fresh || *k.pool) && k.derive(m, s)) return 1;
@@ -687,7 +700,7 @@ void drop_graphs(l2s_model* m) {
 
 // everything this file allocates on the device for a model that is about to be deleted
 void free_model_device(l2s_model* m) {
-    for (void* p : {(void*)m->blob, (void*)m->r_key, (void*)m->r_idx, m->r_tables, (void*)m->merge_scratch, m->lstm_planes, m->gemm_planes, m->unit_planes})
+    for (void* p : {(void*)m->blob, (void*)m->r_key, (void*)m->r_idx, m->r_tables, (void*)m->merge_scratch, m->lstm_planes, m->gemm_planes, m->unit_planes, m->wino_weights})
         if (p) (void)hipFree(p);
 }
 

@@ -56,12 +56,12 @@ ABI_SYMBOLS = (
 DIAG_SYMBOLS = (
     "l2s_op_gemm", "l2s_op_conv1d", "l2s_op_gemm_ex", "l2s_op_conv1d_ex", "l2s_op_conv1d_bwd", "l2s_op_frontend", "l2s_op_launch_chain", "l2s_op_launch_chain2", "l2s_op_skinny_timeline", "l2s_op_attn_timeline", "l2s_op_flat_timeline", "l2s_op_pdecode_timeline", "l2s_op_gemm_x3_timeline", "l2s_op_fused_unit_timeline", "l2s_op_lstm_cell_chain", "l2s_op_step_attn_chain", "l2s_op_stamp_log", "l2s_op_skinny_form", "l2s_op_step_site", "l2s_op_skinny", "l2s_op_skinny_hoist",
     "l2s_op_face_conv2d", "l2s_op_face_taps", "l2s_op_speaker_taps", "l2s_op_speaker_taps_packed", "l2s_op_encoder_taps",
-    "l2s_op_gemm_bwd", "l2s_op_gemm_bwd_recorder", "l2s_op_upload_table", "l2s_op_table_layout", "l2s_op_jpeg_entropy_host",
+    "l2s_op_gemm_bwd", "l2s_op_gemm_bwd_recorder", "l2s_op_upload_table", "l2s_op_table_layout", "l2s_op_jpeg_entropy_host", "l2s_op_post_wino_matrices",
 )
 
 # run-time options only the diagnostic build accepts (block-form A/B switches of the same arithmetic, include/l2s_diag.h)
 DIAG_OPTIONS = frozenset(("overlap_postnet", "fuse_trunk", "fuse_s2", "skinny_static", "skinny_sized", "skinny_split", "skinny_split8", "skinny_rc", "skinny_rc_jb",
-                          "skinny_rc_multi", "skinny_flat", "hoist_vproj", "attn_lds", "flat_half", "half_min_mts", "gemm_x3_dma", "flat_xcd", "attn_skip0", "trunk_chain", "frontend_solo"))
+                          "skinny_rc_multi", "skinny_flat", "hoist_vproj", "attn_lds", "flat_half", "half_min_mts", "gemm_x3_dma", "flat_xcd", "attn_skip0", "trunk_chain", "frontend_solo", "post_wino"))
 
 ST_K, ST_V, ST_CKEY, ST_CVAL, ST_ECELL, ST_H, ST_C, ST_ENC, ST_STOPC, ST_VP, ST_CP = range(11)
 
@@ -358,6 +358,8 @@ def _bind_diag(L: ctypes.CDLL) -> None:
         L.l2s_op_table_layout.argtypes = [_vp, _i64, _vp, _i64, _i, _vp, ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(_i64), _vp]
     if hasattr(L, "l2s_op_jpeg_entropy_host"):
         L.l2s_op_jpeg_entropy_host.argtypes = [_vp, _i64, ctypes.POINTER(JpegImage), _i, ctypes.POINTER(JpegTables), _i, _vp, _i64, _vp]
+    if hasattr(L, "l2s_op_post_wino_matrices"):
+        L.l2s_op_post_wino_matrices.argtypes = [_vp, _vp, _vp]
 
 
 def check(rc: int, L: Optional[ctypes.CDLL] = None) -> None:
@@ -1713,6 +1715,14 @@ def op_table_layout(a, b, fill: bool = True, dst: Optional[torch.Tensor] = None)
         _dcheck(diag().l2s_op_table_layout(ctypes.addressof(ha) if fill else None, len(a), ctypes.addressof(hb) if fill else None, len(b), 1 if fill else 0,
                                            _ptr(d), ctypes.byref(off_a), ctypes.byref(off_b), ctypes.byref(words), _stream() if d is not None else None))
     return off_a.value, off_b.value, words.value
+
+
+def op_post_wino_matrices():
+    """`l2s_op_post_wino_matrices` (diagnostic library, no device): the matrices of the post-net's Winograd F(4,5) route as float64 numpy arrays
+    `(AT (4, 8), G (8, 5), BT (8, 8))` - AT ((G g) * (BT d)) is the 4-output correlation of 5 taps g with an 8-frame tile d."""
+    AT, G, BT = np.zeros((4, 8)), np.zeros((8, 5)), np.zeros((8, 8))
+    _dcheck(diag().l2s_op_post_wino_matrices(AT.ctypes.data, G.ctypes.data, BT.ctypes.data))
+    return AT, G, BT
 
 
 # ---------------------------------------------------------------------------------------------- profiling

@@ -10,7 +10,13 @@ build every round's figure, the median of the rounds and the spread (max - min),
 build alone, 7 424 x 512 on the wide tile against the narrow one (116 tiles against 232, one round of blocks each): the case the tile choice
 (x3_wide in gemm_x3.hip) decides by its cost ratio.
 `CLIPS=` (256) scales every shape's row count; `ROUNDS=`, `REPS=`.
--> profiles/gemm_x3_shape_times.txt (stdout)"""
+-> profiles/gemm_x3_shape_times.txt (stdout)
+
+`POST_WINO=1`: instead of the above, the post-net (l2s_postnet, five layers) with layers 1-3 direct (diagnostic option "post_wino" = 0) against their
+Winograd F(4,5) form (1: eight K = 512 products of the same family per layer, csrc/post_wino.h) at CLIPS x 300 and CLIPS / 8 x 300 rows, and
+`PARENT_LIB=<the parent commit's libl2s_hip.so>` in the same process; same rounds; then the library's event profile per kernel name, five calls averaged.
+-> profiles/post_wino_times.txt (stdout)"""
+import ctypes
 import os
 import statistics
 import sys
@@ -63,7 +69,48 @@ def show(name, variants, t):
         print(f"    {bname:<12} rounds: " + " ".join(f"{v * 1e3:8.1f}" for v in x))
 
 
+def event_profile(nm, call):
+    """{kernel name: (launches, ms)} per call of `call`, five calls averaged, from the event brackets of the library that owns `nm`"""
+    L = nm._L
+    call(); torch.cuda.synchronize()
+    native.check(L.l2s_profile_reset(), L); native.check(L.l2s_profile_enable(1), L)
+    for _ in range(5):
+        call()
+    torch.cuda.synchronize()
+    out = {}
+    for i in range(L.l2s_profile_count()):
+        name, n, ms = ctypes.c_char_p(), ctypes.c_int64(), ctypes.c_double()
+        native.check(L.l2s_profile_get(i, ctypes.byref(name), ctypes.byref(n), ctypes.byref(ms)), L)
+        if n.value:
+            out[name.value.decode()] = (n.value // 5, ms.value / 5)
+    native.check(L.l2s_profile_enable(0), L); native.check(L.l2s_profile_reset(), L)
+    return out
+
+
+def post_wino():
+    parents = abtime.libs_from_env("PARENT_LIB", native._load)[:1]
+    direct, wino = abtime.synth_model(native.diag(), post_wino=0), abtime.synth_model(native.diag(), post_wino=1)
+    models = [("this build, post_wino 0", direct), ("this build, post_wino 1", wino)] + [(f"parent build ({label})", abtime.synth_model(lib)) for label, lib in parents]
+    print(f"l2s_postnet, five layers; {ROUNDS} interleaved rounds x {REPS} warm calls, HIP events; median of the rounds, spread = max - min")
+    for B in (CLIPS, max(1, CLIPS // 8)):
+        torch.manual_seed(1)
+        mel = torch.randn(B, 300, 80, device="cuda")
+        variants = [(name, (lambda m=m: m.postnet(mel)[0])) for name, m in models]
+        t, outs = abtime.rounds(variants, ROUNDS, REPS)
+        print(f"\n{B * 300} rows (B = {B}, S = 300)")
+        med = abtime.report(variants, t, ratio="post_wino 0")
+        print(f"    Winograd - direct: {(med[1] - med[0]) * 1e3:8.1f} us over three layers = {(med[1] - med[0]) * 1e3 / 3:7.1f} us per layer; "
+              f"every Winograd round under every direct round: {abtime.wholly_under(t[1], t[0])}")
+        print(f"    max |Winograd - direct| = {float((outs[1] - outs[0]).abs().max()):.3e}, max |out| = {float(outs[0].abs().max()):.2f}"
+              + (f"; post_wino 0 has the parent's bits: {torch.equal(outs[0], outs[2])}" if parents else ""))
+        for name, m in models[:2]:
+            pr = event_profile(m, lambda: m.postnet(mel))
+            print(f"    event profile, {name}: " + ", ".join(f"{k} {n} x = {ms * 1e3:.0f} us" for k, (n, ms) in sorted(pr.items())))
+
+
 def main():
+    if os.environ.get("POST_WINO", "0") != "0":
+        return post_wino()
     torch.manual_seed(0)
     rows = CLIPS * 29
     multihop = ("MultiHop branches, 8 convs 512 -> 512 (k = 1, 3, 7, 11 twice), %d x 29 rows" % CLIPS,
