@@ -401,7 +401,7 @@ int l2s_inference(l2s_model* m, const float* video, const float* emb, const floa
  * Options: masked calls take the launch-per-phase route - "persist_decode" and "use_graph" do not apply to them - unless "persist_masked" is set
  * (below: free-running masked calls inside the persistent envelope then take the persistent forms); "early_stop", "fold_step_weights" and
  * "infer_bf16" compose.  The grouped (*_multi) entry points have no masked form: batches of unequal length share a launch chain through
- * l2s_inference_ragged and, on the evaluate route, l2s_forward_eval_ragged ("ragged groups" below); the training (l2s_train_*) entry points have none.
+ * l2s_inference_ragged and, on the evaluate route, l2s_forward_eval_ragged ("ragged groups" below); the training entry points have their own (l2s_train_*_masked_fwd / _masked_bwd, "training with per-clip video lengths" below).
  * Workspace: l2s_workspace_bytes_masked (the unmasked size plus the device length table), for all four calls.
  * l2s_masked_bilstm_plan: the launch plan of the BiLSTM recurrence, a pure host function.  The recurrence stays T uniform launches (step s reads frame
  * s forward and frame T-1-s backward); capture_steps = the steps AFTER which a row kernel hands over the forward finals of the clips that ended there
@@ -599,6 +599,54 @@ int64_t l2s_train_encoder_ws_bytes(int B, int T, int H);
 int l2s_train_encoder_fwd(l2s_model* m, const float* video, int B, int T, int H, int W, const float* emb, float* vis, float* feat, float* tape, void* stream);
 int l2s_train_encoder_bwd(l2s_model* m, const float* video, int B, int T, int H, int W, const float* dfeat, int ld_dfeat, float* tape, void* ws, int64_t ws_bytes,
                           void* stream);
+
+/* ---- training with per-clip video lengths: the training step of a zero-padded batch, forward and backward --------------------------------------
+ * l2s_train_<stage>_masked_fwd / _masked_bwd, stage = encoder, prologue, steps (the word order keeps the names l2s_train_*_fwd_masked free: their
+ * ABSENCE is what tests/test_masked_lengths_host.py has pinned since the forward-only masked family).
+ * The masked forms of the three stages that see the video take their unmasked signature plus `video_lengths`, the HOST array of B int32 of the
+ * masked family above ("per-clip video lengths": clips ZERO-padded to T, len_b in [7, T] or an error that names the row, before anything is
+ * launched).  Every call carries the lengths to the device itself (csrc/host_table.h: kernel arguments on `stream`, no allocation, no
+ * synchronisation; the array may be freed when the call returns) into its TAPE: size the tapes with the *_tape_floats_masked sizers and the
+ * workspaces of the encoder and the prologue with *_ws_bytes_masked (the loop keeps l2s_train_steps_ws_bytes).  l2s_train_postnet_* and
+ * l2s_loss do not depend on video lengths and are unchanged: the loop runs S steps for every clip, the loss covers padded target frames, as in the
+ * reference, and the KLD term keeps its mean over all B * min_T(T) rows (rows of unused slots are zeros and add nothing to the sum).
+ * Forward.  Row b of mel, stop and the attention logits - so of mel_post - is what the unmasked training forward gives clip b ALONE at B = 1,
+ * T = len_b with the same teacher frames, dropout multipliers and its first m_b = l2s_min_T(len_b) Gumbel rows.  Attention logits at t >= len_b
+ * are -INFINITY; content_dis rows of slots >= m_b and the 768 feature columns of vis / feat rows t >= len_b are exact zeros (the speaker
+ * columns of vis are the clip's own on every row).
+ * Backward.  Every parameter gradient is the sum over the clips of the gradient the unmasked backward computes for that clip alone, fed the same
+ * upstream-gradient rows.  dvis rows t >= len_b, dk / dv rows t >= len_b and dckey / dcval of slots >= m_b are exact zeros; the -INFINITY logits
+ * give no NaN.  Same bits run to run.  With every len_b = T every output, tape and gradient has the bits of the unmasked entry points.
+ * Never read, whatever they hold: drop_attn at columns t >= len_b, rows t >= len_b of dfeat (l2s_train_encoder_masked_bwd), Gumbel rows >= m_b
+ * of a clip, dcontent_dis rows of slots >= m_b, and K / V rows t >= len_b of the state.
+ * How.  The front-end runs on the padded batch (its temporal zero padding is what makes a padded clip's real frames see what a solo clip sees);
+ * the real frames of its pooled map are gathered into a compact list and the trunk runs at sum(len_b) frames, forward and backward; the
+ * recurrence of the prologue keeps its T uniform launches with the capture / reset row kernels of the masked inference prologue laid over them
+ * and their adjoints over its backward; the attention blocks and their backward run every row over its own frames and slots.
+ * Refused by name: batch_stats = 1 (l2s_train_set_bn) - the masked calls run on running statistics; a batch-statistics mode that leaves pad
+ * positions out of every BatchNorm does not exist yet, and one that counts them is not offered - and option "train_bf16".  No grouped or
+ * ragged training forms. */
+int64_t l2s_train_encoder_tape_floats_masked(int B, int T, int H);
+int64_t l2s_train_encoder_ws_bytes_masked(int B, int T, int H);
+int64_t l2s_train_prologue_tape_floats_masked(int B, int T);
+int64_t l2s_train_prologue_ws_bytes_masked(int B, int T);
+int64_t l2s_train_steps_tape_floats_masked(int B, int S);
+int l2s_train_encoder_masked_fwd(l2s_model* m, const float* video, int B, int T, int H, int W, const float* emb, float* vis, float* feat, float* tape, void* stream,
+                                 const int32_t* video_lengths);
+int l2s_train_encoder_masked_bwd(l2s_model* m, const float* video, int B, int T, int H, int W, const float* dfeat, int ld_dfeat, float* tape, void* ws,
+                                 int64_t ws_bytes, void* stream, const int32_t* video_lengths);
+int l2s_train_prologue_masked_fwd(l2s_model* m, const float* vis, const float* emb, const float* gumbel, int B, int T, float* state, float* content_dis,
+                                  float* tape, void* ws, int64_t ws_bytes, void* stream, const int32_t* video_lengths);
+int l2s_train_prologue_masked_bwd(l2s_model* m, const float* vis, const float* emb, int B, int T, float* state, float* tape, float* wbuf, const float* dk,
+                                  const float* dv, const float* dckey, const float* dcval, const float* dh_init, const float* de_c,
+                                  const float* dcontent_dis, float* dvis, void* ws, int64_t ws_bytes, void* stream, const int32_t* video_lengths);
+int l2s_train_steps_masked_fwd(l2s_model* m, float* state, int B, int T, int S, const float* teacher, const uint8_t* teacher_mask,
+                               const uint8_t* teacher_mask_dev, float* tape, float* mel, float* stop, float* attn_logits, const float* drop_prenet,
+                               const float* drop_attn, const float* drop_rnn, void* ws, int64_t ws_bytes, void* stream, const int32_t* video_lengths);
+int l2s_train_steps_masked_bwd(l2s_model* m, float* state, int B, int T, int S, const uint8_t* teacher_mask, float* tape, const float* attn_logits,
+                               const float* dmel, const float* dstop, float* wbuf, float* dk, float* dv, float* dckey, float* dcval, float* dh_init,
+                               float* de_c, const float* drop_prenet, const float* drop_attn, const float* drop_rnn, void* ws, int64_t ws_bytes,
+                               void* stream, const int32_t* video_lengths);
 
 /* ---- run-time options ------------------------------------------------------------------------------------------------------------
  * l2s_set_option changes the PROCESS DEFAULTS: what l2s_model_create copies into a new model.  l2s_model_set_option changes one model.

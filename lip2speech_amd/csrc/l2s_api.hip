@@ -340,7 +340,7 @@ static int encoder_run(l2s_model* m, const FrameSrc& video, int B, int T, int H,
 
 // ------------------------------------------------------------------------------------------------ decoder prologue
 // ---- per-clip video lengths (the *_masked entry points, include/l2s.h)
-static int check_lengths(const int32_t* video_lengths, int B, int T) {
+int check_lengths(const int32_t* video_lengths, int B, int T) {      // (shared with the l2s_train_*_masked_fwd / _masked_bwd entry points: l2s_common.h)
     L2S_REQUIRE(video_lengths, "video_lengths is null");
     for (int b = 0; b < B; ++b)
         if (video_lengths[b] < 7 || video_lengths[b] > T) {

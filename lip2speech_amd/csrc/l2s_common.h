@@ -518,6 +518,31 @@ int launch_pool_cat_masked(const PoolCatP& p, const PoolDiv& d, const int* lens,
 int launch_zero_slot_rows(float* z, int ldz, float* dis, int n, int B, int m, const int* lens, hipStream_t s);
 // launch_step_attn with per-row lengths: row b's soft-max and a @ V' over t < len_b (attention columns past it: 0, or -inf for logits), content over m_b slots
 int launch_step_attn_masked(const AttnP& at, const SkinnyP& pre2, int pre2_tiles, const int* lens, hipStream_t s, int lds_values = 1, int skip0 = 0);
+// ---- per-clip video lengths on the training path (masked_train.hip; the l2s_train_*_masked_fwd / _masked_bwd entry points).  The device table is 3*B int32: the two
+// segments above, then frame0_b = sum of len_c over c < b (clip b's first frame in the encoder trunk's compact frame list)
+int check_lengths(const int32_t* video_lengths, int B, int T);      // l2s_api.hip: every len_b in [7, T], else an error that names the row
+int64_t train_len_table_words(int B);
+int launch_train_len_table(const int32_t* lens_host, int B, int* table, hipStream_t s);
+// rows of `cols` floats between the padded layout (row b*T + t) and the compact one (row frame0_b + t): to_compact gathers the real rows; otherwise the
+// padded rows are written from the compact ones, rows t >= len_b as zeros
+int launch_frame_rows(const float* src, float* dst, const int* lens, int B, int T, int64_t cols, bool to_compact, hipStream_t s);
+// compact normalised features (sum len, C) -> vis rows [feat | emb_b] and / or feat rows of the padded batch; feature columns of rows t >= len_b are zeros
+int launch_feat_rows_store(const float* featc, int C, const float* emb, int E, const int* lens, int B, int T, float* vis, int ldv, float* feat, hipStream_t s);
+// dfeat rows (stride ld_df) of the real frames -> compact (sum len, C); rows t >= len_b are never read
+int launch_feat_rows_gather(const float* dfeat, int ld_df, int C, const int* lens, int B, int T, float* out, hipStream_t s);
+// launch_bilstm_reset that also writes the post-reset state into the tape's predecessor rows (plain (B,512) each)
+int launch_bilstm_reset_tape(float* h_frag, float* c_frag, float* hprev, float* cprev, const int* lens, int B, int t, const float* s_e, hipStream_t s);
+// adjoint of the capture: dh_last (B,512) = dh_init where len_b == T, else 0 with dc_carry[b] = 0 and drnn[b][len_b - 1][0:512] += dh_init[b] ...
+int launch_bilstm_capture_adj_init(const float* dh_init, float* dh_last, float* dc_carry, float* drnn, int ld_rnn, const int* lens, int B, int T, hipStream_t s);
+// ... and dc_carry[b] = dcell[b] for the rows with len_b == len
+int launch_bilstm_capture_adj_cell(const float* dcell, int ld_dcell, float* dc_carry, const int* lens, int B, int len, hipStream_t s);
+// adjoint of the reset, rows with len_b == len: gate gradients (frag16, K = 2048) move to dg_reset, the carried cell gradient to ds_e; both are cut
+int launch_bilstm_reset_adj(float* dg_frag, float* dg_reset, float* dc_carry, float* ds_e, const int* lens, int B, int len, hipStream_t s);
+// rows t >= len_b of x (B*T rows, ldx) := 0 over `cols` columns
+int launch_zero_pad_rows(float* x, int ldx, const int* lens, int B, int T, int cols, hipStream_t s);
+// backward of the adaptive average pooling + concatenation: dp (B,m,nmaps*C) -> d map_j; acc[j]: add to dx[j].  The masked form matches pool_cat_masked's bins
+struct PoolCatBwdP { float* dx[5]; int L[5]; int ld[5]; int acc[5]; int nmaps; int B, m, C; const float* dp; };
+int launch_pool_cat_masked_bwd(const PoolCatBwdP& p, const PoolDiv& d, const int* lens, hipStream_t s);
 int launch_frame_window(const float* audio, int B, int N, int L, int n_fft, int hop, const float* window, float* frames, hipStream_t s);
 int launch_power(const float* spec, int lds, int64_t rows, int nf, float* power, int ldp, hipStream_t s);
 // ---- the voice tower over clips of unequal length (l2s_speaker_encoder_packed): the time-major compact layout - frame l of the clip of rank r (clips

@@ -1227,7 +1227,7 @@ __device__ __forceinline__ float block_sum8(float x, float* scratch) {
 template <bool TRAIN = false, bool TIMED = false, bool VLDS = false, bool SKIP0 = false, bool ML = false>
 __device__ __forceinline__ void attention_block(const AttnP& p, int b, float* sm, const AttnTrain* tr = nullptr, unsigned long long* ats = nullptr, int len = 0) {
     static_assert(!SKIP0 || VLDS, "the zero-weight skip rides on the buffer-load form of the inference step");
-    static_assert(!ML || (!TRAIN && !TIMED), "per-row lengths: the inference step only");
+    static_assert(!ML || !TIMED, "per-row lengths: the inference step and the training step, not the stamped build");
     L2S_ATT_STAMP(0);
     float* qs = sm;                  // 512
     float* sc = sm + 512;            // ATT_MAXT
@@ -1453,7 +1453,7 @@ __device__ __forceinline__ void content_block_long(const AttnP& p, int b, float*
         p.cc_frag[frag16_index(b, tid, 256)] = o;
         if constexpr (TRAIN) {
             if (tr->cc_plain) tr->cc_plain[(int64_t)b * 256 + tid] = o;
-            if (tr->alpha && tid < m) tr->alpha[(int64_t)b * tr->ld_alpha + tid] = expf(csc[tid] - cmx) / csum;
+            if (tr->alpha && tid < m) tr->alpha[(int64_t)b * tr->ld_alpha + tid] = (ML && tid >= me) ? 0.f : expf(csc[tid] - cmx) / csum;      // slots past the clip's: weight 0
         }
     }
 }
@@ -1522,7 +1522,7 @@ __device__ __forceinline__ void content_block(const AttnP& p, int b, float* sm, 
         pcc[frag16_index(b, tid, 256)] = o;
         if constexpr (TRAIN) {
             if (tr->cc_plain) tr->cc_plain[(int64_t)b * 256 + tid] = o;
-            if (tr->alpha && tid < m) tr->alpha[(int64_t)b * tr->ld_alpha + tid] = expf(csc[tid] - cmx) / csum;
+            if (tr->alpha && tid < m) tr->alpha[(int64_t)b * tr->ld_alpha + tid] = (ML && tid >= me) ? 0.f : expf(csc[tid] - cmx) / csum;      // slots past the clip's: weight 0
         }
     }
 }

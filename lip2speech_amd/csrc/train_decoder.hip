@@ -9,8 +9,10 @@
 #include "l2s_model.h"
 #include "decode_step.h"
 #include "decoder_stages.h"
+#include "pdecode.h"      // ClipLens: the device length table of a *_masked call and the host array it was built from
 
 #include <algorithm>
+#include <vector>
 
 namespace l2s {
 
@@ -356,6 +358,19 @@ __global__ __launch_bounds__(512) void train_step_attn_kernel(const TrainStepB s
     else if (bid < 2 * nb) content_block<true>(sb.at, bid - nb, sm, &sb.att);
     else { const int j = bid - 2 * nb; skinny_block<true, TR_MAXC>(sb.pre2, j % sb.pre2_tiles, j / sb.pre2_tiles, sm, 1 << 30, &sb.pre2t); }
 }
+// the same grid with per-row lengths (l2s_train_steps_masked_fwd): lens[b] = len_b frames, lens[B + b] = m_b content slots, as in step_attn_masked_kernel
+// (skinny.hip) - soft-max, a @ v, the dropout multipliers and the tape rows of row b run over its own frames and slots; logits past len_b are -inf
+__global__ __launch_bounds__(512) void train_step_attn_masked_kernel(const TrainStepB sb, const int* __restrict__ lens) {
+    __shared__ __attribute__((aligned(16))) float sm[ATT_SM_FLOATS > SK_RED_FLOATS ? ATT_SM_FLOATS : SK_RED_FLOATS];
+    const int nb = sb.at.B, bid = blockIdx.x;
+    if (bid < nb) {
+        const int len = min(max(lens[bid], 1), sb.at.T);       // validated on the host (7 .. T); clamped so that no table content can index past a row
+        attention_block<true, false, false, false, true>(sb.at, bid, sm, &sb.att, nullptr, len);
+    } else if (bid < 2 * nb) {
+        const int mb = min(max(lens[bid], 1), sb.at.m);         // lens[B + b] with b = bid - B
+        content_block<true, true>(sb.at, bid - nb, sm, &sb.att, mb);
+    } else { const int j = bid - 2 * nb; skinny_block<true, TR_MAXC>(sb.pre2, j % sb.pre2_tiles, j / sb.pre2_tiles, sm, 1 << 30, &sb.pre2t); }
+}
 
 // ---- tape of the loop: time-major plain tensors
 struct StepTape {
@@ -473,16 +488,22 @@ struct AttnBwdP {
     int B, T, m;
 };
 
-__global__ __launch_bounds__(512) void attn_bwd_kernel(const AttnBwdP p) {
+// ML (l2s_train_steps_masked_bwd): row b has lens[b] frames and lens[B + b] content slots inside rows laid out for T / m - every loop and soft-max lane
+// runs over those, as a solo call at T = len_b does; dk / dv rows and dckey / dcval slots past them are never touched (they keep the zeros of the fill),
+// and the -inf logits, the dropout multipliers and the K / V rows past len_b are never read
+template <bool ML>
+__global__ __launch_bounds__(512) void attn_bwd_kernel(const AttnBwdP p, const int* __restrict__ lens) {
     __shared__ float s_dav[512], s_a[ATT_MAXT], s_dl[ATT_MAXT], s_red[16], s_dcc[256], s_qc[256], s_dlc[ATT_MAXM], s_al[ATT_MAXM];
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int T = p.T, m = p.m;
+    const int T = p.T, m = p.m;                                                    // row pitches of k / v / dk / dv and of the content slots
+    const int Te = ML ? min(max(lens[b], 1), T) : T;                               // frames and
+    const int me = ML ? min(max(lens[p.B + b], 1), m) : m;                         // slots the clip has
     const float tau = p.tau[0], tau_c = p.tau_c[0];
     const float* kb = p.k + (int64_t)b * T * 512;
     const float* vb = p.v + (int64_t)b * T * 512;
     s_dav[tid] = p.dav[(int64_t)b * (p.ld_dav ? p.ld_dav : 512) + tid];
     // softmax of the stored logits
-    const bool on = tid < T;
+    const bool on = tid < Te;
     const float l = on ? p.logits[(int64_t)b * p.ld_logit_b + tid] : -INFINITY;
     float mx = wave_max_f(l);
     __syncthreads();
@@ -500,7 +521,7 @@ __global__ __launch_bounds__(512) void attn_bwd_kernel(const AttnBwdP p) {
     if (on) s_a[tid] = ex / sm;
     __syncthreads();
     // da[t] = dav . v[t]  (wave per row)
-    for (int t = wave; t < T; t += 8) {
+    for (int t = wave; t < Te; t += 8) {
         float acc = 0.f;
 #pragma unroll
         for (int e = 0; e < 8; ++e) acc = fmaf(s_dav[lane * 8 + e], vb[(int64_t)t * 512 + lane * 8 + e], acc);
@@ -541,17 +562,17 @@ __global__ __launch_bounds__(512) void attn_bwd_kernel(const AttnBwdP p) {
         // dk / dv accumulate over the steps in HBM: a read-modify-write per (t, column). Eight frames per trip with all 24 loads
         // issued before the first store - one frame at a time was a chain of 29 dependent round trips (23 us per launch)
         constexpr int TC = 8;
-        for (int t0 = 0; t0 < T; t0 += TC) {
+        for (int t0 = 0; t0 < Te; t0 += TC) {
             float kk[TC], dkv[TC], dvv[TC];
 #pragma unroll
             for (int u = 0; u < TC; ++u) {
-                const int64_t o = (int64_t)min(t0 + u, T - 1) * 512;
+                const int64_t o = (int64_t)min(t0 + u, Te - 1) * 512;
                 kk[u] = kb[o + tid]; dkv[u] = dkb[o]; dvv[u] = dvb[o];
             }
 #pragma unroll
             for (int u = 0; u < TC; ++u) {
                 const int t = t0 + u;
-                if (t < T) {
+                if (t < Te) {
                     const float dl_t = s_dl[t];
                     dq = fmaf(dl_t, kk[u], dq);
                     dkb[(int64_t)t * 512] = dkv[u] + tau * dl_t * q;
@@ -570,12 +591,12 @@ __global__ __launch_bounds__(512) void attn_bwd_kernel(const AttnBwdP p) {
         const float zc = p.zc[(int64_t)b * 256 + tid];
         s_qc[tid] = zc / (1.f + expf(-zc));
     }
-    if (tid < ATT_MAXM) s_al[tid] = tid < m ? p.alpha[(int64_t)b * ATT_MAXM + tid] : 0.f;
+    if (tid < ATT_MAXM) s_al[tid] = tid < me ? p.alpha[(int64_t)b * ATT_MAXM + tid] : 0.f;
     __syncthreads();
     const float* keyb = p.ckey + (int64_t)b * m * 256;
     const float* valb = p.cval + (int64_t)b * m * 256;
     __shared__ float s_dal[ATT_MAXM], s_dot[ATT_MAXM];
-    for (int j = wave; j < m; j += 8) {                  // d alpha_j = dcc . value_j ; dot_j = qc . key_j
+    for (int j = wave; j < me; j += 8) {                  // d alpha_j = dcc . value_j ; dot_j = qc . key_j
         float a0 = 0.f, a1 = 0.f;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
@@ -588,26 +609,26 @@ __global__ __launch_bounds__(512) void attn_bwd_kernel(const AttnBwdP p) {
     __syncthreads();
     if (tid == 0) {
         float sa = 0.f;
-        for (int j = 0; j < m; ++j) sa += s_al[j] * s_dal[j];
+        for (int j = 0; j < me; ++j) sa += s_al[j] * s_dal[j];
         float dtc = 0.f;
-        for (int j = 0; j < m; ++j) { const float d = s_al[j] * (s_dal[j] - sa); s_dlc[j] = d; dtc += d * s_dot[j]; }
+        for (int j = 0; j < me; ++j) { const float d = s_al[j] * (s_dal[j] - sa); s_dlc[j] = d; dtc += d * s_dot[j]; }
         p.dtauc_part[b] = dtc;
     }
     __syncthreads();
     if (tid < 256) {
         float dqc = 0.f;
         constexpr int MC = 4;
-        for (int j0 = 0; j0 < m; j0 += MC) {                 // same read-modify-write pattern: loads first
+        for (int j0 = 0; j0 < me; j0 += MC) {                 // same read-modify-write pattern: loads first
             float kk[MC], dkv[MC], dvv[MC];
 #pragma unroll
             for (int u = 0; u < MC; ++u) {
-                const int64_t o = ((int64_t)b * m + min(j0 + u, m - 1)) * 256 + tid;
-                kk[u] = keyb[(int64_t)min(j0 + u, m - 1) * 256 + tid]; dkv[u] = p.dckey[o]; dvv[u] = p.dcval[o];
+                const int64_t o = ((int64_t)b * m + min(j0 + u, me - 1)) * 256 + tid;
+                kk[u] = keyb[(int64_t)min(j0 + u, me - 1) * 256 + tid]; dkv[u] = p.dckey[o]; dvv[u] = p.dcval[o];
             }
 #pragma unroll
             for (int u = 0; u < MC; ++u) {
                 const int j = j0 + u;
-                if (j < m) {
+                if (j < me) {
                     dqc = fmaf(s_dlc[j], kk[u], dqc);
                     p.dckey[((int64_t)b * m + j) * 256 + tid] = dkv[u] + tau_c * s_dlc[j] * s_qc[tid];
                     p.dcval[((int64_t)b * m + j) * 256 + tid] = dvv[u] + s_al[j] * s_dcc[tid];
@@ -669,7 +690,8 @@ static int64_t step_fwd_ws_floats(int B) { return (int64_t)pad16(B) * (512 * 8 +
 struct StepDrop { const float* prenet; const float* attn; const float* rnn; };
 
 static int decode_train_fwd(l2s_model* m, float* state, int B, int T, int S, const float* teacher, const uint8_t* mask, const uint8_t* mask_dev,
-                            float* tape_base, float* mel, float* stop, float* attn_logits, StepDrop drop, void* ws, int64_t ws_bytes, hipStream_t s) {
+                            float* tape_base, float* mel, float* stop, float* attn_logits, StepDrop drop, void* ws, int64_t ws_bytes, hipStream_t s,
+                            const int* lens = nullptr) {      // lens: the device length table of a masked call (row b attends to its own frames and slots)
     const Weights& w = m->w;
     StateLayout sl = state_layout(B, T);
     StepTape tp = step_tape(tape_base, B, S);
@@ -720,7 +742,8 @@ static int decode_train_fwd(l2s_model* m, float* state, int B, int T, int S, con
             sb.att.alpha = tp.alpha + (int64_t)i * B * ATT_MAXM; sb.att.ld_alpha = ATT_MAXM; sb.att.av_plain = tp.av + r512; sb.att.cc_plain = tp.cc + r256;
             sb.pre2t.zsave = tp.z2 + r256; sb.pre2t.ld_z = 256;
             ProfScope ps("train_step_attention_prenet2", s);
-            hipLaunchKernelGGL(train_step_attn_kernel, dim3(2 * B + sb.pre2_tiles * (Bp / 16)), dim3(512), 0, s, sb);
+            if (lens) hipLaunchKernelGGL(train_step_attn_masked_kernel, dim3(2 * B + sb.pre2_tiles * (Bp / 16)), dim3(512), 0, s, sb, lens);
+            else hipLaunchKernelGGL(train_step_attn_kernel, dim3(2 * B + sb.pre2_tiles * (Bp / 16)), dim3(512), 0, s, sb);
             L2S_CHECK_HIP(hipGetLastError());
         }
         if (!fold) {      // phase C
@@ -858,7 +881,7 @@ static int64_t step_bwd_ws_floats(int B, int S) {
 // Outputs: parameter gradients (bound slots), dk/dv (B,T,512), dckey/dcval (B,m,256), dh_init (2,B,512), de_c (B,512).
 static int decode_train_bwd(l2s_model* m, float* state, int B, int T, int S, const uint8_t* mask, float* tape_base, const float* attn_logits,
                             const float* dmel, const float* dstop, float* wbuf, float* dk, float* dv, float* dckey, float* dcval, float* dh_init,
-                            float* de_c, StepDrop drop, void* ws, int64_t ws_bytes, hipStream_t s) {
+                            float* de_c, StepDrop drop, void* ws, int64_t ws_bytes, hipStream_t s, const int* lens = nullptr) {      // lens: as in decode_train_fwd
     const Weights& w = m->w;
     StateLayout sl = state_layout(B, T);
     StepTape tp = step_tape(tape_base, B, S);
@@ -926,7 +949,8 @@ static int decode_train_bwd(l2s_model* m, float* state, int B, int T, int S, con
             a.dk = dk; a.dv = dv; a.dckey = dckey; a.dcval = dcval; a.dzq_frag = f_dzq; a.dq_stack = st_dq + r512; a.dzc_frag = f_dzc;
             a.dqc_stack = st_dqc + r256; a.dtau_part = st_dtau + (int64_t)i * B; a.dtauc_part = st_dtauc + (int64_t)i * B;
             a.B = B; a.T = T; a.m = sl.m;
-            hipLaunchKernelGGL(attn_bwd_kernel, dim3(B), dim3(512), 0, s, a);
+            if (lens) hipLaunchKernelGGL(attn_bwd_kernel<true>, dim3(B), dim3(512), 0, s, a, lens);
+            else hipLaunchKernelGGL(attn_bwd_kernel<false>, dim3(B), dim3(512), 0, s, a, lens);
         }
         {
             SkinnyBatch sb{}; TrainSkinnyBatch tb{};
@@ -1080,8 +1104,10 @@ static ProTape pro_tape(float* base, int B, int T) {
 
 static int64_t pro_fwd_ws_floats(int B) { return (int64_t)pad16(B) * 512 * 6 + 64 * 8; }
 
+// lens (l2s_train_prologue_masked_fwd): row b computes what clip b alone at T = len_b computes - the row kernels of the masked inference prologue
+// (masked_kernels.hip) laid over the taped launches, and a reset that also rewrites the tape's predecessor rows
 static int prologue_train_fwd(l2s_model* m, const float* vis, const float* emb, const float* gumbel, int B, int T, float* state, float* content_dis,
-                              float* tape_base, void* ws, int64_t ws_bytes, hipStream_t s) {
+                              float* tape_base, void* ws, int64_t ws_bytes, hipStream_t s, ClipLens lens = {}) {
     const Weights& w = m->w;
     StateLayout sl = state_layout(B, T);
     ProTape tp = pro_tape(tape_base, B, T);
@@ -1105,9 +1131,20 @@ static int prologue_train_fwd(l2s_model* m, const float* vis, const float* emb, 
         L2S_CHECK_HIP(hipMemcpyAsync(tp.hproc[d], tp.s_e, sizeof(float) * B * 512, hipMemcpyDeviceToDevice, s));
         L2S_CHECK_HIP(hipMemcpyAsync(tp.cproc[d], tp.s_e, sizeof(float) * B * 512, hipMemcpyDeviceToDevice, s));
     }
+    std::vector<int32_t> cap_steps(B), rst_steps(B);
+    int n_cap = 0, n_rst = 0, cap_i = 0, rst_i = 0;
+    if (lens) {
+        if (l2s_masked_bilstm_plan(lens.host, B, T, cap_steps.data(), rst_steps.data(), &n_cap, &n_rst)) return 1;
+        if (launch_fill(state + sl.h, (int64_t)Bp * 512, 0.f, s)) return 1;      // forward finals arrive row by row; the padded rows stay zero
+    }
     for (int step = 0; step < T; ++step) {
         SkinnyBatch sb{}; TrainSkinnyBatch tb{};
         const int cur = step & 1, nxt = cur ^ 1;
+        if (rst_i < n_rst && rst_steps[rst_i] == step) {      // backward rows whose clip ends at frame T-1-step start here from s_e; the tape's predecessor rows say so
+            ++rst_i;
+            if (launch_bilstm_reset_tape(tp.hf[1][cur], tp.cf[1], tp.hproc[1] + (int64_t)step * B * 512, tp.cproc[1] + (int64_t)step * B * 512, lens.dev, B,
+                                         T - 1 - step, tp.s_e, s)) return 1;
+        }
         for (int d = 0; d < 2; ++d) {
             bilstm_step_group(sb, d, w, false, B, T, d == 0 ? step : T - 1 - step, tp.hf[d][cur], tp.hf[d][nxt], tp.cf[d], tp.gin, tp.rnn);
             sb.p[d].h_plain = tp.hproc[d] + (int64_t)(step + 1) * B * 512; sb.p[d].ld_hplain = 512;
@@ -1116,12 +1153,18 @@ static int prologue_train_fwd(l2s_model* m, const float* vis, const float* emb, 
         }
         sb.count = 2;
         if (launch_train_skinny(sb, tb, s, "train_bilstm_step")) return 1;
+        if (cap_i < n_cap && cap_steps[cap_i] == step) {      // forward rows whose clip ended at frame `step`: their finals, now
+            ++cap_i;
+            if (launch_bilstm_capture(tp.hf[0][nxt], tp.cf[0], lens.dev, B, step, state + sl.h, tp.cellcat, 1024, s)) return 1;
+        }
     }
-    if (bilstm_finals(tp, state, sl, B, T, true, s)) return 1;
+    if (bilstm_finals(tp, state, sl, B, T, !lens, s)) return 1;      // a masked call has captured the forward finals row by row
     if (launch_gemm1(pro.e_c(), s, "train_prologue_gemm")) return 1;
     if (launch_stop_const(state + sl.ecell, w.stop_tail, w.stop_bias, B, state + sl.stopc, s)) return 1;
     if (launch_gemm1(pro.enc_proj(), s, "train_prologue_gemm")) return 1;
-    if (launch_copy_cols(tp.cat, PRO_CAT, 0, state + sl.enc, 512, 0, 1, BT, 512, s)) return 1;
+    // with lengths: rows t >= len_b become zeros on the way (the same-pad K / V convolutions then read past a clip's end what a solo call reads as padding)
+    if (lens ? launch_mask_copy_rows(tp.cat, PRO_CAT, state + sl.enc, 512, lens.dev, B, T, 512, s)
+             : launch_copy_cols(tp.cat, PRO_CAT, 0, state + sl.enc, 512, 0, 1, BT, 512, s)) return 1;
     BnLayer bn[8]; int rows[8];
     {
         GemmBatch gb{};
@@ -1149,7 +1192,7 @@ static int prologue_train_fwd(l2s_model* m, const float* vis, const float* emb, 
         }
         if (m->bn_batch ? launch_gemm_batch_stats(m, gb, tp.stats, tp.stats_group, bn, rows, s, "train_content_agg_stats", "train_content_agg_epilogue")
                         : launch_gemm(gb, s, "train_content_agg_gemm")) return 1;
-        if (launch_pool_cat(pro.pool_cat(), s)) return 1;
+        if (lens ? launch_pool_cat_masked(pro.pool_cat(), pro.pool_div(), lens.dev, s) : launch_pool_cat(pro.pool_cat(), s)) return 1;
         if (launch_gemm1(pro.ct_bott(), s, "train_content_gemm")) return 1;
         GemmBatch g1 = pro.ct_pair0(), g2 = pro.ct_pair2();
         GemmP p3 = pro.ct_fc4();
@@ -1158,6 +1201,8 @@ static int prologue_train_fwd(l2s_model* m, const float* vis, const float* emb, 
         if (launch_gemm(g2, s, "train_content_gemm")) return 1;
         if (launch_gemm1(p3, s, "train_content_gemm")) return 1;
         if (launch_gumbel_softmax(tp.logits, gumbel, R, VOC, 0.1f, tp.zsoft, VOCP, content_dis ? content_dis : tp.dis, s)) return 1;
+        // slots i >= m_b: zero z (so zero values) and zero content_dis - whatever their Gumbel rows hold
+        if (lens && launch_zero_slot_rows(tp.zsoft, VOCP, content_dis ? content_dis : tp.dis, VOC, B, tp.m, lens.dev, s)) return 1;
         if (content_dis) L2S_CHECK_HIP(hipMemcpyAsync(tp.dis, content_dis, sizeof(float) * R * VOC, hipMemcpyDeviceToDevice, s));
         if (launch_gemm1(pro.ct_emb(), s, "train_content_gemm")) return 1;
     }
@@ -1195,8 +1240,7 @@ __global__ __launch_bounds__(256) void content_softmax_bwd_kernel(const float* _
 }
 
 // backward of the adaptive average pooling + concatenation: dpooled (B,m,nmaps*C) -> d map_j[b][t][c] (+)= sum over bins containing t of dpooled / binsize
-struct PoolBwdP { float* dx[5]; int L[5]; int ld[5]; int acc[5]; int nmaps; int B, m, C; const float* dp; };
-__global__ __launch_bounds__(256) void pool_cat_bwd_kernel(const PoolBwdP p) {
+__global__ __launch_bounds__(256) void pool_cat_bwd_kernel(const PoolCatBwdP p) {      // (the masked form, with per-clip bins: masked_train.hip)
     int64_t total = 0;
     for (int j = 0; j < p.nmaps; ++j) total += (int64_t)p.B * p.L[j] * p.C;
     for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * 256) {
@@ -1230,6 +1274,8 @@ __global__ __launch_bounds__(256) void add3_kernel(const float* __restrict__ a, 
     }
 }
 
+// what a masked backward carves on top: dh_last, the product of the reset rows (B,512 each) and their gate gradients (frag16, K = 2048)
+static int64_t pro_bwd_ws_extra_masked(int B) { return (int64_t)B * 1024 + (int64_t)pad16(B) * 2048 + 64 * 4; }
 static int64_t pro_bwd_ws_floats(int B, int T) {
     int L[4]; const int m = content_lens(T, L);
     const int64_t BT = (int64_t)B * T, R = (int64_t)B * m, Bp = pad16(B);
@@ -1241,7 +1287,10 @@ static int64_t pro_bwd_ws_floats(int B, int T) {
 // Inputs: gradients of the state the loop consumed.  Outputs: every prologue parameter gradient (bound slots) and dvis (B,T,1024).
 static int prologue_train_bwd(l2s_model* m, const float* vis, const float* emb, int B, int T, float* state, float* tape_base, float* wbuf,
                               const float* dk, const float* dv, const float* dckey, const float* dcval, const float* dh_init, const float* de_c,
-                              const float* ddis, float* dvis, void* ws, int64_t ws_bytes, hipStream_t s) {
+                              const float* ddis, float* dvis, void* ws, int64_t ws_bytes, hipStream_t s, ClipLens lens = {}) {
+    // lens (l2s_train_prologue_masked_bwd; running statistics): the gradients arrive with zero rows past every clip's frames and slots (attn_bwd_kernel<true>),
+    // every epilogue backward keeps a zero row zero, and what is laid over the unmasked backward are the adjoints of the forward's row kernels: slot rows of
+    // d logits, the masked pool_cat backward, pad rows of d enc, capture and reset of the recurrence
     const Weights& w = m->w;
     ProTape tp = pro_tape(tape_base, B, T);
     TrainW tw = train_w(wbuf);
@@ -1263,6 +1312,8 @@ static int prologue_train_bwd(l2s_model* m, const float* vis, const float* emb, 
     float* dmap[4]; for (int j = 0; j < 4; ++j) dmap[j] = bp.f((int64_t)B * tp.L[j] * 512);
     float* small = bp.f(8192);
     float* skp = bp.f((int64_t)16 * BT * 512);                  // split-K partials of the wide input gradients
+    float* dh_last0 = lens ? bp.f((int64_t)B * 512) : nullptr; float* dh_rst = lens ? bp.f((int64_t)B * 512) : nullptr;
+    float* dg_reset = lens ? bp.f((int64_t)Bp * 2048) : nullptr;
     L2S_REQUIRE(!bp.overflow, "training prologue backward workspace too small");
     auto G = [&](const std::string& k) { return m->grad(D + k); };
     auto Cn = [&](const std::string& k) { return m->canon(D + k); };
@@ -1341,6 +1392,7 @@ static int prologue_train_bwd(l2s_model* m, const float* vis, const float* emb, 
             hipLaunchKernelGGL(copy_rows_kernel, dim3(ew(VOC * 256)), dim3(256), 0, s, tmpE, 256, g, 256, VOC, 256);
         }
         hipLaunchKernelGGL(content_softmax_bwd_kernel, dim3(R), dim3(256), 0, s, tp.zsoft, dzs, 504, tp.dis, ddis, VOC, 10.0f, dl, 504);
+        if (lens && launch_zero_slot_rows(dl, 504, nullptr, 0, B, mT, lens.dev, s)) return 1;      // slots i >= m_b: the forward wrote constants, whatever ddis holds there
         // location_fc.4 (+SiLU): dz4 padded to 504 columns
         if (launch_fill(dz4, (int64_t)R * 504, 0.f, s)) return 1;
         if (act(dl, 504, tp.zf4, VOC, dz4, 504, R, VOC, ACT_SILU, nullptr, nullptr, nullptr, nullptr, G("content.location_fc.4.bias"), nullptr, nullptr, nullptr)) return 1;
@@ -1367,11 +1419,16 @@ static int prologue_train_bwd(l2s_model* m, const float* vis, const float* emb, 
         if (dW(dwv, 256, 256, tp.pooled, 2560, 2560, R, G("content.bottleneck.weight"), 2560)) return 1;
         if (float* g = G("content.bottleneck.bias")) { if (colsum(dwv, R, 256, partials, dzt, g, false, s)) return 1; }
         if (dX(dwv, 256, 256, w.ct_bott.W, 2560, dpooled, 2560, 2560, R, false)) return 1;
-        PoolBwdP pb{};
+        PoolCatBwdP pb{};
         pb.dx[0] = dcat; pb.L[0] = T; pb.ld[0] = 4608; pb.acc[0] = 1;
         for (int j = 0; j < 4; ++j) { pb.dx[j + 1] = dmap[j]; pb.L[j + 1] = tp.L[j]; pb.ld[j + 1] = 512; pb.acc[j + 1] = 0; }
         pb.nmaps = 5; pb.B = B; pb.m = mT; pb.C = 512; pb.dp = dpooled;
-        hipLaunchKernelGGL(pool_cat_bwd_kernel, dim3(2048), dim3(256), 0, s, pb);
+        if (lens) {
+            PoolDiv pd{};
+            pd.div[0] = 1;
+            for (int j = 0; j < 4; ++j) pd.div[j + 1] = CT_KS[j];
+            if (launch_pool_cat_masked_bwd(pb, pd, lens.dev, s)) return 1;
+        } else hipLaunchKernelGGL(pool_cat_bwd_kernel, dim3(2048), dim3(256), 0, s, pb);
         for (int j = 0; j < 4; ++j) {
             const int k = CT_KS[j], Lj = tp.L[j];
             const std::string c = "content.agg." + std::to_string(j);
@@ -1390,6 +1447,8 @@ static int prologue_train_bwd(l2s_model* m, const float* vis, const float* emb, 
     }
     // ---- D. enc = encoder_proj(rnn_out) + s_a + residual_bottleneck(vis)
     hipLaunchKernelGGL(add3_kernel, dim3(2048), dim3(256), 0, s, dcat, 4608, dxc, 512, denc, 512, (int64_t)BT, 512);
+    // with lengths the forward replaced rows t >= len_b of enc by zeros: what the same-pad convolutions sent back to those rows stops here
+    if (lens && launch_zero_pad_rows(denc, 512, lens.dev, B, T, 512, s)) return 1;
     if (dW(denc, 512, 512, tp.rnn, 1024, 1024, BT, G("encoder_proj.linear_layer.weight"), 1024)) return 1;
     if (dW(denc, 512, 512, vis, 1024, 1024, BT, G("residual_bottleneck.weight"), 1024)) return 1;
     if (colsum(denc, BT, 512, partials, gconv, small, false, s)) return 1;
@@ -1410,16 +1469,40 @@ static int prologue_train_bwd(l2s_model* m, const float* vis, const float* emb, 
     // (d h_{step-1} = dg_step @ W_hh + d rnn_out): one launch per time step for the pair (was four: cell kernel + product, per direction).
     if (launch_fill(ds_e, (int64_t)B * 512, 0.f, s)) return 1;
     auto t_of = [&](int d, int step) { return d == 0 ? step : T - 1 - step; };
+    // with lengths: the plan of the forward's row kernels, walked backwards.  Forward direction: the finals of a clip with len_b < T were captured after
+    // step len_b - 1, so dh_init / d cellcat enter at that step's cell backward and nothing flows through the pad steps after it.  Backward direction: the
+    // step T - len_b of such a clip started from s_e, so what its cell backward carries goes to d s_e and is cut
+    std::vector<int32_t> cap_steps(B), rst_steps(B);
+    int n_cap = 0, n_rst = 0;
+    if (lens) {
+        if (l2s_masked_bilstm_plan(lens.host, B, T, cap_steps.data(), rst_steps.data(), &n_cap, &n_rst)) return 1;
+        if (n_rst && launch_fill(dg_reset, (int64_t)Bp * 2048, 0.f, s)) return 1;
+    }
+    int cap_i = n_cap - 1, rst_i = n_rst - 1;
+    if (cap_i >= 0 && cap_steps[cap_i] == T - 1) --cap_i;      // the clips of full length: the unmasked injection below
     for (int d = 0; d < 2; ++d) {       // last processed step first: its dh is the decoder's initial-state gradient plus d rnn_out
         hipLaunchKernelGGL(copy_rows_kernel, dim3(ew(B * 512)), dim3(256), 0, s, dcellcat + d * 512, 1024, dccd[d], 512, B, 512);
         const int step = T - 1, t = t_of(d, step);
-        hipLaunchKernelGGL(lstm_bwd_kernel, dim3(ew(B * 512)), dim3(256), 0, s, dh_init + (int64_t)d * B * 512, 512, drnn + (int64_t)t * 1024 + d * 512, T * 1024, dccd[d],
+        const float* dh_last = dh_init + (int64_t)d * B * 512;
+        if (lens && d == 0 && n_cap && cap_steps[0] < T - 1) {      // some clip is shorter than T
+            if (launch_bilstm_capture_adj_init(dh_init, dh_last0, dccd[0], drnn, 1024, lens.dev, B, T, s)) return 1;
+            dh_last = dh_last0;
+        }
+        hipLaunchKernelGGL(lstm_bwd_kernel, dim3(ew(B * 512)), dim3(256), 0, s, dh_last, 512, drnn + (int64_t)t * 1024 + d * 512, T * 1024, dccd[d],
                            tp.gates[d] + (int64_t)step * B * 2048, tp.cproc[d] + (int64_t)step * B * 512, tp.cproc[d] + (int64_t)(step + 1) * B * 512, B, 512, f_dgd[d][0],
                            dgk2[d] + (int64_t)step * B * 2048, dgbt[d] + (int64_t)t * 2048, (int64_t)T * 2048);
     }
     for (int step = T - 1; step >= 0; --step) {
         const int cur = (T - 1 - step) & 1;
         SkinnyBatch sb{}; TrainSkinnyBatch tb{};
+        if (cap_i >= 0 && cap_steps[cap_i] == step - 1) {      // this launch's epilogue is the cell backward of step - 1 = len_b - 1: the captured c's gradient
+            --cap_i;
+            if (launch_bilstm_capture_adj_cell(dcellcat, 1024, dccd[0], lens.dev, B, step, s)) return 1;
+        }
+        if (rst_i >= 0 && rst_steps[rst_i] == step) {          // this launch's product is d(predecessor of step T - len_b): for those rows that is s_e
+            --rst_i;
+            if (launch_bilstm_reset_adj(f_dgd[1][cur], dg_reset, dccd[1], ds_e, lens.dev, B, T - step, s)) return 1;
+        }
         for (int d = 0; d < 2; ++d) {
             sb.p[d] = bsk(tw.bhh[d], 512, 2048, B, f_dgd[d][cur], dhd[d], 512); sb.ntiles[d] = 32;
             if (step > 0) {             // the cell of step-1 in this product's epilogue
@@ -1433,6 +1516,10 @@ static int prologue_train_bwd(l2s_model* m, const float* vis, const float* emb, 
         }
         sb.count = 2;
         if (launch_train_skinny(sb, tb, s, "train_bwd_bilstm_dx")) return 1;
+    }
+    if (n_rst) {      // the reset rows: d s_e += (gate gradients of their first real step) W_hh, one product for all of them (the other rows of dg_reset are zeros)
+        if (run1(bsk(tw.bhh[1], 512, 2048, B, dg_reset, dh_rst, 512), s, "train_bwd_bilstm_dx")) return 1;
+        if (add_into(dh_rst, ds_e, (int64_t)B * 512, s)) return 1;
     }
     for (int d = 0; d < 2; ++d) {
         const std::string suf = d == 0 ? "l0" : "l0_reverse";
@@ -1522,6 +1609,70 @@ int l2s_train_prologue_bwd(l2s_model* m, const float* vis, const float* emb, int
     L2S_REQUIRE(m->canon("decoder.encoder_rnn.weight_hh_l0") != nullptr, "parameters not bound (l2s_train_bind)");
     Bf16Scope bf16scope(m->opt.train_bf16);      // GEMMs / Conv1d stacks with bf16 operands when the model asks for it (fp32 accumulation)
     return prologue_train_bwd(m, vis, emb, B, T, state, tape, wbuf, dk, dv, dckey, dcval, dh_init, de_c, dcontent_dis, dvis, ws, ws_bytes, (hipStream_t)stream);
+}
+
+// ---- per-clip video lengths (include/l2s.h "training with per-clip video lengths").  Every masked call writes its device length table behind the
+// unmasked tape (the *_tape_floats_masked sizers), on its stream, before its first launch: forward and backward each carry their own copy of the lengths
+static int64_t tape_table_floats(int B) { return align_up(train_len_table_words(B), 64) + 64; }
+static int masked_train_lens(const l2s_model* m, const int32_t* video_lengths, int B, int T, float* tape, int64_t tape_floats, bool has_bn, hipStream_t s, ClipLens& lens) {
+    if (check_lengths(video_lengths, B, T)) return 1;
+    L2S_REQUIRE(!has_bn || !m->bn_batch, "the l2s_train_*_masked_fwd / _masked_bwd entry points run on running statistics: batch_stats = 1 (l2s_train_set_bn) with video_lengths is not supported");
+    L2S_REQUIRE(!has_bn || !m->opt.train_bf16, "option \"train_bf16\" with video_lengths is not supported");
+    lens = {reinterpret_cast<int*>(tape + align_up(tape_floats, 64)), video_lengths};
+    return launch_train_len_table(video_lengths, B, lens.dev, s);
+}
+
+int64_t l2s_train_steps_tape_floats_masked(int B, int S) { return align_up(step_tape_floats(B, S), 64) + tape_table_floats(B); }
+int64_t l2s_train_prologue_tape_floats_masked(int B, int T) { return align_up(pro_tape_floats(B, T), 64) + tape_table_floats(B); }
+int64_t l2s_train_prologue_ws_bytes_masked(int B, int T) {
+    return (std::max(pro_fwd_ws_floats(B), pro_bwd_ws_floats(B, T) + pro_bwd_ws_extra_masked(B)) + 1024) * (int64_t)sizeof(float);
+}
+
+int l2s_train_steps_masked_fwd(l2s_model* m, float* state, int B, int T, int S, const float* teacher, const uint8_t* teacher_mask,
+                               const uint8_t* teacher_mask_dev, float* tape, float* mel, float* stop, float* attn_logits, const float* drop_prenet,
+                               const float* drop_attn, const float* drop_rnn, void* ws, int64_t ws_bytes, void* stream, const int32_t* video_lengths) {
+    L2S_REQUIRE(m && m->finalized && m->has_dec && state && tape && mel && stop && attn_logits && ws, "bad arguments");
+    L2S_REQUIRE(S >= 1 && S <= L2S_MAX_STEPS && B >= 1 && B <= 96, "sizes");
+    L2S_REQUIRE(train_attn_sizes_ok(T), "T must be in [7, 300] (m = T / 7 content keys <= ATT_MAXM)");
+    L2S_REQUIRE(!teacher || (teacher_mask && teacher_mask_dev), "teacher frames need the step mask on host and device");
+    ClipLens lens;
+    if (masked_train_lens(m, video_lengths, B, T, tape, step_tape_floats(B, S), false, (hipStream_t)stream, lens)) return 1;
+    return decode_train_fwd(m, state, B, T, S, teacher, teacher_mask, teacher_mask_dev, tape, mel, stop, attn_logits, StepDrop{drop_prenet, drop_attn, drop_rnn}, ws,
+                            ws_bytes, (hipStream_t)stream, lens.dev);
+}
+
+int l2s_train_steps_masked_bwd(l2s_model* m, float* state, int B, int T, int S, const uint8_t* teacher_mask, float* tape, const float* attn_logits,
+                               const float* dmel, const float* dstop, float* wbuf, float* dk, float* dv, float* dckey, float* dcval, float* dh_init,
+                               float* de_c, const float* drop_prenet, const float* drop_attn, const float* drop_rnn, void* ws, int64_t ws_bytes, void* stream,
+                               const int32_t* video_lengths) {
+    L2S_REQUIRE(m && m->finalized && m->has_dec && state && tape && attn_logits && dmel && dstop && wbuf && dk && dv && dckey && dcval && dh_init && de_c && ws,
+                "bad arguments");
+    L2S_REQUIRE(S >= 1 && S <= L2S_MAX_STEPS && B >= 1 && B <= 96, "sizes");
+    L2S_REQUIRE(train_attn_sizes_ok(T), "T must be in [7, 300] (m = T / 7 content keys <= ATT_MAXM)");
+    ClipLens lens;
+    if (masked_train_lens(m, video_lengths, B, T, tape, step_tape_floats(B, S), false, (hipStream_t)stream, lens)) return 1;
+    return decode_train_bwd(m, state, B, T, S, teacher_mask, tape, attn_logits, dmel, dstop, wbuf, dk, dv, dckey, dcval, dh_init, de_c,
+                            StepDrop{drop_prenet, drop_attn, drop_rnn}, ws, ws_bytes, (hipStream_t)stream, lens.dev);
+}
+
+int l2s_train_prologue_masked_fwd(l2s_model* m, const float* vis, const float* emb, const float* gumbel, int B, int T, float* state, float* content_dis,
+                                  float* tape, void* ws, int64_t ws_bytes, void* stream, const int32_t* video_lengths) {
+    L2S_REQUIRE(m && m->finalized && m->has_dec && vis && emb && gumbel && state && tape && ws, "bad arguments");
+    L2S_REQUIRE(B >= 1 && B <= 96 && T >= 7 && T <= L2S_MAX_STEPS, "sizes");
+    ClipLens lens;
+    if (masked_train_lens(m, video_lengths, B, T, tape, pro_tape_floats(B, T), true, (hipStream_t)stream, lens)) return 1;
+    return prologue_train_fwd(m, vis, emb, gumbel, B, T, state, content_dis, tape, ws, ws_bytes, (hipStream_t)stream, lens);
+}
+
+int l2s_train_prologue_masked_bwd(l2s_model* m, const float* vis, const float* emb, int B, int T, float* state, float* tape, float* wbuf, const float* dk,
+                                  const float* dv, const float* dckey, const float* dcval, const float* dh_init, const float* de_c, const float* dcontent_dis,
+                                  float* dvis, void* ws, int64_t ws_bytes, void* stream, const int32_t* video_lengths) {
+    L2S_REQUIRE(m && m->finalized && m->has_dec && vis && emb && state && tape && wbuf && dk && dv && dckey && dcval && dh_init && de_c && dvis && ws, "bad arguments");
+    L2S_REQUIRE(B >= 1 && B <= 96 && T >= 7 && T <= L2S_MAX_STEPS, "sizes");
+    L2S_REQUIRE(m->canon("decoder.encoder_rnn.weight_hh_l0") != nullptr, "parameters not bound (l2s_train_bind)");
+    ClipLens lens;
+    if (masked_train_lens(m, video_lengths, B, T, tape, pro_tape_floats(B, T), true, (hipStream_t)stream, lens)) return 1;
+    return prologue_train_bwd(m, vis, emb, B, T, state, tape, wbuf, dk, dv, dckey, dcval, dh_init, de_c, dcontent_dis, dvis, ws, ws_bytes, (hipStream_t)stream, lens);
 }
 
 int64_t l2s_train_postnet_tape_floats(int B, int S) { return post_tape_floats(B, S); }

@@ -13,6 +13,7 @@
 #include "l2s_common.h"
 #include "l2s_model.h"
 #include "decoder_stages.h"
+#include "pdecode.h"      // ClipLens
 
 #include <algorithm>
 #include <string>
@@ -79,11 +80,32 @@ static int64_t enc_tape_layout(EncTape* t, float* base, int B, int T, int H) {
     return o + 64;
 }
 
+// What a masked call keeps behind the unmasked tape: the pooled front-end map of the PADDED batch (the tape's x[0] is then the compact list of real frames),
+// the compact normalised features, and the device length table
+struct EncMaskedTape { float* x0p; float* featc; int* lens; };
+static int64_t enc_tape_table_floats(int B) { return align_up(train_len_table_words(B), 64) + 64; }
+static int64_t enc_masked_tape_layout(EncMaskedTape* t, float* base, int B, int T, int H) {
+    int64_t o = align_up(enc_tape_layout(nullptr, nullptr, B, T, H), 64);
+    auto take = [&](int64_t n) { float* r = base ? base + o : nullptr; o += align_up(n, 64); return r; };
+    float* x0p = take((int64_t)B * T * (H / 4) * (H / 4) * STAGE_CH[0]);
+    float* featc = take((int64_t)B * T * LAST_CH);
+    float* lens = take(enc_tape_table_floats(B));
+    if (t) { t->x0p = x0p; t->featc = featc; t->lens = reinterpret_cast<int*>(lens); }
+    return o + 64;
+}
+static int sum_lengths(const int32_t* lens_host, int B) { int n = 0; for (int b = 0; b < B; ++b) n += lens_host[b]; return n; }
+
+// lens (l2s_train_encoder_masked_fwd; running statistics): the front-end runs on the padded batch - its temporal zero padding is what makes a padded clip's
+// real frames see what a solo clip sees - then the real frames of the pooled map are gathered into a compact list, the trunk and conv_last run at
+// NF = sum len_b through the unchanged launches, and the normalised features go back to the padded rows (zeros at t >= len_b)
 static int encoder_train_fwd(l2s_model* m, const float* video, int B, int T, int H, int W, const float* emb, float* vis, float* feat, float* tape_base,
-                             hipStream_t s) {
+                             hipStream_t s, ClipLens lens = {}) {
     const Weights& w = m->w;
     EncTape tp; enc_tape_layout(&tp, tape_base, B, T, H);
+    EncMaskedTape mt{};
+    if (lens) { enc_masked_tape_layout(&mt, tape_base, B, T, H); tp.NF = sum_lengths(lens.host, B); }
     const int NF = tp.NF;
+    float* const x0_front = lens ? mt.x0p : tp.x[0];      // where the front-end writes its pooled map
     const bool bnb = m->bn_batch;
     // 1x1 conv + BN + ReLU; with batch statistics: stats pass -> finalize -> the same fused kernel with this batch's scale/shift
     auto run_pw = [&](GemmP p, float* zbuf, int id, const std::string& key, const char* name) -> int {
@@ -122,7 +144,8 @@ static int encoder_train_fwd(l2s_model* m, const float* video, int B, int T, int
             if (bn_stats_finalize(tp.stats, nblk, 48, px, L, m->bn_momentum, s)) return 1;
             if (launch_bn_apply(tp.z0, px, 24, 24, 0, L.scale, L.shift, s, true)) return 1;
             if (launch_frontend_pool(tp.z0, w.fe.slope, NF, H / 2, W / 2, tp.x[0], s)) return 1;
-        } else if (launch_frontend(fe, video, B, T, H, W, tp.x[0], s, tp.z0)) return 1;
+        } else if (launch_frontend(fe, video, B, T, H, W, x0_front, s, tp.z0)) return 1;
+        if (lens && launch_frame_rows(mt.x0p, tp.x[0], lens.dev, B, T, (int64_t)(H / 4) * (H / 4) * STAGE_CH[0], true, s)) return 1;
     }
     for (int u = 0; u < N_UNITS; ++u) {
         const UnitW& U = w.unit[u];
@@ -148,6 +171,10 @@ static int encoder_train_fwd(l2s_model* m, const float* video, int B, int T, int
     const int hl = tp.h[N_UNITS];
     const int64_t px = (int64_t)NF * hl * hl;
     if (run_pw(pw_gemm(tp.x[N_UNITS], STAGE_CH[3], 0, w.conv_last, tp.last, LAST_CH, 0, 1, px, LAST_CH, STAGE_CH[3], ACT_RELU, false), tp.lastz, 81, "trunk.1.1", "train_conv_last_gemm")) return 1;
+    if (lens) {      // compact features first (the sums of the unmasked kernel, frame by frame), then the padded rows
+        if (launch_pool_norm_cat(tp.last, NF, hl * hl, LAST_CH, nullptr, L2S_D_EMB, T, nullptr, L2S_D_VIS, mt.featc, s)) return 1;
+        return launch_feat_rows_store(mt.featc, LAST_CH, emb, L2S_D_EMB, lens.dev, B, T, vis, L2S_D_VIS, feat, s);
+    }
     if (launch_pool_norm_cat(tp.last, NF, hl * hl, LAST_CH, emb, L2S_D_EMB, T, vis, L2S_D_VIS, feat, s)) return 1;
     return 0;
 }
@@ -486,25 +513,30 @@ static int64_t enc_bwd_ws_floats(int B, int T, int H) {
     return n + 64 * 32;
 }
 
+// lens: the mirror of the masked forward - dfeat rows of the real frames are gathered, the trunk's backward runs at NF = sum len_b, the gradient of the
+// pooled map is scattered into the padded batch with zero pad frames, and the front-end's backward runs on the padded batch (NFp frames)
 static int encoder_train_bwd(l2s_model* m, const float* video, int B, int T, int H, int W, const float* dfeat, int ld_df, float* tape_base, void* ws, int64_t ws_bytes,
-                             hipStream_t s) {
+                             hipStream_t s, ClipLens lens = {}) {
     const Weights& w = m->w;
     EncTape tp; enc_tape_layout(&tp, tape_base, B, T, H);
-    const int NF = tp.NF, Hc = H / 2, Hp = H / 4;
+    const int NFp = tp.NF;                                  // frames of the padded batch: the front-end's
+    if (lens) tp.NF = sum_lengths(lens.host, B);
+    const int NF = tp.NF, Hc = H / 2, Hp = H / 4;           // frames of the trunk
     const std::string E = "encoder.";
     Bump bp(ws, ws_bytes);
-    const int64_t maxact = std::max<int64_t>((int64_t)NF * Hp * Hp * 24, (int64_t)NF * ((Hp + 1) / 2) * ((Hp + 1) / 2) * 116);
-    const int64_t maxhalf = (int64_t)NF * Hp * Hp * 58;
+    const int64_t maxact = std::max<int64_t>((int64_t)NFp * Hp * Hp * 24, (int64_t)NFp * ((Hp + 1) / 2) * ((Hp + 1) / 2) * 116);
+    const int64_t maxhalf = (int64_t)NFp * Hp * Hp * 58;
     float* dA = bp.f(maxact); float* dB = bp.f(maxact);
     float* g = bp.f(maxhalf); float* dt = bp.f(maxhalf); float* gd = bp.f(maxhalf); float* dt1 = bp.f(maxhalf);
-    float* dlast = bp.f((int64_t)NF * 9 * LAST_CH); float* gconv = bp.f((int64_t)NF * 9 * LAST_CH);
-    float* dconv = bp.f((int64_t)NF * Hc * Hc * 24);
+    float* dlast = bp.f((int64_t)NFp * 9 * LAST_CH); float* gconv = bp.f((int64_t)NFp * 9 * LAST_CH);
+    float* dconv = bp.f((int64_t)NFp * Hc * Hc * 24);
     const int fd_strips = (Hc + FD_CR - 1) / FD_CR;
-    float* fdp = bp.f((int64_t)NF * fd_strips * FD_PART);
+    float* fdp = bp.f((int64_t)NFp * fd_strips * FD_PART);
     const int64_t splitk_cap = (int64_t)64 * LAST_CH * STAGE_CH[3];     // floats; 256 slices of a <= 232 x 232 gradient fit as well
     float* skp = bp.f(splitk_cap);
-    float* dwp = bp.f((int64_t)DW_RS * 9 * 512); float* abp = bp.f((int64_t)AB_RS * 3 * 1024); float* fbp = bp.f((int64_t)NF * fb_strips(Hc) * 3 * 24);
+    float* dwp = bp.f((int64_t)DW_RS * 9 * 512); float* abp = bp.f((int64_t)AB_RS * 3 * 1024); float* fbp = bp.f((int64_t)NFp * fb_strips(Hc) * 3 * 24);
     float* totals = bp.f(2 * 1024);
+    float* dfeatc = lens ? bp.f((int64_t)NFp * LAST_CH) : nullptr;      // dfeat of the real frames, compact
     L2S_REQUIRE(!bp.overflow, "encoder training backward workspace too small");
     auto G = [&](const std::string& k) { return m->grad(E + k); };
     auto Cn = [&](const std::string& k) { return m->canon(E + k); };
@@ -557,7 +589,10 @@ static int encoder_train_bwd(l2s_model* m, const float* video, int B, int T, int
     const int64_t pxl = (int64_t)NF * P;
     {
         ProfScope ps("train_bwd_pool_norm", s);
-        hipLaunchKernelGGL(pool_norm_bwd_kernel, dim3(NF), dim3(256), 0, s, tp.last, P, LAST_CH, dfeat, ld_df, dlast);
+        if (lens) {
+            if (launch_feat_rows_gather(dfeat, ld_df, LAST_CH, lens.dev, B, T, dfeatc, s)) return 1;
+            hipLaunchKernelGGL(pool_norm_bwd_kernel, dim3(NF), dim3(256), 0, s, tp.last, P, LAST_CH, dfeatc, LAST_CH, dlast);
+        } else hipLaunchKernelGGL(pool_norm_bwd_kernel, dim3(NF), dim3(256), 0, s, tp.last, P, LAST_CH, dfeat, ld_df, dlast);
     }
     if (epi(dlast, LAST_CH, 1, 0, bnb ? tp.lastz : tp.last, LAST_CH, 1, 0, gconv, pxl, LAST_CH, ACT_RELU, w.conv_last.scale, "trunk.1.1", 81)) return 1;
     float* dy = dA; float* dx = dB;
@@ -595,31 +630,35 @@ static int encoder_train_bwd(l2s_model* m, const float* video, int B, int T, int
     }
 
     // ---- front-end: MaxPool + PReLU + BN backward, then the Conv3d weight gradient
+    if (lens) {      // the gradient of the compact pooled map goes back to the padded batch; pad frames get zeros
+        if (launch_frame_rows(dy, dx, lens.dev, B, T, (int64_t)Hp * Hp * STAGE_CH[0], false, s)) return 1;
+        std::swap(dy, dx);
+    }
     {
         const float* gamma = Cn("frontend3D.1.weight"); const float* beta = Cn("frontend3D.1.bias");
         L2S_REQUIRE(gamma && beta, "encoder parameters not bound (l2s_train_bind)");
         ProfScope ps("train_bwd_frontend_pool_prelu_bn", s);
         const float* fscale = bnb ? bn_scale(tp, 0) : w.fe.scale;
-        const int fb_blocks = NF * fb_strips(Hc);
-        if (Hc == 48) hipLaunchKernelGGL(frontend_bwd_kernel<48>, dim3(fb_strips(Hc), NF), dim3(256), 0, s, tp.z0, dy, NF, w.fe.slope, fscale, gamma, beta, dconv, fbp);
-        else hipLaunchKernelGGL(frontend_bwd_kernel<44>, dim3(fb_strips(Hc), NF), dim3(256), 0, s, tp.z0, dy, NF, w.fe.slope, fscale, gamma, beta, dconv, fbp);
+        const int fb_blocks = NFp * fb_strips(Hc);
+        if (Hc == 48) hipLaunchKernelGGL(frontend_bwd_kernel<48>, dim3(fb_strips(Hc), NFp), dim3(256), 0, s, tp.z0, dy, NFp, w.fe.slope, fscale, gamma, beta, dconv, fbp);
+        else hipLaunchKernelGGL(frontend_bwd_kernel<44>, dim3(fb_strips(Hc), NFp), dim3(256), 0, s, tp.z0, dy, NFp, w.fe.slope, fscale, gamma, beta, dconv, fbp);
         float* outs[3] = {G("frontend3D.1.bias"), G("frontend3D.1.weight"), G("frontend3D.2.weight")};
         for (int k = 0; k < 3; ++k) {
             float* dst = k < 2 ? totals + k * 24 : outs[2];                  // r0, r1 are needed by the batch-statistics correction as well
             if (dst) hipLaunchKernelGGL(reduce_partials_kernel, dim3(1), dim3(1024), 0, s, fbp + k * 24, fb_blocks, 72, 1, 24, dst, 0, 1, 0);
             if (k < 2 && outs[k]) L2S_CHECK_HIP(hipMemcpyAsync(outs[k], totals + k * 24, 24 * sizeof(float), hipMemcpyDeviceToDevice, s));
         }
-        if (bnb) { if (bn_train_fix(dconv, 24, tp.z0, 24, 1, 0, gamma, beta, fscale, totals, (int64_t)NF * Hc * Hc, 24, s)) return 1; }
+        if (bnb) { if (bn_train_fix(dconv, 24, tp.z0, 24, 1, 0, gamma, beta, fscale, totals, (int64_t)NFp * Hc * Hc, 24, s)) return 1; }
     }
     L2S_CHECK_HIP(hipGetLastError());
     if (float* gw = G("frontend3D.0.weight")) {
         {
             ProfScope ps("train_bwd_frontend_dw", s);
-            if (H == 96) hipLaunchKernelGGL(frontend_dw_kernel<96>, dim3(fd_strips, NF), dim3(256), 0, s, video, dconv, T, fdp);
-            else hipLaunchKernelGGL(frontend_dw_kernel<88>, dim3(fd_strips, NF), dim3(256), 0, s, video, dconv, T, fdp);
+            if (H == 96) hipLaunchKernelGGL(frontend_dw_kernel<96>, dim3(fd_strips, NFp), dim3(256), 0, s, video, dconv, T, fdp);
+            else hipLaunchKernelGGL(frontend_dw_kernel<88>, dim3(fd_strips, NFp), dim3(256), 0, s, video, dconv, T, fdp);
         }
         ProfScope ps("train_bwd_frontend_dw_reduce", s);
-        hipLaunchKernelGGL(reduce_partials_kernel, dim3((FD_PART + 63) / 64), dim3(1024), 0, s, fdp, NF * fd_strips, FD_PART, 1, FD_PART, gw, 0, 1, 0);
+        hipLaunchKernelGGL(reduce_partials_kernel, dim3((FD_PART + 63) / 64), dim3(1024), 0, s, fdp, NFp * fd_strips, FD_PART, 1, FD_PART, gw, 0, 1, 0);
     }
     L2S_CHECK_HIP(hipGetLastError());
     return 0;
@@ -634,6 +673,8 @@ extern "C" {
 
 int64_t l2s_train_encoder_tape_floats(int B, int T, int H) { return enc_tape_layout(nullptr, nullptr, B, T, H); }
 int64_t l2s_train_encoder_ws_bytes(int B, int T, int H) { return (enc_bwd_ws_floats(B, T, H) + 1024) * (int64_t)sizeof(float); }
+int64_t l2s_train_encoder_tape_floats_masked(int B, int T, int H) { return enc_masked_tape_layout(nullptr, nullptr, B, T, H); }
+int64_t l2s_train_encoder_ws_bytes_masked(int B, int T, int H) { return (enc_bwd_ws_floats(B, T, H) + (int64_t)B * T * LAST_CH + 64 + 1024) * (int64_t)sizeof(float); }
 
 int l2s_train_encoder_fwd(l2s_model* m, const float* video, int B, int T, int H, int W, const float* emb, float* vis, float* feat, float* tape, void* stream) {
     L2S_REQUIRE(m && m->finalized && m->has_enc && video && tape && (vis || feat), "bad arguments");
@@ -649,6 +690,36 @@ int l2s_train_encoder_bwd(l2s_model* m, const float* video, int B, int T, int H,
     L2S_REQUIRE(B >= 1 && T >= 1 && H == W && (H == 96 || H == 88) && ld_dfeat >= LAST_CH, "sizes");
     Bf16Scope bf16scope(m->opt.train_bf16);      // GEMMs / Conv1d stacks with bf16 operands when the model asks for it (fp32 accumulation)
     return encoder_train_bwd(m, video, B, T, H, W, dfeat, ld_dfeat, tape, ws, ws_bytes, (hipStream_t)stream);
+}
+
+// ---- per-clip video lengths (include/l2s.h "training with per-clip video lengths"): each call writes its device length table into its tape first
+static int enc_masked_lens(const l2s_model* m, const int32_t* video_lengths, int B, int T, int H, float* tape, hipStream_t s, ClipLens& lens) {
+    if (check_lengths(video_lengths, B, T)) return 1;
+    L2S_REQUIRE(!m->bn_batch, "the l2s_train_*_masked_fwd / _masked_bwd entry points run on running statistics: batch_stats = 1 (l2s_train_set_bn) with video_lengths is not supported");
+    L2S_REQUIRE(!m->opt.train_bf16, "option \"train_bf16\" with video_lengths is not supported");
+    EncMaskedTape mt{};
+    enc_masked_tape_layout(&mt, tape, B, T, H);
+    lens = {mt.lens, video_lengths};
+    return launch_train_len_table(video_lengths, B, lens.dev, s);
+}
+
+int l2s_train_encoder_masked_fwd(l2s_model* m, const float* video, int B, int T, int H, int W, const float* emb, float* vis, float* feat, float* tape, void* stream,
+                                 const int32_t* video_lengths) {
+    L2S_REQUIRE(m && m->finalized && m->has_enc && video && tape && (vis || feat), "bad arguments");
+    L2S_REQUIRE(B >= 1 && T >= 1 && H == W && (H == 96 || H == 88), "sizes");
+    L2S_REQUIRE(!vis || emb, "the visual sequence needs the speaker embedding");
+    ClipLens lens;
+    if (enc_masked_lens(m, video_lengths, B, T, H, tape, (hipStream_t)stream, lens)) return 1;
+    return encoder_train_fwd(m, video, B, T, H, W, emb, vis, feat, tape, (hipStream_t)stream, lens);
+}
+
+int l2s_train_encoder_masked_bwd(l2s_model* m, const float* video, int B, int T, int H, int W, const float* dfeat, int ld_dfeat, float* tape, void* ws, int64_t ws_bytes,
+                                 void* stream, const int32_t* video_lengths) {
+    L2S_REQUIRE(m && m->finalized && m->has_enc && video && dfeat && tape && ws, "bad arguments");
+    L2S_REQUIRE(B >= 1 && T >= 1 && H == W && (H == 96 || H == 88) && ld_dfeat >= LAST_CH, "sizes");
+    ClipLens lens;
+    if (enc_masked_lens(m, video_lengths, B, T, H, tape, (hipStream_t)stream, lens)) return 1;
+    return encoder_train_bwd(m, video, B, T, H, W, dfeat, ld_dfeat, tape, ws, ws_bytes, (hipStream_t)stream, lens);
 }
 
 }  // extern "C"

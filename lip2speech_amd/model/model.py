@@ -28,7 +28,9 @@ class _HipTrainStep(torch.autograd.Function):
     parameter of the model - it only makes autograd call `backward`."""
 
     @staticmethod
-    def forward(ctx, anchor, model, video, emb, gumbel, mels, mask, drop):
+    def forward(ctx, anchor, model, video, emb, gumbel, mels, mask, drop, lens=None):
+        # lens (`Lip2Speech.train_video_lengths`): the host lengths of a ZERO-padded batch - the three stages that see the video run their *_masked
+        # entry points (include/l2s.h "training with per-clip video lengths"), forward and backward
         nm = model.native_model()
         B, _, T, _, _ = video.shape
         S = mels.shape[2]
@@ -36,17 +38,24 @@ class _HipTrainStep(torch.autograd.Function):
         ctx.bn_batch = bool(model.training)                 # nn.Module.train(): batch statistics + running-statistics update (in the bound buffers)
         nm.train_set_bn(ctx.bn_batch)
         pdrop = native.postnet_drop_pack(drop["post"]) if drop.get("post") is not None else None
-        vis, _, etape = nm.train_encoder_fwd(video, emb)
-        if drop.get("feat") is not None:
-            vis[:, :, :768] *= drop["feat"]                 # F.dropout(self.encoder(video_frames), 0.1, self.training), model.py:26
-        state, dis, ptape = nm.train_prologue_fwd(vis, emb, gumbel)
+        vis, _, etape = nm.train_encoder_fwd(video, emb, video_lengths=lens)
+        real = None
+        if lens is not None:                                # (B,T,1): frames a clip has; the multipliers of its pad rows are never read
+            real = (torch.arange(T, device=video.device)[None, :] < torch.as_tensor(list(lens), device=video.device)[:, None]).unsqueeze(2)
+        if drop.get("feat") is not None:                    # F.dropout(self.encoder(video_frames), 0.1, self.training), model.py:26
+            if real is None:
+                vis[:, :, :768] *= drop["feat"]
+            else:
+                vis[:, :, :768] = torch.where(real, vis[:, :, :768] * drop["feat"], torch.zeros((), device=video.device))
+        state, dis, ptape = nm.train_prologue_fwd(vis, emb, gumbel, video_lengths=lens)
         teacher = None
         if mask is not None:
             bos = model.decoder.BOS.detach().to(torch.float32).reshape(1, 1, -1).expand(B, 1, -1)
             teacher = torch.cat([bos, mels.detach().to(torch.float32).permute(0, 2, 1)[:, :S - 1]], dim=1).contiguous()
-        (mel, stop, logits), sctx = nm.train_steps_fwd(state, B, T, S, teacher, mask, drop=drop)
+        (mel, stop, logits), sctx = nm.train_steps_fwd(state, B, T, S, teacher, mask, drop=drop, video_lengths=lens)
         mel_post, post_tape = nm.train_postnet_fwd(mel, pdrop)
         ctx.model, ctx.tapes = model, (video, emb, vis, etape, state, ptape, sctx, mel, post_tape, pdrop, drop.get("feat"))
+        ctx.lens, ctx.real = lens, real
         ctx.mark_non_differentiable(logits)
         if ctx.bn_batch:
             model._count_batch()
@@ -72,9 +81,12 @@ class _HipTrainStep(torch.autograd.Function):
         if dmel_cf is not None:
             dmel += dmel_cf.permute(0, 2, 1)
         sg = nm.train_steps_bwd(sctx, dmel, z(dstop, mel[:, :, :1]).reshape(B, S), wbuf=wbuf)
-        dvis = nm.train_prologue_bwd(vis, emb, state, ptape, sg, dcontent_dis=ddis, wbuf=wbuf)
+        dvis = nm.train_prologue_bwd(vis, emb, state, ptape, sg, dcontent_dis=ddis, wbuf=wbuf, video_lengths=ctx.lens)
         if fdrop is not None:
-            dvis[:, :, :768] *= fdrop
+            if ctx.real is None:
+                dvis[:, :, :768] *= fdrop
+            else:
+                dvis[:, :, :768] = torch.where(ctx.real, dvis[:, :, :768] * fdrop, torch.zeros((), device=dvis.device))
         # every decoder gradient is final here (the flat buffer holds the decoder group first): a data-parallel caller's hook starts the
         # all-reduce of those buckets now, under the encoder backward (train.py:184-193's hook point; bench.py --mode train does the same)
         if prev is not None:
@@ -82,11 +94,11 @@ class _HipTrainStep(torch.autograd.Function):
         hook = model.__dict__.get("_on_decoder_grads")
         if hook is not None:
             hook()
-        nm.train_encoder_bwd(video, dvis, etape)
+        nm.train_encoder_bwd(video, dvis, etape, video_lengths=ctx.lens)
         if prev is not None:
             flat.grad[n_dec:] += prev[n_dec:]
         model._attach_grads()
-        return (None,) * 8
+        return (None,) * 9
 
 
 class Lip2Speech(NativeBacked):
@@ -100,8 +112,13 @@ class Lip2Speech(NativeBacked):
         self.decoder = Decoder()
         # Off (the default): `video_lengths` is ignored as in the reference, whatever hparams.mask_padding says (nothing reads that).  On: eval-mode
         # `forward` hands the `video_lengths` it receives to `l2s_forward_eval_masked` - every clip of a ZERO-padded batch then comes out as it would
-        # alone (include/l2s.h "per-clip video lengths").  train() mode has no masked form: `forward` raises NotImplementedError.
+        # alone (include/l2s.h "per-clip video lengths").  A call that wants gradients raises NotImplementedError unless `train_video_lengths` is on too.
         self.honour_video_lengths = False
+        # Off (the default): as above.  On, together with `honour_video_lengths`: a differentiable `forward` hands its `video_lengths` to the
+        # l2s_train_*_masked_fwd / _masked_bwd entry points (include/l2s.h "training with per-clip video lengths") - the model that is trained is then the function of
+        # the weights that is evaluated and served with lengths honoured.  Running statistics only: the module must be in eval() mode (dropout then
+        # comes through `dropout_masks=`); train() mode - batch statistics - is refused by name, as the library refuses it.
+        self.train_video_lengths = False
         # one packed weight blob for the whole path; the sub-modules borrow it while they live inside this model
         self.encoder.__dict__["_native_parent"] = self
         self.decoder.__dict__["_native_parent"] = self
@@ -171,11 +188,20 @@ class Lip2Speech(NativeBacked):
     def forward(self, video_frames, face_frames, audio_frames, melspecs, video_lengths, audio_lengths, melspec_lengths,
                 tf_ratio, speaker_embedding=None, gumbel_noise=None, dropout_masks=None):
         masked = bool(self.honour_video_lengths) and video_lengths is not None
-        if masked and (self.training or (torch.is_grad_enabled() and any(p.requires_grad for p in self.decoder.parameters()))):
-            raise NotImplementedError("honour_video_lengths: the training entry points have no length-masked form (include/l2s.h); "
-                                      "use it in eval() mode under torch.no_grad()")
-        if torch.is_grad_enabled() and any(p.requires_grad for p in self.decoder.parameters()):
-            return self._forward_train(video_frames, face_frames, melspecs, video_lengths, tf_ratio, speaker_embedding, gumbel_noise, dropout_masks)
+        wants_grad = torch.is_grad_enabled() and any(p.requires_grad for p in self.decoder.parameters())
+        if masked and (self.training or wants_grad):
+            if not self.train_video_lengths:
+                raise NotImplementedError("honour_video_lengths: a training call takes the length-masked entry points (l2s_train_*_masked_fwd / _masked_bwd, include/l2s.h) only "
+                                          "with `train_video_lengths` switched on as well; otherwise use it in eval() mode under torch.no_grad()")
+            if self.training:
+                raise NotImplementedError("train_video_lengths: train() mode normalises with batch statistics, and the length-masked training entry points "
+                                          "run on running statistics only (batch_stats = 1 with video_lengths is refused, include/l2s.h); call in eval() "
+                                          "mode and hand the dropout multipliers in through dropout_masks=")
+            if not wants_grad:
+                raise NotImplementedError("train_video_lengths: no gradient is wanted here; the forward-only length-masked route is eval() mode under torch.no_grad()")
+        if wants_grad:
+            return self._forward_train(video_frames, face_frames, melspecs, video_lengths, tf_ratio, speaker_embedding, gumbel_noise, dropout_masks,
+                                       honour_lengths=masked)
         if self.training:
             # a no_grad call on a train()-mode module: the feature dropout of model.py:26 is live - the staged route through the sub-modules
             video_features = F.dropout(self.encoder(video_frames), 0.1, True)
@@ -339,7 +365,8 @@ class Lip2Speech(NativeBacked):
         job["entry"], job["video_lengths"] = "forward_ragged", lens
         return job
 
-    def _forward_train(self, video_frames, face_frames, melspecs, video_lengths, tf_ratio, speaker_embedding, gumbel_noise, dropout_masks=None):
+    def _forward_train(self, video_frames, face_frames, melspecs, video_lengths, tf_ratio, speaker_embedding, gumbel_noise, dropout_masks=None,
+                       honour_lengths=False):
         """The differentiable route (train.py:167-184): same outputs as `forward`, attached to autograd through `_HipTrainStep`.
         In `train()` mode the five dropout sites of the reference are active (multipliers drawn on the device by `training.draw_dropout`
         and handed to the kernels as inputs, or supplied through `dropout_masks=`); in `eval()` mode they are off (the configuration the
@@ -361,8 +388,10 @@ class Lip2Speech(NativeBacked):
         if drop is None and self.training:
             from ..training import draw_dropout
             drop = draw_dropout(B, T, S, video_frames.device)
+        # `honour_lengths` (forward: both switches on): checked on the host before anything reaches the device
+        lens = native.video_lengths_array(video_lengths, B, T) if honour_lengths else None
         mel, mel_post, stop, attn, dis = _HipTrainStep.apply(self.decoder.BOS, self, video_frames.detach().to(torch.float32).contiguous(), emb,
-                                                             gumbel_noise.detach().to(torch.float32).contiguous(), melspecs, mask if any(mask) else None, drop)
+                                                             gumbel_noise.detach().to(torch.float32).contiguous(), melspecs, mask if any(mask) else None, drop, lens)
         return [mel, mel_post, stop, emb, attn, dis, video_lengths]
 
     def inference(self, video_frames, face_frames, speaker_embedding=None, return_attention_map=False, gumbel_noise=None, early_stop=None,

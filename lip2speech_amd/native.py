@@ -49,6 +49,9 @@ ABI_SYMBOLS = (
     "l2s_train_steps_fwd", "l2s_train_steps_bwd",
     "l2s_train_set_bn", "l2s_train_refresh_weights", "l2s_train_encoder_tape_floats", "l2s_train_encoder_ws_bytes", "l2s_train_encoder_fwd", "l2s_train_encoder_bwd",
     "l2s_train_prologue_tape_floats", "l2s_train_prologue_ws_bytes", "l2s_train_prologue_fwd", "l2s_train_prologue_bwd",
+    "l2s_train_encoder_tape_floats_masked", "l2s_train_encoder_ws_bytes_masked", "l2s_train_prologue_tape_floats_masked", "l2s_train_prologue_ws_bytes_masked",
+    "l2s_train_steps_tape_floats_masked", "l2s_train_encoder_masked_fwd", "l2s_train_encoder_masked_bwd", "l2s_train_prologue_masked_fwd",
+    "l2s_train_prologue_masked_bwd", "l2s_train_steps_masked_fwd", "l2s_train_steps_masked_bwd",
     "l2s_train_bind", "l2s_train_postnet_tape_floats", "l2s_train_postnet_ws_bytes", "l2s_train_postnet_fwd", "l2s_train_postnet_bwd",
     "l2s_profile_enable", "l2s_profile_reset", "l2s_profile_count", "l2s_profile_get",
 )
@@ -272,6 +275,15 @@ def _bind(L: ctypes.CDLL) -> None:
         L.l2s_forward_eval_masked.argtypes = L.l2s_forward_eval.argtypes + [_lens]
         L.l2s_decoder_prologue_masked.argtypes = L.l2s_decoder_prologue.argtypes + [_lens]
         L.l2s_decode_steps_masked.argtypes = L.l2s_decode_steps.argtypes + [_lens]
+    # training with per-clip video lengths (include/l2s.h): likewise absent from a library built before them (timing/masked_train times one next to this build)
+    if hasattr(L, "l2s_train_steps_masked_fwd"):
+        _lens = ctypes.POINTER(ctypes.c_int32)
+        for name, n in (("l2s_train_encoder_tape_floats_masked", 3), ("l2s_train_encoder_ws_bytes_masked", 3), ("l2s_train_prologue_tape_floats_masked", 2),
+                        ("l2s_train_prologue_ws_bytes_masked", 2), ("l2s_train_steps_tape_floats_masked", 2)):
+            getattr(L, name).argtypes = [_i] * n
+            getattr(L, name).restype = _i64
+        for name in ("l2s_train_encoder_fwd", "l2s_train_encoder_bwd", "l2s_train_prologue_fwd", "l2s_train_prologue_bwd", "l2s_train_steps_fwd", "l2s_train_steps_bwd"):
+            getattr(L, name[:-4] + "_masked" + name[-4:]).argtypes = getattr(L, name).argtypes + [_lens]      # l2s_train_<stage>_masked_fwd / _bwd
     # ragged groups (include/l2s.h): likewise absent from a library built before them (tools/ragged/time_ragged.py times one next to this build)
     if hasattr(L, "l2s_inference_ragged"):
         _lens = ctypes.POINTER(ctypes.c_int32)
@@ -1013,16 +1025,19 @@ class NativeModel:
         self._check(L.l2s_train_steps_pack_weights(self._h, _ptr(wbuf), _stream()))
         return wbuf
 
-    def train_steps_fwd(self, state, B, T, S, teacher=None, teacher_mask=None, drop=None):
+    def train_steps_fwd(self, state, B, T, S, teacher=None, teacher_mask=None, drop=None, video_lengths=None):
         """Loop forward with a tape.  Returns (mel (B,S,80), stop (B,S), attn_logits (B,S,T)) and the context for train_steps_bwd.
-        drop: dict of dropout multipliers (any subset): 'prenet' (S,B,256), 'attn' (S,B,T), 'rnn' (S,B,512)."""
+        drop: dict of dropout multipliers (any subset): 'prenet' (S,B,256), 'attn' (S,B,T), 'rnn' (S,B,512).
+        `video_lengths` (B integers in [7, T]; a state of `train_prologue_fwd(..., video_lengths=)`): `l2s_train_steps_masked_fwd` - row b attends to its
+        own frames and content slots, attn_logits at t >= len_b are -inf; the context carries the lengths to `train_steps_bwd`."""
+        lens = video_lengths_array(video_lengths, B, T) if video_lengths is not None else None
         drop = {k: _f32(v) for k, v in (drop or {}).items() if k in ("prenet", "attn", "rnn") and v is not None}
         dp, da, dr = drop.get("prenet"), drop.get("attn"), drop.get("rnn")
         assert dp is None or tuple(dp.shape) == (S, B, 256)
         assert da is None or tuple(da.shape) == (S, B, T)
         assert dr is None or tuple(dr.shape) == (S, B, 512)
         L, dev = self._L, state.device
-        tape = torch.zeros(int(L.l2s_train_steps_tape_floats(B, S)), dtype=torch.float32, device=dev)
+        tape = torch.zeros(int((L.l2s_train_steps_tape_floats_masked if lens is not None else L.l2s_train_steps_tape_floats)(B, S)), dtype=torch.float32, device=dev)
         ws = torch.empty(int(L.l2s_train_steps_ws_bytes(B, S)), dtype=torch.uint8, device=dev)
         mel = torch.empty(B, S, 80, dtype=torch.float32, device=dev)
         stop = torch.empty(B, S, dtype=torch.float32, device=dev)
@@ -1033,10 +1048,15 @@ class NativeModel:
             mask_np = np.ascontiguousarray(np.asarray(teacher_mask, dtype=np.uint8))
             mask_dev = torch.from_numpy(mask_np).to(dev)
             mask_ptr = mask_np.ctypes.data_as(_vp)
-        self._check(L.l2s_train_steps_fwd(self._h, _ptr(state), B, T, S, _ptr(teacher), mask_ptr, _ptr(mask_dev) if mask_dev is not None else None,
-                                    _ptr(tape), _ptr(mel), _ptr(stop), _ptr(logits), _ptr(dp), _ptr(da), _ptr(dr), _ptr(ws), ws.numel(), _stream()))
+        args = (self._h, _ptr(state), B, T, S, _ptr(teacher), mask_ptr, _ptr(mask_dev) if mask_dev is not None else None,
+                _ptr(tape), _ptr(mel), _ptr(stop), _ptr(logits), _ptr(dp), _ptr(da), _ptr(dr), _ptr(ws), ws.numel(), _stream())
+        if lens is not None:
+            self.calls["l2s_train_steps_masked_fwd"] += 1
+            self._check(L.l2s_train_steps_masked_fwd(*args, lens))
+        else:
+            self._check(L.l2s_train_steps_fwd(*args))
         ctx = dict(state=state, B=B, T=T, S=S, tape=tape, ws=ws, logits=logits, mask_np=mask_np, mask_ptr=mask_ptr, teacher=teacher, mask_dev=mask_dev,
-                   drop=(dp, da, dr))
+                   drop=(dp, da, dr), lens=lens)
         return (mel, stop, logits), ctx
 
     def train_steps_bwd(self, ctx, dmel, dstop, wbuf=None):
@@ -1049,63 +1069,97 @@ class NativeModel:
         if wbuf is None:
             wbuf = self.train_pack_weights(dev)
         ws = ctx["ws"]
-        self._check(L.l2s_train_steps_bwd(self._h, _ptr(state), B, T, S, ctx["mask_ptr"], _ptr(ctx["tape"]), _ptr(ctx["logits"]), _ptr(_f32(dmel)), _ptr(_f32(dstop)),
-                                    _ptr(wbuf), _ptr(out["dk"]), _ptr(out["dv"]), _ptr(out["dckey"]), _ptr(out["dcval"]), _ptr(out["dh_init"]), _ptr(out["de_c"]),
-                                    _ptr(ctx["drop"][0]), _ptr(ctx["drop"][1]), _ptr(ctx["drop"][2]), _ptr(ws), ws.numel(), _stream()))
+        args = (self._h, _ptr(state), B, T, S, ctx["mask_ptr"], _ptr(ctx["tape"]), _ptr(ctx["logits"]), _ptr(_f32(dmel)), _ptr(_f32(dstop)),
+                _ptr(wbuf), _ptr(out["dk"]), _ptr(out["dv"]), _ptr(out["dckey"]), _ptr(out["dcval"]), _ptr(out["dh_init"]), _ptr(out["de_c"]),
+                _ptr(ctx["drop"][0]), _ptr(ctx["drop"][1]), _ptr(ctx["drop"][2]), _ptr(ws), ws.numel(), _stream())
+        if ctx.get("lens") is not None:      # a masked forward: dk / dv rows t >= len_b and the content gradients of slots >= m_b come back as exact zeros
+            self.calls["l2s_train_steps_masked_bwd"] += 1
+            self._check(L.l2s_train_steps_masked_bwd(*args, ctx["lens"]))
+        else:
+            self._check(L.l2s_train_steps_bwd(*args))
         return out
 
-    def train_steps(self, state, B, T, S, dmel, dstop, teacher=None, teacher_mask=None, drop=None):
+    def train_steps(self, state, B, T, S, dmel, dstop, teacher=None, teacher_mask=None, drop=None, video_lengths=None):
         """Loop forward-with-tape + BPTT (stage 2 of the training path).  Returns (mel, stop, attn_logits) and the state gradients."""
-        outs, ctx = self.train_steps_fwd(state, B, T, S, teacher, teacher_mask, drop=drop)
+        outs, ctx = self.train_steps_fwd(state, B, T, S, teacher, teacher_mask, drop=drop, video_lengths=video_lengths)
         return outs, self.train_steps_bwd(ctx, dmel, dstop)
 
-    def train_encoder_fwd(self, video, emb=None):
-        """Encoder forward with a tape.  Returns (vis (B,T,1024) or None, feat (B,T,768), tape)."""
-        video = _f32(video)
+    def train_encoder_fwd(self, video, emb=None, video_lengths=None):
+        """Encoder forward with a tape.  Returns (vis (B,T,1024) or None, feat (B,T,768), tape).
+        `video_lengths` (B integers in [7, T]; the clips ZERO-padded to T): `l2s_train_encoder_masked_fwd` - the trunk runs on the real frames only, the
+        feature columns of rows t >= len_b are zeros; hand the same lengths (and this tape) to `train_encoder_bwd`."""
         B, _, T, H, W = video.shape
+        lens = video_lengths_array(video_lengths, B, T) if video_lengths is not None else None      # checked on the host, before anything else
+        video = _f32(video)
         L, dev = self._L, video.device
-        tape = torch.empty(int(L.l2s_train_encoder_tape_floats(B, T, H)), dtype=torch.float32, device=dev)
+        tape = torch.empty(int((L.l2s_train_encoder_tape_floats_masked if lens is not None else L.l2s_train_encoder_tape_floats)(B, T, H)), dtype=torch.float32, device=dev)
         feat = torch.empty(B, T, 768, dtype=torch.float32, device=dev)
         vis = torch.empty(B, T, 1024, dtype=torch.float32, device=dev) if emb is not None else None
-        self._check(L.l2s_train_encoder_fwd(self._h, _ptr(video), B, T, H, W, _ptr(_f32(emb)) if emb is not None else None, _ptr(vis), _ptr(feat), _ptr(tape), _stream()))
+        args = (self._h, _ptr(video), B, T, H, W, _ptr(_f32(emb)) if emb is not None else None, _ptr(vis), _ptr(feat), _ptr(tape), _stream())
+        if lens is not None:
+            self.calls["l2s_train_encoder_masked_fwd"] += 1
+            self._check(L.l2s_train_encoder_masked_fwd(*args, lens))
+        else:
+            self._check(L.l2s_train_encoder_fwd(*args))
         return vis, feat, tape
 
-    def train_encoder_bwd(self, video, dfeat, tape) -> None:
-        """Encoder backward: dfeat (B,T,>=768) (e.g. dvis, row stride 1024); parameter gradients land in the bound slots."""
-        video = _f32(video)
+    def train_encoder_bwd(self, video, dfeat, tape, video_lengths=None) -> None:
+        """Encoder backward: dfeat (B,T,>=768) (e.g. dvis, row stride 1024); parameter gradients land in the bound slots.
+        `video_lengths`: the lengths of the masked forward that wrote `tape` (`l2s_train_encoder_masked_bwd`; dfeat rows t >= len_b are never read)."""
         B, _, T, H, W = video.shape
+        lens = video_lengths_array(video_lengths, B, T) if video_lengths is not None else None
+        video = _f32(video)
         L = self._L
         assert dfeat.is_cuda and dfeat.dtype == torch.float32 and dfeat.stride(-1) == 1 and dfeat.stride(0) == T * dfeat.stride(1)
-        ws = torch.empty(int(L.l2s_train_encoder_ws_bytes(B, T, H)), dtype=torch.uint8, device=video.device)
-        self._check(L.l2s_train_encoder_bwd(self._h, _ptr(video), B, T, H, W, dfeat.data_ptr(), int(dfeat.stride(1)), _ptr(tape), _ptr(ws), ws.numel(), _stream()))
+        ws = torch.empty(int((L.l2s_train_encoder_ws_bytes_masked if lens is not None else L.l2s_train_encoder_ws_bytes)(B, T, H)), dtype=torch.uint8, device=video.device)
+        args = (self._h, _ptr(video), B, T, H, W, dfeat.data_ptr(), int(dfeat.stride(1)), _ptr(tape), _ptr(ws), ws.numel(), _stream())
+        if lens is not None:
+            self.calls["l2s_train_encoder_masked_bwd"] += 1
+            self._check(L.l2s_train_encoder_masked_bwd(*args, lens))
+        else:
+            self._check(L.l2s_train_encoder_bwd(*args))
 
-    def train_prologue_fwd(self, vis, emb, gumbel):
-        """Prologue forward with a tape (stage 3).  Returns (state, content_dis, tape)."""
-        vis, emb, gumbel = _f32(vis), _f32(emb), _f32(gumbel)
+    def train_prologue_fwd(self, vis, emb, gumbel, video_lengths=None):
+        """Prologue forward with a tape (stage 3).  Returns (state, content_dis, tape).
+        `video_lengths` (B integers in [7, T]): `l2s_train_prologue_masked_fwd` - hand the same lengths to `train_steps_fwd` and `train_prologue_bwd`."""
         B, T, _ = vis.shape
+        lens = video_lengths_array(video_lengths, B, T) if video_lengths is not None else None      # checked on the host, before anything else
+        vis, emb, gumbel = _f32(vis), _f32(emb), _f32(gumbel)
         L, dev = self._L, vis.device
         state = torch.zeros(int(L.l2s_state_floats(B, T)), dtype=torch.float32, device=dev)
         dis = torch.empty(B * min_T(T), 501, dtype=torch.float32, device=dev)
-        tape = torch.zeros(int(L.l2s_train_prologue_tape_floats(B, T)), dtype=torch.float32, device=dev)
-        ws = torch.empty(int(L.l2s_train_prologue_ws_bytes(B, T)), dtype=torch.uint8, device=dev)
-        self._check(L.l2s_train_prologue_fwd(self._h, _ptr(vis), _ptr(emb), _ptr(gumbel), B, T, _ptr(state), _ptr(dis), _ptr(tape), _ptr(ws), ws.numel(), _stream()))
+        masked = lens is not None
+        tape = torch.zeros(int((L.l2s_train_prologue_tape_floats_masked if masked else L.l2s_train_prologue_tape_floats)(B, T)), dtype=torch.float32, device=dev)
+        ws = torch.empty(int((L.l2s_train_prologue_ws_bytes_masked if masked else L.l2s_train_prologue_ws_bytes)(B, T)), dtype=torch.uint8, device=dev)
+        args = (self._h, _ptr(vis), _ptr(emb), _ptr(gumbel), B, T, _ptr(state), _ptr(dis), _ptr(tape), _ptr(ws), ws.numel(), _stream())
+        if masked:
+            self.calls["l2s_train_prologue_masked_fwd"] += 1
+            self._check(L.l2s_train_prologue_masked_fwd(*args, lens))
+        else:
+            self._check(L.l2s_train_prologue_fwd(*args))
         return state, dis, tape
 
-    def train_prologue_bwd(self, vis, emb, state, tape, g, dcontent_dis=None, wbuf=None):
+    def train_prologue_bwd(self, vis, emb, state, tape, g, dcontent_dis=None, wbuf=None, video_lengths=None):
         """Prologue backward: g = the state gradients of train_steps (dk, dv, dckey, dcval, dh_init, de_c).  Returns dvis (B,T,1024);
-        parameter gradients land in the bound slots."""
-        vis, emb = _f32(vis), _f32(emb)
+        parameter gradients land in the bound slots.  `video_lengths`: the lengths of the masked forward that wrote `tape`
+        (`l2s_train_prologue_masked_bwd`; dvis rows t >= len_b come back as exact zeros)."""
         B, T, _ = vis.shape
+        lens = video_lengths_array(video_lengths, B, T) if video_lengths is not None else None
+        vis, emb = _f32(vis), _f32(emb)
         L, dev = self._L, vis.device
         if wbuf is None:
             wbuf = self.train_pack_weights(dev)
-        ws = torch.empty(int(L.l2s_train_prologue_ws_bytes(B, T)), dtype=torch.uint8, device=dev)
+        ws = torch.empty(int((L.l2s_train_prologue_ws_bytes_masked if lens is not None else L.l2s_train_prologue_ws_bytes)(B, T)), dtype=torch.uint8, device=dev)
         dvis = torch.empty(B, T, 1024, dtype=torch.float32, device=dev)
         gg = {k: _f32(v) for k, v in g.items()}
         dd = _f32(dcontent_dis) if dcontent_dis is not None else None
-        self._check(L.l2s_train_prologue_bwd(self._h, _ptr(vis), _ptr(emb), B, T, _ptr(state), _ptr(tape), _ptr(wbuf), _ptr(gg["dk"]), _ptr(gg["dv"]),
-                                       _ptr(gg["dckey"]), _ptr(gg["dcval"]), _ptr(gg["dh_init"]), _ptr(gg["de_c"]), _ptr(dd), _ptr(dvis),
-                                       _ptr(ws), ws.numel(), _stream()))
+        args = (self._h, _ptr(vis), _ptr(emb), B, T, _ptr(state), _ptr(tape), _ptr(wbuf), _ptr(gg["dk"]), _ptr(gg["dv"]),
+                _ptr(gg["dckey"]), _ptr(gg["dcval"]), _ptr(gg["dh_init"]), _ptr(gg["de_c"]), _ptr(dd), _ptr(dvis), _ptr(ws), ws.numel(), _stream())
+        if lens is not None:
+            self.calls["l2s_train_prologue_masked_bwd"] += 1
+            self._check(L.l2s_train_prologue_masked_bwd(*args, lens))
+        else:
+            self._check(L.l2s_train_prologue_bwd(*args))
         return dvis
 
     def lstm_cell_chain_us(self, B: int, n_pairs: int = 300) -> float:

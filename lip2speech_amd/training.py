@@ -117,22 +117,32 @@ def draw_dropout(B: int, T: int, S: int, device, generator=None) -> dict:
     return d
 
 
-def decoder_forward_backward(nm: "native.NativeModel", vis, emb, gumbel, mel_target, gate_target, teacher_mask=None, bos=None, drop=None):
+def decoder_forward_backward(nm: "native.NativeModel", vis, emb, gumbel, mel_target, gate_target, teacher_mask=None, bos=None, drop=None,
+                             video_lengths=None):
     """Forward + backward of the decoder half of `Lip2Speech.forward` + `Loss.forward` (reference: model.py:34-41 -> decoder.py:320-379,
     losses.py:69-77, train.py:172-184) with eval-mode statistics (running BN stats, no dropout): prologue -> S-step loop -> post-net ->
     4-term loss, then back through the post-net, the loop (BPTT) and the prologue.  Parameter gradients land in the slots bound with
     `nm.train_bind`; returns the outputs, the loss terms and the gradient wrt the visual features `vis` (B,T,1024).
 
     teacher_mask (S,) bool marks the steps whose input frame is the ground-truth previous frame (scheduled sampling made explicit,
-    decoder.py:355-359); `bos` is the device BOS parameter (needed only with a mask)."""
+    decoder.py:355-359); `bos` is the device BOS parameter (needed only with a mask).
+    `video_lengths` (B integers in [7, T]; `vis` of a ZERO-padded batch): the length-masked entry points (include/l2s.h "training with per-clip video
+    lengths"); the feature-dropout multipliers of rows t >= len_b are never read."""
     B, T, _ = vis.shape
     S = mel_target.shape[2]
     drop = drop or {}
+    lens = video_lengths
+    real = None
+    if lens is not None:
+        real = (torch.arange(T, device=vis.device)[None, :] < torch.as_tensor([int(v) for v in lens], device=vis.device)[:, None]).unsqueeze(2)
     pdrop = native.postnet_drop_pack(drop["post"]) if drop.get("post") is not None else None
     if drop.get("feat") is not None:                      # F.dropout on the encoder features (model.py:26); the embedding columns pass
         vis = vis.clone()
-        vis[:, :, :768] *= drop["feat"]
-    state, dis, ptape = nm.train_prologue_fwd(vis, emb, gumbel)
+        if real is None:
+            vis[:, :, :768] *= drop["feat"]
+        else:
+            vis[:, :, :768] = torch.where(real, vis[:, :, :768] * drop["feat"], torch.zeros((), device=vis.device))
+    state, dis, ptape = nm.train_prologue_fwd(vis, emb, gumbel, video_lengths=lens)
     teacher = None
     if teacher_mask is not None and bool(torch.as_tensor(teacher_mask).any()):
         assert bos is not None, "teacher forcing needs the BOS parameter"
@@ -140,7 +150,7 @@ def decoder_forward_backward(nm: "native.NativeModel", vis, emb, gumbel, mel_tar
         teacher_mask = torch.as_tensor(teacher_mask).cpu().numpy()
     else:
         teacher_mask = None
-    (mel, stop, logits), ctx = nm.train_steps_fwd(state, B, T, S, teacher, teacher_mask, drop=drop)
+    (mel, stop, logits), ctx = nm.train_steps_fwd(state, B, T, S, teacher, teacher_mask, drop=drop, video_lengths=lens)
     mel_post, post_tape = nm.train_postnet_fwd(mel, pdrop)
     mel_cf = mel.permute(0, 2, 1).contiguous()
     loss, g = loss_terms(mel_cf, mel_post, stop, dis, mel_target, gate_target)
@@ -148,22 +158,26 @@ def decoder_forward_backward(nm: "native.NativeModel", vis, emb, gumbel, mel_tar
     dmel = nm.train_postnet_bwd(mel, g["mel_post"], post_tape, pdrop)
     dmel += g["mel"].permute(0, 2, 1)
     sg = nm.train_steps_bwd(ctx, dmel, g["stop"], wbuf=wbuf)
-    dvis = nm.train_prologue_bwd(vis, emb, state, ptape, sg, dcontent_dis=g["content_dis"], wbuf=wbuf)
+    dvis = nm.train_prologue_bwd(vis, emb, state, ptape, sg, dcontent_dis=g["content_dis"], wbuf=wbuf, video_lengths=lens)
     if drop.get("feat") is not None:
-        dvis[:, :, :768] *= drop["feat"]
+        if real is None:
+            dvis[:, :, :768] *= drop["feat"]
+        else:
+            dvis[:, :, :768] = torch.where(real, dvis[:, :, :768] * drop["feat"], torch.zeros((), device=dvis.device))
     return {"loss": loss, "mel": mel_cf, "mel_post": mel_post, "stop": stop, "attn_logits": logits, "content_dis": dis, "dvis": dvis}
 
 
 def model_forward_backward(nm: "native.NativeModel", video, emb, gumbel, mel_target, gate_target, teacher_mask=None, bos=None, drop=None,
-                           on_decoder_grads=None):
+                           on_decoder_grads=None, video_lengths=None):
     """`Lip2Speech.forward` + `Loss` + `backward()` (model.py:20-41, train.py:167-184) with the speaker embedding supplied and eval-mode
     statistics: encoder forward with a tape, `decoder_forward_backward`, then the encoder backward fed by the visual-feature gradient.
-    All encoder and decoder parameter gradients land in the bound slots."""
-    vis, _, etape = nm.train_encoder_fwd(video, emb)
-    out = decoder_forward_backward(nm, vis, emb, gumbel, mel_target, gate_target, teacher_mask=teacher_mask, bos=bos, drop=drop)
+    All encoder and decoder parameter gradients land in the bound slots.  `video_lengths`: the clips are ZERO-padded to T and every stage that sees the
+    video takes its length-masked entry point (running statistics only)."""
+    vis, _, etape = nm.train_encoder_fwd(video, emb, video_lengths=video_lengths)
+    out = decoder_forward_backward(nm, vis, emb, gumbel, mel_target, gate_target, teacher_mask=teacher_mask, bos=bos, drop=drop, video_lengths=video_lengths)
     if on_decoder_grads is not None:
         on_decoder_grads()            # every decoder gradient is final: their all-reduce can travel under the encoder backward
-    nm.train_encoder_bwd(video, out["dvis"], etape)
+    nm.train_encoder_bwd(video, out["dvis"], etape, video_lengths=video_lengths)
     return out
 
 
