@@ -609,7 +609,8 @@ int l2s_train_encoder_bwd(l2s_model* m, const float* video, int B, int T, int H,
  * synchronisation; the array may be freed when the call returns) into its TAPE: size the tapes with the *_tape_floats_masked sizers and the
  * workspaces of the encoder and the prologue with *_ws_bytes_masked (the loop keeps l2s_train_steps_ws_bytes).  l2s_train_postnet_* and
  * l2s_loss do not depend on video lengths and are unchanged: the loop runs S steps for every clip, the loss covers padded target frames, as in the
- * reference, and the KLD term keeps its mean over all B * min_T(T) rows (rows of unused slots are zeros and add nothing to the sum).
+ * reference, and the KLD term keeps its mean over all B * min_T(T) rows (rows of unused slots are zeros and add nothing to the sum).  The forms that
+ * honour the MEL lengths as well - l2s_loss_lengths, l2s_train_postnet_masked_* - follow this section.
  * Forward.  Row b of mel, stop and the attention logits - so of mel_post - is what the unmasked training forward gives clip b ALONE at B = 1,
  * T = len_b with the same teacher frames, dropout multipliers and its first m_b = l2s_min_T(len_b) Gumbel rows.  Attention logits at t >= len_b
  * are -INFINITY; content_dis rows of slots >= m_b and the 768 feature columns of vis / feat rows t >= len_b are exact zeros (the speaker
@@ -647,6 +648,48 @@ int l2s_train_steps_masked_bwd(l2s_model* m, float* state, int B, int T, int S, 
                                const float* dmel, const float* dstop, float* wbuf, float* dk, float* dv, float* dckey, float* dcval, float* dh_init,
                                float* de_c, const float* drop_prenet, const float* drop_attn, const float* drop_rnn, void* ws, int64_t ws_bytes,
                                void* stream, const int32_t* video_lengths);
+
+/* ---- training with per-clip mel lengths: the loss and the post-net of a batch whose TARGETS are padded to S ---------------------------------------------
+ * The other half of the padding above.  mel_lengths: a HOST array of B int32, S_b in [1, S] (the collates' melspec_lengths; targets padded with finite
+ * values, the gate target 1 from frame S_b - 1 on); video_lengths as above, or NULL where the model did not honour them (every clip then owns all
+ * m = R / B content rows).  Each call carries its table to the device itself (csrc/host_table.h: kernel arguments on `stream`, no allocation, no
+ * synchronisation, no copy from pageable memory; the arrays may be freed when the call returns) - l2s_loss_lengths into its scratch, the post-net calls
+ * into their tape.
+ * l2s_loss_lengths: l2s_loss's arguments, then the two length arrays, T (the padded frame count video_lengths refers to; ignored with NULL) and per_clip.
+ *   The batch loss is (1/B) sum_b of the loss of clip b ALONE, each term over the clip's own extent: the two mel MSEs over 80 * S_b, BCE over S_b, KLD over
+ *   the clip's own m_b = l2s_min_T(len_b) rows (rows b * m .. b * m + m_b of content_dis).  losses5 as l2s_loss; per_clip dev (B,4) or NULL: each clip's own
+ *   four terms.  Gradients: dmel[b,:,s] = 2 d / (B * 80 * S_b), dmel_post 10 x that, dstop = (sigmoid(x) - y) / (B * S_b), ddis of a used row scaled by
+ *   1 / (B * m_b); every gradient element at s >= S_b and every ddis row >= m_b of a clip is an EXACT ZERO, written by the same pass (no pre-clearing; l2s_loss
+ *   gives a zero row of content_dis the gradient log(1e-20), this call does not).  Nothing at a pad position of mel, mel_post, stop, the targets, or a
+ *   content row >= m_b is read.  Two-stage fp64 like l2s_loss - per-(clip, term) partials, then one block that divides per clip and averages over B: the same
+ *   bits run to run; two launches plus the table's.  With every S_b = S and every m_b = m the call runs l2s_loss's own launches: its bits, terms and gradients
+ *   (the length-aware pass then only fills per_clip).
+ *   l2s_loss_lengths_check: the pure host validator the call runs first - B in [1, 96], every S_b in [1, S] ("mel_lengths[1] = 9 is outside [1, S = 8]"), a
+ *   null table, and video_lengths (when given) as the masked family checks them; nothing is launched on an error.
+ *   scratch: l2s_train_scratch_bytes_lengths(B) (l2s_loss's scratch, the partials, the device table); -1 outside B in [1, 96].
+ * l2s_train_postnet_masked_fwd / _masked_bwd: the unmasked signatures plus mel_lengths.  (Word order as above: the *_fwd_masked names stay free.)
+ *   Forward: `mel` is NOT const - rows s >= S_b, which the loop decoded past the clip's end, are zeroed in place - and the rows s >= S_b of every layer's
+ *   input (mel, x_0 .. x_3) are zeros, so rows < S_b of mel_post are what the unmasked post-net gives the clip alone at S = S_b; mel_post[b,:,s >= S_b] is
+ *   exact zeros.  Backward: the adjoint of the same zeroing: pad positions of dmel_post count as zeros whatever they hold, pad rows of every input gradient
+ *   are zeroed after each dx, so nothing flows from a real row into a pad row, and pad rows add exact zeros to the weight, bias, BatchNorm-affine and PSine
+ *   gradients; pad rows of dmel receive an added exact zero.  Dropout multipliers at pad rows never reach a result (NaN there changes nothing).  With every
+ *   S_b = S: the bits of the unmasked calls (the same launches; the row kernels find nothing to zero).  About ten short launches more per step.
+ *   Tape: l2s_train_postnet_tape_floats_masked (the unmasked tape plus the table); workspace: l2s_train_postnet_ws_bytes_masked (= the unmasked size).
+ * The loop is unchanged - clip b still runs S steps; with exact-zero dmel / dstop at its pad steps, BPTT adds exact zeros for them.  Teacher frames and the
+ * loop's dropout multipliers at pad steps must be finite: the loop reads them.
+ * Refused by name, before any launch: S_b outside [1, S] or a null table (the clip is named), batch_stats = 1 (the post-net's BatchNorms would have to take
+ * their statistics over real rows only: not built) and option "train_bf16". */
+int l2s_loss_lengths_check(const int32_t* mel_lengths, const int32_t* video_lengths, int B, int S, int T);
+int64_t l2s_train_scratch_bytes_lengths(int B);
+int l2s_loss_lengths(const float* mel, const float* mel_post, const float* mel_target, const float* stop, const float* gate_target,
+                     const float* content_dis, int B, int S, int R, float* losses5, float* dmel, float* dmel_post, float* dstop, float* ddis,
+                     void* scratch, void* stream, const int32_t* mel_lengths, const int32_t* video_lengths, int T, float* per_clip);
+int64_t l2s_train_postnet_tape_floats_masked(int B, int S);
+int64_t l2s_train_postnet_ws_bytes_masked(int B, int S);
+int l2s_train_postnet_masked_fwd(l2s_model* m, float* mel, int B, int S, float* tape, float* mel_post, const float* drop, void* stream,
+                                 const int32_t* mel_lengths);
+int l2s_train_postnet_masked_bwd(l2s_model* m, const float* mel, const float* dmel_post, int B, int S, float* tape, float* dmel, const float* drop,
+                                 void* ws, int64_t ws_bytes, void* stream, const int32_t* mel_lengths);
 
 /* ---- run-time options ------------------------------------------------------------------------------------------------------------
  * l2s_set_option changes the PROCESS DEFAULTS: what l2s_model_create copies into a new model.  l2s_model_set_option changes one model.

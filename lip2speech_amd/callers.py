@@ -414,7 +414,7 @@ def reconstruction_losses(outputs, targets) -> dict:
 
 def train_iterations(net, batches: List, n_iters: int, speaker_encoder=None, tf_ratio: float = 0.0, lr: float = 1e-4, weight_decay: float = 1e-6,
                      grad_clip: float = 1.0, fused_optimizer: bool = True, device="cuda", bf16: bool = False,
-                     encoding: str = "voice", honour_lengths: bool = False) -> List[dict]:
+                     encoding: str = "voice", honour_lengths: bool = False, honour_mel_lengths: bool = False) -> List[dict]:
     """The model-facing half of `train.py`'s loop (train.py:102-104,150-193): `net.train()`; cycle through the collated batches
     (`tf_ratio += 0.1` every 10 epochs); forward -> 4-term loss -> `backward()` -> gradient all-reduce when a process group is up
     (one process per GPU) -> clip at `grad_clip` -> AdamW(amsgrad) on the decoder and encoder groups.  Returns the per-iteration loss
@@ -425,16 +425,23 @@ def train_iterations(net, batches: List, n_iters: int, speaker_encoder=None, tf_
     length-masked training entry points (`honour_video_lengths` and `train_video_lengths` switched on for the loop; include/l2s.h "training with
     per-clip video lengths") - every clip is encoded, attended to and differentiated as it would be alone.  Those entry points run on running
     statistics, so the loop keeps the model in eval() mode - every BatchNorm frozen, as when fine-tuning - and draws the five dropout sites itself
-    (`training.draw_dropout`, handed in through `dropout_masks=`); `bf16` is refused with it."""
+    (`training.draw_dropout`, handed in through `dropout_masks=`); `bf16` is refused with it.
+    `honour_mel_lengths=True` (needs `honour_lengths`): the batches' `melspec_lengths` go to the post-net and to the criterion as well (`train_mel_lengths`
+    switched on for the loop; include/l2s.h "training with per-clip mel lengths") - every clip's loss covers its own mel frames and content rows, and
+    the batch loss is the mean over the clips."""
     _check_encoding(encoding)
     from .losses import Loss
     from .training import AdamWAmsgrad, GradAllReducer, draw_dropout
     if honour_lengths and bf16:
         raise NotImplementedError("honour_lengths: option \"train_bf16\" with video_lengths is not supported (include/l2s.h)")
+    if honour_mel_lengths and not honour_lengths:
+        raise NotImplementedError("honour_mel_lengths needs honour_lengths: the mel lengths are the other half of the same padding")
     net.train(not honour_lengths)
-    switches = (net.honour_video_lengths, net.train_video_lengths)
+    switches = (net.honour_video_lengths, net.train_video_lengths, net.train_mel_lengths)
     if honour_lengths:
         net.honour_video_lengths = net.train_video_lengths = True
+    if honour_mel_lengths:
+        net.train_mel_lengths = True
     flat = net._train_state()
     # reduced-precision training (the reference's switch is hparams.fp16_run = apex O2, train.py:106-107,180-191): here bf16 OPERANDS in the
     # GEMMs / Conv1d stacks of encoder, prologue and post-net on the bf16 matrix cores, fp32 accumulation, fp32 master weights, fp32 loop
@@ -462,7 +469,7 @@ def train_iterations(net, batches: List, n_iters: int, speaker_encoder=None, tf_
         drop = draw_dropout(videos.shape[0], videos.shape[2], melspecs.shape[2], device) if honour_lengths else None
         outputs = net(videos.to(device), face_crops.to(device) if face_crops is not None else None, audios.to(device), melspecs.to(device), vlen, alen,
                       mlen, tf_ratio, speaker_embedding=emb, dropout_masks=drop)
-        losses = reconstruction_criterion(outputs, (melspecs.to(device), gates.to(device)), dict())
+        losses = reconstruction_criterion(outputs, (melspecs.to(device), gates.to(device)), dict(), **({"melspec_lengths": mlen} if honour_mel_lengths else {}))
         loss = sum(losses.values())
         optim.zero_grad()
         loss.backward()
@@ -480,5 +487,5 @@ def train_iterations(net, batches: List, n_iters: int, speaker_encoder=None, tf_
         rec.update(loss=float(loss.detach()), grad_norm=float(grad_norm), tf_ratio=tf_ratio, epoch=epoch)
         log.append(rec)
     net.__dict__["_on_decoder_grads"] = None
-    net.honour_video_lengths, net.train_video_lengths = switches
+    net.honour_video_lengths, net.train_video_lengths, net.train_mel_lengths = switches
     return log

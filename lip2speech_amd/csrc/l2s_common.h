@@ -538,8 +538,23 @@ int launch_bilstm_capture_adj_init(const float* dh_init, float* dh_last, float* 
 int launch_bilstm_capture_adj_cell(const float* dcell, int ld_dcell, float* dc_carry, const int* lens, int B, int len, hipStream_t s);
 // adjoint of the reset, rows with len_b == len: gate gradients (frag16, K = 2048) move to dg_reset, the carried cell gradient to ds_e; both are cut
 int launch_bilstm_reset_adj(float* dg_frag, float* dg_reset, float* dc_carry, float* ds_e, const int* lens, int B, int len, hipStream_t s);
-// rows t >= len_b of x (B*T rows, ldx) := 0 over `cols` columns
-int launch_zero_pad_rows(float* x, int ldx, const int* lens, int B, int T, int cols, hipStream_t s);
+// rows t >= lens[b] of x (B*T rows, ldx) := 0 over `cols` columns (lens: segment 0 of a video-length or a mel-length table; `name`: the profile scope)
+int launch_zero_pad_rows(float* x, int ldx, const int* lens, int B, int T, int cols, hipStream_t s, const char* name = "train_bwd_zero_pad_rows");
+// ---- per-clip mel lengths on the training path (masked_mel.hip; l2s_loss_lengths and the l2s_train_postnet_masked_fwd / _masked_bwd entry points).  The device
+// table is 2*B int32: S_b, then m_b = the clip's content rows (video_lengths[b] / 7; m without video lengths).  Segment 0 is what launch_zero_pad_rows reads
+int check_mel_lengths(const int32_t* mel_lengths, int B, int S);      // B in [1, 96] and every S_b in [1, S], else an error that names the clip
+int64_t mel_len_table_words(int B);
+int launch_mel_len_table(const int32_t* mel_lengths, const int32_t* video_lengths, int B, int m, int* table, hipStream_t s);
+int launch_zero_cf_past_len(float* x, const int* lens, int B, int C, int S, hipStream_t s);      // x (B, C, S) channel-first: positions s >= S_b := 0
+// the 4-term loss of train_kernels.hip (l2s_loss): term 0 = sum (a-b)^2 over mel, 1 = same for mel_post, 2 = BCE sum, 3 = KLD sum; gradients in the same pass
+struct LossP {
+    const float* mel; const float* mel_post; const float* mel_tgt;    // (B,80,S) channel-first, like the reference's outputs
+    const float* stop; const float* gate;                            // (B,S)
+    const float* dis;                                                // (R,V)
+    float* dmel; float* dmel_post; float* dstop; float* ddis;        // gradients of the summed loss (may be null)
+    int64_t n_mel, n_stop, n_dis; int R, V;
+};
+int launch_loss(const LossP& p, double* partials /*[4*1024]*/, float* out5, hipStream_t s);
 // backward of the adaptive average pooling + concatenation: dp (B,m,nmaps*C) -> d map_j; acc[j]: add to dx[j].  The masked form matches pool_cat_masked's bins
 struct PoolCatBwdP { float* dx[5]; int L[5]; int ld[5]; int acc[5]; int nmaps; int B, m, C; const float* dp; };
 int launch_pool_cat_masked_bwd(const PoolCatBwdP& p, const PoolDiv& d, const int* lens, hipStream_t s);

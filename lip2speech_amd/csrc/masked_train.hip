@@ -184,11 +184,11 @@ __global__ __launch_bounds__(256) void zero_pad_rows_kernel(float* __restrict__ 
     }
 }
 
-int launch_zero_pad_rows(float* x, int ldx, const int* lens, int B, int T, int cols, hipStream_t s) {
+int launch_zero_pad_rows(float* x, int ldx, const int* lens, int B, int T, int cols, hipStream_t s, const char* name) {
     L2S_REQUIRE(cols % 4 == 0 && ldx % 4 == 0, "zero_pad_rows: float4 rows");
     const int64_t rows = (int64_t)B * T, total = rows * (cols / 4);
     const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>((total + 255) / 256, 8192));
-    ProfScope ps("train_bwd_zero_pad_rows", s);
+    ProfScope ps(name, s);
     hipLaunchKernelGGL(zero_pad_rows_kernel, dim3(blocks), dim3(256), 0, s, x, ldx, lens, T, rows, cols / 4);
     L2S_CHECK_HIP(hipGetLastError());
     return 0;

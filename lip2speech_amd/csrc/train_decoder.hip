@@ -205,7 +205,11 @@ static int launch_gemm_batch_stats(const l2s_model* m, GemmBatch gb, float* stat
     return launch_gemm_finish(gb, s, epilogue_name);
 }
 
-static int postnet_train_fwd(l2s_model* m, const float* mel, int B, int S, float* tape, float* mel_post, const float* drop, hipStream_t s) {
+// mlens (device, B int32; null = unmasked): per-clip mel lengths S_b.  Rows s >= S_b of the input of every layer - the caller zeroed those of `mel` - and of
+// mel_post are zeros: the five 5-tap convs see at a clip's end what they see at the end of a batch of S_b frames.  Dropout multipliers of pad rows only
+// reach values that are overwritten
+static int postnet_train_fwd(l2s_model* m, const float* mel, int B, int S, float* tape, float* mel_post, const float* drop, hipStream_t s,
+                             const int* mlens = nullptr) {
     PostTape t = post_tape(tape, B, S);
     for (int l = 0; l < 5; ++l) {
         // the layer is inference's (decoder_stages.h) on the f32 weights; the tape store and the dropout mask are laid over it
@@ -220,6 +224,8 @@ static int postnet_train_fwd(l2s_model* m, const float* mel, int B, int S, float
             const int rows = B * S;
             if (launch_gemm_batch_stats(m, gb, t.stats, 0, &L, &rows, s, "train_postnet_conv_stats", "train_postnet_conv_epilogue")) return 1;
         } else if (launch_gemm(gb, s, "train_postnet_conv_gemm")) return 1;
+        if (mlens && (l < 4 ? launch_zero_pad_rows(t.x[l], 512, mlens, B, S, 512, s, "train_postnet_zero_pad_rows") : launch_zero_cf_past_len(mel_post, mlens, B, NM_, S, s)))
+            return 1;
     }
     return 0;
 }
@@ -239,10 +245,13 @@ static int mul_inplace(float* x, const float* m, int64_t n, hipStream_t s) {
 }
 
 static int postnet_train_bwd(l2s_model* m, const float* mel, const float* dmel_post_cf, int B, int S, float* tape, float* dmel, const float* drop, void* ws,
-                             int64_t ws_bytes, hipStream_t s) {
+                             int64_t ws_bytes, hipStream_t s, const int* mlens = nullptr) {
     const Weights& w = m->w;
     PostTape t = post_tape(tape, B, S);
     const int64_t R = (int64_t)B * S;
+    // mlens: the adjoint of the forward's zeroing - the gradient of every zeroed row is cut where it arrives (pad rows of dmel_post count as zeros whatever they
+    // hold; pad rows of each dx are zeroed before anything reads them), so pad rows add exact zeros to every parameter gradient and nothing crosses a clip's end
+    auto cut = [&](float* x, int cols) { return mlens ? launch_zero_pad_rows(x, cols, mlens, B, S, cols, s, "train_postnet_bwd_zero_pad_rows") : 0; };
     Bump bp(ws, ws_bytes);
     float* g = bp.f(R * 512);          // gradient wrt the current layer's output
     float* gconv = bp.f(R * 512);      // gradient wrt the conv output
@@ -256,12 +265,13 @@ static int postnet_train_bwd(l2s_model* m, const float* mel, const float* dmel_p
     const std::string P = "decoder.postnet.";
     // mel_post = z4 + mel, channel-first: g4 (B*S,80) = transpose(dmel_post); dmel += g4
     if (add_transposed_bcs(dmel_post_cf, B, NM_, S, g, false, s)) return 1;
+    if (cut(g, NM_)) return 1;
     if (add_into(g, dmel, R * NM_, s)) return 1;
     for (int l = 4; l >= 0; --l) {
         const int cin = l == 0 ? NM_ : 512, cout = l == 4 ? NM_ : 512;
         const float* xin = l == 0 ? mel : t.x[l - 1];
         const std::string c = P + "convolutions." + std::to_string(l);
-        if (drop) { if (mul_inplace(g, post_mask(drop, B, S, l), R * cout, s)) return 1; }     // dropout sits after the residual add (layers 0..3) / after the last conv
+        if (drop) { if (mul_inplace(g, post_mask(drop, B, S, l), R * cout, s) || cut(g, cout)) return 1; }     // dropout sits after the residual add (layers 0..3) / after the last conv; a pad row's multiplier met a zero
         ActBwdP a{};
         a.dy = g; a.z = t.z[l]; a.dconv = gconv; a.rows = R; a.C = cout;
         a.act = l < 4 ? ACT_PSINE : ACT_NONE; a.actw = w.post[l].actw;
@@ -280,6 +290,7 @@ static int postnet_train_bwd(l2s_model* m, const float* mel, const float* dmel_p
         float* gin = gprev;
         // B*S rows by <= 512 columns is 80 tiles at B = 8 with K = 5 * 512: five K slices
         if (launch_gemm_bwd_splitk(bwd_dx(gconv, cout, w.post[l].W, gin, cin, B, S, S, cout, cin, 5, 2, false), 5, skp, s, "train_postnet_dx")) return 1;
+        if (cut(gin, cin)) return 1;
         if (l >= 1 && l <= 3) { if (add_into(g, gin, R * 512, s)) return 1; }     // x_l = PSine(..) + x_{l-1}
         if (l == 0) { if (add_into(gin, dmel, R * NM_, s)) return 1; }
         std::swap(g, gprev);
@@ -1692,6 +1703,40 @@ int l2s_train_postnet_bwd(l2s_model* m, const float* mel, const float* dmel_post
     L2S_REQUIRE(m->canon("decoder.postnet.convolutions.0.1.weight") != nullptr, "parameters not bound (l2s_train_bind)");
     Bf16Scope bf16scope(m->opt.train_bf16);      // GEMMs / Conv1d stacks with bf16 operands when the model asks for it (fp32 accumulation)
     return postnet_train_bwd(m, mel, dmel_post, B, S, tape, dmel, drop, ws, ws_bytes, (hipStream_t)stream);
+}
+
+// ---- per-clip mel lengths (include/l2s.h "training with per-clip mel lengths").  Like the video-length calls, forward and backward each write their own
+// device copy of the table behind the unmasked tape, on their stream, before their first launch
+static int64_t mel_table_floats(int B) { return align_up(mel_len_table_words(B), 64) + 64; }
+static int masked_postnet_lens(const l2s_model* m, const int32_t* mel_lengths, int B, int S, float* tape, hipStream_t s, int*& dev) {
+    if (check_mel_lengths(mel_lengths, B, S)) return 1;
+    L2S_REQUIRE(!m->bn_batch, "the l2s_train_postnet_masked_fwd / _masked_bwd entry points run on running statistics: batch_stats = 1 (l2s_train_set_bn) with mel_lengths is not supported");
+    L2S_REQUIRE(!m->opt.train_bf16, "option \"train_bf16\" with mel_lengths is not supported");
+    dev = reinterpret_cast<int*>(tape + align_up(post_tape_floats(B, S), 64));
+    return launch_mel_len_table(mel_lengths, nullptr, B, 0, dev, s);
+}
+
+int64_t l2s_train_postnet_tape_floats_masked(int B, int S) { return align_up(post_tape_floats(B, S), 64) + mel_table_floats(B); }
+int64_t l2s_train_postnet_ws_bytes_masked(int B, int S) { return l2s_train_postnet_ws_bytes(B, S); }      // the row kernels work in place
+
+int l2s_train_postnet_masked_fwd(l2s_model* m, float* mel, int B, int S, float* tape, float* mel_post, const float* drop, void* stream,
+                                 const int32_t* mel_lengths) {
+    L2S_REQUIRE(m && m->finalized && m->has_dec && mel && tape && mel_post, "bad arguments");
+    L2S_REQUIRE(S >= 1 && S <= L2S_MAX_STEPS, "sizes");
+    int* mlens = nullptr;
+    if (masked_postnet_lens(m, mel_lengths, B, S, tape, (hipStream_t)stream, mlens)) return 1;
+    if (launch_zero_pad_rows(mel, NM_, mlens, B, S, NM_, (hipStream_t)stream, "train_postnet_zero_pad_rows")) return 1;      // what the loop decoded past the clip's end
+    return postnet_train_fwd(m, mel, B, S, tape, mel_post, drop, (hipStream_t)stream, mlens);
+}
+
+int l2s_train_postnet_masked_bwd(l2s_model* m, const float* mel, const float* dmel_post, int B, int S, float* tape, float* dmel, const float* drop, void* ws,
+                                 int64_t ws_bytes, void* stream, const int32_t* mel_lengths) {
+    L2S_REQUIRE(m && m->finalized && m->has_dec && mel && dmel_post && tape && dmel && ws, "bad arguments");
+    L2S_REQUIRE(S >= 1 && S <= L2S_MAX_STEPS, "sizes");
+    L2S_REQUIRE(m->canon("decoder.postnet.convolutions.0.1.weight") != nullptr, "parameters not bound (l2s_train_bind)");
+    int* mlens = nullptr;
+    if (masked_postnet_lens(m, mel_lengths, B, S, tape, (hipStream_t)stream, mlens)) return 1;
+    return postnet_train_bwd(m, mel, dmel_post, B, S, tape, dmel, drop, ws, ws_bytes, (hipStream_t)stream, mlens);
 }
 
 }  // extern "C"

@@ -84,14 +84,7 @@ int launch_adamw(float* p, const float* g, float* m, float* v, float* vmax, int6
 }
 
 // ---- loss (train_utils/losses.py:69-77): mel MSE + 10 * post-net mel MSE + BCE-with-logits on the gate + KLD(content_dis || uniform)
-// term: 0 = sum (a-b)^2 over mel, 1 = same for mel_post, 2 = BCE sum, 3 = KLD sum.  Gradients are written in the same pass.
-struct LossP {
-    const float* mel; const float* mel_post; const float* mel_tgt;    // (B,80,S) channel-first, like the reference's outputs
-    const float* stop; const float* gate;                            // (B,S)
-    const float* dis;                                                // (R,V)
-    float* dmel; float* dmel_post; float* dstop; float* ddis;        // gradients of the summed loss (may be null)
-    int64_t n_mel, n_stop, n_dis; int R, V;
-};
+// term: 0 = sum (a-b)^2 over mel, 1 = same for mel_post, 2 = BCE sum, 3 = KLD sum.  Gradients are written in the same pass.  (LossP: l2s_common.h)
 
 __global__ __launch_bounds__(256) void loss_partial_kernel(const LossP p, double* __restrict__ partials /*[4][RED_BLOCKS]*/) {
     __shared__ double sh[4];

@@ -28,9 +28,10 @@ class _HipTrainStep(torch.autograd.Function):
     parameter of the model - it only makes autograd call `backward`."""
 
     @staticmethod
-    def forward(ctx, anchor, model, video, emb, gumbel, mels, mask, drop, lens=None):
+    def forward(ctx, anchor, model, video, emb, gumbel, mels, mask, drop, lens=None, mlens=None):
         # lens (`Lip2Speech.train_video_lengths`): the host lengths of a ZERO-padded batch - the three stages that see the video run their *_masked
-        # entry points (include/l2s.h "training with per-clip video lengths"), forward and backward
+        # entry points (include/l2s.h "training with per-clip video lengths"), forward and backward.  mlens (`Lip2Speech.train_mel_lengths`): the host mel
+        # lengths - the post-net runs its *_masked entry points ("training with per-clip mel lengths"): rows s >= S_b of mel are zeroed, of mel_post zeros
         nm = model.native_model()
         B, _, T, _, _ = video.shape
         S = mels.shape[2]
@@ -53,9 +54,9 @@ class _HipTrainStep(torch.autograd.Function):
             bos = model.decoder.BOS.detach().to(torch.float32).reshape(1, 1, -1).expand(B, 1, -1)
             teacher = torch.cat([bos, mels.detach().to(torch.float32).permute(0, 2, 1)[:, :S - 1]], dim=1).contiguous()
         (mel, stop, logits), sctx = nm.train_steps_fwd(state, B, T, S, teacher, mask, drop=drop, video_lengths=lens)
-        mel_post, post_tape = nm.train_postnet_fwd(mel, pdrop)
+        mel_post, post_tape = nm.train_postnet_fwd(mel, pdrop, mel_lengths=mlens)
         ctx.model, ctx.tapes = model, (video, emb, vis, etape, state, ptape, sctx, mel, post_tape, pdrop, drop.get("feat"))
-        ctx.lens, ctx.real = lens, real
+        ctx.lens, ctx.real, ctx.mlens = lens, real, mlens
         ctx.mark_non_differentiable(logits)
         if ctx.bn_batch:
             model._count_batch()
@@ -77,7 +78,7 @@ class _HipTrainStep(torch.autograd.Function):
         n_dec = model._n_decoder_elems()
         z = lambda g, ref: torch.zeros_like(ref) if g is None else g  # noqa: E731
         wbuf = nm.train_pack_weights(video.device)
-        dmel = nm.train_postnet_bwd(mel, z(dmel_post, mel.permute(0, 2, 1)), post_tape, pdrop)
+        dmel = nm.train_postnet_bwd(mel, z(dmel_post, mel.permute(0, 2, 1)), post_tape, pdrop, mel_lengths=ctx.mlens)
         if dmel_cf is not None:
             dmel += dmel_cf.permute(0, 2, 1)
         sg = nm.train_steps_bwd(sctx, dmel, z(dstop, mel[:, :, :1]).reshape(B, S), wbuf=wbuf)
@@ -98,7 +99,7 @@ class _HipTrainStep(torch.autograd.Function):
         if prev is not None:
             flat.grad[n_dec:] += prev[n_dec:]
         model._attach_grads()
-        return (None,) * 9
+        return (None,) * 10
 
 
 class Lip2Speech(NativeBacked):
@@ -119,6 +120,11 @@ class Lip2Speech(NativeBacked):
         # the weights that is evaluated and served with lengths honoured.  Running statistics only: the module must be in eval() mode (dropout then
         # comes through `dropout_masks=`); train() mode - batch statistics - is refused by name, as the library refuses it.
         self.train_video_lengths = False
+        # Off (the default): the post-net of a differentiable `forward` runs over all S frames of every clip, as in the reference.  On, together with the two
+        # switches above: it hands `melspec_lengths` to l2s_train_postnet_masked_fwd / _masked_bwd (include/l2s.h "training with per-clip mel lengths") - a
+        # clip's post-net sees zeros past its own last frame, mel_post is zeros there; give the same lengths to `Loss.forward(melspec_lengths=)`.
+        # Running statistics only, like `train_video_lengths`: train() mode is refused by name.
+        self.train_mel_lengths = False
         # one packed weight blob for the whole path; the sub-modules borrow it while they live inside this model
         self.encoder.__dict__["_native_parent"] = self
         self.decoder.__dict__["_native_parent"] = self
@@ -189,6 +195,17 @@ class Lip2Speech(NativeBacked):
                 tf_ratio, speaker_embedding=None, gumbel_noise=None, dropout_masks=None):
         masked = bool(self.honour_video_lengths) and video_lengths is not None
         wants_grad = torch.is_grad_enabled() and any(p.requires_grad for p in self.decoder.parameters())
+        mel_masked = bool(self.train_mel_lengths) and (self.training or wants_grad)
+        if mel_masked:
+            if not (self.honour_video_lengths and self.train_video_lengths):
+                raise NotImplementedError("train_mel_lengths: needs `honour_video_lengths` and `train_video_lengths` switched on as well (the mel lengths are the "
+                                          "other half of the same padding)")
+            if self.training:
+                raise NotImplementedError("train_mel_lengths: train() mode normalises with batch statistics, and the length-masked post-net runs on running "
+                                          "statistics only (batch_stats = 1 with mel_lengths is refused, include/l2s.h); call in eval() mode and hand the "
+                                          "dropout multipliers in through dropout_masks=")
+            if video_lengths is None or melspec_lengths is None:
+                raise ValueError("train_mel_lengths: video_lengths and melspec_lengths are both needed")
         if masked and (self.training or wants_grad):
             if not self.train_video_lengths:
                 raise NotImplementedError("honour_video_lengths: a training call takes the length-masked entry points (l2s_train_*_masked_fwd / _masked_bwd, include/l2s.h) only "
@@ -201,7 +218,7 @@ class Lip2Speech(NativeBacked):
                 raise NotImplementedError("train_video_lengths: no gradient is wanted here; the forward-only length-masked route is eval() mode under torch.no_grad()")
         if wants_grad:
             return self._forward_train(video_frames, face_frames, melspecs, video_lengths, tf_ratio, speaker_embedding, gumbel_noise, dropout_masks,
-                                       honour_lengths=masked)
+                                       honour_lengths=masked, melspec_lengths=melspec_lengths if mel_masked else None)
         if self.training:
             # a no_grad call on a train()-mode module: the feature dropout of model.py:26 is live - the staged route through the sub-modules
             video_features = F.dropout(self.encoder(video_frames), 0.1, True)
@@ -366,7 +383,7 @@ class Lip2Speech(NativeBacked):
         return job
 
     def _forward_train(self, video_frames, face_frames, melspecs, video_lengths, tf_ratio, speaker_embedding, gumbel_noise, dropout_masks=None,
-                       honour_lengths=False):
+                       honour_lengths=False, melspec_lengths=None):
         """The differentiable route (train.py:167-184): same outputs as `forward`, attached to autograd through `_HipTrainStep`.
         In `train()` mode the five dropout sites of the reference are active (multipliers drawn on the device by `training.draw_dropout`
         and handed to the kernels as inputs, or supplied through `dropout_masks=`); in `eval()` mode they are off (the configuration the
@@ -390,8 +407,12 @@ class Lip2Speech(NativeBacked):
             drop = draw_dropout(B, T, S, video_frames.device)
         # `honour_lengths` (forward: both switches on): checked on the host before anything reaches the device
         lens = native.video_lengths_array(video_lengths, B, T) if honour_lengths else None
+        mlens = native.mel_lengths_array(melspec_lengths, B, S) if melspec_lengths is not None else None      # `train_mel_lengths`: likewise
         mel, mel_post, stop, attn, dis = _HipTrainStep.apply(self.decoder.BOS, self, video_frames.detach().to(torch.float32).contiguous(), emb,
-                                                             gumbel_noise.detach().to(torch.float32).contiguous(), melspecs, mask if any(mask) else None, drop, lens)
+                                                             gumbel_noise.detach().to(torch.float32).contiguous(), melspecs, mask if any(mask) else None, drop, lens, mlens)
+        if mlens is not None:      # what `Loss.forward(melspec_lengths=)` reads: the video lengths this call honoured, marked as such
+            video_lengths = torch.as_tensor(video_lengths).detach().clone()
+            video_lengths.l2s_honoured = True
         return [mel, mel_post, stop, emb, attn, dis, video_lengths]
 
     def inference(self, video_frames, face_frames, speaker_embedding=None, return_attention_map=False, gumbel_noise=None, early_stop=None,

@@ -52,6 +52,8 @@ ABI_SYMBOLS = (
     "l2s_train_encoder_tape_floats_masked", "l2s_train_encoder_ws_bytes_masked", "l2s_train_prologue_tape_floats_masked", "l2s_train_prologue_ws_bytes_masked",
     "l2s_train_steps_tape_floats_masked", "l2s_train_encoder_masked_fwd", "l2s_train_encoder_masked_bwd", "l2s_train_prologue_masked_fwd",
     "l2s_train_prologue_masked_bwd", "l2s_train_steps_masked_fwd", "l2s_train_steps_masked_bwd",
+    "l2s_loss_lengths_check", "l2s_train_scratch_bytes_lengths", "l2s_loss_lengths", "l2s_train_postnet_tape_floats_masked", "l2s_train_postnet_ws_bytes_masked",
+    "l2s_train_postnet_masked_fwd", "l2s_train_postnet_masked_bwd",
     "l2s_train_bind", "l2s_train_postnet_tape_floats", "l2s_train_postnet_ws_bytes", "l2s_train_postnet_fwd", "l2s_train_postnet_bwd",
     "l2s_profile_enable", "l2s_profile_reset", "l2s_profile_count", "l2s_profile_get",
 )
@@ -284,6 +286,18 @@ def _bind(L: ctypes.CDLL) -> None:
             getattr(L, name).restype = _i64
         for name in ("l2s_train_encoder_fwd", "l2s_train_encoder_bwd", "l2s_train_prologue_fwd", "l2s_train_prologue_bwd", "l2s_train_steps_fwd", "l2s_train_steps_bwd"):
             getattr(L, name[:-4] + "_masked" + name[-4:]).argtypes = getattr(L, name).argtypes + [_lens]      # l2s_train_<stage>_masked_fwd / _bwd
+    # training with per-clip mel lengths (include/l2s.h): likewise absent from a library built before them (timing/masked_mel times one next to this build)
+    if hasattr(L, "l2s_loss_lengths"):
+        _lens = ctypes.POINTER(ctypes.c_int32)
+        L.l2s_loss_lengths_check.argtypes = [_lens, _lens, _i, _i, _i]
+        L.l2s_train_scratch_bytes_lengths.argtypes = [_i]
+        L.l2s_train_scratch_bytes_lengths.restype = _i64
+        L.l2s_loss_lengths.argtypes = L.l2s_loss.argtypes + [_lens, _lens, _i, _fp]
+        for name in ("l2s_train_postnet_tape_floats_masked", "l2s_train_postnet_ws_bytes_masked"):
+            getattr(L, name).argtypes = [_i, _i]
+            getattr(L, name).restype = _i64
+        L.l2s_train_postnet_masked_fwd.argtypes = L.l2s_train_postnet_fwd.argtypes + [_lens]
+        L.l2s_train_postnet_masked_bwd.argtypes = L.l2s_train_postnet_bwd.argtypes + [_lens]
     # ragged groups (include/l2s.h): likewise absent from a library built before them (tools/ragged/time_ragged.py times one next to this build)
     if hasattr(L, "l2s_inference_ragged"):
         _lens = ctypes.POINTER(ctypes.c_int32)
@@ -421,6 +435,27 @@ def video_lengths_array(video_lengths, B: int, T: int):
     bad = [(b, int(v)) for b, v in enumerate(arr) if v < 7 or v > T]
     if bad:
         raise ValueError(f"video_lengths outside [7, T = {T}]: " + ", ".join(f"clip {b}: {v}" for b, v in bad))
+    return (ctypes.c_int32 * B)(*[int(v) for v in arr])
+
+
+def mel_lengths_array(mel_lengths, B: int, S: int):
+    """The `mel_lengths` argument of `l2s_loss_lengths` and the `l2s_train_postnet_masked_*` entry points (include/l2s.h "training with per-clip mel
+    lengths"), checked BEFORE the native call: B integers in [1, S] -> a host `int32[B]` ctypes array.  Same errors as `video_lengths_array`."""
+    if mel_lengths is None:
+        raise ValueError("mel_lengths is None: one length per clip is needed")
+    if isinstance(mel_lengths, torch.Tensor):
+        if mel_lengths.is_floating_point() or mel_lengths.is_complex() or mel_lengths.dtype == torch.bool:
+            raise TypeError(f"mel_lengths must hold integers, got {mel_lengths.dtype}")
+        arr = mel_lengths.detach().cpu().numpy()
+    else:
+        arr = np.asarray(mel_lengths)
+        if arr.dtype.kind not in "iu":
+            raise TypeError(f"mel_lengths must hold integers, got {arr.dtype}")
+    if arr.shape != (B,):
+        raise ValueError(f"mel_lengths must have shape ({B},) - one length per clip - got {tuple(arr.shape)}")
+    bad = [(b, int(v)) for b, v in enumerate(arr) if v < 1 or v > S]
+    if bad:
+        raise ValueError(f"mel_lengths outside [1, S = {S}]: " + ", ".join(f"clip {b}: {v}" for b, v in bad))
     return (ctypes.c_int32 * B)(*[int(v) for v in arr])
 
 
@@ -993,22 +1028,40 @@ class NativeModel:
         """Device-side re-pack of the weight blob from the bound tensors (needs self.set_option('refresh_map', 1) before load())."""
         self._check(self._L.l2s_train_refresh_weights(self._h, _stream()))
 
-    def train_postnet_fwd(self, mel: torch.Tensor, drop: Optional[torch.Tensor] = None):
-        """Post-net forward with a tape: mel (B,S,80) -> (mel_post (B,80,S), tape).  drop: packed dropout multipliers (postnet_drop_pack)."""
-        mel = _f32(mel)
+    def train_postnet_fwd(self, mel: torch.Tensor, drop: Optional[torch.Tensor] = None, mel_lengths=None):
+        """Post-net forward with a tape: mel (B,S,80) -> (mel_post (B,80,S), tape).  drop: packed dropout multipliers (postnet_drop_pack).
+        `mel_lengths` (B integers in [1, S]): `l2s_train_postnet_masked_fwd` - rows s >= S_b of `mel` are ZEROED IN PLACE (when `mel` is fp32 and contiguous,
+        as the loop returns it), the post-net sees zeros past every clip's end and mel_post[b, :, S_b:] is exact zeros; hand the same lengths (and this tape)
+        to `train_postnet_bwd`."""
         B, S, _ = mel.shape
+        lens = mel_lengths_array(mel_lengths, B, S) if mel_lengths is not None else None      # checked on the host, before anything else
+        mel = _f32(mel)
         L = self._L
-        tape = torch.zeros(int(L.l2s_train_postnet_tape_floats(B, S)), dtype=torch.float32, device=mel.device)
         out = torch.empty(B, 80, S, dtype=torch.float32, device=mel.device)
+        if lens is not None:
+            tape = torch.zeros(int(L.l2s_train_postnet_tape_floats_masked(B, S)), dtype=torch.float32, device=mel.device)
+            self.calls["l2s_train_postnet_masked_fwd"] += 1
+            self._check(L.l2s_train_postnet_masked_fwd(self._h, _ptr(mel), B, S, _ptr(tape), _ptr(out), _ptr(drop), _stream(), lens))
+            return out, tape
+        tape = torch.zeros(int(L.l2s_train_postnet_tape_floats(B, S)), dtype=torch.float32, device=mel.device)
         self._check(L.l2s_train_postnet_fwd(self._h, _ptr(mel), B, S, _ptr(tape), _ptr(out), _ptr(drop), _stream()))
         return out, tape
 
-    def train_postnet_bwd(self, mel: torch.Tensor, dmel_post: torch.Tensor, tape: torch.Tensor, drop: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """Post-net backward: dmel_post (B,80,S) -> dmel (B,S,80) (residual path included); parameter gradients into the bound slots."""
-        mel, dmel_post = _f32(mel), _f32(dmel_post)
+    def train_postnet_bwd(self, mel: torch.Tensor, dmel_post: torch.Tensor, tape: torch.Tensor, drop: Optional[torch.Tensor] = None, mel_lengths=None) -> torch.Tensor:
+        """Post-net backward: dmel_post (B,80,S) -> dmel (B,S,80) (residual path included); parameter gradients into the bound slots.
+        `mel_lengths`: the lengths of the masked forward that wrote `tape` (`l2s_train_postnet_masked_bwd`): pad positions of dmel_post are never used,
+        rows s >= S_b of dmel come back as exact zeros."""
         B, S, _ = mel.shape
+        lens = mel_lengths_array(mel_lengths, B, S) if mel_lengths is not None else None
+        mel, dmel_post = _f32(mel), _f32(dmel_post)
         L = self._L
         dmel = torch.zeros_like(mel)
+        if lens is not None:
+            ws = torch.empty(int(L.l2s_train_postnet_ws_bytes_masked(B, S)), dtype=torch.uint8, device=mel.device)
+            self.calls["l2s_train_postnet_masked_bwd"] += 1
+            self._check(L.l2s_train_postnet_masked_bwd(self._h, _ptr(mel), _ptr(dmel_post), B, S, _ptr(tape), _ptr(dmel), _ptr(drop), _ptr(ws), ws.numel(),
+                                                       _stream(), lens))
+            return dmel
         ws = torch.empty(int(L.l2s_train_postnet_ws_bytes(B, S)), dtype=torch.uint8, device=mel.device)
         self._check(L.l2s_train_postnet_bwd(self._h, _ptr(mel), _ptr(dmel_post), B, S, _ptr(tape), _ptr(dmel), _ptr(drop), _ptr(ws), ws.numel(), _stream()))
         return dmel

@@ -81,9 +81,13 @@ class AdamWAmsgrad:
         return self._norm * grad_mul
 
 
-def loss_terms(mel, mel_post, stop, content_dis, mel_target, gate_target, want_grads: bool = True):
+def loss_terms(mel, mel_post, stop, content_dis, mel_target, gate_target, want_grads: bool = True, mel_lengths=None, video_lengths=None,
+               per_clip: bool = False):
     """The reference's `Loss.forward` (losses.py:69-77) on the device: returns ({'mel_loss','postnet_mel_loss','gate_loss','KLD',
-    'loss'} as a (5,) tensor, gradients dict).  mel/mel_post/mel_target (B,80,S); stop (B,S[,1]); gate (B,S); content_dis (R,501)."""
+    'loss'} as a (5,) tensor, gradients dict).  mel/mel_post/mel_target (B,80,S); stop (B,S[,1]); gate (B,S); content_dis (R,501).
+    `mel_lengths` (B integers in [1, S]): `l2s_loss_lengths` (include/l2s.h "training with per-clip mel lengths") - the mean over the clips of each clip's
+    own loss over its S_b frames and, with `video_lengths` (B integers in [7, T], R = B * min_T(T)), its own min_T(len_b) content rows; gradients at pad
+    positions are exact zeros.  `per_clip`: a third result, the (B,4) tensor of each clip's own four terms."""
     L = native.lib()
     f32 = lambda t: t.detach().to(torch.float32).contiguous()      # noqa: E731
     mel, mel_post, mel_target, content_dis = f32(mel), f32(mel_post), f32(mel_target), f32(content_dis)
@@ -92,12 +96,35 @@ def loss_terms(mel, mel_post, stop, content_dis, mel_target, gate_target, want_g
     B, _, S = mel.shape
     R = content_dis.shape[0]
     out = torch.empty(5, dtype=torch.float32, device=mel.device)
-    scratch = torch.empty(int(L.l2s_train_scratch_bytes()), dtype=torch.uint8, device=mel.device)
     grads = {}
     if want_grads:
         grads = {"mel": torch.empty_like(mel), "mel_post": torch.empty_like(mel_post), "stop": torch.empty_like(stop),
                  "content_dis": torch.empty_like(content_dis)}
     gp = lambda k: grads[k].data_ptr() if want_grads else None      # noqa: E731
+    if mel_lengths is None:
+        if video_lengths is not None or per_clip:
+            raise ValueError("loss_terms: video_lengths= and per_clip= belong to the length-aware loss: give mel_lengths= as well")
+    else:
+        mlens = native.mel_lengths_array(mel_lengths, B, S)      # host checks first: a bad table never reaches the device
+        vlens, T = None, 0
+        if video_lengths is not None:
+            if R % B:
+                raise ValueError(f"loss_terms: content_dis has {R} rows, not a multiple of B = {B}")
+            T = max(int(v) for v in video_lengths)
+            T = max(T, 7 * (R // B))                                  # the padded T itself is not needed: any T with min_T(T) = R / B names the same rows
+            if native.min_T(T) != R // B:
+                raise ValueError(f"loss_terms: content_dis holds {R // B} rows per clip, but a clip of {T} frames has {native.min_T(T)}")
+            vlens = native.video_lengths_array(video_lengths, B, T)
+        pc = torch.empty(B, 4, dtype=torch.float32, device=mel.device) if per_clip else None
+        need = int(L.l2s_train_scratch_bytes_lengths(B))
+        if need < 0:
+            native.check(L.l2s_loss_lengths_check(mlens, vlens, B, S, T))
+        scratch = torch.empty(need, dtype=torch.uint8, device=mel.device)
+        native.check(L.l2s_loss_lengths(mel.data_ptr(), mel_post.data_ptr(), mel_target.data_ptr(), stop.data_ptr(), gate_target.data_ptr(),
+                                        content_dis.data_ptr(), B, S, R, out.data_ptr(), gp("mel"), gp("mel_post"), gp("stop"), gp("content_dis"),
+                                        scratch.data_ptr(), torch.cuda.current_stream().cuda_stream, mlens, vlens, T, pc.data_ptr() if per_clip else None))
+        return (out, grads, pc) if per_clip else (out, grads)
+    scratch = torch.empty(int(L.l2s_train_scratch_bytes()), dtype=torch.uint8, device=mel.device)
     native.check(L.l2s_loss(mel.data_ptr(), mel_post.data_ptr(), mel_target.data_ptr(), stop.data_ptr(), gate_target.data_ptr(),
                             content_dis.data_ptr(), B, S, R, out.data_ptr(), gp("mel"), gp("mel_post"), gp("stop"), gp("content_dis"),
                             scratch.data_ptr(), torch.cuda.current_stream().cuda_stream))
@@ -118,7 +145,7 @@ def draw_dropout(B: int, T: int, S: int, device, generator=None) -> dict:
 
 
 def decoder_forward_backward(nm: "native.NativeModel", vis, emb, gumbel, mel_target, gate_target, teacher_mask=None, bos=None, drop=None,
-                             video_lengths=None):
+                             video_lengths=None, mel_lengths=None):
     """Forward + backward of the decoder half of `Lip2Speech.forward` + `Loss.forward` (reference: model.py:34-41 -> decoder.py:320-379,
     losses.py:69-77, train.py:172-184) with eval-mode statistics (running BN stats, no dropout): prologue -> S-step loop -> post-net ->
     4-term loss, then back through the post-net, the loop (BPTT) and the prologue.  Parameter gradients land in the slots bound with
@@ -127,7 +154,9 @@ def decoder_forward_backward(nm: "native.NativeModel", vis, emb, gumbel, mel_tar
     teacher_mask (S,) bool marks the steps whose input frame is the ground-truth previous frame (scheduled sampling made explicit,
     decoder.py:355-359); `bos` is the device BOS parameter (needed only with a mask).
     `video_lengths` (B integers in [7, T]; `vis` of a ZERO-padded batch): the length-masked entry points (include/l2s.h "training with per-clip video
-    lengths"); the feature-dropout multipliers of rows t >= len_b are never read."""
+    lengths"); the feature-dropout multipliers of rows t >= len_b are never read.
+    `mel_lengths` (B integers in [1, S]; targets padded to S): the post-net and the loss take their mel-length forms (include/l2s.h "training with per-clip
+    mel lengths"); the loop still runs S steps per clip and its pad steps receive exact-zero gradients."""
     B, T, _ = vis.shape
     S = mel_target.shape[2]
     drop = drop or {}
@@ -151,11 +180,11 @@ def decoder_forward_backward(nm: "native.NativeModel", vis, emb, gumbel, mel_tar
     else:
         teacher_mask = None
     (mel, stop, logits), ctx = nm.train_steps_fwd(state, B, T, S, teacher, teacher_mask, drop=drop, video_lengths=lens)
-    mel_post, post_tape = nm.train_postnet_fwd(mel, pdrop)
+    mel_post, post_tape = nm.train_postnet_fwd(mel, pdrop, mel_lengths=mel_lengths)
     mel_cf = mel.permute(0, 2, 1).contiguous()
-    loss, g = loss_terms(mel_cf, mel_post, stop, dis, mel_target, gate_target)
+    loss, g = loss_terms(mel_cf, mel_post, stop, dis, mel_target, gate_target, mel_lengths=mel_lengths, video_lengths=lens if mel_lengths is not None else None)
     wbuf = nm.train_pack_weights(vis.device)
-    dmel = nm.train_postnet_bwd(mel, g["mel_post"], post_tape, pdrop)
+    dmel = nm.train_postnet_bwd(mel, g["mel_post"], post_tape, pdrop, mel_lengths=mel_lengths)
     dmel += g["mel"].permute(0, 2, 1)
     sg = nm.train_steps_bwd(ctx, dmel, g["stop"], wbuf=wbuf)
     dvis = nm.train_prologue_bwd(vis, emb, state, ptape, sg, dcontent_dis=g["content_dis"], wbuf=wbuf, video_lengths=lens)
@@ -168,13 +197,14 @@ def decoder_forward_backward(nm: "native.NativeModel", vis, emb, gumbel, mel_tar
 
 
 def model_forward_backward(nm: "native.NativeModel", video, emb, gumbel, mel_target, gate_target, teacher_mask=None, bos=None, drop=None,
-                           on_decoder_grads=None, video_lengths=None):
+                           on_decoder_grads=None, video_lengths=None, mel_lengths=None):
     """`Lip2Speech.forward` + `Loss` + `backward()` (model.py:20-41, train.py:167-184) with the speaker embedding supplied and eval-mode
     statistics: encoder forward with a tape, `decoder_forward_backward`, then the encoder backward fed by the visual-feature gradient.
     All encoder and decoder parameter gradients land in the bound slots.  `video_lengths`: the clips are ZERO-padded to T and every stage that sees the
-    video takes its length-masked entry point (running statistics only)."""
+    video takes its length-masked entry point (running statistics only).  `mel_lengths`: see `decoder_forward_backward`."""
     vis, _, etape = nm.train_encoder_fwd(video, emb, video_lengths=video_lengths)
-    out = decoder_forward_backward(nm, vis, emb, gumbel, mel_target, gate_target, teacher_mask=teacher_mask, bos=bos, drop=drop, video_lengths=video_lengths)
+    out = decoder_forward_backward(nm, vis, emb, gumbel, mel_target, gate_target, teacher_mask=teacher_mask, bos=bos, drop=drop, video_lengths=video_lengths,
+                                   mel_lengths=mel_lengths)
     if on_decoder_grads is not None:
         on_decoder_grads()            # every decoder gradient is final: their all-reduce can travel under the encoder backward
     nm.train_encoder_bwd(video, out["dvis"], etape, video_lengths=video_lengths)
